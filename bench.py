@@ -6,16 +6,29 @@ phase 2 -> bins, plus the exchange of the posteriors to rank 0 when N > 1) over 
 batches that are already resident in HBM.  metric = genotyped variants/sec (whole job).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload genome24_h64|chr22_h64|...]
+                    [--dump-outputs DIR] [--full]
 
-One JSON line on rank 0:
+A plain run sets the main workload up, runs W warm-up steps and K timed steps, writes the outputs of the last
+timed step if --dump-outputs is given, and prints one JSON line on rank 0:
   value              resident rate of the main workload (inputs in HBM when the timed region starts)
+  ms_per_step        wall time of one timed step
+  kernel_ms          hipEvent time per kernel class of a timed step
+
+--dump-outputs DIR   after the timed steps: what the last step computed, as a caller receives it (pg_job_fetch_all),
+                     on a fixed, seeded sample of every chain's variants, as DIR/<name>.npy (float32 / float64)
+                     — see dump_outputs()
+
+--full adds every other measurement to the same line (each can be left out with its --no-* option):
   value_end_to_end   the same workload timed from host buffers to host results: H2D of every input +
                      run + D2H of every result, into the arena the job already holds
   roofline           dominant kernel of the main workload against the HBM peak
-  cohort             second measurement in the same line: many (sample x contig) chains against ONE
-                     shared index (pg_cohort_new) — the regime in which the sweep
-                     is HBM-bound; per-rank work fixed (weak scaling), with its own roofline
+  dropin_threads     the workload as concurrent one-shot calls from host threads (N = 1 only)
+  cohort             many (sample x contig) chains against ONE shared index (pg_cohort_new)
+                     — the regime in which the sweep is HBM-bound; per-rank work fixed (weak scaling), with its
+                     own roofline; the other panel widths in COHORTS_MORE, panels_h16 and cohort_strong
+  sampler, viterbi   the HaplotypeSampler and the Viterbi phasing path
   cpu_baseline       the CPU port of the reference on a bounded sample (N = 1 only)
+--cohort-only (profiling: one cohort measurement alone) is a --full run.
 
 N > 1 (launched by the driver with torch.distributed.run, one rank per GPU): the chains of the main
 workload are SHARDED over the ranks by longest-processing-time-first (pangenie_amd/dist.py), i.e.
@@ -94,6 +107,66 @@ CONTIG_MB = [248, 242, 198, 190, 181, 171, 159, 145, 138, 134, 135, 133, 114, 10
 def genome_contig_sizes(total_variants: int):
     tot = float(sum(CONTIG_MB))
     return [int(round(total_variants * mb / tot)) for mb in CONTIG_MB]
+
+
+def synthetic_panels(specs):
+    """synthetic_panel(V, H, K, seed=..., multiallelic_frac=...) for every (V, H, K, seed, multi) of `specs`: the very arrays
+    the calls give one after the other (every contig has a seed of its own), on up to 16 threads: the set-up of the main
+    workload is paid on every run of the bench, and numpy's bulk draws and array operations leave the GIL."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    def one(s):
+        return synthetic_panel(s[0], s[1], s[2], seed=s[3], multiallelic_frac=s[4])
+    with ThreadPoolExecutor(max(1, min(len(specs), 16))) as pool:
+        return list(pool.map(one, specs))
+
+
+DUMP_VARIANTS_PER_CHAIN = 16_384   # --dump-outputs: sampled variants per chain (all of a shorter chain)
+DUMP_SEED = 20_240_901
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, chain_ids, results, suffix=""):
+    """--dump-outputs: what the last timed step handed its caller (pg_job_fetch_all: a ContigResult per chain), on a fixed
+    sample of each chain's variants — drawn with a seed of the chain's own (DUMP_SEED + chain index), so the same variants
+    whatever the build or the number of ranks.  Per sampled variant (chain order, then variant order):
+      chain, variant        where it is                              (float64)
+      kept, unique_kmers, local_coverage                             (float32)
+    per genotype bin of a sampled variant:
+      posterior             likelihood normalised over the variant's bins in long double (GenotypingResult::normalize)
+      likelihood_mantissa, likelihood_exponent
+                            the unnormalised likelihood as the ABI returns it: mantissa in [0.5, 1) or 0, times
+                            2^exponent (float64; both finite, unlike a logarithm of a zero bin)
+    and n_columns, one per chain (float64).  `suffix` tells the ranks of a sharded run apart."""
+    from types import SimpleNamespace
+
+    from pangenie_amd.genotyping_result import normalized_bins
+    cols = {k: [] for k in ("chain", "variant", "kept", "unique_kmers", "local_coverage", "posterior", "likelihood_mantissa", "likelihood_exponent", "n_columns")}
+    for i, r in zip(chain_ids, results):
+        V = r.batch.n_variants
+        vs = np.arange(V) if V <= DUMP_VARIANTS_PER_CHAIN else \
+            np.sort(np.random.default_rng(DUMP_SEED + int(i)).choice(V, DUMP_VARIANTS_PER_CHAIN, replace=False))
+        goff = r.geno_off.astype(np.int64)
+        G = goff[vs + 1] - goff[vs]
+        starts = np.cumsum(G) - G
+        bins = np.repeat(goff[vs], G) + np.arange(int(G.sum())) - np.repeat(starts, G)
+        lik_ld = np.ldexp(r.lik[bins].astype(np.longdouble), r.lik_exp[bins].astype(np.int64))
+        cols["posterior"].append(normalized_bins(SimpleNamespace(geno_off=np.append(starts, G.sum())), lik_ld).astype(np.float64))
+        cols["likelihood_mantissa"].append(r.lik[bins].astype(np.float64))
+        cols["likelihood_exponent"].append(r.lik_exp[bins].astype(np.float64))
+        cols["chain"].append(np.full(len(vs), float(i)))
+        cols["variant"].append(vs.astype(np.float64))
+        cols["kept"].append(r.kept[vs].astype(np.float32))
+        cols["unique_kmers"].append(r.n_kmers[vs].astype(np.float32))
+        cols["local_coverage"].append(r.coverage[vs].astype(np.float32))
+        cols["n_columns"].append(np.array([float(r.n_columns)]))
+    arrays = {k: np.concatenate(v) if v else np.zeros(0) for k, v in cols.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), a)
 
 
 def cpu_baseline(batches, H, sample_variants):
@@ -177,8 +250,7 @@ BACKEND = "nccl"
 
 
 def _cuda_ok():
-    import torch
-    return torch.cuda.is_available()
+    return hmm._lib.load_hip().pg_hmm_device_count() > 0
 
 
 def _cuda_set(local_rank):
@@ -313,9 +385,14 @@ def main():
     ap.add_argument("--no-viterbi", action="store_true", help="skip the Viterbi phasing sub-measurement")
     ap.add_argument("--no-dropin", action="store_true", help="skip the threaded one-shot (drop-in) sub-measurement")
     ap.add_argument("--cohort-samples", type=int, default=COHORT["samples"])
+    ap.add_argument("--full", action="store_true", help="every measurement besides the main workload's steps (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.cohort_only and not args.full:
+        ap.error("--cohort-only is a --full measurement")
 
-    import torch
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -323,15 +400,21 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     if not _cuda_ok():
         raise SystemExit("bench.py needs a GPU (no CPU fallback)")
-    _cuda_set(local_rank)
+    # a plain one-GPU run needs no torch (pg_job_run returns synchronised): it is not imported there
+    use_torch = world > 1 or args.full
+    if use_torch:
+        import torch
+        _cuda_set(local_rank)
     dist = None
     if world > 1:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group(BACKEND, rank=rank, world_size=world)
-    dev = _make_device(local_rank)
+    dev = _make_device(local_rank) if use_torch else None
 
     def fence():
+        if not use_torch:
+            return
         _sync()
         if world > 1:
             dist.barrier()
@@ -366,7 +449,7 @@ def main():
             plan = [assign_chains([float(s) * H * H for s in sizes], int(w["share_of"]))[0]]
             V_total = sum(sizes[i] for i in plan[0])
         mine = plan[rank]
-        batches = [synthetic_panel(sizes[i], H, K, seed=12345 + 1000 * i, multiallelic_frac=w["multi"]) for i in mine]
+        batches = synthetic_panels([(sizes[i], H, K, 12345 + 1000 * i, w["multi"]) for i in mine])
         job = hmm.Job(batches, table, params, device=local_rank) if mine else None
         hs = job.host_seconds() if job else {"alloc_s": 0.0, "upload_s": 0.0}
         n_lik = [0] * n_chains
@@ -455,15 +538,19 @@ def main():
                 rows.append({"rank": r, "chains": int(vals[0]), "variants": int(vals[1]), "longest_chain": int(vals[2]),
                              "run_ms_per_step": vals[3], "gather_ms_per_step": vals[4]})
 
+        # the results of the last timed step, as its caller receives them (pg_job_fetch_all into host buffers)
+        results = [hmm.ContigResult(b) for b in batches] if job and (args.full or args.dump_outputs) else []
+        job_info = job_info_of(job) if job else None
+        if results:
+            job.fetch_all(results)
+        if args.dump_outputs and job:
+            dump_outputs(args.dump_outputs, mine, results, suffix=f".rank{rank}" if world > 1 else "")
+
         # end to end: host buffers -> H2D of every input -> run -> D2H of every result, into the resident arena and into
         # result buffers the host already holds (allocated — and touched — once, outside the timed region)
-        results = [hmm.ContigResult(b) for b in batches] if job else []
-        job_info = job_info_of(job) if job else None
-        if job:
-            job.fetch_all(results)
         e2e_rounds, dt_e2e = 2, 0.0
         hs2 = {"upload_s": 0.0, "run_s": 0.0, "fetch_s": 0.0}
-        for _ in range(e2e_rounds):
+        for _ in range(e2e_rounds if args.full else 0):
             fence()
             t0 = time.perf_counter()
             if job:
@@ -483,7 +570,7 @@ def main():
         # the drop-in as the reference drives it (src/commands.cpp:949-978): one one-shot call per contig, all at once
         # from worker threads, host buffers in, host buffers out; the library merges the calls into one device job
         dropin = None
-        if job and world == 1 and not args.no_dropin:
+        if args.full and job and world == 1 and not args.no_dropin:
             job.close()
             job = None
             into = results
@@ -511,12 +598,27 @@ def main():
                       "note": "steady state: device arenas come from the library's pool (first round excluded)"}
 
         if rank == 0:
-            roof, ncol, (mode, chunk_cols) = roofline_of(results, batches, kms, H, args.workload if (V == w["V"] and world == 1) else None, job_info,
-                                                         ms_per_step=dt / args.steps * 1e3)
+            mode, chunk_cols = job_info["mode"], job_info["chunk_cols"]
             out.update({
                 "value": V_total * args.steps / dt, "ms_per_step": dt / args.steps * 1e3,
                 # BASELINE configs[3] as written: the total work is fixed, the chains are sharded over the ranks (one GPU: nothing to scale)
                 "scaling": "strong" if world > 1 else "single",
+                "config": {"workload": f"{args.workload}: {w['cfg']}; {V_total} variants x {H} haplotypes x {K} k-mers/variant in {len(mine) if w.get('share_of') and world == 1 else n_chains} chain(s) "
+                                       f"(longest {max(sizes)}), seeds 12345+1000*chain; " +
+                                       (f"rank 0's share of the {w['share_of']}-GPU plan (LPT)" if w.get("share_of") and world == 1 else f"sharded over {world} GPU(s) by LPT"),
+                           "variants": V_total, "haplotypes": H, "kmers_per_variant": K, "chains": n_chains,
+                           "chains_on_rank0": len(mine), "workgroups_per_chain": 2,
+                           "parallelism": f"contig-sharded x{world}", "sweep_mode": "%s (chunk_cols=%d)" % (mode, chunk_cols),
+                           "gather": gather_kind},
+                "per_rank": rows, "index_pass_ms": job_info.get("index_ms"), "plan": job_info.get("plan"),
+                "kernel_ms": kms, "device_bytes": job_info["device_bytes"],
+                "alloc_s": hs["alloc_s"], "upload_s": hs["upload_s"],
+            })
+        if rank == 0 and args.full:
+            roof, ncol, _ = roofline_of(results, batches, kms, H, args.workload if (V == w["V"] and world == 1) else None, job_info,
+                                        ms_per_step=dt / args.steps * 1e3)
+            out["config"]["kept_columns_rank0"] = ncol
+            out.update({
                 # the call-inclusive rate SURVEY.md §8(d) names (host buffers in, host results out, H2D and D2H inside): `value` stays
                 # the resident rate the bench contract prescribes (inputs in HBM when the timed region starts)
                 "value_call_inclusive": V_total / dt_e2e,
@@ -524,16 +626,7 @@ def main():
                 "end_to_end": {"ms": dt_e2e * 1e3, "h2d_ms": hs2["upload_s"] * 1e3, "run_ms": hs2["run_s"] * 1e3, "d2h_ms": hs2["fetch_s"] * 1e3,
                                "h2d_bytes": sum(job_info["upload_bytes"].values()),
                                "note": "rank 0's share; arena resident (device allocation at job creation: alloc_s)"},
-                "config": {"workload": f"{args.workload}: {w['cfg']}; {V_total} variants x {H} haplotypes x {K} k-mers/variant in {len(mine) if w.get('share_of') and world == 1 else n_chains} chain(s) "
-                                       f"(longest {max(sizes)}), seeds 12345+1000*chain; " +
-                                       (f"rank 0's share of the {w['share_of']}-GPU plan (LPT)" if w.get("share_of") and world == 1 else f"sharded over {world} GPU(s) by LPT"),
-                           "variants": V_total, "haplotypes": H, "kmers_per_variant": K, "chains": n_chains,
-                           "chains_on_rank0": len(mine), "kept_columns_rank0": ncol, "workgroups_per_chain": 2,
-                           "parallelism": f"contig-sharded x{world}", "sweep_mode": "%s (chunk_cols=%d)" % (mode, chunk_cols),
-                           "gather": gather_kind},
-                "per_rank": rows, "index_pass_ms": job_info.get("index_ms"), "plan": job_info.get("plan"),
-                "roofline": roof, "kernel_ms": kms, "device_bytes": job_info["device_bytes"],
-                "alloc_s": hs["alloc_s"], "upload_s": hs["upload_s"],
+                "roofline": roof,
             })
             if dropin:
                 out["dropin_threads"] = dropin
@@ -784,7 +877,7 @@ def main():
         _release_cache()
         return res
 
-    if not args.no_cohort:
+    if args.full and not args.no_cohort:
         if args.cohort_only and args.cohort_key == "panels_h16":
             r = panel_job_measure(PANEL_JOB)
             if rank == 0:
@@ -830,7 +923,7 @@ def main():
                     out["cohort_strong"] = r
 
     # ------------------------------------------------------------------ HaplotypeSampler sub-measurement
-    if not args.no_sampler and not args.cohort_only:
+    if args.full and not args.no_sampler and not args.cohort_only:
         from pangenie_amd import sampler as smp
         sp = SAMPLER
         panels = [synthetic_panel(sp["V"], sp["H"], 20, seed=4242 + 100 * rank + i, multiallelic_frac=0.2) for i in range(sp["contigs"])]
@@ -867,7 +960,7 @@ def main():
             out["sampler"] = sres
 
     # ------------------------------------------------------------------ Viterbi phasing sub-measurement (run_phasing)
-    if not args.no_viterbi and not args.cohort_only:
+    if args.full and not args.no_viterbi and not args.cohort_only:
         vp = VITERBI
         vpanels = [synthetic_panel(vp["V"], vp["H"], 20, seed=777 + 100 * rank + i) for i in range(vp["contigs"])]
         vprm = hmm.make_params(1.26, False, 1e-5, run_genotyping=False, run_phasing=True)

@@ -152,7 +152,7 @@ def main():
     bench.COHORTS_MORE["cohort_h16m"].update(samples=5, contigs=2, V=150, distinct=3)
     bench.PANEL_JOB.update(chains=8, distinct=2, V=100)
     sys.argv = ["bench.py", "--gpus", os.environ["WORLD_SIZE"], "--steps", "2", "--warmup", "1", "--workload", "genome24_small",
-                "--no-sampler", "--no-viterbi", "--no-cpu-baseline", "--cohort-samples", "3"]
+                "--no-sampler", "--no-viterbi", "--no-cpu-baseline", "--cohort-samples", "3", "--full"]
     bench.main()
     if os.environ.get("PG_MOCK_GATHER", "abi") == "abi":
         assert MockGather.calls > 0

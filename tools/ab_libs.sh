@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R
 O=gpurun_out/ab_$K; mkdir -p $O
 for v in "$@"; do
   if [ "$v" = default ]; then unset PANGENIE_HMM_LIB; else export PANGENIE_HMM_LIB=$R/tools/_build/libpangenie_hmm_$v.so; fi
-  python bench.py --steps 3 --warmup 1 --cohort-only --cohort-key $K --no-cpu-baseline --no-sampler > $O/l_$v.log 2>/dev/null
+  python bench.py --full --steps 3 --warmup 1 --cohort-only --cohort-key $K --no-cpu-baseline --no-sampler > $O/l_$v.log 2>/dev/null
   grep '^{' $O/l_$v.log | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); r = d['$K']

@@ -6,7 +6,7 @@
 K=$1; M=$2; shift 2
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R
 O=gpurun_out/ab_$K; mkdir -p $O
-CK="--cohort-only --no-cpu-baseline --no-sampler"; [ "$K" != cohort ] && CK="$CK --cohort-key $K"
+CK="--full --cohort-only --no-cpu-baseline --no-sampler"; [ "$K" != cohort ] && CK="$CK --cohort-key $K"
 line() { grep '^{' $1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(round(d['value']/1e6,2), 'M variants/s', round(d['ms_per_step'],2), 'ms, phase 2', round(r['phase2_ms'],2), 'ms')"; }
 case $M in
   trace)

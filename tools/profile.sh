@@ -22,11 +22,11 @@ cd $R
 #  the per-kernel AVERAGES of a profile would then mix whole and partial launches; profiled runs take the sequential path)
 export PG_NO_PIPELINE=1
 case $W in
-  cohort_h64) CMD="python bench.py --steps 3 --warmup 1 --cohort-only --no-cpu-baseline --no-sampler" ;;
-  cohort_*|panels_h16)   CMD="python bench.py --steps 3 --warmup 1 --cohort-only --cohort-key $W --no-cpu-baseline --no-sampler" ;;
+  cohort_h64) CMD="python bench.py --full --steps 3 --warmup 1 --cohort-only --no-cpu-baseline --no-sampler" ;;
+  cohort_*|panels_h16)   CMD="python bench.py --full --steps 3 --warmup 1 --cohort-only --cohort-key $W --no-cpu-baseline --no-sampler" ;;
   sampler)    CMD="python tools/bench_sampler.py --variants 40000 --paths 215 --size 15 --contigs 8 --cpu-variants 2000" ;;
   viterbi)    CMD="python tools/bench_viterbi.py" ;;
-  *)          CMD="python bench.py --steps 3 --warmup 1 --workload $W --no-cpu-baseline --no-cohort --no-sampler --no-viterbi --no-dropin" ;;
+  *)          CMD="python bench.py --full --steps 3 --warmup 1 --workload $W --no-cpu-baseline --no-cohort --no-sampler --no-viterbi --no-dropin" ;;
 esac
 pass() { local name=$1; shift; timeout 900 rocprofv3 "$@" -d $OUT/$name -o ${name%%_*} --output-format csv -- $CMD > $OUT/$name.log 2>&1; }
 timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- $CMD > $OUT/kt.log 2>&1

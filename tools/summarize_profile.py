@@ -15,7 +15,7 @@ src, prefix, workload = Path(sys.argv[1]), sys.argv[2], sys.argv[3]
 out = {"workload": workload, "kernels": {}, "notes": "rocprofv3 --kernel-trace --stats; --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes; "
        "FETCH_SIZE doubled (gfx950 wide-read correction), KiB -> bytes"}
 stats = list(csv.DictReader(open(src / "kt" / "kt_kernel_stats.csv")))
-lines = ["rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline   (workload %s)" % workload,
+lines = ["rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline   (workload %s)" % workload,
          "%-58s %6s %14s %12s" % ("kernel", "calls", "avg_ns", "percent")]
 for r in stats:
     lines.append("%-58s %6s %14.0f %12s" % (r["Name"][:58], r["Calls"], float(r["AverageNs"]), r["Percentage"]))

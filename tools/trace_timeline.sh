@@ -4,7 +4,7 @@
 W=${1:-genome24_h64}; TAG=${2:-r05}
 R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out/${TAG}_trace_$W; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp; cd $R
-timeout 600 rocprofv3 --kernel-trace -d $OUT/kt -o kt --output-format csv -- python bench.py --steps 1 --warmup 1 --workload $W --no-cpu-baseline --no-cohort --no-sampler --no-viterbi --no-dropin > $OUT/kt.log 2>&1
+timeout 600 rocprofv3 --kernel-trace -d $OUT/kt -o kt --output-format csv -- python bench.py --full --steps 1 --warmup 1 --workload $W --no-cpu-baseline --no-cohort --no-sampler --no-viterbi --no-dropin > $OUT/kt.log 2>&1
 python - <<PY
 import csv, glob
 f = glob.glob("$OUT/kt/*kernel_trace.csv")[0]
