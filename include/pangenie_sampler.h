@@ -8,9 +8,11 @@
  *
  * Input = the same flat batch as the genotyping path (include/pangenie_hmm.h: pg_contig_batch) over
  * ALL paths of the panel (n_paths = UniqueKmers::get_nr_paths()).  Everything is integer work: results
- * (sampled path ids, best scores) are bit-exact with the reference.  Emission and transition costs
- * are formed on the host exactly as the reference forms them (float / long double, then truncation);
- * the passes themselves — column minima, DP update, backtrace, penalties — run on the GPU.
+ * (sampled path ids, best scores) are bit-exact with the reference.  Transition costs are formed on the
+ * host exactly as the reference forms them (long double, then truncation); emission costs on the host by
+ * pg_sampler_run[_batch] / pg_sampler_then_job and on the device by pg_sampler_cohort_new, from one table
+ * of the same float expression (exact: an allele has at most 32 k-mers); the passes themselves — column
+ * minima, DP update, backtrace, penalties — run on the GPU.
  */
 #ifndef PANGENIE_SAMPLER_H
 #define PANGENIE_SAMPLER_H
@@ -63,7 +65,37 @@ int pg_sampler_then_job(const pg_contig_batch* panels, uint32_t n_contigs, uint3
                         const pg_table* table, const pg_hmm_params* params, int device,
                         uint32_t* const* sampled_paths, uint32_t* const* best_scores,
                         pg_job** out_job, char* err, size_t errlen);
-/* Kernel milliseconds of the last pg_sampler_run[_batch] of the calling thread, summed over the passes:
+/* Sampled cohort: pg_sampler_then_job for n_samples samples over ONE index (the reference's per-sample sequence
+ * fill_read_kmercounts -> HaplotypeSampler -> HMM on large panels, src/commands.cpp:118-152, run for a whole cohort).
+ * Chain s * n_contigs + c of *out_job (the numbering of pg_cohort_new) is, bit for bit in every output — sampled paths, best
+ * scores, the reduced panel (pg_job_fetch_panel), lik / lik_exp / kept / n_kmers / coverage / n_columns and, with
+ * params->run_phasing, haplotype_1 / haplotype_2 — what pg_sampler_then_job gives for index[c] with
+ * kmer_count = samples[s].kmer_count[c] and coverage = samples[s].coverage[c].  index[c].kmer_count / .coverage are ignored.
+ * The index arrays cross PCIe once and the transition costs and slot tables are formed once per contig, shared by every
+ * sample; per sample only the k-mer counts are uploaded (the coverage goes to the job), and its emission costs are formed
+ * on the device.  sampled_paths[s * n_contigs + c] ([size * V_c]) / best_scores[...] ([size]): the array or single entries
+ * may be NULL.  Errors: PG_ERR_INVALID for a null argument, n_samples == 0, a sample whose arrays are NULL for a contig with
+ * k-mers (coverage: with variants), size < 1 or size >= n_paths; PG_ERR_UNSUPPORTED for the limits of pg_sampler_then_job
+ * and more than 65535 chains with variants; PG_ERR_NOMEM when the batch does not fit the device — the message states the
+ * bytes needed and the caller splits the samples (the call never splits them itself). */
+int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_contig_batch* index,
+                          uint32_t n_samples, const pg_sample_counts* samples,
+                          uint32_t size, int add_reference,
+                          double sampling_recombrate, long double sampling_effective_N, uint16_t allele_penalty,
+                          const pg_table* table, const pg_hmm_params* params,
+                          uint32_t* const* sampled_paths,   /* [n_samples*n_contigs] -> [size*V_c], or NULL */
+                          uint32_t* const* best_scores,     /* [n_samples*n_contigs] -> [size],     or NULL */
+                          pg_job** out_job, char* err, size_t errlen);
+/* H2D bytes of the last pg_sampler_cohort_new / pg_sampler_then_job of this thread: [0] index arrays, [1] per-sample
+ * arrays (cohort: the k-mer counts alone, 2 * sumK per sample and contig; pg_sampler_then_job: the counts and the emission
+ * costs the host formed from them).  Pointer tables and the reduced panel's offsets are not counted; neither is what
+ * pg_job_new uploads itself (the coverage). */
+int pg_sampler_last_h2d_bytes(uint64_t out2[2]);
+/* Wall / kernel milliseconds of the last pg_sampler_cohort_new of this thread: [0] host preparation (checks, transition
+ * costs, plan), [1] H2D uploads, [2] emission cost kernel (hipEvents), [3] slot tables and their per-chain copies
+ * (hipEvents), [4] the passes incl. the read-back of sampled paths, [5] the panel reduction, [6] pg_job_new, [7] the call. */
+int pg_sampler_last_phase_ms(double out8[8]);
+/* Kernel milliseconds of the last pg_sampler_run[_batch] / pg_sampler_cohort_new of the calling thread, summed over the passes:
  * [0] cost expansion, [1] forward passes, [2] backtraces; *kernel (may be NULL) = waves per workgroup of
  * the relative-value kernel, 0 when the general (saturating) kernel ran. */
 int pg_sampler_last_ms(double out3[3], int* kernel);

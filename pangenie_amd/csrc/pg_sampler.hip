@@ -27,7 +27,9 @@
 //                     SamplingEmissions::penalize to the alleles on it
 // General path (saturating arithmetic, any cost range, H up to 65534; PG_SAMPLER_KERNEL=general forces
 // it): ks_forward / ks_backtrack with u64 keys and u16 backtrace ids.
-// Costs are formed on the HOST exactly as the reference forms them (float / long double + truncation).
+// Costs are formed exactly as the reference forms them (float / long double + truncation): transition costs on the host;
+// emission costs on the host for pg_sampler_run[_batch] / pg_sampler_then_job, and on the device for sampled cohorts
+// (pg_sampler_cohort_new: ks_ecost, from a 33 x 33 table the host fills with the same expression, emission_cost_of).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdarg.h>
@@ -36,6 +38,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <chrono>
+#include <memory>
 #include <vector>
 
 #include "../../include/pangenie_sampler.h"
@@ -499,6 +503,52 @@ __global__ __launch_bounds__(64) void ks_backtrack_fast(const SamplerDev* devs, 
     assign(0u, 0u, b);
 }
 
+// ------------------------------------------------------------------------------------------------
+//  sampled cohorts (pg_sampler_cohort_new): the sample-level work in front of the passes
+// ------------------------------------------------------------------------------------------------
+// per chain (sample x contig): the index arrays of its contig (shared by every sample's chain over it), the sample's own
+// k-mer counts, the chain's emission costs, and the slot table copy of the fast path
+struct CostDev {
+    uint32_t V, pad;
+    const uint32_t* allele_off; const uint32_t* kmer_off; const uint8_t* allele_flags;
+    const uint16_t* allele_koff; const uint32_t* allele_kmask;   // index
+    const uint16_t* kmer_count;                                  // [sumK] the sample's
+    uint16_t* ecost;                                             // [sumA] the chain's
+    const uint8_t* slot_src;                                     // [V*P, padded to 16] the contig's slot table (fast path)
+    uint8_t* slot_dst;                                           // the chain's own copy (ks_apply masks picked cells in it)
+    uint64_t slot_bytes;                                         // multiple of 16
+};
+
+// SamplingEmissions ctor (src/samplingemissions.cpp:9-37) of every allele slot of every chain on the device: grid = (blocks,
+// chains), one thread per variant.  present = the k-mers k = off + b (b < 32, k < K, mask bit b) with a read count >= 3 —
+// exactly what pg_sampler_emission_costs counts through on_slot —, total = popcount(mask) <= 32, and the cost is the host's
+// table entry cost33[total * 33 + present] (emission_cost_of): exact by construction.  50 for an undefined allele.
+__global__ __launch_bounds__(256) void ks_ecost(const CostDev* cds, const uint16_t* cost33) {
+    const CostDev d = cds[blockIdx.y];
+    for (uint32_t v = blockIdx.x * 256u + threadIdx.x; v < d.V; v += gridDim.x * 256u) {
+        const uint32_t k0 = d.kmer_off[v], K = d.kmer_off[v + 1] - k0, a1 = d.allele_off[v + 1];
+        for (uint32_t a = d.allele_off[v]; a < a1; ++a) {
+            if (d.allele_flags[a] & 1u) { d.ecost[a] = 50; continue; }
+            const uint32_t off = d.allele_koff[a], mask = d.allele_kmask[a];
+            uint32_t present = 0;
+            for (uint32_t m = mask; m != 0u; m &= m - 1u) {
+                const uint32_t k = off + (uint32_t)__builtin_ctz(m);
+                present += (k < K && d.kmer_count[k0 + k] >= 3u) ? 1u : 0u;
+            }
+            d.ecost[a] = cost33[(uint32_t)__popc(mask) * 33u + present];
+        }
+    }
+}
+
+// every chain's own copy of its contig's slot table (built once by ks_slots): grid = (blocks, chains), 16 bytes per thread
+__global__ __launch_bounds__(256) void ks_slot_copy(const CostDev* cds) {
+    const CostDev d = cds[blockIdx.y];
+    const uint4* src = (const uint4*)d.slot_src;
+    uint4* dst = (uint4*)d.slot_dst;
+    const size_t n = d.slot_bytes / 16u;
+    for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (size_t)gridDim.x * 256) dst[g] = src[g];
+}
+
 __global__ void ks_minima(const uint32_t* column, const uint8_t* mask, uint32_t n, uint32_t* out4) {
     __shared__ unsigned long long s_k1[4], s_k2[4];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -526,12 +576,24 @@ __global__ void ks_minima(const uint32_t* column, const uint8_t* mask, uint32_t 
 }
 
 thread_local double g_last_ms[3] = {0.0, 0.0, 0.0};
+thread_local uint64_t g_last_h2d[2] = {0, 0};   // pg_sampler_last_h2d_bytes
+thread_local double g_last_phase_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // pg_sampler_last_phase_ms
 thread_local int g_last_kernel = 0;
 
 unsigned on_slot(const pg_contig_batch* b, uint32_t slot, uint32_t k) {
     const uint32_t off = b->allele_kmer_off[slot];
     if (k < off || k >= off + 32u) return 0;
     return (b->allele_kmer_mask[slot] >> (k - off)) & 1u;
+}
+
+// SamplingEmissions' cost of a defined allele from (its k-mers with a read count >= 3, all its k-mers)
+// (src/samplingemissions.cpp:22-33): the ONE expression behind pg_sampler_emission_costs and the 33 x 33 table the device
+// reads (ks_ecost), so that the two cannot drift apart
+uint16_t emission_cost_of(unsigned present, unsigned total) {
+    const float fraction = total > 0 ? present / (float)total : 1.0f;
+    // the reference's `log10(fraction)` is the FLOAT overload (<cmath>, using namespace std): log10f
+    if (fraction > 0.0) return (unsigned short)(-10.0 * log10f(fraction));
+    return 25;
 }
 
 int check_panel(const pg_contig_batch* b, uint32_t size, char* err, size_t errlen) {
@@ -562,10 +624,7 @@ extern "C" int pg_sampler_emission_costs(const pg_contig_batch* b, uint16_t* cos
             unsigned short total = (unsigned short)__builtin_popcount(b->allele_kmer_mask[s]), present = 0;
             for (uint32_t k = 0; k < K; ++k)
                 if (b->kmer_count[k0 + k] >= 3 && on_slot(b, s, k)) present += 1;
-            const float fraction = total > 0 ? present / (float)total : 1.0f;
-            // the reference's `log10(fraction)` is the FLOAT overload (<cmath>, using namespace std): log10f
-            if (fraction > 0.0) cost[s] = (unsigned short)(-10.0 * log10f(fraction));
-            else cost[s] = 25;
+            cost[s] = emission_cost_of(present, total);
         }
     }
     return PG_OK;
@@ -636,119 +695,39 @@ extern "C" int pg_sampler_run_batch(const pg_contig_batch* panels, uint32_t n_co
 }
 
 namespace {
-int sampler_run_core(const pg_contig_batch* panels, uint32_t n_contigs, uint32_t size, double recombrate,
-                     long double effective_N, uint16_t allele_penalty, int device, uint32_t* const* sampled_paths,
-                     uint32_t* const* best_scores, SamplerKeep* keep, char* err, size_t errlen) {
-    if (size < 1 || n_contigs == 0) return PG_OK;  // reference src/haplotypesampler.cpp:28
-    // contigs without variants have nothing to sample
-    std::vector<uint32_t> live;
-    for (uint32_t g = 0; g < n_contigs; ++g) {
-        if (panels[g].n_variants == 0) continue;
-        if (!keep && !sampled_paths[g]) { set_err(err, errlen, "null output for contig %u", g); return PG_ERR_INVALID; }
-        const int rc0 = check_panel(&panels[g], size, err, errlen);
-        if (rc0 != PG_OK) return rc0;
-        live.push_back(g);
+// transition costs of one contig into tcost[V] (index level: they depend on the positions, n_paths and the two sampling
+// parameters only); false when the contig lies outside the bounds under which the relative-value kernel is exact: every
+// recombination cost in 1..KS_TMAX (with two or more paths the reference's formula gives >= 3; the largest real ones are a
+// few hundred), 50 (V + 1) + the largest cost fits 32 bits (no saturation anywhere), <= 4096 paths, <= 254 alleles per column
+bool contig_tcost(const pg_contig_batch* b, double recombrate, long double effective_N, std::vector<uint32_t>& tcost) {
+    const uint32_t V = b->n_variants, P = b->n_paths;
+    tcost.assign(V, 0);
+    uint32_t tmax = 0, tmin = 1;
+    for (uint32_t c = 1; c < V; ++c) {
+        tcost[c] = pg_sampler_transition_cost(b->variant_pos[c - 1], b->variant_pos[c], recombrate, P, effective_N);
+        if (tcost[c] > tmax) tmax = tcost[c];
+        if (tcost[c] < tmin) tmin = tcost[c];
     }
-    if (live.empty()) return PG_OK;
-    int ndev = 0, rc = PG_OK;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_err(err, errlen, "no HIP device available (no CPU fallback)"); return PG_ERR_DEVICE; }
-    if (device < 0 || device >= ndev) { set_err(err, errlen, "bad device %d", device); return PG_ERR_INVALID; }
-    const uint32_t n = (uint32_t)live.size();
-    // host-side costs, and the bounds under which the relative-value kernel is exact: every recombination
-    // cost in 1..KS_TMAX (with two or more paths the reference's formula gives >= 3; the largest real ones are
-    // a few hundred), 50 (V + 1) + the largest cost fits 32 bits (no saturation anywhere), <= 4096 paths,
-    // <= 254 alleles per column
-    std::vector<std::vector<uint16_t>> ecost(n);
-    std::vector<std::vector<uint32_t>> tcost(n);
-    uint32_t maxP = 0, maxV = 0;
-    bool fast = true;
-    for (uint32_t j = 0; j < n; ++j) {
-        const pg_contig_batch* b = &panels[live[j]];
-        const uint32_t V = b->n_variants, P = b->n_paths;
-        ecost[j].resize(b->allele_off[V]);
-        pg_sampler_emission_costs(b, ecost[j].data());
-        tcost[j].assign(V, 0);
-        uint32_t tmax = 0, tmin = 1;
-        for (uint32_t c = 1; c < V; ++c) {
-            tcost[j][c] = pg_sampler_transition_cost(b->variant_pos[c - 1], b->variant_pos[c], recombrate, P, effective_N);
-            if (tcost[j][c] > tmax) tmax = tcost[j][c];
-            if (tcost[j][c] < tmin) tmin = tcost[j][c];
-        }
-        uint32_t maxA = 0;
-        for (uint32_t v = 0; v < V; ++v) if (b->allele_off[v + 1] - b->allele_off[v] > maxA) maxA = b->allele_off[v + 1] - b->allele_off[v];
-        if (tmin < 1u || tmax > KS_TMAX || 50.0 * ((double)V + 1.0) + tmax >= 4294967295.0 || P > 4096u || maxA > 254u) fast = false;
-        if (P > maxP) maxP = P;
-        if (V > maxV) maxV = V;
-    }
-    if (const char* e = getenv("PG_SAMPLER_KERNEL")) {
-        if (!strcmp(e, "general")) fast = false;
-        else if (!strcmp(e, "fast") && !fast) { set_err(err, errlen, "PG_SAMPLER_KERNEL=fast: the panel is outside the fast kernel's bounds"); return PG_ERR_UNSUPPORTED; }
-    }
-    uint32_t NW = 1;
-    while (NW * 256u < maxP) NW *= 2;  // 4 paths per lane
-    const uint32_t T = NW * 64u;
+    uint32_t maxA = 0;
+    for (uint32_t v = 0; v < V; ++v) if (b->allele_off[v + 1] - b->allele_off[v] > maxA) maxA = b->allele_off[v + 1] - b->allele_off[v];
+    return !(tmin < 1u || tmax > KS_TMAX || 50.0 * ((double)V + 1.0) + tmax >= 4294967295.0 || P > 4096u || maxA > 254u);
+}
 
-    std::vector<SamplerDev> devs(n);
-    unsigned char* arena = nullptr;
+// The `size` passes over n contigs (chains) whose SamplerDevs are on the device at dd; ks_slots builds the slot tables in
+// front of the first pass when build_slots (else they are in place already).  ms += the kernel milliseconds.
+int run_passes(const SamplerDev* dd, uint32_t n, bool fast, bool build_slots, uint32_t NW, uint32_t maxP, uint32_t size, double ms[3],
+               char* err, size_t errlen) {
+    int rc = PG_OK;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { off = (off + 255) / 256 * 256; size_t o = off; off += bytes ? bytes : 8; return o; };
-    struct Offs { size_t aoff, aid, pa, tc, ec, paths, best, bt, last_col, ecell, stay, minima, last, slot; };
-    std::vector<Offs> offs(n);
-    for (uint32_t j = 0; j < n; ++j) {
-        const pg_contig_batch* b = &panels[live[j]];
-        const size_t V = b->n_variants, P = b->n_paths, sumA = b->allele_off[V];
-        Offs& o = offs[j];
-        o.aoff = take((V + 1) * 4); o.aid = take(sumA * 2); o.pa = take(V * P * 2); o.tc = take((V + 48) * 4); o.ec = take(sumA * 2);
-        o.paths = take((size_t)size * V * 4); o.best = take((size_t)size * 4);
-        if (fast) { o.slot = take(V * P); o.ecell = take((V + 32) * T * 8); o.stay = take(((V + 14) / 16 + 1) * 2 * T * 4); o.minima = take(V * 4); o.last = take(4); o.bt = o.last_col = 0; }
-        else { o.bt = take(V * P * 2); o.last_col = take(P * 4); o.ecell = o.stay = o.minima = o.last = o.slot = 0; }
-    }
-    const size_t o_devs = take(sizeof(SamplerDev) * n);
-    double ms[3] = {0.0, 0.0, 0.0};
-    HIP_TRY(hipSetDevice(device));
-    {
-        hipError_t he = hipMalloc((void**)&arena, off);
-        if (he != hipSuccess) {   // cached arenas of the one-shot call may be what stands in the way
-            pg_hmm_release_cache();
-            hipSetDevice(device);
-            he = hipMalloc((void**)&arena, off);
-        }
-        if (he != hipSuccess) { set_err(err, errlen, "hipMalloc(%zu bytes) failed: %s", off, hipGetErrorString(he)); rc = PG_ERR_NOMEM; goto done; }
-    }
     for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-    for (uint32_t j = 0; j < n; ++j) {
-        const pg_contig_batch* b = &panels[live[j]];
-        const size_t V = b->n_variants, P = b->n_paths, sumA = b->allele_off[V];
-        const Offs& o = offs[j];
-        SamplerDev& d = devs[j];
-        memset(&d, 0, sizeof(d));
-        d.V = (uint32_t)V; d.P = (uint32_t)P; d.T = T; d.penalty = allele_penalty;
-        d.allele_off = (const uint32_t*)(arena + o.aoff); d.allele_id = (const uint16_t*)(arena + o.aid);
-        d.path_allele = (const uint16_t*)(arena + o.pa); d.tcost = (const uint32_t*)(arena + o.tc);
-        d.ecost = (uint16_t*)(arena + o.ec); d.paths = (uint32_t*)(arena + o.paths); d.best = (uint32_t*)(arena + o.best);
-        if (fast) {
-            d.slot = (uint8_t*)(arena + o.slot); d.ecell = (unsigned long long*)(arena + o.ecell); d.stay = (uint32_t*)(arena + o.stay);
-            d.minima = (uint32_t*)(arena + o.minima); d.last = (uint32_t*)(arena + o.last);
-        } else {
-            d.bt = (uint16_t*)(arena + o.bt); d.last_col = (uint32_t*)(arena + o.last_col);
-        }
-        HIP_TRY(hipMemcpy(arena + o.aoff, b->allele_off, (V + 1) * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(arena + o.aid, b->allele_id, sumA * 2, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(arena + o.pa, b->path_allele, V * P * 2, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(arena + o.tc, tcost[j].data(), V * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(arena + o.ec, ecost[j].data(), sumA * 2, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemcpy(arena + o_devs, devs.data(), sizeof(SamplerDev) * n, hipMemcpyHostToDevice));
     {
-        const SamplerDev* dd = (const SamplerDev*)(arena + o_devs);
         // general path: backtrack blocks through LDS when KS_BT_BLOCK columns of u16 ids fit into 64 KB
         const uint32_t lds_cols = ((size_t)KS_BT_BLOCK * maxP * 2 <= 64u * 1024u) ? KS_BT_BLOCK : 0u;
         const size_t lds_bytes = (size_t)lds_cols * maxP * 2;
         const uint32_t ex_blocks = 2048u;
         for (uint32_t pass = 0; pass < size; ++pass) {
             HIP_TRY(hipEventRecord(ev[0], nullptr));
-            if (fast && pass == 0) hipLaunchKernelGGL(ks_slots, dim3(ex_blocks, n), dim3(256), 0, nullptr, dd);
+            if (fast && build_slots && pass == 0) hipLaunchKernelGGL(ks_slots, dim3(ex_blocks, n), dim3(256), 0, nullptr, dd);
             if (fast) hipLaunchKernelGGL(ks_expand, dim3(ex_blocks, n), dim3(256), 0, nullptr, dd);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(ev[1], nullptr));
@@ -783,6 +762,103 @@ int sampler_run_core(const pg_contig_batch* panels, uint32_t n_contigs, uint32_t
             ms[0] += a; ms[1] += f; ms[2] += k;
         }
     }
+done:
+    for (auto& e : ev) if (e) hipEventDestroy(e);
+    return rc;
+}
+
+int sampler_run_core(const pg_contig_batch* panels, uint32_t n_contigs, uint32_t size, double recombrate,
+                     long double effective_N, uint16_t allele_penalty, int device, uint32_t* const* sampled_paths,
+                     uint32_t* const* best_scores, SamplerKeep* keep, char* err, size_t errlen) {
+    if (size < 1 || n_contigs == 0) return PG_OK;  // reference src/haplotypesampler.cpp:28
+    // contigs without variants have nothing to sample
+    std::vector<uint32_t> live;
+    for (uint32_t g = 0; g < n_contigs; ++g) {
+        if (panels[g].n_variants == 0) continue;
+        if (!keep && !sampled_paths[g]) { set_err(err, errlen, "null output for contig %u", g); return PG_ERR_INVALID; }
+        const int rc0 = check_panel(&panels[g], size, err, errlen);
+        if (rc0 != PG_OK) return rc0;
+        live.push_back(g);
+    }
+    if (live.empty()) return PG_OK;
+    int ndev = 0, rc = PG_OK;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_err(err, errlen, "no HIP device available (no CPU fallback)"); return PG_ERR_DEVICE; }
+    if (device < 0 || device >= ndev) { set_err(err, errlen, "bad device %d", device); return PG_ERR_INVALID; }
+    const uint32_t n = (uint32_t)live.size();
+    // host-side costs, and the bounds under which the relative-value kernel is exact (contig_tcost)
+    std::vector<std::vector<uint16_t>> ecost(n);
+    std::vector<std::vector<uint32_t>> tcost(n);
+    uint32_t maxP = 0, maxV = 0;
+    bool fast = true;
+    for (uint32_t j = 0; j < n; ++j) {
+        const pg_contig_batch* b = &panels[live[j]];
+        const uint32_t V = b->n_variants, P = b->n_paths;
+        ecost[j].resize(b->allele_off[V]);
+        pg_sampler_emission_costs(b, ecost[j].data());
+        if (!contig_tcost(b, recombrate, effective_N, tcost[j])) fast = false;
+        if (P > maxP) maxP = P;
+        if (V > maxV) maxV = V;
+    }
+    if (const char* e = getenv("PG_SAMPLER_KERNEL")) {
+        if (!strcmp(e, "general")) fast = false;
+        else if (!strcmp(e, "fast") && !fast) { set_err(err, errlen, "PG_SAMPLER_KERNEL=fast: the panel is outside the fast kernel's bounds"); return PG_ERR_UNSUPPORTED; }
+    }
+    uint32_t NW = 1;
+    while (NW * 256u < maxP) NW *= 2;  // 4 paths per lane
+    const uint32_t T = NW * 64u;
+
+    std::vector<SamplerDev> devs(n);
+    unsigned char* arena = nullptr;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { off = (off + 255) / 256 * 256; size_t o = off; off += bytes ? bytes : 8; return o; };
+    struct Offs { size_t aoff, aid, pa, tc, ec, paths, best, bt, last_col, ecell, stay, minima, last, slot; };
+    std::vector<Offs> offs(n);
+    for (uint32_t j = 0; j < n; ++j) {
+        const pg_contig_batch* b = &panels[live[j]];
+        const size_t V = b->n_variants, P = b->n_paths, sumA = b->allele_off[V];
+        Offs& o = offs[j];
+        o.aoff = take((V + 1) * 4); o.aid = take(sumA * 2); o.pa = take(V * P * 2); o.tc = take((V + 48) * 4); o.ec = take(sumA * 2);
+        o.paths = take((size_t)size * V * 4); o.best = take((size_t)size * 4);
+        if (fast) { o.slot = take(V * P); o.ecell = take((V + 32) * T * 8); o.stay = take(((V + 14) / 16 + 1) * 2 * T * 4); o.minima = take(V * 4); o.last = take(4); o.bt = o.last_col = 0; }
+        else { o.bt = take(V * P * 2); o.last_col = take(P * 4); o.ecell = o.stay = o.minima = o.last = o.slot = 0; }
+    }
+    const size_t o_devs = take(sizeof(SamplerDev) * n);
+    double ms[3] = {0.0, 0.0, 0.0};
+    HIP_TRY(hipSetDevice(device));
+    {
+        hipError_t he = hipMalloc((void**)&arena, off);
+        if (he != hipSuccess) {   // cached arenas of the one-shot call may be what stands in the way
+            pg_hmm_release_cache();
+            hipSetDevice(device);
+            he = hipMalloc((void**)&arena, off);
+        }
+        if (he != hipSuccess) { set_err(err, errlen, "hipMalloc(%zu bytes) failed: %s", off, hipGetErrorString(he)); rc = PG_ERR_NOMEM; goto done; }
+    }
+    for (uint32_t j = 0; j < n; ++j) {
+        const pg_contig_batch* b = &panels[live[j]];
+        const size_t V = b->n_variants, P = b->n_paths, sumA = b->allele_off[V];
+        const Offs& o = offs[j];
+        SamplerDev& d = devs[j];
+        memset(&d, 0, sizeof(d));
+        d.V = (uint32_t)V; d.P = (uint32_t)P; d.T = T; d.penalty = allele_penalty;
+        d.allele_off = (const uint32_t*)(arena + o.aoff); d.allele_id = (const uint16_t*)(arena + o.aid);
+        d.path_allele = (const uint16_t*)(arena + o.pa); d.tcost = (const uint32_t*)(arena + o.tc);
+        d.ecost = (uint16_t*)(arena + o.ec); d.paths = (uint32_t*)(arena + o.paths); d.best = (uint32_t*)(arena + o.best);
+        if (fast) {
+            d.slot = (uint8_t*)(arena + o.slot); d.ecell = (unsigned long long*)(arena + o.ecell); d.stay = (uint32_t*)(arena + o.stay);
+            d.minima = (uint32_t*)(arena + o.minima); d.last = (uint32_t*)(arena + o.last);
+        } else {
+            d.bt = (uint16_t*)(arena + o.bt); d.last_col = (uint32_t*)(arena + o.last_col);
+        }
+        HIP_TRY(hipMemcpy(arena + o.aoff, b->allele_off, (V + 1) * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(arena + o.aid, b->allele_id, sumA * 2, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(arena + o.pa, b->path_allele, V * P * 2, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(arena + o.tc, tcost[j].data(), V * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(arena + o.ec, ecost[j].data(), sumA * 2, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemcpy(arena + o_devs, devs.data(), sizeof(SamplerDev) * n, hipMemcpyHostToDevice));
+    rc = run_passes((const SamplerDev*)(arena + o_devs), n, fast, true, NW, maxP, size, ms, err, errlen);
+    if (rc != PG_OK) goto done;
     for (uint32_t j = 0; j < n; ++j) {
         const size_t V = panels[live[j]].n_variants;
         if (sampled_paths && sampled_paths[live[j]]) HIP_TRY(hipMemcpy(sampled_paths[live[j]], arena + offs[j].paths, (size_t)size * V * 4, hipMemcpyDeviceToHost));
@@ -793,7 +869,6 @@ int sampler_run_core(const pg_contig_batch* panels, uint32_t n_contigs, uint32_t
     g_last_kernel = fast ? (int)NW : 0;
     if (keep) { keep->arena = arena; arena = nullptr; }
 done:
-    for (auto& e : ev) if (e) hipEventDestroy(e);
     if (arena) hipFree(arena);
     return rc;
 }
@@ -942,6 +1017,7 @@ extern "C" int pg_sampler_then_job(const pg_contig_batch* panels, uint32_t n_con
                                    const pg_table* table, const pg_hmm_params* params, int device,
                                    uint32_t* const* sampled_paths, uint32_t* const* best_scores,
                                    pg_job** out_job, char* err, size_t errlen) {
+    g_last_h2d[0] = g_last_h2d[1] = 0;
     if (!panels || !table || !params || !out_job || n_contigs == 0) { set_err(err, errlen, "null argument"); return PG_ERR_INVALID; }
     *out_job = nullptr;
     if (size < 1) { set_err(err, errlen, "pg_sampler_then_job: at least one pass"); return PG_ERR_INVALID; }
@@ -1047,11 +1123,365 @@ extern "C" int pg_sampler_then_job(const pg_contig_batch* panels, uint32_t n_con
         q.allele_kmer_off = (const uint16_t*)(stage + t.nakoff); q.allele_kmer_mask = (const uint32_t*)(stage + t.nakmask);
         q.path_allele = (const uint16_t*)(stage + t.npa);
     }
+    {   // what crossed PCIe for the sampler and the update (pg_sampler_last_h2d_bytes): [1] = what differs per sample, the k-mer
+        // counts and the emission costs the host formed from them; [0] = the rest
+        uint64_t ix = 0, ps = 0;
+        for (uint32_t g = 0; g < n_contigs; ++g) {
+            const uint64_t V = panels[g].n_variants;
+            if (V == 0) continue;
+            const uint64_t sumK = panels[g].kmer_off[V], sumA = panels[g].allele_off[V];
+            ix += (V + 1) * 8 + V * 4 + sumA * (2 + 1 + 2 + 4) + V * panels[g].n_paths * 2;
+            ps += sumK * 2 + sumA * 2;
+        }
+        g_last_h2d[0] = ix; g_last_h2d[1] = ps;
+    }
     rc = pg_job_new(device, n_contigs, nb.data(), table, params, out_job, err, errlen);
 done:
     if (stage) hipFree(stage);
     if (keep.arena) hipFree(keep.arena);
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+//  Sampled cohorts: sampler -> panel update -> genotyping job for n_samples samples over ONE index.
+//
+//  Index level, once per call and shared by every sample's chain over a contig: the index arrays (uploaded once), the
+//  transition costs (host, they hang on positions, n_paths and the two sampling parameters only) and the slot table of the
+//  fast path (ks_slots).  Sample level: the k-mer counts (the only per-sample upload), the emission costs (ks_ecost, on the
+//  device), and — because ks_apply masks a picked cell by overwriting its slot byte — every chain's own copy of the slot
+//  table (ks_slot_copy, V*P bytes D2D per chain; DESIGN.md 4b has the measurement behind that choice).  The passes are
+//  run_passes over n_samples * n_live SamplerDevs whose index pointers alias the shared arrays; the reduction is ku_count /
+//  ku_write per chain; the job is pg_job_new over the reduced panels, on the device, after every sampler buffer is freed.
+// ------------------------------------------------------------------------------------------------
+extern "C" int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_contig_batch* index, uint32_t n_samples,
+                                     const pg_sample_counts* samples, uint32_t size, int add_reference, double sampling_recombrate,
+                                     long double sampling_effective_N, uint16_t allele_penalty, const pg_table* table,
+                                     const pg_hmm_params* params, uint32_t* const* sampled_paths, uint32_t* const* best_scores,
+                                     pg_job** out_job, char* err, size_t errlen) {
+    using clk = std::chrono::steady_clock;
+    const auto t_start = clk::now();
+    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
+    if (out_job) *out_job = nullptr;
+    g_last_h2d[0] = g_last_h2d[1] = 0;
+    for (double& x : g_last_phase_ms) x = 0.0;
+    if (!index || !samples || !table || !params || !out_job || n_contigs == 0) { set_err(err, errlen, "pg_sampler_cohort_new: null argument"); return PG_ERR_INVALID; }
+    if (n_samples == 0) { set_err(err, errlen, "pg_sampler_cohort_new: no samples"); return PG_ERR_INVALID; }
+    if (size < 1) { set_err(err, errlen, "pg_sampler_cohort_new: at least one pass"); return PG_ERR_INVALID; }
+    const uint32_t S = size + (add_reference ? 1u : 0u);
+    if (S > KU_MAX_PATHS) { set_err(err, errlen, "pg_sampler_cohort_new: at most %u kept paths", KU_MAX_PATHS); return PG_ERR_UNSUPPORTED; }
+    // ---- host preparation: checks, transition costs (index level), the cost table
+    std::vector<uint32_t> live;                               // index contigs with variants
+    std::vector<std::vector<uint32_t>> tcost(n_contigs);
+    bool fast = true;
+    uint32_t maxP = 0;
+    static const uint16_t no_counts = 0;
+    for (uint32_t c = 0; c < n_contigs; ++c) {
+        if (index[c].n_variants == 0) continue;
+        pg_contig_batch chk = index[c];
+        chk.kmer_count = &no_counts;                          // (ignored: the samples carry the counts)
+        const int rc0 = check_panel(&chk, size, err, errlen);
+        if (rc0 != PG_OK) return rc0;
+        if (!index[c].variant_pos) { set_err(err, errlen, "batch has null arrays"); return PG_ERR_INVALID; }
+        if (!contig_tcost(&index[c], sampling_recombrate, sampling_effective_N, tcost[c])) fast = false;
+        if (index[c].n_paths > maxP) maxP = index[c].n_paths;
+        live.push_back(c);
+    }
+    for (uint32_t s = 0; s < n_samples; ++s)
+        for (uint32_t c = 0; c < n_contigs; ++c) {
+            const uint32_t V = index[c].n_variants;
+            if (V == 0) continue;
+            if (index[c].kmer_off[V] > 0 && (!samples[s].kmer_count || !samples[s].kmer_count[c])) {
+                set_err(err, errlen, "pg_sampler_cohort_new: sample %u has no k-mer counts for contig %u", s, c);
+                return PG_ERR_INVALID;
+            }
+            if (!samples[s].coverage || !samples[s].coverage[c]) {
+                set_err(err, errlen, "pg_sampler_cohort_new: sample %u has no coverage for contig %u", s, c);
+                return PG_ERR_INVALID;
+            }
+        }
+    if (const char* e = getenv("PG_SAMPLER_KERNEL")) {
+        if (!strcmp(e, "general")) fast = false;
+        else if (!strcmp(e, "fast") && !fast) { set_err(err, errlen, "PG_SAMPLER_KERNEL=fast: the panel is outside the fast kernel's bounds"); return PG_ERR_UNSUPPORTED; }
+    }
+    int ndev = 0, rc = PG_OK;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_err(err, errlen, "no HIP device available (no CPU fallback)"); return PG_ERR_DEVICE; }
+    if (device < 0 || device >= ndev) { set_err(err, errlen, "bad device %d", device); return PG_ERR_INVALID; }
+    uint32_t NW = 1;
+    while (NW * 256u < maxP) NW *= 2;                        // 4 paths per lane
+    const uint32_t T = NW * 64u;
+    uint16_t cost33[33 * 33];
+    for (uint32_t total = 0; total <= 32u; ++total)
+        for (uint32_t present = 0; present <= 32u; ++present) cost33[total * 33u + present] = emission_cost_of(present, total);
+    const uint32_t nL = (uint32_t)live.size(), nch = n_samples * nL;   // chain j = s * nL + l runs contig live[l] of sample s
+    if ((uint64_t)n_samples * nL > 65535u) {   // (the chains are a grid dimension of the pass kernels)
+        set_err(err, errlen, "pg_sampler_cohort_new: at most 65535 sampled chains per call (%u samples x %u contigs with variants): split the samples", n_samples, nL);
+        return PG_ERR_UNSUPPORTED;
+    }
+
+    // ---- the plan: four arenas.  idx (index level) and chain (per chain: counts, costs, picks) live until the reduction;
+    // pass (the passes' own buffers) is freed before the reduced panels are allocated; red (reduced panels) lives until
+    // the job has copied them.  Peak = idx + chain + max(pass, red); then red + the job.
+    size_t o_idx = 0, o_ch = 0, o_pass = 0, o_red = 0;
+    auto take = [](size_t& off, size_t bytes) { off = (off + 255) / 256 * 256; size_t o = off; off += bytes ? bytes : 8; return o; };
+    struct IdxOffs { size_t aoff, aid, pa, tc, koff, aflag, akoff, akmask, slot; };
+    struct ChOffs { size_t kcnt, ec, paths, best, slot, ecell, stay, minima, last, bt, last_col, nkcnt, naid, naflag, nakoff, nakmask, npa, counts, offs; };
+    std::vector<IdxOffs> io(nL);
+    std::vector<ChOffs> co(nch);
+    for (uint32_t l = 0; l < nL; ++l) {
+        const pg_contig_batch& b = index[live[l]];
+        const size_t V = b.n_variants, P = b.n_paths, sumA = b.allele_off[V];
+        IdxOffs& o = io[l];
+        o.aoff = take(o_idx, (V + 1) * 4); o.aid = take(o_idx, sumA * 2); o.pa = take(o_idx, V * P * 2); o.tc = take(o_idx, (V + 48) * 4);
+        o.koff = take(o_idx, (V + 1) * 4); o.aflag = take(o_idx, sumA); o.akoff = take(o_idx, sumA * 2); o.akmask = take(o_idx, sumA * 4);
+        o.slot = fast ? take(o_idx, (V * P + 15) / 16 * 16) : 0;
+    }
+    const size_t o_cost33 = take(o_idx, sizeof(cost33));
+    size_t red_counts = 0, red_offs = 0;   // running u32 positions in the one counts / offsets range of all chains
+    for (uint32_t j = 0; j < nch; ++j) {
+        const pg_contig_batch& b = index[live[j % nL]];
+        const size_t V = b.n_variants, P = b.n_paths, sumA = b.allele_off[V], sumK = b.kmer_off[V];
+        ChOffs& o = co[j];
+        o.kcnt = take(o_ch, sumK * 2); o.ec = take(o_ch, sumA * 2); o.paths = take(o_ch, (size_t)size * V * 4); o.best = take(o_ch, (size_t)size * 4);
+        if (fast) {
+            o.slot = take(o_pass, (V * P + 15) / 16 * 16); o.ecell = take(o_pass, (V + 32) * T * 8); o.stay = take(o_pass, ((V + 14) / 16 + 1) * 2 * T * 4);
+            o.minima = take(o_pass, V * 4); o.last = take(o_pass, 4); o.bt = o.last_col = 0;
+        } else {
+            o.bt = take(o_pass, V * P * 2); o.last_col = take(o_pass, P * 4); o.slot = o.ecell = o.stay = o.minima = o.last = 0;
+        }
+        o.nkcnt = take(o_red, sumK * 2); o.naid = take(o_red, sumA * 2); o.naflag = take(o_red, sumA); o.nakoff = take(o_red, sumA * 2);
+        o.nakmask = take(o_red, sumA * 4); o.npa = take(o_red, V * S * 2);
+        o.counts = red_counts; red_counts += 2 * V;
+        o.offs = red_offs; red_offs += 2 * (V + 1);
+    }
+    const size_t o_devs = take(o_pass, sizeof(SamplerDev) * nch), o_cdevs = take(o_pass, sizeof(CostDev) * nch), o_ldevs = take(o_pass, sizeof(SamplerDev) * nL);
+    const size_t o_counts = take(o_red, red_counts * 4), o_offs = take(o_red, red_offs * 4), o_err = take(o_red, 4);
+
+    unsigned char *idx = nullptr, *ch = nullptr, *pass = nullptr, *red = nullptr;
+    std::vector<SamplerDev> devs(nch), ldevs(nL);
+    std::vector<CostDev> cdevs(nch);
+    std::unique_ptr<uint32_t[]> counts_h(new uint32_t[red_counts + 1]), offs_h(new uint32_t[red_offs + 1]);   // (every entry is written: no fill)
+    std::vector<pg_contig_batch> nb((size_t)n_samples * n_contigs);
+    uint32_t dev_err = 0;
+    double ms[3] = {0.0, 0.0, 0.0};
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    auto t = clk::now();
+    auto alloc = [&](unsigned char** p, size_t bytes) -> int {
+        hipError_t he = hipMalloc((void**)p, bytes);
+        if (he != hipSuccess) {   // cached arenas of the one-shot call may be what stands in the way
+            (void)hipGetLastError();
+            pg_hmm_release_cache();
+            hipSetDevice(device);
+            he = hipMalloc((void**)p, bytes);
+        }
+        if (he == hipSuccess) return PG_OK;
+        (void)hipGetLastError();
+        *p = nullptr;
+        set_err(err, errlen,
+                "pg_sampler_cohort_new: %u samples x %u contigs need %zu bytes of device memory at the peak (index %zu, per-sample %zu, "
+                "pass buffers %zu, reduced panels %zu; then the job beside the reduced panels): split the samples",
+                n_samples, n_contigs, o_idx + o_ch + (o_pass > o_red ? o_pass : o_red), o_idx, o_ch, o_pass, o_red);
+        return PG_ERR_NOMEM;
+    };
+    g_last_phase_ms[0] = ms_since(t_start);
+    HIP_TRY(hipSetDevice(device));
+    if (nch > 0) {
+        for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+        if ((rc = alloc(&idx, o_idx)) != PG_OK) goto done;
+        if ((rc = alloc(&ch, o_ch)) != PG_OK) goto done;
+        if ((rc = alloc(&pass, o_pass)) != PG_OK) goto done;
+        // ---- H2D: the index once, then every sample's counts
+        t = clk::now();
+        for (uint32_t l = 0; l < nL; ++l) {
+            const pg_contig_batch& b = index[live[l]];
+            const size_t V = b.n_variants, P = b.n_paths, sumA = b.allele_off[V];
+            const IdxOffs& o = io[l];
+            HIP_TRY(hipMemcpy(idx + o.aoff, b.allele_off, (V + 1) * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(idx + o.aid, b.allele_id, sumA * 2, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(idx + o.pa, b.path_allele, V * P * 2, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(idx + o.tc, tcost[live[l]].data(), V * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(idx + o.koff, b.kmer_off, (V + 1) * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(idx + o.aflag, b.allele_flags, sumA, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(idx + o.akoff, b.allele_kmer_off, sumA * 2, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(idx + o.akmask, b.allele_kmer_mask, sumA * 4, hipMemcpyHostToDevice));
+            g_last_h2d[0] += (V + 1) * 8 + V * P * 2 + V * 4 + sumA * (2 + 1 + 2 + 4);
+        }
+        HIP_TRY(hipMemcpy(idx + o_cost33, cost33, sizeof(cost33), hipMemcpyHostToDevice));
+        g_last_h2d[0] += sizeof(cost33);
+        for (uint32_t j = 0; j < nch; ++j) {
+            const uint32_t s = j / nL, c = live[j % nL];
+            const size_t sumK = index[c].kmer_off[index[c].n_variants];
+            if (sumK) HIP_TRY(hipMemcpy(ch + co[j].kcnt, samples[s].kmer_count[c], sumK * 2, hipMemcpyHostToDevice));
+            g_last_h2d[1] += sumK * 2;
+        }
+        g_last_phase_ms[1] = ms_since(t);
+        // ---- pointer sets: index arrays aliased, the rest the chain's own
+        for (uint32_t l = 0; l < nL; ++l) {
+            const pg_contig_batch& b = index[live[l]];
+            SamplerDev& d = ldevs[l];
+            memset(&d, 0, sizeof(d));
+            d.V = b.n_variants; d.P = b.n_paths; d.T = T;
+            d.allele_off = (const uint32_t*)(idx + io[l].aoff); d.allele_id = (const uint16_t*)(idx + io[l].aid);
+            d.path_allele = (const uint16_t*)(idx + io[l].pa); d.slot = fast ? idx + io[l].slot : nullptr;
+        }
+        for (uint32_t j = 0; j < nch; ++j) {
+            const uint32_t l = j % nL;
+            const pg_contig_batch& b = index[live[l]];
+            const size_t V = b.n_variants, P = b.n_paths;
+            const IdxOffs& x = io[l];
+            const ChOffs& o = co[j];
+            SamplerDev& d = devs[j];
+            memset(&d, 0, sizeof(d));
+            d.V = (uint32_t)V; d.P = (uint32_t)P; d.T = T; d.penalty = allele_penalty;
+            d.allele_off = (const uint32_t*)(idx + x.aoff); d.allele_id = (const uint16_t*)(idx + x.aid);
+            d.path_allele = (const uint16_t*)(idx + x.pa); d.tcost = (const uint32_t*)(idx + x.tc);
+            d.ecost = (uint16_t*)(ch + o.ec); d.paths = (uint32_t*)(ch + o.paths); d.best = (uint32_t*)(ch + o.best);
+            if (fast) {
+                d.slot = pass + o.slot; d.ecell = (unsigned long long*)(pass + o.ecell); d.stay = (uint32_t*)(pass + o.stay);
+                d.minima = (uint32_t*)(pass + o.minima); d.last = (uint32_t*)(pass + o.last);
+            } else {
+                d.bt = (uint16_t*)(pass + o.bt); d.last_col = (uint32_t*)(pass + o.last_col);
+            }
+            CostDev& q = cdevs[j];
+            memset(&q, 0, sizeof(q));
+            q.V = (uint32_t)V;
+            q.allele_off = d.allele_off; q.kmer_off = (const uint32_t*)(idx + x.koff); q.allele_flags = idx + x.aflag;
+            q.allele_koff = (const uint16_t*)(idx + x.akoff); q.allele_kmask = (const uint32_t*)(idx + x.akmask);
+            q.kmer_count = (const uint16_t*)(ch + o.kcnt); q.ecost = d.ecost;
+            if (fast) { q.slot_src = idx + x.slot; q.slot_dst = d.slot; q.slot_bytes = (V * P + 15) / 16 * 16; }
+        }
+        HIP_TRY(hipMemcpy(pass + o_devs, devs.data(), sizeof(SamplerDev) * nch, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(pass + o_cdevs, cdevs.data(), sizeof(CostDev) * nch, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(pass + o_ldevs, ldevs.data(), sizeof(SamplerDev) * nL, hipMemcpyHostToDevice));
+        // ---- the emission costs of every chain; the slot tables once per contig, then every chain's copy
+        HIP_TRY(hipEventRecord(ev[0], nullptr));
+        hipLaunchKernelGGL(ks_ecost, dim3(64, nch), dim3(256), 0, nullptr, (const CostDev*)(pass + o_cdevs), (const uint16_t*)(idx + o_cost33));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev[1], nullptr));
+        if (fast) {
+            hipLaunchKernelGGL(ks_slots, dim3(2048, nL), dim3(256), 0, nullptr, (const SamplerDev*)(pass + o_ldevs));
+            hipLaunchKernelGGL(ks_slot_copy, dim3(256, nch), dim3(256), 0, nullptr, (const CostDev*)(pass + o_cdevs));
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(ev[2], nullptr));
+        HIP_TRY(hipEventSynchronize(ev[2]));
+        {
+            float a = 0.f, b = 0.f;
+            HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
+            HIP_TRY(hipEventElapsedTime(&b, ev[1], ev[2]));
+            g_last_phase_ms[2] = a; g_last_phase_ms[3] = b;
+        }
+        // ---- the passes
+        t = clk::now();
+        rc = run_passes((const SamplerDev*)(pass + o_devs), nch, fast, false, NW, maxP, size, ms, err, errlen);
+        if (rc != PG_OK) goto done;
+        g_last_ms[0] = ms[0]; g_last_ms[1] = ms[1]; g_last_ms[2] = ms[2];
+        g_last_kernel = fast ? (int)NW : 0;
+        for (uint32_t j = 0; j < nch; ++j) {
+            const uint32_t g = (j / nL) * n_contigs + live[j % nL];
+            const size_t V = index[live[j % nL]].n_variants;
+            if (sampled_paths && sampled_paths[g]) HIP_TRY(hipMemcpy(sampled_paths[g], ch + co[j].paths, (size_t)size * V * 4, hipMemcpyDeviceToHost));
+            if (best_scores && best_scores[g]) HIP_TRY(hipMemcpy(best_scores[g], ch + co[j].best, (size_t)size * 4, hipMemcpyDeviceToHost));
+        }
+        g_last_phase_ms[4] = ms_since(t);
+        HIP_TRY(hipFree(pass));
+        pass = nullptr;
+        // ---- the panels reduced to the picks, per chain over the shared index and the chain's own counts
+        t = clk::now();
+        if ((rc = alloc(&red, o_red)) != PG_OK) goto done;
+        HIP_TRY(hipMemset(red + o_err, 0, 4));
+        for (int phase = 0; phase < 2; ++phase) {
+            for (uint32_t j = 0; j < nch; ++j) {
+                const uint32_t l = j % nL;
+                const pg_contig_batch& b = index[live[l]];
+                const IdxOffs& x = io[l];
+                const ChOffs& o = co[j];
+                UpdateDev d;
+                memset(&d, 0, sizeof(d));
+                d.V = b.n_variants; d.P = b.n_paths; d.S = S; d.size = size;
+                d.kmer_off = (const uint32_t*)(idx + x.koff); d.kmer_count = (const uint16_t*)(ch + o.kcnt);
+                d.allele_off = (const uint32_t*)(idx + x.aoff); d.allele_id = (const uint16_t*)(idx + x.aid);
+                d.allele_flags = idx + x.aflag; d.allele_koff = (const uint16_t*)(idx + x.akoff); d.allele_kmask = (const uint32_t*)(idx + x.akmask);
+                d.path_allele = (const uint16_t*)(idx + x.pa); d.paths = (const uint32_t*)(ch + o.paths);
+                d.counts = (uint32_t*)(red + o_counts) + o.counts;
+                d.new_koff = (const uint32_t*)(red + o_offs) + o.offs; d.new_aoff = d.new_koff + (b.n_variants + 1);
+                d.new_kcount = (uint16_t*)(red + o.nkcnt); d.new_aid = (uint16_t*)(red + o.naid); d.new_aflags = red + o.naflag;
+                d.new_akoff = (uint16_t*)(red + o.nakoff); d.new_akmask = (uint32_t*)(red + o.nakmask); d.new_pa = (uint16_t*)(red + o.npa);
+                d.err = (uint32_t*)(red + o_err);
+                if (phase == 0) hipLaunchKernelGGL(ku_count, dim3((b.n_variants + 3) / 4), dim3(256), 0, nullptr, d);
+                else hipLaunchKernelGGL(ku_write, dim3((b.n_variants + 3) / 4), dim3(256), 0, nullptr, d);
+                HIP_TRY(hipGetLastError());
+            }
+            HIP_TRY(hipStreamSynchronize(nullptr));
+            HIP_TRY(hipMemcpy(&dev_err, red + o_err, 4, hipMemcpyDeviceToHost));
+            if (phase == 0) {
+                if (dev_err & 1u) { set_err(err, errlen, "pg_sampler_cohort_new: a variant has more than %u alleles or %u k-mers", KU_MAX_ALLELES, KU_MAX_KMERS); rc = PG_ERR_UNSUPPORTED; goto done; }
+                // all chains' counts -> offsets in one round trip (the job's arena is planned from them on the host)
+                HIP_TRY(hipMemcpy(counts_h.get(), red + o_counts, red_counts * 4, hipMemcpyDeviceToHost));
+                for (uint32_t j = 0; j < nch; ++j) {
+                    const size_t V = index[live[j % nL]].n_variants;
+                    const uint32_t* cnt = counts_h.get() + co[j].counts;
+                    uint32_t* nk = offs_h.get() + co[j].offs;
+                    uint32_t* na = nk + (V + 1);
+                    nk[0] = na[0] = 0;
+                    for (size_t v = 0; v < V; ++v) { na[v + 1] = na[v] + cnt[2 * v]; nk[v + 1] = nk[v] + cnt[2 * v + 1]; }
+                }
+                HIP_TRY(hipMemcpy(red + o_offs, offs_h.get(), red_offs * 4, hipMemcpyHostToDevice));
+            } else if (dev_err & 2u) {
+                set_err(err, errlen, "pg_sampler_cohort_new: an allele's k-mers span more than 32 positions after the update");
+                rc = PG_ERR_INVALID;
+                goto done;
+            }
+        }
+        HIP_TRY(hipFree(idx));
+        idx = nullptr;
+        HIP_TRY(hipFree(ch));
+        ch = nullptr;
+        g_last_phase_ms[5] = ms_since(t);
+    }
+    // ---- the job over the reduced panels: chain s * n_contigs + c; offsets, positions and the sample's coverage from the
+    // host, the six big arrays from the device
+    t = clk::now();
+    {
+        std::vector<uint32_t> live_of(n_contigs, 0);
+        for (uint32_t l = 0; l < nL; ++l) live_of[live[l]] = l;
+        for (uint32_t s = 0; s < n_samples; ++s)
+            for (uint32_t c = 0; c < n_contigs; ++c) {
+                pg_contig_batch& q = nb[(size_t)s * n_contigs + c];
+                q = index[c];
+                q.kmer_count = nullptr;
+                q.coverage = samples[s].coverage ? samples[s].coverage[c] : nullptr;
+                if (index[c].n_variants == 0) continue;
+                const uint32_t j = s * nL + live_of[c];
+                const ChOffs& o = co[j];
+                q.n_paths = S;
+                q.kmer_off = offs_h.get() + o.offs; q.allele_off = offs_h.get() + o.offs + (index[c].n_variants + 1);
+                q.kmer_count = (const uint16_t*)(red + o.nkcnt); q.allele_id = (const uint16_t*)(red + o.naid); q.allele_flags = red + o.naflag;
+                q.allele_kmer_off = (const uint16_t*)(red + o.nakoff); q.allele_kmer_mask = (const uint32_t*)(red + o.nakmask);
+                q.path_allele = (const uint16_t*)(red + o.npa);
+            }
+    }
+    rc = pg_job_new(device, n_samples * n_contigs, nb.data(), table, params, out_job, err, errlen);
+    g_last_phase_ms[6] = ms_since(t);
+done:
+    for (auto& e : ev) if (e) hipEventDestroy(e);
+    if (pass) hipFree(pass);
+    if (idx) hipFree(idx);
+    if (ch) hipFree(ch);
+    if (red) hipFree(red);
+    g_last_phase_ms[7] = ms_since(t_start);
+    return rc;
+}
+
+extern "C" int pg_sampler_last_h2d_bytes(uint64_t out2[2]) {
+    if (!out2) return PG_ERR_INVALID;
+    out2[0] = g_last_h2d[0]; out2[1] = g_last_h2d[1];
+    return PG_OK;
+}
+
+extern "C" int pg_sampler_last_phase_ms(double out8[8]) {
+    if (!out8) return PG_ERR_INVALID;
+    for (int i = 0; i < 8; ++i) out8[i] = g_last_phase_ms[i];
+    return PG_OK;
 }
 
 extern "C" int pg_sampler_last_ms(double out3[3], int* kernel) {

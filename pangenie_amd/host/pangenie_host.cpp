@@ -741,6 +741,102 @@ std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohor
     return out;
 }
 
+// ------------------------------------------------------------------ sampled cohort job
+std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohort_sampled(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::vector<SampleCounts>& samples,
+    size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device,
+    std::vector<std::map<std::string, SampledPaths>>* sampled) {
+    const size_t C = chromosomes.size(), S = samples.size();
+    std::vector<std::map<std::string, std::vector<GenotypingResult>>> out(S);
+    if (sampled) sampled->assign(S, {});
+    if (C == 0 || S == 0) return out;
+    std::vector<std::string> names;
+    std::vector<FlatContig> flat(C);   // ALL paths of the panel
+    std::vector<pg_contig_batch> index(C);
+    size_t c = 0;
+    for (auto& kv : chromosomes) {
+        names.push_back(kv.first);
+        flatten(&kv.second, nullptr, flat[c]);
+        index[c] = flat[c].batch;
+        c += 1;
+    }
+    static const uint16_t none = 0;
+    std::vector<std::vector<const uint16_t*>> count_rows(S, std::vector<const uint16_t*>(C)), cov_rows(S, std::vector<const uint16_t*>(C));
+    std::vector<pg_sample_counts> rows(S);
+    for (size_t s = 0; s < S; ++s) {
+        for (c = 0; c < C; ++c) {
+            const auto k = samples[s].kmer_count.find(names[c]), v = samples[s].coverage.find(names[c]);
+            if (k == samples[s].kmer_count.end() || v == samples[s].coverage.end() || k->second.size() != flat[c].kmer_count.size() ||
+                v->second.size() != flat[c].variant_pos.size())
+                fail("genotype_cohort_sampled: sample " + std::to_string(s) + " does not fit the index on " + names[c]);
+            count_rows[s][c] = k->second.empty() ? &none : k->second.data();
+            cov_rows[s][c] = v->second.empty() ? &none : v->second.data();
+        }
+        rows[s].kmer_count = count_rows[s].data();
+        rows[s].coverage = cov_rows[s].data();
+    }
+    const uint32_t size = (uint32_t)panel_size;
+    std::vector<std::vector<uint32_t>> picks(sampled ? S * C : 0);
+    std::vector<uint32_t*> pick_rows(S * C, nullptr);
+    for (size_t g = 0; g < picks.size(); ++g) {
+        picks[g].assign((size_t)size * flat[g % C].variant_pos.size() + 1, 0);
+        pick_rows[g] = picks[g].data();
+    }
+    pg_hmm_params prm{};
+    prm.effective_N = effective_N; prm.recombrate = recombrate; prm.uniform = uniform ? 1 : 0; prm.run_genotyping = 1;
+    char err[1024] = {0};
+    pg_job* job = nullptr;
+    int rc = pg_sampler_cohort_new(device, (uint32_t)C, index.data(), (uint32_t)S, rows.data(), size, add_reference ? 1 : 0, recombrate,
+                                   sampling_effective_N, allele_penalty, probabilities->handle(), &prm, sampled ? pick_rows.data() : nullptr,
+                                   nullptr, &job, err, sizeof(err));
+    if (rc == PG_OK) rc = pg_job_run(job, nullptr, err, sizeof(err));
+    if (rc != PG_OK) { if (job) pg_job_destroy(job); check_rc(rc, err); }
+    for (size_t s = 0; s < S && rc == PG_OK; ++s)
+        for (c = 0; c < C && rc == PG_OK; ++c) {
+            const uint32_t chain = (uint32_t)(s * C + c);   // chain id = sample * n_contigs + contig
+            const size_t V = flat[c].variant_pos.size();
+            // the reduced panel of this chain, back from the device: the allele ids of the results are its own
+            FlatContig r;
+            uint32_t nv = 0, np = 0;
+            uint64_t sk = 0, sa = 0;
+            rc = pg_job_panel_sizes(job, chain, &nv, &np, &sk, &sa);
+            if (rc != PG_OK) { std::snprintf(err, sizeof(err), "genotype_cohort_sampled: pg_job_panel_sizes failed"); break; }
+            r.variant_pos = flat[c].variant_pos;
+            r.coverage.assign(cov_rows[s][c], cov_rows[s][c] + V);
+            r.kmer_off.assign(nv + 1, 0); r.allele_off.assign(nv + 1, 0);
+            r.kmer_count.assign(sk, 0); r.allele_id.assign(sa, 0); r.allele_flags.assign(sa, 0); r.allele_kmer_off.assign(sa, 0);
+            r.allele_kmer_mask.assign(sa, 0); r.path_allele.assign((size_t)nv * np, 0);
+            r.paths.resize(V ? np : 0);
+            for (size_t p = 0; p < r.paths.size(); ++p) r.paths[p] = (unsigned short)p;
+            if (V) {
+                rc = pg_job_fetch_panel(job, chain, r.kmer_off.data(), r.kmer_count.data(), r.allele_off.data(), r.allele_id.data(), r.allele_flags.data(),
+                                        r.allele_kmer_off.data(), r.allele_kmer_mask.data(), r.path_allele.data(), err, sizeof(err));
+                if (rc != PG_OK) break;
+            }
+            r.bind();
+            std::vector<uint64_t> goff(V + 1, 0);
+            pg_hmm_geno_offsets(&r.batch, goff.data());
+            const uint64_t n = goff.back();
+            std::vector<double> lik(n ? n : 1);
+            std::vector<int32_t> lexp(n ? n : 1);
+            pg_contig_result res{};
+            res.lik = lik.data(); res.lik_exp = lexp.data();
+            rc = pg_job_fetch(job, chain, &res, err, sizeof(err));
+            if (rc != PG_OK) break;
+            out[s][names[c]] = results_of_chain(r, cov_rows[s][c], goff, lik.data(), lexp.data());
+            if (sampled) {   // as HaplotypeSampler::get_sampled_paths() has them (src/haplotypesampler.cpp:28-44)
+                SampledPaths& sp = (*sampled)[s][names[c]];
+                const uint32_t* pk = picks[s * C + c].data();
+                for (uint32_t i = 0; i < size; ++i) sp.sampled_paths.emplace_back(pk + (size_t)i * V, pk + (size_t)(i + 1) * V);
+                if (add_reference) sp.sampled_paths.push_back(std::vector<size_t>(V, 0));
+            }
+        }
+    pg_job_destroy(job);
+    check_rc(rc, err);
+    return out;
+}
+
 void HMM::combine_likelihoods(HMM& other) {
     if (genotyping_result_.size() != other.genotyping_result_.size())
         fail("HMM::combine_likelihoods: HMMs to be combined must be of the same size.");

@@ -384,4 +384,20 @@ private:
     SampledPaths sampled_paths;
 };
 
+/** The sampled counterpart of genotype_cohort (C ABI pg_sampler_cohort_new): many samples against ONE index of a large panel,
+ *  in one device job.  Per sample and chromosome it returns what the reference's per-sample sequence returns on that sample's
+ *  counts — fill_read_kmercounts, then HaplotypeSampler(&objects, panel_size, recombrate, sampling_effective_N, ...,
+ *  add_reference, ..., allele_penalty), then HMM(&objects, probabilities, true, false, recombrate, uniform, effective_N,
+ *  nullptr, normalize = false) (src/commands.cpp:118-160) — without touching the objects of `chromosomes`: the index
+ *  arrays go to the device once, each sample's panel is sampled and reduced there.  Allele ids of the results are the panel's
+ *  own, so Graph::write_genotypes takes them unchanged.  `sampled` (may be null): per sample and chromosome the sampled paths
+ *  as HaplotypeSampler::get_sampled_paths() returns them (with the reference path when add_reference), for
+ *  Graph::write_sampled_panel.  `probabilities` as for genotype_cohort.  Throws std::runtime_error on samples whose arrays do
+ *  not fit the index and on the C ABI's errors (PG_ERR_NOMEM: split the samples). */
+std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohort_sampled(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::vector<SampleCounts>& samples,
+    size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
+    std::vector<std::map<std::string, SampledPaths>>* sampled = nullptr);
+
 }  // namespace pangenie

@@ -13,7 +13,7 @@ from typing import Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import PgContigBatch, u8p, u16p, u32p, f64p, c_ld as _c_ld
+from ._lib import PgContigBatch, PgSampleCounts, u8p, u16p, u32p, f64p, c_ld as _c_ld
 from .panel import ContigBatch
 
 _bound = False
@@ -42,12 +42,22 @@ def _hip():
         lib.pg_sampler_then_job.restype = C.c_int
         lib.pg_sampler_last_ms.argtypes = [f64p, C.POINTER(C.c_int)]
         lib.pg_sampler_last_ms.restype = C.c_int
+        lib.pg_sampler_cohort_new.argtypes = [C.c_int, C.c_uint32, C.POINTER(PgContigBatch), C.c_uint32, C.POINTER(PgSampleCounts),
+                                              C.c_uint32, C.c_int, C.c_double, ld, C.c_uint16, C.c_void_p, C.c_void_p,
+                                              C.POINTER(u32p), C.POINTER(u32p), C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+        lib.pg_sampler_cohort_new.restype = C.c_int
+        lib.pg_sampler_last_h2d_bytes.argtypes = [C.POINTER(C.c_uint64)]
+        lib.pg_sampler_last_h2d_bytes.restype = C.c_int
+        lib.pg_sampler_last_phase_ms.argtypes = [f64p]
+        lib.pg_sampler_last_phase_ms.restype = C.c_int
         _bound = True
     return lib
 
 
 SAMPLER_ABI_SYMBOLS = ["pg_sampler_emission_costs", "pg_sampler_transition_cost", "pg_sampler_column_minima",
-                       "pg_sampler_run", "pg_sampler_run_batch", "pg_sampler_last_ms", "pg_sampler_then_job"]
+                       "pg_sampler_run", "pg_sampler_run_batch", "pg_sampler_last_ms", "pg_sampler_then_job",
+                       "pg_sampler_cohort_new", "pg_sampler_last_phase_ms"]
+# (pg_sampler_last_h2d_bytes is exported too; it stays off this list, which mirrors the header's letters-only names)
 NO_ID = 0xFFFFFFFF
 
 
@@ -179,6 +189,77 @@ def sample_then_job(batches: Sequence[ContigBatch], size: int, table, params=Non
     if want_paths:
         return job, [s[:, : b.n_variants] for s, b in zip(sampled, batches)], [x[:size] for x in best]
     return job, None, None
+
+
+def marshal_samples(index: Sequence[ContigBatch], samples):
+    """(pg_sample_counts[n], arrays to keep alive) from samples in the format of hmm.Job.cohort — one (kmer_counts,
+    coverages) per sample, one uint16 array per index contig —, the lengths checked against the index on the host."""
+    nc = len(index)
+    arr = (PgSampleCounts * len(samples))()
+    keep = []
+    for s, (kcs, covs) in enumerate(samples):
+        if len(kcs) != nc or len(covs) != nc:
+            raise ValueError(f"sample {s}: {len(kcs)} count arrays and {len(covs)} coverage arrays for {nc} contigs")
+        kc = [np.ascontiguousarray(a, np.uint16) for a in kcs]
+        cv = [np.ascontiguousarray(a, np.uint16) for a in covs]
+        for c, b in enumerate(index):
+            if kc[c].size != int(b.kmer_off[-1]) or cv[c].size != b.n_variants:
+                raise ValueError(f"sample {s}, contig {c}: {kc[c].size} counts / {cv[c].size} coverages, the index has "
+                                 f"{int(b.kmer_off[-1])} k-mers / {b.n_variants} variants")
+        kc = [a if a.size else np.zeros(1, np.uint16) for a in kc]
+        cv = [a if a.size else np.zeros(1, np.uint16) for a in cv]
+        pk = (u16p * nc)(*[a.ctypes.data_as(u16p) for a in kc])
+        pc = (u16p * nc)(*[a.ctypes.data_as(u16p) for a in cv])
+        arr[s].kmer_count = pk
+        arr[s].coverage = pc
+        keep += [kc, cv, pk, pc]
+    return arr, keep
+
+
+def sample_cohort(index: Sequence[ContigBatch], samples, size: int, table, params=None, add_reference: bool = False,
+                  recombrate: float = 1.26, effective_N=25000.0, allele_penalty: int = 10, device: int = 0, want_paths: bool = True):
+    """pg_sampler_cohort_new: sample_then_job for every sample over ONE index (uploaded once; per sample only the k-mer
+    counts).  samples: as hmm.Job.cohort takes them.  -> (hmm.Job — chain s * n_contigs + c; job.batches are the reduced
+    panels read back from the device —, sampled[s][c] [size, V_c] or None, best[s][c] [size] or None)."""
+    from . import hmm
+    index = list(index)
+    samples = list(samples)
+    nc, ns = len(index), len(samples)
+    arr = (PgContigBatch * nc)(*[b.as_c() for b in index])
+    cs, keep = marshal_samples(index, samples)
+    sampled = best = sp = bp = None
+    if want_paths:
+        sampled = [[np.zeros((size, max(1, b.n_variants)), np.uint32) for b in index] for _ in range(ns)]
+        best = [[np.zeros(max(1, size), np.uint32) for _ in index] for _ in range(ns)]
+        sp = (u32p * (ns * nc))(*[a.ctypes.data_as(u32p) for row in sampled for a in row])
+        bp = (u32p * (ns * nc))(*[a.ctypes.data_as(u32p) for row in best for a in row])
+    params = params or hmm.make_params()
+    err = C.create_string_buffer(1024)
+    h = C.c_void_p()
+    rc = _hip().pg_sampler_cohort_new(device, nc, arr, ns, cs, size, int(bool(add_reference)), float(recombrate), _c_ld(effective_N),
+                                      int(allele_penalty), table.h, C.byref(params), sp, bp, C.byref(h), err, 1024)
+    del keep
+    if rc:
+        raise hmm.PanGenieError(rc, err.value.decode(errors="replace"))
+    job = hmm.Job.from_handle(h.value, table, params)
+    if want_paths:
+        return (job, [[s[:, : b.n_variants] for s, b in zip(row, index)] for row in sampled],
+                [[x[:size] for x in row] for row in best])
+    return job, None, None
+
+
+def last_h2d_bytes():
+    """H2D bytes of this thread's last sample_cohort / sample_then_job: (index arrays, per-sample arrays)"""
+    out = (C.c_uint64 * 2)()
+    _hip().pg_sampler_last_h2d_bytes(out)
+    return int(out[0]), int(out[1])
+
+
+def last_phase_ms() -> dict:
+    """Milliseconds of this thread's last sample_cohort, phase by phase (include/pangenie_sampler.h: pg_sampler_last_phase_ms)."""
+    ms = np.zeros(8)
+    _hip().pg_sampler_last_phase_ms(ms.ctypes.data_as(f64p))
+    return dict(zip(("host_prep", "h2d", "cost_kernel", "slots", "passes", "reduction", "job_new", "total"), map(float, ms)))
 
 
 class HaplotypeSampler:
