@@ -1,6 +1,8 @@
 // kmer_counts.cpp — see kmer_counts.hpp.
 #include "kmer_counts.hpp"
 
+#include "../../include/pangenie_kmers.h"
+
 #include <zlib.h>
 
 #include <algorithm>
@@ -568,6 +570,212 @@ unsigned short windowed_mean(const std::vector<size_t>& counts, size_t expected)
     return (unsigned short)((used && sum) ? sum / used : expected);
 }
 }  // namespace
+
+// ------------------------------------------------------------------ DeviceKmerCounter
+namespace {
+inline pg_kmer_counter* dev(void* h) { return static_cast<pg_kmer_counter*>(h); }
+}
+
+DeviceKmerCounter::DeviceKmerCounter(size_t kmer_size, bool unregistered_counts_zero, int device) : k_(kmer_size), lenient_(unregistered_counts_zero) {
+    if (k_ == 0 || k_ > 32) throw std::runtime_error("DeviceKmerCounter: k-mer size must be 1..32");
+    pg_kmer_counter* h = nullptr;
+    check(pg_kmer_counter_new((uint32_t)k_, device, &h), "pg_kmer_counter_new");
+    handle_ = h;
+}
+
+DeviceKmerCounter::~DeviceKmerCounter() { pg_kmer_counter_destroy(dev(handle_)); }
+
+void DeviceKmerCounter::check(int rc, const char* what) const {
+    if (rc != PG_OK) throw std::runtime_error(std::string("DeviceKmerCounter: ") + what + " failed (" + std::to_string(rc) + "): " + pg_kmer_last_error());
+}
+
+bool DeviceKmerCounter::encode_canonical(const char* s, uint64_t& code) const {
+    uint64_t fwd = 0, rev = 0;
+    for (size_t i = 0; i < k_; ++i) {
+        const int b = base_code(s[i]);
+        if (b < 0) return false;
+        fwd = (fwd << 2) | (uint64_t)b;
+        rev = (rev >> 2) | ((uint64_t)(3 - b) << (2 * (k_ - 1)));
+    }
+    code = fwd < rev ? fwd : rev;
+    return true;
+}
+
+void DeviceKmerCounter::flush_codes() {
+    if (codes_.empty()) return;
+    check(pg_kmer_counter_add_codes(dev(handle_), codes_.data(), codes_.size()), "pg_kmer_counter_add_codes");
+    codes_.clear();
+}
+
+void DeviceKmerCounter::add_target(std::string_view kmer) {
+    if (counting_) throw std::runtime_error("DeviceKmerCounter: targets must be registered before the reads are counted");
+    if (kmer.size() != k_) throw std::runtime_error("DeviceKmerCounter::add_target: k-mer of length " + std::to_string(kmer.size()) + ", counter holds " + std::to_string(k_) + "-mers");
+    uint64_t code;
+    if (encode_canonical(kmer.data(), code)) codes_.push_back(code);
+    if (codes_.size() >= ((size_t)1 << 20)) flush_codes();
+}
+
+size_t DeviceKmerCounter::add_targets_from_table(const std::string& kmers_tsv_gz) {
+    gzFile file = gzopen(kmers_tsv_gz.c_str(), "rb");
+    if (!file) throw std::runtime_error("DeviceKmerCounter: kmer file cannot be opened.");
+    std::vector<char> buf(1u << 16);
+    std::string line;
+    size_t rows = 0;
+    try {
+        while (gzgets(file, buf.data(), (int)buf.size()) != nullptr) {
+            line += buf.data();
+            if (line.empty() || line.back() != '\n') continue;
+            line.pop_back();
+            const KmerRow row(line);
+            if (!row.header) {
+                KmerRow::each_item(row.column[3], [&](std::string_view k) { add_target(k); });
+                KmerRow::each_item(row.column[4], [&](std::string_view k) { add_target(k); });
+                rows += 1;
+            }
+            line.clear();
+        }
+    } catch (...) {
+        gzclose(file);
+        throw;
+    }
+    gzclose(file);
+    return rows;
+}
+
+void DeviceKmerCounter::add_targets_of(std::string_view sequence) {
+    if (counting_) throw std::runtime_error("DeviceKmerCounter: targets must be registered before the reads are counted");
+    check(pg_kmer_counter_add_text(dev(handle_), sequence.data(), sequence.size(), nullptr), "pg_kmer_counter_add_text");
+}
+
+size_t DeviceKmerCounter::add_targets_from_sequences(const std::string& fasta) {
+    if (counting_) throw std::runtime_error("DeviceKmerCounter: targets must be registered before the reads are counted");
+    // batches as in count(): sequences back to back, a newline after each, coded and registered on the device
+    std::string text;
+    text.reserve((4u << 20) + (1u << 16));
+    size_t registered = 0;
+    auto flush = [&]() {
+        uint64_t windows = 0;
+        check(pg_kmer_counter_add_text(dev(handle_), text.data(), text.size(), &windows), "pg_kmer_counter_add_text");
+        registered += (size_t)windows;
+        text.clear();
+    };
+    stream_sequences(fasta, [&](const std::string& seq) {
+        text.append(seq);
+        text.push_back('\n');
+        if (text.size() >= (4u << 20)) flush();
+    });
+    if (!text.empty()) flush();
+    return registered;
+}
+
+void DeviceKmerCounter::count(const std::string& readfile, unsigned) {
+    flush_codes();
+    counting_ = true;
+    fetched_.store(false);
+    // the batch builder of TargetedKmerCounter::count with a pinned staging buffer in the place of a Batch: the device copies
+    // and counts the last buffers while the reader fills this one
+    pg_kmer_counter* h = dev(handle_);
+    char* buf = nullptr;
+    uint64_t room = 0, used = 0;
+    check(pg_kmer_counter_acquire(h, &buf, &room), "pg_kmer_counter_acquire");
+    std::exception_ptr failure;
+    try {
+        stream_sequences(readfile, [&](const std::string& seq) {
+            const uint64_t need = seq.size() + 1;
+            if (used + need > room) {
+                check(pg_kmer_counter_submit(h, used), "pg_kmer_counter_submit");
+                buf = nullptr; used = 0;
+                if (need > room) {   // a single sequence longer than a staging buffer: through pg_kmer_counter_count, which splits it
+                    check(pg_kmer_counter_count(h, seq.data(), seq.size()), "pg_kmer_counter_count");
+                    check(pg_kmer_counter_acquire(h, &buf, &room), "pg_kmer_counter_acquire");
+                    return;
+                }
+                check(pg_kmer_counter_acquire(h, &buf, &room), "pg_kmer_counter_acquire");
+            }
+            std::memcpy(buf + used, seq.data(), seq.size());
+            buf[used + seq.size()] = '\n';
+            used += need;
+        });
+    } catch (...) {
+        failure = std::current_exception();
+    }
+    if (buf) { const int rc = pg_kmer_counter_submit(h, failure ? 0 : used); if (!failure) check(rc, "pg_kmer_counter_submit"); }
+    const int rc = pg_kmer_counter_sync(h);
+    if (failure) std::rethrow_exception(failure);
+    check(rc, "pg_kmer_counter_sync");
+}
+
+void DeviceKmerCounter::fetch_table() {
+    std::lock_guard<std::mutex> hold(fetch_lock_);
+    if (fetched_.load()) return;
+    flush_codes();
+    pg_kmer_counter* h = dev(handle_);
+    check(pg_kmer_counter_capacity(h, &cap_), "pg_kmer_counter_capacity");
+    counting_ = true;   // (the table is built: as TargetedKmerCounter after its freeze())
+    table_.resize(2 * (size_t)cap_);
+    check(pg_kmer_counter_table(h, table_.data(), cap_), "pg_kmer_counter_table");
+    fetched_.store(true);
+}
+
+size_t DeviceKmerCounter::getKmerAbundance(std::string kmer) {
+    if (kmer.size() != k_) throw std::runtime_error("DeviceKmerCounter::getKmerAbundance: k-mer of length " + std::to_string(kmer.size()) + ", counter holds " + std::to_string(k_) + "-mers");
+    if (!fetched_.load()) fetch_table();
+    uint64_t code;
+    if (!encode_canonical(kmer.data(), code)) return 0;   // (letters outside ACGT: no window of a read can be this k-mer)
+    // the device's table has the layout of TargetedKmerCounter's (include/pangenie_kmers.h): the same walk
+    size_t at = slot_of(code, (size_t)cap_);
+    while (true) {
+        const uint64_t key = table_[2 * at];
+        if (key == code) return (size_t)table_[2 * at + 1];
+        if (key == kEmpty) break;
+        if (++at == cap_) at = 0;
+    }
+    if (lenient_) return 0;
+    throw std::runtime_error("DeviceKmerCounter::getKmerAbundance: " + kmer + " was not registered before the reads were counted");
+}
+
+size_t DeviceKmerCounter::targets() {
+    flush_codes();
+    counting_ = true;
+    uint64_t n = 0;
+    check(pg_kmer_counter_stats(dev(handle_), &n, nullptr), "pg_kmer_counter_stats");
+    return (size_t)n;
+}
+
+size_t DeviceKmerCounter::kmers_seen() {
+    uint64_t n = 0;
+    check(pg_kmer_counter_stats(dev(handle_), nullptr, &n), "pg_kmer_counter_stats");
+    return (size_t)n;
+}
+
+std::vector<size_t> DeviceKmerCounter::abundance_histogram(size_t max_count) {
+    flush_codes();
+    counting_ = true;
+    std::vector<uint64_t> seen(max_count + 1, 0);
+    check(pg_kmer_counter_histogram(dev(handle_), max_count, seen.data()), "pg_kmer_counter_histogram");
+    return std::vector<size_t>(seen.begin(), seen.end());
+}
+
+void DeviceKmerCounter::reset_counts() {
+    flush_codes();
+    counting_ = true;
+    fetched_.store(false);
+    check(pg_kmer_counter_reset_counts(dev(handle_)), "pg_kmer_counter_reset_counts");
+}
+
+size_t for_each_read_batch(const std::string& readfile, const std::function<void(std::string_view)>& sink, size_t batch_bytes) {
+    std::string text;
+    text.reserve(batch_bytes + (1u << 16));
+    size_t total = 0;
+    auto flush = [&]() { total += text.size(); sink(text); text.clear(); };
+    stream_sequences(readfile, [&](const std::string& seq) {
+        text.append(seq);
+        text.push_back('\n');
+        if (text.size() >= batch_bytes) flush();
+    });
+    if (!text.empty()) flush();
+    return total;
+}
 
 void parse_kmer_line(std::string line, std::string& chrom, size_t& start, std::vector<std::string>& kmers,
                      std::vector<std::string>& flanking_kmers, bool& is_header) {

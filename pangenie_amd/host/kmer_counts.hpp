@@ -1,6 +1,7 @@
 // kmer_counts.hpp — the step that turns an index into a sample's input: read k-mer counts and local coverage of every
 // variant (reference fill_read_kmercounts, src/commands.cpp:74-139; src/kmerparser.cpp; src/kmercounter.hpp) —
-// SURVEY.md §8(f)-3.  Host code; not on the GPU path (hash lookups and text parsing).
+// SURVEY.md §8(f)-3.  Host code (hash lookups and text parsing), except DeviceKmerCounter: the same counts with the table
+// and the counting on the GPU (include/pangenie_kmers.h), the reader alone on the host.
 //
 // The reference's count source is Jellyfish (third party, pinned jellyfish=2.2.10 in environment.yml; not in this
 // image): JellyfishCounter runs `mer_counter` over the read file with canonical = true (src/jellyfishcounter.cpp:26-49),
@@ -15,8 +16,11 @@
 // region-reads.fa must give tests/data/region_UniqueKmersList.cereal (what tests/CommandsTest.cpp:59-93 feeds its HMM).
 #pragma once
 
+#include <atomic>
 #include <cstdint>
+#include <functional>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <string_view>
 #include <vector>
@@ -108,6 +112,54 @@ private:
     bool frozen_ = false;
     bool lenient_ = false;
 };
+
+/** TargetedKmerCounter with the table in HBM and the counting on the GPU (include/pangenie_kmers.h): the same
+ *  public interface, the same counts.  The reader stays on the host (gz, FASTA / FASTQ grammar) and writes the sequences of a
+ *  batch straight into a pinned staging buffer, which the device copies and counts while the reader fills the next one.
+ *  After counting, getKmerAbundance answers from a host copy of the table fetched once (on the first call, which may come
+ *  from any thread), so fill_read_kmercounts[_all] work with it unchanged.  Everything else is called from one thread. */
+class DeviceKmerCounter : public KmerCounter {
+public:
+    explicit DeviceKmerCounter(size_t kmer_size, bool unregistered_counts_zero = false, int device = 0);
+    ~DeviceKmerCounter() override;
+    DeviceKmerCounter(const DeviceKmerCounter&) = delete;
+    DeviceKmerCounter& operator=(const DeviceKmerCounter&) = delete;
+    void add_target(std::string_view kmer);
+    size_t add_targets_from_table(const std::string& kmers_tsv_gz);
+    size_t add_targets_from_sequences(const std::string& fasta);
+    void add_targets_of(std::string_view sequence);
+    /** `threads` is accepted for the interface's sake: one reader feeds the device */
+    void count(const std::string& readfile, unsigned threads = 1);
+    size_t getKmerAbundance(std::string kmer) override;
+    size_t targets();
+    std::vector<size_t> abundance_histogram(size_t max_count);
+    size_t kmers_seen();
+    /** zero counts and windows seen, keep the registered k-mers: the next sample over the same index */
+    void reset_counts();
+    /** the C handle (pg_kmer_counter*), for callers that go on with pg_kmer_counter_lookup */
+    void* handle() const { return handle_; }
+
+private:
+    bool encode_canonical(const char* s, uint64_t& code) const;
+    void flush_codes();
+    void fetch_table();
+    void check(int rc, const char* what) const;
+    static constexpr uint64_t kEmpty = ~0ull;
+    size_t k_;
+    bool lenient_;
+    void* handle_ = nullptr;
+    bool counting_ = false;               // the first count is behind us: no more targets
+    std::vector<uint64_t> codes_;         // add_target's codes, sent in blocks
+    std::vector<uint64_t> table_;         // host copy: key, count of slot i at [2i], [2i+1]
+    uint64_t cap_ = 0;
+    std::atomic<bool> fetched_{false};
+    std::mutex fetch_lock_;
+};
+
+/** The reader of the counters' count() on its own: the sequences of a FASTA / FASTQ file (plain or gzipped) in batches of
+ *  about `batch_bytes`, back to back with a newline after each, handed to `sink`; returns the bytes of all batches.  With a sink
+ *  that drops its batch this is the ceiling of any design with one host reader (tools/bench_kmer_counter.py). */
+size_t for_each_read_batch(const std::string& readfile, const std::function<void(std::string_view)>& sink, size_t batch_bytes = (size_t)4 << 20);
 
 /** one row of `<prefix>_<chromosome>_kmers.tsv(.gz)` — the reference's interface (src/kmerparser.hpp); implemented
  *  over an in-place column scanner (kmer_counts.cpp: KmerRow) */

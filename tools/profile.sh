@@ -8,7 +8,7 @@
 #            serialise the dispatches — ten minutes per workload on the cohorts; budget for it
 # usage: [SQ=1] [UNITS=1] tools/profile.sh <workload> <tag>
 #   <workload> = a main workload of bench.py (genome24_h64, chr22_h64, ...), `cohort_h64`, any key of bench.py's COHORTS_MORE
-#                (cohort_h16, cohort_h16m, cohort_h16w, cohort_h64m, cohort_h128, cohort_h17), `sampler` or `viterbi`
+#                (cohort_h16, cohort_h16m, cohort_h16w, cohort_h64m, cohort_h128, cohort_h17), `sampler`, `viterbi` or `kmers`
 # output: gpurun_out/<tag>_<workload>/ (raw, trimmed) and gpurun_out/profiles/<tag>_<workload>_{summary.txt,summary.json,kernel_stats.csv}
 #         — copy the latter into profiles/ (tracked).  Every summary under profiles/ of round 5 on was made by this script.
 set -u
@@ -26,6 +26,11 @@ case $W in
   cohort_*|panels_h16)   CMD="python bench.py --full --steps 3 --warmup 1 --cohort-only --cohort-key $W --no-cpu-baseline --no-sampler" ;;
   sampler)    CMD="python tools/bench_sampler.py --variants 40000 --paths 215 --size 15 --contigs 8 --cpu-variants 2000" ;;
   viterbi)    CMD="python tools/bench_viterbi.py" ;;
+  kmers)      # the device k-mer counter: the inputs are made first, untraced; the traced process is the C++ driver itself
+              KW=$(mktemp -d /tmp/pg_kmer_prof.XXXXXX); trap 'rm -rf "$KW"' EXIT
+              python tools/bench_kmer_counter.py --shape ${KMER_SHAPE:-full} --prepare-only --keep $KW > /dev/null || exit 1
+              export PG_KMER_BENCH_DEVICE_ONLY=1
+              CMD="tools/kmer_counter_bench.bin 31 $KW/idx_path_segments.fasta $KW/q_reads.fa $(ls $KW/idx_*_kmers.tsv.gz | tr '\n' ' ')" ;;
   *)          CMD="python bench.py --full --steps 3 --warmup 1 --workload $W --no-cpu-baseline --no-cohort --no-sampler --no-viterbi --no-dropin" ;;
 esac
 pass() { local name=$1; shift; timeout 900 rocprofv3 "$@" -d $OUT/$name -o ${name%%_*} --output-format csv -- $CMD > $OUT/$name.log 2>&1; }
