@@ -13,7 +13,7 @@ HIP_LIB = CSRC / "libpangenie_hmm.so"
 HIP_SOURCES = [CSRC / "pg_kernels.hip", CSRC / "pg_shim.cpp", CSRC / "pg_gather.cpp", CSRC / "pg_sampler.hip", CSRC / "pg_viterbi.hip",
                CSRC / "pg_kmers.hip"]
 HIP_DEPS = HIP_SOURCES + [CSRC / "pg_device.h", CSRC / "pg_devmath.h", CSRC / "pg_small16x.h", CSRC / "pg_experiments.h", CSRC / "pg_split.h", ROOT / "include" / "pangenie_hmm.h", ROOT / "include" / "pangenie_sampler.h",
-                          ROOT / "include" / "pangenie_kmers.h"]
+                          ROOT / "include" / "pangenie_kmers.h", ROOT / "include" / "pangenie_counts.h"]
 
 
 def _stale(target: Path, deps) -> bool:

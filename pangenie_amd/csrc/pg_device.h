@@ -21,6 +21,7 @@
 //   lik / lik_exp : outputs, one (mantissa, exponent) pair per genotype bin
 //   vit_*         : (run_phasing) Viterbi backtrace and haplotypes, see DevContig
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #define PG_AMAX 5                 // max distinct alleles on the selected paths of a NARROW column (table inside the record)
@@ -301,3 +302,21 @@ struct DevContig {
     double*   lik;             // [n_lik] mantissa in [0.5,1) or 0
     int32_t*  lik_exp;         // [n_lik] exponent: L = lik * 2^lik_exp
 };
+
+// ------------------------------------------------------------------------------------------------------------------
+//  The seam between the count plan (pg_kmers.hip owns the counter and the plan) and a cohort job (pg_shim.cpp owns pg_job):
+//  pg_count_plan_fill_job (include/pangenie_counts.h) writes one sample's arrays straight into the job.  Internal: not
+//  part of any public header, not exported.
+//   _begin: checks (cohort job on `device`, no upload in flight, sample in range, contig c has n_variants[c] and
+//           kmer_off[c]), makes `stream` (a hipStream_t) wait for the job's stream, and answers the device arrays of chains
+//           sample * n_contigs + c inside the set the next pg_job_run reads.
+//   _end:   the job's stream waits for `stream`, coverage[c] (host, n_variants[c] entries) becomes the host copy of those
+//           chains' coverage, and the results of the last run are invalidated (as pg_job_upload_end does).
+struct pg_job;
+extern "C" {
+__attribute__((visibility("hidden"))) int pgi_job_fill_begin(struct pg_job* job, uint32_t sample, int device, uint32_t n_contigs, const uint32_t* n_variants,
+                                                            const uint32_t* const* kmer_off, void* stream, uint16_t** d_kmer_count, uint16_t** d_coverage,
+                                                            char* err, size_t errlen);
+__attribute__((visibility("hidden"))) int pgi_job_fill_end(struct pg_job* job, uint32_t sample, uint32_t n_contigs, const uint16_t* const* coverage, void* stream,
+                                                          char* err, size_t errlen);
+}

@@ -17,8 +17,11 @@
 
 #include <algorithm>
 #include <new>
+#include <vector>
 
+#include "../../include/pangenie_counts.h"
 #include "../../include/pangenie_kmers.h"
+#include "pg_device.h"
 
 #define KK_BLOCK 256
 #define KK_WPL 16                     // windows per lane = letters per 16-byte chunk
@@ -241,6 +244,100 @@ __global__ __launch_bounds__(256) void kk_histogram(const Slot* __restrict__ slo
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < KK_HIST_LDS; i += blockDim.x)
         if (s_h[i]) atomicAdd(&hist[i], (unsigned long long)s_h[i]);
+}
+
+// ---------------------------------------------------------------------------------------------------- the count plan
+// (include/pangenie_counts.h).  Index level, once: kk_plan_resolve turns every code the index asks about into the index
+// of its slot.  Sample level: kk_plan_fill gathers the counts of those slots — no probing, no key is compared.
+#define KP_BLOCK 256
+#define KP_ROW 16                        // lanes that share a variant's flanking k-mers
+#define KP_ROWS (KP_BLOCK / KP_ROW)      // variants per workgroup of the coverage part
+template <class I> struct PlanIdx;
+template <> struct PlanIdx<uint32_t> { static constexpr uint32_t none = 0xFFFFFFFFu; };
+template <> struct PlanIdx<uint64_t> { static constexpr uint64_t none = ~0ull; };
+
+// One entry per contig and one behind the last (its k_blk0 / c_blk0 = the totals).  Blocks [0, k blocks) of the grid
+// take 256 unique k-mers each, the blocks behind them 16 variants each; a block finds its contig by bisection.
+struct PlanDesc {
+    uint64_t k_base;       // first entry of the contig in the list of unique k-mer slots
+    uint64_t v_base;       // first variant of the contig in the list of flank offsets
+    uint32_t k_blk0, c_blk0;
+    uint32_t n_k, n_v;
+    uint16_t* out_k;
+    uint16_t* out_c;
+};
+
+// ctr[0] = valid codes that are not in the table, ctr[1] = the smallest `first + i` among them
+template <class I>
+__global__ __launch_bounds__(KP_BLOCK) void kk_plan_resolve(const unsigned long long* __restrict__ codes, uint64_t n, uint64_t first,
+                                                            const Slot* __restrict__ slots, uint64_t cap, I* __restrict__ idx,
+                                                            unsigned long long* __restrict__ ctr) {
+    const uint64_t i = (uint64_t)blockIdx.x * KP_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long code = codes[i];
+    I answer = PlanIdx<I>::none;
+    if (code != KK_EMPTY) {   // (a k-mer with a letter outside ACGT: no slot, counts 0)
+        uint64_t at = slot_of(code, cap);
+        while (true) {
+            const unsigned long long key = slots[at].key;
+            if (key == code) { answer = (I)at; break; }
+            if (key == KK_EMPTY) break;
+            if (++at == cap) at = 0;
+        }
+        if (answer == PlanIdx<I>::none) {
+            atomicAdd(&ctr[0], 1ull);
+            atomicMin(&ctr[1], (unsigned long long)(first + i));
+        }
+    }
+    idx[i] = answer;
+}
+
+__device__ __forceinline__ uint32_t plan_contig_of(const PlanDesc* __restrict__ desc, uint32_t n_contigs, uint32_t block, bool cov) {
+    uint32_t lo = 0, hi = n_contigs;   // the last contig whose first block is not behind `block` (empty contigs share their successor's)
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if ((cov ? desc[mid].c_blk0 : desc[mid].k_blk0) <= block) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// One launch per sample for all contigs.  Unique k-mers: a lane per k-mer, one 8-byte load of the slot's count, 2-byte
+// stores side by side.  Coverage: a row of 16 lanes per variant — the row reads 16 consecutive slot indices (one 64-byte
+// piece) and has 16 gathers in flight, then sums over the row by shuffles; lists are a few dozen entries, so a lane per
+// variant would walk its list alone, index after index, with every lane of the wave in a different 64-byte piece.
+template <class I>
+__global__ __launch_bounds__(KP_BLOCK) void kk_plan_fill(const PlanDesc* __restrict__ desc, uint32_t n_contigs, uint32_t k_blocks,
+                                                         const I* __restrict__ kidx, const I* __restrict__ fidx,
+                                                         const unsigned long long* __restrict__ foff, const Slot* __restrict__ slots,
+                                                         uint64_t kmer_coverage) {
+    const uint32_t b = blockIdx.x;
+    if (b < k_blocks) {
+        const PlanDesc d = desc[plan_contig_of(desc, n_contigs, b, false)];
+        const uint64_t i = (uint64_t)(b - d.k_blk0) * KP_BLOCK + threadIdx.x;
+        if (i >= d.n_k) return;
+        const I at = kidx[d.k_base + i];
+        const unsigned long long count = at == PlanIdx<I>::none ? 0ull : slots[at].count;
+        d.out_k[i] = (uint16_t)count;   // (the cast of update_readcount(i, (unsigned short)...): it truncates)
+        return;
+    }
+    const uint32_t cb = b - k_blocks;
+    const PlanDesc d = desc[plan_contig_of(desc, n_contigs, cb, true)];
+    const uint32_t v = (cb - d.c_blk0) * KP_ROWS + threadIdx.x / KP_ROW, lane = threadIdx.x % KP_ROW;
+    if (v >= d.n_v) return;   // (whole rows leave: the shuffles below stay inside a row)
+    const uint64_t lo = foff[d.v_base + v], hi = foff[d.v_base + v + 1];
+    const uint64_t lowest = kmer_coverage / 4, highest = kmer_coverage * 4;
+    unsigned long long sum = 0, used = 0;
+    for (uint64_t j = lo + lane; j < hi; j += KP_ROW) {
+        const I at = fidx[j];
+        const unsigned long long count = at == PlanIdx<I>::none ? 0ull : slots[at].count;
+        if (count >= lowest && count <= highest) { sum += count; used += 1; }
+    }
+#pragma unroll
+    for (int m = KP_ROW / 2; m > 0; m >>= 1) {
+        sum += __shfl_xor(sum, m, KP_ROW);
+        used += __shfl_xor(used, m, KP_ROW);
+    }
+    if (lane == 0) d.out_c[v] = (uint16_t)((used && sum) ? sum / used : kmer_coverage);
 }
 
 struct Stage {
@@ -616,5 +713,335 @@ int pg_kmer_counter_count_resident(pg_kmer_counter* h, const char* text, uint64_
     if (e != hipSuccess) return hip_fail(e, "pg_kmer_counter_count_resident");
     return PG_OK;
 }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------- the count plan
+struct pg_count_plan {
+    pg_kmer_counter* counter = nullptr;
+    bool lenient = false, wide = false;          // wide: the table has 2^32 - 1 slots or more, slot indices take 64 bits
+    uint32_t nc = 0;
+    std::vector<uint32_t> n_variants;            // [nc]
+    std::vector<std::vector<uint32_t>> koff;     // [nc][V + 1] host copies: what pg_count_plan_fill_job compares with the job's
+    std::vector<PlanDesc> desc;                  // [nc + 1]; the output pointers are set by every fill
+    uint64_t n_k = 0, n_f = 0, n_v = 0, unresolved = 0, device_bytes = 0;
+    uint32_t k_blocks = 0, c_blocks = 0;
+    void* d_kidx = nullptr;                      // [n_k] slot of every unique k-mer, contig after contig
+    void* d_fidx = nullptr;                      // [n_f] ... of every flanking k-mer
+    unsigned long long* d_foff = nullptr;        // [n_v + 1] flanking k-mers of variant v (over all contigs): [d_foff[v], d_foff[v + 1])
+    PlanDesc* d_desc = nullptr;
+    uint16_t* d_out_k = nullptr;                 // pg_count_plan_fill_host's device arrays (allocated by its first call)
+    uint16_t* d_out_c = nullptr;
+    uint16_t* h_k = nullptr;                     // pinned: [n_k] (fill_host), [n_v] (fill_host, fill_job)
+    uint16_t* h_c = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double last_ms = 0.0;
+};
+
+namespace {
+
+constexpr uint64_t kPlanChunk = (uint64_t)1 << 24;   // codes resolved per launch: 128 MB of codes on the device at a time
+
+int plan_use(pg_count_plan* p, const char* who) {
+    if (!p) return fail(PG_ERR_INVALID, "%s: null plan", who);
+    if (int rc = use(p->counter)) return rc;
+    if (int rc = busy(p->counter, who)) return rc;
+    return sync_all(p->counter);   // everything submitted is counted
+}
+
+// `n` codes of one contig's list through the resolve kernel, a chunk at a time
+int plan_resolve(pg_count_plan* p, const uint64_t* codes, uint64_t n, uint64_t base, bool flanks, unsigned long long* d_codes, unsigned long long* d_ctr) {
+    pg_kmer_counter* h = p->counter;
+    for (uint64_t at = 0; at < n; at += kPlanChunk) {
+        const uint64_t m = std::min<uint64_t>(kPlanChunk, n - at);
+        KK_TRY(hipMemcpyAsync(d_codes, codes + at, m * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+        const dim3 grid((uint32_t)((m + KP_BLOCK - 1) / KP_BLOCK));
+        unsigned long long* ctr = d_ctr + (flanks ? 2 : 0);
+        if (p->wide) {
+            uint64_t* idx = (uint64_t*)(flanks ? p->d_fidx : p->d_kidx) + base + at;
+            hipLaunchKernelGGL(kk_plan_resolve<uint64_t>, grid, dim3(KP_BLOCK), 0, h->stream, d_codes, m, base + at, h->slots, h->cap, idx, ctr);
+        } else {
+            uint32_t* idx = (uint32_t*)(flanks ? p->d_fidx : p->d_kidx) + base + at;
+            hipLaunchKernelGGL(kk_plan_resolve<uint32_t>, grid, dim3(KP_BLOCK), 0, h->stream, d_codes, m, base + at, h->slots, h->cap, idx, ctr);
+        }
+        KK_TRY(hipGetLastError());
+        KK_TRY(hipStreamSynchronize(h->stream));   // (d_codes is free for the next chunk; a pageable source has been read)
+    }
+    return PG_OK;
+}
+
+// descriptors (with this fill's output pointers) to the device, the kernel between the two events
+int plan_launch(pg_count_plan* p, uint64_t kmer_coverage) {
+    pg_kmer_counter* h = p->counter;
+    const uint32_t blocks = p->k_blocks + p->c_blocks;
+    p->last_ms = 0.0;
+    if (blocks == 0) return PG_OK;
+    KK_TRY(hipMemcpyAsync(p->d_desc, p->desc.data(), p->desc.size() * sizeof(PlanDesc), hipMemcpyHostToDevice, h->stream));
+    KK_TRY(hipEventRecord(p->ev[0], h->stream));
+    if (p->wide)
+        hipLaunchKernelGGL(kk_plan_fill<uint64_t>, dim3(blocks), dim3(KP_BLOCK), 0, h->stream, p->d_desc, p->nc, p->k_blocks, (const uint64_t*)p->d_kidx,
+                           (const uint64_t*)p->d_fidx, p->d_foff, h->slots, kmer_coverage);
+    else
+        hipLaunchKernelGGL(kk_plan_fill<uint32_t>, dim3(blocks), dim3(KP_BLOCK), 0, h->stream, p->d_desc, p->nc, p->k_blocks, (const uint32_t*)p->d_kidx,
+                           (const uint32_t*)p->d_fidx, p->d_foff, h->slots, kmer_coverage);
+    KK_TRY(hipGetLastError());
+    KK_TRY(hipEventRecord(p->ev[1], h->stream));
+    return PG_OK;
+}
+int plan_finish(pg_count_plan* p) {
+    KK_TRY(hipStreamSynchronize(p->counter->stream));
+    if (p->k_blocks + p->c_blocks) {
+        float ms = 0.f;
+        KK_TRY(hipEventElapsedTime(&ms, p->ev[0], p->ev[1]));
+        p->last_ms = ms;
+    }
+    return PG_OK;
+}
+
+// where entry `flat` of the concatenated lists lies: contig, variant, position inside the variant's list
+template <class Off>
+void plan_locate(const pg_count_plan* p, const pg_count_contig* contigs, bool flanks, uint64_t flat, uint32_t* c_out, uint32_t* v_out, uint64_t* at_out) {
+    uint64_t base = 0;
+    for (uint32_t c = 0; c < p->nc; ++c) {
+        const uint32_t V = contigs[c].n_variants;
+        const Off* off = flanks ? (const Off*)(const void*)contigs[c].flank_off : (const Off*)(const void*)contigs[c].kmer_off;
+        const uint64_t n = V ? (uint64_t)off[V] : 0;
+        if (flat < base + n) {
+            const uint64_t local = flat - base;
+            const uint32_t v = (uint32_t)(std::upper_bound(off, off + V + 1, (Off)local) - off) - 1;
+            *c_out = c; *v_out = v; *at_out = local - off[v];
+            return;
+        }
+        base += n;
+    }
+    *c_out = *v_out = 0; *at_out = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pg_count_plan_destroy(pg_count_plan* p) {
+    if (!p) return PG_OK;
+    if (p->counter) (void)hipSetDevice(p->counter->device);
+    if (p->counter && p->counter->stream) (void)hipStreamSynchronize(p->counter->stream);
+    for (void* d : {p->d_kidx, p->d_fidx, (void*)p->d_foff, (void*)p->d_desc, (void*)p->d_out_k, (void*)p->d_out_c})
+        if (d) (void)hipFree(d);
+    if (p->h_k) (void)hipHostFree(p->h_k);
+    if (p->h_c) (void)hipHostFree(p->h_c);
+    for (hipEvent_t e : p->ev) if (e) (void)hipEventDestroy(e);
+    delete p;
+    return PG_OK;
+}
+
+int pg_count_plan_new(pg_kmer_counter* counter, uint32_t n_contigs, const pg_count_contig* contigs, int unregistered_counts_zero, pg_count_plan** out) {
+    if (!out) return fail(PG_ERR_INVALID, "pg_count_plan_new: null out");
+    *out = nullptr;
+    if (!counter) return fail(PG_ERR_INVALID, "pg_count_plan_new: null counter");
+    if (n_contigs && !contigs) return fail(PG_ERR_INVALID, "pg_count_plan_new: null contigs");
+    // everything the host can decide, before any device call
+    const uint32_t k = counter->k;
+    uint64_t n_k = 0, n_f = 0, n_v = 0, k_blocks = 0, c_blocks = 0;
+    for (uint32_t c = 0; c < n_contigs; ++c) {
+        const pg_count_contig& g = contigs[c];
+        const uint32_t V = g.n_variants;
+        uint64_t nk = 0, nf = 0;
+        if (V) {
+            if (!g.kmer_off || !g.flank_off) return fail(PG_ERR_INVALID, "pg_count_plan_new: contig %u has %u variants and a null offset array", c, V);
+            if (g.kmer_off[0] != 0 || g.flank_off[0] != 0) return fail(PG_ERR_INVALID, "pg_count_plan_new: contig %u: offsets must start at 0", c);
+            for (uint32_t v = 0; v < V; ++v)
+                if (g.kmer_off[v + 1] < g.kmer_off[v] || g.flank_off[v + 1] < g.flank_off[v])
+                    return fail(PG_ERR_INVALID, "pg_count_plan_new: contig %u: offsets decrease at variant %u", c, v);
+            nk = g.kmer_off[V];
+            nf = g.flank_off[V];
+        }
+        if ((nk && !g.kmer_code) || (nf && !g.flank_code)) return fail(PG_ERR_INVALID, "pg_count_plan_new: contig %u has a null code array", c);
+        if (k < 32) {
+            const uint64_t limit = 1ull << (2 * k);
+            for (int pass = 0; pass < 2; ++pass) {
+                const uint64_t* codes = pass ? g.flank_code : g.kmer_code;
+                const uint64_t n = pass ? nf : nk;
+                for (uint64_t i = 0; i < n; ++i)
+                    if (codes[i] >= limit && codes[i] != KK_EMPTY)
+                        return fail(PG_ERR_INVALID, "pg_count_plan_new: contig %u: %s code %llu at %llu is no %u-mer", c, pass ? "flanking" : "unique",
+                                    (unsigned long long)codes[i], (unsigned long long)i, k);
+            }
+        }
+        n_k += nk; n_f += nf; n_v += V;
+        k_blocks += (nk + KP_BLOCK - 1) / KP_BLOCK;
+        c_blocks += ((uint64_t)V + KP_ROWS - 1) / KP_ROWS;
+    }
+    if (k_blocks + c_blocks > 0x7FFFFFFFull) return fail(PG_ERR_UNSUPPORTED, "pg_count_plan_new: %llu k-mers and %llu variants are more than one launch takes",
+                                                          (unsigned long long)n_k, (unsigned long long)n_v);
+    if (int rc = use(counter)) return rc;
+    if (int rc = pg_kmer_counter_freeze(counter)) return rc;
+    pg_count_plan* p = new (std::nothrow) pg_count_plan;
+    if (!p) return fail(PG_ERR_NOMEM, "pg_count_plan_new: out of host memory");
+    p->counter = counter;
+    p->lenient = unregistered_counts_zero != 0;
+    p->wide = counter->cap > 0xFFFFFFFFull;   // (slot indices up to cap - 1 and the sentinel 2^32 - 1)
+    p->nc = n_contigs;
+    p->n_k = n_k; p->n_f = n_f; p->n_v = n_v;
+    p->k_blocks = (uint32_t)k_blocks; p->c_blocks = (uint32_t)c_blocks;
+    p->n_variants.resize(n_contigs);
+    p->koff.resize(n_contigs);
+    p->desc.assign((size_t)n_contigs + 1, PlanDesc{});
+    std::vector<unsigned long long> foff((size_t)n_v + 1, 0);
+    {
+        uint64_t kb = 0, fb = 0, vb = 0;
+        uint32_t kblk = 0, cblk = 0;
+        for (uint32_t c = 0; c < n_contigs; ++c) {
+            const pg_count_contig& g = contigs[c];
+            const uint32_t V = g.n_variants;
+            p->n_variants[c] = V;
+            if (V) p->koff[c].assign(g.kmer_off, g.kmer_off + V + 1);
+            PlanDesc& d = p->desc[c];
+            d.k_base = kb; d.v_base = vb; d.k_blk0 = kblk; d.c_blk0 = cblk;
+            d.n_k = V ? g.kmer_off[V] : 0; d.n_v = V;
+            for (uint32_t v = 0; v < V; ++v) foff[vb + v] = fb + g.flank_off[v];
+            kb += d.n_k; fb += V ? g.flank_off[V] : 0; vb += V;
+            kblk += (uint32_t)(((uint64_t)d.n_k + KP_BLOCK - 1) / KP_BLOCK);
+            cblk += (V + KP_ROWS - 1) / KP_ROWS;
+        }
+        foff[n_v] = fb;
+        PlanDesc& end = p->desc[n_contigs];
+        end.k_base = kb; end.v_base = vb; end.k_blk0 = kblk; end.c_blk0 = cblk;
+    }
+    const size_t isz = p->wide ? 8 : 4;
+    unsigned long long* d_codes = nullptr;
+    unsigned long long* d_ctr = nullptr;
+    auto body = [&]() -> int {
+        KK_TRY(hipEventCreate(&p->ev[0]));
+        KK_TRY(hipEventCreate(&p->ev[1]));
+        KK_TRY(hipMalloc(&p->d_kidx, std::max<uint64_t>(n_k, 1) * isz));
+        KK_TRY(hipMalloc(&p->d_fidx, std::max<uint64_t>(n_f, 1) * isz));
+        KK_TRY(hipMalloc((void**)&p->d_foff, foff.size() * sizeof(unsigned long long)));
+        KK_TRY(hipMalloc((void**)&p->d_desc, p->desc.size() * sizeof(PlanDesc)));
+        KK_TRY(hipHostMalloc((void**)&p->h_c, std::max<uint64_t>(n_v, 1) * 2, hipHostMallocDefault));
+        p->device_bytes = (n_k + n_f) * isz + foff.size() * sizeof(unsigned long long) + p->desc.size() * sizeof(PlanDesc);
+        uint64_t longest = 1;
+        for (uint32_t c = 0; c < n_contigs; ++c) longest = std::max<uint64_t>(longest, std::max<uint64_t>(p->desc[c].n_k, foff[p->desc[c + 1].v_base] - foff[p->desc[c].v_base]));
+        KK_TRY(hipMalloc((void**)&d_codes, std::min<uint64_t>(longest, kPlanChunk) * sizeof(unsigned long long)));
+        KK_TRY(hipMalloc((void**)&d_ctr, 4 * sizeof(unsigned long long)));
+        unsigned long long ctr[4] = {0ull, KK_EMPTY, 0ull, KK_EMPTY};
+        KK_TRY(hipMemcpyAsync(d_ctr, ctr, sizeof ctr, hipMemcpyHostToDevice, counter->stream));
+        KK_TRY(hipMemcpyAsync(p->d_foff, foff.data(), foff.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, counter->stream));
+        KK_TRY(hipStreamSynchronize(counter->stream));
+        for (uint32_t c = 0; c < n_contigs; ++c) {
+            const PlanDesc& d = p->desc[c];
+            if (int rc = plan_resolve(p, contigs[c].kmer_code, d.n_k, d.k_base, false, d_codes, d_ctr)) return rc;
+            const uint64_t f0 = foff[d.v_base], f1 = foff[p->desc[c + 1].v_base];
+            if (int rc = plan_resolve(p, contigs[c].flank_code, f1 - f0, f0, true, d_codes, d_ctr)) return rc;
+        }
+        KK_TRY(hipMemcpyAsync(ctr, d_ctr, sizeof ctr, hipMemcpyDeviceToHost, counter->stream));
+        KK_TRY(hipStreamSynchronize(counter->stream));
+        p->unresolved = ctr[0] + ctr[2];
+        if (p->unresolved && !p->lenient) {
+            // the first one in index order: contig, then variant, then the variant's unique k-mers in front of its flanking ones
+            uint32_t c[2] = {~0u, ~0u}, v[2] = {~0u, ~0u};
+            uint64_t at[2] = {0, 0};
+            if (ctr[0]) plan_locate<uint32_t>(p, contigs, false, ctr[1], &c[0], &v[0], &at[0]);
+            if (ctr[2]) plan_locate<uint64_t>(p, contigs, true, ctr[3], &c[1], &v[1], &at[1]);
+            const int w = (c[1] < c[0] || (c[1] == c[0] && v[1] < v[0])) ? 1 : 0;
+            const uint64_t code = w ? contigs[c[w]].flank_code[contigs[c[w]].flank_off[v[w]] + at[w]] : contigs[c[w]].kmer_code[contigs[c[w]].kmer_off[v[w]] + at[w]];
+            return fail(PG_ERR_INVALID, "pg_count_plan_new: contig %u, variant %u, %s k-mer %llu (code %llu) was not registered before the reads were counted (%llu such codes)",
+                        c[w], v[w], w ? "flanking" : "unique", (unsigned long long)at[w], (unsigned long long)code, (unsigned long long)p->unresolved);
+        }
+        return PG_OK;
+    };
+    const int rc = body();
+    if (d_codes) (void)hipFree(d_codes);
+    if (d_ctr) (void)hipFree(d_ctr);
+    if (rc != PG_OK) { pg_count_plan_destroy(p); return rc; }
+    *out = p;
+    return PG_OK;
+}
+
+int pg_count_plan_fill_host(pg_count_plan* p, uint64_t kmer_coverage, uint16_t* const* kmer_count, uint16_t* const* coverage) {
+    if (!p) return fail(PG_ERR_INVALID, "pg_count_plan_fill_host: null plan");
+    if (p->nc && (!kmer_count || !coverage)) return fail(PG_ERR_INVALID, "pg_count_plan_fill_host: null argument");
+    for (uint32_t c = 0; c < p->nc; ++c)
+        if ((p->desc[c].n_k && !kmer_count[c]) || (p->desc[c].n_v && !coverage[c])) return fail(PG_ERR_INVALID, "pg_count_plan_fill_host: contig %u has a null array", c);
+    if (int rc = plan_use(p, "pg_count_plan_fill_host")) return rc;
+    // (each of the three on its own: a call that failed half way leaves the rest to the next one)
+    if (!p->d_out_k) { KK_TRY(hipMalloc((void**)&p->d_out_k, std::max<uint64_t>(p->n_k, 1) * 2)); p->device_bytes += p->n_k * 2; }
+    if (!p->d_out_c) { KK_TRY(hipMalloc((void**)&p->d_out_c, std::max<uint64_t>(p->n_v, 1) * 2)); p->device_bytes += p->n_v * 2; }
+    if (!p->h_k) KK_TRY(hipHostMalloc((void**)&p->h_k, std::max<uint64_t>(p->n_k, 1) * 2, hipHostMallocDefault));
+    for (uint32_t c = 0; c < p->nc; ++c) {
+        p->desc[c].out_k = p->d_out_k + p->desc[c].k_base;
+        p->desc[c].out_c = p->d_out_c + p->desc[c].v_base;
+    }
+    if (int rc = plan_launch(p, kmer_coverage)) return rc;
+    hipStream_t s = p->counter->stream;
+    if (p->n_k) KK_TRY(hipMemcpyAsync(p->h_k, p->d_out_k, p->n_k * 2, hipMemcpyDeviceToHost, s));
+    if (p->n_v) KK_TRY(hipMemcpyAsync(p->h_c, p->d_out_c, p->n_v * 2, hipMemcpyDeviceToHost, s));
+    if (int rc = plan_finish(p)) return rc;
+    for (uint32_t c = 0; c < p->nc; ++c) {
+        const PlanDesc& d = p->desc[c];
+        if (d.n_k) memcpy(kmer_count[c], p->h_k + d.k_base, (size_t)d.n_k * 2);
+        if (d.n_v) memcpy(coverage[c], p->h_c + d.v_base, (size_t)d.n_v * 2);
+    }
+    return PG_OK;
+}
+
+int pg_count_plan_fill_device(pg_count_plan* p, uint64_t kmer_coverage, uint16_t* const* d_kmer_count, uint16_t* const* d_coverage) {
+    if (!p) return fail(PG_ERR_INVALID, "pg_count_plan_fill_device: null plan");
+    if (p->nc && (!d_kmer_count || !d_coverage)) return fail(PG_ERR_INVALID, "pg_count_plan_fill_device: null argument");
+    for (uint32_t c = 0; c < p->nc; ++c)
+        if ((p->desc[c].n_k && !d_kmer_count[c]) || (p->desc[c].n_v && !d_coverage[c])) return fail(PG_ERR_INVALID, "pg_count_plan_fill_device: contig %u has a null array", c);
+    if (int rc = plan_use(p, "pg_count_plan_fill_device")) return rc;
+    for (uint32_t c = 0; c < p->nc; ++c) {   // a host pointer would fault the kernel: refused here
+        for (int which = 0; which < 2; ++which) {
+            const void* ptr = which ? (const void*)d_coverage[c] : (const void*)d_kmer_count[c];
+            if (!(which ? p->desc[c].n_v : p->desc[c].n_k)) continue;
+            hipPointerAttribute_t at;
+            if (hipPointerGetAttributes(&at, ptr) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != p->counter->device) {
+                (void)hipGetLastError();
+                return fail(PG_ERR_INVALID, "pg_count_plan_fill_device: contig %u: the %s array is not in the memory of device %d", c, which ? "coverage" : "kmer_count", p->counter->device);
+            }
+        }
+        p->desc[c].out_k = d_kmer_count[c];
+        p->desc[c].out_c = d_coverage[c];
+    }
+    if (int rc = plan_launch(p, kmer_coverage)) return rc;
+    return plan_finish(p);
+}
+
+int pg_count_plan_fill_job(pg_count_plan* p, uint64_t kmer_coverage, pg_job* job, uint32_t sample, char* err, size_t errlen) {
+    auto said = [&](int rc) { if (rc != PG_OK && err && errlen) snprintf(err, errlen, "%s", g_err); return rc; };
+    if (err && errlen) err[0] = 0;
+    if (!p) return said(fail(PG_ERR_INVALID, "pg_count_plan_fill_job: null plan"));
+    if (!job) return said(fail(PG_ERR_INVALID, "pg_count_plan_fill_job: null job"));
+    if (int rc = plan_use(p, "pg_count_plan_fill_job")) return said(rc);
+    std::vector<const uint32_t*> koff(p->nc);
+    std::vector<uint16_t*> d_k(p->nc), d_c(p->nc);
+    for (uint32_t c = 0; c < p->nc; ++c) koff[c] = p->koff[c].data();
+    char text[400] = "";
+    hipStream_t s = p->counter->stream;
+    if (int rc = pgi_job_fill_begin(job, sample, p->counter->device, p->nc, p->n_variants.data(), koff.data(), (void*)s, d_k.data(), d_c.data(), text, sizeof text))
+        return said(fail(rc, "pg_count_plan_fill_job: %s", text));
+    for (uint32_t c = 0; c < p->nc; ++c) { p->desc[c].out_k = d_k[c]; p->desc[c].out_c = d_c[c]; }
+    if (int rc = plan_launch(p, kmer_coverage)) return said(rc);
+    std::vector<const uint16_t*> cov(p->nc);
+    for (uint32_t c = 0; c < p->nc; ++c) {   // the job keeps a host copy of every chain's coverage: 2 bytes per variant come back
+        const PlanDesc& d = p->desc[c];
+        cov[c] = p->h_c + d.v_base;
+        if (d.n_v) { const hipError_t e = hipMemcpyAsync(p->h_c + d.v_base, d_c[c], (size_t)d.n_v * 2, hipMemcpyDeviceToHost, s); if (e != hipSuccess) return said(hip_fail(e, "pg_count_plan_fill_job")); }
+    }
+    if (int rc = plan_finish(p)) return said(rc);
+    if (int rc = pgi_job_fill_end(job, sample, p->nc, cov.data(), (void*)s, text, sizeof text)) return said(fail(rc, "pg_count_plan_fill_job: %s", text));
+    return PG_OK;
+}
+
+int pg_count_plan_stats(const pg_count_plan* p, uint64_t* n_kmers, uint64_t* n_flanks, uint64_t* unresolved, uint64_t* device_bytes) {
+    if (!p) return fail(PG_ERR_INVALID, "pg_count_plan_stats: null plan");
+    if (n_kmers) *n_kmers = p->n_k;
+    if (n_flanks) *n_flanks = p->n_f;
+    if (unresolved) *unresolved = p->unresolved;
+    if (device_bytes) *device_bytes = p->device_bytes;
+    return PG_OK;
+}
+
+double pg_count_plan_last_fill_ms(const pg_count_plan* p) { return p ? p->last_ms : 0.0; }
 
 }  // extern "C"

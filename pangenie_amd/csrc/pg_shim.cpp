@@ -509,6 +509,7 @@ struct pg_job {
     int upload_rc = PG_OK;
     std::string upload_err;
     std::vector<std::vector<uint16_t>> next_coverage;   // host copies of the pending batch's coverage arrays
+    hipEvent_t ev_fill = nullptr;             // orders a count plan's stream against the job's (pgi_job_fill_begin / _end; made by the first fill)
 };
 
 extern "C" void pg_job_destroy(pg_job* job) {
@@ -518,6 +519,7 @@ extern "C" void pg_job_destroy(pg_job* job) {
     for (auto& t : job->late_threads) if (t.joinable()) t.join();
     if (job->ev_late_made) { hipEventDestroy(job->ev_late[0]); hipEventDestroy(job->ev_late[1]); }
     if (job->copy_stream) { hipStreamSynchronize(job->copy_stream); hipStreamDestroy(job->copy_stream); }
+    if (job->ev_fill) hipEventDestroy(job->ev_fill);
     if (job->staging) hipHostFree(job->staging);
     if (job->alt_samples) hipFree(job->alt_samples);
     if (job->d_contigs_owned) hipFree(job->d_contigs_owned);
@@ -1764,6 +1766,50 @@ extern "C" int pg_job_upload_end(pg_job* job, char* err, size_t errlen) {
     for (size_t c = 0; c < job->chains.size(); ++c) {
         job->chains[c].coverage.swap(job->next_coverage[c]);
         job->chains[c].d = job->h_contigs[c];
+    }
+    job->ran = false;
+    return PG_OK;
+}
+
+// One sample's arrays written by a kernel of the count plan instead of an upload (pg_device.h: the seam to pg_kmers.hip).
+extern "C" int pgi_job_fill_begin(pg_job* job, uint32_t sample, int device, uint32_t n_contigs, const uint32_t* n_variants,
+                                  const uint32_t* const* kmer_off, void* stream, uint16_t** d_kmer_count, uint16_t** d_coverage,
+                                  char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    if (!job->cohort) { set_err(err, errlen, "not a cohort job"); return PG_ERR_INVALID; }
+    if (job->upload_pending) { set_err(err, errlen, "an asynchronous upload is in flight: call pg_job_upload_end first"); return PG_ERR_INVALID; }
+    if (job->device != device) { set_err(err, errlen, "the job is on device %d, the counter on device %d", job->device, device); return PG_ERR_INVALID; }
+    if (sample >= job->n_samples) { set_err(err, errlen, "sample %u of %u", sample, job->n_samples); return PG_ERR_INVALID; }
+    if (n_contigs != job->n_contigs) { set_err(err, errlen, "the plan has %u contigs, the job %u", n_contigs, job->n_contigs); return PG_ERR_INVALID; }
+    for (uint32_t c = 0; c < n_contigs; ++c) {
+        const IndexHost& x = job->index[c];
+        if (n_variants[c] != x.V || (x.V && memcmp(kmer_off[c], x.koff.data(), ((size_t)x.V + 1) * 4) != 0)) {
+            set_err(err, errlen, "contig %u: variants or k-mers per variant of the plan differ from the resident job", c);
+            return PG_ERR_INVALID;
+        }
+    }
+    HIP_TRY(hipSetDevice(job->device));
+    if (!job->ev_fill) HIP_TRY(hipEventCreateWithFlags(&job->ev_fill, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(job->ev_fill, job->stream));
+    HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, job->ev_fill, 0));
+    // from here on the chains' arrays are being rewritten: whatever happens to the fill, the results of the last run no
+    // longer belong to the inputs the job holds
+    job->ran = false;
+    for (uint32_t c = 0; c < n_contigs; ++c) {
+        const ChainHost& ch = job->chains[(size_t)sample * n_contigs + c];
+        d_kmer_count[c] = (uint16_t*)(job->cur_samples + (ch.o_kcnt - job->sample_lo));
+        d_coverage[c] = (uint16_t*)(job->cur_samples + (ch.o_cov - job->sample_lo));
+    }
+    return PG_OK;
+}
+
+extern "C" int pgi_job_fill_end(pg_job* job, uint32_t sample, uint32_t n_contigs, const uint16_t* const* coverage, void* stream,
+                                char* err, size_t errlen) {
+    HIP_TRY(hipEventRecord(job->ev_fill, (hipStream_t)stream));   // (the event _begin made)
+    HIP_TRY(hipStreamWaitEvent(job->stream, job->ev_fill, 0));
+    for (uint32_t c = 0; c < n_contigs; ++c) {
+        const uint32_t V = job->index[c].V;
+        if (V) job->chains[(size_t)sample * n_contigs + c].coverage.assign(coverage[c], coverage[c] + V);
     }
     job->ran = false;
     return PG_OK;

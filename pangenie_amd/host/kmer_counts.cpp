@@ -1,6 +1,7 @@
 // kmer_counts.cpp — see kmer_counts.hpp.
 #include "kmer_counts.hpp"
 
+#include "../../include/pangenie_counts.h"
 #include "../../include/pangenie_kmers.h"
 
 #include <zlib.h>
@@ -762,6 +763,146 @@ void DeviceKmerCounter::reset_counts() {
     fetched_.store(false);
     check(pg_kmer_counter_reset_counts(dev(handle_)), "pg_kmer_counter_reset_counts");
 }
+
+// ------------------------------------------------------------------ DeviceCountPlan
+namespace {
+inline pg_count_plan* plan_of(void* h) { return static_cast<pg_count_plan*>(h); }
+// canonical code of a k-mer of the table; PG_KMER_NOT_REGISTERED for one with a letter outside ACGT
+uint64_t table_code(std::string_view kmer, size_t k) {
+    if (kmer.size() != k) throw std::runtime_error("DeviceCountPlan: k-mer of length " + std::to_string(kmer.size()) + ", counter holds " + std::to_string(k) + "-mers");
+    uint64_t fwd = 0, rev = 0;
+    for (size_t i = 0; i < k; ++i) {
+        const int b = base_code(kmer[i]);
+        if (b < 0) return PG_KMER_NOT_REGISTERED;
+        fwd = (fwd << 2) | (uint64_t)b;
+        rev = (rev >> 2) | ((uint64_t)(3 - b) << (2 * (k - 1)));
+    }
+    return fwd < rev ? fwd : rev;
+}
+}  // namespace
+
+DeviceCountPlan::DeviceCountPlan(DeviceKmerCounter& counter, UniqueKmersMap& index, const std::string& prefix, bool register_targets) {
+    const size_t k = index.kmersize;
+    struct Lists { std::vector<uint32_t> koff{0}; std::vector<uint64_t> kcode, foff{0}, fcode; };
+    std::vector<Lists> lists;
+    for (auto& kv : index.unique_kmers) {
+        const std::string& chromosome = kv.first;
+        const auto& objects = kv.second;
+        names_.push_back(chromosome);
+        lists.emplace_back();
+        Lists& l = lists.back();
+        const std::string path = prefix + "_" + chromosome + "_kmers.tsv.gz";
+        gzFile file = gzopen(path.c_str(), "rb");
+        if (!file) throw std::runtime_error("DeviceCountPlan: kmer file cannot be opened.");
+        std::vector<char> buf(1u << 16);
+        std::string line;
+        size_t var_index = 0;
+        try {
+            while (gzgets(file, buf.data(), (int)buf.size()) != nullptr) {
+                line += buf.data();
+                if (line.empty() || line.back() != '\n') continue;
+                line.pop_back();
+                const KmerRow row(line);
+                if (!row.header) {
+                    if (row.column[0] != chromosome) throw std::runtime_error("DeviceCountPlan: line of chromosome " + std::string(row.column[0]) + " in the table of " + chromosome);
+                    if (var_index >= objects.size()) throw std::runtime_error("DeviceCountPlan: more lines than variants");
+                    const UniqueKmers& u = *objects[var_index];
+                    if (row.start() != u.get_variant_position()) throw std::runtime_error("DeviceCountPlan: position " + std::to_string(row.start()) + " does not match the index");
+                    KmerRow::each_item(row.column[3], [&](std::string_view s) { l.kcode.push_back(table_code(s, k)); });
+                    KmerRow::each_item(row.column[4], [&](std::string_view s) { l.fcode.push_back(table_code(s, k)); });
+                    if (l.kcode.size() - l.koff.back() != u.size())
+                        throw std::runtime_error("DeviceCountPlan: " + std::to_string(l.kcode.size() - l.koff.back()) + " unique k-mers at position " + std::to_string(row.start()) +
+                                                 " of " + chromosome + ", the index holds " + std::to_string(u.size()));
+                    if (l.kcode.size() > 0xFFFFFFFFull) throw std::runtime_error("DeviceCountPlan: more than 2^32 - 1 unique k-mers on " + chromosome);
+                    l.koff.push_back((uint32_t)l.kcode.size());
+                    l.foff.push_back(l.fcode.size());
+                    var_index += 1;
+                }
+                line.clear();
+            }
+        } catch (...) {
+            gzclose(file);
+            throw;
+        }
+        gzclose(file);
+        if (var_index != objects.size()) throw std::runtime_error("DeviceCountPlan: fewer lines than variants (" + std::to_string(var_index) + " of " + std::to_string(objects.size()) + " on " + chromosome + ")");
+        n_kmers_.push_back(l.kcode.size());
+        n_variants_.push_back(objects.size());
+    }
+    if (register_targets) {
+        if (counter.counting_) throw std::runtime_error("DeviceKmerCounter: targets must be registered before the reads are counted");
+        counter.flush_codes();
+        std::vector<uint64_t> valid;
+        for (const Lists& l : lists)
+            for (const std::vector<uint64_t>* codes : {&l.kcode, &l.fcode}) {
+                valid.clear();
+                for (const uint64_t c : *codes) if (c != PG_KMER_NOT_REGISTERED) valid.push_back(c);
+                if (!valid.empty()) counter.check(pg_kmer_counter_add_codes(dev(counter.handle_), valid.data(), valid.size()), "pg_kmer_counter_add_codes");
+            }
+    }
+    counter.flush_codes();
+    counter.counting_ = true;   // (the plan freezes the table: as after a first count)
+    std::vector<pg_count_contig> contigs(lists.size());
+    for (size_t c = 0; c < lists.size(); ++c) {
+        const Lists& l = lists[c];
+        contigs[c].n_variants = (uint32_t)n_variants_[c];
+        contigs[c].kmer_off = l.koff.data();
+        contigs[c].kmer_code = l.kcode.data();
+        contigs[c].flank_off = l.foff.data();
+        contigs[c].flank_code = l.fcode.data();
+    }
+    pg_count_plan* plan = nullptr;
+    const int rc = pg_count_plan_new(dev(counter.handle_), (uint32_t)contigs.size(), contigs.data(), counter.lenient_ ? 1 : 0, &plan);
+    if (rc != PG_OK) throw std::runtime_error(std::string("DeviceCountPlan: pg_count_plan_new failed (") + std::to_string(rc) + "): " + pg_kmer_last_error());
+    handle_ = plan;
+}
+
+DeviceCountPlan::~DeviceCountPlan() { pg_count_plan_destroy(plan_of(handle_)); }
+
+SampleCounts DeviceCountPlan::fill(size_t kmer_coverage) {
+    SampleCounts out;
+    std::vector<uint16_t*> kc(names_.size()), cv(names_.size());
+    for (size_t c = 0; c < names_.size(); ++c) {
+        std::vector<uint16_t>& k = out.kmer_count[names_[c]];
+        std::vector<uint16_t>& v = out.coverage[names_[c]];
+        k.resize(n_kmers_[c]);
+        v.resize(n_variants_[c]);
+        kc[c] = k.data();
+        cv[c] = v.data();
+    }
+    const int rc = pg_count_plan_fill_host(plan_of(handle_), kmer_coverage, kc.data(), cv.data());
+    if (rc != PG_OK) throw std::runtime_error(std::string("DeviceCountPlan: pg_count_plan_fill_host failed (") + std::to_string(rc) + "): " + pg_kmer_last_error());
+    return out;
+}
+
+void DeviceCountPlan::fill_into(UniqueKmersMap* index, size_t kmer_coverage) {
+    const SampleCounts counts = fill(kmer_coverage);
+    for (size_t c = 0; c < names_.size(); ++c) {
+        const auto found = index->unique_kmers.find(names_[c]);
+        if (found == index->unique_kmers.end() || found->second.size() != n_variants_[c]) throw std::runtime_error("DeviceCountPlan::fill_into: the index does not fit the plan on " + names_[c]);
+        const std::vector<uint16_t>& k = counts.kmer_count.at(names_[c]);
+        const std::vector<uint16_t>& v = counts.coverage.at(names_[c]);
+        size_t at = 0;
+        for (const std::shared_ptr<UniqueKmers>& u : found->second) at += u->size();
+        if (at != k.size()) throw std::runtime_error("DeviceCountPlan::fill_into: the index does not fit the plan on " + names_[c]);
+        at = 0;
+        for (size_t i = 0; i < found->second.size(); ++i) {
+            UniqueKmers& u = *found->second[i];
+            for (size_t j = 0; j < u.size(); ++j) u.update_readcount(j, k[at++]);
+            u.set_coverage(v[i]);
+        }
+    }
+}
+
+void DeviceCountPlan::fill_job(pg_job* job, uint32_t sample, size_t kmer_coverage) {
+    char err[512] = {0};
+    const int rc = pg_count_plan_fill_job(plan_of(handle_), kmer_coverage, job, sample, err, sizeof err);
+    if (rc != PG_OK) throw std::runtime_error(std::string("DeviceCountPlan: pg_count_plan_fill_job failed (") + std::to_string(rc) + "): " + err);
+}
+
+size_t DeviceCountPlan::unique_kmers() const { uint64_t n = 0; pg_count_plan_stats(plan_of(handle_), &n, nullptr, nullptr, nullptr); return (size_t)n; }
+size_t DeviceCountPlan::flanking_kmers() const { uint64_t n = 0; pg_count_plan_stats(plan_of(handle_), nullptr, &n, nullptr, nullptr); return (size_t)n; }
+double DeviceCountPlan::last_fill_ms() const { return pg_count_plan_last_fill_ms(plan_of(handle_)); }
 
 size_t for_each_read_batch(const std::string& readfile, const std::function<void(std::string_view)>& sink, size_t batch_bytes) {
     std::string text;

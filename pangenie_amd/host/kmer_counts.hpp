@@ -140,6 +140,7 @@ public:
     void* handle() const { return handle_; }
 
 private:
+    friend class DeviceCountPlan;
     bool encode_canonical(const char* s, uint64_t& code) const;
     void flush_codes();
     void fetch_table();
@@ -155,6 +156,51 @@ private:
     std::atomic<bool> fetched_{false};
     std::mutex fetch_lock_;
 };
+
+/** The index-level half of fill_read_kmercounts_all, resident on the device (include/pangenie_counts.h):
+ *  every `<prefix>_<chromosome>_kmers.tsv.gz` of the index is read ONCE, its k-mers coded and resolved against the
+ *  counter's table; a sample's numbers are then formed by one kernel per sample, without the host copy of the table.
+ *  The counter must outlive the plan; both are used from one thread. */
+class DeviceCountPlan {
+public:
+    /** Reads the tables with the checks of fill_read_kmercounts (foreign chromosome, more lines than variants, position
+     *  mismatch) and two of its own (fewer lines than variants; the unique k-mers of a line are not UniqueKmers::size()).
+     *  `register_targets`: also registers every k-mer of the tables with the counter (in place of a separate
+     *  add_targets_from_table pass; the counter must not have counted yet).  A k-mer that is not registered: throws unless
+     *  the counter was made with unregistered_counts_zero. */
+    DeviceCountPlan(DeviceKmerCounter& counter, UniqueKmersMap& index, const std::string& prefix, bool register_targets);
+    ~DeviceCountPlan();
+    DeviceCountPlan(const DeviceCountPlan&) = delete;
+    DeviceCountPlan& operator=(const DeviceCountPlan&) = delete;
+    /** the numbers fill_read_kmercounts_all + SampleCounts::of give for the reads counted so far */
+    SampleCounts fill(size_t kmer_coverage);
+    /** update_readcount / set_coverage on every object of `index` (the one the plan was made over, or a copy of it): the
+     *  drop-in for fill_read_kmercounts_all */
+    void fill_into(UniqueKmersMap* index, size_t kmer_coverage);
+    /** straight into sample `sample` of a cohort job over the same index (pg_cohort_new; chromosomes in map order) */
+    void fill_job(pg_job* job, uint32_t sample, size_t kmer_coverage);
+    /** the C handle (pg_count_plan*) */
+    void* handle() const { return handle_; }
+    const std::vector<std::string>& chromosomes() const { return names_; }
+    size_t unique_kmers() const;
+    size_t flanking_kmers() const;
+    /** device time of the last fill's kernel, ms */
+    double last_fill_ms() const;
+
+private:
+    void* handle_ = nullptr;
+    std::vector<std::string> names_;
+    std::vector<size_t> n_kmers_, n_variants_;   // per chromosome
+};
+
+/** genotype_cohort with the counting in it: one DeviceKmerCounter and one DeviceCountPlan over `index` (tables at
+ *  `<prefix>_<chromosome>_kmers.tsv.gz`, their k-mers are the registered set), one cohort job for up to `batch` samples; per
+ *  sample reset_counts, count(readfiles[s]), fill_job with kmer_coverages[s]; per batch one run.  Returns what
+ *  genotype_cohort returns for the SampleCounts of the same samples.  The objects of `index` are not touched. */
+std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohort_reads(
+    UniqueKmersMap& index, const std::string& prefix, const std::vector<std::string>& readfiles, const std::vector<size_t>& kmer_coverages,
+    ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
+    size_t batch = 64);
 
 /** The reader of the counters' count() on its own: the sequences of a FASTA / FASTQ file (plain or gzipped) in batches of
  *  about `batch_bytes`, back to back with a newline after each, handed to `sink`; returns the bytes of all batches.  With a sink

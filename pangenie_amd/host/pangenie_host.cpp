@@ -1,5 +1,6 @@
 // pangenie_host.cpp — see pangenie_host.hpp.  Host containers + the HMM adapter over the C ABI.
 #include "pangenie_host.hpp"
+#include "kmer_counts.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -736,6 +737,75 @@ std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohor
             rc = pg_job_fetch(job, (uint32_t)(s * C + c), &r, err, sizeof(err));   // chain id = sample * n_contigs + contig
             if (rc == PG_OK) out[s][names[c]] = results_of_chain(flat[c], cov_rows[s][c], goff[c], lik.data(), lexp.data());
         }
+    pg_job_destroy(job);
+    check_rc(rc, err);
+    return out;
+}
+
+// ------------------------------------------------------------------ cohort job fed by the device counter
+std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohort_reads(
+    UniqueKmersMap& index, const std::string& prefix, const std::vector<std::string>& readfiles, const std::vector<size_t>& kmer_coverages,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device, size_t batch) {
+    auto& chromosomes = index.unique_kmers;
+    const size_t C = chromosomes.size(), S = readfiles.size();
+    if (kmer_coverages.size() != S) fail("genotype_cohort_reads: one k-mer coverage per read file");
+    std::vector<std::map<std::string, std::vector<GenotypingResult>>> out(S);
+    if (C == 0 || S == 0) return out;
+    const size_t B = std::max<size_t>(1, std::min(batch, S));
+    DeviceKmerCounter counter(index.kmersize, false, device);
+    DeviceCountPlan plan(counter, index, prefix, true);
+    std::vector<std::string> names;
+    std::vector<FlatContig> flat(C);
+    std::vector<std::vector<uint64_t>> goff(C);
+    std::vector<pg_contig_batch> batches(C);
+    size_t c = 0;
+    for (auto& kv : chromosomes) {   // (map order: the plan's)
+        names.push_back(kv.first);
+        flatten(&kv.second, nullptr, flat[c]);
+        goff[c].assign(flat[c].variant_pos.size() + 1, 0);
+        pg_hmm_geno_offsets(&flat[c].batch, goff[c].data());
+        batches[c] = flat[c].batch;
+        c += 1;
+    }
+    // the job is made with the index's own numbers in every sample's place; every sample that is run is filled first
+    std::vector<const uint16_t*> count_row(C), cov_row(C);
+    for (c = 0; c < C; ++c) { count_row[c] = flat[c].batch.kmer_count; cov_row[c] = flat[c].batch.coverage; }
+    std::vector<pg_sample_counts> rows(B);
+    for (pg_sample_counts& r : rows) { r.kmer_count = count_row.data(); r.coverage = cov_row.data(); }
+    pg_hmm_params prm{};
+    prm.effective_N = effective_N; prm.recombrate = recombrate; prm.uniform = uniform ? 1 : 0; prm.run_genotyping = 1;
+    char err[512] = {0};
+    pg_job* job = nullptr;
+    int rc = pg_cohort_new(device, (uint32_t)C, batches.data(), (uint32_t)B, rows.data(), probabilities->handle(), &prm, &job, err, sizeof(err));
+    if (rc != PG_OK) { if (job) pg_job_destroy(job); check_rc(rc, err); }
+    try {
+        for (size_t s0 = 0; s0 < S; s0 += B) {
+            const size_t n = std::min(B, S - s0);   // (a last, shorter batch: the other samples' chains run on what they hold and are not fetched)
+            for (size_t s = 0; s < n; ++s) {
+                counter.reset_counts();
+                counter.count(readfiles[s0 + s]);
+                plan.fill_job(job, (uint32_t)s, kmer_coverages[s0 + s]);
+            }
+            rc = pg_job_run(job, nullptr, err, sizeof(err));
+            for (size_t s = 0; s < n && rc == PG_OK; ++s)
+                for (c = 0; c < C && rc == PG_OK; ++c) {
+                    const uint64_t nl = goff[c].back();
+                    const size_t V = flat[c].variant_pos.size();
+                    std::vector<double> lik(nl ? nl : 1);
+                    std::vector<int32_t> lexp(nl ? nl : 1);
+                    std::vector<uint16_t> cov(V ? V : 1);
+                    pg_contig_result r{};
+                    r.lik = lik.data(); r.lik_exp = lexp.data(); r.coverage = cov.data();
+                    rc = pg_job_fetch(job, (uint32_t)(s * C + c), &r, err, sizeof(err));
+                    // (pg_job_fetch hands the coverage out only when the chain has columns: exactly when results_of_chain reads it)
+                    if (rc == PG_OK) out[s0 + s][names[c]] = results_of_chain(flat[c], cov.data(), goff[c], lik.data(), lexp.data());
+                }
+            if (rc != PG_OK) break;
+        }
+    } catch (...) {
+        pg_job_destroy(job);
+        throw;
+    }
     pg_job_destroy(job);
     check_rc(rc, err);
     return out;
