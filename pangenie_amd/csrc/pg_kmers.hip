@@ -13,6 +13,7 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -880,6 +881,11 @@ int pg_count_plan_new(pg_kmer_counter* counter, uint32_t n_contigs, const pg_cou
     p->counter = counter;
     p->lenient = unregistered_counts_zero != 0;
     p->wide = counter->cap > 0xFFFFFFFFull;   // (slot indices up to cap - 1 and the sentinel 2^32 - 1)
+    // PG_COUNT_PLAN=wide (a test switch): 64-bit slot indices whatever the table's size, so that the kernels
+    // of a table of 2^32 slots run on one of thousands; any other value is ignored
+    if (const char* e = getenv("PG_COUNT_PLAN")) {
+        if (!strcmp(e, "wide")) p->wide = true;
+    }
     p->nc = n_contigs;
     p->n_k = n_k; p->n_f = n_f; p->n_v = n_v;
     p->k_blocks = (uint32_t)k_blocks; p->c_blocks = (uint32_t)c_blocks;

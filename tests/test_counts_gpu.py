@@ -92,8 +92,9 @@ def on_host(tensors):
     return [t.cpu().numpy().view(np.uint16) for t in tensors]
 
 
-@pytest.mark.parametrize("k", [5, 21, 31, 32])
-def test_fill_equals_the_restated_host_loop(k):
+def fill_equals_the_restated_host_loop(k, plan_of):
+    """the body of the test of that name; `plan_of(counter, contigs, lenient=False)` makes the plan (tests/test_counts_wide_gpu.py
+    runs the same body over plans with 64-bit slot indices)"""
     rng = np.random.default_rng(100 + k)
     g = genome(rng, 4000)
     pool = np.unique(kmers.canonical_codes(windows(g, k), k))
@@ -106,7 +107,7 @@ def test_fill_equals_the_restated_host_loop(k):
     with kmers.KmerCounter(k) as counter:
         counter.add_codes(pool)
         counter.count(text)
-        with kmers.CountPlan(counter, contigs) as plan:
+        with plan_of(counter, contigs) as plan:
             st = plan.stats()
             assert st.n_kmers == sum(c.kmer_code.size for c in contigs) and st.n_flanks == sum(c.flank_code.size for c in contigs)
             assert st.unresolved == 0 and st.device_bytes >= 4 * (st.n_kmers + st.n_flanks)
@@ -131,8 +132,12 @@ def test_fill_equals_the_restated_host_loop(k):
             assert kmers._counts().pg_count_plan_fill_device(plan._h, 3, pk, pc) == _lib.PG_ERR_INVALID
 
 
-def test_named_cases_by_hand():
-    """counts above 65 535 are truncated, not saturated; the window's edges; all flanks outside; all flanks 0; an N"""
+@pytest.mark.parametrize("k", [5, 21, 31, 32])
+def test_fill_equals_the_restated_host_loop(k):
+    fill_equals_the_restated_host_loop(k, kmers.CountPlan)
+
+
+def named_cases_by_hand(plan_of):
     k = 31
     rng = np.random.default_rng(7)
     many, five, never = (genome(rng, k) for _ in range(3))
@@ -147,7 +152,7 @@ def test_named_cases_by_hand():
         counter.add_codes([c_many, c_five, c_never])
         counter.count((many + b"\n") * 70000 + (five.translate(COMP)[::-1] + b"\n") * 5)
         assert counter.lookup_codes([c_many])[0] == 70000
-        with kmers.CountPlan(counter, [contig]) as plan:
+        with plan_of(counter, [contig]) as plan:
             trunc = 70000 - 65536
             expect = {
                 #        many alone  never x2  five alone  N + five    many + five          none
@@ -166,7 +171,12 @@ def test_named_cases_by_hand():
                 assert on_host(kd)[0].tolist() == [trunc, 5, 0, 0] and on_host(cd)[0].tolist() == want, coverage
 
 
-def test_strict_plan_names_the_first_unregistered_code_and_a_lenient_one_counts_zero():
+def test_named_cases_by_hand():
+    """counts above 65 535 are truncated, not saturated; the window's edges; all flanks outside; all flanks 0; an N"""
+    named_cases_by_hand(kmers.CountPlan)
+
+
+def strict_plan_names_the_first_unregistered_code_and_a_lenient_one_counts_zero(plan_of):
     k = 21
     rng = np.random.default_rng(3)
     g = genome(rng, 600)
@@ -187,10 +197,10 @@ def test_strict_plan_names_the_first_unregistered_code_and_a_lenient_one_counts_
         counter.add_codes(known)
         counter.count(text)
         with pytest.raises(kmers.KmerCounterError) as e:
-            kmers.CountPlan(counter, [a, b])
+            plan_of(counter, [a, b])
         assert e.value.code == _lib.PG_ERR_INVALID
         assert f"contig 1, variant {v}, flanking k-mer {at - int(b.flank_off[v])} (code {int(unknown[0])})" in str(e.value), str(e.value)
-        with kmers.CountPlan(counter, [a, b], lenient=True) as plan:
+        with plan_of(counter, [a, b], lenient=True) as plan:
             assert plan.stats().unresolved == int((b.flank_code == unknown[0]).sum() + (b.kmer_code == unknown[1]).sum()) > 0
             want = restated_fill([a, b], seen, 3)
             got = plan.fill(3)
@@ -201,8 +211,12 @@ def test_strict_plan_names_the_first_unregistered_code_and_a_lenient_one_counts_
                     kmers.CountContig(np.array([0, 1], np.uint32), np.array([1 << 42], np.uint64), np.zeros(2, np.uint64), known[:0]),
                     kmers.CountContig(np.array([1, 2], np.uint32), known[:2], np.zeros(2, np.uint64), known[:0])):
             with pytest.raises(kmers.KmerCounterError) as e:
-                kmers.CountPlan(counter, [bad], lenient=True)
+                plan_of(counter, [bad], lenient=True)
             assert e.value.code == _lib.PG_ERR_INVALID
+
+
+def test_strict_plan_names_the_first_unregistered_code_and_a_lenient_one_counts_zero():
+    strict_plan_names_the_first_unregistered_code_and_a_lenient_one_counts_zero(kmers.CountPlan)
 
 
 def test_two_samples_through_one_plan_equal_two_fresh_counters():
@@ -267,8 +281,7 @@ def plan_over(rng, index, pool):
     return contigs
 
 
-@pytest.mark.parametrize("paths", [16, 64])
-def test_fill_job_equals_an_upload_of_the_host_filled_arrays(paths):
+def fill_job_equals_an_upload_of_the_host_filled_arrays(paths, plan_of):
     k, S = 21, 3
     rng = np.random.default_rng(paths)
     g = genome(rng, 5000)
@@ -281,7 +294,7 @@ def test_fill_job_equals_an_upload_of_the_host_filled_arrays(paths):
     job = hmm.Job.cohort(index, zeros, table, params)
     with kmers.KmerCounter(k) as counter:
         counter.add_codes(pool)
-        with kmers.CountPlan(counter, contigs) as plan:
+        with plan_of(counter, contigs) as plan:
             for round_ in range(2):   # the second round: other reads into the same job, after a run
                 coverages = [28 + 3 * s + round_ for s in range(S)]
                 filled = []
@@ -313,16 +326,16 @@ def test_fill_job_equals_an_upload_of_the_host_filled_arrays(paths):
                 assert e.value.code == _lib.PG_ERR_INVALID and text in str(e.value), str(e.value)
             refused(lambda: plan.fill_job(job, S, 30), f"sample {S} of {S}")
             plain = hmm.Job(index[:1], table, params)
-            with kmers.CountPlan(counter, contigs[:1]) as one:
+            with plan_of(counter, contigs[:1]) as one:
                 refused(lambda: one.fill_job(plain, 0, 30), "not a cohort job")
             plain.close()
             other = [c for c in contigs]
             koff = other[2].kmer_off.copy()
             koff[5] += 1 if koff[5] < koff[6] else -1
             other[2] = other[2]._replace(kmer_off=koff)
-            with kmers.CountPlan(counter, other) as changed:
+            with plan_of(counter, other) as changed:
                 refused(lambda: changed.fill_job(job, 0, 30), "contig 2")
-            with kmers.CountPlan(counter, contigs[:3]) as short:
+            with plan_of(counter, contigs[:3]) as short:
                 refused(lambda: short.fill_job(job, 0, 30), "3 contigs")
             job.upload_begin(zeros)
             refused(lambda: plan.fill_job(job, 0, 30), "pg_job_upload_end")
@@ -331,3 +344,8 @@ def test_fill_job_equals_an_upload_of_the_host_filled_arrays(paths):
             job.run()
             assert job.fetch(0).n_columns > 0
     job.close()
+
+
+@pytest.mark.parametrize("paths", [16, 64])
+def test_fill_job_equals_an_upload_of_the_host_filled_arrays(paths):
+    fill_job_equals_an_upload_of_the_host_filled_arrays(paths, kmers.CountPlan)

@@ -53,6 +53,35 @@ def test_no_scratch(asm, stem):
         assert re.search(r"\.private_segment_fixed_size:\s+0\b", meta), meta[:400]
 
 
+def wide_and_narrow(text, stem):
+    """(the instantiation for uint64_t slot indices, the one for uint32_t): `m` and `j` in the mangled template argument"""
+    names = kernels(text, stem)
+    wide = [n for n in names if re.search(r"%sImE" % stem, n)]
+    narrow = [n for n in names if re.search(r"%sIjE" % stem, n)]
+    assert len(wide) == 1 and len(narrow) == 1, names
+    return wide[0], narrow[0]
+
+
+@pytest.mark.parametrize("stem", ["kk_plan_fill", "kk_plan_resolve"])
+def test_the_wide_instantiations_are_in_the_code_object_and_meet_the_same_bounds(asm, stem):
+    """the kernels of a table of 2^32 slots or more (PG_COUNT_PLAN=wide runs them on small tables: tests/test_counts_wide_gpu.py)"""
+    wide, narrow = wide_and_narrow(asm, stem)
+    for kernel in (wide, narrow):
+        meta = metadata_of(asm, kernel)
+        assert re.search(r"\.symbol:\s+%s\.kd" % re.escape(kernel), meta), meta[:400]   # a kernel of the code object, not a name in passing
+        assert "scratch_" not in body_of(asm, kernel), kernel
+        assert re.search(r"\.private_segment_fixed_size:\s+0\b", meta), meta[:400]
+    if stem == "kk_plan_fill":
+        body, meta = body_of(asm, wide), metadata_of(asm, wide)
+        assert not re.search(r"atomic|cmpswap", body)
+        assert re.search(r"\b(global|flat)_store_short\b", body) and "global_load_dwordx2" in body
+        assert re.search(r"\.group_segment_fixed_size:\s+0\b", meta), meta[:400]
+        assert int(re.search(r"\.vgpr_count:\s+(\d+)", meta).group(1)) <= 64
+    else:
+        # the slot index leaves as 8 bytes in the wide kernel, as 4 in the narrow one
+        assert re.search(r"\bglobal_store_dwordx2\b", body_of(asm, wide)) and not re.search(r"\bglobal_store_dwordx2\b", body_of(asm, narrow))
+
+
 def test_fill_kernel_only_gathers_and_stores(asm):
     for kernel in kernels(asm, "kk_plan_fill"):
         body = body_of(asm, kernel)
