@@ -12,8 +12,8 @@ CSRC = ROOT / "pangenie_amd" / "csrc"
 HIP_LIB = CSRC / "libpangenie_hmm.so"
 HIP_SOURCES = [CSRC / "pg_kernels.hip", CSRC / "pg_shim.cpp", CSRC / "pg_gather.cpp", CSRC / "pg_sampler.hip", CSRC / "pg_viterbi.hip",
                CSRC / "pg_kmers.hip"]
-HIP_DEPS = HIP_SOURCES + [CSRC / "pg_device.h", CSRC / "pg_devmath.h", CSRC / "pg_small16x.h", CSRC / "pg_experiments.h", CSRC / "pg_split.h", ROOT / "include" / "pangenie_hmm.h", ROOT / "include" / "pangenie_sampler.h",
-                          ROOT / "include" / "pangenie_kmers.h", ROOT / "include" / "pangenie_counts.h"]
+# every header is a dependency of the library: a new one is picked up without anyone listing it
+HIP_DEPS = HIP_SOURCES + sorted(CSRC.glob("*.h")) + sorted((ROOT / "include").glob("*.h"))
 
 
 def _stale(target: Path, deps) -> bool:
@@ -73,10 +73,7 @@ def build_host(force: bool = False) -> Path:
     the C ABI) and tests/cpp/test_host.bin."""
     build_hip()
     cxx = shutil.which("g++") or "g++"
-    deps = [HOST_DIR / "pangenie_host.cpp", HOST_DIR / "pangenie_host.hpp", HOST_DIR / "cereal_io.cpp", HOST_DIR / "cereal_io.hpp",
-            HOST_DIR / "kmer_counts.cpp", HOST_DIR / "kmer_counts.hpp", HOST_DIR / "graph_io.cpp", HOST_DIR / "graph_io.hpp",
-            HOST_DIR / "index_builder.cpp", HOST_DIR / "index_builder.hpp", HOST_DIR / "archive_bytes.hpp", ROOT / "include" / "pangenie_hmm.h",
-            ROOT / "include" / "pangenie_sampler.h", ROOT / "include" / "pangenie_kmers.h"]
+    deps = sorted(HOST_DIR.glob("*.cpp")) + sorted(HOST_DIR.glob("*.hpp")) + sorted((ROOT / "include").glob("*.h"))
     if force or _stale(HOST_LIB, deps):
         cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", str(HOST_DIR / "pangenie_host.cpp"), str(HOST_DIR / "cereal_io.cpp"),
                str(HOST_DIR / "kmer_counts.cpp"), str(HOST_DIR / "graph_io.cpp"), str(HOST_DIR / "index_builder.cpp"), "-o", str(HOST_LIB), f"-L{CSRC}", "-lpangenie_hmm", "-lpthread", "-lz", "-Wl,-rpath,$ORIGIN/../csrc"]

@@ -35,6 +35,7 @@
 
 #include "pg_device.h"
 #include "pg_devmath.h"
+#include "pg_launch.h"   // the launchers at the bottom of this file and their masks, as the shim sees them
 
 #define DEVI __device__ __forceinline__
 typedef double v2f64 __attribute__((ext_vector_type(2)));  // native vector type (address-space qualifiable)
@@ -6785,7 +6786,7 @@ __global__ __launch_bounds__(256) void k_bins_wide(const DevContig* __restrict__
 // ------------------------------------------------------------------------------------------
 //  host-callable launchers (defined here so that the shim needs no kernel templates)
 // ------------------------------------------------------------------------------------------
-// hp_mask: bit0 HP=16, bit1 HP=32, bit2 HP=64, bit3 HP=128; phase 1 = store halves, 2 = posterior halves
+// hp_mask: the PG_SWEEP_* bits of pg_launch.h; phase 1 = store halves, 2 = posterior halves
 // The opt-in to more than 64 KiB of dynamic LDS is a per-device attribute of a kernel: it is set once
 // per (kernel, device) — jobs on several devices can share a process (HMM::set_device()).  A racing
 // second thread at worst sets it twice.
@@ -6813,39 +6814,40 @@ static void launch_one(const DevContig* d_contigs, uint32_t n_contigs, uint32_t 
 }
 template <int PHASE>
 static void launch_sweep(const DevContig* d_contigs, uint32_t n_contigs, uint32_t hp_mask, uint32_t chunk, hipStream_t s) {
-    if (hp_mask & 1u) launch_one<16, 4, 1, true, PHASE>(d_contigs, n_contigs, chunk, s);
+    if (hp_mask & PG_SWEEP_HP16) launch_one<16, 4, 1, true, PHASE>(d_contigs, n_contigs, chunk, s);
 #ifndef PG_HP32_ROWS
 #define PG_HP32_ROWS 8
 #endif
-    if (hp_mask & 2u) launch_one<32, PG_HP32_ROWS, 1, true, PHASE>(d_contigs, n_contigs, chunk, s);
-    if (hp_mask & 4u) launch_one<64, 16, 1, true, PHASE>(d_contigs, n_contigs, chunk, s);
+    if (hp_mask & PG_SWEEP_HP32) launch_one<32, PG_HP32_ROWS, 1, true, PHASE>(d_contigs, n_contigs, chunk, s);
+    if (hp_mask & PG_SWEEP_HP64) launch_one<64, 16, 1, true, PHASE>(d_contigs, n_contigs, chunk, s);
     if constexpr (PHASE == 1) {
-        if (hp_mask & 2048u)   // bit 11: 64-path triangle chains that are not lean chains, phase 1 on the general kernel (PG_KERNELS=noleanx)
+        if (hp_mask & PG_SWEEP_TRI1)   // 64-path triangle chains that are not lean chains, phase 1 on the general kernel (PG_KERNELS=noleanx)
             hipLaunchKernelGGL(k_sweep_tri1, dim3(n_contigs, 2), dim3(ChainCfg<64, 16, sweep_has_loader<64, 1>()>::TT), 0, s, d_contigs);
-        if (hp_mask & 4096u)   // bit 12: ... on the lean-x step (DevContig::leanx == 2)
+        if (hp_mask & PG_SWEEP_LEANX_TRI)   // ... on the lean-x step (DevContig::leanx == 2)
             hipLaunchKernelGGL(k_sweep_leanx_tri, dim3(n_contigs, 2), dim3(LxCfg<64>::T), 0, s, d_contigs);
-        if (hp_mask & 16384u)  // bit 14: ... of chains with wide columns (DevContig::widef)
+        if (hp_mask & PG_SWEEP_LEANX_TRIW)  // ... of chains with wide columns (DevContig::widef)
             hipLaunchKernelGGL(k_sweep_leanx_triw, dim3(n_contigs, 2), dim3(LxCfg<64>::T), 0, s, d_contigs);
     }
-    if (hp_mask & 8u) launch_one<128, 32, 1, false, PHASE>(d_contigs, n_contigs, chunk, s);
+    if (hp_mask & PG_SWEEP_HP128) launch_one<128, 32, 1, false, PHASE>(d_contigs, n_contigs, chunk, s);
     if constexpr (PHASE == 2) {
-        if (hp_mask & 256u) hipLaunchKernelGGL((k_sweep_lean2<16>), dim3(n_contigs, 2), dim3(256), 0, s, d_contigs);  // bit 8: chains with tri == 2
-        if (hp_mask & 8192u) hipLaunchKernelGGL(k_sweep_leanx2, dim3(n_contigs, 2), dim3(256), 0, s, d_contigs);      // bit 13: DevContig::leanx2
+        if (hp_mask & PG_SWEEP_LEAN2) hipLaunchKernelGGL((k_sweep_lean2<16>), dim3(n_contigs, 2), dim3(256), 0, s, d_contigs);  // chains with tri == 2
+        if (hp_mask & PG_SWEEP_LEANX2) hipLaunchKernelGGL(k_sweep_leanx2, dim3(n_contigs, 2), dim3(256), 0, s, d_contigs);  // DevContig::leanx2
     }
     if constexpr (PHASE != 2) {
-        if (hp_mask & 64u) {  // bit 6: the job has lean chains (all-biallelic, H = HP = 64)
-            if (PHASE == 1 && (hp_mask & 128u))  // bit 7: fused job whose lean chains store triangles (DevContig::tri)
+        if (hp_mask & PG_SWEEP_LEAN) {  // the job has lean chains (all-biallelic, H = HP = 64)
+            if (PHASE == 1 && (hp_mask & PG_SWEEP_TRI))  // fused job whose lean chains store triangles (DevContig::tri)
                 hipLaunchKernelGGL((k_sweep_lean_tri<PHASE, 16>), dim3(n_contigs, 2), dim3(256), 0, s, d_contigs, chunk);
             else hipLaunchKernelGGL((k_sweep_lean<PHASE, 16, false>), dim3(n_contigs, 2), dim3(256), 0, s, d_contigs, chunk);
         }
-        if (hp_mask & 512u)   // bit 9: the job has lean-x chains at HP = 128 (narrow columns only)
+        if (hp_mask & PG_SWEEP_LEANX128)   // the job has lean-x chains at HP = 128 (narrow columns only)
             hipLaunchKernelGGL((k_sweep_leanx<PHASE, 128>), dim3(n_contigs, 2), dim3(LxCfg<128>::T), 0, s, d_contigs, chunk);
-        if (hp_mask & 1024u)  // bit 10: ... at HP = 64 (chains with multiallelic objects; all-biallelic H = 64 chains are bit 6)
+        if (hp_mask & PG_SWEEP_LEANX64)  // ... at HP = 64 (chains with multiallelic objects; all-biallelic H = 64 chains are PG_SWEEP_LEAN's)
             hipLaunchKernelGGL((k_sweep_leanx<PHASE, 64>), dim3(n_contigs, 2), dim3(LxCfg<64>::T), 0, s, d_contigs, chunk);
-        // bit 4: contigs with HP >= 256; bit 5: (forced) the generic kernel for every HP >= 64
-        if (hp_mask & 48u)
+        // contigs with HP >= 256; PG_SWEEP_GENERIC64: (forced) the generic kernel for every HP >= 64
+        const bool from64 = hp_mask & PG_SWEEP_GENERIC64;
+        if (hp_mask & (PG_SWEEP_GENERIC | PG_SWEEP_GENERIC64))
             hipLaunchKernelGGL(k_sweep_generic<PHASE>, dim3(n_contigs, 2), dim3(PG_GEN_THREADS), 0, s, d_contigs, chunk,
-                               (hp_mask & 32u) ? 64u : 256u);
+                               from64 ? 64u : 256u);
     }
 }
 extern "C" {
@@ -6886,21 +6888,22 @@ void pgk_launch_records(const DevContig* d_contigs, uint32_t n_contigs, uint32_t
     dim3 grid((max_v + 255) / 256, n_contigs);   // 256 columns per block either way (a thread or a quarter of a wave's 64 each)
     hipLaunchKernelGGL(k_records, grid, dim3(256), 0, s, d_contigs);
 }
-// which: bit 0 = the job has chains whose bins k_bins forms, bit 1 = chains on k_sweep_lean2 (k_bins_lean2), bit 2 = chains of k_bins_thin
+// which: the PG_BINS_* bits of pg_launch.h
 void pgk_launch_bins(const DevContig* d_contigs, uint32_t n_contigs, uint32_t max_v, uint32_t which, uint32_t max_wide, hipStream_t s) {
     // (a chain on k_sweep_lean2 that ends up with a single column is k_bins' too: one block per chain covers that)
-    dim3 grid((which & 1u) ? (max_v + 3) / 4 : 1u, n_contigs);
+    const bool full = which & PG_BINS_FULL;
+    dim3 grid(full ? (max_v + 3) / 4 : 1u, n_contigs);
     hipLaunchKernelGGL(k_bins, grid, dim3(256), 0, s, d_contigs);
-    dim3 grid256((max_v + 255) / 256, n_contigs);
-    if (which & 2u) hipLaunchKernelGGL(k_bins_lean2, grid256, dim3(256), 0, s, d_contigs);  // (each kernel skips the other's columns)
-    if (which & 4u) hipLaunchKernelGGL(k_bins_thin, grid256, dim3(256), 0, s, d_contigs);
-    if (which & 8u) hipLaunchKernelGGL(k_bins_x, grid256, dim3(256), 0, s, d_contigs);      // bit 3: chains on k_sweep_small16x<2>
-    if ((which & 16u) && max_wide)   // bit 4: ... with objects of more than PG_AMAX alleles: one wave per listed wide column
+    dim3 grid256((max_v + 255) / 256, n_contigs), grid16((max_v + 15u) / 16u, n_contigs);
+    if (which & PG_BINS_LEAN2) hipLaunchKernelGGL(k_bins_lean2, grid256, dim3(256), 0, s, d_contigs);  // (each kernel skips the other's columns)
+    if (which & PG_BINS_THIN) hipLaunchKernelGGL(k_bins_thin, grid256, dim3(256), 0, s, d_contigs);
+    if (which & PG_BINS_X) hipLaunchKernelGGL(k_bins_x, grid256, dim3(256), 0, s, d_contigs);      // chains on k_sweep_small16x<2>
+    if ((which & PG_BINS_WIDE) && max_wide)   // ... with objects of more than PG_AMAX alleles: one wave per listed wide column
         hipLaunchKernelGGL(k_bins_wide, dim3((max_wide + 3u) / 4u, n_contigs), dim3(256), 0, s, d_contigs);
-    if (which & 32u) hipLaunchKernelGGL(k_bins_s, grid256, dim3(256), 0, s, d_contigs);     // bit 5: split chains (pg_split.h)
-    if ((which & 64u) && max_wide)   // bit 6: ... with wide columns
+    if (which & PG_BINS_S) hipLaunchKernelGGL(k_bins_s, grid256, dim3(256), 0, s, d_contigs);     // split chains (pg_split.h)
+    if ((which & PG_BINS_WIDE_S) && max_wide)   // ... with wide columns
         hipLaunchKernelGGL(k_bins_wide_s, dim3((max_wide + 3u) / 4u, n_contigs), dim3(256), 0, s, d_contigs);
-    if (which & 128u) hipLaunchKernelGGL(k_bins_q, dim3((max_v + 15u) / 16u, n_contigs), dim3(256), 0, s, d_contigs);   // bit 7: chains on k_sweep_leanx2
+    if (which & PG_BINS_Q) hipLaunchKernelGGL(k_bins_q, grid16, dim3(256), 0, s, d_contigs);   // chains on k_sweep_leanx2
 }
 void pgk_launch_sweep(const DevContig* d_contigs, uint32_t n_contigs, uint32_t hp_mask, int phase, hipStream_t s) {
     if (phase == 1) launch_sweep<1>(d_contigs, n_contigs, hp_mask, 0, s);

@@ -1,0 +1,64 @@
+// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip).
+//
+// The ONE declaration of every host-callable launcher and of the two launch masks a job hands them.  Both sides include
+// it: a launcher whose parameter list changes on one side only no longer compiles (C linkage: the linker would not notice).
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <stdint.h>
+
+#include "pg_device.h"
+
+// Sweep mask (pg_job::hp_mask -> pgk_launch_sweep / pgk_launch_sweep_chunk): which chain kernels a job's sweep launches.
+// Every kernel walks all chains of the job and returns at once for a chain that is not its own.
+enum : uint32_t {
+    PG_SWEEP_HP16 = 1u,            // k_sweep<16,4>: the general kernel, one bit per padded path count
+    PG_SWEEP_HP32 = 2u,            // k_sweep<32,8>
+    PG_SWEEP_HP64 = 4u,            // k_sweep<64,16>
+    PG_SWEEP_HP128 = 8u,           // k_sweep<128,32>
+    PG_SWEEP_GENERIC = 16u,        // k_sweep_generic: chains with HP >= 256
+    PG_SWEEP_GENERIC64 = 32u,      // (forced, PG_KERNELS=generic) ... for every HP >= 64; goes with PG_SWEEP_GENERIC: one launch covers both
+    PG_SWEEP_LEAN = 64u,           // k_sweep_lean: lean chains (all-biallelic, H = HP = 64), the store-only phases
+    PG_SWEEP_TRI = 128u,           // fused job whose 64-path chains store triangles (DevContig::tri): phase 1 of the lean chains on k_sweep_lean_tri
+    PG_SWEEP_LEAN2 = 256u,         // k_sweep_lean2: phase 2 of the chains with tri == 2
+    PG_SWEEP_LEANX128 = 512u,      // k_sweep_leanx<., 128>: lean-x chains at HP = 128 (narrow columns only)
+    PG_SWEEP_LEANX64 = 1024u,      // k_sweep_leanx<., 64>: ... at HP = 64 (chains with multiallelic objects; all-biallelic ones are PG_SWEEP_LEAN's)
+    PG_SWEEP_TRI1 = 2048u,         // k_sweep_tri1: 64-path triangle chains that are not lean chains, phase 1 on the general kernel (PG_KERNELS=noleanx)
+    PG_SWEEP_LEANX_TRI = 4096u,    // k_sweep_leanx_tri: ... on the lean-x step (DevContig::leanx == 2)
+    PG_SWEEP_LEANX2 = 8192u,       // k_sweep_leanx2: phase 2 of the chains with DevContig::leanx2
+    PG_SWEEP_LEANX_TRIW = 16384u,  // k_sweep_leanx_triw: phase 1 of those triangle chains that have wide columns (DevContig::widef)
+};
+
+// Bins mask (pg_job::bins_which -> pgk_launch_bins): which kernels form a fused job's bins.
+enum : uint32_t {
+    PG_BINS_FULL = 1u,     // k_bins has chains of its own (it is launched either way: one block per chain without this bit)
+    PG_BINS_LEAN2 = 2u,    // k_bins_lean2: chains on k_sweep_lean2, and class sums (DevContig::cls4)
+    PG_BINS_THIN = 4u,     // k_bins_thin: at most 64 partial entries per column
+    PG_BINS_X = 8u,        // k_bins_x: chains on k_sweep_small16x<2>
+    PG_BINS_WIDE = 16u,    // k_bins_wide: ... with objects of more than PG_AMAX alleles, and DevContig::widef chains: one wave per listed wide column
+    PG_BINS_S = 32u,       // k_bins_s: split chains (pg_split.h)
+    PG_BINS_WIDE_S = 64u,  // k_bins_wide_s: ... with wide columns
+    PG_BINS_Q = 128u,      // k_bins_q: chains on k_sweep_leanx2
+};
+
+extern "C" {
+// pg_kernels.hip
+void pgk_launch_prep(const DevContig* d_contigs, uint32_t n_contigs, uint32_t max_v, uint32_t max_w, uint32_t max_m4, DevTable tab, hipStream_t s);
+void pgk_launch_compact(const DevContig* d_contigs, uint32_t n_contigs, hipStream_t s);
+void pgk_launch_index(const DevContig* d_reps, uint32_t n_index, uint32_t max_v, uint32_t max_big, int any_split, hipStream_t s);
+void pgk_launch_prep_split(const DevContig* d_contigs, uint32_t n_contigs, uint32_t max_b, uint32_t max_m4, uint32_t max_w, DevTable tab, hipStream_t s);
+void pgk_launch_records(const DevContig* d_contigs, uint32_t n_contigs, uint32_t max_v, hipStream_t s);
+void pgk_launch_bins(const DevContig* d_contigs, uint32_t n_contigs, uint32_t max_v, uint32_t which, uint32_t max_wide, hipStream_t s);
+void pgk_launch_sweep(const DevContig* d_contigs, uint32_t n_contigs, uint32_t hp_mask, int phase, hipStream_t s);
+void pgk_launch_sweep_chunk(const DevContig* d_contigs, uint32_t n_contigs, uint32_t hp_mask, uint32_t chunk, hipStream_t s);
+void pgk_launch_sweep_small(const DevContig* d_contigs, const uint32_t* d_ids, uint32_t n_ids, int phase, uint32_t chunk, double* d_dump, hipStream_t s);
+void pgk_launch_sweep_smallx(const DevContig* d_contigs, const uint32_t* d_ids, uint32_t n_ids, int phase, uint32_t chunk, double* d_dump, hipStream_t s);
+uint32_t pgk_post_blocks(uint32_t n_contigs, uint32_t chunk_cols, uint32_t* cus_out);
+void pgk_launch_post(const DevContig* d_contigs, uint32_t n_contigs, uint32_t chunk_cols, uint32_t chunk, hipStream_t s);
+void pgk_launch_stream_handshake(uint32_t* d_words, hipStream_t s, hipStream_t s2);
+void pgk_launch_phase2_persistent(const DevContig* d_contigs, uint32_t n_contigs, uint32_t post_blocks, hipStream_t s, hipStream_t s2);
+void pgk_launch_emission_single(const DevContig* d_contig, DevTable tab, uint32_t v, double* out_m, int* out_e, hipStream_t s);
+void pgk_launch_transition_single(double d, uint32_t H, int uniform, double* out3, hipStream_t s);
+uint32_t pgk_threads_for_hp(uint32_t hp);
+// pg_viterbi.hip
+void pgk_launch_viterbi(const DevContig* d_contigs, uint32_t n, uint32_t max_v, uint32_t hp_bits, hipStream_t s);
+}

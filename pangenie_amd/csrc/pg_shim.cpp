@@ -31,27 +31,8 @@
 
 #include "../../include/pangenie_hmm.h"
 #include "pg_device.h"
+#include "pg_launch.h"
 
-extern "C" {
-void pgk_launch_prep(const DevContig*, uint32_t, uint32_t, uint32_t, uint32_t, DevTable, hipStream_t);
-void pgk_launch_compact(const DevContig*, uint32_t, hipStream_t);
-void pgk_launch_index(const DevContig*, uint32_t, uint32_t, uint32_t, int, hipStream_t);
-void pgk_launch_prep_split(const DevContig*, uint32_t, uint32_t, uint32_t, uint32_t, DevTable, hipStream_t);
-void pgk_launch_records(const DevContig*, uint32_t, uint32_t, hipStream_t);
-void pgk_launch_bins(const DevContig*, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
-void pgk_launch_sweep(const DevContig*, uint32_t, uint32_t, int, hipStream_t);
-void pgk_launch_sweep_chunk(const DevContig*, uint32_t, uint32_t, uint32_t, hipStream_t);
-void pgk_launch_post(const DevContig*, uint32_t, uint32_t, uint32_t, hipStream_t);
-uint32_t pgk_post_blocks(uint32_t, uint32_t, uint32_t*);
-void pgk_launch_phase2_persistent(const DevContig*, uint32_t, uint32_t, hipStream_t, hipStream_t);
-void pgk_launch_stream_handshake(uint32_t*, hipStream_t, hipStream_t);
-void pgk_launch_sweep_small(const DevContig*, const uint32_t*, uint32_t, int, uint32_t, double*, hipStream_t);
-void pgk_launch_sweep_smallx(const DevContig*, const uint32_t*, uint32_t, int, uint32_t, double*, hipStream_t);
-void pgk_launch_emission_single(const DevContig*, DevTable, uint32_t, double*, int*, hipStream_t);
-void pgk_launch_transition_single(double, uint32_t, int, double*, hipStream_t);
-uint32_t pgk_threads_for_hp(uint32_t);
-void pgk_launch_viterbi(const DevContig*, uint32_t, uint32_t, uint32_t, hipStream_t);  // pg_viterbi.hip
-}
 
 namespace {
 
@@ -445,10 +426,10 @@ struct pg_job {
     std::vector<double> tab_m;
     std::vector<int32_t> tab_e;
     DevTable tab;
-    uint32_t hp_mask = 0, max_v = 0;
+    uint32_t hp_mask = 0, max_v = 0;   // hp_mask: the PG_SWEEP_* bits of the job's chain kernels (pg_launch.h; choose_chain_kernels)
     uint32_t max_wide = 0;   // grid extent of k_bins_wide: the longest list of wide-column candidates
     uint32_t max_prep_w = 0, max_prep_m4 = 0;   // grid extents of k_prep (lists or all variants) and k_prep_m4
-    uint32_t bins_which = 0;   // bit 0: chains whose bins k_bins forms, bit 1: chains on k_sweep_lean2 (k_bins_lean2), bit 2: k_bins_thin
+    uint32_t bins_which = 0;   // the PG_BINS_* bits of the kernels that form a fused job's bins
     uint32_t vit_bits = 0;     // run_phasing: 1 / 2 / 4 = chains with 16 / 32 / 64 padded paths
     hipEvent_t ev_vit[2];
     double vit_ms = 0.0;
@@ -619,6 +600,13 @@ int sample_upload(pg_job* job, const std::vector<ChainSpec>& specs, unsigned cha
 }
 
 bool streams_concurrent(pg_job* job, hipStream_t s);   // (below, in front of pg_job_run)
+// Group B's copies of a pipelined first run (pg_job::late_threads) read the caller's arrays and feed the job's second stream:
+// whoever needs either to be left alone waits for the threads first.
+void join_late_threads(pg_job* job) {
+    for (auto& t : job->late_threads) if (t.joinable()) t.join();
+    job->late_threads.clear();
+    job->late_pending = false;
+}
 // H2D of the inputs into a planned job.  Copies are queued on the job's stream; pageable sources are
 // staged by the runtime, so every call returns when its source has been read.
 int upload_inputs(pg_job* job, const pg_contig_batch* batches, const std::vector<ChainSpec>& specs, bool with_index,
@@ -631,6 +619,8 @@ int upload_inputs(pg_job* job, const pg_contig_batch* batches, const std::vector
     // arrays, 1.06 GB) is then issued from several host threads on streams of their own — the runtime stages a pageable
     // source through its bounce buffers on the calling thread, one copy after the other: 24 ms on one thread
     struct Copy { void* dst; const void* src; size_t bytes; };
+    // (the caller's arrays are valid until this call returns: once group B's threads run, an error return waits for them)
+    struct LateGuard { pg_job* job; bool armed; ~LateGuard() { if (armed) join_late_threads(job); } } late_guard{job, false};
     std::vector<Copy> copies, late_copies;   // late: group B of a pipelined first run (pg_job::pipeline) — issued here, waited for in pg_job_run
     // (the pipelined first run needs the job's two streams to run side by side: asked once, here, where nothing is in flight)
     if (with_index && job->pipeline && !streams_concurrent(job, s)) job->pipeline = false;
@@ -776,6 +766,7 @@ int upload_inputs(pg_job* job, const pg_contig_batch* batches, const std::vector
             job->late_threads.clear();
             for (unsigned t = 0; t < ntb; ++t) job->late_threads.emplace_back(staged_worker, share[t], &job->late_rc[t]);
             job->late_pending = true;
+            late_guard.armed = true;
         }
     }
     HIP_TRY(hipStreamSynchronize(s));
@@ -800,6 +791,7 @@ int upload_inputs(pg_job* job, const pg_contig_batch* batches, const std::vector
     }
     job->up_bytes[0] = bi; job->up_bytes[1] = bs;
     job->host_s[1] = now_s() - t0;
+    late_guard.armed = false;   // (pg_job_run joins them, beside group A's kernels)
     return PG_OK;
 }
 
@@ -869,19 +861,37 @@ void parallel_contigs(uint32_t n, const pg_contig_batch* batches, F&& f) {
     for (auto& t : th) t.join();
 }
 
-// (chunk_cap: 0, or the most chunk columns this attempt may plan for — the retry of a chunked job whose arena did not fit)
-int job_build(int device, uint32_t n_index, const pg_contig_batch* batches, const std::vector<ChainSpec>& specs,
-              uint32_t n_samples, bool cohort, const pg_table* table, const pg_hmm_params* params, bool cache_arena,
-              pg_job** out, char* err, size_t errlen, size_t chunk_cap = 0) {
-    *out = nullptr;
+// ---------------------------------------------------------------------------------------
+//  job_build: a job from the caller's arrays, as a sequence of steps — check, classify the index contigs, choose the mode
+//  and every chain's kernels, lay the arena out, allocate it, fill and upload the descriptors, upload the inputs.
+//  Deciding, laying out and touching the device are kept apart: a new kernel is a row of the tables below and a branch of
+//  choose_chain_kernels.
+// ---------------------------------------------------------------------------------------
+// what the steps share: the caller's arguments and the kernel override, fixed for the whole construction
+struct BuildArgs {
+    uint32_t n_index;
+    const pg_contig_batch* batches;
+    const std::vector<ChainSpec>& specs;
+    const pg_hmm_params& params;
+    KernelChoice kc;
+    bool cohort, cache_arena;
+};
+
+// destroys the job on every way out of job_build but the last
+struct JobOwner {
+    pg_job* job;
+    ~JobOwner() { if (job) pg_job_destroy(job); }
+    pg_job* release() { pg_job* j = job; job = nullptr; return j; }
+};
+
+int hip_fail(char* err, size_t errlen, const char* what, hipError_t e) {
+    set_err(err, errlen, "%s: %s", what, hipGetErrorString(e));
+    return PG_ERR_DEVICE;
+}
+
+int check_inputs(uint32_t n_index, const pg_contig_batch* batches, const std::vector<ChainSpec>& specs, const pg_table* table,
+                 const pg_hmm_params* params, bool cohort, char* err, size_t errlen) {
     if (!batches || !table || !params || n_index == 0 || specs.empty()) { set_err(err, errlen, "null argument"); return PG_ERR_INVALID; }
-#ifdef PG_HOST_TIMING   // (measurement builds: where the host time of a job's construction goes)
-    const double tb0 = now_s();
-    double tb_last = tb0;
-    auto lap = [&](const char* what) { const double t = now_s(); fprintf(stderr, "[job_build] %-28s %8.3f ms\n", what, (t - tb_last) * 1e3); tb_last = t; };
-#else
-    auto lap = [](const char*) {};
-#endif
     if (params->run_phasing) {
         // Viterbi (pg_viterbi.hip): a row of states is one wave's lanes, so at most 64 selected paths (the reference's
         // own callers pass at most 30, src/commands.cpp:939)
@@ -892,7 +902,7 @@ int job_build(int device, uint32_t n_index, const pg_contig_batch* batches, cons
             }
     }
     {   // (per-variant validation: contigs on worker threads when there is enough of it — a merged one-shot job of a whole
-        //  genome spent 3 + 22 ms here and in the planning loop below, single-threaded, per round)
+        //  genome spent 3 + 22 ms here and in the classification below, single-threaded, per round)
         std::vector<int> rcs(n_index, PG_OK);
         std::vector<std::string> msgs(n_index);
         parallel_contigs(n_index, batches, [&](uint32_t i) {
@@ -910,165 +920,138 @@ int job_build(int device, uint32_t n_index, const pg_contig_batch* batches, cons
             return PG_ERR_INVALID;
         }
     }
-    lap("batch checks");
+    return PG_OK;
+}
+
+int select_device(int device, char* err, size_t errlen) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_err(err, errlen, "no HIP device available (no CPU fallback)"); return PG_ERR_DEVICE; }
     if (device < 0 || device >= ndev) { set_err(err, errlen, "bad device %d", device); return PG_ERR_INVALID; }
     if (hipSetDevice(device) != hipSuccess) { set_err(err, errlen, "hipSetDevice failed"); return PG_ERR_DEVICE; }
+    return PG_OK;
+}
 
-    const uint32_t n_chains = (uint32_t)specs.size();
-    pg_job* job = new pg_job();
-    job->device = device;
-    job->params = *params;
-    job->cache_arena = cache_arena;
-    job->cohort = cohort;
-    job->n_samples = n_samples;
-    job->n_contigs = n_index;
-    auto fail = [&](int rc, const char* what, hipError_t e) -> int {
-        set_err(err, errlen, "%s: %s", what, hipGetErrorString(e));
-        pg_job_destroy(job);
-        return rc;
-    };
-    hipError_t he;
-    if ((he = hipStreamCreate(&job->stream)) != hipSuccess) return fail(PG_ERR_DEVICE, "hipStreamCreate", he);
-    for (auto& e : job->ev)
-        if ((he = hipEventCreate(&e)) != hipSuccess) return fail(PG_ERR_DEVICE, "hipEventCreate", he);
-    for (auto& e : job->ev_vit)
-        if ((he = hipEventCreate(&e)) != hipSuccess) return fail(PG_ERR_DEVICE, "hipEventCreate", he);
-    for (auto& e : job->ev_ix)
-        if ((he = hipEventCreate(&e)) != hipSuccess) return fail(PG_ERR_DEVICE, "hipEventCreate", he);
-    job->events = true;
-    table_snapshot(const_cast<pg_table*>(table), job->tab_m, job->tab_e, job->tab_p, &job->tab);
-
-    lap("streams, events, table");
-    // ---- index contigs -------------------------------------------------------------------
-    job->index.resize(n_index);
-    bool wide_candidates = false, generic_needed = false;
-    uint32_t max_v = 0;
-    bool lean_ok = true, force_generic = false;
-    const KernelChoice kc = kernel_choice();
-    if (!kc.unknown.empty()) {
-        set_err(err, errlen, "PG_KERNELS: unknown token '%s'", kc.unknown.c_str());
-        pg_job_destroy(job);
-        return PG_ERR_INVALID;
+// One index contig: its shape, the per-variant tables the kernels are handed (goff, n_kmers, the preparation lists, widx, auxidx)
+// and which kernels its shape ALLOWS (lean, small, smallx, cls4, leanx, prep_fast, widef_cand) — what the job's mode makes of
+// that is choose_job_mode's.  Host code only.  Two passes over the variants: the second, over those with more than two alleles,
+// only when the first has found some that need a wide entry or an aux slot.  False: the wide-column tables exceed 64 GB.
+bool classify_index_contig(const pg_contig_batch& b, const KernelChoice& kc, const pg_hmm_params& params, IndexHost& x) {
+    const bool lean_ok = !kc.general && !kc.generic;
+    x.V = b.n_variants; x.H = b.n_paths; x.HP = pad_paths(x.H ? x.H : 1);
+    x.T = pgk_threads_for_hp(x.HP); x.RB = pg_rec_bytes(x.HP);
+    x.sumK = x.V ? b.kmer_off[x.V] : 0; x.sumA = x.V ? b.allele_off[x.V] : 0;
+    x.goff.assign((size_t)x.V + 1, 0);
+    x.n_kmers.resize(x.V);
+    if (x.V) { x.koff.assign(b.kmer_off, b.kmer_off + x.V + 1); x.aoff.assign(b.allele_off, b.allele_off + x.V + 1); }
+    // k_prep_bi (four variants per wave) takes the two-allele objects with <= 32 k-mers of chains with <= 64 paths; the others
+    // walk lists: list_m4 (3 .. PG_AMAX alleles, <= 64 k-mers: k_prep_m4), list_w (k_prep) and list_b (k_prep_bi's own).  Who wants
+    // the lists is known after the pass only, so they start at the first object that is not k_prep_bi's — every one in front of
+    // it is list_b's — and are dropped again below if nobody does.
+    const bool fast_ok = x.H <= 64u && x.V > 0 && !kc.prepwave;
+    const bool small_shape = lean_ok && x.HP == 16u && x.H == 16u;
+    bool listing = false, two_alleles = true;
+    uint64_t maxA = 1;
+    uint32_t maxK = 0, n_bi = 0;
+    for (uint32_t v = 0; v < x.V; ++v) {
+        const uint64_t A = b.allele_off[v + 1] - b.allele_off[v];
+        const uint32_t K = b.kmer_off[v + 1] - b.kmer_off[v];
+        x.goff[v + 1] = x.goff[v] + A * (A + 1) / 2;
+        x.n_kmers[v] = (uint16_t)K;
+        if (A > maxA) maxA = A;
+        if (K > maxK) maxK = K;
+        if (A > 32u) x.list_big.push_back(v);
+        if (A != 2) two_alleles = false;
+        const bool bi = A == 2 && K <= 32u;
+        if (bi) n_bi += 1;
+        else if (!listing && (fast_ok || small_shape)) {
+            listing = true;
+            x.list_b.resize(v);
+            for (uint32_t u = 0; u < v; ++u) x.list_b[u] = u;
+        }
+        if (listing) (bi ? x.list_b : (A >= 3 && A <= PG_AMAX && K <= 64u) ? x.list_m4 : x.list_w).push_back(v);
     }
-    force_generic = kc.generic; lean_ok = !kc.general && !kc.generic;
-    std::vector<char> wide_overflow(n_index, 0);
-    parallel_contigs(n_index, batches, [&](uint32_t i) {
-        const pg_contig_batch& b = batches[i];
-        IndexHost& x = job->index[i];
-        x.V = b.n_variants; x.H = b.n_paths; x.HP = pad_paths(x.H ? x.H : 1);
-        x.T = pgk_threads_for_hp(x.HP); x.RB = pg_rec_bytes(x.HP);
-        x.sumK = x.V ? b.kmer_off[x.V] : 0; x.sumA = x.V ? b.allele_off[x.V] : 0;
-        x.goff.assign((size_t)x.V + 1, 0);
-        x.n_kmers.resize(x.V);
-        if (x.V) { x.koff.assign(b.kmer_off, b.kmer_off + x.V + 1); x.aoff.assign(b.allele_off, b.allele_off + x.V + 1); }
-        uint64_t maxA = 1, woff = 0;
-        bool two_alleles = true;
-        uint32_t maxK = 0, n_bi = 0;
+    // prep_fast 1 = the whole chain is k_prep_bi's objects, 2 = at least half of it (k_prep takes the rest: HPRC-style panels and the
+    // 15 + 1 sampled paths have a fifth of their objects multiallelic); PG_KERNELS=prepwave: k_prep for everything (cross-check)
+    x.all_sb = two_alleles && maxK <= 32u;
+    x.prep_fast = !fast_ok ? 0u : (x.all_sb ? 1u : (2u * n_bi >= x.V ? 2u : 0u));
+    // (the same lists serve the split path's emission kernels — 16-path chains, whatever the share of biallelic objects)
+    if (!(x.prep_fast == 2u || (small_shape && !x.all_sb))) {
+        std::vector<uint32_t>().swap(x.list_b); std::vector<uint32_t>().swap(x.list_m4); std::vector<uint32_t>().swap(x.list_w);
+    }
+    x.n_lik = x.goff[x.V];
+    x.pair_n = (uint32_t)(maxA < PG_AMAX ? maxA : PG_AMAX);
+    x.part_slots = (x.pair_n + 1u) & ~1u;  // partials are stored as allele pairs (16-byte stores)
+    if (x.part_slots < 2) x.part_slots = 2;
+    x.lean = lean_ok && x.HP == 64 && x.H == 64 && maxA == 2 && x.V > 0;
+    x.small = small_shape && maxA == 2 && x.V > 0;   // (and enough of them: choose_job_mode)
+    // the same shape with multiallelic objects — 15 sampled paths + the reference path, bubbles keeping every allele those
+    // paths carry (src/commands.cpp:799-803, src/multiallelicuniquekmers.cpp:195-232): k_sweep_small16x, any allele count
+    // per object (narrow columns from the record's table, wide ones from the side table: per COLUMN)
+    x.smallx = small_shape && maxA > 2 && x.V > 0;
+    // PG_KERNELS=nocls4: per-thread partials + k_bins (cross-check)
+    // (the class sums are formed by a half-chain's ONE compute wave: 16 paths, and 32 when the kernel is built with 16 rows per lane)
+    x.cls4 = (x.HP == 16 || (x.HP == 32 && pgk_threads_for_hp(32) == 64u)) && x.H == x.HP && maxA == 2 && x.V > 0 && !kc.nocls4;
+    // PG_KERNELS=noleanx: the general kernel (cross-check)
+    x.leanx = lean_ok && (x.HP == 128 || x.HP == 64) && !x.lean && maxA >= 1 && maxA <= PG_AMAX && x.V > 0 && kc.leanx != 0;
+    // Variants with more than PG_AMAX alleles may turn into WIDE columns (as many distinct alleles on the selected paths): a wide
+    // entry with room for min(A, H) local alleles each.  Aux slots, where a fused phase 2 leaves what k_bins_x / k_bins_wide
+    // finish: smallx chains — a variant with 3 .. PG_AMAX alleles as its (up to) fifteen bins (128 bytes), one with more as a whole
+    // column (or as bins, if its paths carry at most PG_AMAX of them); 64-path chains of the general kernel (DevContig::widef) —
+    // one column (8 HP^2 bytes) for every variant that may turn into a wide column.
+    const bool wide = maxA > PG_AMAX;
+    const bool widef_shape = x.HP == 64 && wide && x.V > 0 && !kc.nowidef && !kc.generic && params.run_genotyping && !params.run_phasing;
+    if (wide || x.smallx) {
+        const bool aux_x = x.smallx;
+        const uint64_t bins_slot = 128u /* fifteen bins */, col_slot = (uint64_t)x.HP * x.HP * 8u;
+        uint64_t woff = 0, ao = 0;
+        if (wide) x.widx.assign(x.V, PG_WIDE_NONE);
+        if (aux_x || widef_shape) x.auxidx.assign(x.V, PG_WIDE_NONE);
         for (uint32_t v = 0; v < x.V; ++v) {
             const uint64_t A = b.allele_off[v + 1] - b.allele_off[v];
-            x.goff[v + 1] = x.goff[v] + A * (A + 1) / 2;
-            if (A > maxA) maxA = A;
-            if (A > 32u) x.list_big.push_back(v);
-            if (A != 2) two_alleles = false;
-            x.n_kmers[v] = (uint16_t)(b.kmer_off[v + 1] - b.kmer_off[v]);
-            if (b.kmer_off[v + 1] - b.kmer_off[v] > maxK) maxK = b.kmer_off[v + 1] - b.kmer_off[v];
-            if (A == 2 && b.kmer_off[v + 1] - b.kmer_off[v] <= 32u) n_bi += 1;
-        }
-        {
-            // k_prep_bi (four variants per wave) takes the two-allele objects with <= 32 k-mers of chains with <= 64 paths:
-            // 1 = the whole chain is such objects, 2 = at least half of it (k_prep takes the rest: HPRC-style panels and the
-            // 15 + 1 sampled paths have a fifth of their objects multiallelic); PG_KERNELS=prepwave: k_prep for everything (cross-check)
-            const bool ok = x.H <= 64u && x.V > 0 && !kc.prepwave;
-            x.prep_fast = !ok ? 0u : ((two_alleles && maxK <= 32u) ? 1u : (2u * n_bi >= x.V ? 2u : 0u));
-            x.all_sb = two_alleles && maxK <= 32u;
-            // (the same lists serve the split path's emission kernels — 16-path chains, whatever the share of biallelic objects)
-            if (x.prep_fast == 2u || (lean_ok && x.HP == 16u && x.H == 16u && !x.all_sb)) {   // who prepares what: k_prep_bi scans the chain for its own, the others walk lists
-                for (uint32_t v = 0; v < x.V; ++v) {
-                    const uint64_t A = b.allele_off[v + 1] - b.allele_off[v];
-                    const uint32_t Kv = b.kmer_off[v + 1] - b.kmer_off[v];
-                    if (A == 2 && Kv <= 32u) { x.list_b.push_back(v); continue; }
-                    if (A >= 3 && A <= PG_AMAX && Kv <= 64u) x.list_m4.push_back(v);
-                    else x.list_w.push_back(v);
-                }
+            if (A <= 2) continue;
+            const bool cand = A > PG_AMAX;
+            if (cand) {
+                uint64_t nl = A < x.H ? A : x.H;
+                if (nl > PG_WIDE_MAX) nl = PG_WIDE_MAX;
+                x.widx[v] = (uint32_t)(woff / 16);
+                woff += pg_wide_entry_bytes((uint32_t)nl);
+                if (woff / 16 >= 0xFFFFFFF0ull) return false;
             }
+            if (!aux_x && !(widef_shape && cand)) continue;
+            x.auxidx[v] = (uint32_t)(ao / 16);
+            if (cand) x.n_wide_cand += 1;
+            ao += !cand ? bins_slot : (aux_x && bins_slot > col_slot) ? bins_slot : col_slot;
         }
-        x.n_lik = x.goff[x.V];
-        x.pair_n = (uint32_t)(maxA < PG_AMAX ? maxA : PG_AMAX);
-        x.part_slots = (x.pair_n + 1u) & ~1u;  // partials are stored as allele pairs (16-byte stores)
-        if (x.part_slots < 2) x.part_slots = 2;
-        if (maxA > PG_AMAX) {
-            // variants with more than PG_AMAX alleles may turn into WIDE columns (as many distinct alleles
-            // on the selected paths): room for min(A, H) local alleles each
-            x.widx.assign(x.V, PG_WIDE_NONE);
-            for (uint32_t v = 0; v < x.V; ++v) {
-                const uint64_t A = b.allele_off[v + 1] - b.allele_off[v];
-                if (A > PG_AMAX) {
-                    uint64_t nl = A < x.H ? A : x.H;
-                    if (nl > PG_WIDE_MAX) nl = PG_WIDE_MAX;
-                    x.widx[v] = (uint32_t)(woff / 16);
-                    woff += pg_wide_entry_bytes((uint32_t)nl);
-                    if (woff / 16 >= 0xFFFFFFF0ull) { wide_overflow[i] = 1; return; }
-                }
-            }
-            x.wide_bytes = woff;
-        }
-        x.lean = lean_ok && x.HP == 64 && x.H == 64 && maxA == 2 && x.V > 0;
-        x.small = lean_ok && x.HP == 16 && x.H == 16 && maxA == 2 && x.V > 0;   // (and enough of them: below)
-        // the same shape with multiallelic objects — 15 sampled paths + the reference path, bubbles keeping every allele those
-        // paths carry (src/commands.cpp:799-803, src/multiallelicuniquekmers.cpp:195-232): k_sweep_small16x, any allele count
-        // per object (narrow columns from the record's table, wide ones from the side table: per COLUMN)
-        x.smallx = lean_ok && x.HP == 16 && x.H == 16 && maxA > 2 && x.V > 0;
-        if (x.smallx) {
-            // aux slots: a variant with 3 .. PG_AMAX alleles leaves phase 2 as its (up to) fifteen bins (128 bytes), one with
-            // more as a whole column (a wide column) — or as bins, if its paths carry at most PG_AMAX of them
-            x.auxidx.assign(x.V, PG_WIDE_NONE);
-            uint64_t ao = 0;
-            for (uint32_t v = 0; v < x.V; ++v) {
-                const uint64_t A = b.allele_off[v + 1] - b.allele_off[v];
-                if (A <= 2) continue;
-                const uint64_t small_slot = 128u /* fifteen bins */, col_slot = (uint64_t)x.HP * x.HP * 8u;
-                x.auxidx[v] = (uint32_t)(ao / 16);
-                if (A > PG_AMAX) x.n_wide_cand += 1;
-                ao += A > PG_AMAX ? (col_slot > small_slot ? col_slot : small_slot) : small_slot;
-            }
-            if (ao / 16 >= 0xFFFFFFF0ull) x.smallx = false;   // (the general kernel then)
-            else x.aux_bytes = ao;
-        }
-        {
-            // PG_KERNELS=nocls4: per-thread partials + k_bins (cross-check)
-            // (the class sums are formed by a half-chain's ONE compute wave: 16 paths, and 32 when the kernel is built with 16 rows per lane)
-            x.cls4 = (x.HP == 16 || (x.HP == 32 && pgk_threads_for_hp(32) == 64u)) && x.H == x.HP && maxA == 2 && x.V > 0 && !kc.nocls4;
-        }
-        {
-            // PG_KERNELS=noleanx: the general kernel (cross-check)
-            x.leanx = lean_ok && (x.HP == 128 || x.HP == 64) && !x.lean && maxA >= 1 && maxA <= PG_AMAX && x.V > 0 && kc.leanx != 0;
-        }
-        if (x.HP == 64 && maxA > PG_AMAX && x.V > 0 && !kc.nowidef && !force_generic && params->run_genotyping && !params->run_phasing) {
-            // DevContig::widef: an aux slot of one column (8 HP^2 bytes) for every variant that may turn into a wide column
-            x.auxidx.assign(x.V, PG_WIDE_NONE);
-            uint64_t ao = 0;
-            for (uint32_t v = 0; v < x.V; ++v) {
-                const uint64_t A = b.allele_off[v + 1] - b.allele_off[v];
-                if (A <= PG_AMAX) continue;
-                x.auxidx[v] = (uint32_t)(ao / 16);
-                x.n_wide_cand += 1;
-                ao += (uint64_t)x.HP * x.HP * 8u;
-            }
-            if (ao / 16 < 0xFFFFFFF0ull) { x.aux_bytes = ao; x.widef_cand = true; }
+        if (wide) x.wide_bytes = woff;
+        const bool fits = ao / 16 < 0xFFFFFFF0ull;
+        if (aux_x) { if (fits) x.aux_bytes = ao; else x.smallx = false; }   // (the general kernel then)
+        if (widef_shape) {
+            if (fits) { x.aux_bytes = ao; x.widef_cand = true; }
             else { x.auxidx.clear(); x.n_wide_cand = 0; }
         }
-    });
-    for (uint32_t i = 0; i < n_index; ++i) {
-        const IndexHost& x = job->index[i];
-        if (wide_overflow[i]) { pg_job_destroy(job); set_err(err, errlen, "wide-column tables exceed 64 GB"); return PG_ERR_UNSUPPORTED; }
-        if (x.wide_bytes) wide_candidates = true;
-        if (x.HP >= 256) generic_needed = true;
-        if (x.V > max_v) max_v = x.V;
     }
-    job->max_v = max_v;
-    lap("index planning");
+    return true;
+}
+
+int classify_index(pg_job* job, const BuildArgs& a, char* err, size_t errlen) {
+    job->index.resize(a.n_index);
+    std::vector<char> ok(a.n_index, 1);
+    parallel_contigs(a.n_index, a.batches, [&](uint32_t i) { ok[i] = classify_index_contig(a.batches[i], a.kc, a.params, job->index[i]); });
+    for (uint32_t i = 0; i < a.n_index; ++i) {
+        if (!ok[i]) { set_err(err, errlen, "wide-column tables exceed 64 GB"); return PG_ERR_UNSUPPORTED; }
+        job->max_v = std::max(job->max_v, job->index[i].V);
+    }
+    return PG_OK;
+}
+
+// The job's mode, decided from the classified contigs: which of the kernels a contig's shape allows its chains get (the small
+// kernels' crossover), fused or chunked, the chunk size, the persistent pair, the split path.  chunk_cap: 0, or the most chunk
+// columns this attempt may plan for (job_build's retry of a chunked job whose arena did not fit).  No device objects are made.
+void choose_job_mode(pg_job* job, const BuildArgs& a, size_t chunk_cap) {
+    const KernelChoice& kc = a.kc;
+    const pg_hmm_params& params = a.params;
+    const uint32_t n_chains = (uint32_t)a.specs.size();
+    job->persist = false; job->post_blocks = 0; job->any_split = false;
     {
         // k_sweep_small16 packs four H = 16 half-chains into a wave: a throughput kernel.  A single chain is faster on the
         // general kernel (four states per lane instead of sixteen: 375 vs 470 ns per column); PG_KERNELS=small / nosmall forces.
@@ -1081,7 +1064,7 @@ int job_build(int device, uint32_t n_index, const pg_contig_batch* batches, cons
         // -> from 256 chains on when every such chain is biallelic, from 320 when some have multiallelic objects (512 for both
         //    until round 6: a 256-chain biallelic cohort ran 14 % below what it could).
         size_t n_small_chains = 0, n_x_chains = 0;
-        for (const ChainSpec& sp : specs) {
+        for (const ChainSpec& sp : a.specs) {
             n_small_chains += (job->index[sp.index].small || job->index[sp.index].smallx) ? 1 : 0;
             n_x_chains += job->index[sp.index].smallx ? 1 : 0;
         }
@@ -1091,137 +1074,283 @@ int job_build(int device, uint32_t n_index, const pg_contig_batch* batches, cons
     // A WIDE column (more than PG_AMAX alleles on the selected paths) costs that column, not the job, on the kernels that
     // take it inside a fused phase 2 — k_sweep_small16x (its column goes to the aux slot, k_bins_wide forms the bins); a
     // chain of any other kernel with such an object still makes the job chunked (k_post is their only wide path)
-    wide_candidates = false;
+    bool wide_candidates = false, generic_needed = false;
     for (const IndexHost& x : job->index) {
         // (a k_sweep_small16x chain left with ONE column that is wide has its bins formed by k_bins_wide_s — the split path; jobs
         //  that cannot take the split path — run_phasing, 2^32 bins — go chunked as before round 5 instead of failing such a chain
         //  with PG_DEVERR_WIDE_FUSED at run time.  PG_KERNELS=nosplit keeps the fused job: a cross-check switch.)
-        const bool split_possible = kc.nosplit || (!params->run_phasing && params->run_genotyping && x.n_lik < 0xFFFFFFF0ull);
+        const bool split_possible = kc.nosplit || (!params.run_phasing && params.run_genotyping && x.n_lik < 0xFFFFFFF0ull);
         if (x.wide_bytes && !(x.smallx && !kc.nosmall2 && split_possible) && !x.widef_cand) wide_candidates = true;
+        if (x.HP >= 256) generic_needed = true;
     }
-
     // ---- sweep mode ------------------------------------------------------------------------
-    {
-        size_t per_col = 0;  // scratch bytes per chunk column over all chains (PG_SCRATCH_BUFS buffers x 2 roles)
-        for (const ChainSpec& sp : specs) { const IndexHost& x = job->index[sp.index]; per_col += (size_t)2 * PG_SCRATCH_BUFS * x.HP * x.HP * sizeof(double); }
-        // wide columns of chains that are not k_sweep_small16x's (wide_candidates, above) and HP >= 256 have their posteriors formed by k_post only: such jobs always run chunked
-        bool want = n_chains * 2u < 128u;  // fewer workgroups than half the CUs
-        // merged one-shot calls (cache_arena): always the mode — and with it the kernels — every one of them runs alone, so
-        // that a caller's result does not depend on who else happened to be in flight (bit for bit, by construction)
-        if (cache_arena) want = true;
-        if (const char* m = getenv("PG_SWEEP_MODE")) {
-            if (!strcmp(m, "fused")) want = false;
-            else if (!strcmp(m, "chunked")) want = true;
-        }
-        if (wide_candidates || generic_needed || force_generic) want = true;
-        job->chunked = want && max_v > 0 && params->run_genotyping;
-        // k_sweep_leanx is a latency kernel (lone chains: 1470 vs 2645 ns per column at 128 paths); phase 1 of a fused job
-        // with hundreds of chains is bound by HBM writes, where the general kernel measured faster (7.8 vs 8.9 ms on 128 chains
-        // of 128 paths).  PG_KERNELS=leanx forces it there too.
-        if (job->chunked) for (auto& x : job->index) { x.cls4 = false; x.aux_bytes = 0; }   // (chunked jobs form their posteriors in k_post)
-        if (kc.nosmall2) for (auto& x : job->index) if (!x.widef_cand) x.aux_bytes = 0;
-        for (auto& x : job->index) x.widef = x.widef_cand && !job->chunked && x.aux_bytes != 0;
-        if (!job->chunked) {
-            if (kc.leanx != 1) for (auto& x : job->index) x.leanx = false;
-        }
-        if (job->chunked) {
-            // 8192 columns per chunk (round 6; 4096 before): 25 chunk rounds instead of 50 on the whole genome.  With k_post no longer
-            // the bound (post_lean64, the idle CUs shared out over the chains still running) what a chunk round costs beyond its columns
-            // is its launches and resume prologues, and how much THAT is varies from box to box: 4096 / 6144 / 8192 / 12288 columns:
-            // 128.7 / 128.5 / 126.9 / - ms of phase 2 on one box, 133.8 / 127.8 / 127.9 / 127.5 on another (profiles/r06_persist.txt 8).
-            size_t k = 8192;
-            const size_t budget = (size_t)39 << 30;   // (three buffers: 8192 columns for the 24 chains of a whole genome at 64 paths)
-            if (per_col * k > budget) k = budget / per_col;
-            if (const char* e = getenv("PG_CHUNK_COLS")) { const long v = strtol(e, nullptr, 0); if (v > 0) k = (size_t)v; }
-            if (chunk_cap && k > chunk_cap) k = chunk_cap;
-            const size_t half = (size_t)max_v / 2 + 1;
-            if (k > half) k = half;
-            if (k < 1) k = 1;
-            job->chunk_cols = (uint32_t)k;
-            job->n_chunks = (uint32_t)((half + k - 1) / k);
-            if ((he = hipStreamCreateWithFlags(&job->stream2, hipStreamNonBlocking)) != hipSuccess) return fail(PG_ERR_DEVICE, "hipStreamCreate", he);
-            for (int q = 0; q < (int)PG_SCRATCH_BUFS; ++q) {
-                if ((he = hipEventCreateWithFlags(&job->ev_sweep[q], hipEventDisableTiming)) != hipSuccess) return fail(PG_ERR_DEVICE, "hipEventCreate", he);
-                if ((he = hipEventCreateWithFlags(&job->ev_post[q], hipEventDisableTiming)) != hipSuccess) return fail(PG_ERR_DEVICE, "hipEventCreate", he);
-            }
-            job->events2 = true;
-            // the persistent phase 2: every chain a lean chain (or empty), an even chunk (the lean step runs two columns per loop
-            // iteration) unless a chunk is the whole half, and a CU for every workgroup of the two kernels that wait for each other
-            bool all_lean = kc.persist, any_lean = false;
-            for (const ChainSpec& sp : specs) { const IndexHost& x = job->index[sp.index]; if (x.V && !x.lean) all_lean = false; if (x.lean) any_lean = true; }
-            if (all_lean && any_lean && ((job->chunk_cols & 1u) == 0u || job->n_chunks == 1u)) {
-                uint32_t cus = 0;
-                uint32_t pb = pgk_post_blocks((uint32_t)n_chains, job->chunk_cols, &cus);
-                // (the sweep's workgroups MUST all be running — a k_post_loop block that is not merely takes no work —: eight CUs are
-                //  left free beside the two grids, whatever else may hold a CU)
-                const uint32_t margin = 8u;
-                if (n_chains <= 64u && cus > 2u * n_chains + margin) {   // (k_post_loop looks at all chains with one lane each)
-                    const uint32_t room = (cus - 2u * n_chains - margin) / n_chains;
-                    if (pb > room) pb = room;
-                    if (const char* e = getenv("PG_POST_BLOCKS")) { const long v = strtol(e, nullptr, 0); if (v >= 1 && (uint32_t)v < pb) pb = (uint32_t)v; }   // (experiments: fewer)
-                    if (pb >= 1u) { job->persist = true; job->post_blocks = pb; }
-                }
+    size_t per_col = 0;  // scratch bytes per chunk column over all chains (PG_SCRATCH_BUFS buffers x 2 roles)
+    for (const ChainSpec& sp : a.specs) { const IndexHost& x = job->index[sp.index]; per_col += (size_t)2 * PG_SCRATCH_BUFS * x.HP * x.HP * sizeof(double); }
+    // wide columns of chains that are not k_sweep_small16x's (wide_candidates, above) and HP >= 256 have their posteriors formed by k_post only: such jobs always run chunked
+    bool want = n_chains * 2u < 128u;  // fewer workgroups than half the CUs
+    // merged one-shot calls (cache_arena): always the mode — and with it the kernels — every one of them runs alone, so
+    // that a caller's result does not depend on who else happened to be in flight (bit for bit, by construction)
+    if (a.cache_arena) want = true;
+    if (const char* m = getenv("PG_SWEEP_MODE")) {
+        if (!strcmp(m, "fused")) want = false;
+        else if (!strcmp(m, "chunked")) want = true;
+    }
+    if (wide_candidates || generic_needed || kc.generic) want = true;
+    job->chunked = want && job->max_v > 0 && params.run_genotyping;
+    if (job->chunked) for (auto& x : job->index) { x.cls4 = false; x.aux_bytes = 0; }   // (chunked jobs form their posteriors in k_post)
+    if (kc.nosmall2) for (auto& x : job->index) if (!x.widef_cand) x.aux_bytes = 0;
+    for (auto& x : job->index) x.widef = x.widef_cand && !job->chunked && x.aux_bytes != 0;
+    // k_sweep_leanx is a latency kernel (lone chains: 1470 vs 2645 ns per column at 128 paths); phase 1 of a fused job
+    // with hundreds of chains is bound by HBM writes, where the general kernel measured faster (7.8 vs 8.9 ms on 128 chains
+    // of 128 paths).  PG_KERNELS=leanx forces it there too.
+    if (!job->chunked && kc.leanx != 1) for (auto& x : job->index) x.leanx = false;
+    if (job->chunked) {
+        // 8192 columns per chunk (round 6; 4096 before): 25 chunk rounds instead of 50 on the whole genome.  With k_post no longer
+        // the bound (post_lean64, the idle CUs shared out over the chains still running) what a chunk round costs beyond its columns
+        // is its launches and resume prologues, and how much THAT is varies from box to box: 4096 / 6144 / 8192 / 12288 columns:
+        // 128.7 / 128.5 / 126.9 / - ms of phase 2 on one box, 133.8 / 127.8 / 127.9 / 127.5 on another (profiles/r06_persist.txt 8).
+        size_t k = 8192;
+        const size_t budget = (size_t)39 << 30;   // (three buffers: 8192 columns for the 24 chains of a whole genome at 64 paths)
+        if (per_col * k > budget) k = budget / per_col;
+        if (const char* e = getenv("PG_CHUNK_COLS")) { const long v = strtol(e, nullptr, 0); if (v > 0) k = (size_t)v; }
+        if (chunk_cap && k > chunk_cap) k = chunk_cap;
+        const size_t half = (size_t)job->max_v / 2 + 1;
+        if (k > half) k = half;
+        if (k < 1) k = 1;
+        job->chunk_cols = (uint32_t)k;
+        job->n_chunks = (uint32_t)((half + k - 1) / k);
+        // the persistent phase 2: every chain a lean chain (or empty), an even chunk (the lean step runs two columns per loop
+        // iteration) unless a chunk is the whole half, and a CU for every workgroup of the two kernels that wait for each other
+        bool all_lean = kc.persist, any_lean = false;
+        for (const ChainSpec& sp : a.specs) { const IndexHost& x = job->index[sp.index]; if (x.V && !x.lean) all_lean = false; if (x.lean) any_lean = true; }
+        if (all_lean && any_lean && ((job->chunk_cols & 1u) == 0u || job->n_chunks == 1u)) {
+            uint32_t cus = 0;
+            uint32_t pb = pgk_post_blocks(n_chains, job->chunk_cols, &cus);
+            // (the sweep's workgroups MUST all be running — a k_post_loop block that is not merely takes no work —: eight CUs are
+            //  left free beside the two grids, whatever else may hold a CU)
+            const uint32_t margin = 8u;
+            if (n_chains <= 64u && cus > 2u * n_chains + margin) {   // (k_post_loop looks at all chains with one lane each)
+                const uint32_t room = (cus - 2u * n_chains - margin) / n_chains;
+                if (pb > room) pb = room;
+                if (const char* e = getenv("PG_POST_BLOCKS")) { const long v = strtol(e, nullptr, 0); if (v >= 1 && (uint32_t)v < pb) pb = (uint32_t)v; }   // (experiments: fewer)
+                if (pb >= 1u) { job->persist = true; job->post_blocks = pb; }
             }
         }
     }
-
     // ---- the split path: which index contigs' chains take it (pg_device.h) ---------------------------
     for (auto& x : job->index) {
-        const bool s1 = x.small && !job->chunked && x.cls4 && !kc.nosmall2;   // (DevContig::small == 2 below)
+        const bool s1 = x.small && !job->chunked && x.cls4 && !kc.nosmall2;   // (DevContig::small == 2)
         const bool s2 = x.smallx && !job->chunked && !kc.nosmall2;            // (DevContig::smallx == 2)
-        const bool ok = !kc.nosplit && !params->run_phasing && params->run_genotyping && x.n_lik < 0xFFFFFFF0ull && x.V > 0;
+        const bool ok = !kc.nosplit && !params.run_phasing && params.run_genotyping && x.n_lik < 0xFFFFFFF0ull && x.V > 0;
         x.split = !ok ? 0u : (s1 ? 1u : (s2 ? 2u : 0u));
         if (x.split) job->any_split = true;
     }
+}
 
-    // ---- plan the arena -----------------------------------------------------------------------
-    job->chains.resize(n_chains);
+// ---- which kernels run a chain -------------------------------------------------------------
+// A kernel's identity; its row of the table gives its launch bits (pg_launch.h) and its name in the plan text (pg_job_plan):
+// the launch masks and the text are both made from a chain's ChainKernels and from nothing else.
+enum SweepKernel : uint8_t {
+    SW_NONE, SW_HP16, SW_HP32, SW_HP64, SW_HP128, SW_GENERIC, SW_GENERIC64, SW_LEAN, SW_LEAN_TRI, SW_LEAN2, SW_LEANX128, SW_LEANX64,
+    SW_TRI1, SW_LEANX_TRI, SW_LEANX_TRIW, SW_LEANX2, SW_SMALL16, SW_SMALL16X, SW_COUNT
+};
+// (phased: the phase is a template argument, "<1>" .. "<4>" in the text.  PG_SWEEP_TRI goes with every kernel that stores
+//  triangles: the launcher reads it beside PG_SWEEP_LEAN only.  The four-half-chains-per-wave kernels have no bit: they walk
+//  chain-id lists, pgk_launch_sweep_small / _smallx.)
+struct SweepRow { uint32_t bits; const char* name; bool phased; };
+const SweepRow kSweep[SW_COUNT] = {
+    {0u, "", false},
+    {PG_SWEEP_HP16, "k_sweep<16,4>", true}, {PG_SWEEP_HP32, "k_sweep<32,8>", true},
+    {PG_SWEEP_HP64, "k_sweep<64,16>", true}, {PG_SWEEP_HP128, "k_sweep<128,32>", true},
+    {PG_SWEEP_GENERIC, "k_sweep_generic", true},
+    {PG_SWEEP_GENERIC64 | PG_SWEEP_GENERIC /* one generic launch covers both */, "k_sweep_generic", true},
+    {PG_SWEEP_LEAN, "k_sweep_lean", true}, {PG_SWEEP_LEAN | PG_SWEEP_TRI, "k_sweep_lean_tri", true}, {PG_SWEEP_LEAN2, "k_sweep_lean2", false},
+    {PG_SWEEP_LEANX128, "k_sweep_leanx", true}, {PG_SWEEP_LEANX64, "k_sweep_leanx", true},
+    {PG_SWEEP_TRI1 | PG_SWEEP_TRI, "k_sweep_tri1", false}, {PG_SWEEP_LEANX_TRI | PG_SWEEP_TRI, "k_sweep_leanx_tri", false},
+    {PG_SWEEP_LEANX_TRIW | PG_SWEEP_TRI, "k_sweep_leanx_triw", false}, {PG_SWEEP_LEANX2, "k_sweep_leanx2", false},
+    {0u, "k_sweep_small16", true}, {0u, "k_sweep_small16x", true}
+};
+enum BinsKernel : uint8_t { BN_NONE, BN_FULL, BN_LEAN2, BN_THIN, BN_X, BN_WIDE, BN_S, BN_WIDE_S, BN_Q, BN_COUNT };
+struct BinsRow { uint32_t bit; const char* name; };
+const BinsRow kBins[BN_COUNT] = {{0u, ""}, {PG_BINS_FULL, "k_bins"}, {PG_BINS_LEAN2, "k_bins_lean2"}, {PG_BINS_THIN, "k_bins_thin"}, {PG_BINS_X, "k_bins_x"},
+                                 {PG_BINS_WIDE, "k_bins_wide"}, {PG_BINS_S, "k_bins_s"}, {PG_BINS_WIDE_S, "k_bins_wide_s"}, {PG_BINS_Q, "k_bins_q"}};
+enum PrepKernels : uint8_t { PREP_S_BI, PREP_S_LISTS, PREP_BI, PREP_BI_LISTS, PREP_W, PREP_COUNT };
+const char* const kPrepName[PREP_COUNT] = {
+    "index pass once (k_index_scan, k_compact, k_index_cols); per run k_prep_s_bi",
+    "index pass once (k_index_scan, k_compact, k_index_cols); per run k_prep_s_bi + k_prep_s_m4 + k_prep_s_w",
+    "index pass once (k_index_scan, k_compact); per run k_prep_bi + k_records",
+    "index pass once (k_index_scan, k_compact); per run k_prep_bi + k_prep_m4 + k_prep + k_records",
+    "index pass once (k_index_scan, k_compact); per run k_prep + k_records"
+};
+enum PostKernels : uint8_t { POST_NONE, POST_CHUNKS, POST_LOOP };   // fused: bins | k_post per chunk | the persistent pair's k_post_loop
+
+struct ChainKernels {
+    PrepKernels prep = PREP_W;
+    SweepKernel phase1 = SW_NONE;
+    SweepKernel phase2 = SW_NONE;    // fused jobs: the posterior half; chunked jobs: the store-only kernel of every chunk
+    // the general (or generic) kernel whose launches walk this chain too, SW_NONE: none does.  It does a phase that has no kernel
+    // of its own and returns at once in the others
+    SweepKernel general = SW_NONE;
+    PostKernels post = POST_NONE;
+    BinsKernel bins = BN_NONE;       // who forms the chain's bins in a fused job ...
+    BinsKernel bins_one = BN_NONE;   // ... those of a k_sweep_small16x chain left with a single column
+    BinsKernel bins_wide = BN_NONE;  // ... and those of its wide columns
+    // the values of the DevContig fields of the same names
+    uint32_t lean = 0, leanx = 0, leanx2 = 0, tri = 0, cls4 = 0, small = 0, smallx = 0, widef = 0, T = 0;
+};
+
+// Every chain's kernels from its index contig's class and the job's mode; from them the two launch masks.
+std::vector<ChainKernels> choose_chain_kernels(pg_job* job, const BuildArgs& a) {
+    const KernelChoice& kc = a.kc;
+    const bool fused = !job->chunked;
+    std::vector<ChainKernels> kernels(a.specs.size());
+    job->hp_mask = 0; job->bins_which = 0; job->vit_bits = 0;
+    for (size_t c = 0; c < kernels.size(); ++c) {
+        const IndexHost& x = job->index[a.specs[c].index];
+        ChainKernels& k = kernels[c];
+        // fused jobs: lean chains store / read their columns as compact upper triangles (18 KB instead of 32 KB per
+        // column: half the sweep's HBM bytes and of the arena); PG_KERNELS=notri keeps full columns (cross-check)
+        // (round 6: and the 64-path chains with multiallelic objects — every column narrow — whose phase 1 runs on the general
+        //  kernel: it stores the same triangles, phase 2 reads them through its triangle ring: DevContig::tri == 1)
+        // (DevContig::widef chains too: their wide columns leave phase 2 through aux slots, k_bins_wide reads the stored triangle)
+        const bool tri_multi = !x.lean && !x.leanx && x.HP == 64 && x.H == 64 && (!x.wide_bytes || x.widef) && x.pair_n > 2 && !kc.generic && !kc.general;
+        const bool tri = (x.lean || tri_multi) && fused && !kc.notri;
+        k.lean = x.lean ? 1u : 0u; k.cls4 = x.cls4 ? 1u : 0u; k.widef = x.widef ? 1u : 0u; k.T = part_entries(x);
+        k.small = x.small ? ((fused && x.cls4 && !kc.nosmall2) ? 2u : 1u) : 0u;   // 2: phase 2 on k_sweep_small16 too (class sums)
+        k.smallx = x.smallx ? ((fused && !kc.nosmall2) ? 2u : 1u) : 0u;
+        k.tri = tri ? ((kc.nolean2 || !x.lean) ? 1u : 2u) : 0u;   // (PG_KERNELS=nolean2, and chains with multiallelic objects: phase 2 of triangle chains on the general kernel's triangle ring)
+        if (k.tri == 1u && !x.lean && x.HP == 64u && !kc.noleanx2 && !a.params.run_phasing && !x.widef) { k.leanx2 = 1u; k.T = 64u; }   // phase 2 on k_sweep_leanx2 (no wide columns there)
+        // phase 1 of the triangle chains that are not lean chains: the lean-x step with triangle stores (DevContig::leanx == 2; it
+        // needs the column-order records of the general kernel, which phase 2 reads too) — PG_KERNELS=noleanx: the general kernel
+        // with triangle stores (k_sweep_tri1)
+        k.leanx = (k.tri && !x.lean && kc.leanx != 0) ? 2u : (x.leanx ? 1u : 0u);
+        k.prep = x.split ? (x.all_sb ? PREP_S_BI : PREP_S_LISTS) : x.prep_fast == 1u ? PREP_BI : x.prep_fast == 2u ? PREP_BI_LISTS : PREP_W;
+
+        const SweepKernel own = x.HP >= 256 ? SW_GENERIC : (kc.generic && x.HP >= 64) ? SW_GENERIC64
+                              : x.HP == 16 ? SW_HP16 : x.HP == 32 ? SW_HP32 : x.HP == 64 ? SW_HP64 : SW_HP128;
+        const SweepKernel leanx_kernel = x.HP == 128 ? SW_LEANX128 : SW_LEANX64;
+        // (split chains never run on the general kernel; nor do, in a chunked job — no phase 2 —, the chains whose store-only phases
+        //  have a kernel of their own: the general kernel's launch returned at once for them, fifty empty launches on the
+        //  whole-genome job's phase 2)
+        const bool walked = own == SW_GENERIC || own == SW_GENERIC64 || (!x.split && !(job->chunked && (x.lean || x.small || x.smallx || x.leanx)));
+        k.general = walked ? own : SW_NONE;
+        k.phase1 = k.lean ? (k.tri ? SW_LEAN_TRI : SW_LEAN) : k.leanx == 2u ? (k.widef ? SW_LEANX_TRIW : SW_LEANX_TRI) : k.leanx ? leanx_kernel
+                 : k.small ? SW_SMALL16 : k.smallx ? SW_SMALL16X : k.tri ? SW_TRI1 : own;
+        if (fused) k.phase2 = k.leanx2 ? SW_LEANX2 : k.tri == 2u ? SW_LEAN2 : k.small == 2u ? SW_SMALL16 : k.smallx == 2u ? SW_SMALL16X : own;
+        else k.phase2 = k.lean ? SW_LEAN : k.leanx ? leanx_kernel : k.small ? SW_SMALL16 : k.smallx ? SW_SMALL16X : own;
+        k.post = fused ? POST_NONE : job->persist ? POST_LOOP : POST_CHUNKS;
+        // (k_bins_thin: what bins_thin() in pg_kernels.hip says — at most 64 partial entries per column, fused job)
+        const BinsKernel own_bins = k.leanx2 ? BN_Q : (k.tri == 2u || k.cls4) ? BN_LEAN2 : (k.T <= 64u && x.HP <= 32u && fused) ? BN_THIN : BN_FULL;
+        if (x.split) { k.bins = BN_S; k.bins_wide = (x.split == 2u && x.wide_bytes) ? BN_WIDE_S : BN_NONE; }
+        else if (k.smallx == 2u) { k.bins = BN_X; k.bins_one = own_bins; k.bins_wide = x.wide_bytes ? BN_WIDE : BN_NONE; }
+        else { k.bins = own_bins; k.bins_wide = (k.widef && x.n_wide_cand) ? BN_WIDE : BN_NONE; }
+
+        job->hp_mask |= kSweep[k.phase1].bits | kSweep[k.phase2].bits | kSweep[k.general].bits;
+        job->bins_which |= kBins[k.bins].bit | kBins[k.bins_one].bit | kBins[k.bins_wide].bit;
+        if (a.params.run_phasing) job->vit_bits |= x.HP == 16 ? 1u : (x.HP == 32 ? 2u : 4u);
+    }
+    return kernels;
+}
+
+std::string sweep_name(SweepKernel k, int phase) {
+    const SweepRow& n = kSweep[k];
+    return n.phased ? std::string(n.name) + "<" + std::to_string(phase) + ">" : std::string(n.name);
+}
+
+// the plan as text (pg_job_plan): one line per group of chains with the same kernels
+std::string plan_text(const pg_job* job, const BuildArgs& a, const std::vector<ChainKernels>& kernels) {
+    struct Group { std::string text; uint32_t count = 0; };
+    std::vector<Group> groups;
+    for (size_t c = 0; c < kernels.size(); ++c) {
+        const IndexHost& x = job->index[a.specs[c].index];
+        const ChainKernels& k = kernels[c];
+        if (x.V == 0) continue;
+        // (PG_KERNELS=generic: the text has always named the generic kernel for chains below 64 paths too, which it does not
+        //  take — they run on k_sweep<HP>, as their launch bit says.  Kept: this text is what callers compare.)
+        auto name = [&](SweepKernel s, int phase) { return sweep_name(a.kc.generic && s >= SW_HP16 && s <= SW_HP128 ? SW_GENERIC : s, phase); };
+        std::string p2, bins;
+        if (k.post == POST_LOOP) { p2 = name(k.phase2, 4) + " (one launch, all chunks) + k_post_loop"; bins = "(k_post_loop)"; }
+        else if (k.post == POST_CHUNKS) { p2 = name(k.phase2, 3) + " chunks + k_post"; bins = "(k_post)"; }
+        else {
+            p2 = name(k.phase2, 2);
+            if (k.tri && k.phase2 == k.general) p2 += " (triangle ring)";
+            if (k.widef) p2 += " (wide columns to their aux slots)";
+            bins = kBins[k.bins].name;
+            if (k.bins_wide) bins += std::string(" + ") + kBins[k.bins_wide].name;
+        }
+        char head[160];
+        snprintf(head, sizeof(head), "%u path(s) (padded %u), %s%s%s columns: ", x.H, x.HP, x.pair_n > 2 ? "multiallelic" : "biallelic", x.wide_bytes ? " + wide" : "",
+                 k.tri ? ", triangle" : "");
+        const std::string text = std::string(head) + "prep = " + kPrepName[k.prep] + "; phase 1 = " + name(k.phase1, 1) + "; phase 2 = " + p2 + "; bins = " + bins;
+        bool found = false;
+        for (auto& g : groups) if (g.text == text) { g.count += 1; found = true; break; }
+        if (!found) groups.push_back({text, 1});
+    }
+    std::string out = std::string(job->chunked ? "chunked" : "fused") + " job, " + std::to_string(kernels.size()) + " chain(s)" + (a.params.run_phasing ? ", run_phasing (k_viterbi)" : "") + "\n";
+    for (const auto& g : groups) out += "  " + std::to_string(g.count) + " x " + g.text + "\n";
+    return out;
+}
+
+// ---- the arena ------------------------------------------------------------------------------
+// offsets of what the job as a whole and every chain own; those of an index contig's arrays are IndexHost's (o_*), a chain's
+// sample arrays ChainHost's
+struct ChainOffsets { size_t sync, wcols, wlist, aux, frec, scratch, wide, vpair, xbuf, prof, fback, fscale, bscale, bsum, vrec, colrec, fwd, part, cprec,
+                      vtq, vback, vbest, hap1, hap2; };
+struct ArenaLayout {
+    size_t o_contigs, o_reps, o_contigs_g, o_reps_g, o_small, o_dump, o_handshake, o_err, o_lik, o_likexp, o_ncols, o_ixerr;
+    size_t zero_lo, zero_hi, ix_lo, ix_hi, vrec_lo, vrec_hi, srec_lo, srec_hi;   // the runs that are zeroed as one
+    size_t bytes;
+    std::vector<ChainOffsets> chain;
+};
+
+// Only arithmetic: where everything lies.  The ORDER of the take() calls is the layout — alignment and the zeroed runs hang on it.
+ArenaLayout layout_arena(pg_job* job, const BuildArgs& a, const std::vector<ChainKernels>& kernels) {
+    const uint32_t n_chains = (uint32_t)a.specs.size(), n_index = a.n_index;
+    const bool vit = a.params.run_phasing != 0;
+    const bool geno = a.params.run_genotyping != 0;  // (a phasing-only job has no sweep: no columns, no partials)
+    ArenaLayout L;
+    L.chain.resize(n_chains);
     size_t off = 0;
     auto take = [&](size_t bytes, size_t al = 256) { off = align_up(off, al); size_t o = off; off += (bytes ? bytes : 8); return o; };
-    struct Plan { size_t sync, wcols, aux, frec, scratch, wide, vpair, xbuf, prof, fback, fscale, bscale, bsum, vrec, colrec, fwd, part, cprec,
-                  vtq, vback, vbest, hap1, hap2; };
-    std::vector<Plan> plan(n_chains);
-    const size_t o_contigs = take(sizeof(DevContig) * n_chains);
-    const size_t o_reps = take(sizeof(DevContig) * n_index);
-    const size_t o_contigs_g = take(sizeof(DevContig) * n_chains), o_reps_g = take(sizeof(DevContig) * n_index);   // (the pipelined first run: group order)
-    const size_t o_small = take(sizeof(uint32_t) * n_chains);   // chain ids of the H = 16 chains (k_sweep_small16)
-    const size_t o_dump = take(64 * 8 * 16 + 8 * 16 * 16 * 16);  // scrap column for the stores of its rows that are done
-    const size_t o_handshake = take(64);   // k_stream_handshake's words
+    L.o_contigs = take(sizeof(DevContig) * n_chains);
+    L.o_reps = take(sizeof(DevContig) * n_index);
+    L.o_contigs_g = take(sizeof(DevContig) * n_chains); L.o_reps_g = take(sizeof(DevContig) * n_index);   // (the pipelined first run: group order)
+    L.o_small = take(sizeof(uint32_t) * n_chains);   // chain ids of the H = 16 chains (k_sweep_small16)
+    L.o_dump = take(64 * 8 * 16 + 8 * 16 * 16 * 16);  // scrap column for the stores of its rows that are done
+    L.o_handshake = take(64);   // k_stream_handshake's words
     // zeroed-every-run block: n_cols, err, per chain kept / fallback flags / profile counters / allele_present,
     // then the packed lik and lik_exp regions (chain after chain, no gaps: one range each for a gather)
-    const size_t zero_lo = align_up(off);
-    const size_t o_err = take(sizeof(uint32_t) * n_chains);
+    L.zero_lo = align_up(off);
+    L.o_err = take(sizeof(uint32_t) * n_chains);
     uint64_t lik_total = 0;
     for (uint32_t c = 0; c < n_chains; ++c) {
         ChainHost& ch = job->chains[c];
-        ch.index = specs[c].index;
         const IndexHost& x = job->index[ch.index];
-        plan[c].fback = take(x.V);
-        plan[c].prof = take(64 * sizeof(unsigned long long));
-        plan[c].wcols = take(4);   // (the count of the chain's wide-column list: zeroed with the rest of this block; the list itself below)
-        plan[c].sync = take(job->chunked ? PG_SYNC_WORDS * sizeof(uint32_t) : 0);   // (chunk hand-over words of the persistent phase 2)
-        const bool vit = params->run_phasing != 0;
-        plan[c].vbest = take(vit ? 4 : 0);
-        plan[c].hap1 = take(vit ? (size_t)x.V * 2 : 0);
-        plan[c].hap2 = take(vit ? (size_t)x.V * 2 : 0);
+        ChainOffsets& p = L.chain[c];
+        p.fback = take(x.V);
+        p.prof = take(64 * sizeof(unsigned long long));
+        p.wcols = take(4);   // (the count of the chain's wide-column list: zeroed with the rest of this block; the list itself below)
+        p.sync = take(job->chunked ? PG_SYNC_WORDS * sizeof(uint32_t) : 0);   // (chunk hand-over words of the persistent phase 2)
+        p.vbest = take(vit ? 4 : 0);
+        p.hap1 = take(vit ? (size_t)x.V * 2 : 0);
+        p.hap2 = take(vit ? (size_t)x.V * 2 : 0);
         ch.lik_first = lik_total;
         lik_total += x.n_lik;
     }
     job->n_lik_total = lik_total;
-    const size_t o_lik = take(lik_total * sizeof(double));
-    const size_t o_likexp = take(lik_total * sizeof(int32_t));
-    const size_t zero_hi = off;
+    L.o_lik = take(lik_total * sizeof(double));
+    L.o_likexp = take(lik_total * sizeof(int32_t));
+    L.zero_hi = off;
     job->o_tab_m = take(job->tab_m.size() * sizeof(double));
     job->o_tab_e = take(job->tab_e.size() * sizeof(int32_t));
     job->o_tab_p = take(job->tab_p.size());
     // what the index alone decides, formed by the index-level kernels whenever an index is uploaded (pg_split.h): one run of the
     // arena, zeroed before every such pass — column flags, present alleles, the column list and its inverse for every index
     // contig; for split contigs the per-column records and the list of wide columns
-    const size_t ix_lo = align_up(off);
-    const size_t o_ncols = take(sizeof(uint32_t) * n_index);
-    const size_t o_ixerr = take(sizeof(uint32_t) * n_index);
-    for (uint32_t i = 0; i < n_index; ++i) {
-        IndexHost& x = job->index[i];
+    L.ix_lo = align_up(off);
+    L.o_ncols = take(sizeof(uint32_t) * n_index);
+    L.o_ixerr = take(sizeof(uint32_t) * n_index);
+    for (IndexHost& x : job->index) {
         x.o_kept = take(x.V); x.o_apres = take(x.sumA);
         x.o_colv = take((size_t)x.V * 4); x.o_colof = take((size_t)x.V * 4);
         x.o_ixpd = take(x.split ? (size_t)x.V * PG_IXPD_BYTES : 0);
@@ -1230,9 +1359,8 @@ int job_build(int device, uint32_t n_index, const pg_contig_batch* batches, cons
         x.o_ixwl = take(x.split == 2u && x.wide_bytes ? (size_t)x.n_wide_cand * 4 : 0);
         x.o_ixnw = take(4);
     }
-    const size_t ix_hi = off > ix_lo ? off : ix_lo;
-    for (uint32_t i = 0; i < n_index; ++i) {
-        IndexHost& x = job->index[i];
+    L.ix_hi = off > L.ix_lo ? off : L.ix_lo;
+    for (IndexHost& x : job->index) {
         x.o_pos = take((size_t)x.V * 8);
         x.o_koff = take(((size_t)x.V + 1) * 4);
         x.o_aoff = take(((size_t)x.V + 1) * 4); x.o_aid = take((size_t)x.sumA * 2);
@@ -1247,135 +1375,137 @@ int job_build(int device, uint32_t n_index, const pg_contig_batch* batches, cons
         x.o_list_big = take(x.list_big.size() * 4);
     }
     job->sample_lo = align_up(off);   // the per-sample arrays of all chains, one contiguous run (pg_job::sample_lo)
-    for (uint32_t c = 0; c < n_chains; ++c) {
-        ChainHost& ch = job->chains[c];
+    for (ChainHost& ch : job->chains) {
         const IndexHost& x = job->index[ch.index];
         ch.o_cov = take((size_t)x.V * 2); ch.o_kcnt = take((size_t)x.sumK * 2);
     }
     job->sample_bytes = align_up(off) - job->sample_lo;
-    std::vector<char> tri_of_chain(n_chains, 0);
-    std::vector<size_t> plan_wlist(n_chains, 0);
     // The variant records of all chains in ONE run of the arena, zeroed once when the job is built: k_prep_bi writes only the
     // pieces of a biallelic object's record that are not zero by construction (header, row bits, four table entries, the path
     // alleles: 96 of 384 bytes at 16 paths — it is a kernel that waits for its memory 70 % of the time); what it leaves out — the
     // rest of the 6 x 6 table, the padding — has to BE zero for every reader of the full record.
-    const size_t vrec_lo = align_up(off);
-    for (uint32_t c = 0; c < n_chains; ++c) { const IndexHost& x = job->index[job->chains[c].index]; plan[c].vrec = take(x.split ? 0 : (size_t)x.V * x.RB); }
-    const size_t vrec_hi = off;
+    L.vrec_lo = align_up(off);
+    for (uint32_t c = 0; c < n_chains; ++c) { const IndexHost& x = job->index[job->chains[c].index]; L.chain[c].vrec = take(x.split ? 0 : (size_t)x.V * x.RB); }
+    L.vrec_hi = off;
     // ... and the sample records of the split chains in another: zeroed with every index pass (k_prep_s_bi stores only the pieces
     // of a biallelic column's 128-byte record that are not zero by construction; which columns those are hangs on the index alone)
-    const size_t srec_lo = align_up(off);
+    L.srec_lo = align_up(off);
     for (uint32_t c = 0; c < n_chains; ++c) {
         const IndexHost& x = job->index[job->chains[c].index];
-        if (x.split) plan[c].frec = take((size_t)x.V * (x.split == 1u ? PG_SREC1_BYTES : PG_SREC2_BYTES));
+        if (x.split) L.chain[c].frec = take((size_t)x.V * (x.split == 1u ? PG_SREC1_BYTES : PG_SREC2_BYTES));
     }
-    const size_t srec_hi = off > srec_lo ? off : srec_lo;   // (no split chain: an empty run)
+    L.srec_hi = off > L.srec_lo ? off : L.srec_lo;   // (no split chain: an empty run)
     for (uint32_t c = 0; c < n_chains; ++c) {
-        ChainHost& ch = job->chains[c];
-        const IndexHost& x = job->index[ch.index];
-        Plan& p = plan[c];
+        const IndexHost& x = job->index[job->chains[c].index];
+        const ChainKernels& k = kernels[c];
+        ChainOffsets& p = L.chain[c];
         p.colrec = take(x.split ? 0 : (size_t)x.V * x.RB);
         p.cprec = take(x.split ? (size_t)x.V * PG_CPREC_BYTES : 0);
-        // fused jobs: lean chains store / read their columns as compact upper triangles (18 KB instead of 32 KB per
-        // column: half the sweep's HBM bytes and of the arena); PG_KERNELS=notri keeps full columns (cross-check)
-        // (round 6: and the 64-path chains with multiallelic objects — every column narrow — whose phase 1 runs on the general
-        //  kernel: it stores the same triangles, phase 2 reads them through its triangle ring: DevContig::tri == 1)
-        // (DevContig::widef chains too: their wide columns leave phase 2 through aux slots, k_bins_wide reads the stored triangle)
-        const bool tri_multi = !x.lean && !x.leanx && x.HP == 64 && x.H == 64 && (!x.wide_bytes || x.widef) && x.pair_n > 2 && !force_generic && !kc.general;
-        const bool tri = (x.lean || tri_multi) && !job->chunked && !kc.notri;
-        tri_of_chain[c] = tri;
-        const bool geno = params->run_genotyping != 0;  // (a phasing-only job has no sweep: no columns, no partials)
-        p.fwd = take(geno ? (size_t)x.V * (tri ? 2304u : (size_t)x.HP * x.HP) * sizeof(double) : 0);
+        p.fwd = take(geno ? (size_t)x.V * (k.tri ? 2304u : (size_t)x.HP * x.HP) * sizeof(double) : 0);   // (triangle chains: 2304 doubles per column)
         // fused mode: posterior partials; chunked mode: the chunk scratch instead (k_post writes lik directly)
         // (x chains of fused jobs: four class sums per column — plus the per-thread partials of ONE column, should the chain
         //  be left with a single column and run its phase 2 on the general kernel)
-        const bool x2 = x.smallx && !job->chunked && !kc.nosmall2;
+        const bool x2 = k.smallx == 2u;
         p.part = take(job->chunked || !geno ? 0 : (x2 ? (size_t)x.V * 32u + (size_t)x.part_slots * part_entries(x) * sizeof(double)
                                                       : (size_t)x.V * x.part_slots * part_entries(x) * sizeof(double)));
         p.aux = take((x2 || x.widef) && geno ? x.aux_bytes : 0);
-        const size_t o_wlist = take((x2 || x.widef) && geno && x.wide_bytes && !x.split ? (size_t)x.n_wide_cand * 4 : 0);
-        plan_wlist[c] = o_wlist;
+        p.wlist = take((x2 || x.widef) && geno && x.wide_bytes && !x.split ? (size_t)x.n_wide_cand * 4 : 0);
         // Viterbi: transition probabilities and one 2-byte backpointer per state and column
-        p.vtq = take(params->run_phasing ? (size_t)x.V * 8 * sizeof(double) : 0);
-        p.vback = take(params->run_phasing ? (size_t)x.V * x.H * x.HP * sizeof(uint16_t) : 0);
-        if (params->run_phasing) job->vit_bits |= x.HP == 16 ? 1u : (x.HP == 32 ? 2u : 4u);
+        p.vtq = take(vit ? (size_t)x.V * 8 * sizeof(double) : 0);
+        p.vback = take(vit ? (size_t)x.V * x.H * x.HP * sizeof(uint16_t) : 0);
         p.scratch = take(job->chunked ? (size_t)2 * PG_SCRATCH_BUFS * job->chunk_cols * x.HP * x.HP * sizeof(double) : 0);
         p.wide = take(x.wide_bytes);
         p.vpair = take(x.split ? 0 : (size_t)x.V * pg_pair_bytes(x.pair_n));
-        p.xbuf = take((x.HP >= 256 || (force_generic && x.HP >= 64)) ? (size_t)2 * x.HP * x.HP * sizeof(double) : 0);
+        p.xbuf = take((x.HP >= 256 || (a.kc.generic && x.HP >= 64)) ? (size_t)2 * x.HP * x.HP * sizeof(double) : 0);
         if (!x.split) p.frec = take((x.lean || x.small) ? (size_t)x.V * 64 : (x.smallx ? (size_t)x.V * 192 : 0));
-        if (x.lean) job->hp_mask |= 64u;
-        if (x.leanx) job->hp_mask |= x.HP == 128 ? 512u : 1024u;
         p.fscale = take((size_t)x.V * sizeof(double));
         p.bscale = take((size_t)x.V * sizeof(double));
         p.bsum = take((size_t)x.V * sizeof(double));
-        if (x.HP >= 256) job->hp_mask |= 16u;
-        else if (force_generic && x.HP >= 64) job->hp_mask |= 32u;
-        // (split chains never run on the general kernel; nor do, in a chunked job — no phase 2 —, the chains whose store-only phases
-        //  have a kernel of their own: the general kernel's launch returned at once for them, fifty empty launches on the
-        //  whole-genome job's phase 2)
-        else if (!x.split && !(job->chunked && (x.lean || x.small || x.smallx || x.leanx)))
-            job->hp_mask |= x.HP == 16 ? 1u : x.HP == 32 ? 2u : x.HP == 64 ? 4u : 8u;
     }
-    if (job->hp_mask & 32u) job->hp_mask |= 16u;  // one generic launch covers both
-    job->arena_bytes = align_up(off);
-    const double t_alloc = now_s();
-    if (cache_arena) g_pool.take(device, job->arena_bytes, &job->arena, &job->arena_bytes);
+    L.bytes = align_up(off);
+    return L;
+}
+
+// The arena: from the process pool (one-shot jobs), else hipMalloc — once more after the pool has been emptied.
+hipError_t allocate_arena(pg_job* job, size_t bytes) {
+    const double t0 = now_s();
+    job->arena_bytes = bytes;
+    if (job->cache_arena) g_pool.take(job->device, job->arena_bytes, &job->arena, &job->arena_bytes);
+    hipError_t he = hipSuccess;
     if (!job->arena) {
         he = hipMalloc((void**)&job->arena, job->arena_bytes);
         if (he != hipSuccess) {
             (void)hipGetLastError();
             pg_hmm_release_cache();  // cached arenas may be what stands in the way
-            hipSetDevice(device);
+            hipSetDevice(job->device);
             he = hipMalloc((void**)&job->arena, job->arena_bytes);
         }
-        if (he != hipSuccess) {
-            job->arena = nullptr;
-            (void)hipGetLastError();
-            // A chunked job's scratch (PG_SCRATCH_BUFS buffers of chunk_cols columns per half-chain: up to 18 GB) is a choice, not
-            // a need: before giving up, plan again with half the chunk columns (the fixed budget could fail a job
-            // that fitted with smaller chunks — on a smaller device, or next to other resident jobs)
-            if (job->chunked && job->chunk_cols > 64u) {
-                const size_t next_cap = job->chunk_cols / 2u;
-                pg_job_destroy(job);
-                return job_build(device, n_index, batches, specs, n_samples, cohort, table, params, cache_arena, out, err, errlen, next_cap);
-            }
-            set_err(err, errlen, "hipMalloc(%zu bytes) failed: %s", job->arena_bytes, hipGetErrorString(he));
-            pg_job_destroy(job);
-            return PG_ERR_NOMEM;
-        }
+        if (he != hipSuccess) { job->arena = nullptr; (void)hipGetLastError(); }
     }
-    if ((he = hipMemsetAsync(job->arena + vrec_lo, 0, vrec_hi - vrec_lo, job->stream)) != hipSuccess) return fail(PG_ERR_DEVICE, "hipMemset (variant records)", he);
-    job->host_s[0] = now_s() - t_alloc;
-    lap("arena plan + allocation");
+    job->host_s[0] = now_s() - t0;
+    return he;
+}
+
+// the job's streams and events; the second stream and the chunk events for chunked jobs only
+int create_device_objects(pg_job* job, char* err, size_t errlen) {
+    hipError_t he;
+    if ((he = hipStreamCreate(&job->stream)) != hipSuccess) return hip_fail(err, errlen, "hipStreamCreate", he);
+    for (auto& e : job->ev)
+        if ((he = hipEventCreate(&e)) != hipSuccess) return hip_fail(err, errlen, "hipEventCreate", he);
+    for (auto& e : job->ev_vit)
+        if ((he = hipEventCreate(&e)) != hipSuccess) return hip_fail(err, errlen, "hipEventCreate", he);
+    for (auto& e : job->ev_ix)
+        if ((he = hipEventCreate(&e)) != hipSuccess) return hip_fail(err, errlen, "hipEventCreate", he);
+    job->events = true;
+    if (!job->chunked) return PG_OK;
+    if ((he = hipStreamCreateWithFlags(&job->stream2, hipStreamNonBlocking)) != hipSuccess) return hip_fail(err, errlen, "hipStreamCreate", he);
+    for (int q = 0; q < (int)PG_SCRATCH_BUFS; ++q) {
+        if ((he = hipEventCreateWithFlags(&job->ev_sweep[q], hipEventDisableTiming)) != hipSuccess) return hip_fail(err, errlen, "hipEventCreate", he);
+        if ((he = hipEventCreateWithFlags(&job->ev_post[q], hipEventDisableTiming)) != hipSuccess) return hip_fail(err, errlen, "hipEventCreate", he);
+    }
+    job->events2 = true;
+    return PG_OK;
+}
+
+// the job's pointers into its arena
+void bind_arena(pg_job* job, const ArenaLayout& L) {
     unsigned char* A = job->arena;
-    job->d_contigs = (DevContig*)(A + o_contigs);
-    job->d_reps = (DevContig*)(A + o_reps);
-    job->d_contigs_g = (DevContig*)(A + o_contigs_g); job->d_reps_g = (DevContig*)(A + o_reps_g);
-    job->d_ixerr = (uint32_t*)(A + o_ixerr);
-    job->ix_base = A + ix_lo; job->ix_bytes = ix_hi - ix_lo;
-    job->srec_base = A + srec_lo; job->srec_bytes = srec_hi - srec_lo;
-    job->d_ncols = (uint32_t*)(A + o_ncols);
-    job->d_err = (uint32_t*)(A + o_err);
-    job->d_lik = (double*)(A + o_lik);
-    job->d_likexp = (int32_t*)(A + o_likexp);
-    job->zero_base = A + zero_lo;
-    job->zero_bytes = zero_hi - zero_lo;
+    job->d_contigs = (DevContig*)(A + L.o_contigs);
+    job->d_reps = (DevContig*)(A + L.o_reps);
+    job->d_contigs_g = (DevContig*)(A + L.o_contigs_g); job->d_reps_g = (DevContig*)(A + L.o_reps_g);
+    job->d_small = (uint32_t*)(A + L.o_small);
+    job->d_dump = (double*)(A + L.o_dump);
+    job->d_handshake = (uint32_t*)(A + L.o_handshake);
+    job->d_ixerr = (uint32_t*)(A + L.o_ixerr);
+    job->ix_base = A + L.ix_lo; job->ix_bytes = L.ix_hi - L.ix_lo;
+    job->srec_base = A + L.srec_lo; job->srec_bytes = L.srec_hi - L.srec_lo;
+    job->d_ncols = (uint32_t*)(A + L.o_ncols);
+    job->d_err = (uint32_t*)(A + L.o_err);
+    job->d_lik = (double*)(A + L.o_lik);
+    job->d_likexp = (int32_t*)(A + L.o_likexp);
+    job->zero_base = A + L.zero_lo;
+    job->zero_bytes = L.zero_hi - L.zero_lo;
     job->tab.mant = (const double*)(A + job->o_tab_m);
     job->tab.expo = (const int32_t*)(A + job->o_tab_e);
     job->tab.packed = A + job->o_tab_p;
+    job->cur_samples = A + job->sample_lo;
+}
 
-    // ---- chain descriptors ----------------------------------------------------------------------
-    std::vector<DevContig> hd(n_chains);
-    const long double dist_scale = 0.000004L * ((long double)params->recombrate) * params->effective_N;
-    for (uint32_t c = 0; c < n_chains; ++c) {
+// One DevContig per chain from the offsets and the chain's kernels, and the grid extents of the kernels that walk lists.
+std::vector<DevContig> fill_descriptors(pg_job* job, const BuildArgs& a, const std::vector<ChainKernels>& kernels, const ArenaLayout& L) {
+    unsigned char* A = job->arena;
+    const pg_hmm_params& params = a.params;
+    std::vector<DevContig> hd(job->chains.size());
+    const long double dist_scale = 0.000004L * ((long double)params.recombrate) * params.effective_N;
+    for (size_t c = 0; c < hd.size(); ++c) {
         ChainHost& ch = job->chains[c];
         const IndexHost& x = job->index[ch.index];
-        const Plan& p = plan[c];
+        const ChainOffsets& p = L.chain[c];
+        const ChainKernels& k = kernels[c];
         DevContig& d = hd[c];
         memset(&d, 0, sizeof(d));
-        d.V = x.V; d.H = x.H; d.HP = x.HP; d.RB = x.RB; d.T = part_entries(x); d.part_slots = x.part_slots; d.pair_n = x.pair_n;
-        d.dist_scale = (double)dist_scale; d.uniform = params->uniform ? 1 : 0;
+        d.V = x.V; d.H = x.H; d.HP = x.HP; d.RB = x.RB; d.T = k.T; d.part_slots = x.part_slots; d.pair_n = x.pair_n;
+        d.dist_scale = (double)dist_scale; d.uniform = params.uniform ? 1 : 0;
         d.debug = 8u;   // (bit 3: the in-kernel cycle counters of -DPG_CHAIN_PROF builds; the product build has none)
         d.pos = (const uint64_t*)(A + x.o_pos); d.cov = (const uint16_t*)(A + ch.o_cov);
         d.kmer_off = (const uint32_t*)(A + x.o_koff); d.kmer_count = (const uint16_t*)(A + ch.o_kcnt);
@@ -1397,193 +1527,181 @@ int job_build(int device, uint32_t n_index, const pg_contig_batch* batches, cons
         d.scratch = (double*)(A + p.scratch); d.chunk_cols = job->chunk_cols; d.sync = (uint32_t*)(A + p.sync);
         d.wide = A + p.wide; d.wide_idx = x.wide_bytes ? (const uint32_t*)(A + x.o_widx) : nullptr;
         d.vpair = A + p.vpair; d.xbuf = (double*)(A + p.xbuf);
-        d.frec = (double*)(A + p.frec); d.lean = x.lean ? 1u : 0u; d.small = x.small ? ((!job->chunked && x.cls4 && !kc.nosmall2) ? 2u : 1u) : 0u; d.leanx = x.leanx ? 1u : 0u; d.cls4 = x.cls4 ? 1u : 0u;
-        d.smallx = x.smallx ? ((!job->chunked && !kc.nosmall2) ? 2u : 1u) : 0u;
-        d.widef = x.widef ? 1u : 0u;
+        d.frec = (double*)(A + p.frec);
+        d.lean = k.lean; d.small = k.small; d.smallx = k.smallx; d.leanx = k.leanx; d.leanx2 = k.leanx2; d.cls4 = k.cls4; d.widef = k.widef; d.tri = k.tri;
+        d.col_stride = d.tri ? 2304u : x.HP * x.HP;
         d.aux = A + p.aux; d.aux_idx = ((d.smallx == 2u || x.widef) && x.aux_bytes) ? (const uint32_t*)(A + x.o_auxidx) : nullptr;
         if ((d.smallx == 2u || x.widef) && x.wide_bytes && x.n_wide_cand) {
             // (split chains: the wide columns hang on the index alone — one list per index contig, made by k_index_cols)
             if (x.split) { d.wcols = (uint32_t*)(A + x.o_ixwl); d.n_wcols = (uint32_t*)(A + x.o_ixnw); }
-            else { d.wcols = (uint32_t*)(A + plan_wlist[c]); d.n_wcols = (uint32_t*)(A + p.wcols); }
+            else { d.wcols = (uint32_t*)(A + p.wlist); d.n_wcols = (uint32_t*)(A + p.wcols); }
             job->max_wide = std::max(job->max_wide, x.n_wide_cand);
         }
-        d.live = (!job->chunked && x.HP == 32u && !kc.fullcols) ? std::min<uint32_t>(x.HP, (x.H + 3u) & ~3u) : x.HP;
+        d.live = (!job->chunked && x.HP == 32u && !a.kc.fullcols) ? std::min<uint32_t>(x.HP, (x.H + 3u) & ~3u) : x.HP;
         d.prep_fast = x.prep_fast;
-        if (x.split) {
-            // the split path's emission kernels: lists unless every object is k_prep_s_bi's
-            if (!x.all_sb) {
-                d.prep_m4 = (const uint32_t*)(A + x.o_list_m4); d.n_prep_m4 = (uint32_t)x.list_m4.size();
-                d.prep_w = (const uint32_t*)(A + x.o_list_w); d.n_prep_w = (uint32_t)x.list_w.size();
-                d.prep_b = (const uint32_t*)(A + x.o_list_b); d.n_prep_b = (uint32_t)x.list_b.size();
-            }
-            job->max_sb = std::max(job->max_sb, x.all_sb ? x.V : d.n_prep_b);
-            job->max_sm4 = std::max(job->max_sm4, d.n_prep_m4);
-            job->max_sw = std::max(job->max_sw, d.n_prep_w);
-        } else {
-        job->any_legacy_prep = true;
-        if (x.prep_fast == 2u) {   // (a non-null list pointer = "walk the list", also when it is empty)
+        // who walks lists: the split path's emission kernels unless every object is k_prep_s_bi's, the others when only a part
+        // of the objects is k_prep_bi's (a non-null list pointer = "walk the list", also when it is empty)
+        if (k.prep == PREP_S_LISTS || k.prep == PREP_BI_LISTS) {
             d.prep_m4 = (const uint32_t*)(A + x.o_list_m4); d.n_prep_m4 = (uint32_t)x.list_m4.size();
             d.prep_w = (const uint32_t*)(A + x.o_list_w); d.n_prep_w = (uint32_t)x.list_w.size();
             d.prep_b = (const uint32_t*)(A + x.o_list_b); d.n_prep_b = (uint32_t)x.list_b.size();
-            job->max_prep_m4 = std::max(job->max_prep_m4, d.n_prep_m4);
-            job->max_prep_w = std::max(job->max_prep_w, d.n_prep_w);
-        } else if (x.prep_fast == 0u) job->max_prep_w = std::max(job->max_prep_w, x.V);
         }
-        if (params->run_phasing) {
+        if (x.split) {
+            job->max_sb = std::max(job->max_sb, k.prep == PREP_S_BI ? x.V : d.n_prep_b);
+            job->max_sm4 = std::max(job->max_sm4, d.n_prep_m4);
+            job->max_sw = std::max(job->max_sw, d.n_prep_w);
+        } else {
+            job->any_legacy_prep = true;
+            job->max_prep_m4 = std::max(job->max_prep_m4, d.n_prep_m4);
+            job->max_prep_w = std::max(job->max_prep_w, k.prep == PREP_W ? x.V : d.n_prep_w);
+        }
+        if (params.run_phasing) {
             d.vit_tq = (double*)(A + p.vtq); d.vit_back = (uint16_t*)(A + p.vback); d.vit_best = (uint32_t*)(A + p.vbest);
             d.hap1 = (uint16_t*)(A + p.hap1); d.hap2 = (uint16_t*)(A + p.hap2);
         }
-        d.tri = tri_of_chain[c] ? ((kc.nolean2 || !x.lean) ? 1u : 2u) : 0u;   // (PG_KERNELS=nolean2, and chains with multiallelic objects: phase 2 of triangle chains on the general kernel's triangle ring)
-        d.col_stride = d.tri ? 2304u : x.HP * x.HP;
-        if (d.tri == 1u && !x.lean && x.HP == 64u && !kc.noleanx2 && !params->run_phasing && !x.widef) {   // phase 2 on k_sweep_leanx2 (no wide columns there)
-            d.leanx2 = 1u; d.T = 64u; job->hp_mask |= 8192u;
-        }
-        if (d.tri) job->hp_mask |= 128u;
-        if (d.tri && !x.lean) {
-            // phase 1 of such chains: the lean-x step with triangle stores (DevContig::leanx == 2; it needs the column-order records
-            // of the general kernel, which phase 2 reads too) — PG_KERNELS=noleanx: the general kernel with triangle stores
-            if (kc.leanx != 0) { d.leanx = 2u; job->hp_mask |= x.widef ? 16384u : 4096u; }   // (DevContig::widef chains: k_sweep_leanx_triw — leanx_forward / _backward's wide_fix)
-            else job->hp_mask |= 2048u;
-        }
-        if (d.tri == 2u) job->hp_mask |= 256u;
-        // (k_bins_thin: what bins_thin() in pg_kernels.hip says — at most 64 partial entries per column, fused job)
-        if (x.split) job->bins_which |= 32u | ((x.split == 2u && x.wide_bytes) ? 64u : 0u);   // k_bins_s, k_bins_wide_s
-        else {
-        job->bins_which |= d.leanx2 ? 128u : (d.tri == 2u || d.cls4) ? 2u : ((d.T <= 64u && d.HP <= 32u && !job->chunked) ? 4u : 1u);   // (bit 7: k_bins_q)
-        if (d.smallx == 2u) job->bins_which |= 8u | (x.wide_bytes ? 16u : 0u);   // k_bins_x, k_bins_wide (a chain left with one column: k_bins_thin, above)
-        if (x.widef && x.n_wide_cand) job->bins_which |= 16u;   // k_bins_wide for the wide columns of DevContig::widef chains
-        }
         ch.d = d;
     }
-    {
-        // chain ids of the four-half-chains-per-wave kernels: the all-biallelic chains first, then the x chains; each list in the
-        // order of the index contigs (stable), so that the four rows of a wave are — in a cohort — samples of ONE contig: the same
-        // columns are multiallelic / wide in all four (the wide branch of k_sweep_small16x is wave-uniform)
-        std::vector<uint32_t> small_ids, x_ids;
-        for (uint32_t c = 0; c < n_chains; ++c) {
-            if (hd[c].small) { small_ids.push_back(c); if (hd[c].small == 2u) job->small_phase2 = true; }
-            if (hd[c].smallx) { x_ids.push_back(c); if (hd[c].smallx == 2u) job->smallx_phase2 = true; }
-        }
-        auto by_index = [&](uint32_t a, uint32_t b) { return job->chains[a].index < job->chains[b].index; };
-        std::stable_sort(small_ids.begin(), small_ids.end(), by_index);
-        std::stable_sort(x_ids.begin(), x_ids.end(), by_index);
-        job->n_small = (uint32_t)small_ids.size();
-        job->n_smallx = (uint32_t)x_ids.size();
-        job->d_small = (uint32_t*)(A + o_small);
-        job->d_smallx = job->d_small + job->n_small;
-        job->d_dump = (double*)(A + o_dump);
-        job->d_handshake = (uint32_t*)(A + o_handshake);
-        small_ids.insert(small_ids.end(), x_ids.begin(), x_ids.end());
-        if (!small_ids.empty() && (he = hipMemcpyAsync(job->d_small, small_ids.data(), sizeof(uint32_t) * small_ids.size(), hipMemcpyHostToDevice, job->stream)) != hipSuccess)
-            return fail(PG_ERR_DEVICE, "hipMemcpy small ids", he);
-        if (!small_ids.empty() && (he = hipStreamSynchronize(job->stream)) != hipSuccess) return fail(PG_ERR_DEVICE, "hipMemcpy small ids", he);
+    return hd;
+}
+
+// What the kernels read of the job itself goes to the device: the variant records' zeroes, the chain-id lists of the
+// four-half-chains-per-wave kernels, one descriptor per index contig, the chain descriptors.
+int upload_descriptors(pg_job* job, const ArenaLayout& L, const std::vector<DevContig>& hd, char* err, size_t errlen) {
+    hipError_t he;
+    hipStream_t s = job->stream;
+    const uint32_t n_chains = (uint32_t)hd.size(), n_index = (uint32_t)job->index.size();
+    if ((he = hipMemsetAsync(job->arena + L.vrec_lo, 0, L.vrec_hi - L.vrec_lo, s)) != hipSuccess) return hip_fail(err, errlen, "hipMemset (variant records)", he);
+    // chain ids: the all-biallelic chains first, then the x chains; each list in the order of the index contigs (stable), so that
+    // the four rows of a wave are — in a cohort — samples of ONE contig: the same columns are multiallelic / wide in all four
+    // (the wide branch of k_sweep_small16x is wave-uniform)
+    std::vector<uint32_t> small_ids, x_ids;
+    for (uint32_t c = 0; c < n_chains; ++c) {
+        if (hd[c].small) { small_ids.push_back(c); if (hd[c].small == 2u) job->small_phase2 = true; }
+        if (hd[c].smallx) { x_ids.push_back(c); if (hd[c].smallx == 2u) job->smallx_phase2 = true; }
     }
-    {   // the plan as text (pg_job_plan): one line per group of chains with the same kernels
-        struct Group { std::string text; uint32_t count = 0; };
-        std::vector<Group> groups;
-        for (uint32_t c = 0; c < n_chains; ++c) {
-            const DevContig& d = hd[c];
-            const IndexHost& x = job->index[job->chains[c].index];
-            if (x.V == 0) continue;
-            const bool multi = x.pair_n > 2, wide = x.wide_bytes != 0;
-            std::string prep, p1, p2, bins;
-            const char* gen = d.HP >= 256 || force_generic ? "k_sweep_generic" : (d.HP == 16 ? "k_sweep<16,4>" : d.HP == 32 ? "k_sweep<32,8>" : d.HP == 64 ? "k_sweep<64,16>" : "k_sweep<128,32>");
-            if (d.split) {
-                prep = std::string("index pass once (k_index_scan, k_compact, k_index_cols); per run k_prep_s_bi") + (x.all_sb ? "" : " + k_prep_s_m4 + k_prep_s_w");
-                p1 = d.split == 1u ? "k_sweep_small16<1>" : "k_sweep_small16x<1>";
-                p2 = d.split == 1u ? "k_sweep_small16<2>" : "k_sweep_small16x<2>";
-                bins = std::string("k_bins_s") + (wide ? " + k_bins_wide_s" : "");
-            } else {
-                prep = "index pass once (k_index_scan, k_compact); per run ";
-                prep += x.prep_fast == 1u ? "k_prep_bi" : (x.prep_fast == 2u ? "k_prep_bi + k_prep_m4 + k_prep" : "k_prep");
-                prep += " + k_records";
-                p1 = d.lean ? (d.tri ? "k_sweep_lean_tri<1>" : "k_sweep_lean<1>") : d.leanx == 2u ? (d.widef ? "k_sweep_leanx_triw" : "k_sweep_leanx_tri") : d.leanx ? "k_sweep_leanx<1>"
-                     : d.small ? "k_sweep_small16<1>" : d.smallx ? "k_sweep_small16x<1>" : (d.tri ? "k_sweep_tri1" : std::string(gen) + "<1>");
-                if (job->chunked && job->persist) {
-                    p2 = "k_sweep_lean<4> (one launch, all chunks) + k_post_loop";
-                    bins = "(k_post_loop)";
-                } else if (job->chunked) {
-                    p2 = d.lean ? "k_sweep_lean<3>" : d.leanx ? "k_sweep_leanx<3>" : d.small ? "k_sweep_small16<3>" : d.smallx ? "k_sweep_small16x<3>" : std::string(gen) + "<3>";
-                    p2 += " chunks + k_post";
-                    bins = "(k_post)";
-                } else {
-                    p2 = d.leanx2 ? "k_sweep_leanx2" : d.tri == 2u ? "k_sweep_lean2" : d.small == 2u ? "k_sweep_small16<2>" : d.smallx == 2u ? "k_sweep_small16x<2>"
-                         : std::string(gen) + (d.tri ? "<2> (triangle ring)" : "<2>");
-                    bins = d.leanx2 ? "k_bins_q" : (d.tri == 2u || d.cls4) ? "k_bins_lean2" : d.smallx == 2u ? (wide ? "k_bins_x + k_bins_wide" : "k_bins_x")
-                           : (d.T <= 64u && d.HP <= 32u) ? "k_bins_thin" : "k_bins";
-                    if (d.widef) { p2 += " (wide columns to their aux slots)"; bins += " + k_bins_wide"; }
-                }
-            }
-            char head[160];
-            snprintf(head, sizeof(head), "%u path(s) (padded %u), %s%s%s columns: ", d.H, d.HP, multi ? "multiallelic" : "biallelic", wide ? " + wide" : "",
-                     d.tri ? ", triangle" : "");
-            std::string text = std::string(head) + "prep = " + prep + "; phase 1 = " + p1 + "; phase 2 = " + p2 + "; bins = " + bins;
-            bool found = false;
-            for (auto& g : groups) if (g.text == text) { g.count += 1; found = true; break; }
-            if (!found) groups.push_back({text, 1});
-        }
-        job->plan_text = std::string(job->chunked ? "chunked" : "fused") + " job, " + std::to_string(n_chains) + " chain(s)" + (params->run_phasing ? ", run_phasing (k_viterbi)" : "") + "\n";
-        for (const auto& g : groups) job->plan_text += "  " + std::to_string(g.count) + " x " + g.text + "\n";
-    }
+    auto by_index = [&](uint32_t p, uint32_t q) { return job->chains[p].index < job->chains[q].index; };
+    std::stable_sort(small_ids.begin(), small_ids.end(), by_index);
+    std::stable_sort(x_ids.begin(), x_ids.end(), by_index);
+    job->n_small = (uint32_t)small_ids.size();
+    job->n_smallx = (uint32_t)x_ids.size();
+    job->d_smallx = job->d_small + job->n_small;
+    small_ids.insert(small_ids.end(), x_ids.begin(), x_ids.end());
+    if (!small_ids.empty() && ((he = hipMemcpyAsync(job->d_small, small_ids.data(), sizeof(uint32_t) * small_ids.size(), hipMemcpyHostToDevice, s)) != hipSuccess ||
+                               (he = hipStreamSynchronize(s)) != hipSuccess))
+        return hip_fail(err, errlen, "hipMemcpy small ids", he);
+    // one descriptor per index contig for the index-level kernels (any chain over it: they touch index-level fields only)
+    std::vector<DevContig> reps(n_index);
+    for (auto& r : reps) memset(&r, 0, sizeof(r));
+    std::vector<char> have(n_index, 0);
+    for (uint32_t c = 0; c < n_chains; ++c) { const uint32_t i = job->chains[c].index; if (!have[i]) { have[i] = 1; reps[i] = hd[c]; } }
+    if ((he = hipMemcpyAsync(job->d_reps, reps.data(), sizeof(DevContig) * n_index, hipMemcpyHostToDevice, s)) != hipSuccess ||
+        (he = hipStreamSynchronize(s)) != hipSuccess)
+        return hip_fail(err, errlen, "hipMemcpy index descriptors", he);
+    if ((he = hipMemcpyAsync(job->d_contigs, hd.data(), sizeof(DevContig) * n_chains, hipMemcpyHostToDevice, s)) != hipSuccess ||
+        (he = hipStreamSynchronize(s)) != hipSuccess)
+        return hip_fail(err, errlen, "hipMemcpy contigs", he);
     job->h_contigs = hd;
-    job->cur_samples = A + job->sample_lo;
-    {   // one descriptor per index contig for the index-level kernels (any chain over it: they touch index-level fields only)
-        std::vector<DevContig> reps(n_index);
-        for (auto& r : reps) memset(&r, 0, sizeof(r));
-        std::vector<char> have(n_index, 0);
-        for (uint32_t c = 0; c < n_chains; ++c) { const uint32_t i = job->chains[c].index; if (!have[i]) { have[i] = 1; reps[i] = hd[c]; } }
-        if ((he = hipMemcpyAsync(job->d_reps, reps.data(), sizeof(DevContig) * n_index, hipMemcpyHostToDevice, job->stream)) != hipSuccess ||
-            (he = hipStreamSynchronize(job->stream)) != hipSuccess)
-            return fail(PG_ERR_DEVICE, "hipMemcpy index descriptors", he);
+    return PG_OK;
+}
+
+// The pipelined first run (pg_job::pipeline): a one-shot job — upload and run inside one call — of few chains (chunked: bound
+// by its longest chain, not by throughput), every chain over an index contig of its own, on kernels that take a sub-range
+// of the descriptor array (no chain-id lists, no split path), with enough bytes to upload that hiding them matters.
+// Group A = the chains with at least 0.78 of the longest one's variants (they decide the wall time; the others, starting
+// later by their upload — ~10 % of a run at 40 GB/s —, still end phase 1 first), unless that is most of the bytes anyway.
+int plan_pipeline(pg_job* job, const BuildArgs& a, const std::vector<DevContig>& hd, char* err, size_t errlen) {
+    const uint32_t n_chains = (uint32_t)hd.size();
+    bool ok = job->chunked && !a.cohort && a.n_index == n_chains && n_chains >= 2 && !job->any_split &&
+              a.params.run_genotyping && !a.params.run_phasing && getenv("PG_NO_PIPELINE") == nullptr;
+    for (uint32_t c = 0; ok && c < n_chains; ++c) ok = job->chains[c].index == c && !job->index[c].small && !job->index[c].smallx;
+    if (!ok) return PG_OK;
+    uint64_t vmax = 0, wA = 0, wAll = 0;
+    for (const IndexHost& x : job->index) vmax = std::max<uint64_t>(vmax, x.V);
+    std::vector<uint32_t> ga, gb;
+    for (uint32_t c = 0; c < n_chains; ++c) {
+        const IndexHost& x = job->index[c];
+        const uint64_t w = (uint64_t)x.V * x.H * 2u + (uint64_t)x.sumK * 2u + (uint64_t)x.V * 24u;
+        wAll += w;
+        if ((double)x.V >= 0.78 * (double)vmax) { ga.push_back(c); wA += w; } else gb.push_back(c);
     }
-    if ((he = hipMemcpyAsync(job->d_contigs, hd.data(), sizeof(DevContig) * n_chains, hipMemcpyHostToDevice, job->stream)) != hipSuccess ||
+    uint64_t min_bytes = (uint64_t)128 << 20;   // (PG_PIPELINE_MIN_MB: tests put small jobs through the pipelined run)
+    if (const char* e = getenv("PG_PIPELINE_MIN_MB")) min_bytes = (uint64_t)strtoul(e, nullptr, 0) << 20;
+    if (gb.empty() || wAll < min_bytes || (double)wA > 0.6 * (double)wAll) return PG_OK;
+    job->grp_order = ga;
+    job->grp_order.insert(job->grp_order.end(), gb.begin(), gb.end());
+    job->nA = (uint32_t)ga.size();
+    std::vector<DevContig> g(n_chains);
+    for (uint32_t k = 0; k < n_chains; ++k) g[k] = hd[job->grp_order[k]];
+    // (chain c over index c: the chain's descriptor serves as its index contig's)
+    hipError_t he;
+    if ((he = hipMemcpyAsync(job->d_contigs_g, g.data(), sizeof(DevContig) * n_chains, hipMemcpyHostToDevice, job->stream)) != hipSuccess ||
+        (he = hipMemcpyAsync(job->d_reps_g, g.data(), sizeof(DevContig) * n_chains, hipMemcpyHostToDevice, job->stream)) != hipSuccess ||
         (he = hipStreamSynchronize(job->stream)) != hipSuccess)
-        return fail(PG_ERR_DEVICE, "hipMemcpy contigs", he);
-    lap("descriptors");
-    {
-        // The pipelined first run (pg_job::pipeline): a one-shot job — upload and run inside one call — of few chains (chunked: bound
-        // by its longest chain, not by throughput), every chain over an index contig of its own, on kernels that take a sub-range
-        // of the descriptor array (no chain-id lists, no split path), with enough bytes to upload that hiding them matters.
-        // Group A = the chains with at least 0.78 of the longest one's variants (they decide the wall time; the others, starting
-        // later by their upload — ~10 % of a run at 40 GB/s —, still end phase 1 first), unless that is most of the bytes anyway.
-        bool ok = job->chunked && !cohort && n_index == n_chains && n_chains >= 2 && !job->any_split &&
-                  params->run_genotyping && !params->run_phasing && getenv("PG_NO_PIPELINE") == nullptr;
-        for (uint32_t c = 0; ok && c < n_chains; ++c) ok = job->chains[c].index == c && !job->index[c].small && !job->index[c].smallx;
-        if (ok) {
-            uint64_t vmax = 0, wA = 0, wAll = 0;
-            for (const IndexHost& x : job->index) vmax = std::max<uint64_t>(vmax, x.V);
-            std::vector<uint32_t> a, b;
-            for (uint32_t c = 0; c < n_chains; ++c) {
-                const IndexHost& x = job->index[c];
-                const uint64_t w = (uint64_t)x.V * x.H * 2u + (uint64_t)x.sumK * 2u + (uint64_t)x.V * 24u;
-                wAll += w;
-                if ((double)x.V >= 0.78 * (double)vmax) { a.push_back(c); wA += w; } else b.push_back(c);
-            }
-            uint64_t min_bytes = (uint64_t)128 << 20;   // (PG_PIPELINE_MIN_MB: tests put small jobs through the pipelined run)
-            if (const char* e = getenv("PG_PIPELINE_MIN_MB")) min_bytes = (uint64_t)strtoul(e, nullptr, 0) << 20;
-            if (!b.empty() && wAll >= min_bytes && (double)wA <= 0.6 * (double)wAll) {
-                job->grp_order = a;
-                job->grp_order.insert(job->grp_order.end(), b.begin(), b.end());
-                job->nA = (uint32_t)a.size();
-                std::vector<DevContig> g(n_chains);
-                for (uint32_t k = 0; k < n_chains; ++k) g[k] = hd[job->grp_order[k]];
-                // (chain c over index c: the chain's descriptor serves as its index contig's)
-                if ((he = hipMemcpyAsync(job->d_contigs_g, g.data(), sizeof(DevContig) * n_chains, hipMemcpyHostToDevice, job->stream)) != hipSuccess ||
-                    (he = hipMemcpyAsync(job->d_reps_g, g.data(), sizeof(DevContig) * n_chains, hipMemcpyHostToDevice, job->stream)) != hipSuccess ||
-                    (he = hipStreamSynchronize(job->stream)) != hipSuccess)
-                    return fail(PG_ERR_DEVICE, "hipMemcpy group descriptors", he);
-                if (hipEventCreateWithFlags(&job->ev_late[0], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&job->ev_late[1], hipEventDisableTiming) == hipSuccess) {
-                    job->ev_late_made = true;
-                    job->pipeline_capable = true;
-                    job->pipeline = cache_arena;   // (a resident job's first upload returns to a caller who may free the arrays: pg_job_upload_run asks for it)
-                }
-            }
-        }
+        return hip_fail(err, errlen, "hipMemcpy group descriptors", he);
+    if (hipEventCreateWithFlags(&job->ev_late[0], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&job->ev_late[1], hipEventDisableTiming) == hipSuccess) {
+        job->ev_late_made = true;
+        job->pipeline_capable = true;
+        job->pipeline = a.cache_arena;   // (a resident job's first upload returns to a caller who may free the arrays: pg_job_upload_run asks for it)
     }
-    const int rc = upload_inputs(job, batches, specs, true, err, errlen);
-    if (rc != PG_OK) { pg_job_destroy(job); return rc; }
+    return PG_OK;
+}
+
+int job_build(int device, uint32_t n_index, const pg_contig_batch* batches, const std::vector<ChainSpec>& specs,
+              uint32_t n_samples, bool cohort, const pg_table* table, const pg_hmm_params* params, bool cache_arena,
+              pg_job** out, char* err, size_t errlen) {
+    *out = nullptr;
+#ifdef PG_HOST_TIMING   // (measurement builds: where the host time of a job's construction goes)
+    double tb_last = now_s();
+    auto lap = [&](const char* what) { const double t = now_s(); fprintf(stderr, "[job_build] %-28s %8.3f ms\n", what, (t - tb_last) * 1e3); tb_last = t; };
+#else
+    auto lap = [](const char*) {};
+#endif
+    int rc = check_inputs(n_index, batches, specs, table, params, cohort, err, errlen);
+    if (rc == PG_OK) rc = select_device(device, err, errlen);
+    if (rc != PG_OK) return rc;
+    lap("checks");
+    const BuildArgs a{n_index, batches, specs, *params, kernel_choice(), cohort, cache_arena};
+    if (!a.kc.unknown.empty()) { set_err(err, errlen, "PG_KERNELS: unknown token '%s'", a.kc.unknown.c_str()); return PG_ERR_INVALID; }
+    JobOwner owner{new pg_job()};
+    pg_job* job = owner.job;
+    job->device = device;
+    job->params = *params;
+    job->cache_arena = cache_arena;
+    job->cohort = cohort;
+    job->n_samples = n_samples;
+    job->n_contigs = n_index;
+    job->chains.resize(specs.size());
+    for (size_t c = 0; c < specs.size(); ++c) job->chains[c].index = specs[c].index;
+    table_snapshot(const_cast<pg_table*>(table), job->tab_m, job->tab_e, job->tab_p, &job->tab);
+    lap("table");
+    if ((rc = classify_index(job, a, err, errlen)) != PG_OK) return rc;
+    lap("index classification");
+    // A chunked job's scratch (PG_SCRATCH_BUFS buffers of chunk_cols columns per half-chain: up to choose_job_mode's 39 GB budget) is a choice, not a need:
+    // before giving up, plan again with half the chunk columns, down to 64 (the fixed budget could fail a job that
+    // fitted with smaller chunks — on a smaller device, or next to other resident jobs)
+    std::vector<ChainKernels> kernels;
+    ArenaLayout L;
+    hipError_t he = hipSuccess;
+    for (size_t chunk_cap = 0;; chunk_cap = job->chunk_cols / 2u) {
+        choose_job_mode(job, a, chunk_cap);
+        kernels = choose_chain_kernels(job, a);
+        L = layout_arena(job, a, kernels);
+        he = allocate_arena(job, L.bytes);
+        if (he == hipSuccess || !job->chunked || job->chunk_cols <= 64u) break;
+    }
+    if (he != hipSuccess) { set_err(err, errlen, "hipMalloc(%zu bytes) failed: %s", L.bytes, hipGetErrorString(he)); return PG_ERR_NOMEM; }
+    lap("mode, kernels, arena");
+    if ((rc = create_device_objects(job, err, errlen)) != PG_OK) return rc;
+    lap("streams, events");
+    bind_arena(job, L);
+    const std::vector<DevContig> hd = fill_descriptors(job, a, kernels, L);
+    job->plan_text = plan_text(job, a, kernels);
+    if ((rc = upload_descriptors(job, L, hd, err, errlen)) != PG_OK) return rc;
+    lap("descriptors");
+    if ((rc = plan_pipeline(job, a, hd, err, errlen)) != PG_OK) return rc;
+    if ((rc = upload_inputs(job, batches, specs, true, err, errlen)) != PG_OK) return rc;
     lap("upload of the inputs");
-    *out = job;
+    *out = owner.release();
     return PG_OK;
 }
 
@@ -1892,12 +2010,22 @@ extern "C" int pg_job_run(pg_job* job, void* stream_, char* err, size_t errlen) 
     hipStream_t s = stream_ ? (hipStream_t)stream_ : job->stream;
     const uint32_t n = (uint32_t)job->chains.size();
     job->host_s[3] = 0.0;
+    const bool late_own_stream = job->late_pending && s != job->stream;
+    if (late_own_stream) {
+        // (a caller's own stream: no pipelining — group B's inputs are waited for NOW, before streams_concurrent may replace the
+        //  second stream, which their copies are on; `s` waits for the copies, group B's index pass is made up below)
+        join_late_threads(job);
+        for (int rcb : job->late_rc)
+            if (rcb != (int)hipSuccess) { set_err(err, errlen, "input upload: %s", hipGetErrorString((hipError_t)rcb)); return PG_ERR_DEVICE; }
+        HIP_TRY(hipEventRecord(job->ev_late[1], job->stream2));
+        HIP_TRY(hipStreamWaitEvent(s, job->ev_late[1], 0));
+    }
     const bool persist_now = job->persist && job->max_v > 0 && job->params.run_genotyping && streams_concurrent(job, s);   // (may replace stream2)
     if (job->persist && job->max_v > 0 && job->params.run_genotyping) { if (persist_now) job->persist_runs += 1; else job->persist_fallbacks += 1; }
     HIP_TRY(hipMemsetAsync(job->zero_base, 0, job->zero_bytes, s));
     if (job->max_v > 0 && job->params.run_genotyping) {
         HIP_TRY(hipEventRecord(job->ev[0], s));
-        if (job->late_pending && s == job->stream) {
+        if (job->late_pending) {
             // The pipelined first run (pg_job::pipeline): group A's preparation and phase 1 start NOW, on `s`; the host then waits for
             // group B's inputs (they have been crossing PCIe since job_build) and puts B's index pass, preparation and phase 1 on the
             // second stream, beside A's.  Phase 2 (below) starts when both are done.  (The timing classes: B's preparation counts
@@ -1913,9 +2041,7 @@ extern "C" int pg_job_run(pg_job* job, void* stream_, char* err, size_t errlen) 
             HIP_TRY(hipEventRecord(job->ev[3], s));
             pgk_launch_sweep(job->d_contigs_g, nA, job->hp_mask, 1, s);
             HIP_TRY(hipGetLastError());
-            for (auto& t : job->late_threads) if (t.joinable()) t.join();   // (their copies are ISSUED — 17 ms on the whole genome —, on stream2)
-            job->late_threads.clear();
-            job->late_pending = false;
+            join_late_threads(job);   // (their copies are ISSUED — 17 ms on the whole genome —, on stream2)
             for (int rcb : job->late_rc)
                 if (rcb != (int)hipSuccess) { set_err(err, errlen, "input upload: %s", hipGetErrorString((hipError_t)rcb)); return PG_ERR_DEVICE; }
             hipStream_t sb = job->stream2;
@@ -1931,13 +2057,7 @@ extern "C" int pg_job_run(pg_job* job, void* stream_, char* err, size_t errlen) 
             HIP_TRY(hipStreamWaitEvent(s, job->ev_late[1], 0));
             HIP_TRY(hipEventRecord(job->ev[4], s));
         } else {
-        if (job->late_pending) {
-            // (a caller's own stream: no pipelining — group B's inputs are waited for, its index pass made up, then the run as ever)
-            for (auto& t : job->late_threads) if (t.joinable()) t.join();
-            job->late_threads.clear();
-            job->late_pending = false;
-            for (int rcb : job->late_rc)
-                if (rcb != (int)hipSuccess) { set_err(err, errlen, "input upload: %s", hipGetErrorString((hipError_t)rcb)); return PG_ERR_DEVICE; }
+        if (late_own_stream) {   // (group B's index pass, then the run as ever)
             uint32_t max_big = 0;
             for (const IndexHost& x : job->index) max_big = std::max<uint32_t>(max_big, (uint32_t)x.list_big.size());
             pgk_launch_index(job->d_reps_g + job->nA, n - job->nA, job->max_v, max_big, 0, s);

@@ -37,6 +37,7 @@
 
 #include "pg_device.h"
 #include "pg_devmath.h"
+#include "pg_launch.h"   // pgk_launch_viterbi as the shim sees it
 
 #define DEVI __device__ __forceinline__
 #include "pg_experiments.h"
