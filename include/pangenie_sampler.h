@@ -86,12 +86,47 @@ int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_contig_batch*
                           uint32_t* const* sampled_paths,   /* [n_samples*n_contigs] -> [size*V_c], or NULL */
                           uint32_t* const* best_scores,     /* [n_samples*n_contigs] -> [size],     or NULL */
                           pg_job** out_job, char* err, size_t errlen);
-/* H2D bytes of the last pg_sampler_cohort_new / pg_sampler_then_job of this thread: [0] index arrays, [1] per-sample
- * arrays (cohort: the k-mer counts alone, 2 * sumK per sample and contig; pg_sampler_then_job: the counts and the emission
- * costs the host formed from them).  Pointer tables and the reduced panel's offsets are not counted; neither is what
+/* Device-resident per-sample arrays of a sampled cohort in the making: for each of n_samples samples and n_contigs contigs
+ * one uint16_t[n_kmers[c]] and one uint16_t[n_variants[c]], all in ONE allocation on `device` (every array 256-byte aligned;
+ * a contig without k-mers or variants gets a valid, non-null, zero-length slice).  Nothing is written to them here: a count
+ * plan's device fill, a kernel or a D2D copy of the caller fills them.  PG_ERR_INVALID (decided before any device call) for a
+ * null argument, n_contigs == 0 or n_samples == 0; PG_ERR_DEVICE without a GPU; PG_ERR_NOMEM — after the one-shot arena pool
+ * was emptied — with the bytes needed in the message: fewer samples per handle is the caller's remedy. */
+typedef struct pg_sampler_counts pg_sampler_counts;
+int pg_sampler_counts_new(int device, uint32_t n_contigs, const uint64_t* n_kmers, const uint32_t* n_variants,
+                          uint32_t n_samples, pg_sampler_counts** out, char* err, size_t errlen);
+/* NULL is PG_OK */
+int pg_sampler_counts_destroy(pg_sampler_counts* h);
+/* The two pointer tables ([n_contigs] each, owned by the handle, valid until it is destroyed) of one sample: what a device
+ * fill of the count plan (include/pangenie_counts.h) takes as d_kmer_count / d_coverage, and what a pg_sample_counts row of
+ * pg_sampler_cohort_new_device points at.  Either output may be NULL.  PG_ERR_INVALID for sample >= n_samples. */
+int pg_sampler_counts_rows(const pg_sampler_counts* h, uint32_t sample, uint16_t* const** d_kmer_count, uint16_t* const** d_coverage,
+                           char* err, size_t errlen);
+/* pg_sampler_cohort_new with every d_samples[s].kmer_count[c] AND d_samples[s].coverage[c] in the memory of `device` (the
+ * two pointer tables of a row are host arrays, as before).  Every output is bit for bit what pg_sampler_cohort_new gives for
+ * host copies of the same arrays; limits and error codes are its own.  The count arrays are read in place — no copy of them
+ * is made and the call's per-chain memory no longer holds them —, so they must stay valid and unwritten until the call
+ * returns; the returned job does not reference them.  The coverage (which pg_job_new takes from the host) is gathered by one
+ * kernel into one buffer and comes back with ONE D2H copy of 2 * V bytes per sample and contig.  Before any allocation or
+ * launch every array that is needed (kmer_count: contig with k-mers; coverage: contig with variants) is asked about with
+ * hipPointerGetAttributes: anything that is not device memory of `device` — a host pointer, managed memory — is PG_ERR_INVALID
+ * with sample, contig and array named (a host pointer would fault a kernel).  Null-argument checks come first and need no
+ * device.  After the call pg_sampler_last_h2d_bytes answers [1] == 0 and [0] as after pg_sampler_cohort_new;
+ * pg_sampler_last_phase_ms[1] covers the index upload alone and [4] includes the read-back of the coverage. */
+int pg_sampler_cohort_new_device(int device, uint32_t n_contigs, const pg_contig_batch* index,
+                                 uint32_t n_samples, const pg_sample_counts* d_samples,
+                                 uint32_t size, int add_reference,
+                                 double sampling_recombrate, long double sampling_effective_N, uint16_t allele_penalty,
+                                 const pg_table* table, const pg_hmm_params* params,
+                                 uint32_t* const* sampled_paths,   /* [n_samples*n_contigs] -> [size*V_c], or NULL */
+                                 uint32_t* const* best_scores,     /* [n_samples*n_contigs] -> [size],     or NULL */
+                                 pg_job** out_job, char* err, size_t errlen);
+/* H2D bytes of the last pg_sampler_cohort_new[_device] / pg_sampler_then_job of this thread: [0] index arrays, [1] per-sample
+ * arrays (cohort: the k-mer counts alone, 2 * sumK per sample and contig, 0 for _device; pg_sampler_then_job: the counts and the
+ * emission costs the host formed from them).  Pointer tables and the reduced panel's offsets are not counted; neither is what
  * pg_job_new uploads itself (the coverage). */
 int pg_sampler_last_h2d_bytes(uint64_t out2[2]);
-/* Wall / kernel milliseconds of the last pg_sampler_cohort_new of this thread: [0] host preparation (checks, transition
+/* Wall / kernel milliseconds of the last pg_sampler_cohort_new[_device] of this thread: [0] host preparation (checks, transition
  * costs, plan), [1] H2D uploads, [2] emission cost kernel (hipEvents), [3] slot tables and their per-chain copies
  * (hipEvents), [4] the passes incl. the read-back of sampled paths, [5] the panel reduction, [6] pg_job_new, [7] the call. */
 int pg_sampler_last_phase_ms(double out8[8]);

@@ -549,6 +549,19 @@ __global__ __launch_bounds__(256) void ks_slot_copy(const CostDev* cds) {
     for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (size_t)gridDim.x * 256) dst[g] = src[g];
 }
 
+// pg_sampler_cohort_new_device: every chain's coverage (device arrays of the caller, anywhere) gathered into ONE contiguous
+// buffer that a single D2H copy brings back (pg_job_new takes the coverage from the host): grid = (blocks, chains)
+struct CovDev {
+    const uint16_t* src;   // [V] the sample's coverage of the chain's contig
+    uint16_t* dst;         // the chain's place in the packed buffer
+    uint32_t V, pad;
+};
+
+__global__ __launch_bounds__(256) void ks_cov_pack(const CovDev* cvs) {
+    const CovDev d = cvs[blockIdx.y];
+    for (uint32_t v = blockIdx.x * 256u + threadIdx.x; v < d.V; v += gridDim.x * 256u) d.dst[v] = d.src[v];
+}
+
 __global__ void ks_minima(const uint32_t* column, const uint8_t* mask, uint32_t n, uint32_t* out4) {
     __shared__ unsigned long long s_k1[4], s_k2[4];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -1152,23 +1165,27 @@ done:
 //  table (ks_slot_copy, V*P bytes D2D per chain; DESIGN.md 4b has the measurement behind that choice).  The passes are
 //  run_passes over n_samples * n_live SamplerDevs whose index pointers alias the shared arrays; the reduction is ku_count /
 //  ku_write per chain; the job is pg_job_new over the reduced panels, on the device, after every sampler buffer is freed.
+//
+//  pg_sampler_cohort_new_device is the same body with the samples' arrays already in HBM (`counts_on_device`): the counts are
+//  read where they lie (CostDev / UpdateDev point at the caller's arrays; the chain arena holds no copy), and the coverage,
+//  which pg_job_new wants on the host, is packed by ks_cov_pack and read back once.  `fn` names the entry in messages.
 // ------------------------------------------------------------------------------------------------
-extern "C" int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_contig_batch* index, uint32_t n_samples,
-                                     const pg_sample_counts* samples, uint32_t size, int add_reference, double sampling_recombrate,
-                                     long double sampling_effective_N, uint16_t allele_penalty, const pg_table* table,
-                                     const pg_hmm_params* params, uint32_t* const* sampled_paths, uint32_t* const* best_scores,
-                                     pg_job** out_job, char* err, size_t errlen) {
+static int cohort_build(const char* fn, bool counts_on_device, int device, uint32_t n_contigs, const pg_contig_batch* index, uint32_t n_samples,
+                        const pg_sample_counts* samples, uint32_t size, int add_reference, double sampling_recombrate,
+                        long double sampling_effective_N, uint16_t allele_penalty, const pg_table* table,
+                        const pg_hmm_params* params, uint32_t* const* sampled_paths, uint32_t* const* best_scores,
+                        pg_job** out_job, char* err, size_t errlen) {
     using clk = std::chrono::steady_clock;
     const auto t_start = clk::now();
     auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
     if (out_job) *out_job = nullptr;
     g_last_h2d[0] = g_last_h2d[1] = 0;
     for (double& x : g_last_phase_ms) x = 0.0;
-    if (!index || !samples || !table || !params || !out_job || n_contigs == 0) { set_err(err, errlen, "pg_sampler_cohort_new: null argument"); return PG_ERR_INVALID; }
-    if (n_samples == 0) { set_err(err, errlen, "pg_sampler_cohort_new: no samples"); return PG_ERR_INVALID; }
-    if (size < 1) { set_err(err, errlen, "pg_sampler_cohort_new: at least one pass"); return PG_ERR_INVALID; }
+    if (!index || !samples || !table || !params || !out_job || n_contigs == 0) { set_err(err, errlen, "%s: null argument", fn); return PG_ERR_INVALID; }
+    if (n_samples == 0) { set_err(err, errlen, "%s: no samples", fn); return PG_ERR_INVALID; }
+    if (size < 1) { set_err(err, errlen, "%s: at least one pass", fn); return PG_ERR_INVALID; }
     const uint32_t S = size + (add_reference ? 1u : 0u);
-    if (S > KU_MAX_PATHS) { set_err(err, errlen, "pg_sampler_cohort_new: at most %u kept paths", KU_MAX_PATHS); return PG_ERR_UNSUPPORTED; }
+    if (S > KU_MAX_PATHS) { set_err(err, errlen, "%s: at most %u kept paths", fn, KU_MAX_PATHS); return PG_ERR_UNSUPPORTED; }
     // ---- host preparation: checks, transition costs (index level), the cost table
     std::vector<uint32_t> live;                               // index contigs with variants
     std::vector<std::vector<uint32_t>> tcost(n_contigs);
@@ -1191,11 +1208,11 @@ extern "C" int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_co
             const uint32_t V = index[c].n_variants;
             if (V == 0) continue;
             if (index[c].kmer_off[V] > 0 && (!samples[s].kmer_count || !samples[s].kmer_count[c])) {
-                set_err(err, errlen, "pg_sampler_cohort_new: sample %u has no k-mer counts for contig %u", s, c);
+                set_err(err, errlen, "%s: sample %u has no k-mer counts for contig %u", fn, s, c);
                 return PG_ERR_INVALID;
             }
             if (!samples[s].coverage || !samples[s].coverage[c]) {
-                set_err(err, errlen, "pg_sampler_cohort_new: sample %u has no coverage for contig %u", s, c);
+                set_err(err, errlen, "%s: sample %u has no coverage for contig %u", fn, s, c);
                 return PG_ERR_INVALID;
             }
         }
@@ -1206,6 +1223,23 @@ extern "C" int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_co
     int ndev = 0, rc = PG_OK;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_err(err, errlen, "no HIP device available (no CPU fallback)"); return PG_ERR_DEVICE; }
     if (device < 0 || device >= ndev) { set_err(err, errlen, "bad device %d", device); return PG_ERR_INVALID; }
+    if (counts_on_device)   // a host pointer would fault a kernel: refused here, before anything is allocated or launched
+        for (uint32_t s = 0; s < n_samples; ++s)
+            for (uint32_t c = 0; c < n_contigs; ++c) {
+                const uint32_t V = index[c].n_variants;
+                if (V == 0) continue;
+                for (int which = 0; which < 2; ++which) {
+                    if (which == 0 && index[c].kmer_off[V] == 0) continue;
+                    const void* ptr = which ? (const void*)samples[s].coverage[c] : (const void*)samples[s].kmer_count[c];
+                    hipPointerAttribute_t at;
+                    if (hipPointerGetAttributes(&at, ptr) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
+                        (void)hipGetLastError();
+                        set_err(err, errlen, "%s: sample %u, contig %u: the %s array is not in the memory of device %d", fn, s, c,
+                                which ? "coverage" : "kmer_count", device);
+                        return PG_ERR_INVALID;
+                    }
+                }
+            }
     uint32_t NW = 1;
     while (NW * 256u < maxP) NW *= 2;                        // 4 paths per lane
     const uint32_t T = NW * 64u;
@@ -1214,7 +1248,7 @@ extern "C" int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_co
         for (uint32_t present = 0; present <= 32u; ++present) cost33[total * 33u + present] = emission_cost_of(present, total);
     const uint32_t nL = (uint32_t)live.size(), nch = n_samples * nL;   // chain j = s * nL + l runs contig live[l] of sample s
     if ((uint64_t)n_samples * nL > 65535u) {   // (the chains are a grid dimension of the pass kernels)
-        set_err(err, errlen, "pg_sampler_cohort_new: at most 65535 sampled chains per call (%u samples x %u contigs with variants): split the samples", n_samples, nL);
+        set_err(err, errlen, "%s: at most 65535 sampled chains per call (%u samples x %u contigs with variants): split the samples", fn, n_samples, nL);
         return PG_ERR_UNSUPPORTED;
     }
 
@@ -1241,7 +1275,7 @@ extern "C" int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_co
         const pg_contig_batch& b = index[live[j % nL]];
         const size_t V = b.n_variants, P = b.n_paths, sumA = b.allele_off[V], sumK = b.kmer_off[V];
         ChOffs& o = co[j];
-        o.kcnt = take(o_ch, sumK * 2); o.ec = take(o_ch, sumA * 2); o.paths = take(o_ch, (size_t)size * V * 4); o.best = take(o_ch, (size_t)size * 4);
+        o.kcnt = counts_on_device ? 0 : take(o_ch, sumK * 2); o.ec = take(o_ch, sumA * 2); o.paths = take(o_ch, (size_t)size * V * 4); o.best = take(o_ch, (size_t)size * 4);
         if (fast) {
             o.slot = take(o_pass, (V * P + 15) / 16 * 16); o.ecell = take(o_pass, (V + 32) * T * 8); o.stay = take(o_pass, ((V + 14) / 16 + 1) * 2 * T * 4);
             o.minima = take(o_pass, V * 4); o.last = take(o_pass, 4); o.bt = o.last_col = 0;
@@ -1254,11 +1288,17 @@ extern "C" int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_co
         o.offs = red_offs; red_offs += 2 * (V + 1);
     }
     const size_t o_devs = take(o_pass, sizeof(SamplerDev) * nch), o_cdevs = take(o_pass, sizeof(CostDev) * nch), o_ldevs = take(o_pass, sizeof(SamplerDev) * nL);
+    // (_device) all chains' coverage back to back in chain order, and the packing kernel's table
+    std::vector<size_t> cov_at(nch + 1, 0);
+    for (uint32_t j = 0; j < nch; ++j) cov_at[j + 1] = cov_at[j] + index[live[j % nL]].n_variants;
+    const size_t o_cov = counts_on_device ? take(o_pass, cov_at[nch] * 2) : 0, o_cvdevs = counts_on_device ? take(o_pass, sizeof(CovDev) * nch) : 0;
+    std::vector<uint16_t> cov_h(counts_on_device ? cov_at[nch] + 1 : 0);
     const size_t o_counts = take(o_red, red_counts * 4), o_offs = take(o_red, red_offs * 4), o_err = take(o_red, 4);
 
     unsigned char *idx = nullptr, *ch = nullptr, *pass = nullptr, *red = nullptr;
     std::vector<SamplerDev> devs(nch), ldevs(nL);
     std::vector<CostDev> cdevs(nch);
+    std::vector<const uint16_t*> kcnt_of;   // [nch] the chain's k-mer counts on the device: its own upload, or the caller's array
     std::unique_ptr<uint32_t[]> counts_h(new uint32_t[red_counts + 1]), offs_h(new uint32_t[red_offs + 1]);   // (every entry is written: no fill)
     std::vector<pg_contig_batch> nb((size_t)n_samples * n_contigs);
     uint32_t dev_err = 0;
@@ -1277,9 +1317,9 @@ extern "C" int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_co
         (void)hipGetLastError();
         *p = nullptr;
         set_err(err, errlen,
-                "pg_sampler_cohort_new: %u samples x %u contigs need %zu bytes of device memory at the peak (index %zu, per-sample %zu, "
+                "%s: %u samples x %u contigs need %zu bytes of device memory at the peak (index %zu, per-sample %zu, "
                 "pass buffers %zu, reduced panels %zu; then the job beside the reduced panels): split the samples",
-                n_samples, n_contigs, o_idx + o_ch + (o_pass > o_red ? o_pass : o_red), o_idx, o_ch, o_pass, o_red);
+                fn, n_samples, n_contigs, o_idx + o_ch + (o_pass > o_red ? o_pass : o_red), o_idx, o_ch, o_pass, o_red);
         return PG_ERR_NOMEM;
     };
     g_last_phase_ms[0] = ms_since(t_start);
@@ -1307,9 +1347,12 @@ extern "C" int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_co
         }
         HIP_TRY(hipMemcpy(idx + o_cost33, cost33, sizeof(cost33), hipMemcpyHostToDevice));
         g_last_h2d[0] += sizeof(cost33);
+        kcnt_of.resize(nch);
         for (uint32_t j = 0; j < nch; ++j) {
             const uint32_t s = j / nL, c = live[j % nL];
             const size_t sumK = index[c].kmer_off[index[c].n_variants];
+            if (counts_on_device) { kcnt_of[j] = sumK ? samples[s].kmer_count[c] : nullptr; continue; }   // (read where they lie; none: never read)
+            kcnt_of[j] = (const uint16_t*)(ch + co[j].kcnt);
             if (sumK) HIP_TRY(hipMemcpy(ch + co[j].kcnt, samples[s].kmer_count[c], sumK * 2, hipMemcpyHostToDevice));
             g_last_h2d[1] += sumK * 2;
         }
@@ -1346,7 +1389,7 @@ extern "C" int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_co
             q.V = (uint32_t)V;
             q.allele_off = d.allele_off; q.kmer_off = (const uint32_t*)(idx + x.koff); q.allele_flags = idx + x.aflag;
             q.allele_koff = (const uint16_t*)(idx + x.akoff); q.allele_kmask = (const uint32_t*)(idx + x.akmask);
-            q.kmer_count = (const uint16_t*)(ch + o.kcnt); q.ecost = d.ecost;
+            q.kmer_count = kcnt_of[j]; q.ecost = d.ecost;
             if (fast) { q.slot_src = idx + x.slot; q.slot_dst = d.slot; q.slot_bytes = (V * P + 15) / 16 * 16; }
         }
         HIP_TRY(hipMemcpy(pass + o_devs, devs.data(), sizeof(SamplerDev) * nch, hipMemcpyHostToDevice));
@@ -1382,6 +1425,18 @@ extern "C" int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_co
             if (sampled_paths && sampled_paths[g]) HIP_TRY(hipMemcpy(sampled_paths[g], ch + co[j].paths, (size_t)size * V * 4, hipMemcpyDeviceToHost));
             if (best_scores && best_scores[g]) HIP_TRY(hipMemcpy(best_scores[g], ch + co[j].best, (size_t)size * 4, hipMemcpyDeviceToHost));
         }
+        if (counts_on_device) {   // every chain's coverage: one kernel, one copy
+            std::vector<CovDev> cvdevs(nch);
+            for (uint32_t j = 0; j < nch; ++j) {
+                const uint32_t s = j / nL, c = live[j % nL];
+                cvdevs[j].src = samples[s].coverage[c]; cvdevs[j].dst = (uint16_t*)(pass + o_cov) + cov_at[j];
+                cvdevs[j].V = index[c].n_variants; cvdevs[j].pad = 0;
+            }
+            HIP_TRY(hipMemcpy(pass + o_cvdevs, cvdevs.data(), sizeof(CovDev) * nch, hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(ks_cov_pack, dim3(16, nch), dim3(256), 0, nullptr, (const CovDev*)(pass + o_cvdevs));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpy(cov_h.data(), pass + o_cov, cov_at[nch] * 2, hipMemcpyDeviceToHost));
+        }
         g_last_phase_ms[4] = ms_since(t);
         HIP_TRY(hipFree(pass));
         pass = nullptr;
@@ -1398,7 +1453,7 @@ extern "C" int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_co
                 UpdateDev d;
                 memset(&d, 0, sizeof(d));
                 d.V = b.n_variants; d.P = b.n_paths; d.S = S; d.size = size;
-                d.kmer_off = (const uint32_t*)(idx + x.koff); d.kmer_count = (const uint16_t*)(ch + o.kcnt);
+                d.kmer_off = (const uint32_t*)(idx + x.koff); d.kmer_count = kcnt_of[j];
                 d.allele_off = (const uint32_t*)(idx + x.aoff); d.allele_id = (const uint16_t*)(idx + x.aid);
                 d.allele_flags = idx + x.aflag; d.allele_koff = (const uint16_t*)(idx + x.akoff); d.allele_kmask = (const uint32_t*)(idx + x.akmask);
                 d.path_allele = (const uint16_t*)(idx + x.pa); d.paths = (const uint32_t*)(ch + o.paths);
@@ -1414,7 +1469,7 @@ extern "C" int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_co
             HIP_TRY(hipStreamSynchronize(nullptr));
             HIP_TRY(hipMemcpy(&dev_err, red + o_err, 4, hipMemcpyDeviceToHost));
             if (phase == 0) {
-                if (dev_err & 1u) { set_err(err, errlen, "pg_sampler_cohort_new: a variant has more than %u alleles or %u k-mers", KU_MAX_ALLELES, KU_MAX_KMERS); rc = PG_ERR_UNSUPPORTED; goto done; }
+                if (dev_err & 1u) { set_err(err, errlen, "%s: a variant has more than %u alleles or %u k-mers", fn, KU_MAX_ALLELES, KU_MAX_KMERS); rc = PG_ERR_UNSUPPORTED; goto done; }
                 // all chains' counts -> offsets in one round trip (the job's arena is planned from them on the host)
                 HIP_TRY(hipMemcpy(counts_h.get(), red + o_counts, red_counts * 4, hipMemcpyDeviceToHost));
                 for (uint32_t j = 0; j < nch; ++j) {
@@ -1427,7 +1482,7 @@ extern "C" int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_co
                 }
                 HIP_TRY(hipMemcpy(red + o_offs, offs_h.get(), red_offs * 4, hipMemcpyHostToDevice));
             } else if (dev_err & 2u) {
-                set_err(err, errlen, "pg_sampler_cohort_new: an allele's k-mers span more than 32 positions after the update");
+                set_err(err, errlen, "%s: an allele's k-mers span more than 32 positions after the update", fn);
                 rc = PG_ERR_INVALID;
                 goto done;
             }
@@ -1449,9 +1504,10 @@ extern "C" int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_co
                 pg_contig_batch& q = nb[(size_t)s * n_contigs + c];
                 q = index[c];
                 q.kmer_count = nullptr;
-                q.coverage = samples[s].coverage ? samples[s].coverage[c] : nullptr;
+                q.coverage = counts_on_device ? &no_counts : samples[s].coverage ? samples[s].coverage[c] : nullptr;   // (a device pointer never goes to the host's side)
                 if (index[c].n_variants == 0) continue;
                 const uint32_t j = s * nL + live_of[c];
+                if (counts_on_device) q.coverage = cov_h.data() + cov_at[j];
                 const ChOffs& o = co[j];
                 q.n_paths = S;
                 q.kmer_off = offs_h.get() + o.offs; q.allele_off = offs_h.get() + o.offs + (index[c].n_variants + 1);
@@ -1470,6 +1526,93 @@ done:
     if (red) hipFree(red);
     g_last_phase_ms[7] = ms_since(t_start);
     return rc;
+}
+
+extern "C" int pg_sampler_cohort_new(int device, uint32_t n_contigs, const pg_contig_batch* index, uint32_t n_samples,
+                                     const pg_sample_counts* samples, uint32_t size, int add_reference, double sampling_recombrate,
+                                     long double sampling_effective_N, uint16_t allele_penalty, const pg_table* table,
+                                     const pg_hmm_params* params, uint32_t* const* sampled_paths, uint32_t* const* best_scores,
+                                     pg_job** out_job, char* err, size_t errlen) {
+    return cohort_build("pg_sampler_cohort_new", false, device, n_contigs, index, n_samples, samples, size, add_reference, sampling_recombrate,
+                        sampling_effective_N, allele_penalty, table, params, sampled_paths, best_scores, out_job, err, errlen);
+}
+
+extern "C" int pg_sampler_cohort_new_device(int device, uint32_t n_contigs, const pg_contig_batch* index, uint32_t n_samples,
+                                            const pg_sample_counts* d_samples, uint32_t size, int add_reference, double sampling_recombrate,
+                                            long double sampling_effective_N, uint16_t allele_penalty, const pg_table* table,
+                                            const pg_hmm_params* params, uint32_t* const* sampled_paths, uint32_t* const* best_scores,
+                                            pg_job** out_job, char* err, size_t errlen) {
+    return cohort_build("pg_sampler_cohort_new_device", true, device, n_contigs, index, n_samples, d_samples, size, add_reference,
+                        sampling_recombrate, sampling_effective_N, allele_penalty, table, params, sampled_paths, best_scores, out_job, err, errlen);
+}
+
+// ------------------------------------------------------------------------------------------------
+//  pg_sampler_counts: the per-sample arrays of a sampled cohort in the making, in one device allocation.  The host library
+//  allocates no device memory of its own; this handle is what gives it arrays a count plan can fill and
+//  pg_sampler_cohort_new_device can read.
+// ------------------------------------------------------------------------------------------------
+struct pg_sampler_counts {
+    int device = 0;
+    uint32_t n_contigs = 0, n_samples = 0;
+    unsigned char* arena = nullptr;
+    std::vector<uint16_t*> kmer_count, coverage;   // [n_samples * n_contigs], row s at s * n_contigs
+};
+
+extern "C" int pg_sampler_counts_new(int device, uint32_t n_contigs, const uint64_t* n_kmers, const uint32_t* n_variants, uint32_t n_samples,
+                                     pg_sampler_counts** out, char* err, size_t errlen) {
+    if (out) *out = nullptr;
+    if (!n_kmers || !n_variants || !out) { set_err(err, errlen, "pg_sampler_counts_new: null argument"); return PG_ERR_INVALID; }
+    if (n_contigs == 0 || n_samples == 0) { set_err(err, errlen, "pg_sampler_counts_new: no %s", n_contigs == 0 ? "contigs" : "samples"); return PG_ERR_INVALID; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); set_err(err, errlen, "no HIP device available (no CPU fallback)"); return PG_ERR_DEVICE; }
+    if (device < 0 || device >= ndev) { set_err(err, errlen, "bad device %d", device); return PG_ERR_INVALID; }
+    size_t off = 0;
+    auto take = [&off](size_t bytes) { off = (off + 255) / 256 * 256; size_t o = off; off += bytes ? bytes : 8; return o; };
+    const size_t n = (size_t)n_samples * n_contigs;
+    std::vector<size_t> ok(n), oc(n);
+    for (size_t g = 0; g < n; ++g) { ok[g] = take((size_t)n_kmers[g % n_contigs] * 2); oc[g] = take((size_t)n_variants[g % n_contigs] * 2); }
+    pg_sampler_counts* h = new pg_sampler_counts;
+    h->device = device; h->n_contigs = n_contigs; h->n_samples = n_samples;
+    hipError_t he = hipSetDevice(device);
+    if (he == hipSuccess) he = hipMalloc((void**)&h->arena, off);
+    if (he == hipErrorOutOfMemory) {   // cached arenas of the one-shot call may be what stands in the way
+        (void)hipGetLastError();
+        pg_hmm_release_cache();
+        hipSetDevice(device);
+        he = hipMalloc((void**)&h->arena, off);
+    }
+    if (he != hipSuccess) {
+        (void)hipGetLastError();
+        delete h;
+        if (he == hipErrorOutOfMemory) {
+            set_err(err, errlen, "pg_sampler_counts_new: %u samples x %u contigs need %zu bytes of device memory: fewer samples per handle", n_samples, n_contigs, off);
+            return PG_ERR_NOMEM;
+        }
+        set_err(err, errlen, "pg_sampler_counts_new: hipMalloc(%zu bytes) failed: %s", off, hipGetErrorString(he));
+        return PG_ERR_DEVICE;
+    }
+    h->kmer_count.resize(n); h->coverage.resize(n);
+    for (size_t g = 0; g < n; ++g) { h->kmer_count[g] = (uint16_t*)(h->arena + ok[g]); h->coverage[g] = (uint16_t*)(h->arena + oc[g]); }
+    *out = h;
+    return PG_OK;
+}
+
+extern "C" int pg_sampler_counts_destroy(pg_sampler_counts* h) {
+    if (!h) return PG_OK;
+    if (h->arena) { hipSetDevice(h->device); hipFree(h->arena); }
+    delete h;
+    return PG_OK;
+}
+
+extern "C" int pg_sampler_counts_rows(const pg_sampler_counts* h, uint32_t sample, uint16_t* const** d_kmer_count, uint16_t* const** d_coverage,
+                                      char* err, size_t errlen) {
+    if (d_kmer_count) *d_kmer_count = nullptr;
+    if (d_coverage) *d_coverage = nullptr;
+    if (!h) { set_err(err, errlen, "pg_sampler_counts_rows: null handle"); return PG_ERR_INVALID; }
+    if (sample >= h->n_samples) { set_err(err, errlen, "pg_sampler_counts_rows: sample %u of %u", sample, h->n_samples); return PG_ERR_INVALID; }
+    if (d_kmer_count) *d_kmer_count = h->kmer_count.data() + (size_t)sample * h->n_contigs;
+    if (d_coverage) *d_coverage = h->coverage.data() + (size_t)sample * h->n_contigs;
+    return PG_OK;
 }
 
 extern "C" int pg_sampler_last_h2d_bytes(uint64_t out2[2]) {

@@ -875,6 +875,11 @@ SampleCounts DeviceCountPlan::fill(size_t kmer_coverage) {
     return out;
 }
 
+void DeviceCountPlan::fill_device(size_t kmer_coverage, uint16_t* const* d_kmer_count, uint16_t* const* d_coverage) {
+    const int rc = pg_count_plan_fill_device(plan_of(handle_), kmer_coverage, d_kmer_count, d_coverage);
+    if (rc != PG_OK) throw std::runtime_error(std::string("DeviceCountPlan: pg_count_plan_fill_device failed (") + std::to_string(rc) + "): " + pg_kmer_last_error());
+}
+
 void DeviceCountPlan::fill_into(UniqueKmersMap* index, size_t kmer_coverage) {
     const SampleCounts counts = fill(kmer_coverage);
     for (size_t c = 0; c < names_.size(); ++c) {

@@ -174,6 +174,9 @@ public:
     DeviceCountPlan& operator=(const DeviceCountPlan&) = delete;
     /** the numbers fill_read_kmercounts_all + SampleCounts::of give for the reads counted so far */
     SampleCounts fill(size_t kmer_coverage);
+    /** the same numbers into arrays in the memory of the counter's device, one pointer per chromosome in chromosomes()
+     *  order (a pg_sampler_counts row, include/pangenie_sampler.h: pg_sampler_counts_rows); nothing comes back to the host */
+    void fill_device(size_t kmer_coverage, uint16_t* const* d_kmer_count, uint16_t* const* d_coverage);
     /** update_readcount / set_coverage on every object of `index` (the one the plan was made over, or a copy of it): the
      *  drop-in for fill_read_kmercounts_all */
     void fill_into(UniqueKmersMap* index, size_t kmer_coverage);
@@ -201,6 +204,20 @@ std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohor
     UniqueKmersMap& index, const std::string& prefix, const std::vector<std::string>& readfiles, const std::vector<size_t>& kmer_coverages,
     ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
     size_t batch = 64);
+
+/** genotype_cohort_sampled with the counting in it — reads -> counts -> sampler -> HMM with only the reads going up: one
+ *  DeviceKmerCounter and one DeviceCountPlan over `index` (as genotype_cohort_reads makes them); per batch of up to `batch`
+ *  samples one pg_sampler_counts; per sample reset_counts, count(readfiles[s]), fill_device into that sample's rows; per batch
+ *  pg_sampler_cohort_new_device (the counts are read where they lie), one run, and the fetch: 2 bytes of coverage per variant
+ *  and the reduced panels come back.  Returns what genotype_cohort_sampled returns for the SampleCounts of the same samples,
+ *  `sampled` (may be null) the same SampledPaths.  The objects of `index` are not touched.  C ABI errors become
+ *  std::runtime_error; when a batch does not fit the device (PG_ERR_NOMEM) the message says to lower `batch`: batches are
+ *  never split here. */
+std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohort_sampled_reads(
+    UniqueKmersMap& index, const std::string& prefix, const std::vector<std::string>& readfiles, const std::vector<size_t>& kmer_coverages,
+    size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
+    size_t batch = 64, std::vector<std::map<std::string, SampledPaths>>* sampled = nullptr);
 
 /** The reader of the counters' count() on its own: the sequences of a FASTA / FASTQ file (plain or gzipped) in batches of
  *  about `batch_bytes`, back to back with a newline after each, handed to `sink`; returns the bytes of all batches.  With a sink

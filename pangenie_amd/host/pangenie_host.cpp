@@ -812,6 +812,53 @@ std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohor
 }
 
 // ------------------------------------------------------------------ sampled cohort job
+// The fetch tail of one chain of a sampled cohort job (chain id = sample * n_contigs + contig), shared by
+// genotype_cohort_sampled and genotype_cohort_sampled_reads: the reduced panel back from the device (the allele ids of the
+// results are its own), the results over it, and the picks as HaplotypeSampler::get_sampled_paths() has them.  `full` = the
+// contig over ALL paths; `coverage` = the chain's local coverages, or null: then they are what pg_job_fetch hands out (a
+// chain whose counts never were on the host).  Returns the C ABI's code, its text in `err`.
+static int fetch_sampled_chain(pg_job* job, uint32_t chain, const FlatContig& full, const uint16_t* coverage, uint32_t size, bool add_reference,
+                               const uint32_t* picks, std::vector<GenotypingResult>* results, SampledPaths* sampled, char* err, size_t errlen) {
+    const size_t V = full.variant_pos.size();
+    FlatContig r;
+    uint32_t nv = 0, np = 0;
+    uint64_t sk = 0, sa = 0;
+    int rc = pg_job_panel_sizes(job, chain, &nv, &np, &sk, &sa);
+    if (rc != PG_OK) { std::snprintf(err, errlen, "genotype_cohort_sampled: pg_job_panel_sizes failed"); return rc; }
+    r.variant_pos = full.variant_pos;
+    if (coverage) r.coverage.assign(coverage, coverage + V);
+    else r.coverage.assign(V, 0);
+    r.kmer_off.assign(nv + 1, 0); r.allele_off.assign(nv + 1, 0);
+    r.kmer_count.assign(sk, 0); r.allele_id.assign(sa, 0); r.allele_flags.assign(sa, 0); r.allele_kmer_off.assign(sa, 0);
+    r.allele_kmer_mask.assign(sa, 0); r.path_allele.assign((size_t)nv * np, 0);
+    r.paths.resize(V ? np : 0);
+    for (size_t p = 0; p < r.paths.size(); ++p) r.paths[p] = (unsigned short)p;
+    if (V) {
+        rc = pg_job_fetch_panel(job, chain, r.kmer_off.data(), r.kmer_count.data(), r.allele_off.data(), r.allele_id.data(), r.allele_flags.data(),
+                                r.allele_kmer_off.data(), r.allele_kmer_mask.data(), r.path_allele.data(), err, errlen);
+        if (rc != PG_OK) return rc;
+    }
+    r.bind();
+    std::vector<uint64_t> goff(V + 1, 0);
+    pg_hmm_geno_offsets(&r.batch, goff.data());
+    const uint64_t n = goff.back();
+    std::vector<double> lik(n ? n : 1);
+    std::vector<int32_t> lexp(n ? n : 1);
+    std::vector<uint16_t> cov(V ? V : 1);
+    pg_contig_result res{};
+    res.lik = lik.data(); res.lik_exp = lexp.data();
+    if (!coverage) res.coverage = cov.data();
+    rc = pg_job_fetch(job, chain, &res, err, errlen);
+    if (rc != PG_OK) return rc;
+    // (pg_job_fetch hands the coverage out only when the chain has columns: exactly when results_of_chain reads it)
+    *results = results_of_chain(r, coverage ? coverage : cov.data(), goff, lik.data(), lexp.data());
+    if (sampled) {   // as HaplotypeSampler::get_sampled_paths() has them (src/haplotypesampler.cpp:28-44)
+        for (uint32_t i = 0; i < size; ++i) sampled->sampled_paths.emplace_back(picks + (size_t)i * V, picks + (size_t)(i + 1) * V);
+        if (add_reference) sampled->sampled_paths.push_back(std::vector<size_t>(V, 0));
+    }
+    return PG_OK;
+}
+
 std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohort_sampled(
     std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::vector<SampleCounts>& samples,
     size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
@@ -863,47 +910,93 @@ std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohor
     if (rc == PG_OK) rc = pg_job_run(job, nullptr, err, sizeof(err));
     if (rc != PG_OK) { if (job) pg_job_destroy(job); check_rc(rc, err); }
     for (size_t s = 0; s < S && rc == PG_OK; ++s)
-        for (c = 0; c < C && rc == PG_OK; ++c) {
-            const uint32_t chain = (uint32_t)(s * C + c);   // chain id = sample * n_contigs + contig
-            const size_t V = flat[c].variant_pos.size();
-            // the reduced panel of this chain, back from the device: the allele ids of the results are its own
-            FlatContig r;
-            uint32_t nv = 0, np = 0;
-            uint64_t sk = 0, sa = 0;
-            rc = pg_job_panel_sizes(job, chain, &nv, &np, &sk, &sa);
-            if (rc != PG_OK) { std::snprintf(err, sizeof(err), "genotype_cohort_sampled: pg_job_panel_sizes failed"); break; }
-            r.variant_pos = flat[c].variant_pos;
-            r.coverage.assign(cov_rows[s][c], cov_rows[s][c] + V);
-            r.kmer_off.assign(nv + 1, 0); r.allele_off.assign(nv + 1, 0);
-            r.kmer_count.assign(sk, 0); r.allele_id.assign(sa, 0); r.allele_flags.assign(sa, 0); r.allele_kmer_off.assign(sa, 0);
-            r.allele_kmer_mask.assign(sa, 0); r.path_allele.assign((size_t)nv * np, 0);
-            r.paths.resize(V ? np : 0);
-            for (size_t p = 0; p < r.paths.size(); ++p) r.paths[p] = (unsigned short)p;
-            if (V) {
-                rc = pg_job_fetch_panel(job, chain, r.kmer_off.data(), r.kmer_count.data(), r.allele_off.data(), r.allele_id.data(), r.allele_flags.data(),
-                                        r.allele_kmer_off.data(), r.allele_kmer_mask.data(), r.path_allele.data(), err, sizeof(err));
-                if (rc != PG_OK) break;
-            }
-            r.bind();
-            std::vector<uint64_t> goff(V + 1, 0);
-            pg_hmm_geno_offsets(&r.batch, goff.data());
-            const uint64_t n = goff.back();
-            std::vector<double> lik(n ? n : 1);
-            std::vector<int32_t> lexp(n ? n : 1);
-            pg_contig_result res{};
-            res.lik = lik.data(); res.lik_exp = lexp.data();
-            rc = pg_job_fetch(job, chain, &res, err, sizeof(err));
-            if (rc != PG_OK) break;
-            out[s][names[c]] = results_of_chain(r, cov_rows[s][c], goff, lik.data(), lexp.data());
-            if (sampled) {   // as HaplotypeSampler::get_sampled_paths() has them (src/haplotypesampler.cpp:28-44)
-                SampledPaths& sp = (*sampled)[s][names[c]];
-                const uint32_t* pk = picks[s * C + c].data();
-                for (uint32_t i = 0; i < size; ++i) sp.sampled_paths.emplace_back(pk + (size_t)i * V, pk + (size_t)(i + 1) * V);
-                if (add_reference) sp.sampled_paths.push_back(std::vector<size_t>(V, 0));
-            }
-        }
+        for (c = 0; c < C && rc == PG_OK; ++c)
+            rc = fetch_sampled_chain(job, (uint32_t)(s * C + c), flat[c], cov_rows[s][c], size, add_reference, sampled ? picks[s * C + c].data() : nullptr,
+                                     &out[s][names[c]], sampled ? &(*sampled)[s][names[c]] : nullptr, err, sizeof(err));
     pg_job_destroy(job);
     check_rc(rc, err);
+    return out;
+}
+
+// ------------------------------------------------------------------ sampled cohort job fed by the device counter
+std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohort_sampled_reads(
+    UniqueKmersMap& index, const std::string& prefix, const std::vector<std::string>& readfiles, const std::vector<size_t>& kmer_coverages,
+    size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device, size_t batch,
+    std::vector<std::map<std::string, SampledPaths>>* sampled) {
+    auto& chromosomes = index.unique_kmers;
+    const size_t C = chromosomes.size(), S = readfiles.size();
+    if (kmer_coverages.size() != S) fail("genotype_cohort_sampled_reads: one k-mer coverage per read file");
+    std::vector<std::map<std::string, std::vector<GenotypingResult>>> out(S);
+    if (sampled) sampled->assign(S, {});
+    if (C == 0 || S == 0) return out;
+    const size_t B = std::max<size_t>(1, std::min(batch, S));
+    DeviceKmerCounter counter(index.kmersize, false, device);
+    DeviceCountPlan plan(counter, index, prefix, true);
+    std::vector<std::string> names;
+    std::vector<FlatContig> flat(C);   // ALL paths of the panel
+    std::vector<pg_contig_batch> batches(C);
+    std::vector<uint64_t> n_kmers(C);
+    std::vector<uint32_t> n_variants(C);
+    size_t c = 0;
+    for (auto& kv : chromosomes) {   // (map order: the plan's)
+        names.push_back(kv.first);
+        flatten(&kv.second, nullptr, flat[c]);
+        batches[c] = flat[c].batch;
+        n_kmers[c] = flat[c].kmer_count.size();
+        n_variants[c] = (uint32_t)flat[c].variant_pos.size();
+        c += 1;
+    }
+    const uint32_t size = (uint32_t)panel_size;
+    pg_hmm_params prm{};
+    prm.effective_N = effective_N; prm.recombrate = recombrate; prm.uniform = uniform ? 1 : 0; prm.run_genotyping = 1;
+    char err[1024] = {0};
+    auto check_batch = [&](int rc) {   // (a batch that does not fit: the caller's remedy is a smaller one, it is never split here)
+        if (rc == PG_ERR_NOMEM) fail(std::string(err) + " (genotype_cohort_sampled_reads: lower `batch`)");
+        check_rc(rc, err);
+    };
+    for (size_t s0 = 0; s0 < S; s0 += B) {
+        const size_t n = std::min(B, S - s0);
+        pg_sampler_counts* counts = nullptr;
+        pg_job* job = nullptr;
+        int rc = pg_sampler_counts_new(device, (uint32_t)C, n_kmers.data(), n_variants.data(), (uint32_t)n, &counts, err, sizeof(err));
+        check_batch(rc);
+        try {
+            std::vector<pg_sample_counts> rows(n);
+            for (size_t s = 0; s < n; ++s) {
+                uint16_t* const* d_k = nullptr;
+                uint16_t* const* d_c = nullptr;
+                check_rc(pg_sampler_counts_rows(counts, (uint32_t)s, &d_k, &d_c, err, sizeof(err)), err);
+                counter.reset_counts();
+                counter.count(readfiles[s0 + s]);
+                plan.fill_device(kmer_coverages[s0 + s], d_k, d_c);
+                rows[s].kmer_count = d_k;
+                rows[s].coverage = d_c;
+            }
+            std::vector<std::vector<uint32_t>> picks(sampled ? n * C : 0);
+            std::vector<uint32_t*> pick_rows(n * C, nullptr);
+            for (size_t g = 0; g < picks.size(); ++g) {
+                picks[g].assign((size_t)size * flat[g % C].variant_pos.size() + 1, 0);
+                pick_rows[g] = picks[g].data();
+            }
+            rc = pg_sampler_cohort_new_device(device, (uint32_t)C, batches.data(), (uint32_t)n, rows.data(), size, add_reference ? 1 : 0, recombrate,
+                                              sampling_effective_N, allele_penalty, probabilities->handle(), &prm, sampled ? pick_rows.data() : nullptr,
+                                              nullptr, &job, err, sizeof(err));
+            pg_sampler_counts_destroy(counts);   // (the job does not reference the arrays)
+            counts = nullptr;
+            if (rc == PG_OK) rc = pg_job_run(job, nullptr, err, sizeof(err));
+            for (size_t s = 0; s < n && rc == PG_OK; ++s)
+                for (c = 0; c < C && rc == PG_OK; ++c)
+                    rc = fetch_sampled_chain(job, (uint32_t)(s * C + c), flat[c], nullptr, size, add_reference, sampled ? picks[s * C + c].data() : nullptr,
+                                             &out[s0 + s][names[c]], sampled ? &(*sampled)[s0 + s][names[c]] : nullptr, err, sizeof(err));
+        } catch (...) {
+            if (counts) pg_sampler_counts_destroy(counts);
+            if (job) pg_job_destroy(job);
+            throw;
+        }
+        if (job) pg_job_destroy(job);
+        check_batch(rc);
+    }
     return out;
 }
 

@@ -324,8 +324,15 @@ class CountPlan:
         _check(_counts().pg_count_plan_fill_host(self._h, int(kmer_coverage), pk, pc), "pg_count_plan_fill_host")
         return kc, cv
 
-    def fill_device(self, kmer_coverage: int, device: int = 0):
-        """the same into torch tensors on the counter's device (dtype int16: the bits are the uint16 values)"""
+    def fill_device(self, kmer_coverage: int, device: int = 0, out=None):
+        """the same into torch tensors on the counter's device (dtype int16: the bits are the uint16 values).  `out`: two
+        tables of device pointers, one entry per contig (pangenie_amd.sampler.SamplerCounts.rows(s)): the arrays they point
+        at are filled instead, nothing is allocated, and `out` is returned."""
+        if out is not None:
+            pk, pc = out
+            _check(_counts().pg_count_plan_fill_device(self._h, int(kmer_coverage), C.cast(pk, C.POINTER(C.c_void_p)),
+                                                       C.cast(pc, C.POINTER(C.c_void_p))), "pg_count_plan_fill_device")
+            return out
         import torch
         dev = torch.device("cuda", int(device))
         kc = [torch.zeros(nk, dtype=torch.int16, device=dev) for nk, _ in self._sizes()]

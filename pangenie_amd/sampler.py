@@ -46,6 +46,16 @@ def _hip():
                                               C.c_uint32, C.c_int, C.c_double, ld, C.c_uint16, C.c_void_p, C.c_void_p,
                                               C.POINTER(u32p), C.POINTER(u32p), C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
         lib.pg_sampler_cohort_new.restype = C.c_int
+        lib.pg_sampler_cohort_new_device.argtypes = lib.pg_sampler_cohort_new.argtypes
+        lib.pg_sampler_cohort_new_device.restype = C.c_int
+        lib.pg_sampler_counts_new.argtypes = [C.c_int, C.c_uint32, C.POINTER(C.c_uint64), u32p, C.c_uint32, C.POINTER(C.c_void_p),
+                                              C.c_char_p, C.c_size_t]
+        lib.pg_sampler_counts_new.restype = C.c_int
+        lib.pg_sampler_counts_destroy.argtypes = [C.c_void_p]
+        lib.pg_sampler_counts_destroy.restype = C.c_int
+        lib.pg_sampler_counts_rows.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(u16p)), C.POINTER(C.POINTER(u16p)),
+                                               C.c_char_p, C.c_size_t]
+        lib.pg_sampler_counts_rows.restype = C.c_int
         lib.pg_sampler_last_h2d_bytes.argtypes = [C.POINTER(C.c_uint64)]
         lib.pg_sampler_last_h2d_bytes.restype = C.c_int
         lib.pg_sampler_last_phase_ms.argtypes = [f64p]
@@ -56,7 +66,8 @@ def _hip():
 
 SAMPLER_ABI_SYMBOLS = ["pg_sampler_emission_costs", "pg_sampler_transition_cost", "pg_sampler_column_minima",
                        "pg_sampler_run", "pg_sampler_run_batch", "pg_sampler_last_ms", "pg_sampler_then_job",
-                       "pg_sampler_cohort_new", "pg_sampler_last_phase_ms"]
+                       "pg_sampler_cohort_new", "pg_sampler_last_phase_ms", "pg_sampler_cohort_new_device",
+                       "pg_sampler_counts_new", "pg_sampler_counts_destroy", "pg_sampler_counts_rows"]
 # (pg_sampler_last_h2d_bytes is exported too; it stays off this list, which mirrors the header's letters-only names)
 NO_ID = 0xFFFFFFFF
 
@@ -238,6 +249,176 @@ def sample_cohort(index: Sequence[ContigBatch], samples, size: int, table, param
     h = C.c_void_p()
     rc = _hip().pg_sampler_cohort_new(device, nc, arr, ns, cs, size, int(bool(add_reference)), float(recombrate), _c_ld(effective_N),
                                       int(allele_penalty), table.h, C.byref(params), sp, bp, C.byref(h), err, 1024)
+    del keep
+    if rc:
+        raise hmm.PanGenieError(rc, err.value.decode(errors="replace"))
+    job = hmm.Job.from_handle(h.value, table, params)
+    if want_paths:
+        return (job, [[s[:, : b.n_variants] for s, b in zip(row, index)] for row in sampled],
+                [[x[:size] for x in row] for row in best])
+    return job, None, None
+
+
+def _memcpy(dst: int, src: int, nbytes: int, kind: int) -> None:
+    """hipMemcpy of the HIP runtime the product library is linked against, found through the library's own handle (kind 2:
+    device to host, 3: device to device)"""
+    fn = _hip().hipMemcpy
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    fn.restype = C.c_int
+    rc = fn(C.c_void_p(dst), C.c_void_p(src), nbytes, kind)
+    if rc:
+        raise RuntimeError(f"hipMemcpy: error {rc}")
+
+
+class SamplerCounts:
+    """pg_sampler_counts: for each of n_samples samples and every contig of `index` one uint16 array of the contig's k-mers
+    and one of its variants, in one allocation on `device` — what CountPlan.fill_device(out=counts.rows(s)) fills and
+    sample_cohort_device reads.  A context manager; the arrays are gone when it closes."""
+
+    def __init__(self, index: Sequence[ContigBatch], n_samples: int, device: int = 0):
+        from . import hmm
+        self.sizes = [(int(b.kmer_off[-1]), int(b.n_variants)) for b in index]
+        self.n_samples, self.device = int(n_samples), int(device)
+        nc = len(self.sizes)
+        nk = (C.c_uint64 * max(nc, 1))(*[k for k, _ in self.sizes])
+        nv = (C.c_uint32 * max(nc, 1))(*[v for _, v in self.sizes])
+        self._h = C.c_void_p()
+        err = C.create_string_buffer(512)
+        rc = _hip().pg_sampler_counts_new(self.device, nc, nk, nv, self.n_samples, C.byref(self._h), err, 512)
+        if rc:
+            raise hmm.PanGenieError(rc, err.value.decode(errors="replace"))
+
+    def close(self) -> None:
+        if self._h:
+            _hip().pg_sampler_counts_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def rows(self, sample: int):
+        """(d_kmer_count, d_coverage): the handle's own pointer tables of one sample, [n_contigs] device pointers each"""
+        from . import hmm
+        pk, pc = C.POINTER(u16p)(), C.POINTER(u16p)()
+        err = C.create_string_buffer(256)
+        rc = _hip().pg_sampler_counts_rows(self._h, int(sample), C.byref(pk), C.byref(pc), err, 256)
+        if rc:
+            raise hmm.PanGenieError(rc, err.value.decode(errors="replace"))
+        return pk, pc
+
+    def pointers(self, sample: int):
+        """the same as integers: ([address of kmer_count[c]], [address of coverage[c]])"""
+        pk, pc = self.rows(sample)
+        addr = lambda p: C.cast(p, C.c_void_p).value
+        return [addr(pk[c]) for c in range(len(self.sizes))], [addr(pc[c]) for c in range(len(self.sizes))]
+
+    def as_tensors(self, sample: int):
+        """(kmer_count, coverage) of one sample as torch int16 tensors on the host (the bits are the uint16 values), read
+        back from the device"""
+        import torch
+        ks, cs = self.pointers(sample)
+        out = ([], [])
+        with torch.cuda.device(self.device):
+            torch.cuda.synchronize()
+            for c, (nk, nv) in enumerate(self.sizes):
+                for which, (addr, n) in enumerate(((ks[c], nk), (cs[c], nv))):
+                    t = torch.zeros(n, dtype=torch.int16)
+                    if n:
+                        _memcpy(t.data_ptr(), addr, 2 * n, 2)
+                    out[which].append(t)
+        return out
+
+    def copy_from(self, sample: int, kmer_count, coverage) -> None:
+        """fills one sample's arrays from torch int16 tensors on the device, one D2D copy per array"""
+        import torch
+        ks, cs = self.pointers(sample)
+        with torch.cuda.device(self.device):
+            torch.cuda.synchronize()
+            for c, (nk, nv) in enumerate(self.sizes):
+                for t, addr, n in ((kmer_count[c], ks[c], nk), (coverage[c], cs[c], nv)):
+                    if t.numel() != n or t.dtype != torch.int16 or not t.is_cuda:
+                        raise ValueError(f"sample {sample}, contig {c}: an int16 device tensor of {n} entries is expected")
+                    if n:
+                        _memcpy(addr, t.contiguous().data_ptr(), 2 * n, 3)
+
+
+def marshal_device_samples(index: Sequence[ContigBatch], d_samples):
+    """(pg_sample_counts[n], objects to keep alive) from a SamplerCounts, or from one (kmer_counts, coverages) per sample with
+    one torch int16 device tensor per index contig (what CountPlan.fill_device returns).  Lengths are checked against the
+    index here; where the memory lies is checked by the C ABI."""
+    nc = len(index)
+    if isinstance(d_samples, SamplerCounts):
+        if d_samples.sizes != [(int(b.kmer_off[-1]), int(b.n_variants)) for b in index]:
+            raise ValueError("the SamplerCounts was made over another index")
+        arr = (PgSampleCounts * d_samples.n_samples)()
+        for s in range(d_samples.n_samples):
+            arr[s].kmer_count, arr[s].coverage = d_samples.rows(s)
+        return arr, [d_samples]
+    d_samples = list(d_samples)
+    arr = (PgSampleCounts * len(d_samples))()
+    keep = []
+    for s, (kcs, covs) in enumerate(d_samples):
+        if len(kcs) != nc or len(covs) != nc:
+            raise ValueError(f"sample {s}: {len(kcs)} count arrays and {len(covs)} coverage arrays for {nc} contigs")
+        rows = []
+        for what, arrays, sizes in (("kmer_count", kcs, [int(b.kmer_off[-1]) for b in index]), ("coverage", covs, [b.n_variants for b in index])):
+            ptrs = []
+            for c, (a, n) in enumerate(zip(arrays, sizes)):
+                if isinstance(a, np.ndarray):   # (not a device array: handed on as it is, for the C ABI to refuse)
+                    a = np.ascontiguousarray(a, np.uint16)
+                    size, addr = a.size, a.ctypes.data
+                else:
+                    a = a.contiguous()
+                    size, addr = a.numel(), a.data_ptr()
+                    if a.element_size() != 2:
+                        raise ValueError(f"sample {s}, contig {c}: {what} must be 16-bit")
+                if size != n:
+                    raise ValueError(f"sample {s}, contig {c}: {size} entries of {what}, the index has {n}")
+                keep.append(a)
+                ptrs.append(C.cast(C.c_void_p(addr if n else None), u16p))
+            rows.append((u16p * nc)(*ptrs))
+        arr[s].kmer_count, arr[s].coverage = rows
+        keep += rows
+    return arr, keep
+
+
+def sample_cohort_device(index: Sequence[ContigBatch], d_samples, size: int, table, params=None, add_reference: bool = False,
+                         recombrate: float = 1.26, effective_N=25000.0, allele_penalty: int = 10, device: int = 0, want_paths: bool = True):
+    """pg_sampler_cohort_new_device: sample_cohort with the samples' arrays already on the device — `d_samples` a
+    SamplerCounts, or per sample a pair of lists of torch int16 device tensors.  The counts are read in place; only the
+    coverage (2 bytes per variant) comes back.  Returns what sample_cohort returns."""
+    from . import hmm
+    index = list(index)
+    nc = len(index)
+    arr = (PgContigBatch * nc)(*[b.as_c() for b in index])
+    cs, keep = marshal_device_samples(index, d_samples)
+    ns = len(cs)
+    sampled = best = sp = bp = None
+    if want_paths:
+        sampled = [[np.zeros((size, max(1, b.n_variants)), np.uint32) for b in index] for _ in range(ns)]
+        best = [[np.zeros(max(1, size), np.uint32) for _ in index] for _ in range(ns)]
+        sp = (u32p * (ns * nc))(*[a.ctypes.data_as(u32p) for row in sampled for a in row])
+        bp = (u32p * (ns * nc))(*[a.ctypes.data_as(u32p) for row in best for a in row])
+    params = params or hmm.make_params()
+    err = C.create_string_buffer(1024)
+    h = C.c_void_p()
+    try:
+        import torch
+        if torch.cuda.is_available():
+            torch.cuda.synchronize(device)   # (tensors filled on torch's stream: the sampler's kernels sit on the null stream)
+    except ImportError:
+        pass
+    rc = _hip().pg_sampler_cohort_new_device(device, nc, arr, ns, cs, size, int(bool(add_reference)), float(recombrate), _c_ld(effective_N),
+                                             int(allele_penalty), table.h, C.byref(params), sp, bp, C.byref(h), err, 1024)
     del keep
     if rc:
         raise hmm.PanGenieError(rc, err.value.decode(errors="replace"))
