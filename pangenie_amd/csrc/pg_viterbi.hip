@@ -14,7 +14,7 @@
 // is a symmetric matrix — emission table, update and start are symmetric — so the maxima of column j are those of
 // row j), four compare-selects per state, one 2-byte backpointer store per state.  Nothing is loaded on the critical
 // path: the column records (emission table + allele of every path, written by k_prep) and the transition
-// probabilities are staged 64 columns at a time into LDS, one block ahead.
+// probabilities are staged 32 columns (BC) at a time into LDS, one block ahead.
 //
 // Scaling.  The reference divides every column by its sum.  A uniform scale changes no comparison, so columns are
 // instead multiplied by the exact power of two that brings their maximum into [1/2, 1): no sum, no division, and
@@ -104,8 +104,14 @@ DEVI double wave_max(double x) {
 }
 
 // ---- double-double: value = hi + lo, |lo| <= ulp(hi) / 2 (so the order of two values is the order of (hi, lo))
+// The products are error-free transformations: every operation must round exactly as written.  Device code is compiled
+// with floating-point contraction on, and a contracted `p + e` / `s - p` (p = a.hi * b.hi fused into an FMA) takes the
+// EXACT product where the rounded one is meant: the low part then counts the product's rounding error twice, an error
+// of up to 1e-16 relative that is the same for equal high parts (exact ties and the t0 / t1 / t2 of few paths: never
+// seen) and differs where high parts differ by an ulp (tests/viterbi_cases.py: twins_below_fp64).  Hence contract(off).
 struct dd { double hi, lo; };
 DEVI dd dd_mul(dd a, dd b) {
+#pragma clang fp contract(off)
     const double p = a.hi * b.hi;
     double e = fma(a.hi, b.hi, -p);
     e = fma(a.hi, b.lo, e);
@@ -114,6 +120,7 @@ DEVI dd dd_mul(dd a, dd b) {
     return {s, e - (s - p)};
 }
 DEVI dd dd_mul_d(dd a, double b) {
+#pragma clang fp contract(off)
     const double p = a.hi * b;
     double e = fma(a.hi, b, -p);
     e = fma(a.lo, b, e);

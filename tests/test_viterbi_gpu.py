@@ -101,7 +101,7 @@ def test_viterbi_duplicated_paths_and_equal_positions(orc):
 
 
 def test_viterbi_job_of_mixed_chains(orc):
-    """one resident job over chains of different widths and lengths (block staging across several 64-column blocks,
+    """one resident job over chains of different widths and lengths (block staging across several 32-column blocks,
     a contig without kept columns), genotyping and phasing together; the likelihoods are those of a
     genotyping-only run"""
     shapes = [(1000, 30), (70, 9), (64, 16), (65, 40), (129, 64), (33, 8), (300, 20)]
