@@ -337,6 +337,46 @@ int pg_transition_probs(uint64_t from_pos, uint64_t to_pos, double recombrate,
                         uint32_t nr_paths, int uniform, long double effective_N,
                         int device, double out3[3], char* err, size_t errlen);
 
+/* ------------------------------------------------------------------ *
+ *  Genotype calls formed on the device: GT and GQ per variant, 8 bytes each, instead of 12 bytes per
+ *  genotype bin (pangenie_amd/csrc/pg_calls.hip).  What the host does per variant in
+ *  long double — GenotypingResult::normalize, get_likeliest_genotype, get_genotype_quality (reference
+ *  src/genotypingresult.cpp:118-210) on the keys of the variant's map — is done in integer arithmetic
+ *  that gives the long double's bits; the records hold the same GT and GQ.  The bins stay where they
+ *  are: pg_job_fetch* are not affected.
+ * ------------------------------------------------------------------ */
+typedef struct pg_call {
+    uint16_t allele_1, allele_2; /* allele IDS (not slots) of the likeliest genotype, allele_1 <= allele_2; */
+                                 /* 0xFFFF / 0xFFFF unless flags == PG_CALL_OK                              */
+    uint16_t gq;                 /* get_genotype_quality: 0 .. 192, or 10000                               */
+    uint16_t flags;
+} pg_call;
+#define PG_CALL_OK 0         /* a unique likeliest genotype                                                      */
+#define PG_CALL_NONE 1       /* ./. : not a kept column, no key, or every bin zero                               */
+#define PG_CALL_NOT_UNIQUE 2 /* ./. : another genotype within 1e-10 of the best (genotypingresult.cpp:164-172)   */
+#define PG_CALL_DEFERRED 3   /* not decided on the device: the variant's largest bin lies below 2^-16300, next to */
+                             /* long double's subnormals; form the call on the host from this variant's bins      */
+/* Forms the calls of every chain of a job that has run (one launch per kernel, on the job's stream; blocking).
+ * The record buffer (8 bytes x the variants of all chains) is allocated by the first call, outside the job's
+ * arena, and freed by pg_job_destroy.  PG_ERR_INVALID before pg_job_run, after pg_job_upload_end or a count
+ * plan's fill invalidated the run, and for a job without run_genotyping. */
+int  pg_job_calls(pg_job* job, char* err, size_t errlen);
+/* Chain `chain`'s records, out[V] (after pg_job_calls). */
+int  pg_job_fetch_calls(pg_job* job, uint32_t chain, pg_call* out, char* err, size_t errlen);
+/* The same for all chains, outs[n_chains] (a chain without variants may have NULL): copies queued on the job's
+ * stream, one synchronisation. */
+int  pg_job_fetch_calls_all(pg_job* job, pg_call* const* outs, char* err, size_t errlen);
+/* Device-resident records of chain `chain`: pg_call [n]. */
+int  pg_job_device_calls(pg_job* job, uint32_t chain, void** d_calls, uint64_t* n);
+/* Elapsed milliseconds of the kernels of the LAST pg_job_calls (hipEvents on the job's stream). */
+double pg_job_calls_ms(const pg_job* job);
+/* Unit entry point: the calls of n_variants variants from host arrays laid out as pg_contig_batch /
+ * pg_contig_result lay them out (allele_off [V+1], allele_id / allele_present [sumA], kept [V], lik / lik_exp
+ * [sum A (A + 1) / 2]), through the same kernels; out[V].  PG_ERR_DEVICE without a device. */
+int  pg_calls_from_bins(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id,
+                        const uint8_t* kept, const uint8_t* allele_present, const double* lik,
+                        const int32_t* lik_exp, pg_call* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -220,6 +220,19 @@ def _bind_hip(lib):
     lib.pg_hmm_retract.restype = None
     lib.pg_hmm_coalesce_stats.argtypes = [u64p]
     lib.pg_hmm_coalesce_stats.restype = C.c_int
+    # genotype calls on the device (pangenie_amd/calls.py); records are read as numpy arrays of CALL_DTYPE
+    lib.pg_job_calls.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_calls.restype = C.c_int
+    lib.pg_job_fetch_calls.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_fetch_calls.restype = C.c_int
+    lib.pg_job_fetch_calls_all.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+    lib.pg_job_fetch_calls_all.restype = C.c_int
+    lib.pg_job_device_calls.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), u64p]
+    lib.pg_job_device_calls.restype = C.c_int
+    lib.pg_job_calls_ms.argtypes = [C.c_void_p]
+    lib.pg_job_calls_ms.restype = C.c_double
+    lib.pg_calls_from_bins.argtypes = [C.c_int, C.c_uint32, u32p, u16p, u8p, u8p, f64p, i32p, C.c_void_p]
+    lib.pg_calls_from_bins.restype = C.c_int
     return lib
 
 
@@ -235,6 +248,7 @@ HIP_ABI_SYMBOLS = [
     "pg_comm_unique_id", "pg_comm_init", "pg_comm_init_all", "pg_comm_rank", "pg_comm_world", "pg_comm_destroy",
     "pg_hmm_gather", "pg_hmm_gather_all", "pg_hmm_gather_to_host",
     "pg_hmm_announce", "pg_hmm_retract", "pg_hmm_coalesce_stats", "pg_job_fetch_all", "pg_job_panel_sizes", "pg_job_fetch_panel",
+    "pg_job_calls", "pg_job_fetch_calls", "pg_job_fetch_calls_all", "pg_job_device_calls", "pg_job_calls_ms", "pg_calls_from_bins",
 ]
 
 

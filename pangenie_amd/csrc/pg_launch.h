@@ -40,7 +40,19 @@ enum : uint32_t {
     PG_BINS_Q = 128u,      // k_bins_q: chains on k_sweep_leanx2
 };
 
+// Calls (pg_calls.hip): one descriptor per chain that has variants, in chain order.  Blocks [blk0, next blk0) of k_calls take
+// pgk_calls_block() variants of the chain each; `out` = the chain's 8-byte records (pg_call, include/pangenie_hmm.h).
+struct CallsDesc {
+    uint32_t blk0, V;
+    uint32_t chain, pad;   // index into the DevContig array
+    void* out;
+};
+
 extern "C" {
+// pg_calls.hip: d_wide = uint2 {descriptor, variant} of every variant with more than PG_AMAX alleles (k_calls_wide's list)
+void pgk_launch_calls(const DevContig* d_contigs, const CallsDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide, uint32_t n_wide,
+                      const uint64_t* d_thr_m, const int32_t* d_thr_e, hipStream_t s);
+uint32_t pgk_calls_block(void);
 // pg_kernels.hip
 void pgk_launch_prep(const DevContig* d_contigs, uint32_t n_contigs, uint32_t max_v, uint32_t max_w, uint32_t max_m4, DevTable tab, hipStream_t s);
 void pgk_launch_compact(const DevContig* d_contigs, uint32_t n_contigs, hipStream_t s);

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/pangenie_hmm.h"
+#include "pg_calls.h"
 #include "pg_device.h"
 #include "pg_launch.h"
 
@@ -491,6 +492,16 @@ struct pg_job {
     std::string upload_err;
     std::vector<std::vector<uint16_t>> next_coverage;   // host copies of the pending batch's coverage arrays
     hipEvent_t ev_fill = nullptr;             // orders a count plan's stream against the job's (pgi_job_fill_begin / _end; made by the first fill)
+    // Calls (pg_job_calls, pg_calls.hip): one 8-byte record per variant, chain after chain.  NOT part of the arena: made by
+    // the first pg_job_calls (a job whose user fetches bins never pays for it), freed in pg_job_destroy.
+    unsigned char* d_calls = nullptr;         // the records, then the chain descriptors, then k_calls_wide's list
+    std::vector<uint64_t> calls_first;        // [n_chains + 1] first record of every chain
+    std::vector<CallsDesc> calls_desc;        // host copy of the descriptors (chains with variants)
+    uint32_t calls_blocks = 0, calls_wide = 0;
+    size_t o_calls_desc = 0, o_calls_wide = 0;
+    hipEvent_t ev_calls[2];
+    bool calls_events = false;
+    double calls_ms = 0.0;
 };
 
 extern "C" void pg_job_destroy(pg_job* job) {
@@ -501,11 +512,13 @@ extern "C" void pg_job_destroy(pg_job* job) {
     if (job->ev_late_made) { hipEventDestroy(job->ev_late[0]); hipEventDestroy(job->ev_late[1]); }
     if (job->copy_stream) { hipStreamSynchronize(job->copy_stream); hipStreamDestroy(job->copy_stream); }
     if (job->ev_fill) hipEventDestroy(job->ev_fill);
+    if (job->calls_events) { hipEventDestroy(job->ev_calls[0]); hipEventDestroy(job->ev_calls[1]); }
     if (job->staging) hipHostFree(job->staging);
     if (job->alt_samples) hipFree(job->alt_samples);
     if (job->d_contigs_owned) hipFree(job->d_contigs_owned);
     if (job->stream) hipStreamSynchronize(job->stream);
     if (job->stream2) hipStreamSynchronize(job->stream2);
+    if (job->d_calls) hipFree(job->d_calls);
     if (job->events) {
         for (auto& e : job->ev) hipEventDestroy(e);
         for (auto& e : job->ev_vit) hipEventDestroy(e);
@@ -2599,4 +2612,229 @@ extern "C" int pg_transition_probs(uint64_t from_pos, uint64_t to_pos, double re
     hipFree(d);
     if (he != hipSuccess) { set_err(err, errlen, "transition kernel failed: %s", hipGetErrorString(he)); return PG_ERR_DEVICE; }
     return PG_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+//  Genotype calls on the device (pg_calls.hip): GT and GQ per variant as 8-byte records.
+// ---------------------------------------------------------------------------------------
+namespace {
+
+static_assert(sizeof(pg_call) == 8, "pg_call is the 8-byte record k_calls stores");
+static_assert(PG_CALL_OK == PGX_CALL_OK && PG_CALL_NONE == PGX_CALL_NONE && PG_CALL_NOT_UNIQUE == PGX_CALL_NOT_UNIQUE &&
+              PG_CALL_DEFERRED == PGX_CALL_DEFERRED, "the flags of the public header are the kernels' flags");
+
+// The genotype-quality thresholds, built once from log10l itself (pg_calls.h) and uploaded once per device.
+struct GqTables {
+    std::mutex mu;
+    bool built = false, bad = false;
+    uint64_t m[PG_GQ_STEPS];
+    int32_t e[PG_GQ_STEPS];
+    unsigned char* dev[PG_MAX_DEVICES_HOST] = {nullptr};
+} g_gq;
+
+// (the caller has made `device` current)
+int gq_table_on(int device, const uint64_t** d_m, const int32_t** d_e, char* err, size_t errlen) {
+    if (device < 0 || device >= PG_MAX_DEVICES_HOST) { set_err(err, errlen, "device %d out of range", device); return PG_ERR_INVALID; }
+    std::lock_guard<std::mutex> lock(g_gq.mu);
+    if (!g_gq.built) {
+        g_gq.bad = pgx_build_gq_table(g_gq.m, g_gq.e) != 0;
+        g_gq.built = true;
+    }
+    if (g_gq.bad) { set_err(err, errlen, "the genotype-quality table could not be built: log10l is not monotone at a threshold"); return PG_ERR_INVALID; }
+    constexpr size_t off_e = PG_GQ_STEPS * sizeof(uint64_t);
+    if (!g_gq.dev[device]) {
+        unsigned char* d = nullptr;
+        if (hipMalloc((void**)&d, off_e + PG_GQ_STEPS * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of the GQ table failed"); return PG_ERR_NOMEM; }
+        if (hipMemcpy(d, g_gq.m, off_e, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d + off_e, g_gq.e, PG_GQ_STEPS * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+            hipFree(d);
+            set_err(err, errlen, "upload of the GQ table failed");
+            return PG_ERR_DEVICE;
+        }
+        g_gq.dev[device] = d;
+    }
+    *d_m = (const uint64_t*)g_gq.dev[device];
+    *d_e = (const int32_t*)(g_gq.dev[device] + off_e);
+    return PG_OK;
+}
+
+// descriptors and the list of wide variants of a set of chains: aoff(c) = allele_off of chain c (V + 1 entries), on the host
+template <class AoffOf>
+void plan_calls(uint32_t n_chains, const std::vector<uint32_t>& Vs, AoffOf aoff, std::vector<uint64_t>* first, std::vector<CallsDesc>* desc,
+                std::vector<uint32_t>* wide, uint32_t* n_blocks) {
+    const uint32_t per = pgk_calls_block();
+    first->assign((size_t)n_chains + 1, 0);
+    desc->clear();
+    wide->clear();
+    uint32_t blk = 0;
+    for (uint32_t c = 0; c < n_chains; ++c) {
+        const uint32_t V = Vs[c];
+        (*first)[c + 1] = (*first)[c] + V;
+        if (V == 0) continue;
+        CallsDesc d;
+        memset(&d, 0, sizeof(d));
+        d.blk0 = blk; d.V = V; d.chain = c;
+        const uint32_t* off = aoff(c);
+        for (uint32_t v = 0; v < V; ++v)
+            if (off[v + 1] - off[v] > PG_AMAX) { wide->push_back((uint32_t)desc->size()); wide->push_back(v); }
+        desc->push_back(d);
+        blk += (V + per - 1) / per;
+    }
+    *n_blocks = blk;
+}
+
+}  // namespace
+
+extern "C" int pg_job_calls(pg_job* job, char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    if (!job->params.run_genotyping) { set_err(err, errlen, "the job does not run the genotyping: it has no bins to call from"); return PG_ERR_INVALID; }
+    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(job->device));
+    const uint32_t n = (uint32_t)job->chains.size();
+    const uint64_t* d_tm = nullptr;
+    const int32_t* d_te = nullptr;
+    int rc = gq_table_on(job->device, &d_tm, &d_te, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (!job->calls_events) {
+        HIP_TRY(hipEventCreate(&job->ev_calls[0]));
+        HIP_TRY(hipEventCreate(&job->ev_calls[1]));
+        job->calls_events = true;
+    }
+    if (!job->d_calls) {   // the shapes of a job never change: planned once
+        std::vector<uint32_t> Vs(n), wide;
+        for (uint32_t c = 0; c < n; ++c) Vs[c] = job->index[job->chains[c].index].V;
+        plan_calls(n, Vs, [&](uint32_t c) { return job->index[job->chains[c].index].aoff.data(); }, &job->calls_first, &job->calls_desc, &wide,
+                   &job->calls_blocks);
+        job->calls_wide = (uint32_t)(wide.size() / 2);
+        const size_t rec_bytes = align_up((size_t)job->calls_first[n] * sizeof(pg_call) + 8);
+        job->o_calls_desc = rec_bytes;
+        job->o_calls_wide = job->o_calls_desc + align_up(job->calls_desc.size() * sizeof(CallsDesc) + 8);
+        const size_t total = job->o_calls_wide + align_up(wide.size() * sizeof(uint32_t) + 8);
+        unsigned char* d = nullptr;
+        if (hipMalloc((void**)&d, total) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the calls failed", total); return PG_ERR_NOMEM; }
+        for (CallsDesc& cd : job->calls_desc) cd.out = d + job->calls_first[cd.chain] * sizeof(pg_call);
+        hipError_t he = hipSuccess;
+        if (!job->calls_desc.empty()) he = hipMemcpy(d + job->o_calls_desc, job->calls_desc.data(), job->calls_desc.size() * sizeof(CallsDesc), hipMemcpyHostToDevice);
+        if (he == hipSuccess && !wide.empty()) he = hipMemcpy(d + job->o_calls_wide, wide.data(), wide.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (he != hipSuccess) { hipFree(d); set_err(err, errlen, "upload of the calls plan failed: %s", hipGetErrorString(he)); return PG_ERR_DEVICE; }
+        job->d_calls = d;
+    }
+    hipStream_t s = job->stream;
+    HIP_TRY(hipEventRecord(job->ev_calls[0], s));
+    pgk_launch_calls(job->d_contigs, (const CallsDesc*)(job->d_calls + job->o_calls_desc), (uint32_t)job->calls_desc.size(), job->calls_blocks,
+                     job->d_calls + job->o_calls_wide, job->calls_wide, d_tm, d_te, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(job->ev_calls[1], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, job->ev_calls[0], job->ev_calls[1]));
+    job->calls_ms = ms;
+    return PG_OK;
+}
+
+namespace {
+int calls_ready(pg_job* job, char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
+    if (!job->d_calls) { set_err(err, errlen, "pg_job_calls has not been called"); return PG_ERR_INVALID; }
+    return PG_OK;
+}
+}  // namespace
+
+extern "C" int pg_job_fetch_calls(pg_job* job, uint32_t ci, pg_call* out, char* err, size_t errlen) {
+    int rc = calls_ready(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (ci >= job->chains.size() || !out) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(job->device));
+    const uint64_t V = job->calls_first[ci + 1] - job->calls_first[ci];
+    if (V) HIP_TRY(hipMemcpy(out, job->d_calls + job->calls_first[ci] * sizeof(pg_call), V * sizeof(pg_call), hipMemcpyDeviceToHost));
+    return PG_OK;
+}
+
+extern "C" int pg_job_fetch_calls_all(pg_job* job, pg_call* const* outs, char* err, size_t errlen) {
+    int rc = calls_ready(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (!outs) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(job->device));
+    for (size_t ci = 0; ci < job->chains.size(); ++ci) {
+        const uint64_t V = job->calls_first[ci + 1] - job->calls_first[ci];
+        if (V == 0) continue;
+        if (!outs[ci]) { set_err(err, errlen, "no buffer for chain %zu", ci); return PG_ERR_INVALID; }
+        HIP_TRY(hipMemcpyAsync(outs[ci], job->d_calls + job->calls_first[ci] * sizeof(pg_call), V * sizeof(pg_call), hipMemcpyDeviceToHost, job->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(job->stream));
+    return PG_OK;
+}
+
+extern "C" int pg_job_device_calls(pg_job* job, uint32_t ci, void** d_calls, uint64_t* n) {
+    if (!job || ci >= job->chains.size() || !job->d_calls) return PG_ERR_INVALID;
+    if (d_calls) *d_calls = job->d_calls + job->calls_first[ci] * sizeof(pg_call);
+    if (n) *n = job->calls_first[ci + 1] - job->calls_first[ci];
+    return PG_OK;
+}
+
+extern "C" double pg_job_calls_ms(const pg_job* job) { return job ? job->calls_ms : 0.0; }
+
+// The unit entry point: host arrays in, records out, through the same two kernels.
+extern "C" int pg_calls_from_bins(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id, const uint8_t* kept,
+                                  const uint8_t* allele_present, const double* lik, const int32_t* lik_exp, pg_call* out) {
+    const uint32_t V = n_variants;
+    if (V == 0) return PG_OK;
+    if (!allele_off || !allele_id || !kept || !allele_present || !out || allele_off[0] != 0) return PG_ERR_INVALID;
+    std::vector<uint64_t> goff((size_t)V + 1, 0);
+    for (uint32_t v = 0; v < V; ++v) {
+        if (allele_off[v + 1] <= allele_off[v] || allele_off[v + 1] - allele_off[v] > PG_MAX_ALLELES_PER_VARIANT) return PG_ERR_INVALID;
+        const uint64_t A = allele_off[v + 1] - allele_off[v];
+        goff[v + 1] = goff[v] + A * (A + 1) / 2;
+    }
+    const uint64_t n_lik = goff[V], sumA = allele_off[V];
+    if (n_lik && (!lik || !lik_exp)) return PG_ERR_INVALID;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); return PG_ERR_DEVICE; }
+    if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return PG_ERR_DEVICE;
+    const uint64_t* d_tm = nullptr;
+    const int32_t* d_te = nullptr;
+    int rc = gq_table_on(device, &d_tm, &d_te, nullptr, 0);
+    if (rc != PG_OK) return rc;
+    std::vector<uint64_t> first;
+    std::vector<CallsDesc> desc;
+    std::vector<uint32_t> wide, Vs(1, V);
+    uint32_t n_blocks = 0;
+    plan_calls(1, Vs, [&](uint32_t) { return allele_off; }, &first, &desc, &wide, &n_blocks);
+    // one device buffer: every array at a 256-byte boundary
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += align_up(bytes + 8); return at; };
+    const size_t o_contig = take(sizeof(DevContig)), o_desc = take(sizeof(CallsDesc)), o_wide = take(wide.size() * 4), o_aoff = take(((size_t)V + 1) * 4),
+                 o_aid = take(sumA * 2), o_kept = take(V), o_pres = take(sumA), o_goff = take(((size_t)V + 1) * 8), o_lik = take(n_lik * 8),
+                 o_exp = take(n_lik * 4), o_out = take((size_t)V * sizeof(pg_call));
+    unsigned char* d = nullptr;
+    if (hipMalloc((void**)&d, o) != hipSuccess) { (void)hipGetLastError(); return PG_ERR_NOMEM; }
+    DevContig dc;
+    memset(&dc, 0, sizeof(dc));
+    dc.V = V;
+    dc.allele_off = (const uint32_t*)(d + o_aoff);
+    dc.allele_id = (const uint16_t*)(d + o_aid);
+    dc.kept = d + o_kept;
+    dc.allele_present = d + o_pres;
+    dc.geno_off = (const uint64_t*)(d + o_goff);
+    dc.lik = (double*)(d + o_lik);
+    dc.lik_exp = (int32_t*)(d + o_exp);
+    desc[0].out = d + o_out;
+    bool ok = hipMemcpy(d + o_contig, &dc, sizeof(dc), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + o_desc, desc.data(), sizeof(CallsDesc), hipMemcpyHostToDevice) == hipSuccess &&
+              (wide.empty() || hipMemcpy(d + o_wide, wide.data(), wide.size() * 4, hipMemcpyHostToDevice) == hipSuccess) &&
+              hipMemcpy(d + o_aoff, allele_off, ((size_t)V + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + o_aid, allele_id, sumA * 2, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + o_kept, kept, V, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + o_pres, allele_present, sumA, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + o_goff, goff.data(), ((size_t)V + 1) * 8, hipMemcpyHostToDevice) == hipSuccess &&
+              (n_lik == 0 || (hipMemcpy(d + o_lik, lik, n_lik * 8, hipMemcpyHostToDevice) == hipSuccess &&
+                              hipMemcpy(d + o_exp, lik_exp, n_lik * 4, hipMemcpyHostToDevice) == hipSuccess));
+    if (ok) {
+        pgk_launch_calls((const DevContig*)(d + o_contig), (const CallsDesc*)(d + o_desc), 1, n_blocks, d + o_wide, (uint32_t)(wide.size() / 2), d_tm, d_te, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
+             hipMemcpy(out, d + o_out, (size_t)V * sizeof(pg_call), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    hipFree(d);
+    return ok ? PG_OK : PG_ERR_DEVICE;
 }

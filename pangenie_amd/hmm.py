@@ -377,6 +377,17 @@ class Job:
             r.run_genotyping = bool(self.params.run_genotyping)
         return res
 
+    def calls(self, contig: Optional[int] = None):
+        """pg_job_calls + pg_job_fetch_calls[_all]: GT and GQ per variant formed on the device (pangenie_amd/calls.py,
+        DESIGN.md 4e) — 8 bytes per variant cross PCIe instead of every bin.  Returns one record array (calls.CALL_DTYPE)
+        per chain, or chain `contig`'s alone."""
+        from . import calls as _calls
+        return _calls.job_calls(self, contig)
+
+    def calls_ms(self) -> float:
+        """elapsed ms of the kernels of the last calls()"""
+        return float(self._lib.pg_job_calls_ms(self.h))
+
     def viterbi_ms(self) -> float:
         """elapsed ms of the Viterbi kernels (run_phasing) of the last run"""
         return float(self._lib.pg_job_viterbi_ms(self.h))

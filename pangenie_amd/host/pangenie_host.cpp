@@ -742,6 +742,94 @@ std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohor
     return out;
 }
 
+// ------------------------------------------------------------------ cohort job, calls instead of likelihoods
+std::vector<std::map<std::string, std::vector<GenotypeCall>>> genotype_cohort_calls(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::vector<SampleCounts>& samples,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device) {
+    const size_t C = chromosomes.size(), S = samples.size();
+    std::vector<std::map<std::string, std::vector<GenotypeCall>>> out(S);
+    if (C == 0 || S == 0) return out;
+    // (the job is made exactly as genotype_cohort makes it)
+    std::vector<std::string> names;
+    std::vector<FlatContig> flat(C);
+    std::vector<std::vector<uint64_t>> goff(C);
+    std::vector<pg_contig_batch> index(C);
+    size_t c = 0;
+    for (auto& kv : chromosomes) {
+        names.push_back(kv.first);
+        flatten(&kv.second, nullptr, flat[c]);
+        goff[c].assign(flat[c].variant_pos.size() + 1, 0);
+        pg_hmm_geno_offsets(&flat[c].batch, goff[c].data());
+        index[c] = flat[c].batch;
+        c += 1;
+    }
+    static const uint16_t none = 0;
+    std::vector<std::vector<const uint16_t*>> count_rows(S, std::vector<const uint16_t*>(C)), cov_rows(S, std::vector<const uint16_t*>(C));
+    std::vector<pg_sample_counts> rows(S);
+    for (size_t s = 0; s < S; ++s) {
+        for (c = 0; c < C; ++c) {
+            const auto k = samples[s].kmer_count.find(names[c]), v = samples[s].coverage.find(names[c]);
+            if (k == samples[s].kmer_count.end() || v == samples[s].coverage.end() || k->second.size() != flat[c].kmer_count.size() ||
+                v->second.size() != flat[c].variant_pos.size())
+                fail("genotype_cohort_calls: sample " + std::to_string(s) + " does not fit the index on " + names[c]);
+            count_rows[s][c] = k->second.empty() ? &none : k->second.data();
+            cov_rows[s][c] = v->second.empty() ? &none : v->second.data();
+        }
+        rows[s].kmer_count = count_rows[s].data();
+        rows[s].coverage = cov_rows[s].data();
+    }
+    pg_hmm_params prm{};
+    prm.effective_N = effective_N; prm.recombrate = recombrate; prm.uniform = uniform ? 1 : 0; prm.run_genotyping = 1;
+    char err[512] = {0};
+    pg_job* job = nullptr;
+    int rc = pg_cohort_new(device, (uint32_t)C, index.data(), (uint32_t)S, rows.data(), probabilities->handle(), &prm, &job, err, sizeof(err));
+    if (rc == PG_OK) rc = pg_job_run(job, nullptr, err, sizeof(err));
+    if (rc == PG_OK) rc = pg_job_calls(job, err, sizeof(err));
+    if (rc != PG_OK) { if (job) pg_job_destroy(job); check_rc(rc, err); }
+    // all records with one synchronisation
+    std::vector<std::vector<pg_call>> recs(S * C);
+    std::vector<pg_call*> ptrs(S * C, nullptr);
+    for (size_t i = 0; i < S * C; ++i) {
+        recs[i].resize(flat[i % C].variant_pos.size());
+        ptrs[i] = recs[i].empty() ? nullptr : recs[i].data();
+    }
+    rc = pg_job_fetch_calls_all(job, ptrs.data(), err, sizeof(err));
+    for (size_t s = 0; s < S && rc == PG_OK; ++s)
+        for (c = 0; c < C && rc == PG_OK; ++c) {
+            const std::vector<pg_call>& r = recs[s * C + c];   // chain id = sample * n_contigs + contig
+            std::vector<GenotypeCall>& calls = out[s][names[c]];
+            calls.resize(r.size());
+            bool any_deferred = false;
+            for (size_t v = 0; v < r.size(); ++v) {
+                if (r[v].flags == PG_CALL_OK) { calls[v].allele_1 = r[v].allele_1; calls[v].allele_2 = r[v].allele_2; calls[v].quality = r[v].gq; }
+                else if (r[v].flags == PG_CALL_DEFERRED) any_deferred = true;
+            }
+            if (!any_deferred) continue;
+            // the deferred variants of this chain on the host, each from its own bins, through GenotypingResult
+            const uint64_t n = goff[c].back();
+            std::vector<double> lik(n ? n : 1);
+            std::vector<int32_t> lexp(n ? n : 1);
+            pg_contig_result res{};
+            res.lik = lik.data(); res.lik_exp = lexp.data();
+            rc = pg_job_fetch(job, (uint32_t)(s * C + c), &res, err, sizeof(err));
+            if (rc != PG_OK) break;
+            std::vector<GenotypingResult> full = results_of_chain(flat[c], cov_rows[s][c], goff[c], lik.data(), lexp.data());
+            for (size_t v = 0; v < r.size(); ++v) {
+                if (r[v].flags != PG_CALL_DEFERRED) continue;
+                full[v].normalize();
+                const std::pair<int, int> g = full[v].get_likeliest_genotype();
+                calls[v].deferred = true;
+                if (g.first >= 0 && g.second >= 0) {
+                    calls[v].allele_1 = g.first; calls[v].allele_2 = g.second;
+                    calls[v].quality = full[v].get_genotype_quality((unsigned short)g.first, (unsigned short)g.second);
+                }
+            }
+        }
+    pg_job_destroy(job);
+    check_rc(rc, err);
+    return out;
+}
+
 // ------------------------------------------------------------------ cohort job fed by the device counter
 std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohort_reads(
     UniqueKmersMap& index, const std::string& prefix, const std::vector<std::string>& readfiles, const std::vector<size_t>& kmer_coverages,

@@ -333,6 +333,24 @@ std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohor
     std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::vector<SampleCounts>& samples,
     ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0);
 
+/** GT and GQ of one variant as the device forms them (C ABI pg_job_calls): the allele ids of the likeliest
+ *  genotype of the NORMALISED result (GenotypingResult::normalize, get_likeliest_genotype) and its get_genotype_quality;
+ *  -1 / -1 and quality 0 where get_likeliest_genotype answers -1 / -1.  `deferred`: the device left this variant to the
+ *  host (its largest likelihood lies next to long double's subnormals) and the call was formed here, from that variant's
+ *  bins, through GenotypingResult — the caller never has to look at it. */
+struct GenotypeCall {
+    int allele_1 = -1, allele_2 = -1;
+    size_t quality = 0;
+    bool deferred = false;
+};
+
+/** genotype_cohort for a caller who wants calls, not likelihoods: same arguments, same job, but what comes back from the
+ *  device is one 8-byte record per variant instead of every genotype bin.  Per sample and chromosome, element v is what
+ *  normalize() / get_likeliest_genotype() / get_genotype_quality() give on element v of genotype_cohort's result. */
+std::vector<std::map<std::string, std::vector<GenotypeCall>>> genotype_cohort_calls(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::vector<SampleCounts>& samples,
+    ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0);
+
 // ------------------------------------------------------------------ haplotype sampling (include/pangenie_sampler.h)
 /** reference src/haplotypesampler.hpp:16-59 */
 struct SampledPaths {
