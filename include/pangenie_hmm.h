@@ -215,6 +215,14 @@ double pg_job_index_ms(const pg_job* job);
  * sweep mode, the kernels of the preparation / phase 1 / phase 2 / bins).  Writes at most `len` bytes incl. the terminator,
  * returns the length the full text needs.  For logs and DESIGN.md's table; the library takes every decision itself. */
 size_t pg_job_plan(const pg_job* job, char* out, size_t len);
+/* Chunked jobs with lean chains (64 paths, biallelic) that leave compute units idle: phase 1 stores every 64th column, counted
+ * from the phase boundary, and k_refill_lean forms the columns between two stored ones before k_post reads them (pg_job_plan
+ * names it).  The arithmetic both sides use, for tests: segment `j` (0 .. chunk_cols / 64 - 1) of `role` (0 forward, 1 backward)
+ * that chunk `chunk` of phase 2 reads — returns 1 and out = {column it resumes from, first, last column it stores}, 0 when the
+ * chain of n_columns has no such segment, -1 for arguments outside the scheme (chunk_cols no multiple of 64).
+ * pg_sparse_stored_by_chain: 1 if the chain itself stores `column` (its role's phase-1 half is column < n_columns / 2 for role 0). */
+int pg_sparse_segment(uint32_t n_columns, uint32_t chunk_cols, uint32_t chunk, uint32_t role, uint32_t j, uint32_t out[3]);
+int pg_sparse_stored_by_chain(uint32_t n_columns, uint32_t role, uint32_t column);
 /* Elapsed milliseconds of the Viterbi kernels (run_phasing) of the LAST pg_job_run, hipEvents on the launch stream. */
 double pg_job_viterbi_ms(const pg_job* job);
 void pg_job_destroy(pg_job* job);

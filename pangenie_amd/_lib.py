@@ -145,6 +145,10 @@ def _bind_hip(lib):
     lib.pg_job_index_ms.restype = C.c_double
     lib.pg_job_plan.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     lib.pg_job_plan.restype = C.c_size_t
+    lib.pg_sparse_segment.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p]
+    lib.pg_sparse_segment.restype = C.c_int
+    lib.pg_sparse_stored_by_chain.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    lib.pg_sparse_stored_by_chain.restype = C.c_int
     lib.pg_job_kernel_ms.argtypes = [C.c_void_p, f64p]
     lib.pg_job_kernel_ms.restype = C.c_int
     lib.pg_job_kernel_name.argtypes = [C.c_int]
@@ -249,6 +253,7 @@ HIP_ABI_SYMBOLS = [
     "pg_hmm_gather", "pg_hmm_gather_all", "pg_hmm_gather_to_host",
     "pg_hmm_announce", "pg_hmm_retract", "pg_hmm_coalesce_stats", "pg_job_fetch_all", "pg_job_panel_sizes", "pg_job_fetch_panel",
     "pg_job_calls", "pg_job_fetch_calls", "pg_job_fetch_calls_all", "pg_job_device_calls", "pg_job_calls_ms", "pg_calls_from_bins",
+    "pg_sparse_segment", "pg_sparse_stored_by_chain",
 ]
 
 

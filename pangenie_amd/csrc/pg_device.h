@@ -275,7 +275,10 @@ struct DevContig {
     uint32_t* ix_err;          // per index contig: error bits of k_index_scan (PG_DEVERR_*)
     const uint32_t* ix_big;    // per index contig: its variants with more than 32 alleles (the wave-per-object index kernels' list)
     uint32_t n_ix_big;
-    uint32_t pad2;
+    // 1 (lean chains of chunked jobs that leave CUs idle, chunk_cols a multiple of PG_LEAN_SPARSE): phase 1 stores only every
+    // PG_LEAN_SPARSE-th column, counted from the phase boundary (pg_sparse_*, below); k_refill_lean re-runs the columns between two
+    // stored ones on the idle CUs, chunk by chunk, before k_post reads them (PG_KERNELS=nosparse: every column by the chain)
+    uint32_t sparse;
     // the WIDE columns of the chain (smallx == 2, index with objects of more than PG_AMAX alleles): k_records appends every wide
     // column it meets, k_bins_wide walks the list — one wave per entry instead of a scan of all columns for the rare one
     uint32_t* wcols;           // [wide candidates of the index contig]
@@ -302,6 +305,39 @@ struct DevContig {
     double*   lik;             // [n_lik] mantissa in [0.5,1) or 0
     int32_t*  lik_exp;         // [n_lik] exponent: L = lik * 2^lik_exp
 };
+
+// ------------------------------------------------------------------------------------------------------------------
+//  Sparse phase 1 of lean chains (DevContig::sparse): where the stored columns (checkpoints) lie and which columns a refill
+//  segment re-runs.  Host and device take both from here.  With mid = C / 2 the forward role walks columns 0 .. mid-1 and
+//  stores mid-1 - m S, the backward role walks C-1 .. mid and stores mid + m S (m = 0, 1, ...): the column phase 2 resumes
+//  from is always stored, and with chunk_cols a multiple of S the partner columns of a chunk are whole segments.  The columns
+//  in front of a role's first checkpoint (from column 0 / C-1, where the recursion is initialised) are stored by the chain.
+//  Segment m >= 1 of a role resumes from checkpoint m and runs, in the role's own direction, the S - 1 columns up to
+//  checkpoint m - 1.  Chunk i of phase 2 reads segments i q + 1 .. (i + 1) q of either role, q = chunk_cols / S.
+// ------------------------------------------------------------------------------------------------------------------
+#define PG_LEAN_SPARSE 64u
+#ifdef __HIP__   // (the HIP translation units; pg_shim.cpp is host C++)
+#define PG_HD __attribute__((host)) __attribute__((device))
+#else
+#define PG_HD
+#endif
+// segments a role has: checkpoints m = 1 .. this many exist
+PG_HD inline uint32_t pg_sparse_segments(uint32_t C, uint32_t role) {
+    const uint32_t mid = C / 2u;
+    if (role == 0u) return mid ? (mid - 1u) / PG_LEAN_SPARSE : 0u;
+    return C ? (C - 1u - mid) / PG_LEAN_SPARSE : 0u;
+}
+// column of checkpoint m (m <= pg_sparse_segments)
+PG_HD inline uint32_t pg_sparse_checkpoint(uint32_t C, uint32_t role, uint32_t m) {
+    const uint32_t mid = C / 2u;
+    return role == 0u ? mid - 1u - m * PG_LEAN_SPARSE : mid + m * PG_LEAN_SPARSE;
+}
+// does the chain itself store column c of its phase-1 half (a checkpoint, or a column of the leading piece)?
+PG_HD inline bool pg_sparse_stored(uint32_t C, uint32_t role, uint32_t c) {
+    const uint32_t mid = C / 2u;
+    if (role == 0u) return c >= mid || (mid - 1u - c) % PG_LEAN_SPARSE == 0u || c < (mid - 1u) % PG_LEAN_SPARSE;
+    return c < mid || (c - mid) % PG_LEAN_SPARSE == 0u || c > mid + pg_sparse_segments(C, 1u) * PG_LEAN_SPARSE;
+}
 
 // ------------------------------------------------------------------------------------------------------------------
 //  The seam between the count plan (pg_kmers.hip owns the counter and the plan) and a cohort job (pg_shim.cpp owns pg_job):

@@ -3167,8 +3167,12 @@ DEVI double lean_total(const LeanShared<R>& sh, uint32_t pb) {   // (kLeanPreTot
     return (a.x + a.y) + (b.x + b.y);
 }
 
-template <int PHASE, int R, bool TRI>
+// SPARSE (PHASE 1 of DevContig::sparse chains): only the checkpoints of pg_device.h's pg_sparse_* are stored — the step is compiled
+// twice, with and without its column stores.  PHASE 5: a refill segment (k_refill_lean) — `chunk` = the checkpoint column it resumes
+// from; it stores the PG_LEAN_SPARSE - 1 columns behind it and none of the per-column scalars, which are the chain's.
+template <int PHASE, int R, bool TRI, bool SPARSE = false>
 DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint32_t chunk) {
+    static_assert(!SPARSE || (PHASE == 1 && !TRI), "sparse stores: phase 1 of full-column lean chains");
     constexpr int HP = 64;
     constexpr uint32_t RMASK = (1u << R) - 1u;
     const uint32_t mid = C / 2, K = dc.chunk_cols;
@@ -3179,6 +3183,7 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         lo = (uint32_t)l;
         hi = C - lo > K ? lo + K : C;
     }
+    if constexpr (PHASE == 5) { lo = chunk + 1u; hi = chunk + PG_LEAN_SPARSE; }
     if (lo >= hi) return;
     const uint32_t first = lo == 0 ? 1u : lo;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -3215,6 +3220,13 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
     // fixed per thread (row pair i0 + 2q, column = lane).
     double tfa[TRI ? R / 2 : 1], tfb[TRI ? R / 2 : 1];
     uint32_t tskip = 0, tunit[TRI ? R / 2 : 1];
+    // PHASE 5: a refilled column is read by k_post alone, which takes the upper triangle (post_lean64: lane j reads the row pairs
+    // up to its own) — the 128-byte lines wholly below the diagonal are not written: a little over half the bytes of a column
+    uint32_t rskip = 0;
+    if constexpr (PHASE == 5) {
+#pragma unroll
+        for (int q = 0; q < R / 2; ++q) rskip |= (lane < ((i0 + 2u * (uint32_t)q) & ~7u) ? 1u : 0u) << q;
+    }
     if constexpr (TRI) {
 #pragma unroll
         for (int q = 0; q < R / 2; ++q) {
@@ -3229,6 +3241,8 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
     auto put_pair = [&](gdouble2* dst, int q, double a, double b) __attribute__((always_inline)) {
         if constexpr (TRI) {
             if (!((tskip >> q) & 1u)) lean_store((dst - toff) + tunit[q], v2f64{a * tfa[q], b * tfb[q]});
+        } else if constexpr (PHASE == 5) {
+            if (!((rskip >> q) & 1u)) lean_store(dst + (size_t)q * HP, v2f64{a, b});
         } else {
             lean_store(dst + (size_t)q * HP, v2f64{a, b});
         }
@@ -3239,13 +3253,15 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         for (int k = 0; k < R; k += 2) put_pair(dst, k >> 1, v[k], v[k + 1]);
     };
     auto flag_uniform = [&](uint32_t cprev) {
-        if (cprev >= lo) {
+        bool stored = cprev >= lo;
+        if constexpr (SPARSE) stored = pg_sparse_stored(C, 0u, cprev);   // (the refill segment forms the others from the same arithmetic)
+        if (stored) {
             double xu[R];
 #pragma unroll
             for (int k = 0; k < R; ++k) xu[k] = unif;
             store_col(cprev, xu);
         }
-        if (wave == 0) fallback[cprev] = 1;
+        if constexpr (PHASE != 5) if (wave == 0) fallback[cprev] = 1;
     };
 
     ColScalars fsc{&sh.scal[0][0]};
@@ -3273,6 +3289,11 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
             if (!fallback[lo - 1]) {
 #pragma unroll
                 for (int k = 0; k < R; ++k) { const double e = sel_by_bit(rb, k, eA, eB); part = fma(e, x[k], part); x[k] *= e; }
+            } else if constexpr (PHASE == 5) {
+                // (the chain went on from this checkpoint in registers: every state 0, the uniform column entering through the first
+                //  step's zero test — the same instructions here give the same bits; a chunk launch resumes from the STORED uniform column)
+#pragma unroll
+                for (int k = 0; k < R; ++k) x[k] = 0.0;
             } else {
 #pragma unroll
                 for (int k = 0; k < R; ++k) part += x[k];
@@ -3294,7 +3315,8 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
     // variables and the two emission arrays in swapped roles, so nothing is ever moved.
     LeanTimeline tl;
     tl.init();
-    auto step = [&](uint32_t t, const FRec& cur, FRec& nxt) __attribute__((always_inline)) {
+    auto step = [&](auto store_c, uint32_t t, const FRec& cur, FRec& nxt) __attribute__((always_inline)) {
+        constexpr bool STORE = decltype(store_c)::value;   // (false: a column between two checkpoints of a sparse phase 1)
         const uint32_t n = t - first;                 // step number: reads the record with rel = n + 2
         tl.template mark<0>(0.0);                     // (behind the barrier of the step before)
         nxt = read_frec(sh, n + 2u);
@@ -3358,7 +3380,7 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
             // (the fence keeps every pair's store where it is: eight 1 KB stores issued back to back stall the wave
             // on the memory pipeline's queue — 787 instead of ~650 ns per column)
             if constexpr (k & 1) {
-                if (!(kLeanExp & 1)) put_pair(dst, k >> 1, pprev, pk);
+                if constexpr (STORE) { if (!(kLeanExp & 1)) put_pair(dst, k >> 1, pprev, pk); }
                 const v2f64 t2 = (kLeanExp & 2) ? v2f64{0.5, 0.5} : lean_pair<(k >> 1)>(lp);   // e_{t+1} of this row pair
                 ec[k - 1] = t2.x; ec[k] = t2.y;
                 __builtin_amdgcn_sched_barrier(0);
@@ -3366,7 +3388,7 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         });
         tl.template mark<6>(part);                    // the other seven row pairs: states, stores, next emissions
         lean_put_sums<R>(sh, t & 1u, wave, lane, part);
-        if (wave == 0) {  // (scalar branch)
+        if constexpr (PHASE != 5) if (wave == 0) {  // (scalar branch)
             fsc.put(lane, t, m);
             if ((t & 63u) == 63u) fsc.flush(fscale, lane, t);
         }
@@ -3376,6 +3398,8 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         tl.template fold<8>();
     };
     FRec ra = read_frec(sh, 1), rb2;
+    constexpr std::true_type kStore{};
+    constexpr std::false_type kNoStore{};
     // every load of the prologue has landed before the loop is entered: a register still "waiting for a load" at the loop
     // head would make the compiler put a vmcnt wait — a cap on the stores in flight — into every step
     __builtin_amdgcn_s_waitcnt(0x0F70);
@@ -3389,10 +3413,10 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         uint32_t q = 0, cend = hi - lo > K ? lo + K : hi;
         for (;;) {
             for (; t + 1 < cend; t += 2) {
-                step(t, ra, rb2);
-                step(t + 1, rb2, ra);
+                step(kStore, t, ra, rb2);
+                step(kStore, t + 1, rb2, ra);
             }
-            if (t < cend) { step(t, ra, rb2); ++t; }   // (the last chunk only)
+            if (t < cend) { step(kStore, t, ra, rb2); ++t; }   // (the last chunk only)
             // what a chunk launch of PHASE 3 does when it ends: the scalars still parked, the zero test of the chunk's last column
             if (wave == 0 && fsc.valid) fsc.flush(fscale, lane, cend - 1);
             {
@@ -3409,12 +3433,32 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         }
         return;
     }
-    for (; t + 1 < hi; t += 2) {
-        step(t, ra, rb2);
-        step(t + 1, rb2, ra);
+    if constexpr (SPARSE) {
+        // the leading piece up to the first checkpoint as ever; from there PG_LEAN_SPARSE - 1 columns that only stay in registers and
+        // one that is stored (an odd leading piece: the two record variables change places once)
+        const uint32_t ck0 = (hi - 1u) % PG_LEAN_SPARSE;
+        for (; t + 1 <= ck0; t += 2) {
+            step(kStore, t, ra, rb2);
+            step(kStore, t + 1, rb2, ra);
+        }
+        if (t <= ck0) { step(kStore, t, ra, rb2); ra = rb2; ++t; }
+        while (t < hi) {
+            for (uint32_t g = 0; g + 1u < PG_LEAN_SPARSE / 2u; ++g, t += 2) {
+                step(kNoStore, t, ra, rb2);
+                step(kNoStore, t + 1, rb2, ra);
+            }
+            step(kNoStore, t, ra, rb2);
+            step(kStore, t + 1, rb2, ra);
+            t += 2;
+        }
+    } else {
+        for (; t + 1 < hi; t += 2) {
+            step(kStore, t, ra, rb2);
+            step(kStore, t + 1, rb2, ra);
+        }
+        if (t < hi) step(kStore, t, ra, rb2);
     }
-    if (t < hi) step(t, ra, rb2);
-    if (wave == 0 && fsc.valid) fsc.flush(fscale, lane, hi - 1);
+    if constexpr (PHASE != 5) if (wave == 0 && fsc.valid) fsc.flush(fscale, lane, hi - 1);
     if (kLeanTimeline && tid == 0) tl.write(dc.prof + 32);
     {   // the last column of this phase may itself have summed to zero
         const uint32_t pb = (hi - 1) & 1u;
@@ -3423,8 +3467,9 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
     }
 }
 
-template <int PHASE, int R, bool TRI>
+template <int PHASE, int R, bool TRI, bool SPARSE = false>   // (SPARSE, PHASE 5: see lean_forward)
 DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint32_t chunk) {
+    static_assert(!SPARSE || (PHASE == 1 && !TRI), "sparse stores: phase 1 of full-column lean chains");
     constexpr int HP = 64;
     constexpr uint32_t RMASK = (1u << R) - 1u;
     const int64_t mid = C / 2, K = dc.chunk_cols;
@@ -3435,6 +3480,7 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         if (top < 0) return;
         bot = top - K + 1 > 0 ? top - K + 1 : 0;
     }
+    if constexpr (PHASE == 5) { top = (int64_t)chunk - 1; bot = (int64_t)chunk - (int64_t)(PG_LEAN_SPARSE - 1u); }
     if (top < bot) return;
     const int64_t t0 = PHASE == 1 ? top - 1 : top;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -3471,6 +3517,13 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
     };
     double tfa[TRI ? R / 2 : 1], tfb[TRI ? R / 2 : 1];  // see lean_forward
     uint32_t tskip = 0, tunit[TRI ? R / 2 : 1];
+    // PHASE 5: a refilled column is read by k_post alone, which takes the upper triangle (post_lean64: lane j reads the row pairs
+    // up to its own) — the 128-byte lines wholly below the diagonal are not written: a little over half the bytes of a column
+    uint32_t rskip = 0;
+    if constexpr (PHASE == 5) {
+#pragma unroll
+        for (int q = 0; q < R / 2; ++q) rskip |= (lane < ((i0 + 2u * (uint32_t)q) & ~7u) ? 1u : 0u) << q;
+    }
     if constexpr (TRI) {
 #pragma unroll
         for (int q = 0; q < R / 2; ++q) {
@@ -3485,6 +3538,8 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
     auto put_pair = [&](gdouble2* dst, int q, double a, double b) __attribute__((always_inline)) {
         if constexpr (TRI) {
             if (!((tskip >> q) & 1u)) lean_store((dst - toff) + tunit[q], v2f64{a * tfa[q], b * tfb[q]});
+        } else if constexpr (PHASE == 5) {
+            if (!((rskip >> q) & 1u)) lean_store(dst + (size_t)q * HP, v2f64{a, b});
         } else {
             lean_store(dst + (size_t)q * HP, v2f64{a, b});
         }
@@ -3538,7 +3593,8 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
     // (constants of the next step); `ec` = emissions of column t (this step's w), `en` takes those of column t-1.
     LeanTimeline tl;
     tl.init();
-    auto step = [&](int64_t t, const FRec& cur, FRec& nxt) __attribute__((always_inline)) {
+    auto step = [&](auto store_c, int64_t t, const FRec& cur, FRec& nxt) __attribute__((always_inline)) {
+        constexpr bool STORE = decltype(store_c)::value;
         const uint32_t n = (uint32_t)(t0 - t);        // step number: column t is the record with rel = n + 1
         tl.template mark<0>(0.0);
         if (((n + 4u) % PG_LEAN_BLOCK) == 0u) {
@@ -3551,7 +3607,7 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         int es = exponent_of(Sy) - PG_BIAS_B;
         es = es < -900 ? -900 : es;
         const double m = ldexp(Sy, -es - PG_BIAS_B);
-        if (wave == 1) { asm volatile("" ::: "memory"); bsc.put(lane, (uint64_t)t, m); }   // (the per-column scalars are collected by two DIFFERENT waves: the waves meet
+        if constexpr (PHASE != 5) if (wave == 1) { asm volatile("" ::: "memory"); bsc.put(lane, (uint64_t)t, m); }   // (the per-column scalars are collected by two DIFFERENT waves: the waves meet
                                                         // at a barrier every column, one wave's extra instructions are everybody's wait)
         double k0 = ldexp(cur.c0, -es), k1 = ldexp(cur.c1, -es), k2 = ldexp(cur.c2, -es), kap = ldexp(cur.kappa, -es);
         pin_here(k0); pin_here(k1); pin_here(k2); pin_here(kap);   // (in front of the barrier, not behind it)
@@ -3600,7 +3656,7 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
             pin_here(w[k]);
             if constexpr (k == 1) tl.template mark<6>(w[1]);    // u_j, the first row pair's states
             if constexpr (k & 1) {
-                if (!(kLeanExp & 1)) put_pair(dst, k >> 1, yprev, yk);
+                if constexpr (STORE) { if (!(kLeanExp & 1)) put_pair(dst, k >> 1, yprev, yk); }
                 const v2f64 t2 = (kLeanExp & 2) ? v2f64{0.5, 0.5} : lean_pair<(k >> 1)>(lp);   // e_{t-1} of this row pair
                 ec[k - 1] = t2.x; ec[k] = t2.y;
                 __builtin_amdgcn_sched_barrier(0);
@@ -3618,15 +3674,19 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         }
         tl.template mark<7>(part);                    // the other seven row pairs: states, stores, next emissions
         lean_put_sums<R>(sh, (uint32_t)(t - 1) & 1u, wave, lane, part);
-        if (wave == 2) { asm volatile("" ::: "memory"); bsm.put(lane, (uint64_t)t, Snew); }   // (a branch, not predication: three of the four waves skip it)
-        if (((uint64_t)t & 63u) == 0u) {
-            if (wave == 1) bsc.flush(bscale, lane, (uint64_t)t);
-            if (wave == 2) bsm.flush(bsum, lane, (uint64_t)t);
+        if constexpr (PHASE != 5) {
+            if (wave == 2) { asm volatile("" ::: "memory"); bsm.put(lane, (uint64_t)t, Snew); }   // (a branch, not predication: three of the four waves skip it)
+            if (((uint64_t)t & 63u) == 0u) {
+                if (wave == 1) bsc.flush(bscale, lane, (uint64_t)t);
+                if (wave == 2) bsm.flush(bsum, lane, (uint64_t)t);
+            }
         }
         tl.template mark<8>(0.0);                     // partial sum parked, per-column scalars
         tl.template fold<8>();
     };
     FRec rb2;
+    constexpr std::true_type kStore{};
+    constexpr std::false_type kNoStore{};
     int64_t t = t0;
     __builtin_amdgcn_s_waitcnt(0x0F70);   // (see lean_forward: no load of the prologue is still in flight inside the loop)
     if constexpr (PHASE == 4) {
@@ -3635,10 +3695,10 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         uint32_t q = 0;
         for (;;) {
             for (; t - 1 >= cbot; t -= 2) {
-                step(t, cur, rb2);
-                step(t - 1, rb2, cur);
+                step(kStore, t, cur, rb2);
+                step(kStore, t - 1, rb2, cur);
             }
-            if (t >= cbot) { step(t, cur, rb2); --t; }   // (the last chunk only: K is even)
+            if (t >= cbot) { step(kStore, t, cur, rb2); --t; }   // (the last chunk only: K is even)
             if (wave == 1 && bsc.valid) bsc.flush(bscale, lane, (uint64_t)cbot);
             if (wave == 2 && bsm.valid) bsm.flush(bsum, lane, (uint64_t)cbot);
             chunk_publish(dc.sync + 1, q + 1u);
@@ -3651,13 +3711,33 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         }
         return;
     }
-    for (; t - 1 >= bot; t -= 2) {
-        step(t, cur, rb2);
-        step(t - 1, rb2, cur);
+    if constexpr (SPARSE) {   // (see lean_forward)
+        const int64_t ckh = mid + (int64_t)pg_sparse_segments(C, 1u) * (int64_t)PG_LEAN_SPARSE;   // the first checkpoint on the way down
+        for (; t - 1 >= ckh; t -= 2) {
+            step(kStore, t, cur, rb2);
+            step(kStore, t - 1, rb2, cur);
+        }
+        if (t >= ckh) { step(kStore, t, cur, rb2); cur = rb2; --t; }
+        while (t >= bot) {
+            for (uint32_t g = 0; g + 1u < PG_LEAN_SPARSE / 2u; ++g, t -= 2) {
+                step(kNoStore, t, cur, rb2);
+                step(kNoStore, t - 1, rb2, cur);
+            }
+            step(kNoStore, t, cur, rb2);
+            step(kStore, t - 1, rb2, cur);
+            t -= 2;
+        }
+    } else {
+        for (; t - 1 >= bot; t -= 2) {
+            step(kStore, t, cur, rb2);
+            step(kStore, t - 1, rb2, cur);
+        }
+        if (t >= bot) step(kStore, t, cur, rb2);
     }
-    if (t >= bot) step(t, cur, rb2);
-    if (wave == 1 && bsc.valid) bsc.flush(bscale, lane, (uint64_t)bot);
-    if (wave == 2 && bsm.valid) bsm.flush(bsum, lane, (uint64_t)bot);
+    if constexpr (PHASE != 5) {
+        if (wave == 1 && bsc.valid) bsc.flush(bscale, lane, (uint64_t)bot);
+        if (wave == 2 && bsm.valid) bsm.flush(bsum, lane, (uint64_t)bot);
+    }
     if (kLeanTimeline && tid == 0) tl.write(dc.prof + 48);
 }
 
@@ -4056,11 +4136,50 @@ DEVI void sweep_lean_body(const DevContig* __restrict__ contigs, uint32_t chunk,
     const uint32_t C = (uint32_t)__builtin_amdgcn_readfirstlane((int)*dc.n_cols);
     if (C == 0) return;
     const unsigned long long t_begin = kChainProf ? __builtin_amdgcn_s_memtime() : 0ull;
-    if (blockIdx.y == 0) lean_forward<PHASE, R, TRI>(dc, sh, C, chunk);
-    else lean_backward<PHASE, R, TRI>(dc, sh, C, chunk);
+    if constexpr (PHASE == 1 && !TRI) {
+        if (dc.sparse) {   // (uniform; the two bodies are separate code: the dense one is what it was)
+            if (blockIdx.y == 0) lean_forward<PHASE, R, TRI, true>(dc, sh, C, chunk);
+            else lean_backward<PHASE, R, TRI, true>(dc, sh, C, chunk);
+        } else {
+            if (blockIdx.y == 0) lean_forward<PHASE, R, TRI>(dc, sh, C, chunk);
+            else lean_backward<PHASE, R, TRI>(dc, sh, C, chunk);
+        }
+    } else {
+        if (blockIdx.y == 0) lean_forward<PHASE, R, TRI>(dc, sh, C, chunk);
+        else lean_backward<PHASE, R, TRI>(dc, sh, C, chunk);
+    }
     if (kChainProf && threadIdx.x == 0) {  // -DPG_CHAIN_PROF builds only: cycles of this role's launch (last chunk wins)
         unsigned long long* o = dc.prof + (blockIdx.y == 0 ? 0 : 16) + (PHASE == 1 ? 0 : 8);
         o[0] = __builtin_amdgcn_s_memtime() - t_begin;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+//  k_refill_lean : the columns a sparse phase 1 (DevContig::sparse) left out, for the chunk that k_post reads next.  A workgroup is
+//  the four-wave lean step itself (lean_forward / lean_backward, PHASE 5): it resumes from a checkpoint and stores the
+//  PG_LEAN_SPARSE - 1 columns behind it — the bits the chain would have stored, from the same instructions.  Segments are
+//  independent of each other: the blocks stride over the launch's list (both roles of every chain, `q` = chunk_cols / PG_LEAN_SPARSE
+//  segments each, the chain the fastest index so that a short chain's empty items spread over all blocks).  Placed like k_post: as
+//  many blocks as the chains leave CUs idle, with dynamic LDS that does not fit next to a sweep workgroup (PG_REFILL_PLACEMENT_LDS).
+// ------------------------------------------------------------------------------------------
+#define PG_REFILL_PLACEMENT_LDS (100 * 1024)
+template <int R>
+__global__ __launch_bounds__((64 * 64 / R)) void k_refill_lean(const DevContig* __restrict__ contigs, uint32_t n_contigs, uint32_t chunk, uint32_t q) {
+    __shared__ LeanShared<R> sh;
+    static_assert(sizeof(LeanShared<R>) + PG_REFILL_PLACEMENT_LDS <= 160 * 1024 && 2 * sizeof(LeanShared<R>) + PG_REFILL_PLACEMENT_LDS > 160 * 1024,
+                  "a refill block fits a CU of its own and none that runs a sweep workgroup");
+    const uint32_t total = 2u * q * n_contigs;
+    for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {   // (everything below is uniform over the block)
+        const uint32_t chain = w % n_contigs, role = (w / n_contigs) & 1u, j = w / (2u * n_contigs);
+        const DevContig& dc = contigs[chain];
+        if (dc.lean != 1u || dc.tri != 0u || !dc.sparse) continue;
+        const uint32_t C = (uint32_t)__builtin_amdgcn_readfirstlane((int)*dc.n_cols);
+        const unsigned long long m = (unsigned long long)chunk * q + j + 1u;
+        if (m > pg_sparse_segments(C, role)) continue;
+        const uint32_t ck = pg_sparse_checkpoint(C, role, (uint32_t)m);
+        __syncthreads();   // (the segment before this one is done with the LDS)
+        if (role == 0u) lean_forward<5, R, false>(dc, sh, C, ck);
+        else lean_backward<5, R, false>(dc, sh, C, ck);
     }
 }
 
@@ -6949,6 +7068,20 @@ uint32_t pgk_post_blocks(uint32_t n_contigs, uint32_t chunk_cols, uint32_t* cus_
     if (bx > cap) bx = cap;
     if (const char* e = getenv("PG_POST_BLOCKS")) { const long v = strtol(e, nullptr, 0); if (v >= 1 && (uint32_t)v < bx) bx = (uint32_t)v; }   // (experiments: fewer)
     return bx ? bx : 1u;
+}
+// the columns of chunk `chunk`'s partner ranges that the sparse phase 1 left out (k_refill_lean), on the CUs the chains leave idle
+void pgk_launch_refill(const DevContig* d_contigs, uint32_t n_contigs, uint32_t chunk_cols, uint32_t chunk, hipStream_t s) {
+    static bool attr_done[PG_MAX_DEVICES];
+    if (lds_attr_pending(attr_done))
+        (void)hipFuncSetAttribute((const void*)k_refill_lean<16>, hipFuncAttributeMaxDynamicSharedMemorySize, PG_REFILL_PLACEMENT_LDS);
+    uint32_t cus = 0;
+    (void)pgk_post_blocks(n_contigs, chunk_cols, &cus);
+    const uint32_t q = chunk_cols / PG_LEAN_SPARSE;
+    uint32_t blocks = cus > 2u * n_contigs + n_contigs ? cus - 2u * n_contigs : n_contigs;   // (k_post's count)
+    if (const char* e = getenv("PG_REFILL_BLOCKS")) { const long v = strtol(e, nullptr, 0); if (v >= 1 && (uint32_t)v < blocks) blocks = (uint32_t)v; }   // (experiments: fewer)
+    if (blocks > 2u * q * n_contigs) blocks = 2u * q * n_contigs;
+    if (blocks == 0u) return;
+    hipLaunchKernelGGL((k_refill_lean<16>), dim3(blocks), dim3(256), PG_REFILL_PLACEMENT_LDS, s, d_contigs, n_contigs, chunk, q);
 }
 void pgk_launch_post(const DevContig* d_contigs, uint32_t n_contigs, uint32_t chunk_cols, uint32_t chunk, hipStream_t s) {
     static bool attr_done[PG_MAX_DEVICES];

@@ -453,6 +453,10 @@ struct pg_job {
     // of its own: phase 2 is ONE launch of each, chunks handed over through DevContig::sync (PG_KERNELS=nopersist: a launch per chunk)
     bool persist = false;
     uint32_t post_blocks = 0;
+    // chunked jobs (a launch per chunk) that leave CUs idle, chunk_cols a multiple of PG_LEAN_SPARSE: phase 1 of the lean chains stores
+    // only its checkpoints and k_refill_lean forms the columns between them on the second stream, chunk by chunk in front of k_post
+    // (DevContig::sparse; PG_KERNELS=nosparse: every column by the chain)
+    bool sparse = false;
     // The pipelined first run of a one-shot job (job_build with cache_arena: upload and run inside ONE call, the host arrays stay
     // valid): the inputs of the LONG chains (group A: the job's wall time) are uploaded first and their preparation + phase 1
     // start while the other chains' inputs (group B, most of the bytes) are still crossing PCIe; B's index pass, preparation and
@@ -825,11 +829,12 @@ int upload_inputs(pg_job* job, const pg_contig_batch* batches, const std::vector
 //   persist             chunked jobs whose chains are all lean chains run phase 2 as the persistent pair k_sweep_lean<4> + k_post_loop
 //                       (one launch each, chunks handed over on the device) instead of one launch per chunk (k_sweep_lean<3> + k_post).
 //                       Opt-in: measured at par or behind on the whole-genome job (profiles/r06_persist.txt).  nopersist: the default, spelled out
+//   nosparse            phase 1 of the lean chains of chunked jobs stores every column itself (no k_refill_lean) — cross-check
 //   nosplit             the 16-path chains of fused jobs prepare every variant per sample (k_prep*, k_records, k_bins_lean2 / _x) instead of
 //                       taking the split path (pg_split.h)
 struct KernelChoice {
     bool general = false, generic = false, nolean2 = false, notri = false, nocls4 = false, prepwave = false, fullcols = false, nosmall2 = false, nosplit = false;
-    bool persist = false, noleanx2 = false, nowidef = false;
+    bool persist = false, noleanx2 = false, nowidef = false, nosparse = false;
     int leanx = -1, small = -1;   // -1: by the job, 0 / 1: forced
     std::string unknown;          // a token this list does not know
 };
@@ -848,6 +853,7 @@ KernelChoice kernel_choice() {
         else if (tok == "nosplit") k.nosplit = true;
         else if (tok == "noleanx2") k.noleanx2 = true;
         else if (tok == "nowidef") k.nowidef = true;
+        else if (tok == "nosparse") k.nosparse = true;
         else if (tok == "persist") k.persist = true; else if (tok == "nopersist") k.persist = false;
         else if (!tok.empty()) k.unknown = tok;   // (a typo would quietly test the default path against itself: job creation fails)
         tok.clear();
@@ -1064,7 +1070,7 @@ void choose_job_mode(pg_job* job, const BuildArgs& a, size_t chunk_cap) {
     const KernelChoice& kc = a.kc;
     const pg_hmm_params& params = a.params;
     const uint32_t n_chains = (uint32_t)a.specs.size();
-    job->persist = false; job->post_blocks = 0; job->any_split = false;
+    job->persist = false; job->post_blocks = 0; job->any_split = false; job->sparse = false;
     {
         // k_sweep_small16 packs four H = 16 half-chains into a wave: a throughput kernel.  A single chain is faster on the
         // general kernel (four states per lane instead of sixteen: 375 vs 470 ns per column); PG_KERNELS=small / nosmall forces.
@@ -1149,6 +1155,13 @@ void choose_job_mode(pg_job* job, const BuildArgs& a, size_t chunk_cap) {
                 if (pb >= 1u) { job->persist = true; job->post_blocks = pb; }
             }
         }
+        // the sparse phase 1 of lean chains: whole refill segments per chunk, and CUs beside the chains for k_refill_lean (what
+        // pgk_launch_post asks before it shares the idle CUs out)
+        if (any_lean && !job->persist && !kc.nosparse && job->chunk_cols % PG_LEAN_SPARSE == 0u) {
+            uint32_t cus = 0;
+            (void)pgk_post_blocks(n_chains, job->chunk_cols, &cus);
+            job->sparse = cus >= 2u * n_chains + n_chains;
+        }
     }
     // ---- the split path: which index contigs' chains take it (pg_device.h) ---------------------------
     for (auto& x : job->index) {
@@ -1209,7 +1222,7 @@ struct ChainKernels {
     BinsKernel bins_one = BN_NONE;   // ... those of a k_sweep_small16x chain left with a single column
     BinsKernel bins_wide = BN_NONE;  // ... and those of its wide columns
     // the values of the DevContig fields of the same names
-    uint32_t lean = 0, leanx = 0, leanx2 = 0, tri = 0, cls4 = 0, small = 0, smallx = 0, widef = 0, T = 0;
+    uint32_t lean = 0, leanx = 0, leanx2 = 0, tri = 0, cls4 = 0, small = 0, smallx = 0, widef = 0, T = 0, sparse = 0;
 };
 
 // Every chain's kernels from its index contig's class and the job's mode; from them the two launch masks.
@@ -1237,6 +1250,7 @@ std::vector<ChainKernels> choose_chain_kernels(pg_job* job, const BuildArgs& a) 
         // needs the column-order records of the general kernel, which phase 2 reads too) — PG_KERNELS=noleanx: the general kernel
         // with triangle stores (k_sweep_tri1)
         k.leanx = (k.tri && !x.lean && kc.leanx != 0) ? 2u : (x.leanx ? 1u : 0u);
+        k.sparse = (job->sparse && k.lean == 1u && k.tri == 0u) ? 1u : 0u;   // (chunked jobs have no triangle chains)
         k.prep = x.split ? (x.all_sb ? PREP_S_BI : PREP_S_LISTS) : x.prep_fast == 1u ? PREP_BI : x.prep_fast == 2u ? PREP_BI_LISTS : PREP_W;
 
         const SweepKernel own = x.HP >= 256 ? SW_GENERIC : (kc.generic && x.HP >= 64) ? SW_GENERIC64
@@ -1283,7 +1297,7 @@ std::string plan_text(const pg_job* job, const BuildArgs& a, const std::vector<C
         auto name = [&](SweepKernel s, int phase) { return sweep_name(a.kc.generic && s >= SW_HP16 && s <= SW_HP128 ? SW_GENERIC : s, phase); };
         std::string p2, bins;
         if (k.post == POST_LOOP) { p2 = name(k.phase2, 4) + " (one launch, all chunks) + k_post_loop"; bins = "(k_post_loop)"; }
-        else if (k.post == POST_CHUNKS) { p2 = name(k.phase2, 3) + " chunks + k_post"; bins = "(k_post)"; }
+        else if (k.post == POST_CHUNKS) { p2 = name(k.phase2, 3) + " chunks + " + (k.sparse ? "k_refill_lean + " : "") + "k_post"; bins = "(k_post)"; }
         else {
             p2 = name(k.phase2, 2);
             if (k.tri && k.phase2 == k.general) p2 += " (triangle ring)";
@@ -1294,7 +1308,7 @@ std::string plan_text(const pg_job* job, const BuildArgs& a, const std::vector<C
         char head[160];
         snprintf(head, sizeof(head), "%u path(s) (padded %u), %s%s%s columns: ", x.H, x.HP, x.pair_n > 2 ? "multiallelic" : "biallelic", x.wide_bytes ? " + wide" : "",
                  k.tri ? ", triangle" : "");
-        const std::string text = std::string(head) + "prep = " + kPrepName[k.prep] + "; phase 1 = " + name(k.phase1, 1) + "; phase 2 = " + p2 + "; bins = " + bins;
+        const std::string text = std::string(head) + "prep = " + kPrepName[k.prep] + "; phase 1 = " + name(k.phase1, 1) + (k.sparse ? " (sparse: every 64th column stored)" : "") + "; phase 2 = " + p2 + "; bins = " + bins;
         bool found = false;
         for (auto& g : groups) if (g.text == text) { g.count += 1; found = true; break; }
         if (!found) groups.push_back({text, 1});
@@ -1541,7 +1555,7 @@ std::vector<DevContig> fill_descriptors(pg_job* job, const BuildArgs& a, const s
         d.wide = A + p.wide; d.wide_idx = x.wide_bytes ? (const uint32_t*)(A + x.o_widx) : nullptr;
         d.vpair = A + p.vpair; d.xbuf = (double*)(A + p.xbuf);
         d.frec = (double*)(A + p.frec);
-        d.lean = k.lean; d.small = k.small; d.smallx = k.smallx; d.leanx = k.leanx; d.leanx2 = k.leanx2; d.cls4 = k.cls4; d.widef = k.widef; d.tri = k.tri;
+        d.lean = k.lean; d.small = k.small; d.smallx = k.smallx; d.leanx = k.leanx; d.leanx2 = k.leanx2; d.cls4 = k.cls4; d.widef = k.widef; d.tri = k.tri; d.sparse = k.sparse;
         d.col_stride = d.tri ? 2304u : x.HP * x.HP;
         d.aux = A + p.aux; d.aux_idx = ((d.smallx == 2u || x.widef) && x.aux_bytes) ? (const uint32_t*)(A + x.o_auxidx) : nullptr;
         if ((d.smallx == 2u || x.widef) && x.wide_bytes && x.n_wide_cand) {
@@ -2112,7 +2126,10 @@ extern "C" int pg_job_run(pg_job* job, void* stream_, char* err, size_t errlen) 
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipEventRecord(job->ev_post[0], s2));
                 HIP_TRY(hipStreamWaitEvent(s, job->ev_post[0], 0));
-            } else
+            } else {
+            // sparse phase 1: the refill of chunk i's partner columns (k_refill_lean) goes in front of k_post(i) on the second stream —
+            // beside the sweep of chunk i, behind the posteriors of chunk i - 1; it needs phase 1 ended, nothing else
+            if (job->sparse) HIP_TRY(hipStreamWaitEvent(s2, job->ev[4], 0));
             for (uint32_t i = 0; i < job->n_chunks; ++i) {
                 const int b = (int)PG_SCR_BUF(i);
                 if (i >= PG_SCRATCH_BUFS) HIP_TRY(hipStreamWaitEvent(s, job->ev_post[b], 0));
@@ -2121,10 +2138,12 @@ extern "C" int pg_job_run(pg_job* job, void* stream_, char* err, size_t errlen) 
                 pgk_launch_sweep_smallx(job->d_contigs, job->d_smallx, job->n_smallx, 3, i, job->d_dump, s);
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipEventRecord(job->ev_sweep[b], s));
+                if (job->sparse) pgk_launch_refill(job->d_contigs, n, job->chunk_cols, i, s2);
                 HIP_TRY(hipStreamWaitEvent(s2, job->ev_sweep[b], 0));
                 pgk_launch_post(job->d_contigs, n, job->chunk_cols, i, s2);
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipEventRecord(job->ev_post[b], s2));
+            }
             }
             if (!persist_now) for (uint32_t q = 0; q < PG_SCRATCH_BUFS && q < job->n_chunks; ++q) HIP_TRY(hipStreamWaitEvent(s, job->ev_post[q], 0));
             HIP_TRY(hipEventRecord(job->ev[5], s));  // "k_sweep_phase2" = all chunks incl. their posteriors
@@ -2367,6 +2386,18 @@ extern "C" size_t pg_job_plan(const pg_job* job, char* out, size_t len) {
     }
     if (out && len) { const size_t n = t.size() < len - 1 ? t.size() : len - 1; memcpy(out, t.data(), n); out[n] = 0; }
     return t.size() + 1;
+}
+// The segment arithmetic of the sparse phase 1 (pg_device.h: pg_sparse_*), as the kernels use it — for tests on the host.
+extern "C" int pg_sparse_segment(uint32_t n_columns, uint32_t chunk_cols, uint32_t chunk, uint32_t role, uint32_t j, uint32_t out[3]) {
+    if (role > 1u || chunk_cols == 0u || chunk_cols % PG_LEAN_SPARSE != 0u || j >= chunk_cols / PG_LEAN_SPARSE) return -1;
+    const unsigned long long m = (unsigned long long)chunk * (chunk_cols / PG_LEAN_SPARSE) + j + 1u;
+    if (m > pg_sparse_segments(n_columns, role)) return 0;
+    const uint32_t ck = pg_sparse_checkpoint(n_columns, role, (uint32_t)m);
+    if (out) { out[0] = ck; out[1] = role == 0u ? ck + 1u : ck - (PG_LEAN_SPARSE - 1u); out[2] = role == 0u ? ck + (PG_LEAN_SPARSE - 1u) : ck - 1u; }
+    return 1;
+}
+extern "C" int pg_sparse_stored_by_chain(uint32_t n_columns, uint32_t role, uint32_t column) {
+    return role <= 1u && column < n_columns && pg_sparse_stored(n_columns, role, column) ? 1 : 0;
 }
 extern "C" uint32_t pg_job_triangle_chains(const pg_job* job) {
     if (!job) return 0;
