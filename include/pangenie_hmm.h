@@ -385,6 +385,58 @@ int  pg_calls_from_bins(int device, uint32_t n_variants, const uint32_t* allele_
                         const uint8_t* kept, const uint8_t* allele_present, const double* lik,
                         const int32_t* lik_exp, pg_call* out);
 
+/* ------------------------------------------------------------------ *
+ *  Genotype calls per VCF RECORD (DESIGN.md 4e "Records").  The index builder merges records closer than
+ *  k - 1 into one bubble; Graph::write_genotypes takes the bubble apart again: the bubble's normalised
+ *  likelihoods are folded onto each record's own alleles (Variant::separate_variants, reference
+ *  src/variant.cpp:357-384), genotypes over alleles of undefined sequence are dropped and the rest
+ *  renormalised (get_specific_likelihoods), then likeliest genotype and quality (src/graph.cpp:217-273).
+ *  The same on the device, in the integer arithmetic of pg_job_calls: one pg_call per record, holding the
+ *  GT and GQ columns of the VCF.  What a bubble means for its records depends on the index alone: the
+ *  RECORD PLAN of an index contig, uploaded once and shared by every chain (sample) over that contig.
+ *  Limits as for pg_job_calls (PG_CALL_DEFERRED: every record of such a bubble); a record has at most 256
+ *  alleles (PG_ERR_UNSUPPORTED).  `ignore_imputed` is the caller's (a bubble's k-mer count is in kmer_off).
+ * ------------------------------------------------------------------ */
+typedef struct pg_record_plan {
+    uint32_t n_variants;        /* V: the index contig's bubbles                                                      */
+    uint32_t n_records;         /* R = rec_off[V]                                                                     */
+    const uint32_t* rec_off;    /* [V+1] bubble v owns the records rec_off[v] .. rec_off[v+1] - 1, at least one       */
+    const uint32_t* map_off;    /* [R+1]                                                                              */
+    const uint16_t* map;        /* map[map_off[r] + id] = the record allele that bubble allele ID `id` carries        */
+                                /* (allele_combinations[id][r]); by id, not by slot, for id < map_off[r+1]-map_off[r] */
+    const uint16_t* n_alleles;  /* [R] alleles of the record (reference allele included)                              */
+    const uint32_t* vcf_off;    /* [R+1] vcf_off[r+1] - vcf_off[r] == n_alleles[r]                                    */
+    const uint16_t* vcf_index;  /* per record allele: its index among the record's DEFINED alleles (the GT number),   */
+                                /* 0xFFFF if its sequence is undefined; allele 0 is always defined                    */
+} pg_record_plan;
+#define PG_CALL_EMPTY 0x100  /* with PG_CALL_OK: 0/0, GQ 10000 because the bubble has no likelihoods at all (not a   */
+                             /* kept column, no allele on a selected path), as the VCF prints it, not from evidence  */
+/* Checks and uploads the plan of index contig `index_contig` (0 .. n_contigs - 1 of pg_job_create / pg_cohort_new); a
+ * second plan for the same contig replaces the first.  Device memory outside the arena, freed by pg_job_destroy.
+ * PG_ERR_INVALID: n_variants is not the contig's, offsets that do not start at 0 or do not grow (a bubble without a
+ * record), vcf_off that does not follow n_alleles, a map entry >= the record's n_alleles, a vcf_index that is not the
+ * running count of defined alleles.  PG_ERR_UNSUPPORTED: a record with more than 256 alleles. */
+int  pg_job_record_plan(pg_job* job, uint32_t index_contig, const pg_record_plan* plan, char* err, size_t errlen);
+/* Forms one pg_call per record for every chain whose index contig has a plan (a chain without one is left out), on the
+ * job's stream; blocking.  allele_1 <= allele_2 are GT numbers: indices among the record's defined alleles.  Refusals
+ * as pg_job_calls; PG_ERR_INVALID also if an allele id of the index lies outside a record's map (checked here, on the
+ * host, whenever a plan or the index has changed: a sampled panel's ids exist only after its job was made). */
+int  pg_job_record_calls(pg_job* job, char* err, size_t errlen);
+/* Chain `chain`'s records, out[R of its index contig's plan] (after pg_job_record_calls); nothing for a chain without a plan. */
+int  pg_job_fetch_record_calls(pg_job* job, uint32_t chain, pg_call* out, char* err, size_t errlen);
+/* The same for all chains, outs[n_chains] (NULL allowed where a chain has no records): one synchronisation. */
+int  pg_job_fetch_record_calls_all(pg_job* job, pg_call* const* outs, char* err, size_t errlen);
+/* Device-resident records of chain `chain`: pg_call [n] (n = 0 for a chain without a plan). */
+int  pg_job_device_record_calls(pg_job* job, uint32_t chain, void** d_calls, uint64_t* n);
+/* Elapsed milliseconds of the kernels of the LAST pg_job_record_calls. */
+double pg_job_record_calls_ms(const pg_job* job);
+/* Unit entry point: the record calls of n_variants bubbles from host arrays (as pg_calls_from_bins) and a plan, through
+ * the same kernels; out[plan->n_records].  The plan is checked first (PG_ERR_INVALID / PG_ERR_UNSUPPORTED as above, the
+ * allele ids included); then PG_ERR_DEVICE without a device: there is no host fallback. */
+int  pg_record_calls_from_bins(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id,
+                               const uint8_t* kept, const uint8_t* allele_present, const double* lik,
+                               const int32_t* lik_exp, const pg_record_plan* plan, pg_call* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,6 +237,21 @@ def _bind_hip(lib):
     lib.pg_job_calls_ms.restype = C.c_double
     lib.pg_calls_from_bins.argtypes = [C.c_int, C.c_uint32, u32p, u16p, u8p, u8p, f64p, i32p, C.c_void_p]
     lib.pg_calls_from_bins.restype = C.c_int
+    # ... per VCF record (pangenie_amd/calls.py: RecordPlan); the plan is passed as a calls.PgRecordPlan by reference
+    lib.pg_job_record_plan.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_record_plan.restype = C.c_int
+    lib.pg_job_record_calls.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_record_calls.restype = C.c_int
+    lib.pg_job_fetch_record_calls.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_fetch_record_calls.restype = C.c_int
+    lib.pg_job_fetch_record_calls_all.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+    lib.pg_job_fetch_record_calls_all.restype = C.c_int
+    lib.pg_job_device_record_calls.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), u64p]
+    lib.pg_job_device_record_calls.restype = C.c_int
+    lib.pg_job_record_calls_ms.argtypes = [C.c_void_p]
+    lib.pg_job_record_calls_ms.restype = C.c_double
+    lib.pg_record_calls_from_bins.argtypes = [C.c_int, C.c_uint32, u32p, u16p, u8p, u8p, f64p, i32p, C.c_void_p, C.c_void_p]
+    lib.pg_record_calls_from_bins.restype = C.c_int
     return lib
 
 
@@ -253,6 +268,8 @@ HIP_ABI_SYMBOLS = [
     "pg_hmm_gather", "pg_hmm_gather_all", "pg_hmm_gather_to_host",
     "pg_hmm_announce", "pg_hmm_retract", "pg_hmm_coalesce_stats", "pg_job_fetch_all", "pg_job_panel_sizes", "pg_job_fetch_panel",
     "pg_job_calls", "pg_job_fetch_calls", "pg_job_fetch_calls_all", "pg_job_device_calls", "pg_job_calls_ms", "pg_calls_from_bins",
+    "pg_job_record_plan", "pg_job_record_calls", "pg_job_fetch_record_calls", "pg_job_fetch_record_calls_all", "pg_job_device_record_calls",
+    "pg_job_record_calls_ms", "pg_record_calls_from_bins",
     "pg_sparse_segment", "pg_sparse_stored_by_chain",
 ]
 

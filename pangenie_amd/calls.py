@@ -19,6 +19,7 @@ PG_CALL_OK = 0          # a unique likeliest genotype
 PG_CALL_NONE = 1        # ./. : not a kept column, no key, every bin zero
 PG_CALL_NOT_UNIQUE = 2  # ./. : another genotype within 1e-10 of the best
 PG_CALL_DEFERRED = 3    # largest bin below 2^-16300: to be decided on the host from this variant's bins
+PG_CALL_EMPTY = 0x100   # record calls, with PG_CALL_OK: 0/0 and GQ 10000 of a bubble without any likelihood
 _ERRLEN = 512
 
 
@@ -78,3 +79,133 @@ def calls_from_bins(allele_off, allele_id, kept, allele_present, lik, lik_exp, d
         raise _error(rc, None)
     return out[:V]
 
+
+
+# ---------------------------------------------------------------------------------------------------------------
+#  Calls per VCF record (pg_job_record_plan, pg_job_record_calls, pg_record_calls_from_bins; DESIGN.md 4e "Records")
+# ---------------------------------------------------------------------------------------------------------------
+class PgRecordPlan(C.Structure):
+    _fields_ = [("n_variants", C.c_uint32), ("n_records", C.c_uint32), ("rec_off", _lib.u32p), ("map_off", _lib.u32p), ("map", _lib.u16p),
+                ("n_alleles", _lib.u16p), ("vcf_off", _lib.u32p), ("vcf_index", _lib.u16p)]
+
+
+class RecordPlan:
+    """What the bubbles of one index contig mean for their VCF records (pg_record_plan): rec_off [V+1] the records of every
+    bubble; per record r the map from bubble allele ID to record allele (map[map_off[r] + id]), its number of alleles, and
+    for every record allele its index among the defined ones (vcf_index, 0xFFFF: undefined sequence).  Nothing is checked
+    here: the library does that."""
+
+    def __init__(self, rec_off, map_off, map, n_alleles, vcf_off, vcf_index):
+        self.rec_off = np.ascontiguousarray(rec_off, np.uint32)
+        self.map_off = np.ascontiguousarray(map_off, np.uint32)
+        self.n_alleles = np.ascontiguousarray(n_alleles, np.uint16)
+        self.vcf_off = np.ascontiguousarray(vcf_off, np.uint32)
+        pad = lambda a: np.ascontiguousarray(a, np.uint16) if len(a) else np.zeros(1, np.uint16)
+        self.map, self.vcf_index = pad(map), pad(vcf_index)
+        if len(self.n_alleles) == 0:
+            self.n_alleles = np.zeros(1, np.uint16)
+
+    @property
+    def n_variants(self) -> int:
+        return len(self.rec_off) - 1
+
+    @property
+    def n_records(self) -> int:
+        return len(self.map_off) - 1
+
+    @classmethod
+    def from_records(cls, bubbles) -> "RecordPlan":
+        """bubbles: per bubble a list of records, each (own, defined) — own[id] the record allele of bubble allele id,
+        defined[a] whether record allele a has a defined sequence."""
+        rec_off, map_off, mp, nal, vcf_off, vcf = [0], [0], [], [], [0], []
+        for records in bubbles:
+            for own, defined in records:
+                mp += [int(x) for x in own]
+                map_off.append(len(mp))
+                nal.append(len(defined))
+                d = 0
+                for ok in defined:
+                    vcf.append(d if ok else 0xFFFF)
+                    d += 1 if ok else 0
+                vcf_off.append(len(vcf))
+            rec_off.append(len(nal))
+        return cls(rec_off, map_off, mp, nal, vcf_off, vcf)
+
+    def record(self, r: int):
+        """(own, vcf_index) of record r"""
+        return (self.map[int(self.map_off[r]):int(self.map_off[r + 1])], self.vcf_index[int(self.vcf_off[r]):int(self.vcf_off[r + 1])])
+
+    def as_c(self) -> PgRecordPlan:
+        p = lambda a, t: a.ctypes.data_as(t)
+        return PgRecordPlan(self.n_variants, self.n_records, p(self.rec_off, _lib.u32p), p(self.map_off, _lib.u32p), p(self.map, _lib.u16p),
+                            p(self.n_alleles, _lib.u16p), p(self.vcf_off, _lib.u32p), p(self.vcf_index, _lib.u16p))
+
+
+def job_record_plan(job, contig: int, plan: RecordPlan) -> None:
+    err = C.create_string_buffer(_ERRLEN)
+    c = plan.as_c()
+    rc = job._lib.pg_job_record_plan(job.h, contig, C.addressof(c), err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    if not hasattr(job, "_record_plans"):
+        job._record_plans = {}
+    job._record_plans[contig] = plan
+
+
+def _n_records(job) -> List[int]:
+    plans, nc = getattr(job, "_record_plans", {}), len(job.index)
+    return [plans[c % nc].n_records if (c % nc) in plans else 0 for c in range(len(job.batches))]
+
+
+def job_record_calls(job, contig: Optional[int] = None):
+    """Job.record_calls(): forms the record calls of every chain that has a plan, fetches all of them (or chain `contig`'s)."""
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_record_calls(job.h, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    if contig is not None:
+        return fetch_record_calls(job, contig)
+    return fetch_record_calls_all(job)
+
+
+def fetch_record_calls(job, contig: int) -> np.ndarray:
+    R = _n_records(job)[contig]
+    out = np.zeros(max(R, 1), CALL_DTYPE)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_record_calls(job.h, contig, out.ctypes.data, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return out[:R]
+
+
+def fetch_record_calls_all(job) -> List[np.ndarray]:
+    Rs = _n_records(job)
+    outs = [np.zeros(max(R, 1), CALL_DTYPE) for R in Rs]
+    arr = (C.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_record_calls_all(job.h, arr, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return [o[:R] for o, R in zip(outs, Rs)]
+
+
+def record_calls_from_bins(allele_off, allele_id, kept, allele_present, lik, lik_exp, plan: RecordPlan, device: int = 0) -> np.ndarray:
+    """pg_record_calls_from_bins: the calls of the plan's records from host arrays laid out as for calls_from_bins."""
+    lib = _lib.load_hip()
+    aoff = np.ascontiguousarray(allele_off, np.uint32)
+    V = len(aoff) - 1
+    pad = lambda a, dt: np.ascontiguousarray(a, dt) if len(a) else np.zeros(1, dt)
+    aid, kp, pres = pad(allele_id, np.uint16), pad(kept, np.uint8), pad(allele_present, np.uint8)
+    lk, le = pad(lik, np.float64), pad(lik_exp, np.int32)
+    A = np.diff(aoff.astype(np.int64))
+    if len(allele_id) != int(aoff[-1]) or len(allele_present) != int(aoff[-1]) or len(kept) != V or len(lik) != int((A * (A + 1) // 2).sum()) \
+            or len(lik_exp) != len(lik):
+        raise ValueError("record_calls_from_bins: array lengths do not match allele_off")
+    out = np.zeros(max(plan.n_records, 1), CALL_DTYPE)
+    c = plan.as_c()
+    rc = lib.pg_record_calls_from_bins(device, V, aoff.ctypes.data_as(_lib.u32p), aid.ctypes.data_as(_lib.u16p), kp.ctypes.data_as(_lib.u8p),
+                                       pres.ctypes.data_as(_lib.u8p), lk.ctypes.data_as(_lib.f64p), le.ctypes.data_as(_lib.i32p), C.addressof(c),
+                                       out.ctypes.data)
+    if rc:
+        raise _error(rc, None)
+    return out[:plan.n_records]

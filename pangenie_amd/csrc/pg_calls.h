@@ -263,6 +263,111 @@ PGX_FN pgx_decision pgx_decide(Keys& keys, const uint64_t* thr_m, const int32_t*
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+//  One VCF record's call from its bubble's bins: the rules of DESIGN.md 4e "Records".  A bubble that the index builder
+//  merged from several records is taken apart again as Graph::write_genotypes does it: the bubble's normalised values
+//  are folded onto the record's own alleles (Variant::separate_variants), genotypes over alleles of undefined sequence
+//  are dropped and the rest renormalised (get_specific_likelihoods), then likeliest genotype and quality as above.
+//
+//  `Keys` walks the bubble's keys in the map's order — start(), then next(&value, &key) until it answers false — with
+//  key = (ra << 16) | rb, ra <= rb the record alleles the key's two bubble alleles carry.  The folded map F is never
+//  kept: its keys are visited in ascending order, and each visit walks the bubble once, adding the quotients that fall
+//  onto that key in the bubble's order (one division per bubble key and walk) and noting the next key on the way.
+//  `defined(ra)`: the record allele has a defined sequence (asked only if has_undefined).
+// ---------------------------------------------------------------------------------------------------------------
+#define PGX_CALL_EMPTY 0x100u   // with PGX_CALL_OK: 0/0, GQ 10000 from a bubble without keys (F[(0,0)] = 1), not from evidence
+#define PGX_NO_KEY 0xFFFFFFFFFFFFFFFFull
+
+struct pgx_record_decision {
+    uint32_t flags;   // PGX_CALL_* (| PGX_CALL_EMPTY)
+    uint32_t key;     // (ra << 16) | rb of the likeliest genotype (PGX_CALL_OK only)
+    uint32_t gq;
+};
+
+// F[cur] (if `value`) and the smallest key above cur; cur == PGX_NO_KEY: only the smallest key of all
+template <class Keys>
+PGX_FN pgx pgx_fold_key(Keys& keys, pgx sum, uint64_t cur, bool value, uint64_t* next) {
+    pgx acc = pgx_zero(), v;
+    uint32_t k;
+    uint64_t nxt = PGX_NO_KEY;
+    keys.start();
+    while (keys.next(&v, &k)) {
+        if (k == cur) { if (value) acc = pgx_add(acc, pgx_div(v, sum)); }
+        else if ((cur == PGX_NO_KEY || k > cur) && k < nxt) nxt = k;
+    }
+    *next = nxt;
+    return acc;
+}
+
+// Best and runner-up of a sequence taken with `>=`: `best` is the LAST of equal maxima, `second` the largest other value
+// (equal to best for equal maxima).  |x - best| < t holds for some other x iff it holds for `second`: rounded subtraction
+// is monotone.
+struct pgx_top2 {
+    pgx best, second;
+    uint64_t best_key;
+    bool has_second;
+};
+PGX_FN void pgx_top2_init(pgx_top2* t) { t->best = pgx_zero(); t->second = pgx_zero(); t->best_key = PGX_NO_KEY; t->has_second = false; }
+PGX_FN void pgx_top2_take(pgx_top2* t, pgx x, uint64_t key) {
+    if (pgx_cmp(x, t->best) >= 0) {
+        if (t->best_key != PGX_NO_KEY) { t->second = t->best; t->has_second = true; }
+        t->best = x;
+        t->best_key = key;
+    } else {
+        if (!t->has_second || pgx_cmp(x, t->second) > 0) t->second = x;
+        t->has_second = true;
+    }
+}
+
+template <class Keys, class Defined>
+PGX_FN pgx_record_decision pgx_decide_record(Keys& keys, bool has_undefined, Defined& defined, const uint64_t* thr_m, const int32_t* thr_e) {
+    pgx_record_decision r;
+    r.flags = PGX_CALL_NONE;
+    r.key = 0;
+    r.gq = 0;
+    pgx v, sum = pgx_zero(), largest = pgx_zero();
+    uint32_t k, n = 0;
+    keys.start();
+    while (keys.next(&v, &k)) {   // GenotypingResult::normalize of the bubble
+        sum = pgx_add(sum, v);
+        if (pgx_cmp(v, largest) > 0) largest = v;
+        ++n;
+    }
+    if (n == 0) {   // an empty map: F[(0,0)] = 1 (allele 0 is always defined: 1 / 1 after get_specific_likelihoods)
+        r.flags = PGX_CALL_OK | PGX_CALL_EMPTY;
+        r.gq = PG_GQ_CERTAIN;
+        return r;
+    }
+    if (sum.m == 0) return r;   // every bin zero: nothing is normalised, best == 0
+    if (pgx_below_pow2(largest, PG_CALLS_DEFER_EXP)) { r.flags = PGX_CALL_DEFERRED; return r; }
+    uint64_t first, cur, next;
+    (void)pgx_fold_key(keys, sum, PGX_NO_KEY, false, &first);
+    pgx sum2 = pgx_zero();
+    if (has_undefined) {   // get_specific_likelihoods: the defined keys of F added in F's order
+        for (cur = first; cur != PGX_NO_KEY; cur = next) {
+            const bool def = defined((uint32_t)(cur >> 16)) && defined((uint32_t)(cur & 0xFFFFu));
+            const pgx f = pgx_fold_key(keys, sum, cur, def, &next);
+            if (def) sum2 = pgx_add(sum2, f);
+        }
+        if (sum2.m == 0) return r;   // no defined key, or all of them zero: best == 0
+    }
+    pgx_top2 t;
+    pgx_top2_init(&t);
+    for (cur = first; cur != PGX_NO_KEY; cur = next) {   // get_likeliest_genotype over F
+        const bool def = !has_undefined || (defined((uint32_t)(cur >> 16)) && defined((uint32_t)(cur & 0xFFFFu)));
+        pgx f = pgx_fold_key(keys, sum, cur, def, &next);
+        if (!def) continue;
+        if (has_undefined) f = pgx_div(f, sum2);
+        pgx_top2_take(&t, f, cur);
+    }
+    if (t.best.m == 0) return r;
+    if (t.has_second && pgx_within_tie(t.best, t.second)) { r.flags = PGX_CALL_NOT_UNIQUE; return r; }
+    r.flags = PGX_CALL_OK;
+    r.key = (uint32_t)t.best_key;
+    r.gq = pgx_gq_of_best(t.best, thr_m, thr_e);
+    return r;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 //  Host only: the pair <-> long double, and the threshold table from log10l itself.
 // ---------------------------------------------------------------------------------------------------------------
 #include <math.h>

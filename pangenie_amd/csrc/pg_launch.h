@@ -48,7 +48,28 @@ struct CallsDesc {
     void* out;
 };
 
+// Record calls (pg_calls.hip, k_rcalls / k_rcalls_wide): an index contig's record plan as the device holds it, shared by every
+// chain over that contig, and one descriptor per chain that has a plan and variants.  Blocks [blk0, next blk0) of k_rcalls take
+// pgk_calls_block() RECORDS of the chain each; `out` = the chain's 8-byte records, one per VCF record.
+struct RecPlanDev {
+    const uint32_t* rec_var;    // [R] the bubble (variant) of record r; bit 31: the record has alleles of undefined sequence
+    const uint32_t* map_off;    // [R+1]
+    const uint16_t* map;        // map[map_off[r] + allele id] = the record allele that bubble allele carries
+    const uint32_t* vcf_off;    // [R+1]; vcf_off[r + 1] - vcf_off[r] = the record's alleles (at most PG_MAX_ALLELES_PER_VARIANT)
+    const uint16_t* vcf_index;  // per record allele: its index among the defined ones, 0xFFFF if its sequence is undefined
+};
+struct RCallsDesc {
+    uint32_t blk0, R;
+    uint32_t chain, pad;
+    void* out;
+    RecPlanDev plan;
+};
+
 extern "C" {
+// pg_calls.hip: d_wide = uint2 {descriptor, record} of every record of a bubble with more than PG_AMAX alleles; d_stage = n_slots
+// staging slots of `stride` 16-byte values each (max_bins quotients, then the folded map) — one per block of k_rcalls_wide
+void pgk_launch_rcalls(const DevContig* d_contigs, const RCallsDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide, uint32_t n_wide,
+                       void* d_stage, uint32_t max_bins, uint32_t stride, uint32_t n_slots, const uint64_t* d_thr_m, const int32_t* d_thr_e, hipStream_t s);
 // pg_calls.hip: d_wide = uint2 {descriptor, variant} of every variant with more than PG_AMAX alleles (k_calls_wide's list)
 void pgk_launch_calls(const DevContig* d_contigs, const CallsDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide, uint32_t n_wide,
                       const uint64_t* d_thr_m, const int32_t* d_thr_e, hipStream_t s);

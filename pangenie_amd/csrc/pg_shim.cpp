@@ -381,6 +381,16 @@ struct PinnedPool {
     void clear() { std::lock_guard<std::mutex> l(mu); for (unsigned char* p : free_list) hipHostFree(p); free_list.clear(); }
 } g_pinned;
 
+// One index contig's record plan (pg_record_plan, include/pangenie_hmm.h) as the host keeps it, and its device copy.
+struct RecordPlanHost {
+    bool set = false;
+    uint32_t V = 0, R = 0;
+    std::vector<uint32_t> rec_off, rec_var, map_off, vcf_off;
+    std::vector<uint16_t> map, vcf_index;
+    unsigned char* d = nullptr;   // rec_var, map_off, map, vcf_off, vcf_index: one allocation
+    RecPlanDev dev = {};
+};
+
 }  // namespace
 
 struct pg_job {
@@ -506,6 +516,17 @@ struct pg_job {
     hipEvent_t ev_calls[2];
     bool calls_events = false;
     double calls_ms = 0.0;
+    // Record calls (pg_job_record_plan / pg_job_record_calls): one plan per index contig, shared by every chain over it, and one
+    // 8-byte record per VCF record of every chain whose index contig has a plan.  Outside the arena like the calls.
+    std::vector<RecordPlanHost> rplans;       // [n_index] (sized by the first pg_job_record_plan)
+    bool rcalls_dirty = true;                 // a plan or the index changed: descriptors, lists and the id check are redone
+    unsigned char* d_rcalls = nullptr;        // the records, the chain descriptors, k_rcalls_wide's list, its staging slots
+    std::vector<uint64_t> rcalls_first;       // [n_chains + 1] first record of every chain (a chain without a plan has none)
+    std::vector<RCallsDesc> rcalls_desc;
+    uint32_t rcalls_blocks = 0, rcalls_wide = 0, rcalls_max_bins = 0, rcalls_stride = 0, rcalls_slots = 0;
+    size_t o_rcalls_desc = 0, o_rcalls_wide = 0, o_rcalls_stage = 0;
+    bool rcalls_formed = false;
+    double rcalls_ms = 0.0;
 };
 
 extern "C" void pg_job_destroy(pg_job* job) {
@@ -523,6 +544,8 @@ extern "C" void pg_job_destroy(pg_job* job) {
     if (job->stream) hipStreamSynchronize(job->stream);
     if (job->stream2) hipStreamSynchronize(job->stream2);
     if (job->d_calls) hipFree(job->d_calls);
+    if (job->d_rcalls) hipFree(job->d_rcalls);
+    for (RecordPlanHost& rp : job->rplans) if (rp.d) hipFree(rp.d);
     if (job->events) {
         for (auto& e : job->ev) hipEventDestroy(e);
         for (auto& e : job->ev_vit) hipEventDestroy(e);
@@ -654,6 +677,7 @@ int upload_inputs(pg_job* job, const pg_contig_batch* batches, const std::vector
         }                                                                                                     \
     } while (0)
     if (with_index) {
+        job->rcalls_dirty = true;   // (new allele ids: the record plans are checked against them again)
         for (size_t i = 0; i < job->index.size(); ++i) {
             const pg_contig_batch& b = batches[i];
             IndexHost& x = job->index[i];
@@ -2865,6 +2889,344 @@ extern "C" int pg_calls_from_bins(int device, uint32_t n_variants, const uint32_
         pgk_launch_calls((const DevContig*)(d + o_contig), (const CallsDesc*)(d + o_desc), 1, n_blocks, d + o_wide, (uint32_t)(wide.size() / 2), d_tm, d_te, nullptr);
         ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
              hipMemcpy(out, d + o_out, (size_t)V * sizeof(pg_call), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    hipFree(d);
+    return ok ? PG_OK : PG_ERR_DEVICE;
+}
+
+// ---------------------------------------------------------------------------------------
+//  Genotype calls per VCF record (pg_calls.hip: k_rcalls / k_rcalls_wide, DESIGN.md 4e "Records").
+// ---------------------------------------------------------------------------------------
+namespace {
+
+static_assert(PG_CALL_EMPTY == PGX_CALL_EMPTY, "the flag of the public header is the kernels' flag");
+
+// The checks that need the plan alone (everything but the allele ids), and the host copy the job keeps.
+int check_record_plan(const pg_record_plan* p, uint32_t V, RecordPlanHost* h, char* err, size_t errlen) {
+    if (!p) { set_err(err, errlen, "null record plan"); return PG_ERR_INVALID; }
+    if (p->n_variants != V) { set_err(err, errlen, "the record plan has %u variants, the index contig %u", p->n_variants, V); return PG_ERR_INVALID; }
+    RecordPlanHost r;
+    r.set = true;
+    r.V = V;
+    if (V == 0) {
+        if (p->n_records != 0) { set_err(err, errlen, "records without variants"); return PG_ERR_INVALID; }
+        *h = std::move(r);
+        return PG_OK;
+    }
+    if (!p->rec_off || !p->map_off || !p->map || !p->n_alleles || !p->vcf_off || !p->vcf_index) { set_err(err, errlen, "the record plan has null arrays"); return PG_ERR_INVALID; }
+    if (p->rec_off[0] != 0 || p->map_off[0] != 0 || p->vcf_off[0] != 0) { set_err(err, errlen, "the record plan's offset arrays must start at 0"); return PG_ERR_INVALID; }
+    for (uint32_t v = 0; v < V; ++v)
+        if (p->rec_off[v + 1] <= p->rec_off[v]) { set_err(err, errlen, "rec_off does not grow at variant %u: every bubble has at least one record", v); return PG_ERR_INVALID; }
+    const uint32_t R = p->rec_off[V];
+    if (R != p->n_records || R >= 0x80000000u) { set_err(err, errlen, "n_records is %u, rec_off ends at %u", p->n_records, R); return PG_ERR_INVALID; }
+    for (uint32_t q = 0; q < R; ++q) {
+        if (p->map_off[q + 1] < p->map_off[q] || p->vcf_off[q + 1] < p->vcf_off[q]) { set_err(err, errlen, "map_off / vcf_off shrink at record %u", q); return PG_ERR_INVALID; }
+        const uint32_t nA = p->n_alleles[q];
+        if (nA == 0 || p->vcf_off[q + 1] - p->vcf_off[q] != nA) { set_err(err, errlen, "record %u: n_alleles is %u, vcf_off gives %u", q, nA, p->vcf_off[q + 1] - p->vcf_off[q]); return PG_ERR_INVALID; }
+        if (nA > PG_MAX_ALLELES_PER_VARIANT) { set_err(err, errlen, "record %u has %u alleles: more than %d", q, nA, PG_MAX_ALLELES_PER_VARIANT); return PG_ERR_UNSUPPORTED; }
+        for (uint32_t i = p->map_off[q]; i < p->map_off[q + 1]; ++i)
+            if (p->map[i] >= nA) { set_err(err, errlen, "record %u: map entry %u is allele %u of %u", q, i - p->map_off[q], p->map[i], nA); return PG_ERR_INVALID; }
+        uint16_t defined = 0;
+        for (uint32_t a = 0; a < nA; ++a) {
+            const uint16_t x = p->vcf_index[p->vcf_off[q] + a];
+            if (x == 0xFFFFu && a > 0) continue;
+            if (x != defined) { set_err(err, errlen, "record %u: vcf_index of allele %u is %u, not the running count of defined alleles %u", q, a, x, defined); return PG_ERR_INVALID; }
+            ++defined;
+        }
+    }
+    r.R = R;
+    r.rec_off.assign(p->rec_off, p->rec_off + V + 1);
+    r.map_off.assign(p->map_off, p->map_off + R + 1);
+    r.vcf_off.assign(p->vcf_off, p->vcf_off + R + 1);
+    r.map.assign(p->map, p->map + p->map_off[R]);
+    r.vcf_index.assign(p->vcf_index, p->vcf_index + p->vcf_off[R]);
+    r.rec_var.resize(R);
+    for (uint32_t v = 0; v < V; ++v)
+        for (uint32_t q = r.rec_off[v]; q < r.rec_off[v + 1]; ++q) {
+            bool undef = false;
+            for (uint32_t i = r.vcf_off[q]; i < r.vcf_off[q + 1]; ++i) undef = undef || r.vcf_index[i] == 0xFFFFu;
+            r.rec_var[q] = v | (undef ? 0x80000000u : 0u);
+        }
+    *h = std::move(r);
+    return PG_OK;
+}
+
+// every allele id of the contig's bubbles has an entry in the map of each of the bubble's records
+int check_record_plan_ids(const RecordPlanHost& h, const uint32_t* allele_off, const uint16_t* allele_id, char* err, size_t errlen) {
+    for (uint32_t v = 0; v < h.V; ++v)
+        for (uint32_t q = h.rec_off[v]; q < h.rec_off[v + 1]; ++q) {
+            const uint32_t len = h.map_off[q + 1] - h.map_off[q];
+            for (uint32_t a = allele_off[v]; a < allele_off[v + 1]; ++a)
+                if (allele_id[a] >= len) { set_err(err, errlen, "variant %u: allele id %u lies outside the map of record %u (%u entries)", v, allele_id[a], q, len); return PG_ERR_INVALID; }
+        }
+    return PG_OK;
+}
+
+size_t record_plan_device_bytes(const RecordPlanHost& h) {
+    return align_up((size_t)h.R * 4 + 8) + 2 * align_up(((size_t)h.R + 1) * 4 + 8) + align_up(h.map.size() * 2 + 8) + align_up(h.vcf_index.size() * 2 + 8);
+}
+// copies the plan's arrays to d (record_plan_device_bytes of room) and points *dev at them
+bool record_plan_upload(const RecordPlanHost& h, unsigned char* d, RecPlanDev* dev) {
+    size_t o = 0;
+    auto put = [&](const void* src, size_t bytes) -> const void* {
+        unsigned char* at = d + o;
+        o += align_up(bytes + 8);
+        return (bytes == 0 || hipMemcpy(at, src, bytes, hipMemcpyHostToDevice) == hipSuccess) ? at : nullptr;
+    };
+    dev->rec_var = (const uint32_t*)put(h.rec_var.data(), (size_t)h.R * 4);
+    dev->map_off = (const uint32_t*)put(h.map_off.data(), ((size_t)h.R + 1) * 4);
+    dev->vcf_off = (const uint32_t*)put(h.vcf_off.data(), ((size_t)h.R + 1) * 4);
+    dev->map = (const uint16_t*)put(h.map.data(), h.map.size() * 2);
+    dev->vcf_index = (const uint16_t*)put(h.vcf_index.data(), h.vcf_index.size() * 2);
+    return dev->rec_var && dev->map_off && dev->vcf_off && dev->map && dev->vcf_index;
+}
+
+// The wave-per-record kernel stages a bubble's quotients and a record's folded map in device memory: one slot of `stride`
+// 16-byte values per block, at most 1024 blocks and 256 MB (a 256-allele bubble: 32 896 bins and as many keys, 1 MB a slot).
+struct RcallsLaunch {
+    std::vector<uint64_t> first;
+    std::vector<RCallsDesc> desc;
+    std::vector<uint32_t> wide;   // {descriptor, record} pairs
+    uint32_t n_blocks = 0, max_bins = 0, stride = 0, n_slots = 0;
+};
+// planOf(c): the plan of chain c's index contig or nullptr; aoff(c): the chain's allele_off
+template <class PlanOf, class AoffOf>
+void plan_rcalls(uint32_t n_chains, PlanOf planOf, AoffOf aoff, RcallsLaunch* L) {
+    const uint32_t per = pgk_calls_block();
+    L->first.assign((size_t)n_chains + 1, 0);
+    L->desc.clear();
+    L->wide.clear();
+    uint32_t blk = 0;
+    uint64_t max_bins = 0, max_keys = 0;
+    for (uint32_t c = 0; c < n_chains; ++c) {
+        const RecordPlanHost* h = planOf(c);
+        const uint32_t R = h ? h->R : 0;
+        L->first[c + 1] = L->first[c] + R;
+        if (R == 0) continue;
+        RCallsDesc d;
+        memset(&d, 0, sizeof(d));
+        d.blk0 = blk; d.R = R; d.chain = c;
+        d.plan = h->dev;
+        const uint32_t* off = aoff(c);
+        for (uint32_t v = 0; v < h->V; ++v) {
+            const uint64_t A = off[v + 1] - off[v];
+            if (A <= PG_AMAX) continue;
+            for (uint32_t q = h->rec_off[v]; q < h->rec_off[v + 1]; ++q) {
+                const uint64_t nA = h->vcf_off[q + 1] - h->vcf_off[q];
+                L->wide.push_back((uint32_t)L->desc.size());
+                L->wide.push_back(q);
+                max_bins = std::max(max_bins, A * (A + 1) / 2);
+                max_keys = std::max(max_keys, nA * (nA + 1) / 2);
+            }
+        }
+        L->desc.push_back(d);
+        blk += (R + per - 1) / per;
+    }
+    L->n_blocks = blk;
+    L->max_bins = (uint32_t)max_bins;
+    L->stride = (uint32_t)(max_bins + max_keys);
+    const uint64_t n_wide = L->wide.size() / 2;
+    L->n_slots = n_wide ? (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n_wide, 1024), std::max<uint64_t>(1, ((uint64_t)256 << 20) / ((uint64_t)L->stride * 16))) : 0;
+}
+
+int rcalls_ready(pg_job* job, char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
+    if (!job->rcalls_formed || job->rcalls_dirty) { set_err(err, errlen, "pg_job_record_calls has not been called"); return PG_ERR_INVALID; }
+    return PG_OK;
+}
+
+}  // namespace
+
+extern "C" int pg_job_record_plan(pg_job* job, uint32_t ix, const pg_record_plan* plan, char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    if (ix >= job->index.size()) { set_err(err, errlen, "index contig %u of %zu", ix, job->index.size()); return PG_ERR_INVALID; }
+    RecordPlanHost h;
+    int rc = check_record_plan(plan, job->index[ix].V, &h, err, errlen);
+    if (rc != PG_OK) return rc;
+    HIP_TRY(hipSetDevice(job->device));
+    if (h.R) {
+        const size_t bytes = record_plan_device_bytes(h);
+        if (hipMalloc((void**)&h.d, bytes) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the record plan failed", bytes); return PG_ERR_NOMEM; }
+        if (!record_plan_upload(h, h.d, &h.dev)) { hipFree(h.d); set_err(err, errlen, "upload of the record plan failed"); return PG_ERR_DEVICE; }
+    }
+    if (job->rplans.size() != job->index.size()) job->rplans.resize(job->index.size());
+    if (job->stream) HIP_TRY(hipStreamSynchronize(job->stream));   // (nothing reads the plan this one replaces any more)
+    if (job->rplans[ix].d) hipFree(job->rplans[ix].d);
+    job->rplans[ix] = std::move(h);
+    job->rcalls_dirty = true;
+    return PG_OK;
+}
+
+extern "C" int pg_job_record_calls(pg_job* job, char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    if (!job->params.run_genotyping) { set_err(err, errlen, "the job does not run the genotyping: it has no bins to call from"); return PG_ERR_INVALID; }
+    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(job->device));
+    const uint32_t n = (uint32_t)job->chains.size();
+    const uint64_t* d_tm = nullptr;
+    const int32_t* d_te = nullptr;
+    int rc = gq_table_on(job->device, &d_tm, &d_te, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (!job->calls_events) {
+        HIP_TRY(hipEventCreate(&job->ev_calls[0]));
+        HIP_TRY(hipEventCreate(&job->ev_calls[1]));
+        job->calls_events = true;
+    }
+    if (job->rcalls_dirty) {   // a plan or the index has changed: the ids are checked, the descriptors and lists made anew
+        std::vector<uint16_t> aid;
+        for (size_t ix = 0; ix < job->rplans.size(); ++ix) {
+            const RecordPlanHost& h = job->rplans[ix];
+            const IndexHost& x = job->index[ix];
+            if (!h.set || h.R == 0) continue;
+            aid.resize(x.sumA);
+            HIP_TRY(hipMemcpy(aid.data(), job->arena + x.o_aid, (size_t)x.sumA * 2, hipMemcpyDeviceToHost));
+            rc = check_record_plan_ids(h, x.aoff.data(), aid.data(), err, errlen);
+            if (rc != PG_OK) return rc;
+        }
+        RcallsLaunch L;
+        plan_rcalls(n, [&](uint32_t c) -> const RecordPlanHost* {
+                        const uint32_t ix = job->chains[c].index;
+                        return ix < job->rplans.size() && job->rplans[ix].set ? &job->rplans[ix] : nullptr;
+                    },
+                    [&](uint32_t c) { return job->index[job->chains[c].index].aoff.data(); }, &L);
+        const size_t o_desc = align_up((size_t)L.first[n] * sizeof(pg_call) + 8);
+        const size_t o_wide = o_desc + align_up(L.desc.size() * sizeof(RCallsDesc) + 8);
+        const size_t o_stage = o_wide + align_up(L.wide.size() * sizeof(uint32_t) + 8);
+        const size_t total = o_stage + align_up((size_t)L.n_slots * L.stride * 16 + 8);
+        unsigned char* d = nullptr;
+        if (hipMalloc((void**)&d, total) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the record calls failed", total); return PG_ERR_NOMEM; }
+        for (RCallsDesc& cd : L.desc) cd.out = d + L.first[cd.chain] * sizeof(pg_call);
+        hipError_t he = hipSuccess;
+        if (!L.desc.empty()) he = hipMemcpy(d + o_desc, L.desc.data(), L.desc.size() * sizeof(RCallsDesc), hipMemcpyHostToDevice);
+        if (he == hipSuccess && !L.wide.empty()) he = hipMemcpy(d + o_wide, L.wide.data(), L.wide.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (he != hipSuccess) { hipFree(d); set_err(err, errlen, "upload of the record calls' lists failed: %s", hipGetErrorString(he)); return PG_ERR_DEVICE; }
+        if (job->d_rcalls) hipFree(job->d_rcalls);
+        job->d_rcalls = d;
+        job->rcalls_first = std::move(L.first);
+        job->rcalls_desc = std::move(L.desc);
+        job->rcalls_blocks = L.n_blocks; job->rcalls_wide = (uint32_t)(L.wide.size() / 2);
+        job->rcalls_max_bins = L.max_bins; job->rcalls_stride = L.stride; job->rcalls_slots = L.n_slots;
+        job->o_rcalls_desc = o_desc; job->o_rcalls_wide = o_wide; job->o_rcalls_stage = o_stage;
+        job->rcalls_dirty = false;
+        job->rcalls_formed = false;
+    }
+    hipStream_t s = job->stream;
+    HIP_TRY(hipEventRecord(job->ev_calls[0], s));
+    pgk_launch_rcalls(job->d_contigs, (const RCallsDesc*)(job->d_rcalls + job->o_rcalls_desc), (uint32_t)job->rcalls_desc.size(), job->rcalls_blocks,
+                      job->d_rcalls + job->o_rcalls_wide, job->rcalls_wide, job->d_rcalls + job->o_rcalls_stage, job->rcalls_max_bins, job->rcalls_stride,
+                      job->rcalls_slots, d_tm, d_te, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(job->ev_calls[1], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, job->ev_calls[0], job->ev_calls[1]));
+    job->rcalls_ms = ms;
+    job->rcalls_formed = true;
+    return PG_OK;
+}
+
+extern "C" int pg_job_fetch_record_calls(pg_job* job, uint32_t ci, pg_call* out, char* err, size_t errlen) {
+    int rc = rcalls_ready(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (ci >= job->chains.size()) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    const uint64_t R = job->rcalls_first[ci + 1] - job->rcalls_first[ci];
+    if (R == 0) return PG_OK;
+    if (!out) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(job->device));
+    HIP_TRY(hipMemcpy(out, job->d_rcalls + job->rcalls_first[ci] * sizeof(pg_call), R * sizeof(pg_call), hipMemcpyDeviceToHost));
+    return PG_OK;
+}
+
+extern "C" int pg_job_fetch_record_calls_all(pg_job* job, pg_call* const* outs, char* err, size_t errlen) {
+    int rc = rcalls_ready(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (!outs) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(job->device));
+    for (size_t ci = 0; ci < job->chains.size(); ++ci) {
+        const uint64_t R = job->rcalls_first[ci + 1] - job->rcalls_first[ci];
+        if (R == 0) continue;
+        if (!outs[ci]) { set_err(err, errlen, "no buffer for chain %zu", ci); return PG_ERR_INVALID; }
+        HIP_TRY(hipMemcpyAsync(outs[ci], job->d_rcalls + job->rcalls_first[ci] * sizeof(pg_call), R * sizeof(pg_call), hipMemcpyDeviceToHost, job->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(job->stream));
+    return PG_OK;
+}
+
+extern "C" int pg_job_device_record_calls(pg_job* job, uint32_t ci, void** d_calls, uint64_t* n) {
+    if (!job || ci >= job->chains.size() || !job->d_rcalls || job->rcalls_dirty) return PG_ERR_INVALID;
+    if (d_calls) *d_calls = job->d_rcalls + job->rcalls_first[ci] * sizeof(pg_call);
+    if (n) *n = job->rcalls_first[ci + 1] - job->rcalls_first[ci];
+    return PG_OK;
+}
+
+extern "C" double pg_job_record_calls_ms(const pg_job* job) { return job ? job->rcalls_ms : 0.0; }
+
+// The unit entry point: host arrays and a plan in, one record per VCF record out, through the same two kernels.
+extern "C" int pg_record_calls_from_bins(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id, const uint8_t* kept,
+                                         const uint8_t* allele_present, const double* lik, const int32_t* lik_exp, const pg_record_plan* plan,
+                                         pg_call* out) {
+    const uint32_t V = n_variants;
+    if (V && (!allele_off || !allele_id || !kept || !allele_present || allele_off[0] != 0)) return PG_ERR_INVALID;
+    std::vector<uint64_t> goff((size_t)V + 1, 0);
+    for (uint32_t v = 0; v < V; ++v) {
+        if (allele_off[v + 1] <= allele_off[v] || allele_off[v + 1] - allele_off[v] > PG_MAX_ALLELES_PER_VARIANT) return PG_ERR_INVALID;
+        const uint64_t A = allele_off[v + 1] - allele_off[v];
+        goff[v + 1] = goff[v] + A * (A + 1) / 2;
+    }
+    RecordPlanHost h;
+    int rc = check_record_plan(plan, V, &h, nullptr, 0);
+    if (rc == PG_OK && V) rc = check_record_plan_ids(h, allele_off, allele_id, nullptr, 0);
+    if (rc != PG_OK) return rc;
+    if (V == 0) return PG_OK;
+    if (!out) return PG_ERR_INVALID;
+    const uint64_t n_lik = goff[V], sumA = allele_off[V];
+    if (n_lik && (!lik || !lik_exp)) return PG_ERR_INVALID;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); return PG_ERR_DEVICE; }
+    if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return PG_ERR_DEVICE;
+    const uint64_t* d_tm = nullptr;
+    const int32_t* d_te = nullptr;
+    rc = gq_table_on(device, &d_tm, &d_te, nullptr, 0);
+    if (rc != PG_OK) return rc;
+    RcallsLaunch L;
+    plan_rcalls(1, [&](uint32_t) -> const RecordPlanHost* { return &h; }, [&](uint32_t) { return allele_off; }, &L);
+    // one device buffer: every array at a 256-byte boundary
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += align_up(bytes + 8); return at; };
+    const size_t o_contig = take(sizeof(DevContig)), o_desc = take(sizeof(RCallsDesc)), o_wide = take(L.wide.size() * 4), o_aoff = take(((size_t)V + 1) * 4),
+                 o_aid = take(sumA * 2), o_kept = take(V), o_pres = take(sumA), o_goff = take(((size_t)V + 1) * 8), o_lik = take(n_lik * 8),
+                 o_exp = take(n_lik * 4), o_plan = take(record_plan_device_bytes(h)), o_stage = take((size_t)L.n_slots * L.stride * 16),
+                 o_out = take((size_t)h.R * sizeof(pg_call));
+    unsigned char* d = nullptr;
+    if (hipMalloc((void**)&d, o) != hipSuccess) { (void)hipGetLastError(); return PG_ERR_NOMEM; }
+    DevContig dc;
+    memset(&dc, 0, sizeof(dc));
+    dc.V = V;
+    dc.allele_off = (const uint32_t*)(d + o_aoff);
+    dc.allele_id = (const uint16_t*)(d + o_aid);
+    dc.kept = d + o_kept;
+    dc.allele_present = d + o_pres;
+    dc.geno_off = (const uint64_t*)(d + o_goff);
+    dc.lik = (double*)(d + o_lik);
+    dc.lik_exp = (int32_t*)(d + o_exp);
+    bool ok = record_plan_upload(h, d + o_plan, &L.desc[0].plan);
+    L.desc[0].out = d + o_out;
+    ok = ok && hipMemcpy(d + o_contig, &dc, sizeof(dc), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + o_desc, L.desc.data(), sizeof(RCallsDesc), hipMemcpyHostToDevice) == hipSuccess &&
+         (L.wide.empty() || hipMemcpy(d + o_wide, L.wide.data(), L.wide.size() * 4, hipMemcpyHostToDevice) == hipSuccess) &&
+         hipMemcpy(d + o_aoff, allele_off, ((size_t)V + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + o_aid, allele_id, sumA * 2, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + o_kept, kept, V, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + o_pres, allele_present, sumA, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + o_goff, goff.data(), ((size_t)V + 1) * 8, hipMemcpyHostToDevice) == hipSuccess &&
+         (n_lik == 0 || (hipMemcpy(d + o_lik, lik, n_lik * 8, hipMemcpyHostToDevice) == hipSuccess &&
+                         hipMemcpy(d + o_exp, lik_exp, n_lik * 4, hipMemcpyHostToDevice) == hipSuccess));
+    if (ok) {
+        pgk_launch_rcalls((const DevContig*)(d + o_contig), (const RCallsDesc*)(d + o_desc), 1, L.n_blocks, d + o_wide, (uint32_t)(L.wide.size() / 2),
+                          d + o_stage, L.max_bins, L.stride, L.n_slots, d_tm, d_te, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
+             hipMemcpy(out, d + o_out, (size_t)h.R * sizeof(pg_call), hipMemcpyDeviceToHost) == hipSuccess;
     }
     hipFree(d);
     return ok ? PG_OK : PG_ERR_DEVICE;

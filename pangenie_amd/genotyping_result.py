@@ -119,6 +119,33 @@ class GenotypingResult:
         return self.local_coverage
 
 
+def fold_onto_record(result: "GenotypingResult", own: Sequence[int]) -> "GenotypingResult":
+    """One record's share of a merged bubble (Variant::separate_variants, reference src/variant.cpp:357-384): every genotype
+    of the bubble's NORMALISED result, in map order, is added onto the genotype of the record alleles its two bubble alleles
+    carry (own[id] = allele_combinations[id][record])."""
+    res = GenotypingResult()
+    res.local_coverage, res.unique_kmers = result.local_coverage, result.unique_kmers
+    for (a, b), l in sorted(result.genotype_to_likelihood.items()):
+        res.add_to_likelihood(int(own[a]), int(own[b]), l)
+    return res
+
+
+def record_call(result: "GenotypingResult", own: Sequence[int], vcf_index: Sequence[int]):
+    """(GT or None, GQ) of one record as Graph::write_genotypes prints them (reference src/graph.cpp:217-273): fold, an empty
+    map becomes 0/0 with likelihood 1, get_specific_likelihoods if the record has undefined alleles, likeliest genotype and
+    quality.  `result` must be normalised; vcf_index[a] = 0xFFFF for a record allele of undefined sequence."""
+    f = fold_onto_record(result, own)
+    if f.contains_no_likelihoods():
+        f.add_to_likelihood(0, 0, 1.0)
+    defined = [a for a, x in enumerate(vcf_index) if int(x) != 0xFFFF]
+    gl = f.get_specific_likelihoods(defined) if len(defined) < len(vcf_index) else f
+    g = gl.get_likeliest_genotype()
+    if g[0] == -1:
+        return None, None
+    prob_wrong = LD(1) - gl.get_genotype_likelihood(*g)   # get_genotype_quality without its "must be normalised" exception
+    return g, (int(-10 * np.log10(prob_wrong)) if prob_wrong > 0.0 else 10000)
+
+
 def vcf_sample_field(result: "GenotypingResult", defined_alleles: Sequence[int], nr_alleles: int, ignore_imputed: bool = False) -> str:
     """`GT:GQ:GL:KC` of one record as Graph::write_genotypes prints it (reference src/graph.cpp:217-273);
     mirror of pangenie::genotype_field (pangenie_amd/host/pangenie_host.hpp).  `result` must be normalised."""

@@ -388,6 +388,23 @@ class Job:
         """elapsed ms of the kernels of the last calls()"""
         return float(self._lib.pg_job_calls_ms(self.h))
 
+    def record_plan(self, contig: int, plan) -> None:
+        """pg_job_record_plan: checks and uploads the record plan (calls.RecordPlan) of INDEX contig `contig`; every chain
+        over that contig shares it, a second plan replaces the first."""
+        from . import calls as _calls
+        _calls.job_record_plan(self, contig, plan)
+
+    def record_calls(self, contig: Optional[int] = None):
+        """pg_job_record_calls + pg_job_fetch_record_calls[_all]: GT and GQ per VCF RECORD formed on the device (DESIGN.md 4e
+        "Records").  Returns one record array (calls.CALL_DTYPE) per chain — empty for a chain whose index contig has no
+        plan — or chain `contig`'s alone."""
+        from . import calls as _calls
+        return _calls.job_record_calls(self, contig)
+
+    def record_calls_ms(self) -> float:
+        """elapsed ms of the kernels of the last record_calls()"""
+        return float(self._lib.pg_job_record_calls_ms(self.h))
+
     def viterbi_ms(self) -> float:
         """elapsed ms of the Viterbi kernels (run_phasing) of the last run"""
         return float(self._lib.pg_job_viterbi_ms(self.h))

@@ -371,6 +371,46 @@ std::string Graph::reference(const std::string& name) const {
     throw std::runtime_error("Graph::reference: no sequence named " + name);
 }
 
+// ------------------------------------------------------------------ record plan
+RecordPlan Graph::record_plan() const {
+    if (variants_deleted_) throw std::runtime_error("Graph::record_plan: variants have been deleted by delete_variant funtion. Re-build object.");
+    RecordPlan p;
+    p.rec_off.push_back(0); p.map_off.push_back(0); p.vcf_off.push_back(0);
+    for (size_t i = 0; i < size(); ++i) {
+        const Variant& v = get_variant(i);
+        const size_t n_records = v.allele_sequences_.size();
+        for (size_t r = 0; r < n_records; ++r) {
+            for (const std::vector<unsigned short>& combo : v.allele_combinations_) {
+                if (combo.size() != n_records) throw std::runtime_error("Variant: allele combination of the wrong length");
+                p.map.push_back(combo[r]);
+            }
+            p.map_off.push_back((uint32_t)p.map.size());
+            uint16_t defined = 0;
+            for (size_t a = 0; a < v.allele_sequences_[r].size(); ++a) {
+                const bool undefined = a > 0 && v.allele_sequences_[r][a].contains_undefined();   // (REF is written whatever it holds)
+                p.vcf_index.push_back(undefined ? (uint16_t)0xFFFF : defined);
+                if (!undefined) ++defined;
+            }
+            p.n_alleles.push_back((uint16_t)v.allele_sequences_[r].size());
+            p.vcf_off.push_back((uint32_t)p.vcf_index.size());
+        }
+        p.rec_off.push_back((uint32_t)p.n_alleles.size());
+    }
+    return p;
+}
+
+pg_record_plan RecordPlan::view() const {
+    static const uint16_t none = 0;
+    pg_record_plan c{};
+    c.n_variants = (uint32_t)(rec_off.empty() ? 0 : rec_off.size() - 1);
+    c.n_records = (uint32_t)n_alleles.size();
+    c.rec_off = rec_off.data(); c.map_off = map_off.data(); c.vcf_off = vcf_off.data();
+    c.map = map.empty() ? &none : map.data();
+    c.n_alleles = n_alleles.empty() ? &none : n_alleles.data();
+    c.vcf_index = vcf_index.empty() ? &none : vcf_index.data();
+    return c;
+}
+
 // ------------------------------------------------------------------ VCF text
 std::vector<std::string> Graph::genotypes_header(const std::string& sample, const std::string& date) {
     std::string d = date;

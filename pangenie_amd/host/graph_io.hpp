@@ -21,6 +21,7 @@
 #pragma once
 
 #include <cstdint>
+#include <map>
 #include <memory>
 #include <string>
 #include <utility>
@@ -69,6 +70,19 @@ struct VcfSite {
 struct SampledPanel {
     std::vector<unsigned short> path_to_allele;
     size_t unique_kmers = 0;
+};
+
+/** What the bubbles of a graph mean for their single VCF records, flat: the C ABI's pg_record_plan (include/pangenie_hmm.h,
+ *  DESIGN.md 4e "Records").  Bubble v owns the records rec_off[v] .. rec_off[v + 1] - 1 (graph order: the order of
+ *  Graph::genotypes_records); per record r: map[map_off[r] + id] = the record allele that bubble allele id carries
+ *  (Variant's allele_combinations[id][r]), n_alleles[r], and for every record allele its index among the record's defined
+ *  alleles (vcf_index[vcf_off[r] + a]; 0xFFFF: the allele's sequence is undefined). */
+struct RecordPlan {
+    std::vector<uint32_t> rec_off, map_off, vcf_off;
+    std::vector<uint16_t> map, n_alleles, vcf_index;
+    size_t nr_of_records() const { return n_alleles.size(); }
+    /** the C view; valid as long as this object is */
+    pg_record_plan view() const;
 };
 
 /** A variant bubble of the graph: one or several VCF records closer than the k-mer size, merged
@@ -136,6 +150,8 @@ public:
     const std::vector<std::vector<std::string>>& variant_ids() const { return variant_ids_; }
     /** reference sequence the graph was built on */
     std::string reference(const std::string& name) const;
+    /** the record plan of this graph's bubbles (depends on the index alone: one per chromosome, shared by all samples) */
+    RecordPlan record_plan() const;
 
     /** the header lines of a genotyped VCF (reference src/graph.cpp:137-149); `date` = yyyymmdd, today when empty */
     static std::vector<std::string> genotypes_header(const std::string& sample, const std::string& date = "");
@@ -170,5 +186,16 @@ private:
     std::vector<std::shared_ptr<Variant>> variants_;
     std::vector<std::vector<std::string>> variant_ids_;
 };
+
+/** genotype_cohort_calls per VCF RECORD: the arguments of genotype_cohort_calls plus the chromosomes' graphs.  Per sample and
+ *  chromosome one GenotypeCall per single record, in Graph::genotypes_records order, holding what the GT and GQ columns of
+ *  that line say: allele_1 / allele_2 are indices among the record's DEFINED alleles, -1 / -1 and quality 0 for `.`.  The
+ *  records are formed on the device (C ABI pg_job_record_plan / pg_job_record_calls; one plan per chromosome, uploaded once);
+ *  the records of a bubble the device deferred are formed here from that bubble's bins through Variant::records and
+ *  genotype_field's rules.  `ignore_imputed`: a bubble without unique k-mers gives no call. */
+std::vector<std::map<std::string, std::vector<GenotypeCall>>> genotype_cohort_record_calls(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false,
+    long double effective_N = 25000.0L, int device = 0, bool ignore_imputed = false);
 
 }  // namespace pangenie

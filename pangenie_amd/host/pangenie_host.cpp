@@ -1,6 +1,7 @@
 // pangenie_host.cpp — see pangenie_host.hpp.  Host containers + the HMM adapter over the C ABI.
 #include "pangenie_host.hpp"
 #include "kmer_counts.hpp"
+#include "graph_io.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -823,6 +824,135 @@ std::vector<std::map<std::string, std::vector<GenotypeCall>>> genotype_cohort_ca
                     calls[v].allele_1 = g.first; calls[v].allele_2 = g.second;
                     calls[v].quality = full[v].get_genotype_quality((unsigned short)g.first, (unsigned short)g.second);
                 }
+            }
+        }
+    pg_job_destroy(job);
+    check_rc(rc, err);
+    return out;
+}
+
+// ------------------------------------------------------------------ cohort job, calls per VCF record
+// GT and GQ of one record as genotype_field prints them (graph.cpp:217-273), without the text
+static GenotypeCall record_call_on_host(const VcfSite& site) {
+    GenotypingResult tmp = site.likelihoods;
+    if (tmp.contains_no_likelihoods()) tmp.add_to_likelihood(0, 0, 1.0);
+    std::vector<unsigned short> defined = {0};
+    for (size_t a = 1; a < site.alleles.size(); ++a)
+        if (!site.undefined[a]) defined.push_back((unsigned short)a);
+    const GenotypingResult gl = defined.size() < site.alleles.size() ? tmp.get_specific_likelihoods(defined) : tmp;
+    GenotypeCall call;
+    call.deferred = true;
+    const std::pair<int, int> g = gl.get_likeliest_genotype();
+    if (g.first >= 0 && g.second >= 0) {
+        call.allele_1 = g.first; call.allele_2 = g.second;
+        call.quality = gl.get_genotype_quality((unsigned short)g.first, (unsigned short)g.second);
+    }
+    return call;
+}
+
+std::vector<std::map<std::string, std::vector<GenotypeCall>>> genotype_cohort_record_calls(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device,
+    bool ignore_imputed) {
+    const size_t C = chromosomes.size(), S = samples.size();
+    std::vector<std::map<std::string, std::vector<GenotypeCall>>> out(S);
+    if (C == 0 || S == 0) return out;
+    // (the job is made exactly as genotype_cohort makes it)
+    std::vector<std::string> names;
+    std::vector<FlatContig> flat(C);
+    std::vector<std::vector<uint64_t>> goff(C);
+    std::vector<pg_contig_batch> index(C);
+    std::vector<RecordPlan> plans(C);
+    std::vector<const Graph*> graph_of(C, nullptr);
+    std::vector<char> any_column(C, 0);   // (results_of_chain: a chain without a kept column reports no unique k-mers)
+    size_t c = 0;
+    for (auto& kv : chromosomes) {
+        names.push_back(kv.first);
+        flatten(&kv.second, nullptr, flat[c]);
+        goff[c].assign(flat[c].variant_pos.size() + 1, 0);
+        pg_hmm_geno_offsets(&flat[c].batch, goff[c].data());
+        index[c] = flat[c].batch;
+        const auto g = graphs.find(kv.first);
+        if (g == graphs.end() || g->second.size() != kv.second.size()) fail("genotype_cohort_record_calls: no graph of " + kv.first + " with the index's bubbles");
+        graph_of[c] = &g->second;
+        plans[c] = g->second.record_plan();
+        const FlatContig& f = flat[c];
+        const size_t H = f.paths.size();
+        for (size_t v = 0; v < f.variant_pos.size() && !any_column[c]; ++v)
+            for (size_t p = 0; p < H && !any_column[c]; ++p) {
+                const uint16_t a = f.path_allele[v * H + p];
+                for (uint32_t q = f.allele_off[v]; q < f.allele_off[v + 1]; ++q)
+                    if (f.allele_id[q] == a && a != 0 && !(f.allele_flags[q] & 1)) any_column[c] = 1;
+            }
+        c += 1;
+    }
+    static const uint16_t none = 0;
+    std::vector<std::vector<const uint16_t*>> count_rows(S, std::vector<const uint16_t*>(C)), cov_rows(S, std::vector<const uint16_t*>(C));
+    std::vector<pg_sample_counts> rows(S);
+    for (size_t s = 0; s < S; ++s) {
+        for (c = 0; c < C; ++c) {
+            const auto k = samples[s].kmer_count.find(names[c]), v = samples[s].coverage.find(names[c]);
+            if (k == samples[s].kmer_count.end() || v == samples[s].coverage.end() || k->second.size() != flat[c].kmer_count.size() ||
+                v->second.size() != flat[c].variant_pos.size())
+                fail("genotype_cohort_record_calls: sample " + std::to_string(s) + " does not fit the index on " + names[c]);
+            count_rows[s][c] = k->second.empty() ? &none : k->second.data();
+            cov_rows[s][c] = v->second.empty() ? &none : v->second.data();
+        }
+        rows[s].kmer_count = count_rows[s].data();
+        rows[s].coverage = cov_rows[s].data();
+    }
+    pg_hmm_params prm{};
+    prm.effective_N = effective_N; prm.recombrate = recombrate; prm.uniform = uniform ? 1 : 0; prm.run_genotyping = 1;
+    char err[512] = {0};
+    pg_job* job = nullptr;
+    int rc = pg_cohort_new(device, (uint32_t)C, index.data(), (uint32_t)S, rows.data(), probabilities->handle(), &prm, &job, err, sizeof(err));
+    for (c = 0; c < C && rc == PG_OK; ++c) {   // one plan per chromosome, whatever the number of samples
+        const pg_record_plan view = plans[c].view();
+        rc = pg_job_record_plan(job, (uint32_t)c, &view, err, sizeof(err));
+    }
+    if (rc == PG_OK) rc = pg_job_run(job, nullptr, err, sizeof(err));
+    if (rc == PG_OK) rc = pg_job_record_calls(job, err, sizeof(err));
+    if (rc != PG_OK) { if (job) pg_job_destroy(job); check_rc(rc, err); }
+    // all records with one synchronisation
+    std::vector<std::vector<pg_call>> recs(S * C);
+    std::vector<pg_call*> ptrs(S * C, nullptr);
+    for (size_t i = 0; i < S * C; ++i) {
+        recs[i].resize(plans[i % C].nr_of_records());
+        ptrs[i] = recs[i].empty() ? nullptr : recs[i].data();
+    }
+    rc = pg_job_fetch_record_calls_all(job, ptrs.data(), err, sizeof(err));
+    for (size_t s = 0; s < S && rc == PG_OK; ++s)
+        for (c = 0; c < C && rc == PG_OK; ++c) {
+            const std::vector<pg_call>& r = recs[s * C + c];   // chain id = sample * n_contigs + contig
+            const RecordPlan& plan = plans[c];
+            const FlatContig& f = flat[c];
+            std::vector<GenotypeCall>& calls = out[s][names[c]];
+            calls.resize(r.size());
+            bool any_deferred = false;
+            for (size_t v = 0; v + 1 < plan.rec_off.size(); ++v) {
+                const bool imputed = ignore_imputed && (!any_column[c] || f.kmer_off[v + 1] == f.kmer_off[v]);
+                for (size_t q = plan.rec_off[v]; q < plan.rec_off[v + 1]; ++q) {
+                    if (imputed) continue;   // `.`: genotype_field drops the genotype of a bubble without unique k-mers
+                    if ((r[q].flags & 0xFF) == PG_CALL_OK) { calls[q].allele_1 = r[q].allele_1; calls[q].allele_2 = r[q].allele_2; calls[q].quality = r[q].gq; }
+                    else if (r[q].flags == PG_CALL_DEFERRED) any_deferred = true;
+                }
+            }
+            if (!any_deferred) continue;
+            // the deferred bubbles of this chain on the host, each from its own bins, through Variant::records
+            const uint64_t n = goff[c].back();
+            std::vector<double> lik(n ? n : 1);
+            std::vector<int32_t> lexp(n ? n : 1);
+            pg_contig_result res{};
+            res.lik = lik.data(); res.lik_exp = lexp.data();
+            rc = pg_job_fetch(job, (uint32_t)(s * C + c), &res, err, sizeof(err));
+            if (rc != PG_OK) break;
+            std::vector<GenotypingResult> full = results_of_chain(f, cov_rows[s][c], goff[c], lik.data(), lexp.data());
+            for (size_t v = 0; v + 1 < plan.rec_off.size(); ++v) {
+                if (r[plan.rec_off[v]].flags != PG_CALL_DEFERRED) continue;   // (a bubble is deferred with all its records)
+                if (ignore_imputed && full[v].nr_unique_kmers() == 0) continue;
+                full[v].normalize();
+                const std::vector<VcfSite> sites = graph_of[c]->get_variant(v).records(&full[v]);
+                for (size_t k = 0; k < sites.size() && plan.rec_off[v] + k < plan.rec_off[v + 1]; ++k) calls[plan.rec_off[v] + k] = record_call_on_host(sites[k]);
             }
         }
     pg_job_destroy(job);
