@@ -437,6 +437,52 @@ int  pg_record_calls_from_bins(int device, uint32_t n_variants, const uint32_t* 
                                const uint8_t* kept, const uint8_t* allele_present, const double* lik,
                                const int32_t* lik_exp, const pg_record_plan* plan, pg_call* out);
 
+/* ------------------------------------------------------------------ *
+ *  The GL column per VCF RECORD: log10 of the likelihood of every genotype over the record's
+ *  defined alleles, as Graph::write_genotypes prints it (reference src/graph.cpp:243-274) — after the fold onto
+ *  the record's alleles and get_specific_likelihoods, `setprecision(4) << log10(likelihood)`.  A value is what the
+ *  text shows: the four significant decimal digits of log10l(L).  The likelihood is formed in the integer
+ *  arithmetic of pg_job_record_calls; the logarithm is fp64 with a stated error bound, and a value whose fourth
+ *  digit that error could change is PG_GL_DEFERRED (about 2e-9 of all values).  With pg_job_record_calls, no bin
+ *  has to leave the device to write a sample's VCF lines.
+ * ------------------------------------------------------------------ */
+#ifndef PG_GL_DEFINED /* (the same in pangenie_amd/csrc/pg_calls.h) */
+#define PG_GL_DEFINED
+typedef struct pg_gl { int16_t mant; int16_t exp10; } pg_gl;
+/* mant in +-[1000, 9999]: log10(L) = mant * 10^(exp10 - 3), the four digits "%.4Lg" prints; the sign of mant is the log's */
+/* mant == 0 && exp10 == 0 : L == 1 exactly, prints "0"                                                                 */
+#define PG_GL_NEG_INF  (-32768) /* in exp10 (mant 0): L == 0 or no such key, prints "-inf"                               */
+#define PG_GL_DEFERRED (-32767) /* in exp10 (mant 0): not decided on the device, form it on the host from the bins       */
+#endif
+/* gl_off[R + 1]: record r with nd defined alleles owns the nd (nd + 1) / 2 values gl_off[r] .. gl_off[r + 1] - 1 of a
+ * chain, genotype (a <= b) over defined-allele indices at b (b + 1) / 2 + a (the VCF's order).  Host only; the offsets
+ * depend on the plan alone.  PG_ERR_INVALID / PG_ERR_UNSUPPORTED: null arguments, or a plan pg_job_record_plan refuses. */
+int  pg_record_gl_offsets(const pg_record_plan* plan, uint64_t* gl_off);
+/* Forms the GL values of every chain whose index contig has a plan (a chain without one is left out), on the job's
+ * stream; blocking.  The buffer (4 bytes x the values of all chains) is allocated by the first call, outside the
+ * arena, and freed by pg_job_destroy (PG_ERR_NOMEM if it does not fit).  Refusals as pg_job_record_calls.  Every
+ * value of a bubble whose largest bin lies below 2^-16300 is PG_GL_DEFERRED, as is a nonzero likelihood below it. */
+int  pg_job_record_gl(pg_job* job, char* err, size_t errlen);
+/* Chain `chain`'s values, out[gl_off[R]] (after pg_job_record_gl); nothing for a chain without a plan. */
+int  pg_job_fetch_record_gl(pg_job* job, uint32_t chain, pg_gl* out, char* err, size_t errlen);
+/* The same for all chains, outs[n_chains] (NULL allowed where a chain has no values): one synchronisation. */
+int  pg_job_fetch_record_gl_all(pg_job* job, pg_gl* const* outs, char* err, size_t errlen);
+/* Device-resident values of chain `chain`: pg_gl [n] (n = 0 for a chain without a plan). */
+int  pg_job_device_record_gl(pg_job* job, uint32_t chain, void** d_gl, uint64_t* n);
+/* Elapsed milliseconds of the kernels of the LAST pg_job_record_gl. */
+double pg_job_record_gl_ms(const pg_job* job);
+/* Unit entry point: the GL values of the plan's records from host arrays (as pg_record_calls_from_bins), through the
+ * same kernels; out[gl_off[R]].  The plan is checked first; then PG_ERR_DEVICE without a device: no host fallback. */
+int  pg_record_gl_from_bins(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id,
+                            const uint8_t* kept, const uint8_t* allele_present, const double* lik,
+                            const int32_t* lik_exp, const pg_record_plan* plan, pg_gl* out);
+/* Unit entry point of the digits alone: out[i] = the GL of the likelihood m[i] * 2^e[i] (m[i] in [2^63, 2^64), or 0
+ * with e[i] == 0: PG_ERR_INVALID otherwise), by the device's own log10 / log1p.  PG_ERR_DEVICE without a device. */
+int  pg_gl_from_values(int device, uint64_t n, const uint64_t* m, const int32_t* e, pg_gl* out);
+/* Host only: the text `ostream << setprecision(4)` gives of the value ("%.4g" of the decimal; "-inf"; "0"), its
+ * length; -1 for PG_GL_DEFERRED, an encoding that is none of the above, or a buffer too small (32 bytes suffice). */
+int  pg_gl_text(pg_gl value, char* buf, size_t len);
+
 #ifdef __cplusplus
 }
 #endif

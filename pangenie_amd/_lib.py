@@ -97,6 +97,10 @@ class PgSampleCounts(C.Structure):
     ]
 
 
+class PgGl(C.Structure):
+    _fields_ = [("mant", C.c_int16), ("exp10", C.c_int16)]
+
+
 PG_CALL_ANNOUNCED = 1
 
 
@@ -252,6 +256,25 @@ def _bind_hip(lib):
     lib.pg_job_record_calls_ms.restype = C.c_double
     lib.pg_record_calls_from_bins.argtypes = [C.c_int, C.c_uint32, u32p, u16p, u8p, u8p, f64p, i32p, C.c_void_p, C.c_void_p]
     lib.pg_record_calls_from_bins.restype = C.c_int
+    # the GL column per VCF record (pangenie_amd/calls.py); values are read as numpy arrays of GL_DTYPE, pg_gl_text takes a PgGl by value
+    lib.pg_record_gl_offsets.argtypes = [C.c_void_p, u64p]
+    lib.pg_record_gl_offsets.restype = C.c_int
+    lib.pg_job_record_gl.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_record_gl.restype = C.c_int
+    lib.pg_job_fetch_record_gl.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_fetch_record_gl.restype = C.c_int
+    lib.pg_job_fetch_record_gl_all.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+    lib.pg_job_fetch_record_gl_all.restype = C.c_int
+    lib.pg_job_device_record_gl.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), u64p]
+    lib.pg_job_device_record_gl.restype = C.c_int
+    lib.pg_job_record_gl_ms.argtypes = [C.c_void_p]
+    lib.pg_job_record_gl_ms.restype = C.c_double
+    lib.pg_record_gl_from_bins.argtypes = [C.c_int, C.c_uint32, u32p, u16p, u8p, u8p, f64p, i32p, C.c_void_p, C.c_void_p]
+    lib.pg_record_gl_from_bins.restype = C.c_int
+    lib.pg_gl_from_values.argtypes = [C.c_int, C.c_uint64, u64p, i32p, C.c_void_p]
+    lib.pg_gl_from_values.restype = C.c_int
+    lib.pg_gl_text.argtypes = [PgGl, C.c_char_p, C.c_size_t]
+    lib.pg_gl_text.restype = C.c_int
     return lib
 
 
@@ -270,6 +293,8 @@ HIP_ABI_SYMBOLS = [
     "pg_job_calls", "pg_job_fetch_calls", "pg_job_fetch_calls_all", "pg_job_device_calls", "pg_job_calls_ms", "pg_calls_from_bins",
     "pg_job_record_plan", "pg_job_record_calls", "pg_job_fetch_record_calls", "pg_job_fetch_record_calls_all", "pg_job_device_record_calls",
     "pg_job_record_calls_ms", "pg_record_calls_from_bins",
+    "pg_record_gl_offsets", "pg_job_record_gl", "pg_job_fetch_record_gl", "pg_job_fetch_record_gl_all", "pg_job_device_record_gl",
+    "pg_job_record_gl_ms", "pg_record_gl_from_bins", "pg_gl_from_values", "pg_gl_text",
     "pg_sparse_segment", "pg_sparse_stored_by_chain",
 ]
 

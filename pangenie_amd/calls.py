@@ -209,3 +209,118 @@ def record_calls_from_bins(allele_off, allele_id, kept, allele_present, lik, lik
     if rc:
         raise _error(rc, None)
     return out[:plan.n_records]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+#  The GL column per VCF record (pg_job_record_gl, pg_record_gl_from_bins, pg_gl_from_values, pg_gl_text)
+# ---------------------------------------------------------------------------------------------------------------
+GL_DTYPE = np.dtype([("mant", "<i2"), ("exp10", "<i2")])
+PG_GL_NEG_INF = -32768   # in exp10 (mant 0): likelihood 0 or no such key, prints "-inf"
+PG_GL_DEFERRED = -32767  # in exp10 (mant 0): not decided on the device, to be formed on the host from the bins
+
+
+def record_gl_offsets(plan: RecordPlan) -> np.ndarray:
+    """pg_record_gl_offsets: gl_off [R + 1]; record r owns the values gl_off[r] .. gl_off[r + 1] - 1 of a chain, genotype
+    (a <= b) over its defined alleles at b (b + 1) / 2 + a.  Host only."""
+    lib = _lib.load_hip()
+    off = np.zeros(plan.n_records + 1, np.uint64)
+    c = plan.as_c()
+    rc = lib.pg_record_gl_offsets(C.addressof(c), off.ctypes.data_as(_lib.u64p))
+    if rc:
+        raise _error(rc, None)
+    return off
+
+
+def _n_gl(job) -> List[int]:
+    plans, nc = getattr(job, "_record_plans", {}), len(job.index)
+    cache = job.__dict__.setdefault("_gl_counts", {})
+    out = []
+    for c in range(len(job.batches)):
+        plan = plans.get(c % nc)
+        if plan is None:
+            out.append(0)
+            continue
+        if cache.get(c % nc, (None, 0))[0] is not plan:
+            cache[c % nc] = (plan, int(record_gl_offsets(plan)[-1]))
+        out.append(cache[c % nc][1])
+    return out
+
+
+def job_record_gl(job, contig: Optional[int] = None):
+    """Job.record_gl(): forms the GL values of every chain that has a plan, fetches all of them (or chain `contig`'s)."""
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_record_gl(job.h, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    if contig is not None:
+        return fetch_record_gl(job, contig)
+    return fetch_record_gl_all(job)
+
+
+def fetch_record_gl(job, contig: int) -> np.ndarray:
+    N = _n_gl(job)[contig]
+    out = np.zeros(max(N, 1), GL_DTYPE)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_record_gl(job.h, contig, out.ctypes.data, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return out[:N]
+
+
+def fetch_record_gl_all(job) -> List[np.ndarray]:
+    Ns = _n_gl(job)
+    outs = [np.zeros(max(N, 1), GL_DTYPE) for N in Ns]
+    arr = (C.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_record_gl_all(job.h, arr, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return [o[:N] for o, N in zip(outs, Ns)]
+
+
+def record_gl_from_bins(allele_off, allele_id, kept, allele_present, lik, lik_exp, plan: RecordPlan, device: int = 0) -> np.ndarray:
+    """pg_record_gl_from_bins: the GL values of the plan's records from host arrays laid out as for calls_from_bins; record
+    r's values at record_gl_offsets(plan)[r] ..."""
+    lib = _lib.load_hip()
+    aoff = np.ascontiguousarray(allele_off, np.uint32)
+    V = len(aoff) - 1
+    pad = lambda a, dt: np.ascontiguousarray(a, dt) if len(a) else np.zeros(1, dt)
+    aid, kp, pres = pad(allele_id, np.uint16), pad(kept, np.uint8), pad(allele_present, np.uint8)
+    lk, le = pad(lik, np.float64), pad(lik_exp, np.int32)
+    A = np.diff(aoff.astype(np.int64))
+    if len(allele_id) != int(aoff[-1]) or len(allele_present) != int(aoff[-1]) or len(kept) != V or len(lik) != int((A * (A + 1) // 2).sum()) \
+            or len(lik_exp) != len(lik):
+        raise ValueError("record_gl_from_bins: array lengths do not match allele_off")
+    N = int(record_gl_offsets(plan)[-1])
+    out = np.zeros(max(N, 1), GL_DTYPE)
+    c = plan.as_c()
+    rc = lib.pg_record_gl_from_bins(device, V, aoff.ctypes.data_as(_lib.u32p), aid.ctypes.data_as(_lib.u16p), kp.ctypes.data_as(_lib.u8p),
+                                    pres.ctypes.data_as(_lib.u8p), lk.ctypes.data_as(_lib.f64p), le.ctypes.data_as(_lib.i32p), C.addressof(c),
+                                    out.ctypes.data)
+    if rc:
+        raise _error(rc, None)
+    return out[:N]
+
+
+def gl_from_values(m, e, device: int = 0) -> np.ndarray:
+    """pg_gl_from_values: the GL of every likelihood m[i] * 2^e[i] (m[i] in [2^63, 2^64), or 0 with e[i] == 0) by the device's
+    own log10 / log1p."""
+    lib = _lib.load_hip()
+    mm, ee = np.ascontiguousarray(m, np.uint64), np.ascontiguousarray(e, np.int32)
+    if mm.shape != ee.shape or mm.ndim != 1:
+        raise ValueError("gl_from_values: m and e must be one-dimensional and of one length")
+    out = np.zeros(max(len(mm), 1), GL_DTYPE)
+    if len(mm):
+        rc = lib.pg_gl_from_values(device, len(mm), mm.ctypes.data_as(_lib.u64p), ee.ctypes.data_as(_lib.i32p), out.ctypes.data)
+        if rc:
+            raise _error(rc, None)
+    return out[:len(mm)]
+
+
+def gl_text(value) -> Optional[str]:
+    """pg_gl_text: what the VCF shows of one value (a GL_DTYPE element or a (mant, exp10) pair); None for PG_GL_DEFERRED and
+    for an encoding that is no value."""
+    lib = _lib.load_hip()
+    buf = C.create_string_buffer(32)
+    n = lib.pg_gl_text(_lib.PgGl(int(value[0]), int(value[1])), buf, 32)
+    return buf.value.decode() if n >= 0 else None

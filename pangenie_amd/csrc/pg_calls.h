@@ -368,6 +368,129 @@ PGX_FN pgx_record_decision pgx_decide_record(Keys& keys, bool has_undefined, Def
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+//  Genotype likelihoods as the VCF prints them (the GL column): four significant decimal digits of
+//  log10l(L), which is what `ostream << setprecision(4)` shows of it.  The likelihood L itself is formed in the integer
+//  pairs above, bit for bit the host's long double; only the logarithm and its digits are fp64.
+//
+//  The route and its error, in units of u = 2^-53 relative to y = |log10 x| (x = m 2^e, E = e + 64):
+//    E == 0   x = 1 - d 2^-64, d = 2^64 - m an exact integer: (double)d 1u, log1p L ulp = 2L u, the division by the rounded
+//             ln 10 1.5u;                                                                                    2.5u + 2L u
+//    E == 1   x = 1 + d 2^-63, the same with the sign of the logarithm positive;                             2.5u + 2L u
+//    E <  0   y = -(E c_hi + (E c_lo + log10(m 2^-64))): E c_hi is exact (15 x 37 bits), both terms are <= 0 so nothing
+//             cancels and every absolute error is relative to y or less: (double)m 1u / ln 10 of the argument = 0.44u
+//             absolute, against y >= log10 2: 1.5u; log10 L ulp = 2L u; E c_lo and the two additions 3u;    4.5u + 2L u
+//    digits   s = (y 10^n1) 10^n2 with n1, n2 <= 12, both powers exact doubles: two products, 2u.
+//  With L = 4 ulp for log10 and log1p (the device compiler's documentation promises fewer: the bound is taken with room)
+//  the relative error of s is below 14.5u < 16u = 1.78e-15, and s < 10^4: |s - exact| < 1.78e-11.  A digit is decided here
+//  only if s is further than PG_GL_WINDOW = 1e-9 from a rounding boundary .5 — 56 times the bound (at least 16 are asked
+//  for) — and is left to the host otherwise (PG_GL_DEFERRED): exact ties included, and about 2e-9 of all values.
+// ---------------------------------------------------------------------------------------------------------------
+#include <math.h>
+
+#ifndef PG_GL_DEFINED   // (the same in include/pangenie_hmm.h)
+#define PG_GL_DEFINED
+typedef struct pg_gl { int16_t mant; int16_t exp10; } pg_gl;
+#define PG_GL_NEG_INF  (-32768)
+#define PG_GL_DEFERRED (-32767)
+#endif
+
+#define PG_GL_WINDOW 1e-9
+#define PGX_LOG10_2_HI 0x1.34413509fp-2          // the first 37 bits of log10 2
+#define PGX_LOG10_2_LO 0x1.e7fbcc47c4acdp-40     // log10 2 - PGX_LOG10_2_HI
+#define PGX_LN_10 0x1.26bb1bbb55516p+1
+
+PGX_FN pg_gl pgx_gl_of(int mant, int exp10) { pg_gl g; g.mant = (int16_t)mant; g.exp10 = (int16_t)exp10; return g; }
+PGX_FN pg_gl pgx_gl_neg_inf() { return pgx_gl_of(0, PG_GL_NEG_INF); }
+PGX_FN pg_gl pgx_gl_deferred() { return pgx_gl_of(0, PG_GL_DEFERRED); }
+PGX_FN bool pgx_gl_is_deferred(pg_gl g) { return g.mant == 0 && g.exp10 == PG_GL_DEFERRED; }
+
+// y * 10^n, 0 <= n <= 24: two products with exact powers of ten
+PGX_FN double pgx_gl_scale(double y, int n) {
+    const int n1 = n < 12 ? n : 12, n2 = n - n1;
+    double p1 = 1.0, p2 = 1.0;
+    for (int i = 0; i < n1; ++i) p1 *= 10.0;
+    for (int i = 0; i < n2; ++i) p2 *= 10.0;
+    return (y * p1) * p2;
+}
+
+// the four digits of log10(x); a nonzero x below 2^PG_CALLS_DEFER_EXP (the host's quotient there would be subnormal or 0)
+// and a value within PG_GL_WINDOW of a rounding boundary are PG_GL_DEFERRED
+PGX_FN pg_gl pgx_gl(pgx x) {
+    if (x.m == 0) return pgx_gl_neg_inf();
+    if (pgx_below_pow2(x, PG_CALLS_DEFER_EXP)) return pgx_gl_deferred();
+    const int32_t E = x.e + 64;
+    if (E == 1 && x.m == PGX_TOP) return pgx_gl_of(0, 0);
+    double y;
+    bool positive = false;
+    if (E == 0) y = -log1p(-((double)(0ull - x.m) * 0x1p-64)) / PGX_LN_10;
+    else if (E == 1) { y = log1p((double)(x.m - PGX_TOP) * 0x1p-63) / PGX_LN_10; positive = true; }
+    else if (E < 0) y = -((double)E * PGX_LOG10_2_HI + ((double)E * PGX_LOG10_2_LO + log10((double)x.m * 0x1p-64)));
+    else return pgx_gl_deferred();   // x >= 2: no likelihood
+    int k = (int)floor(log10(y));
+    double s = 0.0;
+    for (int it = 0; it < 3; ++it) {   // k until s lies in [1000, 10000)
+        if (k > 3 || k < -21) return pgx_gl_deferred();   // (y in [2.3e-20, 4951]: not reached)
+        s = pgx_gl_scale(y, 3 - k);
+        if (s < 1000.0) --k;
+        else if (s >= 10000.0) ++k;
+        else break;
+    }
+    if (!(s >= 1000.0 && s < 10000.0)) return pgx_gl_deferred();
+    const double fl = floor(s), fr = s - fl;
+    if (fabs(fr - 0.5) < PG_GL_WINDOW) return pgx_gl_deferred();
+    int r = (int)fl + (fr > 0.5 ? 1 : 0);
+    if (r == 10000) { r = 1000; ++k; }
+    return pgx_gl_of(positive ? r : -r, k);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+//  One VCF record's GL values from its bubble's bins.  The likelihoods are those of pgx_decide_record: the bubble's sum,
+//  one pgx_div per key, the additions onto one record key in the bubble's order, and for a record with undefined alleles
+//  sum2 over the defined keys in (ra, rb) order and a second pgx_div if sum2 > 0.  The record's defined genotype pairs are
+//  enumerated in (ra, rb) order, each one walk of the bubble's keys (a key nothing folds onto adds 0 to sum2, which changes
+//  no rounding, and reads -inf).  `vcf(a)`: index of record allele a among the defined ones, 0xFFFF if undefined;
+//  `out(i, g)`: value i of the record, genotype (a <= b) over defined-allele indices at b (b + 1) / 2 + a.
+// ---------------------------------------------------------------------------------------------------------------
+template <class Keys, class Vcf, class Out>
+PGX_FN void pgx_record_gl(Keys& keys, uint32_t n_alleles, bool has_undefined, Vcf& vcf, Out& out) {
+    pgx v, sum = pgx_zero(), largest = pgx_zero();
+    uint32_t k, n = 0, nd = 0;
+    for (uint32_t a = 0; a < n_alleles; ++a) nd += vcf(a) != 0xFFFFu ? 1u : 0u;
+    const uint32_t n_values = nd * (nd + 1u) / 2u;
+    keys.start();
+    while (keys.next(&v, &k)) {   // GenotypingResult::normalize of the bubble
+        sum = pgx_add(sum, v);
+        if (pgx_cmp(v, largest) > 0) largest = v;
+        ++n;
+    }
+    if (n == 0 || sum.m == 0 || pgx_below_pow2(largest, PG_CALLS_DEFER_EXP)) {
+        // an empty map: F[(0,0)] = 1; every bin zero: nothing is normalised, every value 0; below the cut: the host's
+        const pg_gl g = (n == 0 || sum.m == 0) ? pgx_gl_neg_inf() : pgx_gl_deferred();
+        for (uint32_t i = 0; i < n_values; ++i) out(i, (n == 0 && i == 0) ? pgx_gl_of(0, 0) : g);
+        return;
+    }
+    uint64_t next;
+    pgx sum2 = pgx_zero();
+    if (has_undefined)   // get_specific_likelihoods: the defined keys of F added in F's order
+        for (uint32_t ra = 0; ra < n_alleles; ++ra) {
+            if (vcf(ra) == 0xFFFFu) continue;
+            for (uint32_t rb = ra; rb < n_alleles; ++rb)
+                if (vcf(rb) != 0xFFFFu) sum2 = pgx_add(sum2, pgx_fold_key(keys, sum, ((uint64_t)ra << 16) | rb, true, &next));
+        }
+    for (uint32_t ra = 0; ra < n_alleles; ++ra) {
+        const uint32_t va = vcf(ra);
+        if (va == 0xFFFFu) continue;
+        for (uint32_t rb = ra; rb < n_alleles; ++rb) {
+            const uint32_t vb = vcf(rb);
+            if (vb == 0xFFFFu) continue;
+            pgx f = pgx_fold_key(keys, sum, ((uint64_t)ra << 16) | rb, true, &next);
+            if (sum2.m != 0) f = pgx_div(f, sum2);
+            out(vb * (vb + 1u) / 2u + va, pgx_gl(f));
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 //  Host only: the pair <-> long double, and the threshold table from log10l itself.
 // ---------------------------------------------------------------------------------------------------------------
 #include <math.h>
@@ -406,4 +529,46 @@ static inline int pgx_build_gq_table(uint64_t* thr_m, int32_t* thr_e) {
         thr_e[k] = t.e;
     }
     return 0;
+}
+
+// The text of a GL value: what `ostream << setprecision(4)` prints of the long double logarithm, i.e. "%.4g" of the decimal
+// mant 10^(exp10 - 3) — "-inf", "0", fixed notation with trailing zeros stripped for exp10 in [-4, 3], else d.ddde-XX.
+// Returns the length, or -1 for PG_GL_DEFERRED, a value that is none, or a buffer too small (32 bytes always suffice).
+static inline int pgx_gl_text(pg_gl g, char* buf, size_t len) {
+    char t[32];
+    int n = 0;
+    if (g.mant == 0) {
+        if (g.exp10 == PG_GL_NEG_INF) { t[0] = '-'; t[1] = 'i'; t[2] = 'n'; t[3] = 'f'; n = 4; }
+        else if (g.exp10 == 0) t[n++] = '0';
+        else return -1;
+    } else {
+        int a = g.mant < 0 ? -(int)g.mant : (int)g.mant;
+        const int X = g.exp10;
+        if (a < 1000 || a > 9999 || X < -99 || X > 99) return -1;
+        char d[4];
+        for (int i = 3; i >= 0; --i) { d[i] = (char)('0' + a % 10); a /= 10; }
+        int nd = 4;
+        while (nd > 1 && d[nd - 1] == '0') --nd;
+        if (g.mant < 0) t[n++] = '-';
+        if (X < -4 || X >= 4) {
+            t[n++] = d[0];
+            if (nd > 1) { t[n++] = '.'; for (int i = 1; i < nd; ++i) t[n++] = d[i]; }
+            t[n++] = 'e';
+            t[n++] = X < 0 ? '-' : '+';
+            const int ax = X < 0 ? -X : X;
+            t[n++] = (char)('0' + ax / 10);
+            t[n++] = (char)('0' + ax % 10);
+        } else if (X >= 0) {
+            for (int i = 0; i <= X; ++i) t[n++] = i < nd ? d[i] : '0';
+            if (nd > X + 1) { t[n++] = '.'; for (int i = X + 1; i < nd; ++i) t[n++] = d[i]; }
+        } else {
+            t[n++] = '0'; t[n++] = '.';
+            for (int i = 0; i < -X - 1; ++i) t[n++] = '0';
+            for (int i = 0; i < nd; ++i) t[n++] = d[i];
+        }
+    }
+    if (!buf || (size_t)n + 1 > len) return -1;
+    for (int i = 0; i < n; ++i) buf[i] = t[i];
+    buf[n] = 0;
+    return n;
 }

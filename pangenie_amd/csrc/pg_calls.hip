@@ -440,7 +440,208 @@ __global__ __launch_bounds__(PCW_BLOCK) void k_rcalls_wide(const DevContig* __re
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+//  The GL column per VCF record: log10 of every genotype's likelihood over the record's defined alleles, as
+//  the four digits the VCF prints (pg_gl, 4 bytes).  The likelihoods are those of the record calls — the same key iterator,
+//  slot packing and staging — and pgx_gl (pg_calls.h) turns each into its digits or leaves it to the host (PG_GL_DEFERRED).
+//
+//   k_rgl        one lane per record of a bubble with at most PG_AMAX alleles: pgx_record_gl walks the bubble's keys once per
+//                defined genotype pair of the record (twice for a record with undefined alleles: first for sum2)
+//   k_rgl_wide   one wave (= one block) per listed record of a wider bubble: quotients and then the folded map in the block's
+//                staging slot as in k_rcalls_wide, sum2 in key order by every lane alike, lane l converts keys l, l + 64, ...
+//   k_gl_values  one lane per (m, e) pair: the unit entry that puts the device's own log10 / log1p under test
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t gl_word(pg_gl g) { return (uint32_t)(uint16_t)g.mant | ((uint32_t)(uint16_t)g.exp10 << 16); }
+
+struct VcfIndexOf {
+    const uint16_t* vcf;   // the record's vcf_index
+    __device__ uint32_t operator()(uint32_t a) const { return vcf[a]; }
+};
+struct GlStore {
+    uint32_t* out;         // the record's values
+    __device__ void operator()(uint32_t i, pg_gl g) const { out[i] = gl_word(g); }
+};
+
+__device__ __forceinline__ uint32_t rgl_chain_of(const RGlDesc* __restrict__ desc, uint32_t n, uint32_t b) {
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (desc[mid].blk0 <= b) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void k_rgl(const DevContig* __restrict__ contigs, const RGlDesc* __restrict__ desc, uint32_t n_desc) {
+    const uint32_t blk = blockIdx.x;
+    const RGlDesc* __restrict__ cd = desc + rgl_chain_of(desc, n_desc, blk);
+    const uint32_t r = (blk - cd->blk0) * PC_BLOCK + threadIdx.x;
+    if (r >= cd->R) return;
+    const DevContig* __restrict__ c = contigs + cd->chain;
+    const uint32_t rv = cd->plan.rec_var[r], v = rv & 0x7FFFFFFFu;
+    const uint32_t a0 = c->allele_off[v];
+    const uint32_t A = c->allele_off[v + 1] - a0;
+    if (A > PG_AMAX) return;   // k_rgl_wide's
+    const uint32_t m0 = cd->plan.map_off[r], n_map = cd->plan.map_off[r + 1] - m0;
+    const uint16_t* __restrict__ map = cd->plan.map + m0;
+    uint32_t present = 0;
+    unsigned long long own = 0;
+    if (c->kept[v])
+        for (uint32_t a = 0; a < A; ++a)
+            if (c->allele_present[a0 + a]) {
+                present |= 1u << a;
+                const uint32_t id = c->allele_id[a0 + a];   // (the host has checked id < n_map; no read outside the map either way)
+                own |= (unsigned long long)(id < n_map ? map[id] & 0xFFu : 0u) << (8u * a);
+            }
+    const uint64_t g0 = c->geno_off[v];
+    NarrowRecordKeys keys;
+    keys.lik = c->lik + g0;
+    keys.lik_exp = c->lik_exp + g0;
+    keys.A = A;
+    keys.present = present;
+    keys.own = own;
+    const uint32_t vcf0 = cd->plan.vcf_off[r];
+    VcfIndexOf vcf;
+    vcf.vcf = cd->plan.vcf_index + vcf0;
+    GlStore store;
+    store.out = (uint32_t*)cd->out + cd->gl_off[r];
+    pgx_record_gl(keys, cd->plan.vcf_off[r + 1] - vcf0, (rv >> 31) != 0u, vcf, store);
+}
+
+__global__ __launch_bounds__(PCW_BLOCK) void k_rgl_wide(const DevContig* __restrict__ contigs, const RGlDesc* __restrict__ desc,
+                                                        const uint2* __restrict__ list, uint32_t n_list, PgxSlot* __restrict__ stage,
+                                                        uint32_t max_bins, uint32_t stride) {
+    __shared__ uint16_t s_own[PG_MAX_ALLELES_PER_VARIANT];   // per slot: its record allele; 0xFFFF: not on a selected path (or not a kept column)
+    const uint32_t lane = threadIdx.x;
+    PgxSlot* __restrict__ Q = stage + (size_t)blockIdx.x * stride;   // [max_bins] the bubble's quotients
+    PgxSlot* __restrict__ F = Q + max_bins;                          // [stride - max_bins] the folded map
+    for (uint32_t entry = blockIdx.x; entry < n_list; entry += gridDim.x) {
+        __syncthreads();   // the previous record's s_own, Q and F are done with
+        const uint2 e = list[entry];   // {descriptor, record}
+        const RGlDesc* __restrict__ cd = desc + e.x;
+        const uint32_t r = e.y;
+        const DevContig* __restrict__ c = contigs + cd->chain;
+        uint32_t* __restrict__ out = (uint32_t*)cd->out + cd->gl_off[r];
+        const uint32_t rv = cd->plan.rec_var[r], v = rv & 0x7FFFFFFFu;
+        const bool undef = (rv >> 31) != 0u;
+        const uint32_t a0 = c->allele_off[v];
+        const uint32_t A = c->allele_off[v + 1] - a0;
+        const uint32_t m0 = cd->plan.map_off[r], n_map = cd->plan.map_off[r + 1] - m0;
+        const uint16_t* __restrict__ map = cd->plan.map + m0;
+        const uint32_t vcf0 = cd->plan.vcf_off[r], nA = cd->plan.vcf_off[r + 1] - vcf0;
+        const uint16_t* __restrict__ vcf = cd->plan.vcf_index + vcf0;
+        const uint32_t K = nA * (nA + 1u) / 2u;
+        const uint64_t g0 = c->geno_off[v];
+        const double* __restrict__ lik = c->lik + g0;
+        const int32_t* __restrict__ lik_exp = c->lik_exp + g0;
+        const bool kept = c->kept[v] != 0;
+        for (uint32_t a = lane; a < A; a += PCW_BLOCK) {
+            const uint32_t id = c->allele_id[a0 + a];   // (the host has checked id < n_map; no read outside the map either way)
+            s_own[a] = (kept && c->allele_present[a0 + a]) ? (id < n_map ? map[id] : (uint16_t)0u) : (uint16_t)0xFFFFu;
+        }
+        __syncthreads();
+        uint32_t nd = 0;
+        for (uint32_t a = 0; a < nA; ++a) nd += vcf[a] != 0xFFFFu ? 1u : 0u;
+        const uint32_t n_values = nd * (nd + 1u) / 2u;
+        // the bubble's sum, key after key in the map's order, by every lane alike
+        pgx sum = pgx_zero(), largest = pgx_zero();
+        uint32_t n_keys = 0;
+        {
+            uint32_t bin = 0;
+            for (uint32_t a = 0; a < A; ++a) {
+                if (s_own[a] == 0xFFFFu) { bin += A - a; continue; }
+                for (uint32_t b = a; b < A; ++b, ++bin) {
+                    if (s_own[b] == 0xFFFFu) continue;
+                    const pgx x = pgx_from_bin(lik[bin], lik_exp[bin]);
+                    sum = pgx_add(sum, x);
+                    if (pgx_cmp(x, largest) > 0) largest = x;
+                    ++n_keys;
+                }
+            }
+        }
+        if (n_keys == 0 || sum.m == 0 || pgx_below_pow2(largest, PG_CALLS_DEFER_EXP)) {   // (the same on every lane)
+            const uint32_t g = gl_word((n_keys == 0 || sum.m == 0) ? pgx_gl_neg_inf() : pgx_gl_deferred());
+            for (uint32_t i = lane; i < n_values; i += PCW_BLOCK) out[i] = (n_keys == 0 && i == 0) ? gl_word(pgx_gl_of(0, 0)) : g;
+            continue;
+        }
+        // the quotients: lane l takes the keys (a, a + l), (a, a + l + 64), ... of every row a
+        {
+            uint32_t row = 0;
+            for (uint32_t a = 0; a < A; ++a) {
+                if (s_own[a] != 0xFFFFu)
+                    for (uint32_t b = a + lane; b < A; b += PCW_BLOCK) {
+                        if (s_own[b] == 0xFFFFu) continue;
+                        const uint32_t bin = row + (b - a);
+                        slot_put(Q + bin, pgx_div(pgx_from_bin(lik[bin], lik_exp[bin]), sum));
+                    }
+                row += A - a;
+            }
+        }
+        __syncthreads();
+        // the fold: key (ra, rb) receives the keys (a, b) whose slots carry ra and rb, in the bubble's order
+        for (uint32_t k = lane; k < K; k += PCW_BLOCK) {
+            uint32_t ra = 0, rest = k;
+            while (rest >= nA - ra) { rest -= nA - ra; ++ra; }
+            const uint32_t rb = ra + rest;
+            pgx acc = pgx_zero();
+            uint32_t row = 0;
+            for (uint32_t a = 0; a < A; ++a) {
+                const uint32_t oa = s_own[a];
+                if (oa == ra || oa == rb) {
+                    const uint32_t other = oa == ra ? rb : ra;
+                    for (uint32_t b = a; b < A; ++b)
+                        if (s_own[b] == other) acc = pgx_add(acc, slot_get(Q + row + (b - a)));
+                }
+                row += A - a;
+            }
+            slot_put(F + k, acc);
+        }
+        __syncthreads();
+        // get_specific_likelihoods: the defined keys of F added in key order, by every lane alike
+        pgx sum2 = pgx_zero();
+        if (undef) {
+            uint32_t k = 0;
+            for (uint32_t ra = 0; ra < nA; ++ra) {
+                if (vcf[ra] == 0xFFFFu) { k += nA - ra; continue; }
+                for (uint32_t rb = ra; rb < nA; ++rb, ++k)
+                    if (vcf[rb] != 0xFFFFu) sum2 = pgx_add(sum2, slot_get(F + k));
+            }
+        }
+        // the digits: lane l converts and stores the keys l, l + 64, ...
+        for (uint32_t k = lane; k < K; k += PCW_BLOCK) {
+            uint32_t ra = 0, rest = k;
+            while (rest >= nA - ra) { rest -= nA - ra; ++ra; }
+            const uint32_t va = vcf[ra], vb = vcf[ra + rest];
+            if (va == 0xFFFFu || vb == 0xFFFFu) continue;
+            pgx f = slot_get(F + k);
+            if (sum2.m != 0) f = pgx_div(f, sum2);
+            out[vb * (vb + 1u) / 2u + va] = gl_word(pgx_gl(f));
+        }
+    }
+}
+
+__global__ __launch_bounds__(PC_BLOCK) void k_gl_values(const uint64_t* __restrict__ m, const int32_t* __restrict__ e, uint32_t* __restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * PC_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    pgx x;
+    x.m = m[i];
+    x.e = e[i];
+    out[i] = gl_word(pgx_gl(x));
+}
+
 }  // namespace
+
+extern "C" void pgk_launch_rgl(const DevContig* d_contigs, const RGlDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide, uint32_t n_wide,
+                               void* d_stage, uint32_t max_bins, uint32_t stride, uint32_t n_slots, hipStream_t s) {
+    if (n_desc && n_blocks) hipLaunchKernelGGL(k_rgl, dim3(n_blocks), dim3(PC_BLOCK), 0, s, d_contigs, d_desc, n_desc);
+    if (n_wide && n_slots)
+        hipLaunchKernelGGL(k_rgl_wide, dim3(n_slots < n_wide ? n_slots : n_wide), dim3(PCW_BLOCK), 0, s, d_contigs, d_desc, (const uint2*)d_wide, n_wide,
+                           (PgxSlot*)d_stage, max_bins, stride);
+}
+
+extern "C" void pgk_launch_gl_values(const uint64_t* d_m, const int32_t* d_e, void* d_out, uint32_t n, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_gl_values, dim3((n + PC_BLOCK - 1) / PC_BLOCK), dim3(PC_BLOCK), 0, s, d_m, d_e, (uint32_t*)d_out, n);
+}
 
 extern "C" void pgk_launch_rcalls(const DevContig* d_contigs, const RCallsDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide,
                                   uint32_t n_wide, void* d_stage, uint32_t max_bins, uint32_t stride, uint32_t n_slots, const uint64_t* d_thr_m,

@@ -65,7 +65,22 @@ struct RCallsDesc {
     RecPlanDev plan;
 };
 
+// Record GLs (pg_calls.hip, k_rgl / k_rgl_wide): as RCallsDesc; `out` = the chain's 4-byte values (pg_gl), record r's at
+// gl_off[r] .. gl_off[r + 1] (the offsets hang on the plan alone: one array per index contig)
+struct RGlDesc {
+    uint32_t blk0, R;
+    uint32_t chain, pad;
+    void* out;
+    const uint64_t* gl_off;
+    RecPlanDev plan;
+};
+
 extern "C" {
+// pg_calls.hip: the lists and staging slots of pgk_launch_rcalls, descriptors with the GL buffers
+void pgk_launch_rgl(const DevContig* d_contigs, const RGlDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide, uint32_t n_wide,
+                    void* d_stage, uint32_t max_bins, uint32_t stride, uint32_t n_slots, hipStream_t s);
+// pg_calls.hip: out[i] = the pg_gl of m[i] 2^e[i] (m normalised or 0)
+void pgk_launch_gl_values(const uint64_t* d_m, const int32_t* d_e, void* d_out, uint32_t n, hipStream_t s);
 // pg_calls.hip: d_wide = uint2 {descriptor, record} of every record of a bubble with more than PG_AMAX alleles; d_stage = n_slots
 // staging slots of `stride` 16-byte values each (max_bins quotients, then the folded map) — one per block of k_rcalls_wide
 void pgk_launch_rcalls(const DevContig* d_contigs, const RCallsDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide, uint32_t n_wide,

@@ -527,6 +527,16 @@ struct pg_job {
     size_t o_rcalls_desc = 0, o_rcalls_wide = 0, o_rcalls_stage = 0;
     bool rcalls_formed = false;
     double rcalls_ms = 0.0;
+    // Record GLs (pg_job_record_gl): 4 bytes per genotype of every record's defined alleles, chain after chain, under the same
+    // plans.  A buffer of its own outside the arena, made by the first pg_job_record_gl.
+    bool rgl_dirty = true;
+    unsigned char* d_rgl = nullptr;           // the values, the plans' offsets, the chain descriptors, k_rgl_wide's list, its staging slots
+    std::vector<uint64_t> rgl_first;          // [n_chains + 1] first VALUE of every chain
+    std::vector<RGlDesc> rgl_desc;
+    uint32_t rgl_blocks = 0, rgl_wide = 0, rgl_max_bins = 0, rgl_stride = 0, rgl_slots = 0;
+    size_t o_rgl_desc = 0, o_rgl_wide = 0, o_rgl_stage = 0;
+    bool rgl_formed = false;
+    double rgl_ms = 0.0;
 };
 
 extern "C" void pg_job_destroy(pg_job* job) {
@@ -545,6 +555,7 @@ extern "C" void pg_job_destroy(pg_job* job) {
     if (job->stream2) hipStreamSynchronize(job->stream2);
     if (job->d_calls) hipFree(job->d_calls);
     if (job->d_rcalls) hipFree(job->d_rcalls);
+    if (job->d_rgl) hipFree(job->d_rgl);
     for (RecordPlanHost& rp : job->rplans) if (rp.d) hipFree(rp.d);
     if (job->events) {
         for (auto& e : job->ev) hipEventDestroy(e);
@@ -677,7 +688,8 @@ int upload_inputs(pg_job* job, const pg_contig_batch* batches, const std::vector
         }                                                                                                     \
     } while (0)
     if (with_index) {
-        job->rcalls_dirty = true;   // (new allele ids: the record plans are checked against them again)
+        job->rcalls_dirty = true;
+        job->rgl_dirty = true;   // (new allele ids: the record plans are checked against them again)
         for (size_t i = 0; i < job->index.size(); ++i) {
             const pg_contig_batch& b = batches[i];
             IndexHost& x = job->index[i];
@@ -3055,6 +3067,7 @@ extern "C" int pg_job_record_plan(pg_job* job, uint32_t ix, const pg_record_plan
     if (job->rplans[ix].d) hipFree(job->rplans[ix].d);
     job->rplans[ix] = std::move(h);
     job->rcalls_dirty = true;
+    job->rgl_dirty = true;
     return PG_OK;
 }
 
@@ -3227,6 +3240,266 @@ extern "C" int pg_record_calls_from_bins(int device, uint32_t n_variants, const 
                           d + o_stage, L.max_bins, L.stride, L.n_slots, d_tm, d_te, nullptr);
         ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
              hipMemcpy(out, d + o_out, (size_t)h.R * sizeof(pg_call), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    hipFree(d);
+    return ok ? PG_OK : PG_ERR_DEVICE;
+}
+
+// ---------------------------------------------------------------------------------------
+//  The GL column per VCF record (pg_calls.hip: k_rgl / k_rgl_wide / k_gl_values).
+// ---------------------------------------------------------------------------------------
+namespace {
+
+static_assert(sizeof(pg_gl) == 4, "a GL value is 4 bytes");
+
+// record r owns nd (nd + 1) / 2 values, nd its defined alleles
+std::vector<uint64_t> record_gl_offsets(const RecordPlanHost& h) {
+    std::vector<uint64_t> off((size_t)h.R + 1, 0);
+    for (uint32_t q = 0; q < h.R; ++q) {
+        uint64_t nd = 0;
+        for (uint32_t i = h.vcf_off[q]; i < h.vcf_off[q + 1]; ++i) nd += h.vcf_index[i] != 0xFFFFu;
+        off[q + 1] = off[q] + nd * (nd + 1) / 2;
+    }
+    return off;
+}
+
+int rgl_ready(pg_job* job, char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
+    if (!job->rgl_formed || job->rgl_dirty) { set_err(err, errlen, "pg_job_record_gl has not been called"); return PG_ERR_INVALID; }
+    return PG_OK;
+}
+
+RGlDesc rgl_desc_of(const RCallsDesc& c) {
+    RGlDesc d;
+    memset(&d, 0, sizeof(d));
+    d.blk0 = c.blk0; d.R = c.R; d.chain = c.chain;
+    d.plan = c.plan;
+    return d;
+}
+
+}  // namespace
+
+extern "C" int pg_record_gl_offsets(const pg_record_plan* plan, uint64_t* gl_off) {
+    if (!plan || !gl_off) return PG_ERR_INVALID;
+    RecordPlanHost h;
+    const int rc = check_record_plan(plan, plan->n_variants, &h, nullptr, 0);
+    if (rc != PG_OK) return rc;
+    const std::vector<uint64_t> off = record_gl_offsets(h);
+    memcpy(gl_off, off.data(), off.size() * sizeof(uint64_t));
+    return PG_OK;
+}
+
+extern "C" int pg_gl_text(pg_gl value, char* buf, size_t len) { return pgx_gl_text(value, buf, len); }
+
+extern "C" int pg_job_record_gl(pg_job* job, char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    if (!job->params.run_genotyping) { set_err(err, errlen, "the job does not run the genotyping: it has no bins to form likelihoods from"); return PG_ERR_INVALID; }
+    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(job->device));
+    const uint32_t n = (uint32_t)job->chains.size();
+    if (!job->calls_events) {
+        HIP_TRY(hipEventCreate(&job->ev_calls[0]));
+        HIP_TRY(hipEventCreate(&job->ev_calls[1]));
+        job->calls_events = true;
+    }
+    if (job->rgl_dirty) {   // a plan or the index has changed: the ids are checked, the offsets, descriptors and lists made anew
+        std::vector<uint16_t> aid;
+        std::vector<std::vector<uint64_t>> gl_off(job->rplans.size());
+        std::vector<size_t> o_off(job->rplans.size(), 0);
+        for (size_t ix = 0; ix < job->rplans.size(); ++ix) {
+            const RecordPlanHost& h = job->rplans[ix];
+            const IndexHost& x = job->index[ix];
+            if (!h.set || h.R == 0) continue;
+            aid.resize(x.sumA);
+            HIP_TRY(hipMemcpy(aid.data(), job->arena + x.o_aid, (size_t)x.sumA * 2, hipMemcpyDeviceToHost));
+            const int rc = check_record_plan_ids(h, x.aoff.data(), aid.data(), err, errlen);
+            if (rc != PG_OK) return rc;
+            gl_off[ix] = record_gl_offsets(h);
+        }
+        RcallsLaunch L;
+        plan_rcalls(n, [&](uint32_t c) -> const RecordPlanHost* {
+                        const uint32_t ix = job->chains[c].index;
+                        return ix < job->rplans.size() && job->rplans[ix].set ? &job->rplans[ix] : nullptr;
+                    },
+                    [&](uint32_t c) { return job->index[job->chains[c].index].aoff.data(); }, &L);
+        std::vector<uint64_t> first((size_t)n + 1, 0);
+        for (uint32_t c = 0; c < n; ++c) {
+            const uint32_t ix = job->chains[c].index;
+            first[c + 1] = first[c] + (ix < gl_off.size() && !gl_off[ix].empty() ? gl_off[ix].back() : 0);
+        }
+        size_t total = align_up((size_t)first[n] * sizeof(pg_gl) + 8);
+        for (size_t ix = 0; ix < gl_off.size(); ++ix) {
+            if (gl_off[ix].empty()) continue;
+            o_off[ix] = total;
+            total += align_up(gl_off[ix].size() * sizeof(uint64_t) + 8);
+        }
+        const size_t o_desc = total;
+        const size_t o_wide = o_desc + align_up(L.desc.size() * sizeof(RGlDesc) + 8);
+        const size_t o_stage = o_wide + align_up(L.wide.size() * sizeof(uint32_t) + 8);
+        total = o_stage + align_up((size_t)L.n_slots * L.stride * 16 + 8);
+        unsigned char* d = nullptr;
+        if (hipMalloc((void**)&d, total) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the record GLs failed", total); return PG_ERR_NOMEM; }
+        std::vector<RGlDesc> desc;
+        for (const RCallsDesc& c : L.desc) {
+            RGlDesc g = rgl_desc_of(c);
+            g.out = d + first[c.chain] * sizeof(pg_gl);
+            g.gl_off = (const uint64_t*)(d + o_off[job->chains[c.chain].index]);
+            desc.push_back(g);
+        }
+        hipError_t he = hipSuccess;
+        for (size_t ix = 0; ix < gl_off.size() && he == hipSuccess; ++ix)
+            if (!gl_off[ix].empty()) he = hipMemcpy(d + o_off[ix], gl_off[ix].data(), gl_off[ix].size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+        if (he == hipSuccess && !desc.empty()) he = hipMemcpy(d + o_desc, desc.data(), desc.size() * sizeof(RGlDesc), hipMemcpyHostToDevice);
+        if (he == hipSuccess && !L.wide.empty()) he = hipMemcpy(d + o_wide, L.wide.data(), L.wide.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (he != hipSuccess) { hipFree(d); set_err(err, errlen, "upload of the record GLs' lists failed: %s", hipGetErrorString(he)); return PG_ERR_DEVICE; }
+        if (job->d_rgl) hipFree(job->d_rgl);
+        job->d_rgl = d;
+        job->rgl_first = std::move(first);
+        job->rgl_desc = std::move(desc);
+        job->rgl_blocks = L.n_blocks; job->rgl_wide = (uint32_t)(L.wide.size() / 2);
+        job->rgl_max_bins = L.max_bins; job->rgl_stride = L.stride; job->rgl_slots = L.n_slots;
+        job->o_rgl_desc = o_desc; job->o_rgl_wide = o_wide; job->o_rgl_stage = o_stage;
+        job->rgl_dirty = false;
+        job->rgl_formed = false;
+    }
+    hipStream_t s = job->stream;
+    HIP_TRY(hipEventRecord(job->ev_calls[0], s));
+    pgk_launch_rgl(job->d_contigs, (const RGlDesc*)(job->d_rgl + job->o_rgl_desc), (uint32_t)job->rgl_desc.size(), job->rgl_blocks,
+                   job->d_rgl + job->o_rgl_wide, job->rgl_wide, job->d_rgl + job->o_rgl_stage, job->rgl_max_bins, job->rgl_stride, job->rgl_slots, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(job->ev_calls[1], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, job->ev_calls[0], job->ev_calls[1]));
+    job->rgl_ms = ms;
+    job->rgl_formed = true;
+    return PG_OK;
+}
+
+extern "C" int pg_job_fetch_record_gl(pg_job* job, uint32_t ci, pg_gl* out, char* err, size_t errlen) {
+    int rc = rgl_ready(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (ci >= job->chains.size()) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    const uint64_t N = job->rgl_first[ci + 1] - job->rgl_first[ci];
+    if (N == 0) return PG_OK;
+    if (!out) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(job->device));
+    HIP_TRY(hipMemcpy(out, job->d_rgl + job->rgl_first[ci] * sizeof(pg_gl), N * sizeof(pg_gl), hipMemcpyDeviceToHost));
+    return PG_OK;
+}
+
+extern "C" int pg_job_fetch_record_gl_all(pg_job* job, pg_gl* const* outs, char* err, size_t errlen) {
+    int rc = rgl_ready(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (!outs) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(job->device));
+    for (size_t ci = 0; ci < job->chains.size(); ++ci) {
+        const uint64_t N = job->rgl_first[ci + 1] - job->rgl_first[ci];
+        if (N == 0) continue;
+        if (!outs[ci]) { set_err(err, errlen, "no buffer for chain %zu", ci); return PG_ERR_INVALID; }
+        HIP_TRY(hipMemcpyAsync(outs[ci], job->d_rgl + job->rgl_first[ci] * sizeof(pg_gl), N * sizeof(pg_gl), hipMemcpyDeviceToHost, job->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(job->stream));
+    return PG_OK;
+}
+
+extern "C" int pg_job_device_record_gl(pg_job* job, uint32_t ci, void** d_gl, uint64_t* n) {
+    if (!job || ci >= job->chains.size() || !job->d_rgl || job->rgl_dirty) return PG_ERR_INVALID;
+    if (d_gl) *d_gl = job->d_rgl + job->rgl_first[ci] * sizeof(pg_gl);
+    if (n) *n = job->rgl_first[ci + 1] - job->rgl_first[ci];
+    return PG_OK;
+}
+
+extern "C" double pg_job_record_gl_ms(const pg_job* job) { return job ? job->rgl_ms : 0.0; }
+
+// The unit entry point: host arrays and a plan in, the records' GL values out, through the same two kernels.
+extern "C" int pg_record_gl_from_bins(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id, const uint8_t* kept,
+                                      const uint8_t* allele_present, const double* lik, const int32_t* lik_exp, const pg_record_plan* plan, pg_gl* out) {
+    const uint32_t V = n_variants;
+    if (V && (!allele_off || !allele_id || !kept || !allele_present || allele_off[0] != 0)) return PG_ERR_INVALID;
+    std::vector<uint64_t> goff((size_t)V + 1, 0);
+    for (uint32_t v = 0; v < V; ++v) {
+        if (allele_off[v + 1] <= allele_off[v] || allele_off[v + 1] - allele_off[v] > PG_MAX_ALLELES_PER_VARIANT) return PG_ERR_INVALID;
+        const uint64_t A = allele_off[v + 1] - allele_off[v];
+        goff[v + 1] = goff[v] + A * (A + 1) / 2;
+    }
+    RecordPlanHost h;
+    int rc = check_record_plan(plan, V, &h, nullptr, 0);
+    if (rc == PG_OK && V) rc = check_record_plan_ids(h, allele_off, allele_id, nullptr, 0);
+    if (rc != PG_OK) return rc;
+    if (V == 0) return PG_OK;
+    if (!out) return PG_ERR_INVALID;
+    const uint64_t n_lik = goff[V], sumA = allele_off[V];
+    if (n_lik && (!lik || !lik_exp)) return PG_ERR_INVALID;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); return PG_ERR_DEVICE; }
+    if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return PG_ERR_DEVICE;
+    const std::vector<uint64_t> gl_off = record_gl_offsets(h);
+    const uint64_t n_values = gl_off.back();
+    RcallsLaunch L;
+    plan_rcalls(1, [&](uint32_t) -> const RecordPlanHost* { return &h; }, [&](uint32_t) { return allele_off; }, &L);
+    // one device buffer: every array at a 256-byte boundary
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += align_up(bytes + 8); return at; };
+    const size_t o_contig = take(sizeof(DevContig)), o_desc = take(sizeof(RGlDesc)), o_wide = take(L.wide.size() * 4), o_aoff = take(((size_t)V + 1) * 4),
+                 o_aid = take(sumA * 2), o_kept = take(V), o_pres = take(sumA), o_goff = take(((size_t)V + 1) * 8), o_lik = take(n_lik * 8),
+                 o_exp = take(n_lik * 4), o_plan = take(record_plan_device_bytes(h)), o_stage = take((size_t)L.n_slots * L.stride * 16),
+                 o_gloff = take(gl_off.size() * 8), o_out = take((size_t)n_values * sizeof(pg_gl));
+    unsigned char* d = nullptr;
+    if (hipMalloc((void**)&d, o) != hipSuccess) { (void)hipGetLastError(); return PG_ERR_NOMEM; }
+    DevContig dc;
+    memset(&dc, 0, sizeof(dc));
+    dc.V = V;
+    dc.allele_off = (const uint32_t*)(d + o_aoff);
+    dc.allele_id = (const uint16_t*)(d + o_aid);
+    dc.kept = d + o_kept;
+    dc.allele_present = d + o_pres;
+    dc.geno_off = (const uint64_t*)(d + o_goff);
+    dc.lik = (double*)(d + o_lik);
+    dc.lik_exp = (int32_t*)(d + o_exp);
+    bool ok = record_plan_upload(h, d + o_plan, &L.desc[0].plan);
+    RGlDesc gd = rgl_desc_of(L.desc[0]);
+    gd.out = d + o_out;
+    gd.gl_off = (const uint64_t*)(d + o_gloff);
+    ok = ok && hipMemcpy(d + o_contig, &dc, sizeof(dc), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + o_desc, &gd, sizeof(RGlDesc), hipMemcpyHostToDevice) == hipSuccess &&
+         (L.wide.empty() || hipMemcpy(d + o_wide, L.wide.data(), L.wide.size() * 4, hipMemcpyHostToDevice) == hipSuccess) &&
+         hipMemcpy(d + o_aoff, allele_off, ((size_t)V + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + o_aid, allele_id, sumA * 2, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + o_kept, kept, V, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + o_pres, allele_present, sumA, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + o_goff, goff.data(), ((size_t)V + 1) * 8, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(d + o_gloff, gl_off.data(), gl_off.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
+         (n_lik == 0 || (hipMemcpy(d + o_lik, lik, n_lik * 8, hipMemcpyHostToDevice) == hipSuccess &&
+                         hipMemcpy(d + o_exp, lik_exp, n_lik * 4, hipMemcpyHostToDevice) == hipSuccess));
+    if (ok) {
+        pgk_launch_rgl((const DevContig*)(d + o_contig), (const RGlDesc*)(d + o_desc), 1, L.n_blocks, d + o_wide, (uint32_t)(L.wide.size() / 2), d + o_stage,
+                       L.max_bins, L.stride, L.n_slots, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
+             (n_values == 0 || hipMemcpy(out, d + o_out, (size_t)n_values * sizeof(pg_gl), hipMemcpyDeviceToHost) == hipSuccess);
+    }
+    hipFree(d);
+    return ok ? PG_OK : PG_ERR_DEVICE;
+}
+
+// The unit entry point of the digits alone: out[i] = the GL of m[i] 2^e[i] by the device's own log10 / log1p.
+extern "C" int pg_gl_from_values(int device, uint64_t n, const uint64_t* m, const int32_t* e, pg_gl* out) {
+    if (n == 0) return PG_OK;
+    if (!m || !e || !out || n > 0x7FFFFFFFull) return PG_ERR_INVALID;
+    for (uint64_t i = 0; i < n; ++i)   // a pair is normalised, or zero with exponent 0
+        if (m[i] == 0 ? e[i] != 0 : ((m[i] >> 63) == 0 || e[i] < -40000 || e[i] > 40000)) return PG_ERR_INVALID;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); return PG_ERR_DEVICE; }
+    if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return PG_ERR_DEVICE;
+    const size_t o_e = align_up(n * 8 + 8), o_out = o_e + align_up(n * 4 + 8), total = o_out + align_up(n * 4 + 8);
+    unsigned char* d = nullptr;
+    if (hipMalloc((void**)&d, total) != hipSuccess) { (void)hipGetLastError(); return PG_ERR_NOMEM; }
+    bool ok = hipMemcpy(d, m, n * 8, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d + o_e, e, n * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        pgk_launch_gl_values((const uint64_t*)d, (const int32_t*)(d + o_e), d + o_out, (uint32_t)n, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
+             hipMemcpy(out, d + o_out, n * sizeof(pg_gl), hipMemcpyDeviceToHost) == hipSuccess;
     }
     hipFree(d);
     return ok ? PG_OK : PG_ERR_DEVICE;

@@ -405,6 +405,18 @@ class Job:
         """elapsed ms of the kernels of the last record_calls()"""
         return float(self._lib.pg_job_record_calls_ms(self.h))
 
+    def record_gl(self, contig: Optional[int] = None):
+        """pg_job_record_gl + pg_job_fetch_record_gl[_all]: the GL column per VCF RECORD formed on the device:
+        four digits of log10 of every genotype's likelihood over the record's defined alleles.  Returns one value array
+        (calls.GL_DTYPE) per chain, laid out by calls.record_gl_offsets(plan) — empty for a chain whose index contig has no
+        plan — or chain `contig`'s alone."""
+        from . import calls as _calls
+        return _calls.job_record_gl(self, contig)
+
+    def record_gl_ms(self) -> float:
+        """elapsed ms of the kernels of the last record_gl()"""
+        return float(self._lib.pg_job_record_gl_ms(self.h))
+
     def viterbi_ms(self) -> float:
         """elapsed ms of the Viterbi kernels (run_phasing) of the last run"""
         return float(self._lib.pg_job_viterbi_ms(self.h))

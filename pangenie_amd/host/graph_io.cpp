@@ -461,16 +461,37 @@ static std::string phased_field(const VcfSite& site, const std::vector<unsigned 
     return out.str();
 }
 
+// the sample column `GT:GQ:GL:KC` of record q of bubble i from the device's record fields: genotype_field without a likelihood
+static std::string device_field(const RecordFields& f, size_t q, size_t n_defined, unsigned short coverage, bool no_call) {
+    if (q >= f.calls.size() || q + 1 >= f.gl_off.size() || f.gl_off[q + 1] > f.gl.size() || f.gl_off[q + 1] - f.gl_off[q] != n_defined * (n_defined + 1) / 2)
+        throw std::runtime_error("Graph::write_genotypes_of: the record fields do not fit the graph's records");
+    std::ostringstream out;
+    const GenotypeCall& c = f.calls[q];
+    if (!no_call && c.allele_1 >= 0 && c.allele_2 >= 0) out << c.allele_1 << "/" << c.allele_2 << ":" << c.quality << ":";
+    else out << ".:.:";
+    const size_t n = f.gl_off[q + 1] - f.gl_off[q];
+    if (n < 3) throw std::runtime_error("Graph::write_genotypes_of: too few likelihoods (" + std::to_string(n) + ") computed");
+    for (size_t j = 0; j < n; ++j) {
+        char text[32];
+        if (pg_gl_text(f.gl[f.gl_off[q] + j], text, sizeof(text)) < 0)
+            throw std::runtime_error("Graph::write_genotypes_of: a GL value is still deferred (genotype_cohort_record_fields finishes them)");
+        out << (j ? "," : "") << text;
+    }
+    out << ":" << coverage;
+    return out.str();
+}
+
 std::vector<std::string> Graph::sample_records(const std::vector<GenotypingResult>& genotyping_result, bool ignore_imputed, bool phasing,
-                                               const std::vector<SampledPanel>* sampled_paths) const {
+                                               const std::vector<SampledPanel>* sampled_paths, const DeviceFields* device) const {
     const char* who = sampled_paths ? "Graph::write_sampled_panel" : phasing ? "Graph::write_phasing_of" : "Graph::write_genotypes_of";
     if (variants_deleted_) throw std::runtime_error(std::string(who) + ": variants have been deleted by delete_variant funtion. Re-build object.");
-    if ((sampled_paths ? sampled_paths->size() : genotyping_result.size()) != size())
+    if ((sampled_paths ? sampled_paths->size() : device ? std::min(device->coverage->size(), device->unique_kmers->size()) : genotyping_result.size()) != size())
         throw std::runtime_error(std::string(who) + ": number of variants and number of computed " + (phasing || sampled_paths ? "phasings" : "genotypes") + " differ.");
     std::vector<std::string> lines;
     size_t record_index = 0;   // over single records: the row of variant_ids
     for (size_t i = 0; i < size(); ++i) {
-        for (const VcfSite& site : sampled_paths ? get_variant(i).records(nullptr, &(*sampled_paths)[i]) : get_variant(i).records(&genotyping_result[i])) {
+        for (const VcfSite& site : sampled_paths ? get_variant(i).records(nullptr, &(*sampled_paths)[i])
+                                                 : get_variant(i).records(device ? nullptr : &genotyping_result[i])) {
             const size_t n_all = site.alleles.size();
             if (n_all < 2) throw std::runtime_error(std::string(who) + ": less than 2 alleles given for variant at position " + std::to_string(site.start));
             // ALT = the defined alternative alleles; genotypes over undefined alleles are dropped below
@@ -488,7 +509,8 @@ std::vector<std::string> Graph::sample_records(const std::vector<GenotypingResul
             for (size_t k = 0; k < alts.size(); ++k) line << (k ? "," : "") << alts[k];
             line << "\t.\tPASS\tAF=";
             for (size_t k = 1; k < defined.size(); ++k) line << (k > 1 ? "," : "") << std::setprecision(6) << freq[defined[k]] / n_paths;
-            line << ";UK=" << (sampled_paths ? (*sampled_paths)[i].unique_kmers : (size_t)site.likelihoods.nr_unique_kmers()) << ";MA=" << (n_all - defined.size());
+            line << ";UK=" << (sampled_paths ? (*sampled_paths)[i].unique_kmers : device ? (size_t)(*device->unique_kmers)[i] : (size_t)site.likelihoods.nr_unique_kmers())
+                 << ";MA=" << (n_all - defined.size());
             const std::vector<std::string>& ids = variant_ids_.at(record_index);
             if (!ids.empty()) {
                 // the ids are kept in the lexicographic order of their ALT alleles: back into ALT order
@@ -510,6 +532,9 @@ std::vector<std::string> Graph::sample_records(const std::vector<GenotypingResul
                     if (among_defined.at(a) < 0) line << "\t."; else line << '\t' << among_defined[a];
                 }
             }
+            else if (device)
+                line << "\tGT:GQ:GL:KC\t"
+                     << device_field(*device->fields, record_index, defined.size(), (*device->coverage)[i], ignore_imputed && (*device->unique_kmers)[i] == 0);
             else if (phasing) line << "\tGT:KC\t" << phased_field(site, defined, ignore_imputed);
             else line << "\tGT:GQ:GL:KC\t" << genotype_field(site.likelihoods, defined, n_all, ignore_imputed);
             lines.push_back(line.str());
@@ -522,6 +547,22 @@ std::vector<std::string> Graph::sample_records(const std::vector<GenotypingResul
 void Graph::write_genotypes(const std::string& filename, const std::vector<GenotypingResult>& genotyping_result, bool write_header,
                             const std::string& sample, bool ignore_imputed) const {
     const std::vector<std::string> records = genotypes_records(genotyping_result, ignore_imputed);   // (throws before the file is touched)
+    std::ofstream out(filename, write_header ? std::ios::out : std::ios::app);
+    if (!out.is_open()) throw std::runtime_error("Graph::write_genotypes_of: genotyping output file cannot be opened. Note that the filename must not contain non-existing directories.");
+    if (write_header)
+        for (const std::string& h : genotypes_header(sample)) out << h << '\n';
+    for (const std::string& l : records) out << l << '\n';
+}
+
+std::vector<std::string> Graph::genotypes_records(const RecordFields& fields, const std::vector<unsigned short>& coverage,
+                                                  const std::vector<unsigned short>& unique_kmers, bool ignore_imputed) const {
+    const DeviceFields device = {&fields, &coverage, &unique_kmers};
+    return sample_records({}, ignore_imputed, false, nullptr, &device);
+}
+
+void Graph::write_genotypes(const std::string& filename, const RecordFields& fields, const std::vector<unsigned short>& coverage,
+                            const std::vector<unsigned short>& unique_kmers, bool write_header, const std::string& sample, bool ignore_imputed) const {
+    const std::vector<std::string> records = genotypes_records(fields, coverage, unique_kmers, ignore_imputed);   // (throws before the file is touched)
     std::ofstream out(filename, write_header ? std::ios::out : std::ios::app);
     if (!out.is_open()) throw std::runtime_error("Graph::write_genotypes_of: genotyping output file cannot be opened. Note that the filename must not contain non-existing directories.");
     if (write_header)

@@ -85,6 +85,16 @@ struct RecordPlan {
     pg_record_plan view() const;
 };
 
+/** The sample column of a chromosome's VCF lines as the device forms it, per single record in
+ *  Graph::genotypes_records order: `calls` the GT and GQ (genotype_cohort_record_calls), `gl` the GL values — record r's at
+ *  gl_off[r] .. gl_off[r + 1] - 1, genotype (a <= b) over its defined alleles at b (b + 1) / 2 + a (C ABI pg_job_record_gl).
+ *  As genotype_cohort_record_fields returns it, no entry is deferred any more. */
+struct RecordFields {
+    std::vector<GenotypeCall> calls;
+    std::vector<pg_gl> gl;
+    std::vector<uint64_t> gl_off;
+};
+
 /** A variant bubble of the graph: one or several VCF records closer than the k-mer size, merged
  *  (reference src/variant.hpp:28-121). */
 class Variant {
@@ -163,6 +173,14 @@ public:
     void write_genotypes(const std::string& filename, const std::vector<GenotypingResult>& genotyping_result, bool write_header,
                          const std::string& sample, bool ignore_imputed = false) const;
 
+    /** the same lines from the device's record fields, without a likelihood on the host: the fixed columns as above (UK from
+     *  `unique_kmers`, one entry per bubble), GT and GQ from the calls (`.` for a bubble without unique k-mers under
+     *  `ignore_imputed`), GL from pg_gl_text, KC from `coverage` (one entry per bubble: the sample's local coverage) */
+    std::vector<std::string> genotypes_records(const RecordFields& fields, const std::vector<unsigned short>& coverage,
+                                               const std::vector<unsigned short>& unique_kmers, bool ignore_imputed = false) const;
+    void write_genotypes(const std::string& filename, const RecordFields& fields, const std::vector<unsigned short>& coverage,
+                         const std::vector<unsigned short>& unique_kmers, bool write_header, const std::string& sample, bool ignore_imputed = false) const;
+
     /** the phasing VCF of a `-p` run (reference Graph::write_phasing, src/graph.cpp:280-412): the same fixed columns, `GT:KC`
      *  with the Viterbi haplotypes `a|b` (HMM with run_phasing; `.` for an allele of undefined sequence) */
     static std::vector<std::string> phasing_header(const std::string& sample, const std::string& date = "");
@@ -177,8 +195,13 @@ public:
     void write_sampled_panel(const std::string& filename, const std::vector<SampledPanel>& sampled_paths, bool write_header) const;
 
 private:
+    struct DeviceFields {   // the sample column from the device's record fields instead of a GenotypingResult per bubble
+        const RecordFields* fields;
+        const std::vector<unsigned short>* coverage;
+        const std::vector<unsigned short>* unique_kmers;
+    };
     std::vector<std::string> sample_records(const std::vector<GenotypingResult>& genotyping_result, bool ignore_imputed, bool phasing,
-                                            const std::vector<SampledPanel>* sampled_paths = nullptr) const;
+                                            const std::vector<SampledPanel>* sampled_paths = nullptr, const DeviceFields* device = nullptr) const;
     std::vector<std::pair<std::string, std::shared_ptr<DnaSequence>>> fasta_;   // name -> sequence, archive (= sorted) order
     std::string chromosome_;
     size_t kmer_size_ = 0;
@@ -194,6 +217,16 @@ private:
  *  the records of a bubble the device deferred are formed here from that bubble's bins through Variant::records and
  *  genotype_field's rules.  `ignore_imputed`: a bubble without unique k-mers gives no call. */
 std::vector<std::map<std::string, std::vector<GenotypeCall>>> genotype_cohort_record_calls(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false,
+    long double effective_N = 25000.0L, int device = 0, bool ignore_imputed = false);
+
+/** The whole sample column per VCF RECORD from one job: the arguments and the calls of genotype_cohort_record_calls, and the
+ *  GL values of every record (C ABI pg_job_record_gl) — no genotype bin leaves the device.  Entries the device deferred (a
+ *  bubble next to long double's subnormals; a value whose fourth digit the fp64 logarithm could not vouch for, about 2e-9 of
+ *  them) are finished here from that bubble's bins through Variant::records and genotype_field's rules.  Per sample and
+ *  chromosome what Graph::genotypes_records(fields, coverage, unique_kmers) prints. */
+std::vector<std::map<std::string, RecordFields>> genotype_cohort_record_fields(
     std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
     const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false,
     long double effective_N = 25000.0L, int device = 0, bool ignore_imputed = false);

@@ -850,12 +850,43 @@ static GenotypeCall record_call_on_host(const VcfSite& site) {
     return call;
 }
 
-std::vector<std::map<std::string, std::vector<GenotypeCall>>> genotype_cohort_record_calls(
+// the four digits of a long double logarithm as the device stores them: glibc prints the exact decimal expansion
+static pg_gl gl_of_log10(long double v) {
+    pg_gl g;
+    g.mant = 0;
+    if (std::isinf(v) || std::isnan(v)) { g.exp10 = PG_GL_NEG_INF; return g; }   // (log10 of 0; a likelihood is never negative)
+    if (v == 0.0L) { g.exp10 = 0; return g; }
+    char buf[48];
+    std::snprintf(buf, sizeof(buf), "%.3Le", v);   // [-]d.ddde[+-]XX
+    const char* p = buf;
+    const bool negative = *p == '-';
+    if (negative) ++p;
+    const int mant = (p[0] - '0') * 1000 + (p[2] - '0') * 100 + (p[3] - '0') * 10 + (p[4] - '0');
+    g.mant = (int16_t)(negative ? -mant : mant);
+    g.exp10 = (int16_t)std::atoi(p + 6);
+    return g;
+}
+
+// the GL values of one record as genotype_field prints them, from the bubble's bins on the host
+static void record_gl_on_host(const VcfSite& site, pg_gl* out, size_t n) {
+    GenotypingResult tmp = site.likelihoods;
+    if (tmp.contains_no_likelihoods()) tmp.add_to_likelihood(0, 0, 1.0);
+    std::vector<unsigned short> defined = {0};
+    for (size_t a = 1; a < site.alleles.size(); ++a)
+        if (!site.undefined[a]) defined.push_back((unsigned short)a);
+    const GenotypingResult gl = defined.size() < site.alleles.size() ? tmp.get_specific_likelihoods(defined) : tmp;
+    const std::vector<long double> all = gl.get_all_likelihoods(defined.size());
+    if (all.size() != n) fail("genotype_cohort_record_fields: a record's likelihoods do not fit its GL values");
+    for (size_t j = 0; j < n; ++j) out[j] = gl_of_log10(std::log10(all[j]));
+}
+
+// genotype_cohort_record_calls and, `with_gl`, genotype_cohort_record_fields: one job, the calls and the GL values per record
+static std::vector<std::map<std::string, RecordFields>> cohort_record_fields(
     std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
     const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device,
-    bool ignore_imputed) {
+    bool ignore_imputed, bool with_gl) {
     const size_t C = chromosomes.size(), S = samples.size();
-    std::vector<std::map<std::string, std::vector<GenotypeCall>>> out(S);
+    std::vector<std::map<std::string, RecordFields>> out(S);
     if (C == 0 || S == 0) return out;
     // (the job is made exactly as genotype_cohort makes it)
     std::vector<std::string> names;
@@ -912,7 +943,16 @@ std::vector<std::map<std::string, std::vector<GenotypeCall>>> genotype_cohort_re
     }
     if (rc == PG_OK) rc = pg_job_run(job, nullptr, err, sizeof(err));
     if (rc == PG_OK) rc = pg_job_record_calls(job, err, sizeof(err));
+    if (rc == PG_OK && with_gl) rc = pg_job_record_gl(job, err, sizeof(err));
     if (rc != PG_OK) { if (job) pg_job_destroy(job); check_rc(rc, err); }
+    // the offsets of the GL values hang on the plan alone
+    std::vector<std::vector<uint64_t>> gl_off(C);
+    for (c = 0; c < C && with_gl; ++c) {
+        gl_off[c].assign(plans[c].nr_of_records() + 1, 0);
+        const pg_record_plan view = plans[c].view();
+        rc = pg_record_gl_offsets(&view, gl_off[c].data());
+        if (rc != PG_OK) { pg_job_destroy(job); check_rc(rc, "pg_record_gl_offsets refused the record plan"); }
+    }
     // all records with one synchronisation
     std::vector<std::vector<pg_call>> recs(S * C);
     std::vector<pg_call*> ptrs(S * C, nullptr);
@@ -921,14 +961,29 @@ std::vector<std::map<std::string, std::vector<GenotypeCall>>> genotype_cohort_re
         ptrs[i] = recs[i].empty() ? nullptr : recs[i].data();
     }
     rc = pg_job_fetch_record_calls_all(job, ptrs.data(), err, sizeof(err));
+    if (with_gl && rc == PG_OK) {   // ... and all GL values with another
+        std::vector<pg_gl*> gl_ptrs(S * C, nullptr);
+        for (size_t i = 0; i < S * C; ++i) {
+            RecordFields& fields = out[i / C][names[i % C]];
+            fields.gl_off = gl_off[i % C];
+            fields.gl.resize(fields.gl_off.back());
+            gl_ptrs[i] = fields.gl.empty() ? nullptr : fields.gl.data();
+        }
+        rc = pg_job_fetch_record_gl_all(job, gl_ptrs.data(), err, sizeof(err));
+    }
     for (size_t s = 0; s < S && rc == PG_OK; ++s)
         for (c = 0; c < C && rc == PG_OK; ++c) {
             const std::vector<pg_call>& r = recs[s * C + c];   // chain id = sample * n_contigs + contig
             const RecordPlan& plan = plans[c];
             const FlatContig& f = flat[c];
-            std::vector<GenotypeCall>& calls = out[s][names[c]];
+            RecordFields& fields = out[s][names[c]];
+            std::vector<GenotypeCall>& calls = fields.calls;
             calls.resize(r.size());
             bool any_deferred = false;
+            std::vector<char> gl_deferred(with_gl ? plan.rec_off.size() - 1 : 0, 0);   // per bubble: a GL value is left to the host
+            for (size_t v = 0; v < gl_deferred.size(); ++v)
+                for (uint64_t i = fields.gl_off[plan.rec_off[v]]; i < fields.gl_off[plan.rec_off[v + 1]]; ++i)
+                    if (fields.gl[i].mant == 0 && fields.gl[i].exp10 == PG_GL_DEFERRED) { gl_deferred[v] = 1; any_deferred = true; }
             for (size_t v = 0; v + 1 < plan.rec_off.size(); ++v) {
                 const bool imputed = ignore_imputed && (!any_column[c] || f.kmer_off[v + 1] == f.kmer_off[v]);
                 for (size_t q = plan.rec_off[v]; q < plan.rec_off[v + 1]; ++q) {
@@ -948,16 +1003,42 @@ std::vector<std::map<std::string, std::vector<GenotypeCall>>> genotype_cohort_re
             if (rc != PG_OK) break;
             std::vector<GenotypingResult> full = results_of_chain(f, cov_rows[s][c], goff[c], lik.data(), lexp.data());
             for (size_t v = 0; v + 1 < plan.rec_off.size(); ++v) {
-                if (r[plan.rec_off[v]].flags != PG_CALL_DEFERRED) continue;   // (a bubble is deferred with all its records)
-                if (ignore_imputed && full[v].nr_unique_kmers() == 0) continue;
+                const bool call_deferred = r[plan.rec_off[v]].flags == PG_CALL_DEFERRED;   // (a bubble is deferred with all its records)
+                const bool imputed = ignore_imputed && full[v].nr_unique_kmers() == 0;
+                const bool calls_here = call_deferred && !imputed, gl_here = with_gl && gl_deferred[v];
+                if (!calls_here && !gl_here) continue;
                 full[v].normalize();
                 const std::vector<VcfSite> sites = graph_of[c]->get_variant(v).records(&full[v]);
-                for (size_t k = 0; k < sites.size() && plan.rec_off[v] + k < plan.rec_off[v + 1]; ++k) calls[plan.rec_off[v] + k] = record_call_on_host(sites[k]);
+                for (size_t k = 0; k < sites.size() && plan.rec_off[v] + k < plan.rec_off[v + 1]; ++k) {
+                    const size_t q = plan.rec_off[v] + k;
+                    if (calls_here) calls[q] = record_call_on_host(sites[k]);
+                    if (gl_here) record_gl_on_host(sites[k], fields.gl.data() + fields.gl_off[q], fields.gl_off[q + 1] - fields.gl_off[q]);   // (the GL column is printed whatever ignore_imputed says)
+                }
             }
         }
     pg_job_destroy(job);
     check_rc(rc, err);
     return out;
+}
+
+std::vector<std::map<std::string, std::vector<GenotypeCall>>> genotype_cohort_record_calls(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device,
+    bool ignore_imputed) {
+    std::vector<std::map<std::string, std::vector<GenotypeCall>>> out(samples.size());
+    if (chromosomes.empty()) return out;
+    std::vector<std::map<std::string, RecordFields>> fields =
+        cohort_record_fields(chromosomes, graphs, samples, probabilities, recombrate, uniform, effective_N, device, ignore_imputed, false);
+    for (size_t s = 0; s < fields.size(); ++s)
+        for (auto& kv : fields[s]) out[s][kv.first] = std::move(kv.second.calls);
+    return out;
+}
+
+std::vector<std::map<std::string, RecordFields>> genotype_cohort_record_fields(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device,
+    bool ignore_imputed) {
+    return cohort_record_fields(chromosomes, graphs, samples, probabilities, recombrate, uniform, effective_N, device, ignore_imputed, true);
 }
 
 // ------------------------------------------------------------------ cohort job fed by the device counter

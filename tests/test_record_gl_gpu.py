@@ -1,0 +1,160 @@
+"""The GL column per VCF record through a job (pg_job_record_gl / pg_job_fetch_record_gl[_all], k_rgl and k_rgl_wide of
+pangenie_amd/csrc/pg_calls.hip): every value of every chain against pangenie_amd/genotyping_result.py in np.longdouble —
+normalize, the fold onto the record's alleles, get_specific_likelihoods, get_all_likelihoods, the four digits of log10
+(tests/record_gl_util.py) — on the job's OWN fetched bins, under random plans of 1-3 records per bubble with a tenth of the
+record alleles undefined.  None may be deferred (the panels' likelihoods are nowhere near 2^-16300, and a window of 1e-9 meets
+a few hundred thousand values with a chance of a thousandth).  fetch_record_gl_all equals fetch_record_gl, a second call gives
+the same values, the bins and the record calls are what they were; a chain without a plan is left out; the refusals."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from pangenie_amd import calls, hmm
+from pangenie_amd.panel import synthetic_panel, synthetic_sample_counts
+from tests.record_calls_util import random_plan
+from tests.record_gl_util import assert_record_gl, record_gl_yardstick
+
+pytestmark = pytest.mark.gpu
+ARGS = (6, 108, 54, 0.01)
+
+
+def check_gl(job, plans, what):
+    """plans: {index contig: RecordPlan}, already uploaded.  Every chain with a plan: values == yardstick on the fetched bins,
+    none deferred, fetch_record_gl_all == fetch_record_gl, a second pg_job_record_gl gives the same values; the bins and the
+    record calls are what they were before.  Answers the number of finite values."""
+    before, rec_calls = job.fetch_all(), job.record_calls()
+    gls = job.record_gl()
+    again = job.record_gl()
+    after, rec_calls_after = job.fetch_all(), job.record_calls()
+    n_finite, nc = 0, len(job.index)
+    for c, (b, r0, r1) in enumerate(zip(job.batches, before, after)):
+        assert np.array_equal(r0.lik, r1.lik) and np.array_equal(r0.lik_exp, r1.lik_exp) and np.array_equal(r0.kept, r1.kept)
+        assert np.array_equal(rec_calls[c], rec_calls_after[c])
+        plan = plans.get(c % nc)
+        d, n = C.c_void_p(), C.c_uint64()
+        assert job._lib.pg_job_device_record_gl(job.h, c, C.byref(d), C.byref(n)) == 0
+        if plan is None:   # left out, not an error
+            assert len(gls[c]) == 0 and n.value == 0
+            continue
+        gl_off = calls.record_gl_offsets(plan)
+        assert gls[c].dtype == calls.GL_DTYPE and len(gls[c]) == int(gl_off[-1]) == n.value
+        assert np.array_equal(gls[c], again[c]) and np.array_equal(gls[c], calls.fetch_record_gl(job, c))
+        want = record_gl_yardstick(b.allele_off, b.allele_id, r0.kept, r0.allele_present, r0.lik, r0.lik_exp, plan)
+        assert assert_record_gl(gls[c], gl_off, want, (what, c)) == []
+        n_finite += int((gls[c]["mant"] != 0).sum())
+    assert job.record_gl_ms() > 0.0 or n_finite == 0
+    return n_finite
+
+
+def test_64_chains_at_16_paths_with_multiallelic_and_wide_objects_fused(monkeypatch):
+    monkeypatch.setenv("PG_SWEEP_MODE", "fused")
+    monkeypatch.setenv("PG_KERNELS", "small")   # (keeps the wide columns of a job of few 16-path chains fused, as in tests/test_calls_gpu.py)
+    index = [synthetic_panel(300, 16, 20, seed=7500, multiallelic_frac=0.3, wide_frac=0.05, wide_at=(0, 150, 299))]
+    A = np.diff(index[0].allele_off.astype(np.int64))
+    assert (A > 5).sum() >= 3 and ((A > 2) & (A <= 5)).sum() > 30   # both kernels have work
+    samples = [tuple([x] for x in synthetic_sample_counts(index[0], seed=7510 + s)) for s in range(64)]
+    job = hmm.Job.cohort(index, samples, hmm.ProbabilityTable(*ARGS), hmm.make_params(1.26, False, 1e-5))
+    assert job.n_chains == 64 and job.sweep_mode()[0] == "fused", job.plan()
+    job.run()
+    plan = random_plan(np.random.default_rng(7501), index[0])
+    assert int(np.diff(plan.rec_off.astype(np.int64)).max()) == 3 and (plan.vcf_index == 0xFFFF).sum() > 20
+    job.record_plan(0, plan)
+    assert check_gl(job, {0: plan}, "fused") > 64 * 300
+    job.close()
+
+
+def test_two_chains_at_64_paths_chunked_one_plan_then_two_then_one_replaced(monkeypatch):
+    monkeypatch.setenv("PG_SWEEP_MODE", "chunked")
+    monkeypatch.setenv("PG_CHUNK_COLS", "64")
+    batches = [synthetic_panel(300, 64, 20, seed=7600 + i, multiallelic_frac=0.2) for i in range(2)]
+    job = hmm.Job(batches, hmm.ProbabilityTable(*ARGS), hmm.make_params(1.26, False, 1e-5))
+    assert job.sweep_mode()[0] == "chunked", job.plan()
+    job.run()
+    rng = np.random.default_rng(7601)
+    plans = {1: random_plan(rng, batches[1])}
+    job.record_plan(1, plans[1])
+    assert check_gl(job, plans, "chunked, chain 0 without a plan") > 300
+    plans[0] = random_plan(rng, batches[0])
+    job.record_plan(0, plans[0])
+    assert check_gl(job, plans, "chunked") > 600
+    old = job.record_gl()[1].copy()
+    plans[1] = random_plan(rng, batches[1])   # a second plan for the same contig replaces the first
+    job.record_plan(1, plans[1])
+    assert check_gl(job, plans, "chunked, plan replaced") > 600
+    new = job.record_gl()[1]
+    assert len(new) != len(old) or not np.array_equal(new, old)
+    job.close()
+
+
+def test_cohort_of_two_samples_over_three_contigs_one_of_them_empty():
+    full = [synthetic_panel(270, 16, 20, seed=7700, multiallelic_frac=0.3, wide_frac=0.03, wide_at=(269,)),
+            synthetic_panel(120, 16, 20, seed=7701, multiallelic_frac=0.3)]
+    index = [full[0], full[0].slice(0, 0), full[1]]
+    samples = []
+    for s in range(2):
+        kcs, covs = zip(*[synthetic_sample_counts(ix, seed=7710 + 10 * s + c) if ix.n_variants else (np.zeros(0, np.uint16), np.zeros(0, np.uint16))
+                          for c, ix in enumerate(index)])
+        samples.append((list(kcs), list(covs)))
+    job = hmm.Job.cohort(index, samples, hmm.ProbabilityTable(*ARGS), hmm.make_params(1.26, False, 1e-5))
+    assert job.n_chains == 6
+    job.run()
+    rng = np.random.default_rng(7702)
+    plans = {0: random_plan(rng, index[0]), 1: calls.RecordPlan.from_records([]), 2: random_plan(rng, index[2])}
+    for c, p in plans.items():   # once per index contig: both samples' chains share it
+        job.record_plan(c, p)
+    assert check_gl(job, plans, "cohort") > 2 * 390
+    gls = job.record_gl()
+    assert len(gls[1]) == 0 and len(gls[4]) == 0
+    assert len(gls[0]) == len(gls[3]) and not np.array_equal(gls[0], gls[3])   # two samples, one plan, two sets of values
+    # a new batch of samples invalidates the run: the values are refused until the next one
+    job.upload_begin(samples[::-1])
+    job.upload_end()
+    with pytest.raises(hmm.PanGenieError) as e:
+        job.record_gl()
+    assert e.value.code == -1
+    with pytest.raises(hmm.PanGenieError) as e:
+        calls.fetch_record_gl(job, 0)
+    assert e.value.code == -1
+    job.run()
+    swapped = job.record_gl()
+    assert np.array_equal(swapped[0], gls[3]) and np.array_equal(swapped[3], gls[0]) and np.array_equal(swapped[2], gls[5])
+    job.close()
+
+
+def test_refusals():
+    b = synthetic_panel(40, 16, 20, seed=7800)
+    t = hmm.ProbabilityTable(*ARGS)
+    plan = random_plan(np.random.default_rng(7801), b)
+    job = hmm.Job([b], t, hmm.make_params(1.26, False, 1e-5))
+    job.record_plan(0, plan)
+    with pytest.raises(hmm.PanGenieError) as e:   # before pg_job_run
+        job.record_gl()
+    assert e.value.code == -1
+    job.run()
+    with pytest.raises(hmm.PanGenieError) as e:   # values are fetched only after pg_job_record_gl; the record calls do not stand in for it
+        calls.fetch_record_gl(job, 0)
+    assert e.value.code == -1
+    job.record_calls()
+    with pytest.raises(hmm.PanGenieError) as e:
+        calls.fetch_record_gl(job, 0)
+    assert e.value.code == -1
+    assert len(job.record_gl(0)) == int(calls.record_gl_offsets(plan)[-1])
+    # an allele id of the index outside a record's map: found when the values are formed, on the host
+    short = calls.RecordPlan.from_records([[([0], [True])] for _ in range(40)])
+    job.record_plan(0, short)
+    with pytest.raises(hmm.PanGenieError) as e:
+        job.record_gl()
+    assert e.value.code == -1
+    with pytest.raises(hmm.PanGenieError) as e:   # ... and the values of the plan before are gone with it
+        calls.fetch_record_gl(job, 0)
+    assert e.value.code == -1
+    job.record_plan(0, plan)
+    assert len(job.record_gl(0)) == int(calls.record_gl_offsets(plan)[-1])
+    job.close()
+    job = hmm.Job([b], t, hmm.make_params(1.26, False, 1e-5, run_genotyping=False, run_phasing=True))
+    job.run()
+    with pytest.raises(hmm.PanGenieError) as e:   # a job without run_genotyping has no bins
+        job.record_gl()
+    assert e.value.code == -1
+    job.close()
