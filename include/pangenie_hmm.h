@@ -223,6 +223,13 @@ size_t pg_job_plan(const pg_job* job, char* out, size_t len);
  * pg_sparse_stored_by_chain: 1 if the chain itself stores `column` (its role's phase-1 half is column < n_columns / 2 for role 0). */
 int pg_sparse_segment(uint32_t n_columns, uint32_t chunk_cols, uint32_t chunk, uint32_t role, uint32_t j, uint32_t out[3]);
 int pg_sparse_stored_by_chain(uint32_t n_columns, uint32_t role, uint32_t column);
+/* Where every chain with columns is such a chain, the chunk sweeps of phase 2 store every 64th column too (the checkpoints go on
+ * from the phase boundary, into an area of the chain's own), and a second k_refill_lean per chunk forms the chunk's columns behind
+ * its sweep.  Segment `j` of chunk `chunk` itself: returns 1 and out = {column it resumes from, lowest, highest column it stores —
+ * the highest (forward role) or lowest (backward role) is the next checkpoint, except at the end of the half}, 0 / -1 as above.
+ * pg_sparse_chunk_stored_by_chain: 1 if the chain itself stores `column` of its role's phase-2 half. */
+int pg_sparse_chunk_segment(uint32_t n_columns, uint32_t chunk_cols, uint32_t chunk, uint32_t role, uint32_t j, uint32_t out[3]);
+int pg_sparse_chunk_stored_by_chain(uint32_t n_columns, uint32_t role, uint32_t column);
 /* Elapsed milliseconds of the Viterbi kernels (run_phasing) of the LAST pg_job_run, hipEvents on the launch stream. */
 double pg_job_viterbi_ms(const pg_job* job);
 void pg_job_destroy(pg_job* job);

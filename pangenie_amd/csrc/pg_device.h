@@ -279,6 +279,14 @@ struct DevContig {
     // PG_LEAN_SPARSE-th column, counted from the phase boundary (pg_sparse_*, below); k_refill_lean re-runs the columns between two
     // stored ones on the idle CUs, chunk by chunk, before k_post reads them (PG_KERNELS=nosparse: every column by the chain)
     uint32_t sparse;
+    // 1 (sparse, and every chain of the job with columns is such a chain): the chunk sweeps of phase 2 store only their checkpoints
+    // too (pg_sparse2_*, below) — into `ckpt`, an area of the chain's own that no run reuses, not into the scratch buffers: a chunk
+    // sweep then neither stores its columns nor waits for k_post to free a buffer.  k_refill_lean forms the chunk's columns from the
+    // checkpoints into the scratch slots k_post reads, behind the sweep on the second stream (PG_KERNELS=nosparse2: the chunk
+    // sweeps store every column into the scratch buffers, as the chains of every other job do)
+    uint32_t sparse2;
+    uint32_t ckpt_slots;       // pg_sparse2_slots(V)
+    double*  ckpt;             // [2 roles][ckpt_slots][64 * 64], forward role first: slot m = checkpoint m of the role's phase 2
     // the WIDE columns of the chain (smallx == 2, index with objects of more than PG_AMAX alleles): k_records appends every wide
     // column it meets, k_bins_wide walks the list — one wave per entry instead of a scan of all columns for the rare one
     uint32_t* wcols;           // [wide candidates of the index contig]
@@ -337,6 +345,38 @@ PG_HD inline bool pg_sparse_stored(uint32_t C, uint32_t role, uint32_t c) {
     const uint32_t mid = C / 2u;
     if (role == 0u) return c >= mid || (mid - 1u - c) % PG_LEAN_SPARSE == 0u || c < (mid - 1u) % PG_LEAN_SPARSE;
     return c < mid || (c - mid) % PG_LEAN_SPARSE == 0u || c > mid + pg_sparse_segments(C, 1u) * PG_LEAN_SPARSE;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+//  Sparse phase 2 (DevContig::sparse2): the checkpoints go on in phase 1's step from the phase boundary — the forward role walks
+//  mid .. C-1 and stores mid-1 + m S, the backward role walks mid-1 .. 0 and stores mid - m S (m = 1, 2, ...; checkpoint 0 is
+//  phase 1's: fwd[mid-1] / fwd[mid]).  With chunk_cols a multiple of S the last column of every chunk is a checkpoint: the next
+//  chunk launch resumes from it.  Segment m >= 0 of a role resumes from checkpoint m and runs, in the role's own direction, the
+//  S columns up to and including checkpoint m + 1 — fewer at the end of the half, whose last piece the chain does not store
+//  either.  Chunk i of phase 2 is segments i q .. (i + 1) q - 1 of either role, q = chunk_cols / S.
+// ------------------------------------------------------------------------------------------------------------------
+PG_HD inline uint32_t pg_sparse2_slots(uint32_t V) { return (V / 2u + 1u) / PG_LEAN_SPARSE + 2u; }   // (a half has at most V / 2 + 1 columns)
+// segment m of a role: false if it has no columns; out = {checkpoint it resumes from, its lowest column, its highest column}
+PG_HD inline bool pg_sparse2_segment(uint32_t C, uint32_t role, unsigned long long m, uint32_t out[3]) {
+    if (C < 2u) return false;   // (a single column is the forward role's initial one: no checkpoint in front of it)
+    const unsigned long long mid = C / 2u, d = m * PG_LEAN_SPARSE;
+    if (role == 0u) {
+        const unsigned long long ck = mid - 1u + d;
+        if (ck + 1u >= C) return false;
+        out[0] = (uint32_t)ck; out[1] = (uint32_t)ck + 1u; out[2] = (uint32_t)(C - 1u - ck > PG_LEAN_SPARSE ? ck + PG_LEAN_SPARSE : C - 1u);
+    } else {
+        if (d >= mid) return false;
+        const unsigned long long ck = mid - d;
+        out[0] = (uint32_t)ck; out[1] = (uint32_t)(ck > PG_LEAN_SPARSE ? ck - PG_LEAN_SPARSE : 0u); out[2] = (uint32_t)ck - 1u;
+    }
+    return true;
+}
+// does the chain itself store column c of its phase-2 half (a checkpoint)?
+PG_HD inline bool pg_sparse2_stored(uint32_t C, uint32_t role, uint32_t c) {
+    const uint32_t mid = C / 2u;
+    if (C < 2u) return false;
+    if (role == 0u) return c >= mid && c < C && (c - (mid - 1u)) % PG_LEAN_SPARSE == 0u;
+    return c < mid && (mid - c) % PG_LEAN_SPARSE == 0u;
 }
 
 // ------------------------------------------------------------------------------------------------------------------

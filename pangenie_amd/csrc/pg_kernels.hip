@@ -3170,9 +3170,12 @@ DEVI double lean_total(const LeanShared<R>& sh, uint32_t pb) {   // (kLeanPreTot
 // SPARSE (PHASE 1 of DevContig::sparse chains): only the checkpoints of pg_device.h's pg_sparse_* are stored — the step is compiled
 // twice, with and without its column stores.  PHASE 5: a refill segment (k_refill_lean) — `chunk` = the checkpoint column it resumes
 // from; it stores the PG_LEAN_SPARSE - 1 columns behind it and none of the per-column scalars, which are the chain's.
+// SPARSE, PHASE 3 (DevContig::sparse2 chains): the chunk sweep stores the checkpoints of pg_sparse2_* alone, into DevContig::ckpt,
+// and resumes from there; a PHASE 5 segment whose checkpoint lies in phase 2 (at or behind the phase boundary) forms the chunk's
+// columns from them — PG_LEAN_SPARSE columns, its closing checkpoint included — into the scratch slots k_post reads.
 template <int PHASE, int R, bool TRI, bool SPARSE = false>
 DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint32_t chunk) {
-    static_assert(!SPARSE || (PHASE == 1 && !TRI), "sparse stores: phase 1 of full-column lean chains");
+    static_assert(!SPARSE || ((PHASE == 1 || PHASE == 3) && !TRI), "sparse stores: phases 1 and 3 of full-column lean chains");
     constexpr int HP = 64;
     constexpr uint32_t RMASK = (1u << R) - 1u;
     const uint32_t mid = C / 2, K = dc.chunk_cols;
@@ -3183,7 +3186,12 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         lo = (uint32_t)l;
         hi = C - lo > K ? lo + K : C;
     }
-    if constexpr (PHASE == 5) { lo = chunk + 1u; hi = chunk + PG_LEAN_SPARSE; }
+    bool seg2 = false;   // PHASE 5: a segment of phase 2
+    if constexpr (PHASE == 5) {
+        lo = chunk + 1u; hi = chunk + PG_LEAN_SPARSE;
+        seg2 = lo >= mid;
+        if (seg2) hi = C - lo > PG_LEAN_SPARSE ? lo + PG_LEAN_SPARSE : C;
+    }
     if (lo >= hi) return;
     const uint32_t first = lo == 0 ? 1u : lo;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -3205,10 +3213,20 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
     if constexpr (PHASE == 3) {
         gdouble* scr = (gdouble*)dc.scratch;
         wr = scr + (size_t)(PG_SCR_BUF(chunk) * 2u) * K * colsz - (size_t)lo * colsz;
-        if (chunk > 0) resume = (gcdouble*)(scr + ((size_t)(PG_SCR_BUF(chunk - 1u) * 2u) * K + (K - 1u)) * colsz);
+        if constexpr (SPARSE) { if (chunk > 0) resume = (gcdouble*)dc.ckpt + (size_t)(lo - mid) / PG_LEAN_SPARSE * colsz; }
+        else if (chunk > 0) resume = (gcdouble*)(scr + ((size_t)(PG_SCR_BUF(chunk - 1u) * 2u) * K + (K - 1u)) * colsz);
     }
     // PHASE 4: the whole second half in ONE launch, chunk after chunk into the scratch buffers (`chunk` = k_post_loop's blocks per chain)
     if constexpr (PHASE == 4) wr = (gdouble*)dc.scratch - (size_t)lo * colsz;
+    // a segment of phase 2: from checkpoint m (0: phase 1's last column) into the scratch slots of the chunk it lies in.  Where that
+    // checkpoint is the last column of a chunk, the chain itself resumed from memory there (`boundary`, below)
+    bool boundary = false;
+    if constexpr (PHASE == 5) if (seg2) {
+        const uint32_t m = (lo - mid) / PG_LEAN_SPARSE, ci = (lo - mid) / K;
+        if (m) resume = (gcdouble*)dc.ckpt + (size_t)m * colsz;
+        wr = (gdouble*)dc.scratch + (size_t)(PG_SCR_BUF(ci) * 2u) * K * colsz - ((size_t)mid + (size_t)ci * K) * colsz;
+        boundary = (lo - mid) % K == 0u;
+    }
     const size_t toff = (size_t)(i0 >> 1) * HP + lane;  // this thread's first row pair inside a column (in 16-byte units)
     auto emis = [&](const FRec& r, double& eA, double& eB) {  // e(i, j) = row bit ? eB : eA for this lane's column allele
         const bool aj = (r.bits1 >> lane) & 1ull;
@@ -3247,14 +3265,19 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
             lean_store(dst + (size_t)q * HP, v2f64{a, b});
         }
     };
+    auto col_at = [&](uint32_t c) __attribute__((always_inline)) -> gdouble* {   // where column c is stored
+        if constexpr (SPARSE && PHASE == 3) return (gdouble*)dc.ckpt + (size_t)((c - (mid - 1u)) / PG_LEAN_SPARSE) * colsz;   // (checkpoints only)
+        else return wr + (size_t)c * colsz;
+    };
     auto store_col = [&](uint32_t c, const double (&v)[R]) {
-        gdouble2* dst = (gdouble2*)(wr + (size_t)c * colsz) + toff;
+        gdouble2* dst = (gdouble2*)col_at(c) + toff;
 #pragma unroll
         for (int k = 0; k < R; k += 2) put_pair(dst, k >> 1, v[k], v[k + 1]);
     };
     auto flag_uniform = [&](uint32_t cprev) {
         bool stored = cprev >= lo;
-        if constexpr (SPARSE) stored = pg_sparse_stored(C, 0u, cprev);   // (the refill segment forms the others from the same arithmetic)
+        if constexpr (SPARSE && PHASE == 1) stored = pg_sparse_stored(C, 0u, cprev);   // (the refill segment forms the others from the same arithmetic)
+        if constexpr (SPARSE && PHASE == 3) stored = stored && pg_sparse2_stored(C, 0u, cprev);
         if (stored) {
             double xu[R];
 #pragma unroll
@@ -3289,9 +3312,10 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
             if (!fallback[lo - 1]) {
 #pragma unroll
                 for (int k = 0; k < R; ++k) { const double e = sel_by_bit(rb, k, eA, eB); part = fma(e, x[k], part); x[k] *= e; }
-            } else if constexpr (PHASE == 5) {
+            } else if (PHASE == 5 && !boundary) {
                 // (the chain went on from this checkpoint in registers: every state 0, the uniform column entering through the first
-                //  step's zero test — the same instructions here give the same bits; a chunk launch resumes from the STORED uniform column)
+                //  step's zero test — the same instructions here give the same bits; a chunk launch resumes from the STORED uniform
+                //  column, and so does the segment behind a checkpoint that is a chunk's last column)
 #pragma unroll
                 for (int k = 0; k < R; ++k) x[k] = 0.0;
             } else {
@@ -3368,7 +3392,7 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         const double m = ldexp(S, -es - PG_BIAS_F);
         const double sc = ldexp(1.0, -es), c0s = ldexp(c0, -es), ujs = ldexp(uj, -es);
         tl.template mark<4>(c0s + ujs + sc);          // zero test, exponent, scaled constants
-        gdouble2* dst = (gdouble2*)(wr + (size_t)t * colsz) + toff;
+        gdouble2* dst = (gdouble2*)col_at(t) + toff;
         double part = 0.0, pprev = 0.0;
         static_for<0, R>([&](auto kc) __attribute__((always_inline)) {
             constexpr int k = decltype(kc)::value;
@@ -3436,13 +3460,15 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
     if constexpr (SPARSE) {
         // the leading piece up to the first checkpoint as ever; from there PG_LEAN_SPARSE - 1 columns that only stay in registers and
         // one that is stored (an odd leading piece: the two record variables change places once)
-        const uint32_t ck0 = (hi - 1u) % PG_LEAN_SPARSE;
-        for (; t + 1 <= ck0; t += 2) {
-            step(kStore, t, ra, rb2);
-            step(kStore, t + 1, rb2, ra);
+        if constexpr (PHASE == 1) {
+            const uint32_t ck0 = (hi - 1u) % PG_LEAN_SPARSE;
+            for (; t + 1 <= ck0; t += 2) {
+                step(kStore, t, ra, rb2);
+                step(kStore, t + 1, rb2, ra);
+            }
+            if (t <= ck0) { step(kStore, t, ra, rb2); ra = rb2; ++t; }
         }
-        if (t <= ck0) { step(kStore, t, ra, rb2); ra = rb2; ++t; }
-        while (t < hi) {
+        while (hi - t >= PG_LEAN_SPARSE) {   // (phase 1: every column left)
             for (uint32_t g = 0; g + 1u < PG_LEAN_SPARSE / 2u; ++g, t += 2) {
                 step(kNoStore, t, ra, rb2);
                 step(kNoStore, t + 1, rb2, ra);
@@ -3450,6 +3476,13 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
             step(kNoStore, t, ra, rb2);
             step(kStore, t + 1, rb2, ra);
             t += 2;
+        }
+        if constexpr (PHASE == 3) {   // the piece behind the half's last checkpoint: a refill segment's, like every other column
+            for (; t + 1 < hi; t += 2) {
+                step(kNoStore, t, ra, rb2);
+                step(kNoStore, t + 1, rb2, ra);
+            }
+            if (t < hi) step(kNoStore, t, ra, rb2);
         }
     } else {
         for (; t + 1 < hi; t += 2) {
@@ -3469,7 +3502,7 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
 
 template <int PHASE, int R, bool TRI, bool SPARSE = false>   // (SPARSE, PHASE 5: see lean_forward)
 DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint32_t chunk) {
-    static_assert(!SPARSE || (PHASE == 1 && !TRI), "sparse stores: phase 1 of full-column lean chains");
+    static_assert(!SPARSE || ((PHASE == 1 || PHASE == 3) && !TRI), "sparse stores: phases 1 and 3 of full-column lean chains");
     constexpr int HP = 64;
     constexpr uint32_t RMASK = (1u << R) - 1u;
     const int64_t mid = C / 2, K = dc.chunk_cols;
@@ -3480,7 +3513,12 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         if (top < 0) return;
         bot = top - K + 1 > 0 ? top - K + 1 : 0;
     }
-    if constexpr (PHASE == 5) { top = (int64_t)chunk - 1; bot = (int64_t)chunk - (int64_t)(PG_LEAN_SPARSE - 1u); }
+    bool seg2 = false;   // PHASE 5: a segment of phase 2 (see lean_forward)
+    if constexpr (PHASE == 5) {
+        top = (int64_t)chunk - 1; bot = (int64_t)chunk - (int64_t)(PG_LEAN_SPARSE - 1u);
+        seg2 = (int64_t)chunk <= mid;
+        if (seg2) bot = top + 1 > (int64_t)PG_LEAN_SPARSE ? top + 1 - (int64_t)PG_LEAN_SPARSE : 0;
+    }
     if (top < bot) return;
     const int64_t t0 = PHASE == 1 ? top - 1 : top;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -3502,7 +3540,14 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
     if constexpr (PHASE == 3) {
         gdouble* scr = (gdouble*)dc.scratch;
         wr = scr + (size_t)(PG_SCR_BUF(chunk) * 2u + 1u) * (size_t)K * colsz - (size_t)bot * colsz;
-        if (chunk > 0) resume = (gcdouble*)(scr + (size_t)(PG_SCR_BUF(chunk - 1u) * 2u + 1u) * (size_t)K * colsz);
+        if constexpr (SPARSE) { if (chunk > 0) resume = (gcdouble*)dc.ckpt + ((size_t)dc.ckpt_slots + (size_t)(mid - 1 - top) / PG_LEAN_SPARSE) * colsz; }
+        else if (chunk > 0) resume = (gcdouble*)(scr + (size_t)(PG_SCR_BUF(chunk - 1u) * 2u + 1u) * (size_t)K * colsz);
+    }
+    if constexpr (PHASE == 5) if (seg2) {   // (see lean_forward; checkpoint 0 is phase 1's last column, fwd[mid])
+        const size_t m = (size_t)(mid - 1 - top) / PG_LEAN_SPARSE;
+        const int64_t ci = (mid - 1 - top) / K, ctop = mid - 1 - ci * K;
+        if (m) resume = (gcdouble*)dc.ckpt + ((size_t)dc.ckpt_slots + m) * colsz;
+        wr = (gdouble*)dc.scratch + (size_t)(PG_SCR_BUF((uint32_t)ci) * 2u + 1u) * (size_t)K * colsz - (size_t)(ctop - K + 1 > 0 ? ctop - K + 1 : 0) * colsz;
     }
     int64_t cbot = bot;   // PHASE 4 (see lean_forward): the lowest column of the chunk being stored
     if constexpr (PHASE == 4) {
@@ -3544,8 +3589,12 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
             lean_store(dst + (size_t)q * HP, v2f64{a, b});
         }
     };
+    auto col_at = [&](int64_t c) __attribute__((always_inline)) -> gdouble* {   // where column c is stored
+        if constexpr (SPARSE && PHASE == 3) return (gdouble*)dc.ckpt + ((size_t)dc.ckpt_slots + (size_t)(mid - c) / PG_LEAN_SPARSE) * colsz;   // (checkpoints only)
+        else return wr + (size_t)c * colsz;
+    };
     auto store_col = [&](int64_t c, const double (&v)[R]) {
-        gdouble2* dst = (gdouble2*)(wr + (size_t)c * colsz) + toff;
+        gdouble2* dst = (gdouble2*)col_at(c) + toff;
 #pragma unroll
         for (int k = 0; k < R; k += 2) put_pair(dst, k >> 1, v[k], v[k + 1]);
     };
@@ -3645,7 +3694,7 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         const double uj = fma(k2, Sw, ucol);
         const double Snew = kap * Sw;  // = sum(beta'_t)
         Sy = Snew;                     // (1 behind an all-zero column, below)
-        gdouble2* dst = (gdouble2*)(wr + (size_t)t * colsz) + toff;
+        gdouble2* dst = (gdouble2*)col_at(t) + toff;
         double part = 0.0, yprev = 0.0;
         const bool zero = !(Snew > 0.0);   // beta~_t is all zero (below)
         static_for<0, R>([&](auto kc) __attribute__((always_inline)) {
@@ -3712,13 +3761,15 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         return;
     }
     if constexpr (SPARSE) {   // (see lean_forward)
-        const int64_t ckh = mid + (int64_t)pg_sparse_segments(C, 1u) * (int64_t)PG_LEAN_SPARSE;   // the first checkpoint on the way down
-        for (; t - 1 >= ckh; t -= 2) {
-            step(kStore, t, cur, rb2);
-            step(kStore, t - 1, rb2, cur);
+        if constexpr (PHASE == 1) {
+            const int64_t ckh = mid + (int64_t)pg_sparse_segments(C, 1u) * (int64_t)PG_LEAN_SPARSE;   // the first checkpoint on the way down
+            for (; t - 1 >= ckh; t -= 2) {
+                step(kStore, t, cur, rb2);
+                step(kStore, t - 1, rb2, cur);
+            }
+            if (t >= ckh) { step(kStore, t, cur, rb2); cur = rb2; --t; }
         }
-        if (t >= ckh) { step(kStore, t, cur, rb2); cur = rb2; --t; }
-        while (t >= bot) {
+        while (t - bot >= (int64_t)PG_LEAN_SPARSE - 1) {   // (phase 1: every column left)
             for (uint32_t g = 0; g + 1u < PG_LEAN_SPARSE / 2u; ++g, t -= 2) {
                 step(kNoStore, t, cur, rb2);
                 step(kNoStore, t - 1, rb2, cur);
@@ -3726,6 +3777,13 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
             step(kNoStore, t, cur, rb2);
             step(kStore, t - 1, rb2, cur);
             t -= 2;
+        }
+        if constexpr (PHASE == 3) {
+            for (; t - 1 >= bot; t -= 2) {
+                step(kNoStore, t, cur, rb2);
+                step(kNoStore, t - 1, rb2, cur);
+            }
+            if (t >= bot) step(kNoStore, t, cur, rb2);
         }
     } else {
         for (; t - 1 >= bot; t -= 2) {
@@ -4136,8 +4194,9 @@ DEVI void sweep_lean_body(const DevContig* __restrict__ contigs, uint32_t chunk,
     const uint32_t C = (uint32_t)__builtin_amdgcn_readfirstlane((int)*dc.n_cols);
     if (C == 0) return;
     const unsigned long long t_begin = kChainProf ? __builtin_amdgcn_s_memtime() : 0ull;
-    if constexpr (PHASE == 1 && !TRI) {
-        if (dc.sparse) {   // (uniform; the two bodies are separate code: the dense one is what it was)
+    if constexpr ((PHASE == 1 || PHASE == 3) && !TRI) {
+        // (phase 3: a single column is the forward role's initial one, which no refill segment forms: stored as ever)
+        if (PHASE == 1 ? dc.sparse != 0u : (dc.sparse2 != 0u && C >= 2u)) {   // (uniform; the two bodies are separate code: the dense one is what it was)
             if (blockIdx.y == 0) lean_forward<PHASE, R, TRI, true>(dc, sh, C, chunk);
             else lean_backward<PHASE, R, TRI, true>(dc, sh, C, chunk);
         } else {
@@ -4161,10 +4220,12 @@ DEVI void sweep_lean_body(const DevContig* __restrict__ contigs, uint32_t chunk,
 //  independent of each other: the blocks stride over the launch's list (both roles of every chain, `q` = chunk_cols / PG_LEAN_SPARSE
 //  segments each, the chain the fastest index so that a short chain's empty items spread over all blocks).  Placed like k_post: as
 //  many blocks as the chains leave CUs idle, with dynamic LDS that does not fit next to a sweep workgroup (PG_REFILL_PLACEMENT_LDS).
+//  `phase2` (DevContig::sparse2 chains): the segments of chunk `chunk` itself instead of its partner ranges — from the checkpoints
+//  the chunk sweep left in DevContig::ckpt into the scratch buffer k_post reads (pg_sparse2_segment).
 // ------------------------------------------------------------------------------------------
 #define PG_REFILL_PLACEMENT_LDS (100 * 1024)
 template <int R>
-__global__ __launch_bounds__((64 * 64 / R)) void k_refill_lean(const DevContig* __restrict__ contigs, uint32_t n_contigs, uint32_t chunk, uint32_t q) {
+__global__ __launch_bounds__((64 * 64 / R)) void k_refill_lean(const DevContig* __restrict__ contigs, uint32_t n_contigs, uint32_t chunk, uint32_t q, uint32_t phase2) {
     __shared__ LeanShared<R> sh;
     static_assert(sizeof(LeanShared<R>) + PG_REFILL_PLACEMENT_LDS <= 160 * 1024 && 2 * sizeof(LeanShared<R>) + PG_REFILL_PLACEMENT_LDS > 160 * 1024,
                   "a refill block fits a CU of its own and none that runs a sweep workgroup");
@@ -4172,11 +4233,18 @@ __global__ __launch_bounds__((64 * 64 / R)) void k_refill_lean(const DevContig* 
     for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {   // (everything below is uniform over the block)
         const uint32_t chain = w % n_contigs, role = (w / n_contigs) & 1u, j = w / (2u * n_contigs);
         const DevContig& dc = contigs[chain];
-        if (dc.lean != 1u || dc.tri != 0u || !dc.sparse) continue;
+        if (dc.lean != 1u || dc.tri != 0u || !(phase2 ? dc.sparse2 : dc.sparse)) continue;
         const uint32_t C = (uint32_t)__builtin_amdgcn_readfirstlane((int)*dc.n_cols);
-        const unsigned long long m = (unsigned long long)chunk * q + j + 1u;
-        if (m > pg_sparse_segments(C, role)) continue;
-        const uint32_t ck = pg_sparse_checkpoint(C, role, (uint32_t)m);
+        const unsigned long long m = (unsigned long long)chunk * q + j + (phase2 ? 0u : 1u);
+        uint32_t ck;
+        if (phase2) {
+            uint32_t seg[3];
+            if (!pg_sparse2_segment(C, role, m, seg)) continue;
+            ck = seg[0];
+        } else {
+            if (m > pg_sparse_segments(C, role)) continue;
+            ck = pg_sparse_checkpoint(C, role, (uint32_t)m);
+        }
         __syncthreads();   // (the segment before this one is done with the LDS)
         if (role == 0u) lean_forward<5, R, false>(dc, sh, C, ck);
         else lean_backward<5, R, false>(dc, sh, C, ck);
@@ -7070,7 +7138,8 @@ uint32_t pgk_post_blocks(uint32_t n_contigs, uint32_t chunk_cols, uint32_t* cus_
     return bx ? bx : 1u;
 }
 // the columns of chunk `chunk`'s partner ranges that the sparse phase 1 left out (k_refill_lean), on the CUs the chains leave idle
-void pgk_launch_refill(const DevContig* d_contigs, uint32_t n_contigs, uint32_t chunk_cols, uint32_t chunk, hipStream_t s) {
+// (phase2: the columns of the chunk itself, which a sparse phase 2 left out)
+void pgk_launch_refill(const DevContig* d_contigs, uint32_t n_contigs, uint32_t chunk_cols, uint32_t chunk, int phase2, hipStream_t s) {
     static bool attr_done[PG_MAX_DEVICES];
     if (lds_attr_pending(attr_done))
         (void)hipFuncSetAttribute((const void*)k_refill_lean<16>, hipFuncAttributeMaxDynamicSharedMemorySize, PG_REFILL_PLACEMENT_LDS);
@@ -7081,7 +7150,7 @@ void pgk_launch_refill(const DevContig* d_contigs, uint32_t n_contigs, uint32_t 
     if (const char* e = getenv("PG_REFILL_BLOCKS")) { const long v = strtol(e, nullptr, 0); if (v >= 1 && (uint32_t)v < blocks) blocks = (uint32_t)v; }   // (experiments: fewer)
     if (blocks > 2u * q * n_contigs) blocks = 2u * q * n_contigs;
     if (blocks == 0u) return;
-    hipLaunchKernelGGL((k_refill_lean<16>), dim3(blocks), dim3(256), PG_REFILL_PLACEMENT_LDS, s, d_contigs, n_contigs, chunk, q);
+    hipLaunchKernelGGL((k_refill_lean<16>), dim3(blocks), dim3(256), PG_REFILL_PLACEMENT_LDS, s, d_contigs, n_contigs, chunk, q, phase2 ? 1u : 0u);
 }
 void pgk_launch_post(const DevContig* d_contigs, uint32_t n_contigs, uint32_t chunk_cols, uint32_t chunk, hipStream_t s) {
     static bool attr_done[PG_MAX_DEVICES];

@@ -102,7 +102,7 @@ void pgk_launch_sweep_small(const DevContig* d_contigs, const uint32_t* d_ids, u
 void pgk_launch_sweep_smallx(const DevContig* d_contigs, const uint32_t* d_ids, uint32_t n_ids, int phase, uint32_t chunk, double* d_dump, hipStream_t s);
 uint32_t pgk_post_blocks(uint32_t n_contigs, uint32_t chunk_cols, uint32_t* cus_out);
 void pgk_launch_post(const DevContig* d_contigs, uint32_t n_contigs, uint32_t chunk_cols, uint32_t chunk, hipStream_t s);
-void pgk_launch_refill(const DevContig* d_contigs, uint32_t n_contigs, uint32_t chunk_cols, uint32_t chunk, hipStream_t s);
+void pgk_launch_refill(const DevContig* d_contigs, uint32_t n_contigs, uint32_t chunk_cols, uint32_t chunk, int phase2, hipStream_t s);
 void pgk_launch_stream_handshake(uint32_t* d_words, hipStream_t s, hipStream_t s2);
 void pgk_launch_phase2_persistent(const DevContig* d_contigs, uint32_t n_contigs, uint32_t post_blocks, hipStream_t s, hipStream_t s2);
 void pgk_launch_emission_single(const DevContig* d_contig, DevTable tab, uint32_t v, double* out_m, int* out_e, hipStream_t s);

@@ -467,6 +467,11 @@ struct pg_job {
     // only its checkpoints and k_refill_lean forms the columns between them on the second stream, chunk by chunk in front of k_post
     // (DevContig::sparse; PG_KERNELS=nosparse: every column by the chain)
     bool sparse = false;
+    // ... and every chain with columns is such a chain: the chunk sweeps of phase 2 store only their checkpoints too, into an area
+    // of their own (DevContig::sparse2), and k_refill_lean forms each chunk's columns behind its sweep on the second stream — which
+    // then owns the scratch buffers alone: the sweeps wait for no k_post (PG_KERNELS=nosparse2: dense chunk sweeps)
+    bool sparse2 = false;
+    std::vector<hipEvent_t> ev_chunk;   // sparse2: one "sweep done" event per chunk (the sweeps run chunks ahead of the stream that waits for them)
     // The pipelined first run of a one-shot job (job_build with cache_arena: upload and run inside ONE call, the host arrays stay
     // valid): the inputs of the LONG chains (group A: the job's wall time) are uploaded first and their preparation + phase 1
     // start while the other chains' inputs (group B, most of the bytes) are still crossing PCIe; B's index pass, preparation and
@@ -564,6 +569,7 @@ extern "C" void pg_job_destroy(pg_job* job) {
     }
     if (job->events2)
         for (int q = 0; q < (int)PG_SCRATCH_BUFS; ++q) { hipEventDestroy(job->ev_sweep[q]); hipEventDestroy(job->ev_post[q]); }
+    for (hipEvent_t e : job->ev_chunk) hipEventDestroy(e);
     if (job->arena) {
         if (job->cache_arena) g_pool.put(job->device, job->arena, job->arena_bytes);
         else hipFree(job->arena);
@@ -866,11 +872,13 @@ int upload_inputs(pg_job* job, const pg_contig_batch* batches, const std::vector
 //                       (one launch each, chunks handed over on the device) instead of one launch per chunk (k_sweep_lean<3> + k_post).
 //                       Opt-in: measured at par or behind on the whole-genome job (profiles/r06_persist.txt).  nopersist: the default, spelled out
 //   nosparse            phase 1 of the lean chains of chunked jobs stores every column itself (no k_refill_lean) — cross-check
+//   nosparse2           the chunk sweeps of phase 2 store every column into the scratch buffers although phase 1 is sparse (no second
+//                       k_refill_lean per chunk; the sweeps wait for k_post to free a buffer) — cross-check
 //   nosplit             the 16-path chains of fused jobs prepare every variant per sample (k_prep*, k_records, k_bins_lean2 / _x) instead of
 //                       taking the split path (pg_split.h)
 struct KernelChoice {
     bool general = false, generic = false, nolean2 = false, notri = false, nocls4 = false, prepwave = false, fullcols = false, nosmall2 = false, nosplit = false;
-    bool persist = false, noleanx2 = false, nowidef = false, nosparse = false;
+    bool persist = false, noleanx2 = false, nowidef = false, nosparse = false, nosparse2 = false;
     int leanx = -1, small = -1;   // -1: by the job, 0 / 1: forced
     std::string unknown;          // a token this list does not know
 };
@@ -890,6 +898,7 @@ KernelChoice kernel_choice() {
         else if (tok == "noleanx2") k.noleanx2 = true;
         else if (tok == "nowidef") k.nowidef = true;
         else if (tok == "nosparse") k.nosparse = true;
+        else if (tok == "nosparse2") k.nosparse2 = true;
         else if (tok == "persist") k.persist = true; else if (tok == "nopersist") k.persist = false;
         else if (!tok.empty()) k.unknown = tok;   // (a typo would quietly test the default path against itself: job creation fails)
         tok.clear();
@@ -1106,7 +1115,7 @@ void choose_job_mode(pg_job* job, const BuildArgs& a, size_t chunk_cap) {
     const KernelChoice& kc = a.kc;
     const pg_hmm_params& params = a.params;
     const uint32_t n_chains = (uint32_t)a.specs.size();
-    job->persist = false; job->post_blocks = 0; job->any_split = false; job->sparse = false;
+    job->persist = false; job->post_blocks = 0; job->any_split = false; job->sparse = false; job->sparse2 = false;
     {
         // k_sweep_small16 packs four H = 16 half-chains into a wave: a throughput kernel.  A single chain is faster on the
         // general kernel (four states per lane instead of sixteen: 375 vs 470 ns per column); PG_KERNELS=small / nosmall forces.
@@ -1197,6 +1206,10 @@ void choose_job_mode(pg_job* job, const BuildArgs& a, size_t chunk_cap) {
             uint32_t cus = 0;
             (void)pgk_post_blocks(n_chains, job->chunk_cols, &cus);
             job->sparse = cus >= 2u * n_chains + n_chains;
+            // the sparse phase 2: the scratch buffers are the second stream's alone only if no chain's chunk sweep writes them
+            bool only_lean = true;
+            for (const ChainSpec& sp : a.specs) { const IndexHost& x = job->index[sp.index]; if (x.V && !x.lean) only_lean = false; }
+            job->sparse2 = job->sparse && only_lean && !kc.nosparse2;
         }
     }
     // ---- the split path: which index contigs' chains take it (pg_device.h) ---------------------------
@@ -1258,7 +1271,7 @@ struct ChainKernels {
     BinsKernel bins_one = BN_NONE;   // ... those of a k_sweep_small16x chain left with a single column
     BinsKernel bins_wide = BN_NONE;  // ... and those of its wide columns
     // the values of the DevContig fields of the same names
-    uint32_t lean = 0, leanx = 0, leanx2 = 0, tri = 0, cls4 = 0, small = 0, smallx = 0, widef = 0, T = 0, sparse = 0;
+    uint32_t lean = 0, leanx = 0, leanx2 = 0, tri = 0, cls4 = 0, small = 0, smallx = 0, widef = 0, T = 0, sparse = 0, sparse2 = 0;
 };
 
 // Every chain's kernels from its index contig's class and the job's mode; from them the two launch masks.
@@ -1287,6 +1300,7 @@ std::vector<ChainKernels> choose_chain_kernels(pg_job* job, const BuildArgs& a) 
         // with triangle stores (k_sweep_tri1)
         k.leanx = (k.tri && !x.lean && kc.leanx != 0) ? 2u : (x.leanx ? 1u : 0u);
         k.sparse = (job->sparse && k.lean == 1u && k.tri == 0u) ? 1u : 0u;   // (chunked jobs have no triangle chains)
+        k.sparse2 = (job->sparse2 && k.sparse) ? 1u : 0u;
         k.prep = x.split ? (x.all_sb ? PREP_S_BI : PREP_S_LISTS) : x.prep_fast == 1u ? PREP_BI : x.prep_fast == 2u ? PREP_BI_LISTS : PREP_W;
 
         const SweepKernel own = x.HP >= 256 ? SW_GENERIC : (kc.generic && x.HP >= 64) ? SW_GENERIC64
@@ -1333,7 +1347,7 @@ std::string plan_text(const pg_job* job, const BuildArgs& a, const std::vector<C
         auto name = [&](SweepKernel s, int phase) { return sweep_name(a.kc.generic && s >= SW_HP16 && s <= SW_HP128 ? SW_GENERIC : s, phase); };
         std::string p2, bins;
         if (k.post == POST_LOOP) { p2 = name(k.phase2, 4) + " (one launch, all chunks) + k_post_loop"; bins = "(k_post_loop)"; }
-        else if (k.post == POST_CHUNKS) { p2 = name(k.phase2, 3) + " chunks + " + (k.sparse ? "k_refill_lean + " : "") + "k_post"; bins = "(k_post)"; }
+        else if (k.post == POST_CHUNKS) { p2 = name(k.phase2, 3) + (k.sparse2 ? " chunks (sparse: every 64th column stored) + k_refill_lean (both halves) + " : k.sparse ? " chunks + k_refill_lean + " : " chunks + ") + "k_post"; bins = "(k_post)"; }
         else {
             p2 = name(k.phase2, 2);
             if (k.tri && k.phase2 == k.general) p2 += " (triangle ring)";
@@ -1358,7 +1372,7 @@ std::string plan_text(const pg_job* job, const BuildArgs& a, const std::vector<C
 // offsets of what the job as a whole and every chain own; those of an index contig's arrays are IndexHost's (o_*), a chain's
 // sample arrays ChainHost's
 struct ChainOffsets { size_t sync, wcols, wlist, aux, frec, scratch, wide, vpair, xbuf, prof, fback, fscale, bscale, bsum, vrec, colrec, fwd, part, cprec,
-                      vtq, vback, vbest, hap1, hap2; };
+                      vtq, vback, vbest, hap1, hap2, ckpt; };
 struct ArenaLayout {
     size_t o_contigs, o_reps, o_contigs_g, o_reps_g, o_small, o_dump, o_handshake, o_err, o_lik, o_likexp, o_ncols, o_ixerr;
     size_t zero_lo, zero_hi, ix_lo, ix_hi, vrec_lo, vrec_hi, srec_lo, srec_hi;   // the runs that are zeroed as one
@@ -1477,6 +1491,8 @@ ArenaLayout layout_arena(pg_job* job, const BuildArgs& a, const std::vector<Chai
         p.vtq = take(vit ? (size_t)x.V * 8 * sizeof(double) : 0);
         p.vback = take(vit ? (size_t)x.V * x.H * x.HP * sizeof(uint16_t) : 0);
         p.scratch = take(job->chunked ? (size_t)2 * PG_SCRATCH_BUFS * job->chunk_cols * x.HP * x.HP * sizeof(double) : 0);
+        // (sparse phase 2: every checkpoint of the chain's phase 2, never reused within a run)
+        p.ckpt = take(k.sparse2 ? (size_t)2 * pg_sparse2_slots(x.V) * x.HP * x.HP * sizeof(double) : 0);
         p.wide = take(x.wide_bytes);
         p.vpair = take(x.split ? 0 : (size_t)x.V * pg_pair_bytes(x.pair_n));
         p.xbuf = take((x.HP >= 256 || (a.kc.generic && x.HP >= 64)) ? (size_t)2 * x.HP * x.HP * sizeof(double) : 0);
@@ -1527,6 +1543,14 @@ int create_device_objects(pg_job* job, char* err, size_t errlen) {
         if ((he = hipEventCreateWithFlags(&job->ev_post[q], hipEventDisableTiming)) != hipSuccess) return hip_fail(err, errlen, "hipEventCreate", he);
     }
     job->events2 = true;
+    if (job->sparse2) {
+        job->ev_chunk.reserve(job->n_chunks);
+        for (uint32_t q = 0; q < job->n_chunks; ++q) {
+            hipEvent_t e;
+            if ((he = hipEventCreateWithFlags(&e, hipEventDisableTiming)) != hipSuccess) return hip_fail(err, errlen, "hipEventCreate", he);
+            job->ev_chunk.push_back(e);
+        }
+    }
     return PG_OK;
 }
 
@@ -1592,6 +1616,7 @@ std::vector<DevContig> fill_descriptors(pg_job* job, const BuildArgs& a, const s
         d.vpair = A + p.vpair; d.xbuf = (double*)(A + p.xbuf);
         d.frec = (double*)(A + p.frec);
         d.lean = k.lean; d.small = k.small; d.smallx = k.smallx; d.leanx = k.leanx; d.leanx2 = k.leanx2; d.cls4 = k.cls4; d.widef = k.widef; d.tri = k.tri; d.sparse = k.sparse;
+        d.sparse2 = k.sparse2; d.ckpt = (double*)(A + p.ckpt); d.ckpt_slots = pg_sparse2_slots(x.V);
         d.col_stride = d.tri ? 2304u : x.HP * x.HP;
         d.aux = A + p.aux; d.aux_idx = ((d.smallx == 2u || x.widef) && x.aux_bytes) ? (const uint32_t*)(A + x.o_auxidx) : nullptr;
         if ((d.smallx == 2u || x.widef) && x.wide_bytes && x.n_wide_cand) {
@@ -2166,7 +2191,24 @@ extern "C" int pg_job_run(pg_job* job, void* stream_, char* err, size_t errlen) 
             // sparse phase 1: the refill of chunk i's partner columns (k_refill_lean) goes in front of k_post(i) on the second stream —
             // beside the sweep of chunk i, behind the posteriors of chunk i - 1; it needs phase 1 ended, nothing else
             if (job->sparse) HIP_TRY(hipStreamWaitEvent(s2, job->ev[4], 0));
-            for (uint32_t i = 0; i < job->n_chunks; ++i) {
+            // sparse phase 2: the chunk sweeps store their checkpoints into an area of their own and touch no scratch buffer — they
+            // wait for nothing.  The second stream forms chunk i's columns behind sweep i (k_refill_lean from those checkpoints) and
+            // then its posteriors: it writes and reads the scratch buffers alone, in order, so their rotation needs no event
+            if (job->sparse2) for (uint32_t i = 0; i < job->n_chunks; ++i) {
+                pgk_launch_sweep_chunk(job->d_contigs, n, job->hp_mask, i, s);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipEventRecord(job->ev_chunk[i], s));
+                pgk_launch_refill(job->d_contigs, n, job->chunk_cols, i, 0, s2);
+                HIP_TRY(hipStreamWaitEvent(s2, job->ev_chunk[i], 0));
+                pgk_launch_refill(job->d_contigs, n, job->chunk_cols, i, 1, s2);
+                pgk_launch_post(job->d_contigs, n, job->chunk_cols, i, s2);
+                HIP_TRY(hipGetLastError());
+                if (i + 1u == job->n_chunks) {
+                    HIP_TRY(hipEventRecord(job->ev_post[0], s2));
+                    HIP_TRY(hipStreamWaitEvent(s, job->ev_post[0], 0));
+                }
+            }
+            else for (uint32_t i = 0; i < job->n_chunks; ++i) {
                 const int b = (int)PG_SCR_BUF(i);
                 if (i >= PG_SCRATCH_BUFS) HIP_TRY(hipStreamWaitEvent(s, job->ev_post[b], 0));
                 pgk_launch_sweep_chunk(job->d_contigs, n, job->hp_mask, i, s);
@@ -2174,14 +2216,14 @@ extern "C" int pg_job_run(pg_job* job, void* stream_, char* err, size_t errlen) 
                 pgk_launch_sweep_smallx(job->d_contigs, job->d_smallx, job->n_smallx, 3, i, job->d_dump, s);
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipEventRecord(job->ev_sweep[b], s));
-                if (job->sparse) pgk_launch_refill(job->d_contigs, n, job->chunk_cols, i, s2);
+                if (job->sparse) pgk_launch_refill(job->d_contigs, n, job->chunk_cols, i, 0, s2);
                 HIP_TRY(hipStreamWaitEvent(s2, job->ev_sweep[b], 0));
                 pgk_launch_post(job->d_contigs, n, job->chunk_cols, i, s2);
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipEventRecord(job->ev_post[b], s2));
             }
             }
-            if (!persist_now) for (uint32_t q = 0; q < PG_SCRATCH_BUFS && q < job->n_chunks; ++q) HIP_TRY(hipStreamWaitEvent(s, job->ev_post[q], 0));
+            if (!persist_now && !job->sparse2) for (uint32_t q = 0; q < PG_SCRATCH_BUFS && q < job->n_chunks; ++q) HIP_TRY(hipStreamWaitEvent(s, job->ev_post[q], 0));
             HIP_TRY(hipEventRecord(job->ev[5], s));  // "k_sweep_phase2" = all chunks incl. their posteriors
             HIP_TRY(hipEventRecord(job->ev[6], s));  // (no k_bins in this mode)
         }
@@ -2431,6 +2473,17 @@ extern "C" int pg_sparse_segment(uint32_t n_columns, uint32_t chunk_cols, uint32
     const uint32_t ck = pg_sparse_checkpoint(n_columns, role, (uint32_t)m);
     if (out) { out[0] = ck; out[1] = role == 0u ? ck + 1u : ck - (PG_LEAN_SPARSE - 1u); out[2] = role == 0u ? ck + (PG_LEAN_SPARSE - 1u) : ck - 1u; }
     return 1;
+}
+// ... and of the sparse phase 2 (pg_sparse2_*): segment j of chunk `chunk`; out = {checkpoint, lowest column, highest column}
+extern "C" int pg_sparse_chunk_segment(uint32_t n_columns, uint32_t chunk_cols, uint32_t chunk, uint32_t role, uint32_t j, uint32_t out[3]) {
+    if (role > 1u || chunk_cols == 0u || chunk_cols % PG_LEAN_SPARSE != 0u || j >= chunk_cols / PG_LEAN_SPARSE) return -1;
+    uint32_t seg[3];
+    if (!pg_sparse2_segment(n_columns, role, (unsigned long long)chunk * (chunk_cols / PG_LEAN_SPARSE) + j, seg)) return 0;
+    if (out) { out[0] = seg[0]; out[1] = seg[1]; out[2] = seg[2]; }
+    return 1;
+}
+extern "C" int pg_sparse_chunk_stored_by_chain(uint32_t n_columns, uint32_t role, uint32_t column) {
+    return role <= 1u && column < n_columns && pg_sparse2_stored(n_columns, role, column) ? 1 : 0;
 }
 extern "C" int pg_sparse_stored_by_chain(uint32_t n_columns, uint32_t role, uint32_t column) {
     return role <= 1u && column < n_columns && pg_sparse_stored(n_columns, role, column) ? 1 : 0;
