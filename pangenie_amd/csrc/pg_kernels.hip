@@ -3169,10 +3169,14 @@ DEVI double lean_total(const LeanShared<R>& sh, uint32_t pb) {   // (kLeanPreTot
 
 // SPARSE (PHASE 1 of DevContig::sparse chains): only the checkpoints of pg_device.h's pg_sparse_* are stored — the step is compiled
 // twice, with and without its column stores.  PHASE 5: a refill segment (k_refill_lean) — `chunk` = the checkpoint column it resumes
-// from; it stores the PG_LEAN_SPARSE - 1 columns behind it and none of the per-column scalars, which are the chain's.
+// from; it stores the PG_LEAN_SPARSE - 1 columns behind it.
 // SPARSE, PHASE 3 (DevContig::sparse2 chains): the chunk sweep stores the checkpoints of pg_sparse2_* alone, into DevContig::ckpt,
 // and resumes from there; a PHASE 5 segment whose checkpoint lies in phase 2 (at or behind the phase boundary) forms the chunk's
 // columns from them — PG_LEAN_SPARSE columns, its closing checkpoint included — into the scratch slots k_post reads.
+// The per-column scalars go with the columns: fscale[c] / bscale[c] is written by whoever writes column c — the chain at the columns
+// it stores (its store-free step parks no scalar), a segment at the columns it forms, its closing checkpoint excepted, which is the
+// chain's: one writer per entry and run.  Their only readers (k_post: 1 / (fscale bscale)) come behind the refill of the column's
+// chunk.  bsum is the chain's alone, at the columns it stores: a launch or a segment resumes (Sy = bsum[top + 1]) from such a column.
 template <int PHASE, int R, bool TRI, bool SPARSE = false>
 DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint32_t chunk) {
     static_assert(!SPARSE || ((PHASE == 1 || PHASE == 3) && !TRI), "sparse stores: phases 1 and 3 of full-column lean chains");
@@ -3287,6 +3291,10 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         if constexpr (PHASE != 5) if (wave == 0) fallback[cprev] = 1;
     };
 
+    // PHASE 5: a segment writes the scale of every column it forms but the one the chain stored — the closing checkpoint of a
+    // phase-2 segment (every entry of fscale has one writer per run)
+    uint32_t noscal = ~0u;
+    if constexpr (PHASE == 5) if (seg2 && pg_sparse2_stored(C, 0u, hi - 1u)) noscal = hi - 1u;
     ColScalars fsc{&sh.scal[0][0]};
     double x[R];
     {
@@ -3412,8 +3420,13 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         });
         tl.template mark<6>(part);                    // the other seven row pairs: states, stores, next emissions
         lean_put_sums<R>(sh, t & 1u, wave, lane, part);
-        if constexpr (PHASE != 5) if (wave == 0) {  // (scalar branch)
-            fsc.put(lane, t, m);
+        if constexpr (SPARSE) {
+            // the scale of a column is written by whoever writes the column: a store-free step parks nothing and tests for no flush
+            // (one wave's extra instructions in front of the barrier are everybody's wait); a checkpoint is one column in 64 — its
+            // scale goes straight to memory (every lane of the wave the same address and value: no exec juggling)
+            if constexpr (STORE) if (wave == 0) fscale[t] = m;
+        } else if (wave == 0) {  // (scalar branch)
+            if (PHASE != 5 || t != noscal) fsc.put(lane, t, m);
             if ((t & 63u) == 63u) fsc.flush(fscale, lane, t);
         }
         tl.template mark<7>(0.0);                     // partial sum parked, per-column scalar
@@ -3491,7 +3504,7 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         }
         if (t < hi) step(kStore, t, ra, rb2);
     }
-    if constexpr (PHASE != 5) if (wave == 0 && fsc.valid) fsc.flush(fscale, lane, hi - 1);
+    if constexpr (!SPARSE) if (wave == 0 && fsc.valid) fsc.flush(fscale, lane, hi - 1);   // (a segment is not aligned to the 64-column blocks: what is left of its last one)
     if (kLeanTimeline && tid == 0) tl.write(dc.prof + 32);
     {   // the last column of this phase may itself have summed to zero
         const uint32_t pb = (hi - 1) & 1u;
@@ -3599,6 +3612,8 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         for (int k = 0; k < R; k += 2) put_pair(dst, k >> 1, v[k], v[k + 1]);
     };
 
+    int64_t noscal = -1;   // PHASE 5 (see lean_forward): the closing checkpoint of a phase-2 segment — its scale is the chain's
+    if constexpr (PHASE == 5) if (seg2 && pg_sparse2_stored(C, 1u, (uint32_t)bot)) noscal = bot;
     ColScalars bsc{&sh.scal[0][0]}, bsm{&sh.scal[1][0]};
     double w[R], Sy;
     FRec cur = read_frec(sh, 0);  // record t0+1: constants of the gap t0 -> t0+1, emission of column t0+1
@@ -3656,7 +3671,9 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         int es = exponent_of(Sy) - PG_BIAS_B;
         es = es < -900 ? -900 : es;
         const double m = ldexp(Sy, -es - PG_BIAS_B);
-        if constexpr (PHASE != 5) if (wave == 1) { asm volatile("" ::: "memory"); bsc.put(lane, (uint64_t)t, m); }   // (the per-column scalars are collected by two DIFFERENT waves: the waves meet
+        if constexpr (SPARSE) {   // (see lean_forward: the scalars of a column go with the column — a store-free step has none)
+            if constexpr (STORE) if (wave == 1) { asm volatile("" ::: "memory"); bscale[t] = m; }
+        } else if (wave == 1 && (PHASE != 5 || t != noscal)) { asm volatile("" ::: "memory"); bsc.put(lane, (uint64_t)t, m); }   // (the per-column scalars are collected by two DIFFERENT waves: the waves meet
                                                         // at a barrier every column, one wave's extra instructions are everybody's wait)
         double k0 = ldexp(cur.c0, -es), k1 = ldexp(cur.c1, -es), k2 = ldexp(cur.c2, -es), kap = ldexp(cur.kappa, -es);
         pin_here(k0); pin_here(k1); pin_here(k2); pin_here(kap);   // (in front of the barrier, not behind it)
@@ -3723,12 +3740,16 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         }
         tl.template mark<7>(part);                    // the other seven row pairs: states, stores, next emissions
         lean_put_sums<R>(sh, (uint32_t)(t - 1) & 1u, wave, lane, part);
-        if constexpr (PHASE != 5) {
+        if constexpr (SPARSE) {
+            if constexpr (STORE) if (wave == 2) { asm volatile("" ::: "memory"); bsum[t] = Snew; }   // (what a launch or a segment resumes from)
+        } else if constexpr (PHASE != 5) {
             if (wave == 2) { asm volatile("" ::: "memory"); bsm.put(lane, (uint64_t)t, Snew); }   // (a branch, not predication: three of the four waves skip it)
             if (((uint64_t)t & 63u) == 0u) {
                 if (wave == 1) bsc.flush(bscale, lane, (uint64_t)t);
                 if (wave == 2) bsm.flush(bsum, lane, (uint64_t)t);
             }
+        } else {   // (a segment: the scales of the columns it forms, and no bsum)
+            if (wave == 1 && ((uint64_t)t & 63u) == 0u) bsc.flush(bscale, lane, (uint64_t)t);
         }
         tl.template mark<8>(0.0);                     // partial sum parked, per-column scalars
         tl.template fold<8>();
@@ -3792,9 +3813,9 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         }
         if (t >= bot) step(kStore, t, cur, rb2);
     }
-    if constexpr (PHASE != 5) {
+    if constexpr (!SPARSE) {
         if (wave == 1 && bsc.valid) bsc.flush(bscale, lane, (uint64_t)bot);
-        if (wave == 2 && bsm.valid) bsm.flush(bsum, lane, (uint64_t)bot);
+        if (PHASE != 5 && wave == 2 && bsm.valid) bsm.flush(bsum, lane, (uint64_t)bot);
     }
     if (kLeanTimeline && tid == 0) tl.write(dc.prof + 48);
 }
@@ -4216,7 +4237,9 @@ DEVI void sweep_lean_body(const DevContig* __restrict__ contigs, uint32_t chunk,
 // ------------------------------------------------------------------------------------------
 //  k_refill_lean : the columns a sparse phase 1 (DevContig::sparse) left out, for the chunk that k_post reads next.  A workgroup is
 //  the four-wave lean step itself (lean_forward / lean_backward, PHASE 5): it resumes from a checkpoint and stores the
-//  PG_LEAN_SPARSE - 1 columns behind it — the bits the chain would have stored, from the same instructions.  Segments are
+//  PG_LEAN_SPARSE - 1 columns behind it — the bits the chain would have stored, from the same instructions — and with each column
+//  its scale (fscale[c] of a forward segment, bscale[c] of a backward one: the step's own m), which the chain no longer writes for
+//  a column it does not store; staged through ColScalars and flushed where a segment crosses a 64-column block and where it ends.  Segments are
 //  independent of each other: the blocks stride over the launch's list (both roles of every chain, `q` = chunk_cols / PG_LEAN_SPARSE
 //  segments each, the chain the fastest index so that a short chain's empty items spread over all blocks).  Placed like k_post: as
 //  many blocks as the chains leave CUs idle, with dynamic LDS that does not fit next to a sweep workgroup (PG_REFILL_PLACEMENT_LDS).
