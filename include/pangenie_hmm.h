@@ -230,6 +230,11 @@ int pg_sparse_stored_by_chain(uint32_t n_columns, uint32_t role, uint32_t column
  * pg_sparse_chunk_stored_by_chain: 1 if the chain itself stores `column` of its role's phase-2 half. */
 int pg_sparse_chunk_segment(uint32_t n_columns, uint32_t chunk_cols, uint32_t chunk, uint32_t role, uint32_t j, uint32_t out[3]);
 int pg_sparse_chunk_stored_by_chain(uint32_t n_columns, uint32_t role, uint32_t column);
+/* Such a job runs phase 1 as one launch per piece: the phase-1 columns of a role whose partner chunk of phase 2 lies in
+ * [piece * piece_chunks, (piece + 1) * piece_chunks), the farthest piece first; the partner columns of a piece's chunks are refilled
+ * beside the pieces behind it (pg_job_plan names the number of pieces; PG_PIECE_CHUNKS sets piece_chunks).  Returns 1 and
+ * out = {lowest, highest column of the piece}, 0 when the role has no column that far from the phase boundary, -1 as above. */
+int pg_sparse_piece_range(uint32_t n_columns, uint32_t chunk_cols, uint32_t piece_chunks, uint32_t piece, uint32_t role, uint32_t out[2]);
 /* Elapsed milliseconds of the Viterbi kernels (run_phasing) of the LAST pg_job_run, hipEvents on the launch stream. */
 double pg_job_viterbi_ms(const pg_job* job);
 void pg_job_destroy(pg_job* job);

@@ -157,6 +157,8 @@ def _bind_hip(lib):
     lib.pg_sparse_chunk_segment.restype = C.c_int
     lib.pg_sparse_chunk_stored_by_chain.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     lib.pg_sparse_chunk_stored_by_chain.restype = C.c_int
+    lib.pg_sparse_piece_range.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p]
+    lib.pg_sparse_piece_range.restype = C.c_int
     lib.pg_job_kernel_ms.argtypes = [C.c_void_p, f64p]
     lib.pg_job_kernel_ms.restype = C.c_int
     lib.pg_job_kernel_name.argtypes = [C.c_int]
@@ -299,7 +301,7 @@ HIP_ABI_SYMBOLS = [
     "pg_job_record_calls_ms", "pg_record_calls_from_bins",
     "pg_record_gl_offsets", "pg_job_record_gl", "pg_job_fetch_record_gl", "pg_job_fetch_record_gl_all", "pg_job_device_record_gl",
     "pg_job_record_gl_ms", "pg_record_gl_from_bins", "pg_gl_from_values", "pg_gl_text",
-    "pg_sparse_segment", "pg_sparse_stored_by_chain", "pg_sparse_chunk_segment", "pg_sparse_chunk_stored_by_chain",
+    "pg_sparse_segment", "pg_sparse_stored_by_chain", "pg_sparse_chunk_segment", "pg_sparse_chunk_stored_by_chain", "pg_sparse_piece_range",
 ]
 
 

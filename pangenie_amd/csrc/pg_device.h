@@ -346,6 +346,21 @@ PG_HD inline bool pg_sparse_stored(uint32_t C, uint32_t role, uint32_t c) {
     if (role == 0u) return c >= mid || (mid - 1u - c) % PG_LEAN_SPARSE == 0u || c < (mid - 1u) % PG_LEAN_SPARSE;
     return c < mid || (c - mid) % PG_LEAN_SPARSE == 0u || c > mid + pg_sparse_segments(C, 1u) * PG_LEAN_SPARSE;
 }
+// Phase 1 in pieces (pg_job::pieces): a role's phase-1 columns whose partner chunk of phase 2 lies in [g G, (g + 1) G) are piece g,
+// `piece_cols` = G chunk_cols columns (a multiple of S) counted from the phase boundary — one launch per piece, the farthest piece
+// first, so that the partner columns of a piece's chunks can be refilled while the chain runs the pieces nearer the boundary.  The
+// column in front of a piece (the last one of piece g + 1) is a checkpoint: the piece resumes from what the chain stored anyway.
+// false: the role has no column that far from the boundary; out = {lowest column, highest column}
+#define PG_PIECE_CHUNKS_DEFAULT 4u   // G (profiles/r11_refill_beside_phase1.txt); PG_PIECE_CHUNKS overrides it
+PG_HD inline bool pg_sparse_piece(uint32_t C, uint32_t role, uint32_t piece_cols, uint32_t g, uint32_t out[2]) {
+    const unsigned long long mid = C / 2u, half = role == 0u ? mid : C - mid;
+    const unsigned long long d0 = (unsigned long long)g * piece_cols;   // columns between the piece and the phase boundary
+    if (piece_cols == 0u || piece_cols % PG_LEAN_SPARSE != 0u || d0 >= half) return false;
+    const unsigned long long d1 = half - d0 > piece_cols ? d0 + piece_cols : half;
+    if (role == 0u) { out[0] = (uint32_t)(mid - d1); out[1] = (uint32_t)(mid - 1u - d0); }
+    else { out[0] = (uint32_t)(mid + d0); out[1] = (uint32_t)(mid + d1 - 1u); }
+    return true;
+}
 
 // ------------------------------------------------------------------------------------------------------------------
 //  Sparse phase 2 (DevContig::sparse2): the checkpoints go on in phase 1's step from the phase boundary — the forward role walks

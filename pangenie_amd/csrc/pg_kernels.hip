@@ -3177,6 +3177,10 @@ DEVI double lean_total(const LeanShared<R>& sh, uint32_t pb) {   // (kLeanPreTot
 // it stores (its store-free step parks no scalar), a segment at the columns it forms, its closing checkpoint excepted, which is the
 // chain's: one writer per entry and run.  Their only readers (k_post: 1 / (fscale bscale)) come behind the refill of the column's
 // chunk.  bsum is the chain's alone, at the columns it stores: a launch or a segment resumes (Sy = bsum[top + 1]) from such a column.
+// SPARSE, PHASE 1 in pieces (`chunk` != 0: G << 16 | g = piece g of G chunk_cols columns, pg_sparse_piece): a launch per piece.  A piece that does not
+// begin at the chain's end resumes from the checkpoint in front of it as a chunk launch of phase 3 does — but behind a checkpoint
+// that fell back to uniform it goes on from all-zero states, as the single launch did in registers (and a PHASE 5 segment does);
+// a piece that does not end at the phase boundary ends as a chunk launch ends: the zero test of its last column.
 template <int PHASE, int R, bool TRI, bool SPARSE = false>
 DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint32_t chunk) {
     static_assert(!SPARSE || ((PHASE == 1 || PHASE == 3) && !TRI), "sparse stores: phases 1 and 3 of full-column lean chains");
@@ -3189,6 +3193,11 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         if (l >= C) return;
         lo = (uint32_t)l;
         hi = C - lo > K ? lo + K : C;
+    }
+    if constexpr (SPARSE && PHASE == 1) if (chunk) {
+        uint32_t pc[2];
+        if (!pg_sparse_piece(C, 0u, (chunk >> 16) * K, chunk & 0xFFFFu, pc)) return;
+        lo = pc[0]; hi = pc[1] + 1u;
     }
     bool seg2 = false;   // PHASE 5: a segment of phase 2
     if constexpr (PHASE == 5) {
@@ -3320,10 +3329,11 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
             if (!fallback[lo - 1]) {
 #pragma unroll
                 for (int k = 0; k < R; ++k) { const double e = sel_by_bit(rb, k, eA, eB); part = fma(e, x[k], part); x[k] *= e; }
-            } else if (PHASE == 5 && !boundary) {
+            } else if ((PHASE == 5 && !boundary) || (SPARSE && PHASE == 1)) {
                 // (the chain went on from this checkpoint in registers: every state 0, the uniform column entering through the first
                 //  step's zero test — the same instructions here give the same bits; a chunk launch resumes from the STORED uniform
-                //  column, and so does the segment behind a checkpoint that is a chunk's last column)
+                //  column, and so does the segment behind a checkpoint that is a chunk's last column.  A piece of phase 1 stands for
+                //  the single launch: registers)
 #pragma unroll
                 for (int k = 0; k < R; ++k) x[k] = 0.0;
             } else {
@@ -3513,7 +3523,7 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
     }
 }
 
-template <int PHASE, int R, bool TRI, bool SPARSE = false>   // (SPARSE, PHASE 5: see lean_forward)
+template <int PHASE, int R, bool TRI, bool SPARSE = false>   // (SPARSE, PHASE 5, pieces of PHASE 1: see lean_forward)
 DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint32_t chunk) {
     static_assert(!SPARSE || ((PHASE == 1 || PHASE == 3) && !TRI), "sparse stores: phases 1 and 3 of full-column lean chains");
     constexpr int HP = 64;
@@ -3532,8 +3542,15 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         seg2 = (int64_t)chunk <= mid;
         if (seg2) bot = top + 1 > (int64_t)PG_LEAN_SPARSE ? top + 1 - (int64_t)PG_LEAN_SPARSE : 0;
     }
+    bool resumed = PHASE != 1;   // (phase 1 initialises column C - 1 — but for a piece that begins further down: it resumes, as a chunk launch)
+    if constexpr (SPARSE && PHASE == 1) if (chunk) {
+        uint32_t pc[2];
+        if (!pg_sparse_piece(C, 1u, (chunk >> 16) * dc.chunk_cols, chunk & 0xFFFFu, pc)) return;
+        bot = pc[0]; top = pc[1];
+        resumed = top != (int64_t)C - 1;
+    }
     if (top < bot) return;
-    const int64_t t0 = PHASE == 1 ? top - 1 : top;
+    const int64_t t0 = resumed ? top : top - 1;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t i0 = wave * R;
@@ -3619,7 +3636,7 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
     FRec cur = read_frec(sh, 0);  // record t0+1: constants of the gap t0 -> t0+1, emission of column t0+1
     {
         double y[R];
-        if constexpr (PHASE == 1) {
+        if (!resumed) {
             // column C-1: beta~ = 1 (hmm.cpp:356-358), stored at the backward bias
             const double B0 = ldexp(1.0, PG_BIAS_B);
 #pragma unroll
@@ -4201,6 +4218,7 @@ void k_sweep_lean_tri(const DevContig* __restrict__ contigs, uint32_t chunk) {
     sweep_lean_body<PHASE, R, true>(contigs, chunk, sh);
 }
 
+// chunk, PHASE 1 of sparse chains: 0 = the whole first half; G << 16 | g = piece g of G chunks' width (lean_forward)
 template <int PHASE, int R, bool TRI = false>
 __global__ __launch_bounds__((64 * 64 / R)) void k_sweep_lean(const DevContig* __restrict__ contigs, uint32_t chunk) {
     __shared__ LeanShared<R> sh;
@@ -7119,6 +7137,11 @@ void pgk_launch_sweep(const DevContig* d_contigs, uint32_t n_contigs, uint32_t h
     if (phase == 1) launch_sweep<1>(d_contigs, n_contigs, hp_mask, 0, s);
     else launch_sweep<2>(d_contigs, n_contigs, hp_mask, 0, s);
 }
+// piece `piece` (< 2^16) of phase 1 of a job whose chains with columns are all sparse lean chains (pg_job::n_pieces; pg_device.h:
+// pg_sparse_piece), `piece_chunks` (1 .. 2^16 - 1) chunks wide: the lean kernel alone
+void pgk_launch_sweep_piece(const DevContig* d_contigs, uint32_t n_contigs, uint32_t piece_chunks, uint32_t piece, hipStream_t s) {
+    hipLaunchKernelGGL((k_sweep_lean<1, 16, false>), dim3(n_contigs, 2), dim3(256), 0, s, d_contigs, (piece_chunks << 16) | piece);
+}
 // chunked mode: chunk `chunk` of the second half of every half-chain (store-only sweep), then its posteriors
 void pgk_launch_sweep_chunk(const DevContig* d_contigs, uint32_t n_contigs, uint32_t hp_mask, uint32_t chunk, hipStream_t s) {
     launch_sweep<3>(d_contigs, n_contigs, hp_mask, chunk, s);
@@ -7162,7 +7185,7 @@ uint32_t pgk_post_blocks(uint32_t n_contigs, uint32_t chunk_cols, uint32_t* cus_
 }
 // the columns of chunk `chunk`'s partner ranges that the sparse phase 1 left out (k_refill_lean), on the CUs the chains leave idle
 // (phase2: the columns of the chunk itself, which a sparse phase 2 left out)
-void pgk_launch_refill(const DevContig* d_contigs, uint32_t n_contigs, uint32_t chunk_cols, uint32_t chunk, int phase2, hipStream_t s) {
+void pgk_launch_refill(const DevContig* d_contigs, uint32_t n_contigs, uint32_t chunk_cols, uint32_t chunk, int phase2, uint32_t max_blocks, hipStream_t s) {
     static bool attr_done[PG_MAX_DEVICES];
     if (lds_attr_pending(attr_done))
         (void)hipFuncSetAttribute((const void*)k_refill_lean<16>, hipFuncAttributeMaxDynamicSharedMemorySize, PG_REFILL_PLACEMENT_LDS);
@@ -7171,6 +7194,7 @@ void pgk_launch_refill(const DevContig* d_contigs, uint32_t n_contigs, uint32_t 
     const uint32_t q = chunk_cols / PG_LEAN_SPARSE;
     uint32_t blocks = cus > 2u * n_contigs + n_contigs ? cus - 2u * n_contigs : n_contigs;   // (k_post's count)
     if (const char* e = getenv("PG_REFILL_BLOCKS")) { const long v = strtol(e, nullptr, 0); if (v >= 1 && (uint32_t)v < blocks) blocks = (uint32_t)v; }   // (experiments: fewer)
+    if (max_blocks && blocks > max_blocks) blocks = max_blocks;
     if (blocks > 2u * q * n_contigs) blocks = 2u * q * n_contigs;
     if (blocks == 0u) return;
     hipLaunchKernelGGL((k_refill_lean<16>), dim3(blocks), dim3(256), PG_REFILL_PLACEMENT_LDS, s, d_contigs, n_contigs, chunk, q, phase2 ? 1u : 0u);

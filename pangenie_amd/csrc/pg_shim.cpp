@@ -472,6 +472,13 @@ struct pg_job {
     // then owns the scratch buffers alone: the sweeps wait for no k_post (PG_KERNELS=nosparse2: dense chunk sweeps)
     bool sparse2 = false;
     std::vector<hipEvent_t> ev_chunk;   // sparse2: one "sweep done" event per chunk (the sweeps run chunks ahead of the stream that waits for them)
+    // sparse2 jobs of more than one piece: phase 1 runs as one launch per piece of `piece_chunks` partner chunks (pg_device.h:
+    // pg_sparse_piece), the farthest from the phase boundary first, and the second stream — idle in phase 1 — refills the partner
+    // columns of a piece's chunks behind it, beside the pieces that follow.  Only piece 0's chunks are left for phase 2 to refill.
+    // (PG_KERNELS=nopieces: one launch; PG_PIECE_CHUNKS: chunks per piece.)  n_pieces == 1: the single launch
+    uint32_t piece_chunks = 0, n_pieces = 1;
+    uint32_t piece_refill_blocks = 0;   // workgroups of a refill launched beside phase 1: fewer than in phase 2 (job_build)
+    std::vector<hipEvent_t> ev_piece;   // one "piece done" event per piece
     // The pipelined first run of a one-shot job (job_build with cache_arena: upload and run inside ONE call, the host arrays stay
     // valid): the inputs of the LONG chains (group A: the job's wall time) are uploaded first and their preparation + phase 1
     // start while the other chains' inputs (group B, most of the bytes) are still crossing PCIe; B's index pass, preparation and
@@ -570,6 +577,7 @@ extern "C" void pg_job_destroy(pg_job* job) {
     if (job->events2)
         for (int q = 0; q < (int)PG_SCRATCH_BUFS; ++q) { hipEventDestroy(job->ev_sweep[q]); hipEventDestroy(job->ev_post[q]); }
     for (hipEvent_t e : job->ev_chunk) hipEventDestroy(e);
+    for (hipEvent_t e : job->ev_piece) hipEventDestroy(e);
     if (job->arena) {
         if (job->cache_arena) g_pool.put(job->device, job->arena, job->arena_bytes);
         else hipFree(job->arena);
@@ -874,11 +882,14 @@ int upload_inputs(pg_job* job, const pg_contig_batch* batches, const std::vector
 //   nosparse            phase 1 of the lean chains of chunked jobs stores every column itself (no k_refill_lean) — cross-check
 //   nosparse2           the chunk sweeps of phase 2 store every column into the scratch buffers although phase 1 is sparse (no second
 //                       k_refill_lean per chunk; the sweeps wait for k_post to free a buffer) — cross-check
+//   nopieces            phase 1 of a job whose chains are all sparse lean chains is one launch, and every chunk's partner columns are
+//                       refilled in phase 2 (instead of a launch per piece with the refills of all pieces but the last beside phase 1)
+//                       — cross-check
 //   nosplit             the 16-path chains of fused jobs prepare every variant per sample (k_prep*, k_records, k_bins_lean2 / _x) instead of
 //                       taking the split path (pg_split.h)
 struct KernelChoice {
     bool general = false, generic = false, nolean2 = false, notri = false, nocls4 = false, prepwave = false, fullcols = false, nosmall2 = false, nosplit = false;
-    bool persist = false, noleanx2 = false, nowidef = false, nosparse = false, nosparse2 = false;
+    bool persist = false, noleanx2 = false, nowidef = false, nosparse = false, nosparse2 = false, nopieces = false;
     int leanx = -1, small = -1;   // -1: by the job, 0 / 1: forced
     std::string unknown;          // a token this list does not know
 };
@@ -899,6 +910,7 @@ KernelChoice kernel_choice() {
         else if (tok == "nowidef") k.nowidef = true;
         else if (tok == "nosparse") k.nosparse = true;
         else if (tok == "nosparse2") k.nosparse2 = true;
+        else if (tok == "nopieces") k.nopieces = true;
         else if (tok == "persist") k.persist = true; else if (tok == "nopersist") k.persist = false;
         else if (!tok.empty()) k.unknown = tok;   // (a typo would quietly test the default path against itself: job creation fails)
         tok.clear();
@@ -1115,7 +1127,7 @@ void choose_job_mode(pg_job* job, const BuildArgs& a, size_t chunk_cap) {
     const KernelChoice& kc = a.kc;
     const pg_hmm_params& params = a.params;
     const uint32_t n_chains = (uint32_t)a.specs.size();
-    job->persist = false; job->post_blocks = 0; job->any_split = false; job->sparse = false; job->sparse2 = false;
+    job->persist = false; job->post_blocks = 0; job->any_split = false; job->sparse = false; job->sparse2 = false; job->piece_chunks = 0; job->n_pieces = 1;
     {
         // k_sweep_small16 packs four H = 16 half-chains into a wave: a throughput kernel.  A single chain is faster on the
         // general kernel (four states per lane instead of sixteen: 375 vs 470 ns per column); PG_KERNELS=small / nosmall forces.
@@ -1210,6 +1222,22 @@ void choose_job_mode(pg_job* job, const BuildArgs& a, size_t chunk_cap) {
             bool only_lean = true;
             for (const ChainSpec& sp : a.specs) { const IndexHost& x = job->index[sp.index]; if (x.V && !x.lean) only_lean = false; }
             job->sparse2 = job->sparse && only_lean && !kc.nosparse2;
+            // phase 1 in pieces of PG_PIECE_CHUNKS partner chunks each (see pg_job::n_pieces)
+            if (job->sparse2 && !kc.nopieces) {
+                uint32_t G = PG_PIECE_CHUNKS_DEFAULT;
+                if (const char* e = getenv("PG_PIECE_CHUNKS")) { const long v = strtol(e, nullptr, 0); if (v >= 1 && v <= 0xFFFF) G = (uint32_t)v; }
+                // (the piece and G travel in the 16-bit halves of the kernel's `chunk` argument)
+                if ((unsigned long long)G * job->chunk_cols <= 0xFFFFFFFFull && (job->n_chunks + G - 1u) / G <= 0x10000u) {
+                    job->piece_chunks = G;
+                    job->n_pieces = (job->n_chunks + G - 1u) / G;
+                    // the refills beside phase 1 have a whole piece's time for a fraction of its columns: on a third of the idle CUs they
+                    // still end before the next piece does, and slow the chains beside them less than at full width (genome24_h64, phase 1:
+                    // + 3.7 ms on all idle CUs, + 0.3 .. 1.0 ms on a half or a quarter; on an eighth they no longer end in time —
+                    // profiles/r11_refill_beside_phase1.txt).  PG_PIECE_REFILL_BLOCKS: experiments
+                    job->piece_refill_blocks = std::max<uint32_t>((cus - 2u * n_chains) / 3u, 1u);
+                    if (const char* e = getenv("PG_PIECE_REFILL_BLOCKS")) { const long v = strtol(e, nullptr, 0); if (v >= 1 && v <= 0xFFFF) job->piece_refill_blocks = (uint32_t)v; }
+                }
+            }
         }
     }
     // ---- the split path: which index contigs' chains take it (pg_device.h) ---------------------------
@@ -1358,7 +1386,7 @@ std::string plan_text(const pg_job* job, const BuildArgs& a, const std::vector<C
         char head[160];
         snprintf(head, sizeof(head), "%u path(s) (padded %u), %s%s%s columns: ", x.H, x.HP, x.pair_n > 2 ? "multiallelic" : "biallelic", x.wide_bytes ? " + wide" : "",
                  k.tri ? ", triangle" : "");
-        const std::string text = std::string(head) + "prep = " + kPrepName[k.prep] + "; phase 1 = " + name(k.phase1, 1) + (k.sparse ? " (sparse: every 64th column stored)" : "") + "; phase 2 = " + p2 + "; bins = " + bins;
+        const std::string text = std::string(head) + "prep = " + kPrepName[k.prep] + "; phase 1 = " + name(k.phase1, 1) + (k.sparse ? (k.sparse2 && job->n_pieces > 1u ? " (sparse: every 64th column stored, in " + std::to_string(job->n_pieces) + " pieces with k_refill_lean beside them)" : std::string(" (sparse: every 64th column stored)")) : std::string()) + "; phase 2 = " + p2 + "; bins = " + bins;
         bool found = false;
         for (auto& g : groups) if (g.text == text) { g.count += 1; found = true; break; }
         if (!found) groups.push_back({text, 1});
@@ -1549,6 +1577,11 @@ int create_device_objects(pg_job* job, char* err, size_t errlen) {
             hipEvent_t e;
             if ((he = hipEventCreateWithFlags(&e, hipEventDisableTiming)) != hipSuccess) return hip_fail(err, errlen, "hipEventCreate", he);
             job->ev_chunk.push_back(e);
+        }
+        if (job->n_pieces > 1u) for (uint32_t g = 0; g < job->n_pieces; ++g) {
+            hipEvent_t e;
+            if ((he = hipEventCreateWithFlags(&e, hipEventDisableTiming)) != hipSuccess) return hip_fail(err, errlen, "hipEventCreate", he);
+            job->ev_piece.push_back(e);
         }
     }
     return PG_OK;
@@ -2111,6 +2144,7 @@ extern "C" int pg_job_run(pg_job* job, void* stream_, char* err, size_t errlen) 
     const bool persist_now = job->persist && job->max_v > 0 && job->params.run_genotyping && streams_concurrent(job, s);   // (may replace stream2)
     if (job->persist && job->max_v > 0 && job->params.run_genotyping) { if (persist_now) job->persist_runs += 1; else job->persist_fallbacks += 1; }
     HIP_TRY(hipMemsetAsync(job->zero_base, 0, job->zero_bytes, s));
+    bool pieces_now = false;   // this run's phase 1 goes in pieces, and the second stream has refilled the partner columns of all chunks but piece 0's
     if (job->max_v > 0 && job->params.run_genotyping) {
         HIP_TRY(hipEventRecord(job->ev[0], s));
         if (job->late_pending) {
@@ -2160,7 +2194,25 @@ extern "C" int pg_job_run(pg_job* job, void* stream_, char* err, size_t errlen) 
         if (job->any_legacy_prep) pgk_launch_records(job->d_contigs, n, job->max_v, s);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(job->ev[3], s));
-        pgk_launch_sweep(job->d_contigs, n, job->hp_mask, 1, s);
+        // phase 1 in pieces (all chains sparse lean chains; the job's own stream, not the pipelined first run): piece g, then on the
+        // second stream the partner columns of its chunks, the farthest chunk first — a segment resumes from a checkpoint of its own
+        // piece or from the last column of the piece before, both stored by then.  Piece 0's chunks stay with phase 2
+        pieces_now = job->n_pieces > 1u && s == job->stream && !late_own_stream;
+        if (pieces_now) {
+            const uint32_t G = job->piece_chunks;
+            if (job->hp_mask & ~PG_SWEEP_LEAN) pgk_launch_sweep(job->d_contigs, n, job->hp_mask & ~PG_SWEEP_LEAN, 1, s);   // (kernels of chains without columns: the launches they had)
+            for (uint32_t g = job->n_pieces; g-- > 0u;) {
+                pgk_launch_sweep_piece(job->d_contigs, n, G, g, s);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipEventRecord(job->ev_piece[g], s));
+                if (g == 0u) break;
+                HIP_TRY(hipStreamWaitEvent(job->stream2, job->ev_piece[g], 0));
+                for (uint32_t i = std::min((g + 1u) * G, job->n_chunks); i-- > g * G;) pgk_launch_refill(job->d_contigs, n, job->chunk_cols, i, 0, job->piece_refill_blocks, job->stream2);
+                HIP_TRY(hipGetLastError());
+            }
+        } else {
+            pgk_launch_sweep(job->d_contigs, n, job->hp_mask, 1, s);
+        }
         pgk_launch_sweep_small(job->d_contigs, job->d_small, job->n_small, 1, 0, job->d_dump, s);
         pgk_launch_sweep_smallx(job->d_contigs, job->d_smallx, job->n_smallx, 1, 0, job->d_dump, s);
         HIP_TRY(hipGetLastError());
@@ -2198,9 +2250,9 @@ extern "C" int pg_job_run(pg_job* job, void* stream_, char* err, size_t errlen) 
                 pgk_launch_sweep_chunk(job->d_contigs, n, job->hp_mask, i, s);
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipEventRecord(job->ev_chunk[i], s));
-                pgk_launch_refill(job->d_contigs, n, job->chunk_cols, i, 0, s2);
+                if (!pieces_now || i < job->piece_chunks) pgk_launch_refill(job->d_contigs, n, job->chunk_cols, i, 0, 0u, s2);
                 HIP_TRY(hipStreamWaitEvent(s2, job->ev_chunk[i], 0));
-                pgk_launch_refill(job->d_contigs, n, job->chunk_cols, i, 1, s2);
+                pgk_launch_refill(job->d_contigs, n, job->chunk_cols, i, 1, 0u, s2);
                 pgk_launch_post(job->d_contigs, n, job->chunk_cols, i, s2);
                 HIP_TRY(hipGetLastError());
                 if (i + 1u == job->n_chunks) {
@@ -2216,7 +2268,7 @@ extern "C" int pg_job_run(pg_job* job, void* stream_, char* err, size_t errlen) 
                 pgk_launch_sweep_smallx(job->d_contigs, job->d_smallx, job->n_smallx, 3, i, job->d_dump, s);
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipEventRecord(job->ev_sweep[b], s));
-                if (job->sparse) pgk_launch_refill(job->d_contigs, n, job->chunk_cols, i, 0, s2);
+                if (job->sparse) pgk_launch_refill(job->d_contigs, n, job->chunk_cols, i, 0, 0u, s2);
                 HIP_TRY(hipStreamWaitEvent(s2, job->ev_sweep[b], 0));
                 pgk_launch_post(job->d_contigs, n, job->chunk_cols, i, s2);
                 HIP_TRY(hipGetLastError());
@@ -2472,6 +2524,14 @@ extern "C" int pg_sparse_segment(uint32_t n_columns, uint32_t chunk_cols, uint32
     if (m > pg_sparse_segments(n_columns, role)) return 0;
     const uint32_t ck = pg_sparse_checkpoint(n_columns, role, (uint32_t)m);
     if (out) { out[0] = ck; out[1] = role == 0u ? ck + 1u : ck - (PG_LEAN_SPARSE - 1u); out[2] = role == 0u ? ck + (PG_LEAN_SPARSE - 1u) : ck - 1u; }
+    return 1;
+}
+// ... of phase 1 in pieces (pg_sparse_piece): piece `piece` of `piece_chunks` partner chunks; out = {lowest column, highest column}
+extern "C" int pg_sparse_piece_range(uint32_t n_columns, uint32_t chunk_cols, uint32_t piece_chunks, uint32_t piece, uint32_t role, uint32_t out[2]) {
+    if (role > 1u || chunk_cols == 0u || chunk_cols % PG_LEAN_SPARSE != 0u || piece_chunks == 0u || (unsigned long long)piece_chunks * chunk_cols > 0xFFFFFFFFull) return -1;
+    uint32_t r[2];
+    if (!pg_sparse_piece(n_columns, role, piece_chunks * chunk_cols, piece, r)) return 0;
+    if (out) { out[0] = r[0]; out[1] = r[1]; }
     return 1;
 }
 // ... and of the sparse phase 2 (pg_sparse2_*): segment j of chunk `chunk`; out = {checkpoint, lowest column, highest column}
