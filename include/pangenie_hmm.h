@@ -429,10 +429,18 @@ typedef struct pg_record_plan {
  * record), vcf_off that does not follow n_alleles, a map entry >= the record's n_alleles, a vcf_index that is not the
  * running count of defined alleles.  PG_ERR_UNSUPPORTED: a record with more than 256 alleles. */
 int  pg_job_record_plan(pg_job* job, uint32_t index_contig, const pg_record_plan* plan, char* err, size_t errlen);
+/* One plan for every index contig ix with ix % n_contigs == contig: the chains sample * n_contigs + contig of a sampled
+ * cohort job (pg_sampler_cohort_new[_device]: every chain is its own index contig).  Checked once, uploaded once and
+ * referred to by all members; a later pg_job_record_plan on one member replaces that member's reference
+ * alone, a later strided call those of all its members; the device copy is freed with its last reference and by
+ * pg_job_destroy.  PG_ERR_INVALID: n_contigs == 0, contig >= n_contigs, a number of index contigs that is no multiple of
+ * n_contigs, a member whose n_variants is not the plan's; the plan's own refusals as above.  Nothing is attached then. */
+int  pg_job_record_plan_strided(pg_job* job, uint32_t contig, uint32_t n_contigs, const pg_record_plan* plan, char* err, size_t errlen);
 /* Forms one pg_call per record for every chain whose index contig has a plan (a chain without one is left out), on the
  * job's stream; blocking.  allele_1 <= allele_2 are GT numbers: indices among the record's defined alleles.  Refusals
- * as pg_job_calls; PG_ERR_INVALID also if an allele id of the index lies outside a record's map (checked here, on the
- * host, whenever a plan or the index has changed: a sampled panel's ids exist only after its job was made). */
+ * as pg_job_calls; PG_ERR_INVALID also if an allele id of a chain lies outside a record's map (checked here, on the
+ * device, whenever a plan or the index has changed: a sampled panel's ids exist only there, after its job was made; the
+ * message names the lowest chain and its lowest variant). */
 int  pg_job_record_calls(pg_job* job, char* err, size_t errlen);
 /* Chain `chain`'s records, out[R of its index contig's plan] (after pg_job_record_calls); nothing for a chain without a plan. */
 int  pg_job_fetch_record_calls(pg_job* job, uint32_t chain, pg_call* out, char* err, size_t errlen);
@@ -483,6 +491,15 @@ int  pg_job_fetch_record_gl_all(pg_job* job, pg_gl* const* outs, char* err, size
 int  pg_job_device_record_gl(pg_job* job, uint32_t chain, void** d_gl, uint64_t* n);
 /* Elapsed milliseconds of the kernels of the LAST pg_job_record_gl. */
 double pg_job_record_gl_ms(const pg_job* job);
+/* The packed fetches.  The records and the GL values lie chain after chain on the device:
+ * calls_first[n_chains + 1] / gl_first[n_chains + 1] (either may be NULL) give every chain's offset, in elements, in the
+ * two buffers (no padding between chains: chain c owns [first[c], first[c + 1])).  calls_first after pg_job_record_calls,
+ * gl_first after pg_job_record_gl: PG_ERR_INVALID otherwise, and when both are NULL. */
+int  pg_job_record_first(pg_job* job, uint64_t* calls_first, uint64_t* gl_first, char* err, size_t errlen);
+/* All records / all GL values of all chains, out[n] with n = calls_first[n_chains] / gl_first[n_chains]: ONE copy on the
+ * job's stream and one synchronisation.  PG_ERR_INVALID as the per-chain fetches, and when n is not the buffer's length. */
+int  pg_job_fetch_record_calls_packed(pg_job* job, pg_call* out, uint64_t n, char* err, size_t errlen);
+int  pg_job_fetch_record_gl_packed(pg_job* job, pg_gl* out, uint64_t n, char* err, size_t errlen);
 /* Unit entry point: the GL values of the plan's records from host arrays (as pg_record_calls_from_bins), through the
  * same kernels; out[gl_off[R]].  The plan is checked first; then PG_ERR_DEVICE without a device: no host fallback. */
 int  pg_record_gl_from_bins(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id,

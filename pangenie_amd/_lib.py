@@ -277,6 +277,15 @@ def _bind_hip(lib):
     lib.pg_job_record_gl_ms.restype = C.c_double
     lib.pg_record_gl_from_bins.argtypes = [C.c_int, C.c_uint32, u32p, u16p, u8p, u8p, f64p, i32p, C.c_void_p, C.c_void_p]
     lib.pg_record_gl_from_bins.restype = C.c_int
+    # records of sampled cohorts: one plan for a stride of index contigs, the packed fetches
+    lib.pg_job_record_plan_strided.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_record_plan_strided.restype = C.c_int
+    lib.pg_job_record_first.argtypes = [C.c_void_p, u64p, u64p, C.c_char_p, C.c_size_t]
+    lib.pg_job_record_first.restype = C.c_int
+    lib.pg_job_fetch_record_calls_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+    lib.pg_job_fetch_record_calls_packed.restype = C.c_int
+    lib.pg_job_fetch_record_gl_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+    lib.pg_job_fetch_record_gl_packed.restype = C.c_int
     lib.pg_gl_from_values.argtypes = [C.c_int, C.c_uint64, u64p, i32p, C.c_void_p]
     lib.pg_gl_from_values.restype = C.c_int
     lib.pg_gl_text.argtypes = [PgGl, C.c_char_p, C.c_size_t]
@@ -301,6 +310,7 @@ HIP_ABI_SYMBOLS = [
     "pg_job_record_calls_ms", "pg_record_calls_from_bins",
     "pg_record_gl_offsets", "pg_job_record_gl", "pg_job_fetch_record_gl", "pg_job_fetch_record_gl_all", "pg_job_device_record_gl",
     "pg_job_record_gl_ms", "pg_record_gl_from_bins", "pg_gl_from_values", "pg_gl_text",
+    "pg_job_record_plan_strided", "pg_job_record_first", "pg_job_fetch_record_calls_packed", "pg_job_fetch_record_gl_packed",
     "pg_sparse_segment", "pg_sparse_stored_by_chain", "pg_sparse_chunk_segment", "pg_sparse_chunk_stored_by_chain", "pg_sparse_piece_range",
 ]
 

@@ -152,6 +152,63 @@ def job_record_plan(job, contig: int, plan: RecordPlan) -> None:
     job._record_plans[contig] = plan
 
 
+def job_record_plan_strided(job, contig: int, n_contigs: int, plan: RecordPlan) -> None:
+    """pg_job_record_plan_strided: one plan, checked and uploaded once, for every index contig ix with ix % n_contigs ==
+    contig — the chains sample * n_contigs + contig of a sampled cohort job."""
+    err = C.create_string_buffer(_ERRLEN)
+    c = plan.as_c()
+    rc = job._lib.pg_job_record_plan_strided(job.h, contig, n_contigs, C.addressof(c), err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    if not hasattr(job, "_record_plans"):
+        job._record_plans = {}
+    for ix in range(contig, len(job.index), n_contigs):
+        job._record_plans[ix] = plan
+
+
+def job_record_first(job):
+    """pg_job_record_first: (calls_first, gl_first), [n_chains + 1] each — every chain's offset, in elements, in the packed
+    records and the packed GL values; gl_first is None until record_gl() has run."""
+    cf, gf = _record_first(job, True), None
+    try:
+        gf = _record_first(job, False)
+    except Exception:   # (record_gl() has not run: the records' offsets alone)
+        pass
+    return cf, gf
+
+
+def _record_first(job, calls: bool) -> np.ndarray:
+    first = np.zeros(job.n_chains + 1, np.uint64)
+    err = C.create_string_buffer(_ERRLEN)
+    p = first.ctypes.data_as(_lib.u64p)
+    rc = job._lib.pg_job_record_first(job.h, p if calls else None, None if calls else p, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return first
+
+
+def fetch_record_calls_packed(job):
+    """pg_job_fetch_record_calls_packed: (records of all chains as ONE array from one copy, calls_first)."""
+    first = _record_first(job, True)
+    out = np.zeros(max(int(first[-1]), 1), CALL_DTYPE)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_record_calls_packed(job.h, out.ctypes.data, int(first[-1]), err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return out[:int(first[-1])], first
+
+
+def fetch_record_gl_packed(job):
+    """pg_job_fetch_record_gl_packed: (GL values of all chains as ONE array from one copy, gl_first)."""
+    first = _record_first(job, False)
+    out = np.zeros(max(int(first[-1]), 1), GL_DTYPE)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_record_gl_packed(job.h, out.ctypes.data, int(first[-1]), err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return out[:int(first[-1])], first
+
+
 def _n_records(job) -> List[int]:
     plans, nc = getattr(job, "_record_plans", {}), len(job.index)
     return [plans[c % nc].n_records if (c % nc) in plans else 0 for c in range(len(job.batches))]

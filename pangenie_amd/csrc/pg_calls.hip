@@ -263,7 +263,7 @@ __global__ __launch_bounds__(PC_BLOCK) void k_rcalls(const DevContig* __restrict
         for (uint32_t a = 0; a < A; ++a)
             if (c->allele_present[a0 + a]) {
                 present |= 1u << a;
-                const uint32_t id = c->allele_id[a0 + a];   // (the host has checked id < n_map; no read outside the map either way)
+                const uint32_t id = c->allele_id[a0 + a];   // (k_rplan_ids has checked id < n_map; no read outside the map either way)
                 own |= (unsigned long long)(id < n_map ? map[id] & 0xFFu : 0u) << (8u * a);
             }
     const uint64_t g0 = c->geno_off[v];
@@ -279,6 +279,25 @@ __global__ __launch_bounds__(PC_BLOCK) void k_rcalls(const DevContig* __restrict
     unsigned long long rec = pack_no_call(d.flags);
     if ((d.flags & 0xFFu) == PGX_CALL_OK) rec = pack_call(def.vcf[d.key >> 16], def.vcf[d.key & 0xFFFFu], d.gq, d.flags);
     ((unsigned long long*)cd->out)[r] = rec;
+}
+
+// The id check of the record plans: one lane per record of every chain that has a plan, over k_rcalls'
+// descriptors.  Record r of bubble v holds every allele id of v against the length of its map; a lane that finds one
+// outside it leaves (chain << 32 | v) in *hit if that is lower than what is there (the host reads the lowest pair and names
+// it).  The ids of a sampled panel exist on the device alone; k_rcalls' clamp stays whatever this finds.
+__global__ __launch_bounds__(PC_BLOCK) void k_rplan_ids(const DevContig* __restrict__ contigs, const RCallsDesc* __restrict__ desc, uint32_t n_desc,
+                                                        unsigned long long* __restrict__ hit) {
+    const uint32_t blk = blockIdx.x;
+    const RCallsDesc* __restrict__ cd = desc + rcalls_chain_of(desc, n_desc, blk);
+    const uint32_t r = (blk - cd->blk0) * PC_BLOCK + threadIdx.x;
+    if (r >= cd->R) return;
+    const DevContig* __restrict__ c = contigs + cd->chain;
+    const uint32_t v = cd->plan.rec_var[r] & 0x7FFFFFFFu;
+    const uint32_t a0 = c->allele_off[v], a1 = c->allele_off[v + 1];
+    const uint32_t n_map = cd->plan.map_off[r + 1] - cd->plan.map_off[r];
+    bool outside = false;
+    for (uint32_t a = a0; a < a1; ++a) outside = outside || c->allele_id[a] >= n_map;
+    if (outside) atomicMin(hit, ((unsigned long long)cd->chain << 32) | v);
 }
 
 struct PgxSlot {   // a staged value: 16 bytes
@@ -325,7 +344,7 @@ __global__ __launch_bounds__(PCW_BLOCK) void k_rcalls_wide(const DevContig* __re
         const int32_t* __restrict__ lik_exp = c->lik_exp + g0;
         const bool kept = c->kept[v] != 0;
         for (uint32_t a = lane; a < A; a += PCW_BLOCK) {
-            const uint32_t id = c->allele_id[a0 + a];   // (the host has checked id < n_map; no read outside the map either way)
+            const uint32_t id = c->allele_id[a0 + a];   // (k_rplan_ids has checked id < n_map; no read outside the map either way)
             s_own[a] = (kept && c->allele_present[a0 + a]) ? (id < n_map ? map[id] : (uint16_t)0u) : (uint16_t)0xFFFFu;
         }
         __syncthreads();
@@ -490,7 +509,7 @@ __global__ __launch_bounds__(PC_BLOCK) void k_rgl(const DevContig* __restrict__ 
         for (uint32_t a = 0; a < A; ++a)
             if (c->allele_present[a0 + a]) {
                 present |= 1u << a;
-                const uint32_t id = c->allele_id[a0 + a];   // (the host has checked id < n_map; no read outside the map either way)
+                const uint32_t id = c->allele_id[a0 + a];   // (k_rplan_ids has checked id < n_map; no read outside the map either way)
                 own |= (unsigned long long)(id < n_map ? map[id] & 0xFFu : 0u) << (8u * a);
             }
     const uint64_t g0 = c->geno_off[v];
@@ -536,7 +555,7 @@ __global__ __launch_bounds__(PCW_BLOCK) void k_rgl_wide(const DevContig* __restr
         const int32_t* __restrict__ lik_exp = c->lik_exp + g0;
         const bool kept = c->kept[v] != 0;
         for (uint32_t a = lane; a < A; a += PCW_BLOCK) {
-            const uint32_t id = c->allele_id[a0 + a];   // (the host has checked id < n_map; no read outside the map either way)
+            const uint32_t id = c->allele_id[a0 + a];   // (k_rplan_ids has checked id < n_map; no read outside the map either way)
             s_own[a] = (kept && c->allele_present[a0 + a]) ? (id < n_map ? map[id] : (uint16_t)0u) : (uint16_t)0xFFFFu;
         }
         __syncthreads();
@@ -650,6 +669,10 @@ extern "C" void pgk_launch_rcalls(const DevContig* d_contigs, const RCallsDesc* 
     if (n_wide && n_slots)
         hipLaunchKernelGGL(k_rcalls_wide, dim3(n_slots < n_wide ? n_slots : n_wide), dim3(PCW_BLOCK), 0, s, d_contigs, d_desc, (const uint2*)d_wide, n_wide,
                            (PgxSlot*)d_stage, max_bins, stride, d_thr_m, d_thr_e);
+}
+
+extern "C" void pgk_launch_rplan_ids(const DevContig* d_contigs, const RCallsDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, void* d_hit, hipStream_t s) {
+    if (n_desc && n_blocks) hipLaunchKernelGGL(k_rplan_ids, dim3(n_blocks), dim3(PC_BLOCK), 0, s, d_contigs, d_desc, n_desc, (unsigned long long*)d_hit);
 }
 
 extern "C" void pgk_launch_calls(const DevContig* d_contigs, const CallsDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide,

@@ -85,6 +85,9 @@ void pgk_launch_gl_values(const uint64_t* d_m, const int32_t* d_e, void* d_out, 
 // staging slots of `stride` 16-byte values each (max_bins quotients, then the folded map) — one per block of k_rcalls_wide
 void pgk_launch_rcalls(const DevContig* d_contigs, const RCallsDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide, uint32_t n_wide,
                        void* d_stage, uint32_t max_bins, uint32_t stride, uint32_t n_slots, const uint64_t* d_thr_m, const int32_t* d_thr_e, hipStream_t s);
+// pg_calls.hip, k_rplan_ids: the descriptors and blocks of pgk_launch_rcalls; *d_hit (8 bytes, all ones going in) = the lowest
+// (chain << 32 | variant) with an allele id outside the map of one of the variant's records
+void pgk_launch_rplan_ids(const DevContig* d_contigs, const RCallsDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, void* d_hit, hipStream_t s);
 // pg_calls.hip: d_wide = uint2 {descriptor, variant} of every variant with more than PG_AMAX alleles (k_calls_wide's list)
 void pgk_launch_calls(const DevContig* d_contigs, const CallsDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide, uint32_t n_wide,
                       const uint64_t* d_thr_m, const int32_t* d_thr_e, hipStream_t s);

@@ -23,6 +23,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -390,6 +391,12 @@ struct RecordPlanHost {
     unsigned char* d = nullptr;   // rec_var, map_off, map, vcf_off, vcf_index: one allocation
     RecPlanDev dev = {};
 };
+// A plan a job holds: its index contigs refer to it, one alone (pg_job_record_plan) or every member of a stride
+// (pg_job_record_plan_strided); the device copy goes with the last reference.
+using RecordPlanRef = std::shared_ptr<const RecordPlanHost>;
+inline RecordPlanRef record_plan_ref(RecordPlanHost&& h) {
+    return RecordPlanRef(new RecordPlanHost(std::move(h)), [](const RecordPlanHost* p) { if (p->d) hipFree(p->d); delete p; });
+}
 
 }  // namespace
 
@@ -530,8 +537,9 @@ struct pg_job {
     double calls_ms = 0.0;
     // Record calls (pg_job_record_plan / pg_job_record_calls): one plan per index contig, shared by every chain over it, and one
     // 8-byte record per VCF record of every chain whose index contig has a plan.  Outside the arena like the calls.
-    std::vector<RecordPlanHost> rplans;       // [n_index] (sized by the first pg_job_record_plan)
+    std::vector<RecordPlanRef> rplans;        // [n_index] (sized by the first pg_job_record_plan[_strided]); null: no plan
     bool rcalls_dirty = true;                 // a plan or the index changed: descriptors, lists and the id check are redone
+    bool rplan_ids_ok = false;                // k_rplan_ids has passed the plans and the index as they are
     unsigned char* d_rcalls = nullptr;        // the records, the chain descriptors, k_rcalls_wide's list, its staging slots
     std::vector<uint64_t> rcalls_first;       // [n_chains + 1] first record of every chain (a chain without a plan has none)
     std::vector<RCallsDesc> rcalls_desc;
@@ -568,7 +576,7 @@ extern "C" void pg_job_destroy(pg_job* job) {
     if (job->d_calls) hipFree(job->d_calls);
     if (job->d_rcalls) hipFree(job->d_rcalls);
     if (job->d_rgl) hipFree(job->d_rgl);
-    for (RecordPlanHost& rp : job->rplans) if (rp.d) hipFree(rp.d);
+    job->rplans.clear();
     if (job->events) {
         for (auto& e : job->ev) hipEventDestroy(e);
         for (auto& e : job->ev_vit) hipEventDestroy(e);
@@ -704,6 +712,7 @@ int upload_inputs(pg_job* job, const pg_contig_batch* batches, const std::vector
     if (with_index) {
         job->rcalls_dirty = true;
         job->rgl_dirty = true;   // (new allele ids: the record plans are checked against them again)
+        job->rplan_ids_ok = false;
         for (size_t i = 0; i < job->index.size(); ++i) {
             const pg_contig_batch& b = batches[i];
             IndexHost& x = job->index[i];
@@ -3161,6 +3170,58 @@ int rcalls_ready(pg_job* job, char* err, size_t errlen) {
     return PG_OK;
 }
 
+// the plan of chain c's index contig, or nullptr
+const RecordPlanHost* plan_of_chain(const pg_job* job, uint32_t c) {
+    const uint32_t ix = job->chains[c].index;
+    return ix < job->rplans.size() ? job->rplans[ix].get() : nullptr;
+}
+
+// the checked plan on the job's device, ready to be referred to by index contigs
+int record_plan_to_device(pg_job* job, RecordPlanHost&& h, RecordPlanRef* ref, char* err, size_t errlen) {
+    HIP_TRY(hipSetDevice(job->device));
+    if (h.R) {
+        const size_t bytes = record_plan_device_bytes(h);
+        if (hipMalloc((void**)&h.d, bytes) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the record plan failed", bytes); return PG_ERR_NOMEM; }
+        if (!record_plan_upload(h, h.d, &h.dev)) { hipFree(h.d); set_err(err, errlen, "upload of the record plan failed"); return PG_ERR_DEVICE; }
+    }
+    *ref = record_plan_ref(std::move(h));
+    if (job->rplans.size() != job->index.size()) job->rplans.resize(job->index.size());
+    if (job->stream) HIP_TRY(hipStreamSynchronize(job->stream));   // (nothing reads the plans this one replaces any more)
+    return PG_OK;
+}
+
+void record_plans_changed(pg_job* job) {
+    job->rcalls_dirty = true;
+    job->rgl_dirty = true;
+    job->rplan_ids_ok = false;
+}
+
+// The id check on the device (k_rplan_ids): every allele id of every chain that has a plan, against the maps of its bubble's
+// records.  `d_desc` = the RCallsDesc list of plan_rcalls on the device, `d_hit` = 8 bytes next to it.  On a hit the ids of
+// that one chain come to the host and check_record_plan_ids forms the message.
+int check_record_plan_ids_on_device(pg_job* job, const RCallsDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, unsigned char* d_hit, char* err,
+                                    size_t errlen) {
+    if (job->rplan_ids_ok || n_desc == 0 || n_blocks == 0) { job->rplan_ids_ok = true; return PG_OK; }
+    hipStream_t s = job->stream;
+    uint64_t hit = ~(uint64_t)0;
+    HIP_TRY(hipMemcpyAsync(d_hit, &hit, sizeof(hit), hipMemcpyHostToDevice, s));
+    pgk_launch_rplan_ids(job->d_contigs, d_desc, n_desc, n_blocks, d_hit, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&hit, d_hit, sizeof(hit), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (hit == ~(uint64_t)0) { job->rplan_ids_ok = true; return PG_OK; }
+    const uint32_t chain = (uint32_t)(hit >> 32);
+    if (chain >= job->chains.size() || !plan_of_chain(job, chain)) { set_err(err, errlen, "the id check of the record plans answered chain %u", chain); return PG_ERR_DEVICE; }
+    const IndexHost& x = job->index[job->chains[chain].index];
+    std::vector<uint16_t> aid(x.sumA);
+    HIP_TRY(hipMemcpy(aid.data(), job->arena + x.o_aid, (size_t)x.sumA * 2, hipMemcpyDeviceToHost));
+    char text[256] = {0};
+    const int rc = check_record_plan_ids(*plan_of_chain(job, chain), x.aoff.data(), aid.data(), text, sizeof(text));
+    if (rc == PG_OK) { set_err(err, errlen, "chain %u, variant %u: an allele id lies outside a record's map", chain, (uint32_t)hit); return PG_ERR_INVALID; }
+    set_err(err, errlen, "%s, in chain %u", text, chain);
+    return rc;
+}
+
 }  // namespace
 
 extern "C" int pg_job_record_plan(pg_job* job, uint32_t ix, const pg_record_plan* plan, char* err, size_t errlen) {
@@ -3169,18 +3230,33 @@ extern "C" int pg_job_record_plan(pg_job* job, uint32_t ix, const pg_record_plan
     RecordPlanHost h;
     int rc = check_record_plan(plan, job->index[ix].V, &h, err, errlen);
     if (rc != PG_OK) return rc;
-    HIP_TRY(hipSetDevice(job->device));
-    if (h.R) {
-        const size_t bytes = record_plan_device_bytes(h);
-        if (hipMalloc((void**)&h.d, bytes) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the record plan failed", bytes); return PG_ERR_NOMEM; }
-        if (!record_plan_upload(h, h.d, &h.dev)) { hipFree(h.d); set_err(err, errlen, "upload of the record plan failed"); return PG_ERR_DEVICE; }
-    }
-    if (job->rplans.size() != job->index.size()) job->rplans.resize(job->index.size());
-    if (job->stream) HIP_TRY(hipStreamSynchronize(job->stream));   // (nothing reads the plan this one replaces any more)
-    if (job->rplans[ix].d) hipFree(job->rplans[ix].d);
-    job->rplans[ix] = std::move(h);
-    job->rcalls_dirty = true;
-    job->rgl_dirty = true;
+    RecordPlanRef ref;
+    rc = record_plan_to_device(job, std::move(h), &ref, err, errlen);
+    if (rc != PG_OK) return rc;
+    job->rplans[ix] = std::move(ref);   // (this index contig's reference alone: the members of a stride keep theirs)
+    record_plans_changed(job);
+    return PG_OK;
+}
+
+extern "C" int pg_job_record_plan_strided(pg_job* job, uint32_t contig, uint32_t n_contigs, const pg_record_plan* plan, char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    if (n_contigs == 0 || contig >= n_contigs) { set_err(err, errlen, "contig %u of %u", contig, n_contigs); return PG_ERR_INVALID; }
+    if (job->index.size() % n_contigs != 0) { set_err(err, errlen, "the job's %zu index contigs are no multiple of %u contigs", job->index.size(), n_contigs); return PG_ERR_INVALID; }
+    if (!plan) { set_err(err, errlen, "null record plan"); return PG_ERR_INVALID; }
+    for (size_t ix = contig; ix < job->index.size(); ix += n_contigs)
+        if (job->index[ix].V != plan->n_variants) {
+            set_err(err, errlen, "the record plan has %u variants, index contig %zu (member %zu of the stride) %u", plan->n_variants, ix, ix / n_contigs, job->index[ix].V);
+            return PG_ERR_INVALID;
+        }
+    RecordPlanHost h;
+    int rc = check_record_plan(plan, plan->n_variants, &h, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (contig >= job->index.size()) return PG_OK;   // (a job without index contigs: no member)
+    RecordPlanRef ref;
+    rc = record_plan_to_device(job, std::move(h), &ref, err, errlen);
+    if (rc != PG_OK) return rc;
+    for (size_t ix = contig; ix < job->index.size(); ix += n_contigs) job->rplans[ix] = ref;
+    record_plans_changed(job);
     return PG_OK;
 }
 
@@ -3199,27 +3275,14 @@ extern "C" int pg_job_record_calls(pg_job* job, char* err, size_t errlen) {
         HIP_TRY(hipEventCreate(&job->ev_calls[1]));
         job->calls_events = true;
     }
-    if (job->rcalls_dirty) {   // a plan or the index has changed: the ids are checked, the descriptors and lists made anew
-        std::vector<uint16_t> aid;
-        for (size_t ix = 0; ix < job->rplans.size(); ++ix) {
-            const RecordPlanHost& h = job->rplans[ix];
-            const IndexHost& x = job->index[ix];
-            if (!h.set || h.R == 0) continue;
-            aid.resize(x.sumA);
-            HIP_TRY(hipMemcpy(aid.data(), job->arena + x.o_aid, (size_t)x.sumA * 2, hipMemcpyDeviceToHost));
-            rc = check_record_plan_ids(h, x.aoff.data(), aid.data(), err, errlen);
-            if (rc != PG_OK) return rc;
-        }
+    if (job->rcalls_dirty) {   // a plan or the index has changed: the descriptors and lists are made anew, the ids checked on the device
         RcallsLaunch L;
-        plan_rcalls(n, [&](uint32_t c) -> const RecordPlanHost* {
-                        const uint32_t ix = job->chains[c].index;
-                        return ix < job->rplans.size() && job->rplans[ix].set ? &job->rplans[ix] : nullptr;
-                    },
-                    [&](uint32_t c) { return job->index[job->chains[c].index].aoff.data(); }, &L);
+        plan_rcalls(n, [&](uint32_t c) { return plan_of_chain(job, c); }, [&](uint32_t c) { return job->index[job->chains[c].index].aoff.data(); }, &L);
         const size_t o_desc = align_up((size_t)L.first[n] * sizeof(pg_call) + 8);
         const size_t o_wide = o_desc + align_up(L.desc.size() * sizeof(RCallsDesc) + 8);
         const size_t o_stage = o_wide + align_up(L.wide.size() * sizeof(uint32_t) + 8);
-        const size_t total = o_stage + align_up((size_t)L.n_slots * L.stride * 16 + 8);
+        const size_t o_hit = o_stage + align_up((size_t)L.n_slots * L.stride * 16 + 8);
+        const size_t total = o_hit + align_up(8);
         unsigned char* d = nullptr;
         if (hipMalloc((void**)&d, total) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the record calls failed", total); return PG_ERR_NOMEM; }
         for (RCallsDesc& cd : L.desc) cd.out = d + L.first[cd.chain] * sizeof(pg_call);
@@ -3227,6 +3290,8 @@ extern "C" int pg_job_record_calls(pg_job* job, char* err, size_t errlen) {
         if (!L.desc.empty()) he = hipMemcpy(d + o_desc, L.desc.data(), L.desc.size() * sizeof(RCallsDesc), hipMemcpyHostToDevice);
         if (he == hipSuccess && !L.wide.empty()) he = hipMemcpy(d + o_wide, L.wide.data(), L.wide.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
         if (he != hipSuccess) { hipFree(d); set_err(err, errlen, "upload of the record calls' lists failed: %s", hipGetErrorString(he)); return PG_ERR_DEVICE; }
+        rc = check_record_plan_ids_on_device(job, (const RCallsDesc*)(d + o_desc), (uint32_t)L.desc.size(), L.n_blocks, d + o_hit, err, errlen);
+        if (rc != PG_OK) { hipFree(d); return rc; }
         if (job->d_rcalls) hipFree(job->d_rcalls);
         job->d_rcalls = d;
         job->rcalls_first = std::move(L.first);
@@ -3417,55 +3482,48 @@ extern "C" int pg_job_record_gl(pg_job* job, char* err, size_t errlen) {
         job->calls_events = true;
     }
     if (job->rgl_dirty) {   // a plan or the index has changed: the ids are checked, the offsets, descriptors and lists made anew
-        std::vector<uint16_t> aid;
-        std::vector<std::vector<uint64_t>> gl_off(job->rplans.size());
-        std::vector<size_t> o_off(job->rplans.size(), 0);
-        for (size_t ix = 0; ix < job->rplans.size(); ++ix) {
-            const RecordPlanHost& h = job->rplans[ix];
-            const IndexHost& x = job->index[ix];
-            if (!h.set || h.R == 0) continue;
-            aid.resize(x.sumA);
-            HIP_TRY(hipMemcpy(aid.data(), job->arena + x.o_aid, (size_t)x.sumA * 2, hipMemcpyDeviceToHost));
-            const int rc = check_record_plan_ids(h, x.aoff.data(), aid.data(), err, errlen);
-            if (rc != PG_OK) return rc;
-            gl_off[ix] = record_gl_offsets(h);
-        }
+        // the offsets hang on the plan alone: one array per PLAN, whatever the number of index contigs that refer to it
+        struct PlanOffsets { std::vector<uint64_t> gl_off; size_t at = 0; };
+        std::map<const RecordPlanHost*, PlanOffsets> offs;
+        for (const RecordPlanRef& p : job->rplans)
+            if (p && p->R && !offs.count(p.get())) offs[p.get()].gl_off = record_gl_offsets(*p);
         RcallsLaunch L;
-        plan_rcalls(n, [&](uint32_t c) -> const RecordPlanHost* {
-                        const uint32_t ix = job->chains[c].index;
-                        return ix < job->rplans.size() && job->rplans[ix].set ? &job->rplans[ix] : nullptr;
-                    },
-                    [&](uint32_t c) { return job->index[job->chains[c].index].aoff.data(); }, &L);
+        plan_rcalls(n, [&](uint32_t c) { return plan_of_chain(job, c); }, [&](uint32_t c) { return job->index[job->chains[c].index].aoff.data(); }, &L);
         std::vector<uint64_t> first((size_t)n + 1, 0);
         for (uint32_t c = 0; c < n; ++c) {
-            const uint32_t ix = job->chains[c].index;
-            first[c + 1] = first[c] + (ix < gl_off.size() && !gl_off[ix].empty() ? gl_off[ix].back() : 0);
+            const auto o = offs.find(plan_of_chain(job, c));
+            first[c + 1] = first[c] + (o != offs.end() ? o->second.gl_off.back() : 0);
         }
         size_t total = align_up((size_t)first[n] * sizeof(pg_gl) + 8);
-        for (size_t ix = 0; ix < gl_off.size(); ++ix) {
-            if (gl_off[ix].empty()) continue;
-            o_off[ix] = total;
-            total += align_up(gl_off[ix].size() * sizeof(uint64_t) + 8);
+        for (auto& kv : offs) {
+            kv.second.at = total;
+            total += align_up(kv.second.gl_off.size() * sizeof(uint64_t) + 8);
         }
         const size_t o_desc = total;
         const size_t o_wide = o_desc + align_up(L.desc.size() * sizeof(RGlDesc) + 8);
         const size_t o_stage = o_wide + align_up(L.wide.size() * sizeof(uint32_t) + 8);
-        total = o_stage + align_up((size_t)L.n_slots * L.stride * 16 + 8);
+        // (the id check reads the descriptors of the record calls: a copy of them and its word behind the staging slots)
+        const size_t o_ids = o_stage + align_up((size_t)L.n_slots * L.stride * 16 + 8);
+        const size_t o_hit = o_ids + align_up((job->rplan_ids_ok ? 0 : L.desc.size()) * sizeof(RCallsDesc) + 8);
+        total = o_hit + align_up(8);
         unsigned char* d = nullptr;
         if (hipMalloc((void**)&d, total) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the record GLs failed", total); return PG_ERR_NOMEM; }
         std::vector<RGlDesc> desc;
         for (const RCallsDesc& c : L.desc) {
             RGlDesc g = rgl_desc_of(c);
             g.out = d + first[c.chain] * sizeof(pg_gl);
-            g.gl_off = (const uint64_t*)(d + o_off[job->chains[c.chain].index]);
+            g.gl_off = (const uint64_t*)(d + offs[plan_of_chain(job, c.chain)].at);
             desc.push_back(g);
         }
         hipError_t he = hipSuccess;
-        for (size_t ix = 0; ix < gl_off.size() && he == hipSuccess; ++ix)
-            if (!gl_off[ix].empty()) he = hipMemcpy(d + o_off[ix], gl_off[ix].data(), gl_off[ix].size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+        for (auto& kv : offs)
+            if (he == hipSuccess) he = hipMemcpy(d + kv.second.at, kv.second.gl_off.data(), kv.second.gl_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
         if (he == hipSuccess && !desc.empty()) he = hipMemcpy(d + o_desc, desc.data(), desc.size() * sizeof(RGlDesc), hipMemcpyHostToDevice);
         if (he == hipSuccess && !L.wide.empty()) he = hipMemcpy(d + o_wide, L.wide.data(), L.wide.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (he == hipSuccess && !job->rplan_ids_ok && !L.desc.empty()) he = hipMemcpy(d + o_ids, L.desc.data(), L.desc.size() * sizeof(RCallsDesc), hipMemcpyHostToDevice);
         if (he != hipSuccess) { hipFree(d); set_err(err, errlen, "upload of the record GLs' lists failed: %s", hipGetErrorString(he)); return PG_ERR_DEVICE; }
+        const int rc = check_record_plan_ids_on_device(job, (const RCallsDesc*)(d + o_ids), (uint32_t)L.desc.size(), L.n_blocks, d + o_hit, err, errlen);
+        if (rc != PG_OK) { hipFree(d); return rc; }
         if (job->d_rgl) hipFree(job->d_rgl);
         job->d_rgl = d;
         job->rgl_first = std::move(first);
@@ -3525,6 +3583,41 @@ extern "C" int pg_job_device_record_gl(pg_job* job, uint32_t ci, void** d_gl, ui
 }
 
 extern "C" double pg_job_record_gl_ms(const pg_job* job) { return job ? job->rgl_ms : 0.0; }
+
+// The packed fetches: the records and the values lie chain after chain on the device, so the whole of either is one copy.
+extern "C" int pg_job_record_first(pg_job* job, uint64_t* calls_first, uint64_t* gl_first, char* err, size_t errlen) {
+    if (!calls_first && !gl_first) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    int rc = calls_first ? rcalls_ready(job, err, errlen) : PG_OK;
+    if (rc == PG_OK && gl_first) rc = rgl_ready(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (calls_first) memcpy(calls_first, job->rcalls_first.data(), job->rcalls_first.size() * sizeof(uint64_t));
+    if (gl_first) memcpy(gl_first, job->rgl_first.data(), job->rgl_first.size() * sizeof(uint64_t));
+    return PG_OK;
+}
+
+extern "C" int pg_job_fetch_record_calls_packed(pg_job* job, pg_call* out, uint64_t n, char* err, size_t errlen) {
+    int rc = rcalls_ready(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (n != job->rcalls_first.back()) { set_err(err, errlen, "the job holds %llu records, not %llu", (unsigned long long)job->rcalls_first.back(), (unsigned long long)n); return PG_ERR_INVALID; }
+    if (n == 0) return PG_OK;
+    if (!out) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(job->device));
+    HIP_TRY(hipMemcpyAsync(out, job->d_rcalls, n * sizeof(pg_call), hipMemcpyDeviceToHost, job->stream));
+    HIP_TRY(hipStreamSynchronize(job->stream));
+    return PG_OK;
+}
+
+extern "C" int pg_job_fetch_record_gl_packed(pg_job* job, pg_gl* out, uint64_t n, char* err, size_t errlen) {
+    int rc = rgl_ready(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (n != job->rgl_first.back()) { set_err(err, errlen, "the job holds %llu GL values, not %llu", (unsigned long long)job->rgl_first.back(), (unsigned long long)n); return PG_ERR_INVALID; }
+    if (n == 0) return PG_OK;
+    if (!out) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(job->device));
+    HIP_TRY(hipMemcpyAsync(out, job->d_rgl, n * sizeof(pg_gl), hipMemcpyDeviceToHost, job->stream));
+    HIP_TRY(hipStreamSynchronize(job->stream));
+    return PG_OK;
+}
 
 // The unit entry point: host arrays and a plan in, the records' GL values out, through the same two kernels.
 extern "C" int pg_record_gl_from_bins(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id, const uint8_t* kept,

@@ -417,6 +417,31 @@ class Job:
         """elapsed ms of the kernels of the last record_gl()"""
         return float(self._lib.pg_job_record_gl_ms(self.h))
 
+    def record_plan_strided(self, contig: int, n_contigs: int, plan) -> None:
+        """pg_job_record_plan_strided: ONE plan, checked and uploaded once, for every index contig ix with ix % n_contigs ==
+        contig — the chains sample * n_contigs + contig of a sampled cohort job, where every chain is its own index contig
+        (DESIGN.md 4e-3)."""
+        from . import calls as _calls
+        _calls.job_record_plan_strided(self, contig, n_contigs, plan)
+
+    def record_first(self):
+        """pg_job_record_first: (calls_first, gl_first), [n_chains + 1] offsets in elements into the packed records / GL values
+        (after record_calls(); gl_first is None until record_gl() has run)."""
+        from . import calls as _calls
+        return _calls.job_record_first(self)
+
+    def record_calls_packed(self):
+        """pg_job_fetch_record_calls_packed: (all chains' records as one calls.CALL_DTYPE array from ONE copy, calls_first);
+        after record_calls()."""
+        from . import calls as _calls
+        return _calls.fetch_record_calls_packed(self)
+
+    def record_gl_packed(self):
+        """pg_job_fetch_record_gl_packed: (all chains' GL values as one calls.GL_DTYPE array from ONE copy, gl_first); after
+        record_gl()."""
+        from . import calls as _calls
+        return _calls.fetch_record_gl_packed(self)
+
     def viterbi_ms(self) -> float:
         """elapsed ms of the Viterbi kernels (run_phasing) of the last run"""
         return float(self._lib.pg_job_viterbi_ms(self.h))

@@ -231,4 +231,27 @@ std::vector<std::map<std::string, RecordFields>> genotype_cohort_record_fields(
     const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false,
     long double effective_N = 25000.0L, int device = 0, bool ignore_imputed = false);
 
+/** The sample column of one chromosome of a SAMPLED cohort: the record fields, and per bubble what the other columns of the
+ *  line need of the sample — the local coverage (KC) and the unique k-mer count of the sample's reduced panel (UK; 0 for
+ *  every bubble of a chain without a kept column).  Graph::genotypes_records(fields, coverage, unique_kmers, ignore_imputed)
+ *  prints the lines. */
+struct SampledRecordFields {
+    RecordFields fields;
+    std::vector<unsigned short> coverage, unique_kmers;
+};
+
+/** genotype_cohort_sampled for a caller who wants VCF lines: the arguments of genotype_cohort_sampled plus the
+ *  chromosomes' graphs and `ignore_imputed`.  pg_sampler_cohort_new, one pg_job_record_plan_strided per chromosome (the plan is
+ *  checked and uploaded once for all samples), the run, pg_job_record_calls, pg_job_record_gl and the two packed fetches: no
+ *  reduced panel and no genotype bin comes back, except for a chain with an entry the device deferred, which is finished from
+ *  that chain's own reduced panel and bins as genotype_cohort_record_fields finishes them.  The lines equal those of
+ *  Graph::genotypes_records on genotype_cohort_sampled's normalised results.  `sampled` as in genotype_cohort_sampled.  Throws
+ *  std::runtime_error on a missing graph, a graph whose bubble count is not the index's, samples that do not fit, and on the C
+ *  ABI's errors. */
+std::vector<std::map<std::string, SampledRecordFields>> genotype_cohort_sampled_record_fields(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
+    bool ignore_imputed = false, std::vector<std::map<std::string, SampledPaths>>* sampled = nullptr);
+
 }  // namespace pangenie

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "cereal_io.hpp"
+#include "graph_io.hpp"
 
 namespace pangenie {
 
@@ -218,6 +219,18 @@ std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohor
     size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
     ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
     size_t batch = 64, std::vector<std::map<std::string, SampledPaths>>* sampled = nullptr);
+
+/** The whole default pipeline — reads in, VCF sample columns out: genotype_cohort_sampled_reads with the tail
+ *  of genotype_cohort_sampled_record_fields behind pg_sampler_cohort_new_device, batch by batch.  The arguments of
+ *  genotype_cohort_sampled_reads plus the chromosomes' graphs and `ignore_imputed`; per sample and chromosome the record
+ *  fields, the coverage and the reduced panel's unique k-mer count per bubble: what
+ *  Graph::genotypes_records(fields, coverage, unique_kmers, ignore_imputed) prints equals the lines of
+ *  genotype_cohort_sampled_reads' normalised results.  Refusals as both. */
+std::vector<std::map<std::string, SampledRecordFields>> genotype_cohort_sampled_reads_record_fields(
+    UniqueKmersMap& index, const std::map<std::string, Graph>& graphs, const std::string& prefix, const std::vector<std::string>& readfiles,
+    const std::vector<size_t>& kmer_coverages, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
+    size_t batch = 64, bool ignore_imputed = false, std::vector<std::map<std::string, SampledPaths>>* sampled = nullptr);
 
 /** The reader of the counters' count() on its own: the sequences of a FASTA / FASTQ file (plain or gzipped) in batches of
  *  about `batch_bytes`, back to back with a newline after each, handed to `sink`; returns the bytes of all batches.  With a sink

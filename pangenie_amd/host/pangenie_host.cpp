@@ -880,6 +880,51 @@ static void record_gl_on_host(const VcfSite& site, pg_gl* out, size_t n) {
     for (size_t j = 0; j < n; ++j) out[j] = gl_of_log10(std::log10(all[j]));
 }
 
+// One chain's record fields from the device's records `r` (one per record of `plan`; with `with_gl`, fields.gl and
+// fields.gl_off hold the chain's values already): the calls are taken over, and what the device deferred — a bubble next to
+// long double's subnormals, a GL value in the 1e-9 window — is finished here from that chain's own bins through
+// Variant::records and genotype_field's rules.  The tail of every function that returns RecordFields.  `no_kmers(v)`: bubble
+// v reports no unique k-mers; `results(&full)` fetches the chain's bins as one GenotypingResult per bubble and returns the C
+// ABI's code: it is called only for a chain with a deferred entry, so no other chain's bins leave the device.
+template <class NoKmers, class Results>
+static int chain_record_fields(const Graph& graph, const RecordPlan& plan, const pg_call* r, bool ignore_imputed, bool with_gl, NoKmers no_kmers,
+                               Results results, RecordFields& fields) {
+    std::vector<GenotypeCall>& calls = fields.calls;
+    calls.assign(plan.nr_of_records(), GenotypeCall());
+    bool any_deferred = false;
+    std::vector<char> gl_deferred(with_gl ? plan.rec_off.size() - 1 : 0, 0);   // per bubble: a GL value is left to the host
+    for (size_t v = 0; v < gl_deferred.size(); ++v)
+        for (uint64_t i = fields.gl_off[plan.rec_off[v]]; i < fields.gl_off[plan.rec_off[v + 1]]; ++i)
+            if (fields.gl[i].mant == 0 && fields.gl[i].exp10 == PG_GL_DEFERRED) { gl_deferred[v] = 1; any_deferred = true; }
+    for (size_t v = 0; v + 1 < plan.rec_off.size(); ++v) {
+        const bool imputed = ignore_imputed && no_kmers(v);
+        for (size_t q = plan.rec_off[v]; q < plan.rec_off[v + 1]; ++q) {
+            if (imputed) continue;   // `.`: genotype_field drops the genotype of a bubble without unique k-mers
+            if ((r[q].flags & 0xFF) == PG_CALL_OK) { calls[q].allele_1 = r[q].allele_1; calls[q].allele_2 = r[q].allele_2; calls[q].quality = r[q].gq; }
+            else if (r[q].flags == PG_CALL_DEFERRED) any_deferred = true;
+        }
+    }
+    if (!any_deferred) return PG_OK;
+    // the deferred bubbles of this chain on the host, each from its own bins, through Variant::records
+    std::vector<GenotypingResult> full;
+    const int rc = results(&full);
+    if (rc != PG_OK) return rc;
+    for (size_t v = 0; v + 1 < plan.rec_off.size(); ++v) {
+        const bool call_deferred = r[plan.rec_off[v]].flags == PG_CALL_DEFERRED;   // (a bubble is deferred with all its records)
+        const bool imputed = ignore_imputed && full[v].nr_unique_kmers() == 0;
+        const bool calls_here = call_deferred && !imputed, gl_here = with_gl && gl_deferred[v];
+        if (!calls_here && !gl_here) continue;
+        full[v].normalize();
+        const std::vector<VcfSite> sites = graph.get_variant(v).records(&full[v]);
+        for (size_t k = 0; k < sites.size() && plan.rec_off[v] + k < plan.rec_off[v + 1]; ++k) {
+            const size_t q = plan.rec_off[v] + k;
+            if (calls_here) calls[q] = record_call_on_host(sites[k]);
+            if (gl_here) record_gl_on_host(sites[k], fields.gl.data() + fields.gl_off[q], fields.gl_off[q + 1] - fields.gl_off[q]);   // (the GL column is printed whatever ignore_imputed says)
+        }
+    }
+    return PG_OK;
+}
+
 // genotype_cohort_record_calls and, `with_gl`, genotype_cohort_record_fields: one job, the calls and the GL values per record
 static std::vector<std::map<std::string, RecordFields>> cohort_record_fields(
     std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
@@ -977,44 +1022,20 @@ static std::vector<std::map<std::string, RecordFields>> cohort_record_fields(
             const RecordPlan& plan = plans[c];
             const FlatContig& f = flat[c];
             RecordFields& fields = out[s][names[c]];
-            std::vector<GenotypeCall>& calls = fields.calls;
-            calls.resize(r.size());
-            bool any_deferred = false;
-            std::vector<char> gl_deferred(with_gl ? plan.rec_off.size() - 1 : 0, 0);   // per bubble: a GL value is left to the host
-            for (size_t v = 0; v < gl_deferred.size(); ++v)
-                for (uint64_t i = fields.gl_off[plan.rec_off[v]]; i < fields.gl_off[plan.rec_off[v + 1]]; ++i)
-                    if (fields.gl[i].mant == 0 && fields.gl[i].exp10 == PG_GL_DEFERRED) { gl_deferred[v] = 1; any_deferred = true; }
-            for (size_t v = 0; v + 1 < plan.rec_off.size(); ++v) {
-                const bool imputed = ignore_imputed && (!any_column[c] || f.kmer_off[v + 1] == f.kmer_off[v]);
-                for (size_t q = plan.rec_off[v]; q < plan.rec_off[v + 1]; ++q) {
-                    if (imputed) continue;   // `.`: genotype_field drops the genotype of a bubble without unique k-mers
-                    if ((r[q].flags & 0xFF) == PG_CALL_OK) { calls[q].allele_1 = r[q].allele_1; calls[q].allele_2 = r[q].allele_2; calls[q].quality = r[q].gq; }
-                    else if (r[q].flags == PG_CALL_DEFERRED) any_deferred = true;
-                }
-            }
-            if (!any_deferred) continue;
-            // the deferred bubbles of this chain on the host, each from its own bins, through Variant::records
-            const uint64_t n = goff[c].back();
-            std::vector<double> lik(n ? n : 1);
-            std::vector<int32_t> lexp(n ? n : 1);
-            pg_contig_result res{};
-            res.lik = lik.data(); res.lik_exp = lexp.data();
-            rc = pg_job_fetch(job, (uint32_t)(s * C + c), &res, err, sizeof(err));
-            if (rc != PG_OK) break;
-            std::vector<GenotypingResult> full = results_of_chain(f, cov_rows[s][c], goff[c], lik.data(), lexp.data());
-            for (size_t v = 0; v + 1 < plan.rec_off.size(); ++v) {
-                const bool call_deferred = r[plan.rec_off[v]].flags == PG_CALL_DEFERRED;   // (a bubble is deferred with all its records)
-                const bool imputed = ignore_imputed && full[v].nr_unique_kmers() == 0;
-                const bool calls_here = call_deferred && !imputed, gl_here = with_gl && gl_deferred[v];
-                if (!calls_here && !gl_here) continue;
-                full[v].normalize();
-                const std::vector<VcfSite> sites = graph_of[c]->get_variant(v).records(&full[v]);
-                for (size_t k = 0; k < sites.size() && plan.rec_off[v] + k < plan.rec_off[v + 1]; ++k) {
-                    const size_t q = plan.rec_off[v] + k;
-                    if (calls_here) calls[q] = record_call_on_host(sites[k]);
-                    if (gl_here) record_gl_on_host(sites[k], fields.gl.data() + fields.gl_off[q], fields.gl_off[q + 1] - fields.gl_off[q]);   // (the GL column is printed whatever ignore_imputed says)
-                }
-            }
+            rc = chain_record_fields(
+                *graph_of[c], plan, r.data(), ignore_imputed, with_gl,
+                [&](size_t v) { return !any_column[c] || f.kmer_off[v + 1] == f.kmer_off[v]; },
+                [&](std::vector<GenotypingResult>* full) {
+                    const uint64_t n = goff[c].back();
+                    std::vector<double> lik(n ? n : 1);
+                    std::vector<int32_t> lexp(n ? n : 1);
+                    pg_contig_result res{};
+                    res.lik = lik.data(); res.lik_exp = lexp.data();
+                    const int code = pg_job_fetch(job, (uint32_t)(s * C + c), &res, err, sizeof(err));
+                    if (code == PG_OK) *full = results_of_chain(f, cov_rows[s][c], goff[c], lik.data(), lexp.data());
+                    return code;
+                },
+                fields);
         }
     pg_job_destroy(job);
     check_rc(rc, err);
@@ -1111,6 +1132,12 @@ std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohor
 }
 
 // ------------------------------------------------------------------ sampled cohort job
+// a chain's picks as HaplotypeSampler::get_sampled_paths() has them (src/haplotypesampler.cpp:28-44)
+static void sampled_paths_of(const uint32_t* picks, uint32_t size, size_t V, bool add_reference, SampledPaths* sampled) {
+    for (uint32_t i = 0; i < size; ++i) sampled->sampled_paths.emplace_back(picks + (size_t)i * V, picks + (size_t)(i + 1) * V);
+    if (add_reference) sampled->sampled_paths.push_back(std::vector<size_t>(V, 0));
+}
+
 // The fetch tail of one chain of a sampled cohort job (chain id = sample * n_contigs + contig), shared by
 // genotype_cohort_sampled and genotype_cohort_sampled_reads: the reduced panel back from the device (the allele ids of the
 // results are its own), the results over it, and the picks as HaplotypeSampler::get_sampled_paths() has them.  `full` = the
@@ -1151,10 +1178,7 @@ static int fetch_sampled_chain(pg_job* job, uint32_t chain, const FlatContig& fu
     if (rc != PG_OK) return rc;
     // (pg_job_fetch hands the coverage out only when the chain has columns: exactly when results_of_chain reads it)
     *results = results_of_chain(r, coverage ? coverage : cov.data(), goff, lik.data(), lexp.data());
-    if (sampled) {   // as HaplotypeSampler::get_sampled_paths() has them (src/haplotypesampler.cpp:28-44)
-        for (uint32_t i = 0; i < size; ++i) sampled->sampled_paths.emplace_back(picks + (size_t)i * V, picks + (size_t)(i + 1) * V);
-        if (add_reference) sampled->sampled_paths.push_back(std::vector<size_t>(V, 0));
-    }
+    if (sampled) sampled_paths_of(picks, size, V, add_reference, sampled);
     return PG_OK;
 }
 
@@ -1288,6 +1312,239 @@ std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohor
                 for (c = 0; c < C && rc == PG_OK; ++c)
                     rc = fetch_sampled_chain(job, (uint32_t)(s * C + c), flat[c], nullptr, size, add_reference, sampled ? picks[s * C + c].data() : nullptr,
                                              &out[s0 + s][names[c]], sampled ? &(*sampled)[s0 + s][names[c]] : nullptr, err, sizeof(err));
+        } catch (...) {
+            if (counts) pg_sampler_counts_destroy(counts);
+            if (job) pg_job_destroy(job);
+            throw;
+        }
+        if (job) pg_job_destroy(job);
+        check_batch(rc);
+    }
+    return out;
+}
+
+// ------------------------------------------------------------------ sampled cohort job, the sample column per VCF record
+namespace {
+
+// what the record tail needs of one chromosome: depends on the index alone, made once whatever the samples and batches
+struct RecordChromosome {
+    std::string name;
+    const Graph* graph = nullptr;
+    RecordPlan plan;
+    std::vector<uint64_t> gl_off;
+};
+
+// refuses a missing graph or one whose bubble count is not the index's, as cohort_record_fields does; needs no device
+std::vector<RecordChromosome> record_chromosomes(const std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes,
+                                                 const std::map<std::string, Graph>& graphs, const char* who) {
+    std::vector<RecordChromosome> out;
+    for (const auto& kv : chromosomes) {
+        const auto g = graphs.find(kv.first);
+        if (g == graphs.end() || g->second.size() != kv.second.size()) fail(std::string(who) + ": no graph of " + kv.first + " with the index's bubbles");
+        RecordChromosome rc;
+        rc.name = kv.first;
+        rc.graph = &g->second;
+        rc.plan = g->second.record_plan();
+        rc.gl_off.assign(rc.plan.nr_of_records() + 1, 0);
+        const pg_record_plan view = rc.plan.view();
+        if (pg_record_gl_offsets(&view, rc.gl_off.data()) != PG_OK) fail(std::string(who) + ": pg_record_gl_offsets refused the record plan of " + kv.first);
+        out.push_back(std::move(rc));
+    }
+    return out;
+}
+
+// The tail of one sampled cohort job (made, not yet run; chains = n samples x C chromosomes, every chain its own index contig)
+// behind pg_sampler_cohort_new[_device]: one strided plan per chromosome, the run, the record calls and GL values, the two
+// packed fetches, and per chain the fields with what the device deferred finished from that chain's own reduced panel and
+// bins (fetch_sampled_chain).  `cov_rows` = the samples' own coverages ([n][C]) or null: then what pg_job_fetch hands out.
+// out[s] / sampled[s] (may be null) = sample s of this job.  Returns the C ABI's code, its text in `err`.
+int sampled_job_record_fields(pg_job* job, size_t n, const std::vector<RecordChromosome>& chroms, const std::vector<FlatContig>& flat,
+                              const std::vector<std::vector<const uint16_t*>>* cov_rows, uint32_t size, bool add_reference, bool ignore_imputed,
+                              const std::vector<std::vector<uint32_t>>& picks, std::map<std::string, SampledRecordFields>* out,
+                              std::map<std::string, SampledPaths>* sampled, char* err, size_t errlen) {
+    const size_t C = chroms.size();
+    int rc = PG_OK;
+    for (size_t c = 0; c < C && rc == PG_OK; ++c) {   // one plan per chromosome, checked and uploaded once for all samples
+        const pg_record_plan view = chroms[c].plan.view();
+        rc = pg_job_record_plan_strided(job, (uint32_t)c, (uint32_t)C, &view, err, errlen);
+    }
+    if (rc == PG_OK) rc = pg_job_run(job, nullptr, err, errlen);
+    if (rc == PG_OK) rc = pg_job_record_calls(job, err, errlen);
+    if (rc == PG_OK) rc = pg_job_record_gl(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    std::vector<uint64_t> calls_first(n * C + 1, 0), gl_first(n * C + 1, 0);
+    rc = pg_job_record_first(job, calls_first.data(), gl_first.data(), err, errlen);
+    if (rc != PG_OK) return rc;
+    std::vector<pg_call> recs(calls_first.back());
+    std::vector<pg_gl> gls(gl_first.back());
+    rc = pg_job_fetch_record_calls_packed(job, recs.data(), recs.size(), err, errlen);
+    if (rc == PG_OK) rc = pg_job_fetch_record_gl_packed(job, gls.data(), gls.size(), err, errlen);
+    for (size_t s = 0; s < n && rc == PG_OK; ++s)
+        for (size_t c = 0; c < C && rc == PG_OK; ++c) {
+            const uint32_t chain = (uint32_t)(s * C + c);   // chain id = sample * n_contigs + contig
+            const RecordChromosome& x = chroms[c];
+            const size_t V = flat[c].variant_pos.size();
+            if (calls_first[chain + 1] - calls_first[chain] != x.plan.nr_of_records() || gl_first[chain + 1] - gl_first[chain] != x.gl_off.back()) {
+                std::snprintf(err, errlen, "genotype_cohort_sampled_record_fields: chain %u holds other records than its plan's", chain);
+                return PG_ERR_INVALID;
+            }
+            SampledRecordFields& f = out[s][x.name];
+            // per bubble: the reduced panel's k-mer count and the coverage, by pg_job_fetch's rule (a chain without a kept
+            // column reports neither); host memory of the job, no device copy
+            std::vector<uint16_t> nk(V ? V : 1, 0), cov(V ? V : 1, 0);
+            pg_contig_result meta{};
+            meta.n_kmers = nk.data(); meta.coverage = cov.data();
+            rc = pg_job_fetch(job, chain, &meta, err, errlen);
+            if (rc != PG_OK) break;
+            const uint16_t* own = cov_rows ? (*cov_rows)[s][c] : nullptr;
+            f.unique_kmers.assign(nk.begin(), nk.begin() + V);
+            f.coverage.resize(V);
+            for (size_t v = 0; v < V; ++v) f.coverage[v] = own && meta.n_columns > 0 ? own[v] : own ? 0 : cov[v];
+            f.fields.gl_off = x.gl_off;
+            f.fields.gl.assign(gls.begin() + gl_first[chain], gls.begin() + gl_first[chain + 1]);
+            const uint32_t* pk = sampled ? picks[chain].data() : nullptr;
+            if (sampled) sampled_paths_of(pk, size, V, add_reference, &sampled[s][x.name]);
+            rc = chain_record_fields(
+                *x.graph, x.plan, recs.data() + calls_first[chain], ignore_imputed, true, [&](size_t v) { return f.unique_kmers[v] == 0; },
+                [&](std::vector<GenotypingResult>* full) {
+                    return fetch_sampled_chain(job, chain, flat[c], own, size, add_reference, nullptr, full, nullptr, err, errlen);
+                },
+                f.fields);
+        }
+    return rc;
+}
+
+}  // namespace
+
+std::vector<std::map<std::string, SampledRecordFields>> genotype_cohort_sampled_record_fields(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device, bool ignore_imputed,
+    std::vector<std::map<std::string, SampledPaths>>* sampled) {
+    const size_t C = chromosomes.size(), S = samples.size();
+    std::vector<std::map<std::string, SampledRecordFields>> out(S);
+    if (sampled) sampled->assign(S, {});
+    if (C == 0 || S == 0) return out;
+    const std::vector<RecordChromosome> chroms = record_chromosomes(chromosomes, graphs, "genotype_cohort_sampled_record_fields");
+    // (the job is made exactly as genotype_cohort_sampled makes it)
+    std::vector<FlatContig> flat(C);   // ALL paths of the panel
+    std::vector<pg_contig_batch> index(C);
+    size_t c = 0;
+    for (auto& kv : chromosomes) {
+        flatten(&kv.second, nullptr, flat[c]);
+        index[c] = flat[c].batch;
+        c += 1;
+    }
+    static const uint16_t none = 0;
+    std::vector<std::vector<const uint16_t*>> count_rows(S, std::vector<const uint16_t*>(C)), cov_rows(S, std::vector<const uint16_t*>(C));
+    std::vector<pg_sample_counts> rows(S);
+    for (size_t s = 0; s < S; ++s) {
+        for (c = 0; c < C; ++c) {
+            const auto k = samples[s].kmer_count.find(chroms[c].name), v = samples[s].coverage.find(chroms[c].name);
+            if (k == samples[s].kmer_count.end() || v == samples[s].coverage.end() || k->second.size() != flat[c].kmer_count.size() ||
+                v->second.size() != flat[c].variant_pos.size())
+                fail("genotype_cohort_sampled_record_fields: sample " + std::to_string(s) + " does not fit the index on " + chroms[c].name);
+            count_rows[s][c] = k->second.empty() ? &none : k->second.data();
+            cov_rows[s][c] = v->second.empty() ? &none : v->second.data();
+        }
+        rows[s].kmer_count = count_rows[s].data();
+        rows[s].coverage = cov_rows[s].data();
+    }
+    const uint32_t size = (uint32_t)panel_size;
+    std::vector<std::vector<uint32_t>> picks(sampled ? S * C : 0);
+    std::vector<uint32_t*> pick_rows(S * C, nullptr);
+    for (size_t g = 0; g < picks.size(); ++g) {
+        picks[g].assign((size_t)size * flat[g % C].variant_pos.size() + 1, 0);
+        pick_rows[g] = picks[g].data();
+    }
+    pg_hmm_params prm{};
+    prm.effective_N = effective_N; prm.recombrate = recombrate; prm.uniform = uniform ? 1 : 0; prm.run_genotyping = 1;
+    char err[1024] = {0};
+    pg_job* job = nullptr;
+    int rc = pg_sampler_cohort_new(device, (uint32_t)C, index.data(), (uint32_t)S, rows.data(), size, add_reference ? 1 : 0, recombrate,
+                                   sampling_effective_N, allele_penalty, probabilities->handle(), &prm, sampled ? pick_rows.data() : nullptr,
+                                   nullptr, &job, err, sizeof(err));
+    try {
+        if (rc == PG_OK)
+            rc = sampled_job_record_fields(job, S, chroms, flat, &cov_rows, size, add_reference, ignore_imputed, picks, out.data(),
+                                           sampled ? sampled->data() : nullptr, err, sizeof(err));
+    } catch (...) {
+        if (job) pg_job_destroy(job);
+        throw;
+    }
+    if (job) pg_job_destroy(job);
+    check_rc(rc, err);
+    return out;
+}
+
+std::vector<std::map<std::string, SampledRecordFields>> genotype_cohort_sampled_reads_record_fields(
+    UniqueKmersMap& index, const std::map<std::string, Graph>& graphs, const std::string& prefix, const std::vector<std::string>& readfiles,
+    const std::vector<size_t>& kmer_coverages, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device, size_t batch, bool ignore_imputed,
+    std::vector<std::map<std::string, SampledPaths>>* sampled) {
+    auto& chromosomes = index.unique_kmers;
+    const size_t C = chromosomes.size(), S = readfiles.size();
+    if (kmer_coverages.size() != S) fail("genotype_cohort_sampled_reads_record_fields: one k-mer coverage per read file");
+    std::vector<std::map<std::string, SampledRecordFields>> out(S);
+    if (sampled) sampled->assign(S, {});
+    if (C == 0 || S == 0) return out;
+    const std::vector<RecordChromosome> chroms = record_chromosomes(chromosomes, graphs, "genotype_cohort_sampled_reads_record_fields");
+    // (counter, count plan and batches exactly as genotype_cohort_sampled_reads makes them)
+    const size_t B = std::max<size_t>(1, std::min(batch, S));
+    DeviceKmerCounter counter(index.kmersize, false, device);
+    DeviceCountPlan plan(counter, index, prefix, true);
+    std::vector<FlatContig> flat(C);   // ALL paths of the panel
+    std::vector<pg_contig_batch> batches(C);
+    std::vector<uint64_t> n_kmers(C);
+    std::vector<uint32_t> n_variants(C);
+    size_t c = 0;
+    for (auto& kv : chromosomes) {   // (map order: the plan's)
+        flatten(&kv.second, nullptr, flat[c]);
+        batches[c] = flat[c].batch;
+        n_kmers[c] = flat[c].kmer_count.size();
+        n_variants[c] = (uint32_t)flat[c].variant_pos.size();
+        c += 1;
+    }
+    const uint32_t size = (uint32_t)panel_size;
+    pg_hmm_params prm{};
+    prm.effective_N = effective_N; prm.recombrate = recombrate; prm.uniform = uniform ? 1 : 0; prm.run_genotyping = 1;
+    char err[1024] = {0};
+    auto check_batch = [&](int rc) {   // (a batch that does not fit: the caller's remedy is a smaller one, it is never split here)
+        if (rc == PG_ERR_NOMEM) fail(std::string(err) + " (genotype_cohort_sampled_reads_record_fields: lower `batch`)");
+        check_rc(rc, err);
+    };
+    for (size_t s0 = 0; s0 < S; s0 += B) {
+        const size_t n = std::min(B, S - s0);
+        pg_sampler_counts* counts = nullptr;
+        pg_job* job = nullptr;
+        int rc = pg_sampler_counts_new(device, (uint32_t)C, n_kmers.data(), n_variants.data(), (uint32_t)n, &counts, err, sizeof(err));
+        check_batch(rc);
+        try {
+            std::vector<pg_sample_counts> rows(n);
+            for (size_t s = 0; s < n; ++s) {
+                uint16_t* const* d_k = nullptr;
+                uint16_t* const* d_c = nullptr;
+                check_rc(pg_sampler_counts_rows(counts, (uint32_t)s, &d_k, &d_c, err, sizeof(err)), err);
+                counter.reset_counts();
+                counter.count(readfiles[s0 + s]);
+                plan.fill_device(kmer_coverages[s0 + s], d_k, d_c);
+                rows[s].kmer_count = d_k;
+                rows[s].coverage = d_c;
+            }
+            std::vector<std::vector<uint32_t>> picks(sampled ? n * C : 0);
+            std::vector<uint32_t*> pick_rows(n * C, nullptr);
+            for (size_t g = 0; g < picks.size(); ++g) {
+                picks[g].assign((size_t)size * flat[g % C].variant_pos.size() + 1, 0);
+                pick_rows[g] = picks[g].data();
+            }
+            rc = pg_sampler_cohort_new_device(device, (uint32_t)C, batches.data(), (uint32_t)n, rows.data(), size, add_reference ? 1 : 0, recombrate,
+                                              sampling_effective_N, allele_penalty, probabilities->handle(), &prm, sampled ? pick_rows.data() : nullptr,
+                                              nullptr, &job, err, sizeof(err));
+            pg_sampler_counts_destroy(counts);   // (the job does not reference the arrays)
+            counts = nullptr;
+            if (rc == PG_OK)
+                rc = sampled_job_record_fields(job, n, chroms, flat, nullptr, size, add_reference, ignore_imputed, picks, out.data() + s0,
+                                               sampled ? sampled->data() + s0 : nullptr, err, sizeof(err));
         } catch (...) {
             if (counts) pg_sampler_counts_destroy(counts);
             if (job) pg_job_destroy(job);
