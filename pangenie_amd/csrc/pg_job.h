@@ -1,0 +1,271 @@
+// pg_job.h — what the host units of the C-ABI shim share (pg_shim.cpp: jobs, their build and run schedule;
+// pg_shim_calls.cpp: the output columns formed from a job's finished bins): the error helpers, the host's picture of a
+// job's index contigs, chains and record plans, and struct pg_job itself.  Private: nothing here is exported.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include <memory>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/pangenie_hmm.h"
+#include "pg_device.h"
+#include "pg_launch.h"
+
+namespace pgj __attribute__((visibility("hidden"))) {
+
+inline void set_err(char* err, size_t errlen, const char* fmt, ...) {
+    if (!err || errlen == 0) return;
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(err, errlen, fmt, ap);
+    va_end(ap);
+}
+
+#define HIP_TRY(call)                                                                     \
+    do {                                                                                  \
+        hipError_t e_ = (call);                                                           \
+        if (e_ != hipSuccess) {                                                           \
+            set_err(err, errlen, "%s failed: %s", #call, hipGetErrorString(e_));          \
+            return PG_ERR_DEVICE;                                                         \
+        }                                                                                 \
+    } while (0)
+
+constexpr int PG_MAX_DEVICES_HOST = 64;
+inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+struct IndexHost {   // one index contig
+    uint32_t V = 0, H = 0, HP = 0, T = 0, RB = 0, part_slots = 2, pair_n = 1;
+    bool lean = false;  // every object biallelic and H = HP = 64: the store-only phases run on k_sweep_lean
+    bool cls4 = false;  // HP = 16 / 32, H = HP, every object biallelic, fused job: class sums instead of per-thread partials (DevContig::cls4)
+    bool leanx = false; // HP = 128 / 64 and every object has at most PG_AMAX alleles (not `lean`): the store-only phases run on k_sweep_leanx
+    bool small = false; // every object biallelic and H = HP = 16: the store-only phases run on k_sweep_small16
+    bool smallx = false; // H = HP = 16 with multiallelic objects (the 15 + 1 sampled paths): k_sweep_small16x (pg_small16x.h)
+    std::vector<uint32_t> list_b;            // ... and k_prep_bi's own
+    size_t o_list_b = 0;
+    std::vector<uint32_t> list_m4, list_w;   // prep_fast == 2: the objects of k_prep_m4 (3 .. PG_AMAX alleles, <= 64 k-mers) / of k_prep (neither that nor k_prep_bi's)
+    size_t o_list_m4 = 0, o_list_w = 0;
+    std::vector<uint32_t> auxidx;    // [V] aux slot offset / 16 of every variant with more than two alleles (smallx), PG_WIDE_NONE otherwise
+    uint64_t aux_bytes = 0;
+    uint32_t n_wide_cand = 0;        // variants with more than PG_AMAX alleles (each may be a wide column)
+    bool widef_cand = false, widef = false;   // 64-path chains on the general kernel with such variants: in a fused job a wide column costs that column (DevContig::widef)
+    size_t o_auxidx = 0;
+    uint32_t prep_fast = 0;  // 1: every object has exactly two alleles and <= 32 k-mers, H <= 64: k_prep_bi; 2: at least half of them (k_prep the rest)
+    // The split path (pg_device.h, pg_split.h): 1 / 2 = the chains over this index contig are small / smallx chains whose
+    // per-variant work is split into what the index alone decides (formed once per upload) and what the sample's counts decide
+    uint32_t split = 0;
+    bool all_sb = false;     // every object is k_prep_s_bi's (two alleles, <= 32 k-mers): no lists
+    std::vector<uint32_t> list_big;   // variants with more than 32 alleles: the wave-per-object index kernels' list (the others: one thread each)
+    size_t o_list_big = 0;
+    // index-level device arrays (every chain over this contig points at them)
+    size_t o_kept = 0, o_apres = 0, o_colv = 0, o_colof = 0, o_ixpd = 0, o_ixrec = 0, o_ixbin = 0, o_ixwl = 0, o_ixnw = 0;
+    uint32_t sumK = 0, sumA = 0;
+    uint64_t n_lik = 0, wide_bytes = 0;
+    std::vector<uint16_t> n_kmers;   // [V] K of every variant
+    std::vector<uint32_t> widx;      // [V] wide entry offset / 16 (only if wide_bytes)
+    std::vector<uint64_t> goff;      // [V+1]
+    std::vector<uint64_t> pos;       // [V] host copy of the positions (run_phasing: the Viterbi's transition probabilities)
+    std::vector<uint32_t> koff, aoff;  // [V+1] the per-variant layout the arena, goff / widx and the kernel choice were planned for
+    // device
+    size_t o_pos = 0, o_koff = 0, o_aoff = 0, o_aid = 0, o_aflag = 0, o_akoff = 0, o_akmask = 0, o_pa = 0, o_goff = 0, o_widx = 0;
+};
+
+struct ChainHost {
+    uint32_t index = 0;
+    std::vector<uint16_t> coverage;  // [V] host copy (GenotypingResult::set_coverage)
+    size_t o_cov = 0, o_kcnt = 0;
+    uint64_t lik_first = 0;          // offset of this chain's bins inside the packed lik / lik_exp regions
+    DevContig d;
+    uint32_t n_cols_host = 0;
+};
+
+// One index contig's record plan (pg_record_plan, include/pangenie_hmm.h) as the host keeps it, and its device copy.
+struct RecordPlanHost {
+    bool set = false;
+    uint32_t V = 0, R = 0;
+    std::vector<uint32_t> rec_off, rec_var, map_off, vcf_off;
+    std::vector<uint16_t> map, vcf_index;
+    unsigned char* d = nullptr;   // rec_var, map_off, map, vcf_off, vcf_index: one allocation
+    RecPlanDev dev = {};
+};
+// A plan a job holds: its index contigs refer to it, one alone (pg_job_record_plan) or every member of a stride
+// (pg_job_record_plan_strided); the device copy goes with the last reference.
+using RecordPlanRef = std::shared_ptr<const RecordPlanHost>;
+inline RecordPlanRef record_plan_ref(RecordPlanHost&& h) {
+    return RecordPlanRef(new RecordPlanHost(std::move(h)), [](const RecordPlanHost* p) { if (p->d) hipFree(p->d); delete p; });
+}
+
+// What a job keeps of ONE output family (the calls, the record calls, the record GLs; pg_shim_calls.cpp): a device buffer of its
+// own outside the arena — the output chain after chain, then (record GLs: the plans' offsets, then) the chain descriptors, the
+// wide kernel's list and its staging slots — and what a launch over it needs.  Made by the family's first forming (a job whose
+// user fetches bins never pays for it), freed in pg_job_destroy.
+struct OutputFamily {
+    unsigned char* d = nullptr;
+    std::vector<uint64_t> first;              // [n_chains + 1] first element of every chain (a chain without variants / a plan has none)
+    size_t o_desc = 0, o_wide = 0, o_stage = 0;   // bytes into d: descriptors, the wide list, the staging slots (records only)
+    uint32_t blocks = 0, wide = 0, max_bins = 0, stride = 0, slots = 0;
+    bool dirty = true;                        // records: a plan or the index changed: descriptors, lists and the id check are redone
+    bool formed = false;                      // a launch over the buffer as it is has finished (NOT reset by a later pg_job_run)
+    double ms = 0.0;
+    void release() { if (d) hipFree(d); d = nullptr; }
+};
+
+}  // namespace pgj
+
+struct pg_job {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::vector<pgj::IndexHost> index;
+    std::vector<pgj::ChainHost> chains;
+    uint32_t n_contigs = 0, n_samples = 1;  // chains = n_samples * n_contigs (sample-major)
+    bool cohort = false;
+    DevContig* d_contigs = nullptr;
+    unsigned char* arena = nullptr;
+    size_t arena_bytes = 0;
+    bool cache_arena = false;  // hand the arena to the process cache on destroy (one-shot call)
+    // regions zeroed at the start of every run
+    unsigned char* zero_base = nullptr;
+    size_t zero_bytes = 0;
+    uint32_t* d_small = nullptr;  // [n_small] chain ids of the H = 16 chains
+    uint32_t n_small = 0;
+    uint32_t* d_smallx = nullptr; // [n_smallx] ... of those with multiallelic objects (k_sweep_small16x), behind d_small's
+    uint32_t n_smallx = 0;
+    bool smallx_phase2 = false;
+    bool small_phase2 = false;    // some of them (fused jobs, class sums: DevContig::small == 2) also run their phase 2 on k_sweep_small16
+    double* d_dump = nullptr;
+    uint32_t* d_ncols = nullptr;  // [n_index] kept columns of every index contig (k_compact, when the index is uploaded)
+    uint32_t* d_ixerr = nullptr;  // [n_index] error bits of the index-level kernels
+    DevContig* d_reps = nullptr;  // [n_index] one chain descriptor per index contig: what the index-level kernels walk
+    unsigned char* ix_base = nullptr;   // the index-derived arrays of all contigs, one run of the arena (zeroed before every index pass)
+    size_t ix_bytes = 0;
+    unsigned char* srec_base = nullptr; // the sample records of all split chains, one run (zeroed with every index pass: k_prep_s_bi leaves the zero pieces out)
+    size_t srec_bytes = 0;
+    bool any_split = false;
+    uint32_t max_sb = 0, max_sm4 = 0, max_sw = 0;   // grid extents of the split path's emission kernels
+    bool any_legacy_prep = false;
+    hipEvent_t ev_ix[2];
+    double index_ms = 0.0;
+    std::string plan_text;
+    std::vector<unsigned char> tab_p;
+    size_t o_tab_p = 0;
+    uint32_t* d_err = nullptr;    // [n_chains]
+    double* d_lik = nullptr;      // packed, chain after chain
+    int32_t* d_likexp = nullptr;
+    uint64_t n_lik_total = 0;
+    size_t o_tab_m = 0, o_tab_e = 0;
+    std::vector<double> tab_m;
+    std::vector<int32_t> tab_e;
+    DevTable tab;
+    uint32_t hp_mask = 0, max_v = 0;   // hp_mask: the PG_SWEEP_* bits of the job's chain kernels (pg_launch.h; choose_chain_kernels)
+    uint32_t max_wide = 0;   // grid extent of k_bins_wide: the longest list of wide-column candidates
+    uint32_t max_prep_w = 0, max_prep_m4 = 0;   // grid extents of k_prep (lists or all variants) and k_prep_m4
+    uint32_t bins_which = 0;   // the PG_BINS_* bits of the kernels that form a fused job's bins
+    uint32_t vit_bits = 0;     // run_phasing: 1 / 2 / 4 = chains with 16 / 32 / 64 padded paths
+    hipEvent_t ev_vit[2];
+    double vit_ms = 0.0;
+    bool vit_tq_ready = false;  // the transition probabilities of the kept columns are on the device (they depend on the index only)
+    hipEvent_t ev[PG_N_KERNEL_CLASSES + 1];
+    bool events = false;
+    double ms[PG_N_KERNEL_CLASSES] = {0, 0, 0, 0, 0, 0};
+    double host_s[4] = {0, 0, 0, 0};
+    uint64_t up_bytes[2] = {0, 0};
+    pg_hmm_params params;
+    bool ran = false;
+    // Sweep mode.  fused: phase 2 forms the posterior partials inline (k_bins reduces them) — least
+    // HBM traffic, the choice when hundreds of chains fill the chip.  chunked: with few chains the
+    // chip is idle and a chain's time is its per-column latency, so phase 2 runs as store-only
+    // chunks (as cheap per column as phase 1) and k_post forms the posteriors of each finished
+    // chunk on the idle CUs from a second stream.
+    bool chunked = false;
+    uint32_t chunk_cols = 0, n_chunks = 0;
+    // chunked jobs whose chains are ALL lean chains, few enough that every workgroup of k_sweep_lean<4> and k_post_loop has a CU
+    // of its own: phase 2 is ONE launch of each, chunks handed over through DevContig::sync (PG_KERNELS=nopersist: a launch per chunk)
+    bool persist = false;
+    uint32_t post_blocks = 0;
+    // chunked jobs (a launch per chunk) that leave CUs idle, chunk_cols a multiple of PG_LEAN_SPARSE: phase 1 of the lean chains stores
+    // only its checkpoints and k_refill_lean forms the columns between them on the second stream, chunk by chunk in front of k_post
+    // (DevContig::sparse; PG_KERNELS=nosparse: every column by the chain)
+    bool sparse = false;
+    // ... and every chain with columns is such a chain: the chunk sweeps of phase 2 store only their checkpoints too, into an area
+    // of their own (DevContig::sparse2), and k_refill_lean forms each chunk's columns behind its sweep on the second stream — which
+    // then owns the scratch buffers alone: the sweeps wait for no k_post (PG_KERNELS=nosparse2: dense chunk sweeps)
+    bool sparse2 = false;
+    std::vector<hipEvent_t> ev_chunk;   // sparse2: one "sweep done" event per chunk (the sweeps run chunks ahead of the stream that waits for them)
+    // sparse2 jobs of more than one piece: phase 1 runs as one launch per piece of `piece_chunks` partner chunks (pg_device.h:
+    // pg_sparse_piece), the farthest from the phase boundary first, and the second stream — idle in phase 1 — refills the partner
+    // columns of a piece's chunks behind it, beside the pieces that follow.  Only piece 0's chunks are left for phase 2 to refill.
+    // (PG_KERNELS=nopieces: one launch; PG_PIECE_CHUNKS: chunks per piece.)  n_pieces == 1: the single launch
+    uint32_t piece_chunks = 0, n_pieces = 1;
+    uint32_t piece_refill_blocks = 0;   // workgroups of a refill launched beside phase 1: fewer than in phase 2 (job_build)
+    std::vector<hipEvent_t> ev_piece;   // one "piece done" event per piece
+    // The pipelined first run of a one-shot job (job_build with cache_arena: upload and run inside ONE call, the host arrays stay
+    // valid): the inputs of the LONG chains (group A: the job's wall time) are uploaded first and their preparation + phase 1
+    // start while the other chains' inputs (group B, most of the bytes) are still crossing PCIe; B's index pass, preparation and
+    // phase 1 then run on the second stream beside A's.  24 chromosomes x 64 paths: 27 ms of H2D in front of a 252 ms run.
+    bool pipeline = false, pipeline_capable = false, late_pending = false;
+    uint32_t nA = 0;
+    std::vector<uint32_t> grp_order;          // chains (= index contigs: 1:1 in such jobs), group A first
+    DevContig* d_contigs_g = nullptr;         // the chain descriptors in that order
+    DevContig* d_reps_g = nullptr;            // the index descriptors in that order
+    std::vector<std::thread> late_threads;    // group B's copies
+    std::vector<int> late_rc;
+    hipEvent_t ev_late[2];
+    bool ev_late_made = false;
+    hipStream_t persist_checked = nullptr;   // the stream whose kernels are known to run beside stream2's (streams_concurrent)
+    bool persist_checked_any = false;
+    uint32_t* d_handshake = nullptr;
+    uint32_t persist_runs = 0, persist_fallbacks = 0;
+    hipStream_t stream2 = nullptr;
+    hipEvent_t ev_sweep[PG_SCRATCH_BUFS], ev_post[PG_SCRATCH_BUFS];
+    bool events2 = false;
+    // Per-sample inputs (read k-mer counts, local coverage) of all chains lie in ONE contiguous run of the arena,
+    // [sample_lo, sample_lo + sample_bytes): a cohort's next batch of samples is packed by host threads into a pinned
+    // staging buffer of the same layout and moved with a handful of large copies (sample_upload) — and, through
+    // pg_job_upload_begin / _end, into a SECOND set of arrays while the current one is being genotyped.
+    size_t sample_lo = 0, sample_bytes = 0;
+    unsigned char* staging = nullptr;         // pinned, sample_bytes (allocated on first use)
+    bool staging_refused = false;             // hipHostMalloc failed once: sample uploads copy chain by chain from pageable memory
+    unsigned char* alt_samples = nullptr;     // device: the other set of per-sample arrays (allocated on first pg_job_upload_begin)
+    DevContig* d_contigs_alt = nullptr;       // chain descriptors pointing into the other set (the spare of the two descriptor arrays)
+    DevContig* d_contigs_owned = nullptr;     // the descriptor array that is not part of the arena (to free)
+    std::vector<DevContig> h_contigs;         // host copy of the descriptors of the set in use
+    unsigned char* cur_samples = nullptr;     // base of the set in use (arena + sample_lo, or alt_samples)
+    hipStream_t copy_stream = nullptr;
+    std::thread uploader;                     // pg_job_upload_begin's worker
+    bool upload_pending = false;
+    int upload_rc = PG_OK;
+    std::string upload_err;
+    std::vector<std::vector<uint16_t>> next_coverage;   // host copies of the pending batch's coverage arrays
+    hipEvent_t ev_fill = nullptr;             // orders a count plan's stream against the job's (pgi_job_fill_begin / _end; made by the first fill)
+    // The output columns formed from the finished bins (pg_shim_calls.cpp), one OutputFamily each; the host copies of the
+    // descriptors keep their own types.  Calls (pg_job_calls): one 8-byte record per variant, chain after chain.
+    pgj::OutputFamily calls;
+    std::vector<CallsDesc> calls_desc;        // host copy of the descriptors (chains with variants)
+    hipEvent_t ev_calls[2];                   // the three families time their launches with the same two events
+    bool calls_events = false;
+    // Record calls (pg_job_record_plan / pg_job_record_calls): one plan per index contig, shared by every chain over it, and one
+    // 8-byte record per VCF record of every chain whose index contig has a plan.
+    std::vector<pgj::RecordPlanRef> rplans;   // [n_index] (sized by the first pg_job_record_plan[_strided]); null: no plan
+    bool rplan_ids_ok = false;                // k_rplan_ids has passed the plans and the index as they are
+    pgj::OutputFamily rcalls;
+    std::vector<RCallsDesc> rcalls_desc;
+    // Record GLs (pg_job_record_gl): 4 bytes per genotype of every record's defined alleles, chain after chain, under the same plans.
+    pgj::OutputFamily rgl;                    // (first: the first VALUE of every chain)
+    std::vector<RGlDesc> rgl_desc;
+};
+
+namespace pgj __attribute__((visibility("hidden"))) {
+
+// a plan was set or the index uploaded anew (new allele ids): both record families rebuild and the ids are checked again
+inline void record_plans_changed(pg_job* job) {
+    job->rcalls.dirty = true;
+    job->rgl.dirty = true;
+    job->rplan_ids_ok = false;
+}
+
+}  // namespace pgj

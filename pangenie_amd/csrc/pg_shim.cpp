@@ -1,4 +1,7 @@
-// pg_shim.cpp — C-ABI of include/pangenie_hmm.h on top of the HIP kernels (pg_kernels.hip).
+// pg_shim.cpp — C-ABI of include/pangenie_hmm.h on top of the HIP kernels (pg_kernels.hip): the probability table, jobs
+// (their build, upload, run schedule and bin fetches), the coalescer of one-shot calls and the unit entry points of the
+// emission / transition kernels.  The output columns formed from a job's finished bins — calls, record calls, record GLs —
+// are pg_shim_calls.cpp's; the two units share struct pg_job and the host's chain / index / plan types through pg_job.h.
 //
 // Host side of the boundary: argument checking, one device arena per job, H2D/D2H,
 // launch order, hipEvent timing per kernel class.  No compute happens here except the
@@ -31,32 +34,13 @@
 #include <vector>
 
 #include "../../include/pangenie_hmm.h"
-#include "pg_calls.h"
 #include "pg_device.h"
+#include "pg_job.h"
 #include "pg_launch.h"
 
+using namespace pgj;
 
 namespace {
-
-void set_err(char* err, size_t errlen, const char* fmt, ...) {
-    if (!err || errlen == 0) return;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(err, errlen, fmt, ap);
-    va_end(ap);
-}
-
-#define HIP_TRY(call)                                                                     \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            set_err(err, errlen, "%s failed: %s", #call, hipGetErrorString(e_));          \
-            return PG_ERR_DEVICE;                                                         \
-        }                                                                                 \
-    } while (0)
-
-constexpr int PG_MAX_DEVICES_HOST = 64;
-inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
 double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -208,51 +192,6 @@ static const char* const kKernelNames[PG_N_KERNEL_CLASSES] = {"k_prep", "k_compa
 
 namespace {
 
-struct IndexHost {   // one index contig
-    uint32_t V = 0, H = 0, HP = 0, T = 0, RB = 0, part_slots = 2, pair_n = 1;
-    bool lean = false;  // every object biallelic and H = HP = 64: the store-only phases run on k_sweep_lean
-    bool cls4 = false;  // HP = 16 / 32, H = HP, every object biallelic, fused job: class sums instead of per-thread partials (DevContig::cls4)
-    bool leanx = false; // HP = 128 / 64 and every object has at most PG_AMAX alleles (not `lean`): the store-only phases run on k_sweep_leanx
-    bool small = false; // every object biallelic and H = HP = 16: the store-only phases run on k_sweep_small16
-    bool smallx = false; // H = HP = 16 with multiallelic objects (the 15 + 1 sampled paths): k_sweep_small16x (pg_small16x.h)
-    std::vector<uint32_t> list_b;            // ... and k_prep_bi's own
-    size_t o_list_b = 0;
-    std::vector<uint32_t> list_m4, list_w;   // prep_fast == 2: the objects of k_prep_m4 (3 .. PG_AMAX alleles, <= 64 k-mers) / of k_prep (neither that nor k_prep_bi's)
-    size_t o_list_m4 = 0, o_list_w = 0;
-    std::vector<uint32_t> auxidx;    // [V] aux slot offset / 16 of every variant with more than two alleles (smallx), PG_WIDE_NONE otherwise
-    uint64_t aux_bytes = 0;
-    uint32_t n_wide_cand = 0;        // variants with more than PG_AMAX alleles (each may be a wide column)
-    bool widef_cand = false, widef = false;   // 64-path chains on the general kernel with such variants: in a fused job a wide column costs that column (DevContig::widef)
-    size_t o_auxidx = 0;
-    uint32_t prep_fast = 0;  // 1: every object has exactly two alleles and <= 32 k-mers, H <= 64: k_prep_bi; 2: at least half of them (k_prep the rest)
-    // The split path (pg_device.h, pg_split.h): 1 / 2 = the chains over this index contig are small / smallx chains whose
-    // per-variant work is split into what the index alone decides (formed once per upload) and what the sample's counts decide
-    uint32_t split = 0;
-    bool all_sb = false;     // every object is k_prep_s_bi's (two alleles, <= 32 k-mers): no lists
-    std::vector<uint32_t> list_big;   // variants with more than 32 alleles: the wave-per-object index kernels' list (the others: one thread each)
-    size_t o_list_big = 0;
-    // index-level device arrays (every chain over this contig points at them)
-    size_t o_kept = 0, o_apres = 0, o_colv = 0, o_colof = 0, o_ixpd = 0, o_ixrec = 0, o_ixbin = 0, o_ixwl = 0, o_ixnw = 0;
-    uint32_t sumK = 0, sumA = 0;
-    uint64_t n_lik = 0, wide_bytes = 0;
-    std::vector<uint16_t> n_kmers;   // [V] K of every variant
-    std::vector<uint32_t> widx;      // [V] wide entry offset / 16 (only if wide_bytes)
-    std::vector<uint64_t> goff;      // [V+1]
-    std::vector<uint64_t> pos;       // [V] host copy of the positions (run_phasing: the Viterbi's transition probabilities)
-    std::vector<uint32_t> koff, aoff;  // [V+1] the per-variant layout the arena, goff / widx and the kernel choice were planned for
-    // device
-    size_t o_pos = 0, o_koff = 0, o_aoff = 0, o_aid = 0, o_aflag = 0, o_akoff = 0, o_akmask = 0, o_pa = 0, o_goff = 0, o_widx = 0;
-};
-
-struct ChainHost {
-    uint32_t index = 0;
-    std::vector<uint16_t> coverage;  // [V] host copy (GenotypingResult::set_coverage)
-    size_t o_cov = 0, o_kcnt = 0;
-    uint64_t lik_first = 0;          // offset of this chain's bins inside the packed lik / lik_exp regions
-    DevContig d;
-    uint32_t n_cols_host = 0;
-};
-
 // entries of posterior partials per column and slot pair (DevContig::T), the ONE place the arena plan and the chain
 // descriptors take it from: threads per chain workgroup, half of them at HP = 32 (lanes l and l + 32 are folded: fold32)
 uint32_t part_entries(const IndexHost& x) { return x.HP == 32u ? x.T / 2u : x.T; }
@@ -382,182 +321,7 @@ struct PinnedPool {
     void clear() { std::lock_guard<std::mutex> l(mu); for (unsigned char* p : free_list) hipHostFree(p); free_list.clear(); }
 } g_pinned;
 
-// One index contig's record plan (pg_record_plan, include/pangenie_hmm.h) as the host keeps it, and its device copy.
-struct RecordPlanHost {
-    bool set = false;
-    uint32_t V = 0, R = 0;
-    std::vector<uint32_t> rec_off, rec_var, map_off, vcf_off;
-    std::vector<uint16_t> map, vcf_index;
-    unsigned char* d = nullptr;   // rec_var, map_off, map, vcf_off, vcf_index: one allocation
-    RecPlanDev dev = {};
-};
-// A plan a job holds: its index contigs refer to it, one alone (pg_job_record_plan) or every member of a stride
-// (pg_job_record_plan_strided); the device copy goes with the last reference.
-using RecordPlanRef = std::shared_ptr<const RecordPlanHost>;
-inline RecordPlanRef record_plan_ref(RecordPlanHost&& h) {
-    return RecordPlanRef(new RecordPlanHost(std::move(h)), [](const RecordPlanHost* p) { if (p->d) hipFree(p->d); delete p; });
-}
-
 }  // namespace
-
-struct pg_job {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::vector<IndexHost> index;
-    std::vector<ChainHost> chains;
-    uint32_t n_contigs = 0, n_samples = 1;  // chains = n_samples * n_contigs (sample-major)
-    bool cohort = false;
-    DevContig* d_contigs = nullptr;
-    unsigned char* arena = nullptr;
-    size_t arena_bytes = 0;
-    bool cache_arena = false;  // hand the arena to the process cache on destroy (one-shot call)
-    // regions zeroed at the start of every run
-    unsigned char* zero_base = nullptr;
-    size_t zero_bytes = 0;
-    uint32_t* d_small = nullptr;  // [n_small] chain ids of the H = 16 chains
-    uint32_t n_small = 0;
-    uint32_t* d_smallx = nullptr; // [n_smallx] ... of those with multiallelic objects (k_sweep_small16x), behind d_small's
-    uint32_t n_smallx = 0;
-    bool smallx_phase2 = false;
-    bool small_phase2 = false;    // some of them (fused jobs, class sums: DevContig::small == 2) also run their phase 2 on k_sweep_small16
-    double* d_dump = nullptr;
-    uint32_t* d_ncols = nullptr;  // [n_index] kept columns of every index contig (k_compact, when the index is uploaded)
-    uint32_t* d_ixerr = nullptr;  // [n_index] error bits of the index-level kernels
-    DevContig* d_reps = nullptr;  // [n_index] one chain descriptor per index contig: what the index-level kernels walk
-    unsigned char* ix_base = nullptr;   // the index-derived arrays of all contigs, one run of the arena (zeroed before every index pass)
-    size_t ix_bytes = 0;
-    unsigned char* srec_base = nullptr; // the sample records of all split chains, one run (zeroed with every index pass: k_prep_s_bi leaves the zero pieces out)
-    size_t srec_bytes = 0;
-    bool any_split = false;
-    uint32_t max_sb = 0, max_sm4 = 0, max_sw = 0;   // grid extents of the split path's emission kernels
-    bool any_legacy_prep = false;
-    hipEvent_t ev_ix[2];
-    double index_ms = 0.0;
-    std::string plan_text;
-    std::vector<unsigned char> tab_p;
-    size_t o_tab_p = 0;
-    uint32_t* d_err = nullptr;    // [n_chains]
-    double* d_lik = nullptr;      // packed, chain after chain
-    int32_t* d_likexp = nullptr;
-    uint64_t n_lik_total = 0;
-    size_t o_tab_m = 0, o_tab_e = 0;
-    std::vector<double> tab_m;
-    std::vector<int32_t> tab_e;
-    DevTable tab;
-    uint32_t hp_mask = 0, max_v = 0;   // hp_mask: the PG_SWEEP_* bits of the job's chain kernels (pg_launch.h; choose_chain_kernels)
-    uint32_t max_wide = 0;   // grid extent of k_bins_wide: the longest list of wide-column candidates
-    uint32_t max_prep_w = 0, max_prep_m4 = 0;   // grid extents of k_prep (lists or all variants) and k_prep_m4
-    uint32_t bins_which = 0;   // the PG_BINS_* bits of the kernels that form a fused job's bins
-    uint32_t vit_bits = 0;     // run_phasing: 1 / 2 / 4 = chains with 16 / 32 / 64 padded paths
-    hipEvent_t ev_vit[2];
-    double vit_ms = 0.0;
-    bool vit_tq_ready = false;  // the transition probabilities of the kept columns are on the device (they depend on the index only)
-    hipEvent_t ev[PG_N_KERNEL_CLASSES + 1];
-    bool events = false;
-    double ms[PG_N_KERNEL_CLASSES] = {0, 0, 0, 0, 0, 0};
-    double host_s[4] = {0, 0, 0, 0};
-    uint64_t up_bytes[2] = {0, 0};
-    pg_hmm_params params;
-    bool ran = false;
-    // Sweep mode.  fused: phase 2 forms the posterior partials inline (k_bins reduces them) — least
-    // HBM traffic, the choice when hundreds of chains fill the chip.  chunked: with few chains the
-    // chip is idle and a chain's time is its per-column latency, so phase 2 runs as store-only
-    // chunks (as cheap per column as phase 1) and k_post forms the posteriors of each finished
-    // chunk on the idle CUs from a second stream.
-    bool chunked = false;
-    uint32_t chunk_cols = 0, n_chunks = 0;
-    // chunked jobs whose chains are ALL lean chains, few enough that every workgroup of k_sweep_lean<4> and k_post_loop has a CU
-    // of its own: phase 2 is ONE launch of each, chunks handed over through DevContig::sync (PG_KERNELS=nopersist: a launch per chunk)
-    bool persist = false;
-    uint32_t post_blocks = 0;
-    // chunked jobs (a launch per chunk) that leave CUs idle, chunk_cols a multiple of PG_LEAN_SPARSE: phase 1 of the lean chains stores
-    // only its checkpoints and k_refill_lean forms the columns between them on the second stream, chunk by chunk in front of k_post
-    // (DevContig::sparse; PG_KERNELS=nosparse: every column by the chain)
-    bool sparse = false;
-    // ... and every chain with columns is such a chain: the chunk sweeps of phase 2 store only their checkpoints too, into an area
-    // of their own (DevContig::sparse2), and k_refill_lean forms each chunk's columns behind its sweep on the second stream — which
-    // then owns the scratch buffers alone: the sweeps wait for no k_post (PG_KERNELS=nosparse2: dense chunk sweeps)
-    bool sparse2 = false;
-    std::vector<hipEvent_t> ev_chunk;   // sparse2: one "sweep done" event per chunk (the sweeps run chunks ahead of the stream that waits for them)
-    // sparse2 jobs of more than one piece: phase 1 runs as one launch per piece of `piece_chunks` partner chunks (pg_device.h:
-    // pg_sparse_piece), the farthest from the phase boundary first, and the second stream — idle in phase 1 — refills the partner
-    // columns of a piece's chunks behind it, beside the pieces that follow.  Only piece 0's chunks are left for phase 2 to refill.
-    // (PG_KERNELS=nopieces: one launch; PG_PIECE_CHUNKS: chunks per piece.)  n_pieces == 1: the single launch
-    uint32_t piece_chunks = 0, n_pieces = 1;
-    uint32_t piece_refill_blocks = 0;   // workgroups of a refill launched beside phase 1: fewer than in phase 2 (job_build)
-    std::vector<hipEvent_t> ev_piece;   // one "piece done" event per piece
-    // The pipelined first run of a one-shot job (job_build with cache_arena: upload and run inside ONE call, the host arrays stay
-    // valid): the inputs of the LONG chains (group A: the job's wall time) are uploaded first and their preparation + phase 1
-    // start while the other chains' inputs (group B, most of the bytes) are still crossing PCIe; B's index pass, preparation and
-    // phase 1 then run on the second stream beside A's.  24 chromosomes x 64 paths: 27 ms of H2D in front of a 252 ms run.
-    bool pipeline = false, pipeline_capable = false, late_pending = false;
-    uint32_t nA = 0;
-    std::vector<uint32_t> grp_order;          // chains (= index contigs: 1:1 in such jobs), group A first
-    DevContig* d_contigs_g = nullptr;         // the chain descriptors in that order
-    DevContig* d_reps_g = nullptr;            // the index descriptors in that order
-    std::vector<std::thread> late_threads;    // group B's copies
-    std::vector<int> late_rc;
-    hipEvent_t ev_late[2];
-    bool ev_late_made = false;
-    hipStream_t persist_checked = nullptr;   // the stream whose kernels are known to run beside stream2's (streams_concurrent)
-    bool persist_checked_any = false;
-    uint32_t* d_handshake = nullptr;
-    uint32_t persist_runs = 0, persist_fallbacks = 0;
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ev_sweep[PG_SCRATCH_BUFS], ev_post[PG_SCRATCH_BUFS];
-    bool events2 = false;
-    // Per-sample inputs (read k-mer counts, local coverage) of all chains lie in ONE contiguous run of the arena,
-    // [sample_lo, sample_lo + sample_bytes): a cohort's next batch of samples is packed by host threads into a pinned
-    // staging buffer of the same layout and moved with a handful of large copies (sample_upload) — and, through
-    // pg_job_upload_begin / _end, into a SECOND set of arrays while the current one is being genotyped.
-    size_t sample_lo = 0, sample_bytes = 0;
-    unsigned char* staging = nullptr;         // pinned, sample_bytes (allocated on first use)
-    bool staging_refused = false;             // hipHostMalloc failed once: sample uploads copy chain by chain from pageable memory
-    unsigned char* alt_samples = nullptr;     // device: the other set of per-sample arrays (allocated on first pg_job_upload_begin)
-    DevContig* d_contigs_alt = nullptr;       // chain descriptors pointing into the other set (the spare of the two descriptor arrays)
-    DevContig* d_contigs_owned = nullptr;     // the descriptor array that is not part of the arena (to free)
-    std::vector<DevContig> h_contigs;         // host copy of the descriptors of the set in use
-    unsigned char* cur_samples = nullptr;     // base of the set in use (arena + sample_lo, or alt_samples)
-    hipStream_t copy_stream = nullptr;
-    std::thread uploader;                     // pg_job_upload_begin's worker
-    bool upload_pending = false;
-    int upload_rc = PG_OK;
-    std::string upload_err;
-    std::vector<std::vector<uint16_t>> next_coverage;   // host copies of the pending batch's coverage arrays
-    hipEvent_t ev_fill = nullptr;             // orders a count plan's stream against the job's (pgi_job_fill_begin / _end; made by the first fill)
-    // Calls (pg_job_calls, pg_calls.hip): one 8-byte record per variant, chain after chain.  NOT part of the arena: made by
-    // the first pg_job_calls (a job whose user fetches bins never pays for it), freed in pg_job_destroy.
-    unsigned char* d_calls = nullptr;         // the records, then the chain descriptors, then k_calls_wide's list
-    std::vector<uint64_t> calls_first;        // [n_chains + 1] first record of every chain
-    std::vector<CallsDesc> calls_desc;        // host copy of the descriptors (chains with variants)
-    uint32_t calls_blocks = 0, calls_wide = 0;
-    size_t o_calls_desc = 0, o_calls_wide = 0;
-    hipEvent_t ev_calls[2];
-    bool calls_events = false;
-    double calls_ms = 0.0;
-    // Record calls (pg_job_record_plan / pg_job_record_calls): one plan per index contig, shared by every chain over it, and one
-    // 8-byte record per VCF record of every chain whose index contig has a plan.  Outside the arena like the calls.
-    std::vector<RecordPlanRef> rplans;        // [n_index] (sized by the first pg_job_record_plan[_strided]); null: no plan
-    bool rcalls_dirty = true;                 // a plan or the index changed: descriptors, lists and the id check are redone
-    bool rplan_ids_ok = false;                // k_rplan_ids has passed the plans and the index as they are
-    unsigned char* d_rcalls = nullptr;        // the records, the chain descriptors, k_rcalls_wide's list, its staging slots
-    std::vector<uint64_t> rcalls_first;       // [n_chains + 1] first record of every chain (a chain without a plan has none)
-    std::vector<RCallsDesc> rcalls_desc;
-    uint32_t rcalls_blocks = 0, rcalls_wide = 0, rcalls_max_bins = 0, rcalls_stride = 0, rcalls_slots = 0;
-    size_t o_rcalls_desc = 0, o_rcalls_wide = 0, o_rcalls_stage = 0;
-    bool rcalls_formed = false;
-    double rcalls_ms = 0.0;
-    // Record GLs (pg_job_record_gl): 4 bytes per genotype of every record's defined alleles, chain after chain, under the same
-    // plans.  A buffer of its own outside the arena, made by the first pg_job_record_gl.
-    bool rgl_dirty = true;
-    unsigned char* d_rgl = nullptr;           // the values, the plans' offsets, the chain descriptors, k_rgl_wide's list, its staging slots
-    std::vector<uint64_t> rgl_first;          // [n_chains + 1] first VALUE of every chain
-    std::vector<RGlDesc> rgl_desc;
-    uint32_t rgl_blocks = 0, rgl_wide = 0, rgl_max_bins = 0, rgl_stride = 0, rgl_slots = 0;
-    size_t o_rgl_desc = 0, o_rgl_wide = 0, o_rgl_stage = 0;
-    bool rgl_formed = false;
-    double rgl_ms = 0.0;
-};
 
 extern "C" void pg_job_destroy(pg_job* job) {
     if (!job) return;
@@ -573,9 +337,9 @@ extern "C" void pg_job_destroy(pg_job* job) {
     if (job->d_contigs_owned) hipFree(job->d_contigs_owned);
     if (job->stream) hipStreamSynchronize(job->stream);
     if (job->stream2) hipStreamSynchronize(job->stream2);
-    if (job->d_calls) hipFree(job->d_calls);
-    if (job->d_rcalls) hipFree(job->d_rcalls);
-    if (job->d_rgl) hipFree(job->d_rgl);
+    job->calls.release();
+    job->rcalls.release();
+    job->rgl.release();
     job->rplans.clear();
     if (job->events) {
         for (auto& e : job->ev) hipEventDestroy(e);
@@ -710,9 +474,7 @@ int upload_inputs(pg_job* job, const pg_contig_batch* batches, const std::vector
         }                                                                                                     \
     } while (0)
     if (with_index) {
-        job->rcalls_dirty = true;
-        job->rgl_dirty = true;   // (new allele ids: the record plans are checked against them again)
-        job->rplan_ids_ok = false;
+        record_plans_changed(job);   // (new allele ids: the record plans are checked against them again)
         for (size_t i = 0; i < job->index.size(); ++i) {
             const pg_contig_batch& b = batches[i];
             IndexHost& x = job->index[i];
@@ -2801,912 +2563,4 @@ extern "C" int pg_transition_probs(uint64_t from_pos, uint64_t to_pos, double re
     hipFree(d);
     if (he != hipSuccess) { set_err(err, errlen, "transition kernel failed: %s", hipGetErrorString(he)); return PG_ERR_DEVICE; }
     return PG_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-//  Genotype calls on the device (pg_calls.hip): GT and GQ per variant as 8-byte records.
-// ---------------------------------------------------------------------------------------
-namespace {
-
-static_assert(sizeof(pg_call) == 8, "pg_call is the 8-byte record k_calls stores");
-static_assert(PG_CALL_OK == PGX_CALL_OK && PG_CALL_NONE == PGX_CALL_NONE && PG_CALL_NOT_UNIQUE == PGX_CALL_NOT_UNIQUE &&
-              PG_CALL_DEFERRED == PGX_CALL_DEFERRED, "the flags of the public header are the kernels' flags");
-
-// The genotype-quality thresholds, built once from log10l itself (pg_calls.h) and uploaded once per device.
-struct GqTables {
-    std::mutex mu;
-    bool built = false, bad = false;
-    uint64_t m[PG_GQ_STEPS];
-    int32_t e[PG_GQ_STEPS];
-    unsigned char* dev[PG_MAX_DEVICES_HOST] = {nullptr};
-} g_gq;
-
-// (the caller has made `device` current)
-int gq_table_on(int device, const uint64_t** d_m, const int32_t** d_e, char* err, size_t errlen) {
-    if (device < 0 || device >= PG_MAX_DEVICES_HOST) { set_err(err, errlen, "device %d out of range", device); return PG_ERR_INVALID; }
-    std::lock_guard<std::mutex> lock(g_gq.mu);
-    if (!g_gq.built) {
-        g_gq.bad = pgx_build_gq_table(g_gq.m, g_gq.e) != 0;
-        g_gq.built = true;
-    }
-    if (g_gq.bad) { set_err(err, errlen, "the genotype-quality table could not be built: log10l is not monotone at a threshold"); return PG_ERR_INVALID; }
-    constexpr size_t off_e = PG_GQ_STEPS * sizeof(uint64_t);
-    if (!g_gq.dev[device]) {
-        unsigned char* d = nullptr;
-        if (hipMalloc((void**)&d, off_e + PG_GQ_STEPS * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of the GQ table failed"); return PG_ERR_NOMEM; }
-        if (hipMemcpy(d, g_gq.m, off_e, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d + off_e, g_gq.e, PG_GQ_STEPS * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
-            hipFree(d);
-            set_err(err, errlen, "upload of the GQ table failed");
-            return PG_ERR_DEVICE;
-        }
-        g_gq.dev[device] = d;
-    }
-    *d_m = (const uint64_t*)g_gq.dev[device];
-    *d_e = (const int32_t*)(g_gq.dev[device] + off_e);
-    return PG_OK;
-}
-
-// descriptors and the list of wide variants of a set of chains: aoff(c) = allele_off of chain c (V + 1 entries), on the host
-template <class AoffOf>
-void plan_calls(uint32_t n_chains, const std::vector<uint32_t>& Vs, AoffOf aoff, std::vector<uint64_t>* first, std::vector<CallsDesc>* desc,
-                std::vector<uint32_t>* wide, uint32_t* n_blocks) {
-    const uint32_t per = pgk_calls_block();
-    first->assign((size_t)n_chains + 1, 0);
-    desc->clear();
-    wide->clear();
-    uint32_t blk = 0;
-    for (uint32_t c = 0; c < n_chains; ++c) {
-        const uint32_t V = Vs[c];
-        (*first)[c + 1] = (*first)[c] + V;
-        if (V == 0) continue;
-        CallsDesc d;
-        memset(&d, 0, sizeof(d));
-        d.blk0 = blk; d.V = V; d.chain = c;
-        const uint32_t* off = aoff(c);
-        for (uint32_t v = 0; v < V; ++v)
-            if (off[v + 1] - off[v] > PG_AMAX) { wide->push_back((uint32_t)desc->size()); wide->push_back(v); }
-        desc->push_back(d);
-        blk += (V + per - 1) / per;
-    }
-    *n_blocks = blk;
-}
-
-}  // namespace
-
-extern "C" int pg_job_calls(pg_job* job, char* err, size_t errlen) {
-    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
-    if (!job->params.run_genotyping) { set_err(err, errlen, "the job does not run the genotyping: it has no bins to call from"); return PG_ERR_INVALID; }
-    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(job->device));
-    const uint32_t n = (uint32_t)job->chains.size();
-    const uint64_t* d_tm = nullptr;
-    const int32_t* d_te = nullptr;
-    int rc = gq_table_on(job->device, &d_tm, &d_te, err, errlen);
-    if (rc != PG_OK) return rc;
-    if (!job->calls_events) {
-        HIP_TRY(hipEventCreate(&job->ev_calls[0]));
-        HIP_TRY(hipEventCreate(&job->ev_calls[1]));
-        job->calls_events = true;
-    }
-    if (!job->d_calls) {   // the shapes of a job never change: planned once
-        std::vector<uint32_t> Vs(n), wide;
-        for (uint32_t c = 0; c < n; ++c) Vs[c] = job->index[job->chains[c].index].V;
-        plan_calls(n, Vs, [&](uint32_t c) { return job->index[job->chains[c].index].aoff.data(); }, &job->calls_first, &job->calls_desc, &wide,
-                   &job->calls_blocks);
-        job->calls_wide = (uint32_t)(wide.size() / 2);
-        const size_t rec_bytes = align_up((size_t)job->calls_first[n] * sizeof(pg_call) + 8);
-        job->o_calls_desc = rec_bytes;
-        job->o_calls_wide = job->o_calls_desc + align_up(job->calls_desc.size() * sizeof(CallsDesc) + 8);
-        const size_t total = job->o_calls_wide + align_up(wide.size() * sizeof(uint32_t) + 8);
-        unsigned char* d = nullptr;
-        if (hipMalloc((void**)&d, total) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the calls failed", total); return PG_ERR_NOMEM; }
-        for (CallsDesc& cd : job->calls_desc) cd.out = d + job->calls_first[cd.chain] * sizeof(pg_call);
-        hipError_t he = hipSuccess;
-        if (!job->calls_desc.empty()) he = hipMemcpy(d + job->o_calls_desc, job->calls_desc.data(), job->calls_desc.size() * sizeof(CallsDesc), hipMemcpyHostToDevice);
-        if (he == hipSuccess && !wide.empty()) he = hipMemcpy(d + job->o_calls_wide, wide.data(), wide.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-        if (he != hipSuccess) { hipFree(d); set_err(err, errlen, "upload of the calls plan failed: %s", hipGetErrorString(he)); return PG_ERR_DEVICE; }
-        job->d_calls = d;
-    }
-    hipStream_t s = job->stream;
-    HIP_TRY(hipEventRecord(job->ev_calls[0], s));
-    pgk_launch_calls(job->d_contigs, (const CallsDesc*)(job->d_calls + job->o_calls_desc), (uint32_t)job->calls_desc.size(), job->calls_blocks,
-                     job->d_calls + job->o_calls_wide, job->calls_wide, d_tm, d_te, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(job->ev_calls[1], s));
-    HIP_TRY(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, job->ev_calls[0], job->ev_calls[1]));
-    job->calls_ms = ms;
-    return PG_OK;
-}
-
-namespace {
-int calls_ready(pg_job* job, char* err, size_t errlen) {
-    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
-    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
-    if (!job->d_calls) { set_err(err, errlen, "pg_job_calls has not been called"); return PG_ERR_INVALID; }
-    return PG_OK;
-}
-}  // namespace
-
-extern "C" int pg_job_fetch_calls(pg_job* job, uint32_t ci, pg_call* out, char* err, size_t errlen) {
-    int rc = calls_ready(job, err, errlen);
-    if (rc != PG_OK) return rc;
-    if (ci >= job->chains.size() || !out) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(job->device));
-    const uint64_t V = job->calls_first[ci + 1] - job->calls_first[ci];
-    if (V) HIP_TRY(hipMemcpy(out, job->d_calls + job->calls_first[ci] * sizeof(pg_call), V * sizeof(pg_call), hipMemcpyDeviceToHost));
-    return PG_OK;
-}
-
-extern "C" int pg_job_fetch_calls_all(pg_job* job, pg_call* const* outs, char* err, size_t errlen) {
-    int rc = calls_ready(job, err, errlen);
-    if (rc != PG_OK) return rc;
-    if (!outs) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(job->device));
-    for (size_t ci = 0; ci < job->chains.size(); ++ci) {
-        const uint64_t V = job->calls_first[ci + 1] - job->calls_first[ci];
-        if (V == 0) continue;
-        if (!outs[ci]) { set_err(err, errlen, "no buffer for chain %zu", ci); return PG_ERR_INVALID; }
-        HIP_TRY(hipMemcpyAsync(outs[ci], job->d_calls + job->calls_first[ci] * sizeof(pg_call), V * sizeof(pg_call), hipMemcpyDeviceToHost, job->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(job->stream));
-    return PG_OK;
-}
-
-extern "C" int pg_job_device_calls(pg_job* job, uint32_t ci, void** d_calls, uint64_t* n) {
-    if (!job || ci >= job->chains.size() || !job->d_calls) return PG_ERR_INVALID;
-    if (d_calls) *d_calls = job->d_calls + job->calls_first[ci] * sizeof(pg_call);
-    if (n) *n = job->calls_first[ci + 1] - job->calls_first[ci];
-    return PG_OK;
-}
-
-extern "C" double pg_job_calls_ms(const pg_job* job) { return job ? job->calls_ms : 0.0; }
-
-// The unit entry point: host arrays in, records out, through the same two kernels.
-extern "C" int pg_calls_from_bins(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id, const uint8_t* kept,
-                                  const uint8_t* allele_present, const double* lik, const int32_t* lik_exp, pg_call* out) {
-    const uint32_t V = n_variants;
-    if (V == 0) return PG_OK;
-    if (!allele_off || !allele_id || !kept || !allele_present || !out || allele_off[0] != 0) return PG_ERR_INVALID;
-    std::vector<uint64_t> goff((size_t)V + 1, 0);
-    for (uint32_t v = 0; v < V; ++v) {
-        if (allele_off[v + 1] <= allele_off[v] || allele_off[v + 1] - allele_off[v] > PG_MAX_ALLELES_PER_VARIANT) return PG_ERR_INVALID;
-        const uint64_t A = allele_off[v + 1] - allele_off[v];
-        goff[v + 1] = goff[v] + A * (A + 1) / 2;
-    }
-    const uint64_t n_lik = goff[V], sumA = allele_off[V];
-    if (n_lik && (!lik || !lik_exp)) return PG_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); return PG_ERR_DEVICE; }
-    if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return PG_ERR_DEVICE;
-    const uint64_t* d_tm = nullptr;
-    const int32_t* d_te = nullptr;
-    int rc = gq_table_on(device, &d_tm, &d_te, nullptr, 0);
-    if (rc != PG_OK) return rc;
-    std::vector<uint64_t> first;
-    std::vector<CallsDesc> desc;
-    std::vector<uint32_t> wide, Vs(1, V);
-    uint32_t n_blocks = 0;
-    plan_calls(1, Vs, [&](uint32_t) { return allele_off; }, &first, &desc, &wide, &n_blocks);
-    // one device buffer: every array at a 256-byte boundary
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += align_up(bytes + 8); return at; };
-    const size_t o_contig = take(sizeof(DevContig)), o_desc = take(sizeof(CallsDesc)), o_wide = take(wide.size() * 4), o_aoff = take(((size_t)V + 1) * 4),
-                 o_aid = take(sumA * 2), o_kept = take(V), o_pres = take(sumA), o_goff = take(((size_t)V + 1) * 8), o_lik = take(n_lik * 8),
-                 o_exp = take(n_lik * 4), o_out = take((size_t)V * sizeof(pg_call));
-    unsigned char* d = nullptr;
-    if (hipMalloc((void**)&d, o) != hipSuccess) { (void)hipGetLastError(); return PG_ERR_NOMEM; }
-    DevContig dc;
-    memset(&dc, 0, sizeof(dc));
-    dc.V = V;
-    dc.allele_off = (const uint32_t*)(d + o_aoff);
-    dc.allele_id = (const uint16_t*)(d + o_aid);
-    dc.kept = d + o_kept;
-    dc.allele_present = d + o_pres;
-    dc.geno_off = (const uint64_t*)(d + o_goff);
-    dc.lik = (double*)(d + o_lik);
-    dc.lik_exp = (int32_t*)(d + o_exp);
-    desc[0].out = d + o_out;
-    bool ok = hipMemcpy(d + o_contig, &dc, sizeof(dc), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d + o_desc, desc.data(), sizeof(CallsDesc), hipMemcpyHostToDevice) == hipSuccess &&
-              (wide.empty() || hipMemcpy(d + o_wide, wide.data(), wide.size() * 4, hipMemcpyHostToDevice) == hipSuccess) &&
-              hipMemcpy(d + o_aoff, allele_off, ((size_t)V + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d + o_aid, allele_id, sumA * 2, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d + o_kept, kept, V, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d + o_pres, allele_present, sumA, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d + o_goff, goff.data(), ((size_t)V + 1) * 8, hipMemcpyHostToDevice) == hipSuccess &&
-              (n_lik == 0 || (hipMemcpy(d + o_lik, lik, n_lik * 8, hipMemcpyHostToDevice) == hipSuccess &&
-                              hipMemcpy(d + o_exp, lik_exp, n_lik * 4, hipMemcpyHostToDevice) == hipSuccess));
-    if (ok) {
-        pgk_launch_calls((const DevContig*)(d + o_contig), (const CallsDesc*)(d + o_desc), 1, n_blocks, d + o_wide, (uint32_t)(wide.size() / 2), d_tm, d_te, nullptr);
-        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
-             hipMemcpy(out, d + o_out, (size_t)V * sizeof(pg_call), hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    hipFree(d);
-    return ok ? PG_OK : PG_ERR_DEVICE;
-}
-
-// ---------------------------------------------------------------------------------------
-//  Genotype calls per VCF record (pg_calls.hip: k_rcalls / k_rcalls_wide, DESIGN.md 4e "Records").
-// ---------------------------------------------------------------------------------------
-namespace {
-
-static_assert(PG_CALL_EMPTY == PGX_CALL_EMPTY, "the flag of the public header is the kernels' flag");
-
-// The checks that need the plan alone (everything but the allele ids), and the host copy the job keeps.
-int check_record_plan(const pg_record_plan* p, uint32_t V, RecordPlanHost* h, char* err, size_t errlen) {
-    if (!p) { set_err(err, errlen, "null record plan"); return PG_ERR_INVALID; }
-    if (p->n_variants != V) { set_err(err, errlen, "the record plan has %u variants, the index contig %u", p->n_variants, V); return PG_ERR_INVALID; }
-    RecordPlanHost r;
-    r.set = true;
-    r.V = V;
-    if (V == 0) {
-        if (p->n_records != 0) { set_err(err, errlen, "records without variants"); return PG_ERR_INVALID; }
-        *h = std::move(r);
-        return PG_OK;
-    }
-    if (!p->rec_off || !p->map_off || !p->map || !p->n_alleles || !p->vcf_off || !p->vcf_index) { set_err(err, errlen, "the record plan has null arrays"); return PG_ERR_INVALID; }
-    if (p->rec_off[0] != 0 || p->map_off[0] != 0 || p->vcf_off[0] != 0) { set_err(err, errlen, "the record plan's offset arrays must start at 0"); return PG_ERR_INVALID; }
-    for (uint32_t v = 0; v < V; ++v)
-        if (p->rec_off[v + 1] <= p->rec_off[v]) { set_err(err, errlen, "rec_off does not grow at variant %u: every bubble has at least one record", v); return PG_ERR_INVALID; }
-    const uint32_t R = p->rec_off[V];
-    if (R != p->n_records || R >= 0x80000000u) { set_err(err, errlen, "n_records is %u, rec_off ends at %u", p->n_records, R); return PG_ERR_INVALID; }
-    for (uint32_t q = 0; q < R; ++q) {
-        if (p->map_off[q + 1] < p->map_off[q] || p->vcf_off[q + 1] < p->vcf_off[q]) { set_err(err, errlen, "map_off / vcf_off shrink at record %u", q); return PG_ERR_INVALID; }
-        const uint32_t nA = p->n_alleles[q];
-        if (nA == 0 || p->vcf_off[q + 1] - p->vcf_off[q] != nA) { set_err(err, errlen, "record %u: n_alleles is %u, vcf_off gives %u", q, nA, p->vcf_off[q + 1] - p->vcf_off[q]); return PG_ERR_INVALID; }
-        if (nA > PG_MAX_ALLELES_PER_VARIANT) { set_err(err, errlen, "record %u has %u alleles: more than %d", q, nA, PG_MAX_ALLELES_PER_VARIANT); return PG_ERR_UNSUPPORTED; }
-        for (uint32_t i = p->map_off[q]; i < p->map_off[q + 1]; ++i)
-            if (p->map[i] >= nA) { set_err(err, errlen, "record %u: map entry %u is allele %u of %u", q, i - p->map_off[q], p->map[i], nA); return PG_ERR_INVALID; }
-        uint16_t defined = 0;
-        for (uint32_t a = 0; a < nA; ++a) {
-            const uint16_t x = p->vcf_index[p->vcf_off[q] + a];
-            if (x == 0xFFFFu && a > 0) continue;
-            if (x != defined) { set_err(err, errlen, "record %u: vcf_index of allele %u is %u, not the running count of defined alleles %u", q, a, x, defined); return PG_ERR_INVALID; }
-            ++defined;
-        }
-    }
-    r.R = R;
-    r.rec_off.assign(p->rec_off, p->rec_off + V + 1);
-    r.map_off.assign(p->map_off, p->map_off + R + 1);
-    r.vcf_off.assign(p->vcf_off, p->vcf_off + R + 1);
-    r.map.assign(p->map, p->map + p->map_off[R]);
-    r.vcf_index.assign(p->vcf_index, p->vcf_index + p->vcf_off[R]);
-    r.rec_var.resize(R);
-    for (uint32_t v = 0; v < V; ++v)
-        for (uint32_t q = r.rec_off[v]; q < r.rec_off[v + 1]; ++q) {
-            bool undef = false;
-            for (uint32_t i = r.vcf_off[q]; i < r.vcf_off[q + 1]; ++i) undef = undef || r.vcf_index[i] == 0xFFFFu;
-            r.rec_var[q] = v | (undef ? 0x80000000u : 0u);
-        }
-    *h = std::move(r);
-    return PG_OK;
-}
-
-// every allele id of the contig's bubbles has an entry in the map of each of the bubble's records
-int check_record_plan_ids(const RecordPlanHost& h, const uint32_t* allele_off, const uint16_t* allele_id, char* err, size_t errlen) {
-    for (uint32_t v = 0; v < h.V; ++v)
-        for (uint32_t q = h.rec_off[v]; q < h.rec_off[v + 1]; ++q) {
-            const uint32_t len = h.map_off[q + 1] - h.map_off[q];
-            for (uint32_t a = allele_off[v]; a < allele_off[v + 1]; ++a)
-                if (allele_id[a] >= len) { set_err(err, errlen, "variant %u: allele id %u lies outside the map of record %u (%u entries)", v, allele_id[a], q, len); return PG_ERR_INVALID; }
-        }
-    return PG_OK;
-}
-
-size_t record_plan_device_bytes(const RecordPlanHost& h) {
-    return align_up((size_t)h.R * 4 + 8) + 2 * align_up(((size_t)h.R + 1) * 4 + 8) + align_up(h.map.size() * 2 + 8) + align_up(h.vcf_index.size() * 2 + 8);
-}
-// copies the plan's arrays to d (record_plan_device_bytes of room) and points *dev at them
-bool record_plan_upload(const RecordPlanHost& h, unsigned char* d, RecPlanDev* dev) {
-    size_t o = 0;
-    auto put = [&](const void* src, size_t bytes) -> const void* {
-        unsigned char* at = d + o;
-        o += align_up(bytes + 8);
-        return (bytes == 0 || hipMemcpy(at, src, bytes, hipMemcpyHostToDevice) == hipSuccess) ? at : nullptr;
-    };
-    dev->rec_var = (const uint32_t*)put(h.rec_var.data(), (size_t)h.R * 4);
-    dev->map_off = (const uint32_t*)put(h.map_off.data(), ((size_t)h.R + 1) * 4);
-    dev->vcf_off = (const uint32_t*)put(h.vcf_off.data(), ((size_t)h.R + 1) * 4);
-    dev->map = (const uint16_t*)put(h.map.data(), h.map.size() * 2);
-    dev->vcf_index = (const uint16_t*)put(h.vcf_index.data(), h.vcf_index.size() * 2);
-    return dev->rec_var && dev->map_off && dev->vcf_off && dev->map && dev->vcf_index;
-}
-
-// The wave-per-record kernel stages a bubble's quotients and a record's folded map in device memory: one slot of `stride`
-// 16-byte values per block, at most 1024 blocks and 256 MB (a 256-allele bubble: 32 896 bins and as many keys, 1 MB a slot).
-struct RcallsLaunch {
-    std::vector<uint64_t> first;
-    std::vector<RCallsDesc> desc;
-    std::vector<uint32_t> wide;   // {descriptor, record} pairs
-    uint32_t n_blocks = 0, max_bins = 0, stride = 0, n_slots = 0;
-};
-// planOf(c): the plan of chain c's index contig or nullptr; aoff(c): the chain's allele_off
-template <class PlanOf, class AoffOf>
-void plan_rcalls(uint32_t n_chains, PlanOf planOf, AoffOf aoff, RcallsLaunch* L) {
-    const uint32_t per = pgk_calls_block();
-    L->first.assign((size_t)n_chains + 1, 0);
-    L->desc.clear();
-    L->wide.clear();
-    uint32_t blk = 0;
-    uint64_t max_bins = 0, max_keys = 0;
-    for (uint32_t c = 0; c < n_chains; ++c) {
-        const RecordPlanHost* h = planOf(c);
-        const uint32_t R = h ? h->R : 0;
-        L->first[c + 1] = L->first[c] + R;
-        if (R == 0) continue;
-        RCallsDesc d;
-        memset(&d, 0, sizeof(d));
-        d.blk0 = blk; d.R = R; d.chain = c;
-        d.plan = h->dev;
-        const uint32_t* off = aoff(c);
-        for (uint32_t v = 0; v < h->V; ++v) {
-            const uint64_t A = off[v + 1] - off[v];
-            if (A <= PG_AMAX) continue;
-            for (uint32_t q = h->rec_off[v]; q < h->rec_off[v + 1]; ++q) {
-                const uint64_t nA = h->vcf_off[q + 1] - h->vcf_off[q];
-                L->wide.push_back((uint32_t)L->desc.size());
-                L->wide.push_back(q);
-                max_bins = std::max(max_bins, A * (A + 1) / 2);
-                max_keys = std::max(max_keys, nA * (nA + 1) / 2);
-            }
-        }
-        L->desc.push_back(d);
-        blk += (R + per - 1) / per;
-    }
-    L->n_blocks = blk;
-    L->max_bins = (uint32_t)max_bins;
-    L->stride = (uint32_t)(max_bins + max_keys);
-    const uint64_t n_wide = L->wide.size() / 2;
-    L->n_slots = n_wide ? (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n_wide, 1024), std::max<uint64_t>(1, ((uint64_t)256 << 20) / ((uint64_t)L->stride * 16))) : 0;
-}
-
-int rcalls_ready(pg_job* job, char* err, size_t errlen) {
-    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
-    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
-    if (!job->rcalls_formed || job->rcalls_dirty) { set_err(err, errlen, "pg_job_record_calls has not been called"); return PG_ERR_INVALID; }
-    return PG_OK;
-}
-
-// the plan of chain c's index contig, or nullptr
-const RecordPlanHost* plan_of_chain(const pg_job* job, uint32_t c) {
-    const uint32_t ix = job->chains[c].index;
-    return ix < job->rplans.size() ? job->rplans[ix].get() : nullptr;
-}
-
-// the checked plan on the job's device, ready to be referred to by index contigs
-int record_plan_to_device(pg_job* job, RecordPlanHost&& h, RecordPlanRef* ref, char* err, size_t errlen) {
-    HIP_TRY(hipSetDevice(job->device));
-    if (h.R) {
-        const size_t bytes = record_plan_device_bytes(h);
-        if (hipMalloc((void**)&h.d, bytes) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the record plan failed", bytes); return PG_ERR_NOMEM; }
-        if (!record_plan_upload(h, h.d, &h.dev)) { hipFree(h.d); set_err(err, errlen, "upload of the record plan failed"); return PG_ERR_DEVICE; }
-    }
-    *ref = record_plan_ref(std::move(h));
-    if (job->rplans.size() != job->index.size()) job->rplans.resize(job->index.size());
-    if (job->stream) HIP_TRY(hipStreamSynchronize(job->stream));   // (nothing reads the plans this one replaces any more)
-    return PG_OK;
-}
-
-void record_plans_changed(pg_job* job) {
-    job->rcalls_dirty = true;
-    job->rgl_dirty = true;
-    job->rplan_ids_ok = false;
-}
-
-// The id check on the device (k_rplan_ids): every allele id of every chain that has a plan, against the maps of its bubble's
-// records.  `d_desc` = the RCallsDesc list of plan_rcalls on the device, `d_hit` = 8 bytes next to it.  On a hit the ids of
-// that one chain come to the host and check_record_plan_ids forms the message.
-int check_record_plan_ids_on_device(pg_job* job, const RCallsDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, unsigned char* d_hit, char* err,
-                                    size_t errlen) {
-    if (job->rplan_ids_ok || n_desc == 0 || n_blocks == 0) { job->rplan_ids_ok = true; return PG_OK; }
-    hipStream_t s = job->stream;
-    uint64_t hit = ~(uint64_t)0;
-    HIP_TRY(hipMemcpyAsync(d_hit, &hit, sizeof(hit), hipMemcpyHostToDevice, s));
-    pgk_launch_rplan_ids(job->d_contigs, d_desc, n_desc, n_blocks, d_hit, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&hit, d_hit, sizeof(hit), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (hit == ~(uint64_t)0) { job->rplan_ids_ok = true; return PG_OK; }
-    const uint32_t chain = (uint32_t)(hit >> 32);
-    if (chain >= job->chains.size() || !plan_of_chain(job, chain)) { set_err(err, errlen, "the id check of the record plans answered chain %u", chain); return PG_ERR_DEVICE; }
-    const IndexHost& x = job->index[job->chains[chain].index];
-    std::vector<uint16_t> aid(x.sumA);
-    HIP_TRY(hipMemcpy(aid.data(), job->arena + x.o_aid, (size_t)x.sumA * 2, hipMemcpyDeviceToHost));
-    char text[256] = {0};
-    const int rc = check_record_plan_ids(*plan_of_chain(job, chain), x.aoff.data(), aid.data(), text, sizeof(text));
-    if (rc == PG_OK) { set_err(err, errlen, "chain %u, variant %u: an allele id lies outside a record's map", chain, (uint32_t)hit); return PG_ERR_INVALID; }
-    set_err(err, errlen, "%s, in chain %u", text, chain);
-    return rc;
-}
-
-}  // namespace
-
-extern "C" int pg_job_record_plan(pg_job* job, uint32_t ix, const pg_record_plan* plan, char* err, size_t errlen) {
-    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
-    if (ix >= job->index.size()) { set_err(err, errlen, "index contig %u of %zu", ix, job->index.size()); return PG_ERR_INVALID; }
-    RecordPlanHost h;
-    int rc = check_record_plan(plan, job->index[ix].V, &h, err, errlen);
-    if (rc != PG_OK) return rc;
-    RecordPlanRef ref;
-    rc = record_plan_to_device(job, std::move(h), &ref, err, errlen);
-    if (rc != PG_OK) return rc;
-    job->rplans[ix] = std::move(ref);   // (this index contig's reference alone: the members of a stride keep theirs)
-    record_plans_changed(job);
-    return PG_OK;
-}
-
-extern "C" int pg_job_record_plan_strided(pg_job* job, uint32_t contig, uint32_t n_contigs, const pg_record_plan* plan, char* err, size_t errlen) {
-    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
-    if (n_contigs == 0 || contig >= n_contigs) { set_err(err, errlen, "contig %u of %u", contig, n_contigs); return PG_ERR_INVALID; }
-    if (job->index.size() % n_contigs != 0) { set_err(err, errlen, "the job's %zu index contigs are no multiple of %u contigs", job->index.size(), n_contigs); return PG_ERR_INVALID; }
-    if (!plan) { set_err(err, errlen, "null record plan"); return PG_ERR_INVALID; }
-    for (size_t ix = contig; ix < job->index.size(); ix += n_contigs)
-        if (job->index[ix].V != plan->n_variants) {
-            set_err(err, errlen, "the record plan has %u variants, index contig %zu (member %zu of the stride) %u", plan->n_variants, ix, ix / n_contigs, job->index[ix].V);
-            return PG_ERR_INVALID;
-        }
-    RecordPlanHost h;
-    int rc = check_record_plan(plan, plan->n_variants, &h, err, errlen);
-    if (rc != PG_OK) return rc;
-    if (contig >= job->index.size()) return PG_OK;   // (a job without index contigs: no member)
-    RecordPlanRef ref;
-    rc = record_plan_to_device(job, std::move(h), &ref, err, errlen);
-    if (rc != PG_OK) return rc;
-    for (size_t ix = contig; ix < job->index.size(); ix += n_contigs) job->rplans[ix] = ref;
-    record_plans_changed(job);
-    return PG_OK;
-}
-
-extern "C" int pg_job_record_calls(pg_job* job, char* err, size_t errlen) {
-    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
-    if (!job->params.run_genotyping) { set_err(err, errlen, "the job does not run the genotyping: it has no bins to call from"); return PG_ERR_INVALID; }
-    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(job->device));
-    const uint32_t n = (uint32_t)job->chains.size();
-    const uint64_t* d_tm = nullptr;
-    const int32_t* d_te = nullptr;
-    int rc = gq_table_on(job->device, &d_tm, &d_te, err, errlen);
-    if (rc != PG_OK) return rc;
-    if (!job->calls_events) {
-        HIP_TRY(hipEventCreate(&job->ev_calls[0]));
-        HIP_TRY(hipEventCreate(&job->ev_calls[1]));
-        job->calls_events = true;
-    }
-    if (job->rcalls_dirty) {   // a plan or the index has changed: the descriptors and lists are made anew, the ids checked on the device
-        RcallsLaunch L;
-        plan_rcalls(n, [&](uint32_t c) { return plan_of_chain(job, c); }, [&](uint32_t c) { return job->index[job->chains[c].index].aoff.data(); }, &L);
-        const size_t o_desc = align_up((size_t)L.first[n] * sizeof(pg_call) + 8);
-        const size_t o_wide = o_desc + align_up(L.desc.size() * sizeof(RCallsDesc) + 8);
-        const size_t o_stage = o_wide + align_up(L.wide.size() * sizeof(uint32_t) + 8);
-        const size_t o_hit = o_stage + align_up((size_t)L.n_slots * L.stride * 16 + 8);
-        const size_t total = o_hit + align_up(8);
-        unsigned char* d = nullptr;
-        if (hipMalloc((void**)&d, total) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the record calls failed", total); return PG_ERR_NOMEM; }
-        for (RCallsDesc& cd : L.desc) cd.out = d + L.first[cd.chain] * sizeof(pg_call);
-        hipError_t he = hipSuccess;
-        if (!L.desc.empty()) he = hipMemcpy(d + o_desc, L.desc.data(), L.desc.size() * sizeof(RCallsDesc), hipMemcpyHostToDevice);
-        if (he == hipSuccess && !L.wide.empty()) he = hipMemcpy(d + o_wide, L.wide.data(), L.wide.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-        if (he != hipSuccess) { hipFree(d); set_err(err, errlen, "upload of the record calls' lists failed: %s", hipGetErrorString(he)); return PG_ERR_DEVICE; }
-        rc = check_record_plan_ids_on_device(job, (const RCallsDesc*)(d + o_desc), (uint32_t)L.desc.size(), L.n_blocks, d + o_hit, err, errlen);
-        if (rc != PG_OK) { hipFree(d); return rc; }
-        if (job->d_rcalls) hipFree(job->d_rcalls);
-        job->d_rcalls = d;
-        job->rcalls_first = std::move(L.first);
-        job->rcalls_desc = std::move(L.desc);
-        job->rcalls_blocks = L.n_blocks; job->rcalls_wide = (uint32_t)(L.wide.size() / 2);
-        job->rcalls_max_bins = L.max_bins; job->rcalls_stride = L.stride; job->rcalls_slots = L.n_slots;
-        job->o_rcalls_desc = o_desc; job->o_rcalls_wide = o_wide; job->o_rcalls_stage = o_stage;
-        job->rcalls_dirty = false;
-        job->rcalls_formed = false;
-    }
-    hipStream_t s = job->stream;
-    HIP_TRY(hipEventRecord(job->ev_calls[0], s));
-    pgk_launch_rcalls(job->d_contigs, (const RCallsDesc*)(job->d_rcalls + job->o_rcalls_desc), (uint32_t)job->rcalls_desc.size(), job->rcalls_blocks,
-                      job->d_rcalls + job->o_rcalls_wide, job->rcalls_wide, job->d_rcalls + job->o_rcalls_stage, job->rcalls_max_bins, job->rcalls_stride,
-                      job->rcalls_slots, d_tm, d_te, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(job->ev_calls[1], s));
-    HIP_TRY(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, job->ev_calls[0], job->ev_calls[1]));
-    job->rcalls_ms = ms;
-    job->rcalls_formed = true;
-    return PG_OK;
-}
-
-extern "C" int pg_job_fetch_record_calls(pg_job* job, uint32_t ci, pg_call* out, char* err, size_t errlen) {
-    int rc = rcalls_ready(job, err, errlen);
-    if (rc != PG_OK) return rc;
-    if (ci >= job->chains.size()) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
-    const uint64_t R = job->rcalls_first[ci + 1] - job->rcalls_first[ci];
-    if (R == 0) return PG_OK;
-    if (!out) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(job->device));
-    HIP_TRY(hipMemcpy(out, job->d_rcalls + job->rcalls_first[ci] * sizeof(pg_call), R * sizeof(pg_call), hipMemcpyDeviceToHost));
-    return PG_OK;
-}
-
-extern "C" int pg_job_fetch_record_calls_all(pg_job* job, pg_call* const* outs, char* err, size_t errlen) {
-    int rc = rcalls_ready(job, err, errlen);
-    if (rc != PG_OK) return rc;
-    if (!outs) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(job->device));
-    for (size_t ci = 0; ci < job->chains.size(); ++ci) {
-        const uint64_t R = job->rcalls_first[ci + 1] - job->rcalls_first[ci];
-        if (R == 0) continue;
-        if (!outs[ci]) { set_err(err, errlen, "no buffer for chain %zu", ci); return PG_ERR_INVALID; }
-        HIP_TRY(hipMemcpyAsync(outs[ci], job->d_rcalls + job->rcalls_first[ci] * sizeof(pg_call), R * sizeof(pg_call), hipMemcpyDeviceToHost, job->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(job->stream));
-    return PG_OK;
-}
-
-extern "C" int pg_job_device_record_calls(pg_job* job, uint32_t ci, void** d_calls, uint64_t* n) {
-    if (!job || ci >= job->chains.size() || !job->d_rcalls || job->rcalls_dirty) return PG_ERR_INVALID;
-    if (d_calls) *d_calls = job->d_rcalls + job->rcalls_first[ci] * sizeof(pg_call);
-    if (n) *n = job->rcalls_first[ci + 1] - job->rcalls_first[ci];
-    return PG_OK;
-}
-
-extern "C" double pg_job_record_calls_ms(const pg_job* job) { return job ? job->rcalls_ms : 0.0; }
-
-// The unit entry point: host arrays and a plan in, one record per VCF record out, through the same two kernels.
-extern "C" int pg_record_calls_from_bins(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id, const uint8_t* kept,
-                                         const uint8_t* allele_present, const double* lik, const int32_t* lik_exp, const pg_record_plan* plan,
-                                         pg_call* out) {
-    const uint32_t V = n_variants;
-    if (V && (!allele_off || !allele_id || !kept || !allele_present || allele_off[0] != 0)) return PG_ERR_INVALID;
-    std::vector<uint64_t> goff((size_t)V + 1, 0);
-    for (uint32_t v = 0; v < V; ++v) {
-        if (allele_off[v + 1] <= allele_off[v] || allele_off[v + 1] - allele_off[v] > PG_MAX_ALLELES_PER_VARIANT) return PG_ERR_INVALID;
-        const uint64_t A = allele_off[v + 1] - allele_off[v];
-        goff[v + 1] = goff[v] + A * (A + 1) / 2;
-    }
-    RecordPlanHost h;
-    int rc = check_record_plan(plan, V, &h, nullptr, 0);
-    if (rc == PG_OK && V) rc = check_record_plan_ids(h, allele_off, allele_id, nullptr, 0);
-    if (rc != PG_OK) return rc;
-    if (V == 0) return PG_OK;
-    if (!out) return PG_ERR_INVALID;
-    const uint64_t n_lik = goff[V], sumA = allele_off[V];
-    if (n_lik && (!lik || !lik_exp)) return PG_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); return PG_ERR_DEVICE; }
-    if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return PG_ERR_DEVICE;
-    const uint64_t* d_tm = nullptr;
-    const int32_t* d_te = nullptr;
-    rc = gq_table_on(device, &d_tm, &d_te, nullptr, 0);
-    if (rc != PG_OK) return rc;
-    RcallsLaunch L;
-    plan_rcalls(1, [&](uint32_t) -> const RecordPlanHost* { return &h; }, [&](uint32_t) { return allele_off; }, &L);
-    // one device buffer: every array at a 256-byte boundary
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += align_up(bytes + 8); return at; };
-    const size_t o_contig = take(sizeof(DevContig)), o_desc = take(sizeof(RCallsDesc)), o_wide = take(L.wide.size() * 4), o_aoff = take(((size_t)V + 1) * 4),
-                 o_aid = take(sumA * 2), o_kept = take(V), o_pres = take(sumA), o_goff = take(((size_t)V + 1) * 8), o_lik = take(n_lik * 8),
-                 o_exp = take(n_lik * 4), o_plan = take(record_plan_device_bytes(h)), o_stage = take((size_t)L.n_slots * L.stride * 16),
-                 o_out = take((size_t)h.R * sizeof(pg_call));
-    unsigned char* d = nullptr;
-    if (hipMalloc((void**)&d, o) != hipSuccess) { (void)hipGetLastError(); return PG_ERR_NOMEM; }
-    DevContig dc;
-    memset(&dc, 0, sizeof(dc));
-    dc.V = V;
-    dc.allele_off = (const uint32_t*)(d + o_aoff);
-    dc.allele_id = (const uint16_t*)(d + o_aid);
-    dc.kept = d + o_kept;
-    dc.allele_present = d + o_pres;
-    dc.geno_off = (const uint64_t*)(d + o_goff);
-    dc.lik = (double*)(d + o_lik);
-    dc.lik_exp = (int32_t*)(d + o_exp);
-    bool ok = record_plan_upload(h, d + o_plan, &L.desc[0].plan);
-    L.desc[0].out = d + o_out;
-    ok = ok && hipMemcpy(d + o_contig, &dc, sizeof(dc), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d + o_desc, L.desc.data(), sizeof(RCallsDesc), hipMemcpyHostToDevice) == hipSuccess &&
-         (L.wide.empty() || hipMemcpy(d + o_wide, L.wide.data(), L.wide.size() * 4, hipMemcpyHostToDevice) == hipSuccess) &&
-         hipMemcpy(d + o_aoff, allele_off, ((size_t)V + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d + o_aid, allele_id, sumA * 2, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d + o_kept, kept, V, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d + o_pres, allele_present, sumA, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d + o_goff, goff.data(), ((size_t)V + 1) * 8, hipMemcpyHostToDevice) == hipSuccess &&
-         (n_lik == 0 || (hipMemcpy(d + o_lik, lik, n_lik * 8, hipMemcpyHostToDevice) == hipSuccess &&
-                         hipMemcpy(d + o_exp, lik_exp, n_lik * 4, hipMemcpyHostToDevice) == hipSuccess));
-    if (ok) {
-        pgk_launch_rcalls((const DevContig*)(d + o_contig), (const RCallsDesc*)(d + o_desc), 1, L.n_blocks, d + o_wide, (uint32_t)(L.wide.size() / 2),
-                          d + o_stage, L.max_bins, L.stride, L.n_slots, d_tm, d_te, nullptr);
-        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
-             hipMemcpy(out, d + o_out, (size_t)h.R * sizeof(pg_call), hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    hipFree(d);
-    return ok ? PG_OK : PG_ERR_DEVICE;
-}
-
-// ---------------------------------------------------------------------------------------
-//  The GL column per VCF record (pg_calls.hip: k_rgl / k_rgl_wide / k_gl_values).
-// ---------------------------------------------------------------------------------------
-namespace {
-
-static_assert(sizeof(pg_gl) == 4, "a GL value is 4 bytes");
-
-// record r owns nd (nd + 1) / 2 values, nd its defined alleles
-std::vector<uint64_t> record_gl_offsets(const RecordPlanHost& h) {
-    std::vector<uint64_t> off((size_t)h.R + 1, 0);
-    for (uint32_t q = 0; q < h.R; ++q) {
-        uint64_t nd = 0;
-        for (uint32_t i = h.vcf_off[q]; i < h.vcf_off[q + 1]; ++i) nd += h.vcf_index[i] != 0xFFFFu;
-        off[q + 1] = off[q] + nd * (nd + 1) / 2;
-    }
-    return off;
-}
-
-int rgl_ready(pg_job* job, char* err, size_t errlen) {
-    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
-    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
-    if (!job->rgl_formed || job->rgl_dirty) { set_err(err, errlen, "pg_job_record_gl has not been called"); return PG_ERR_INVALID; }
-    return PG_OK;
-}
-
-RGlDesc rgl_desc_of(const RCallsDesc& c) {
-    RGlDesc d;
-    memset(&d, 0, sizeof(d));
-    d.blk0 = c.blk0; d.R = c.R; d.chain = c.chain;
-    d.plan = c.plan;
-    return d;
-}
-
-}  // namespace
-
-extern "C" int pg_record_gl_offsets(const pg_record_plan* plan, uint64_t* gl_off) {
-    if (!plan || !gl_off) return PG_ERR_INVALID;
-    RecordPlanHost h;
-    const int rc = check_record_plan(plan, plan->n_variants, &h, nullptr, 0);
-    if (rc != PG_OK) return rc;
-    const std::vector<uint64_t> off = record_gl_offsets(h);
-    memcpy(gl_off, off.data(), off.size() * sizeof(uint64_t));
-    return PG_OK;
-}
-
-extern "C" int pg_gl_text(pg_gl value, char* buf, size_t len) { return pgx_gl_text(value, buf, len); }
-
-extern "C" int pg_job_record_gl(pg_job* job, char* err, size_t errlen) {
-    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
-    if (!job->params.run_genotyping) { set_err(err, errlen, "the job does not run the genotyping: it has no bins to form likelihoods from"); return PG_ERR_INVALID; }
-    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(job->device));
-    const uint32_t n = (uint32_t)job->chains.size();
-    if (!job->calls_events) {
-        HIP_TRY(hipEventCreate(&job->ev_calls[0]));
-        HIP_TRY(hipEventCreate(&job->ev_calls[1]));
-        job->calls_events = true;
-    }
-    if (job->rgl_dirty) {   // a plan or the index has changed: the ids are checked, the offsets, descriptors and lists made anew
-        // the offsets hang on the plan alone: one array per PLAN, whatever the number of index contigs that refer to it
-        struct PlanOffsets { std::vector<uint64_t> gl_off; size_t at = 0; };
-        std::map<const RecordPlanHost*, PlanOffsets> offs;
-        for (const RecordPlanRef& p : job->rplans)
-            if (p && p->R && !offs.count(p.get())) offs[p.get()].gl_off = record_gl_offsets(*p);
-        RcallsLaunch L;
-        plan_rcalls(n, [&](uint32_t c) { return plan_of_chain(job, c); }, [&](uint32_t c) { return job->index[job->chains[c].index].aoff.data(); }, &L);
-        std::vector<uint64_t> first((size_t)n + 1, 0);
-        for (uint32_t c = 0; c < n; ++c) {
-            const auto o = offs.find(plan_of_chain(job, c));
-            first[c + 1] = first[c] + (o != offs.end() ? o->second.gl_off.back() : 0);
-        }
-        size_t total = align_up((size_t)first[n] * sizeof(pg_gl) + 8);
-        for (auto& kv : offs) {
-            kv.second.at = total;
-            total += align_up(kv.second.gl_off.size() * sizeof(uint64_t) + 8);
-        }
-        const size_t o_desc = total;
-        const size_t o_wide = o_desc + align_up(L.desc.size() * sizeof(RGlDesc) + 8);
-        const size_t o_stage = o_wide + align_up(L.wide.size() * sizeof(uint32_t) + 8);
-        // (the id check reads the descriptors of the record calls: a copy of them and its word behind the staging slots)
-        const size_t o_ids = o_stage + align_up((size_t)L.n_slots * L.stride * 16 + 8);
-        const size_t o_hit = o_ids + align_up((job->rplan_ids_ok ? 0 : L.desc.size()) * sizeof(RCallsDesc) + 8);
-        total = o_hit + align_up(8);
-        unsigned char* d = nullptr;
-        if (hipMalloc((void**)&d, total) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the record GLs failed", total); return PG_ERR_NOMEM; }
-        std::vector<RGlDesc> desc;
-        for (const RCallsDesc& c : L.desc) {
-            RGlDesc g = rgl_desc_of(c);
-            g.out = d + first[c.chain] * sizeof(pg_gl);
-            g.gl_off = (const uint64_t*)(d + offs[plan_of_chain(job, c.chain)].at);
-            desc.push_back(g);
-        }
-        hipError_t he = hipSuccess;
-        for (auto& kv : offs)
-            if (he == hipSuccess) he = hipMemcpy(d + kv.second.at, kv.second.gl_off.data(), kv.second.gl_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
-        if (he == hipSuccess && !desc.empty()) he = hipMemcpy(d + o_desc, desc.data(), desc.size() * sizeof(RGlDesc), hipMemcpyHostToDevice);
-        if (he == hipSuccess && !L.wide.empty()) he = hipMemcpy(d + o_wide, L.wide.data(), L.wide.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-        if (he == hipSuccess && !job->rplan_ids_ok && !L.desc.empty()) he = hipMemcpy(d + o_ids, L.desc.data(), L.desc.size() * sizeof(RCallsDesc), hipMemcpyHostToDevice);
-        if (he != hipSuccess) { hipFree(d); set_err(err, errlen, "upload of the record GLs' lists failed: %s", hipGetErrorString(he)); return PG_ERR_DEVICE; }
-        const int rc = check_record_plan_ids_on_device(job, (const RCallsDesc*)(d + o_ids), (uint32_t)L.desc.size(), L.n_blocks, d + o_hit, err, errlen);
-        if (rc != PG_OK) { hipFree(d); return rc; }
-        if (job->d_rgl) hipFree(job->d_rgl);
-        job->d_rgl = d;
-        job->rgl_first = std::move(first);
-        job->rgl_desc = std::move(desc);
-        job->rgl_blocks = L.n_blocks; job->rgl_wide = (uint32_t)(L.wide.size() / 2);
-        job->rgl_max_bins = L.max_bins; job->rgl_stride = L.stride; job->rgl_slots = L.n_slots;
-        job->o_rgl_desc = o_desc; job->o_rgl_wide = o_wide; job->o_rgl_stage = o_stage;
-        job->rgl_dirty = false;
-        job->rgl_formed = false;
-    }
-    hipStream_t s = job->stream;
-    HIP_TRY(hipEventRecord(job->ev_calls[0], s));
-    pgk_launch_rgl(job->d_contigs, (const RGlDesc*)(job->d_rgl + job->o_rgl_desc), (uint32_t)job->rgl_desc.size(), job->rgl_blocks,
-                   job->d_rgl + job->o_rgl_wide, job->rgl_wide, job->d_rgl + job->o_rgl_stage, job->rgl_max_bins, job->rgl_stride, job->rgl_slots, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(job->ev_calls[1], s));
-    HIP_TRY(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, job->ev_calls[0], job->ev_calls[1]));
-    job->rgl_ms = ms;
-    job->rgl_formed = true;
-    return PG_OK;
-}
-
-extern "C" int pg_job_fetch_record_gl(pg_job* job, uint32_t ci, pg_gl* out, char* err, size_t errlen) {
-    int rc = rgl_ready(job, err, errlen);
-    if (rc != PG_OK) return rc;
-    if (ci >= job->chains.size()) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
-    const uint64_t N = job->rgl_first[ci + 1] - job->rgl_first[ci];
-    if (N == 0) return PG_OK;
-    if (!out) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(job->device));
-    HIP_TRY(hipMemcpy(out, job->d_rgl + job->rgl_first[ci] * sizeof(pg_gl), N * sizeof(pg_gl), hipMemcpyDeviceToHost));
-    return PG_OK;
-}
-
-extern "C" int pg_job_fetch_record_gl_all(pg_job* job, pg_gl* const* outs, char* err, size_t errlen) {
-    int rc = rgl_ready(job, err, errlen);
-    if (rc != PG_OK) return rc;
-    if (!outs) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(job->device));
-    for (size_t ci = 0; ci < job->chains.size(); ++ci) {
-        const uint64_t N = job->rgl_first[ci + 1] - job->rgl_first[ci];
-        if (N == 0) continue;
-        if (!outs[ci]) { set_err(err, errlen, "no buffer for chain %zu", ci); return PG_ERR_INVALID; }
-        HIP_TRY(hipMemcpyAsync(outs[ci], job->d_rgl + job->rgl_first[ci] * sizeof(pg_gl), N * sizeof(pg_gl), hipMemcpyDeviceToHost, job->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(job->stream));
-    return PG_OK;
-}
-
-extern "C" int pg_job_device_record_gl(pg_job* job, uint32_t ci, void** d_gl, uint64_t* n) {
-    if (!job || ci >= job->chains.size() || !job->d_rgl || job->rgl_dirty) return PG_ERR_INVALID;
-    if (d_gl) *d_gl = job->d_rgl + job->rgl_first[ci] * sizeof(pg_gl);
-    if (n) *n = job->rgl_first[ci + 1] - job->rgl_first[ci];
-    return PG_OK;
-}
-
-extern "C" double pg_job_record_gl_ms(const pg_job* job) { return job ? job->rgl_ms : 0.0; }
-
-// The packed fetches: the records and the values lie chain after chain on the device, so the whole of either is one copy.
-extern "C" int pg_job_record_first(pg_job* job, uint64_t* calls_first, uint64_t* gl_first, char* err, size_t errlen) {
-    if (!calls_first && !gl_first) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
-    int rc = calls_first ? rcalls_ready(job, err, errlen) : PG_OK;
-    if (rc == PG_OK && gl_first) rc = rgl_ready(job, err, errlen);
-    if (rc != PG_OK) return rc;
-    if (calls_first) memcpy(calls_first, job->rcalls_first.data(), job->rcalls_first.size() * sizeof(uint64_t));
-    if (gl_first) memcpy(gl_first, job->rgl_first.data(), job->rgl_first.size() * sizeof(uint64_t));
-    return PG_OK;
-}
-
-extern "C" int pg_job_fetch_record_calls_packed(pg_job* job, pg_call* out, uint64_t n, char* err, size_t errlen) {
-    int rc = rcalls_ready(job, err, errlen);
-    if (rc != PG_OK) return rc;
-    if (n != job->rcalls_first.back()) { set_err(err, errlen, "the job holds %llu records, not %llu", (unsigned long long)job->rcalls_first.back(), (unsigned long long)n); return PG_ERR_INVALID; }
-    if (n == 0) return PG_OK;
-    if (!out) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(job->device));
-    HIP_TRY(hipMemcpyAsync(out, job->d_rcalls, n * sizeof(pg_call), hipMemcpyDeviceToHost, job->stream));
-    HIP_TRY(hipStreamSynchronize(job->stream));
-    return PG_OK;
-}
-
-extern "C" int pg_job_fetch_record_gl_packed(pg_job* job, pg_gl* out, uint64_t n, char* err, size_t errlen) {
-    int rc = rgl_ready(job, err, errlen);
-    if (rc != PG_OK) return rc;
-    if (n != job->rgl_first.back()) { set_err(err, errlen, "the job holds %llu GL values, not %llu", (unsigned long long)job->rgl_first.back(), (unsigned long long)n); return PG_ERR_INVALID; }
-    if (n == 0) return PG_OK;
-    if (!out) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(job->device));
-    HIP_TRY(hipMemcpyAsync(out, job->d_rgl, n * sizeof(pg_gl), hipMemcpyDeviceToHost, job->stream));
-    HIP_TRY(hipStreamSynchronize(job->stream));
-    return PG_OK;
-}
-
-// The unit entry point: host arrays and a plan in, the records' GL values out, through the same two kernels.
-extern "C" int pg_record_gl_from_bins(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id, const uint8_t* kept,
-                                      const uint8_t* allele_present, const double* lik, const int32_t* lik_exp, const pg_record_plan* plan, pg_gl* out) {
-    const uint32_t V = n_variants;
-    if (V && (!allele_off || !allele_id || !kept || !allele_present || allele_off[0] != 0)) return PG_ERR_INVALID;
-    std::vector<uint64_t> goff((size_t)V + 1, 0);
-    for (uint32_t v = 0; v < V; ++v) {
-        if (allele_off[v + 1] <= allele_off[v] || allele_off[v + 1] - allele_off[v] > PG_MAX_ALLELES_PER_VARIANT) return PG_ERR_INVALID;
-        const uint64_t A = allele_off[v + 1] - allele_off[v];
-        goff[v + 1] = goff[v] + A * (A + 1) / 2;
-    }
-    RecordPlanHost h;
-    int rc = check_record_plan(plan, V, &h, nullptr, 0);
-    if (rc == PG_OK && V) rc = check_record_plan_ids(h, allele_off, allele_id, nullptr, 0);
-    if (rc != PG_OK) return rc;
-    if (V == 0) return PG_OK;
-    if (!out) return PG_ERR_INVALID;
-    const uint64_t n_lik = goff[V], sumA = allele_off[V];
-    if (n_lik && (!lik || !lik_exp)) return PG_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); return PG_ERR_DEVICE; }
-    if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return PG_ERR_DEVICE;
-    const std::vector<uint64_t> gl_off = record_gl_offsets(h);
-    const uint64_t n_values = gl_off.back();
-    RcallsLaunch L;
-    plan_rcalls(1, [&](uint32_t) -> const RecordPlanHost* { return &h; }, [&](uint32_t) { return allele_off; }, &L);
-    // one device buffer: every array at a 256-byte boundary
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += align_up(bytes + 8); return at; };
-    const size_t o_contig = take(sizeof(DevContig)), o_desc = take(sizeof(RGlDesc)), o_wide = take(L.wide.size() * 4), o_aoff = take(((size_t)V + 1) * 4),
-                 o_aid = take(sumA * 2), o_kept = take(V), o_pres = take(sumA), o_goff = take(((size_t)V + 1) * 8), o_lik = take(n_lik * 8),
-                 o_exp = take(n_lik * 4), o_plan = take(record_plan_device_bytes(h)), o_stage = take((size_t)L.n_slots * L.stride * 16),
-                 o_gloff = take(gl_off.size() * 8), o_out = take((size_t)n_values * sizeof(pg_gl));
-    unsigned char* d = nullptr;
-    if (hipMalloc((void**)&d, o) != hipSuccess) { (void)hipGetLastError(); return PG_ERR_NOMEM; }
-    DevContig dc;
-    memset(&dc, 0, sizeof(dc));
-    dc.V = V;
-    dc.allele_off = (const uint32_t*)(d + o_aoff);
-    dc.allele_id = (const uint16_t*)(d + o_aid);
-    dc.kept = d + o_kept;
-    dc.allele_present = d + o_pres;
-    dc.geno_off = (const uint64_t*)(d + o_goff);
-    dc.lik = (double*)(d + o_lik);
-    dc.lik_exp = (int32_t*)(d + o_exp);
-    bool ok = record_plan_upload(h, d + o_plan, &L.desc[0].plan);
-    RGlDesc gd = rgl_desc_of(L.desc[0]);
-    gd.out = d + o_out;
-    gd.gl_off = (const uint64_t*)(d + o_gloff);
-    ok = ok && hipMemcpy(d + o_contig, &dc, sizeof(dc), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d + o_desc, &gd, sizeof(RGlDesc), hipMemcpyHostToDevice) == hipSuccess &&
-         (L.wide.empty() || hipMemcpy(d + o_wide, L.wide.data(), L.wide.size() * 4, hipMemcpyHostToDevice) == hipSuccess) &&
-         hipMemcpy(d + o_aoff, allele_off, ((size_t)V + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d + o_aid, allele_id, sumA * 2, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d + o_kept, kept, V, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d + o_pres, allele_present, sumA, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d + o_goff, goff.data(), ((size_t)V + 1) * 8, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d + o_gloff, gl_off.data(), gl_off.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
-         (n_lik == 0 || (hipMemcpy(d + o_lik, lik, n_lik * 8, hipMemcpyHostToDevice) == hipSuccess &&
-                         hipMemcpy(d + o_exp, lik_exp, n_lik * 4, hipMemcpyHostToDevice) == hipSuccess));
-    if (ok) {
-        pgk_launch_rgl((const DevContig*)(d + o_contig), (const RGlDesc*)(d + o_desc), 1, L.n_blocks, d + o_wide, (uint32_t)(L.wide.size() / 2), d + o_stage,
-                       L.max_bins, L.stride, L.n_slots, nullptr);
-        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
-             (n_values == 0 || hipMemcpy(out, d + o_out, (size_t)n_values * sizeof(pg_gl), hipMemcpyDeviceToHost) == hipSuccess);
-    }
-    hipFree(d);
-    return ok ? PG_OK : PG_ERR_DEVICE;
-}
-
-// The unit entry point of the digits alone: out[i] = the GL of m[i] 2^e[i] by the device's own log10 / log1p.
-extern "C" int pg_gl_from_values(int device, uint64_t n, const uint64_t* m, const int32_t* e, pg_gl* out) {
-    if (n == 0) return PG_OK;
-    if (!m || !e || !out || n > 0x7FFFFFFFull) return PG_ERR_INVALID;
-    for (uint64_t i = 0; i < n; ++i)   // a pair is normalised, or zero with exponent 0
-        if (m[i] == 0 ? e[i] != 0 : ((m[i] >> 63) == 0 || e[i] < -40000 || e[i] > 40000)) return PG_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); return PG_ERR_DEVICE; }
-    if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return PG_ERR_DEVICE;
-    const size_t o_e = align_up(n * 8 + 8), o_out = o_e + align_up(n * 4 + 8), total = o_out + align_up(n * 4 + 8);
-    unsigned char* d = nullptr;
-    if (hipMalloc((void**)&d, total) != hipSuccess) { (void)hipGetLastError(); return PG_ERR_NOMEM; }
-    bool ok = hipMemcpy(d, m, n * 8, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d + o_e, e, n * 4, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) {
-        pgk_launch_gl_values((const uint64_t*)d, (const int32_t*)(d + o_e), d + o_out, (uint32_t)n, nullptr);
-        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
-             hipMemcpy(out, d + o_out, n * sizeof(pg_gl), hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    hipFree(d);
-    return ok ? PG_OK : PG_ERR_DEVICE;
 }

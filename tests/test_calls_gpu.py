@@ -109,3 +109,26 @@ def test_refusals():
         job.calls()
     assert e.value.code == -1
     job.close()
+
+
+def test_what_only_the_calls_do():
+    """Where pg_job_calls and its fetches differ from the record families (tests/test_record_calls_gpu.py and
+    tests/test_record_gl_gpu.py: test_where_the_records_differ_from_the_calls): a null `out` is refused even for a chain without variants, the device pointers are handed out as soon as the buffer
+    exists, a later pg_job_run leaves the formed calls fetchable, and pg_calls_from_bins answers V = 0 before it looks at a pointer."""
+    import ctypes as C
+    b = synthetic_panel(10, 16, 20, seed=7450)
+    job = hmm.Job([b, b.slice(0, 0)], hmm.ProbabilityTable(*ARGS), hmm.make_params(1.26, False, 1e-5))
+    lib, err = job._lib, C.create_string_buffer(512)
+    job.run()
+    d, n = C.c_void_p(), C.c_uint64()
+    assert lib.pg_job_device_calls(job.h, 0, C.byref(d), C.byref(n)) == -1   # no buffer yet
+    recs = job.calls()
+    assert lib.pg_job_device_calls(job.h, 0, C.byref(d), C.byref(n)) == 0 and n.value == 10 and d.value
+    assert lib.pg_job_device_calls(job.h, 1, C.byref(d), C.byref(n)) == 0 and n.value == 0
+    assert lib.pg_job_fetch_calls(job.h, 1, None, err, 512) == -1 and err.value == b"bad argument"   # nothing to fetch, `out` asked for all the same
+    assert len(calls.fetch_calls(job, 1)) == 0
+    job.run()   # the same inputs again: the records formed before are still there, and still the same after forming them anew
+    assert np.array_equal(calls.fetch_calls(job, 0), recs[0])
+    assert np.array_equal(job.calls()[0], recs[0])
+    job.close()
+    assert lib.pg_calls_from_bins(0, 0, None, None, None, None, None, None, None) == 0

@@ -159,3 +159,34 @@ def test_refusals():
         job.record_calls()
     assert e.value.code == -1
     job.close()
+
+
+def test_where_the_records_differ_from_the_calls():
+    """The record calls' side of tests/test_calls_gpu.py's test_what_only_the_calls_do: a chain with nothing to fetch needs no `out`,
+    the device pointers are refused from a new plan until the records are formed again (the calls' are not), a later pg_job_run
+    leaves the formed records fetchable, and pg_record_calls_from_bins checks its plan before V = 0 answers PG_OK."""
+    b = synthetic_panel(10, 16, 20, seed=7850)
+    rng = np.random.default_rng(7851)
+    job = hmm.Job([b, b.slice(0, 0)], hmm.ProbabilityTable(*ARGS), hmm.make_params(1.26, False, 1e-5))
+    lib, err = job._lib, C.create_string_buffer(512)
+    plan = random_plan(rng, b)
+    job.record_plan(0, plan)
+    job.run()
+    job.calls()
+    recs = job.record_calls()
+    d, n = C.c_void_p(), C.c_uint64()
+    assert lib.pg_job_device_record_calls(job.h, 0, C.byref(d), C.byref(n)) == 0 and n.value == plan.n_records
+    assert lib.pg_job_fetch_record_calls(job.h, 1, None, err, 512) == 0   # nothing to fetch: no `out` needed
+    assert lib.pg_job_fetch_record_calls(job.h, 0, None, err, 512) == -1 and err.value == b"bad argument"
+    job.run()   # the same inputs again: the records formed before are still there
+    assert np.array_equal(calls.fetch_record_calls(job, 0), recs[0])
+    job.record_plan(0, random_plan(rng, b))
+    assert lib.pg_job_device_record_calls(job.h, 0, C.byref(d), C.byref(n)) == -1
+    assert lib.pg_job_device_calls(job.h, 0, C.byref(d), C.byref(n)) == 0 and n.value == 10   # (the calls hang on no plan)
+    with pytest.raises(hmm.PanGenieError) as e:
+        calls.fetch_record_calls(job, 0)
+    assert e.value.code == -1
+    job.record_calls()
+    assert lib.pg_job_device_record_calls(job.h, 0, C.byref(d), C.byref(n)) == 0
+    job.close()
+    assert lib.pg_record_calls_from_bins(0, 0, None, None, None, None, None, None, None, None) == -1   # the null plan, V = 0 or not
