@@ -1,6 +1,7 @@
-// pg_job.h — what the host units of the C-ABI shim share (pg_shim.cpp: jobs, their build and run schedule;
-// pg_shim_calls.cpp: the output columns formed from a job's finished bins): the error helpers, the host's picture of a
-// job's index contigs, chains and record plans, and struct pg_job itself.  Private: nothing here is exported.
+// pg_job.h — what the host units of the C-ABI shim share (pg_shim.cpp: jobs, their build and uploads; pg_shim_run.cpp: the
+// run schedule, pg_job_run; pg_shim_calls.cpp: the output columns formed from a job's finished bins): the error helpers, the
+// host's picture of a job's index contigs, chains and record plans, struct pg_job itself, and the few helpers upload and run
+// both need.  Private: nothing here is exported.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -8,6 +9,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <chrono>
 #include <memory>
 #include <string>
 #include <thread>
@@ -37,6 +39,7 @@ inline void set_err(char* err, size_t errlen, const char* fmt, ...) {
     } while (0)
 
 constexpr int PG_MAX_DEVICES_HOST = 64;
+inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
 struct IndexHost {   // one index contig
@@ -267,5 +270,24 @@ inline void record_plans_changed(pg_job* job) {
     job->rgl.dirty = true;
     job->rplan_ids_ok = false;
 }
+
+// Group B's copies of a pipelined first run (pg_job::late_threads) read the caller's arrays and feed the job's second stream:
+// whoever needs either to be left alone waits for the threads first.
+inline void join_late_threads(pg_job* job) {
+    for (auto& t : job->late_threads) if (t.joinable()) t.join();
+    job->late_threads.clear();
+    job->late_pending = false;
+}
+
+// grid extent of the wave-per-object index kernels (pgk_launch_index): the longest list of variants with more than 32 alleles
+inline uint32_t max_big_list(const pg_job* job) {
+    uint32_t max_big = 0;
+    for (const IndexHost& x : job->index) if (x.list_big.size() > max_big) max_big = (uint32_t)x.list_big.size();
+    return max_big;
+}
+
+// Do the kernels of `s` and of the job's second stream run side by side?  (pg_shim_run.cpp; upload_inputs asks for the pipelined
+// first run, pg_job_run for the persistent phase 2.)  May replace job->stream2.
+bool streams_concurrent(pg_job* job, hipStream_t s);
 
 }  // namespace pgj

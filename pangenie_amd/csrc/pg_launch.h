@@ -1,4 +1,4 @@
-// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp, pg_shim_calls.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip, pg_calls.hip).
+// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp, pg_shim_run.cpp, pg_shim_calls.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip, pg_calls.hip).
 //
 // The ONE declaration of every host-callable launcher and of the two launch masks a job hands them.  Both sides include
 // it: a launcher whose parameter list changes on one side only no longer compiles (C linkage: the linker would not notice).

@@ -1,7 +1,8 @@
 // pg_shim.cpp — C-ABI of include/pangenie_hmm.h on top of the HIP kernels (pg_kernels.hip): the probability table, jobs
-// (their build, upload, run schedule and bin fetches), the coalescer of one-shot calls and the unit entry points of the
-// emission / transition kernels.  The output columns formed from a job's finished bins — calls, record calls, record GLs —
-// are pg_shim_calls.cpp's; the two units share struct pg_job and the host's chain / index / plan types through pg_job.h.
+// (their build, uploads and bin fetches), the coalescer of one-shot calls and the unit entry points of the emission /
+// transition kernels.  A job's run schedule — pg_job_run — is pg_shim_run.cpp's; the output columns formed from a job's
+// finished bins — calls, record calls, record GLs — are pg_shim_calls.cpp's; the three units share struct pg_job and the
+// host's chain / index / plan types through pg_job.h.
 //
 // Host side of the boundary: argument checking, one device arena per job, H2D/D2H,
 // launch order, hipEvent timing per kernel class.  No compute happens here except the
@@ -39,14 +40,6 @@
 #include "pg_launch.h"
 
 using namespace pgj;
-
-namespace {
-
-double now_s() {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-}  // namespace
 
 // ---------------------------------------------------------------------------------------
 //  ProbabilityTable (host, long double) — reference src/probabilitytable.cpp
@@ -436,14 +429,6 @@ int sample_upload(pg_job* job, const std::vector<ChainSpec>& specs, unsigned cha
     return PG_OK;
 }
 
-bool streams_concurrent(pg_job* job, hipStream_t s);   // (below, in front of pg_job_run)
-// Group B's copies of a pipelined first run (pg_job::late_threads) read the caller's arrays and feed the job's second stream:
-// whoever needs either to be left alone waits for the threads first.
-void join_late_threads(pg_job* job) {
-    for (auto& t : job->late_threads) if (t.joinable()) t.join();
-    job->late_threads.clear();
-    job->late_pending = false;
-}
 // H2D of the inputs into a planned job.  Copies are queued on the job's stream; pageable sources are
 // staged by the runtime, so every call returns when its source has been read.
 int upload_inputs(pg_job* job, const pg_contig_batch* batches, const std::vector<ChainSpec>& specs, bool with_index,
@@ -616,8 +601,7 @@ int upload_inputs(pg_job* job, const pg_contig_batch* batches, const std::vector
         HIP_TRY(hipEventRecord(job->ev_ix[0], s));
         HIP_TRY(hipMemsetAsync(job->ix_base, 0, job->ix_bytes, s));
         if (job->srec_bytes) HIP_TRY(hipMemsetAsync(job->srec_base, 0, job->srec_bytes, s));
-        uint32_t max_big = 0;
-        for (const IndexHost& x : job->index) max_big = std::max<uint32_t>(max_big, (uint32_t)x.list_big.size());
+        const uint32_t max_big = max_big_list(job);
         if (pipe) pgk_launch_index(job->d_reps_g, job->nA, job->max_v, max_big, 0, s);   // (group B's: pg_job_run, when its inputs have arrived)
         else pgk_launch_index(job->d_reps, (uint32_t)job->index.size(), job->max_v, max_big, job->any_split ? 1 : 0, s);
         HIP_TRY(hipGetLastError());
@@ -1597,6 +1581,30 @@ int job_build(int device, uint32_t n_index, const pg_contig_batch* batches, cons
     return PG_OK;
 }
 
+// The chains of a cohort, sample-major: chain s * n_contigs + c reads sample s's arrays of contig c.
+int cohort_chain_specs(uint32_t n_samples, uint32_t n_contigs, const pg_sample_counts* samples, std::vector<ChainSpec>& specs,
+                       char* err, size_t errlen) {
+    specs.resize((size_t)n_samples * n_contigs);
+    for (uint32_t s = 0; s < n_samples; ++s) {
+        if (!samples[s].kmer_count || !samples[s].coverage) { set_err(err, errlen, "sample %u has null arrays", s); return PG_ERR_INVALID; }
+        for (uint32_t c = 0; c < n_contigs; ++c)
+            specs[(size_t)s * n_contigs + c] = {c, samples[s].kmer_count[c], samples[s].coverage[c]};
+    }
+    return PG_OK;
+}
+
+// No chain of a resident job that has variants may come with null arrays: the first such chain is refused by its number.
+int check_chain_arrays(const pg_job* job, const std::vector<ChainSpec>& specs, char* err, size_t errlen) {
+    for (size_t c = 0; c < specs.size(); ++c) {
+        const IndexHost& x = job->index[job->chains[c].index];
+        if (x.V > 0 && (!specs[c].coverage || (x.sumK > 0 && !specs[c].kmer_count))) {
+            set_err(err, errlen, "chain %zu has null kmer_count / coverage arrays", c);
+            return PG_ERR_INVALID;
+        }
+    }
+    return PG_OK;
+}
+
 }  // namespace
 
 extern "C" int pg_job_new(int device, uint32_t n_contigs, const pg_contig_batch* batches, const pg_table* table,
@@ -1622,12 +1630,9 @@ extern "C" int pg_cohort_new(int device, uint32_t n_contigs, const pg_contig_bat
     if (!out) { set_err(err, errlen, "null argument"); return PG_ERR_INVALID; }
     *out = nullptr;
     if (!index || !samples || n_contigs == 0 || n_samples == 0) { set_err(err, errlen, "null argument"); return PG_ERR_INVALID; }
-    std::vector<ChainSpec> specs((size_t)n_samples * n_contigs);
-    for (uint32_t s = 0; s < n_samples; ++s) {
-        if (!samples[s].kmer_count || !samples[s].coverage) { set_err(err, errlen, "sample %u has null arrays", s); return PG_ERR_INVALID; }
-        for (uint32_t c = 0; c < n_contigs; ++c)
-            specs[(size_t)s * n_contigs + c] = {c, samples[s].kmer_count[c], samples[s].coverage[c]};
-    }
+    std::vector<ChainSpec> specs;
+    const int rc = cohort_chain_specs(n_samples, n_contigs, samples, specs, err, errlen);
+    if (rc != PG_OK) return rc;
     return job_build(device, n_contigs, index, specs, n_samples, true, table, params, false, out, err, errlen);
 }
 
@@ -1662,45 +1667,16 @@ extern "C" int pg_job_upload(pg_job* job, const pg_contig_batch* batches, const 
         }
     if (job->cohort) {
         if (!samples) { set_err(err, errlen, "cohort job: samples must be given"); return PG_ERR_INVALID; }
-        for (uint32_t s = 0; s < job->n_samples; ++s) {
-            if (!samples[s].kmer_count || !samples[s].coverage) { set_err(err, errlen, "sample %u has null arrays", s); return PG_ERR_INVALID; }
-            for (uint32_t c = 0; c < job->n_contigs; ++c)
-                specs[(size_t)s * job->n_contigs + c] = {c, samples[s].kmer_count[c], samples[s].coverage[c]};
-        }
+        const int rc = cohort_chain_specs(job->n_samples, job->n_contigs, samples, specs, err, errlen);
+        if (rc != PG_OK) return rc;
     } else {
         if (!batches) { set_err(err, errlen, "batches must be given"); return PG_ERR_INVALID; }
         for (uint32_t i = 0; i < n; ++i) specs[i] = {i, batches[i].kmer_count, batches[i].coverage};
     }
-    for (uint32_t c = 0; c < n; ++c) {
-        const IndexHost& x = job->index[job->chains[c].index];
-        if (x.V > 0 && (!specs[c].coverage || (x.sumK > 0 && !specs[c].kmer_count))) {
-            set_err(err, errlen, "chain %u has null kmer_count / coverage arrays", c);
-            return PG_ERR_INVALID;
-        }
-    }
+    const int rc = check_chain_arrays(job, specs, err, errlen);
+    if (rc != PG_OK) return rc;
     return upload_inputs(job, batches, specs, batches != nullptr, err, errlen);
 }
-
-namespace {
-int cohort_specs(pg_job* job, const pg_sample_counts* samples, std::vector<ChainSpec>& specs, char* err, size_t errlen) {
-    if (!job->cohort) { set_err(err, errlen, "not a cohort job"); return PG_ERR_INVALID; }
-    if (!samples) { set_err(err, errlen, "cohort job: samples must be given"); return PG_ERR_INVALID; }
-    specs.resize(job->chains.size());
-    for (uint32_t s = 0; s < job->n_samples; ++s) {
-        if (!samples[s].kmer_count || !samples[s].coverage) { set_err(err, errlen, "sample %u has null arrays", s); return PG_ERR_INVALID; }
-        for (uint32_t c = 0; c < job->n_contigs; ++c)
-            specs[(size_t)s * job->n_contigs + c] = {c, samples[s].kmer_count[c], samples[s].coverage[c]};
-    }
-    for (size_t c = 0; c < specs.size(); ++c) {
-        const IndexHost& x = job->index[job->chains[c].index];
-        if (x.V > 0 && (!specs[c].coverage || (x.sumK > 0 && !specs[c].kmer_count))) {
-            set_err(err, errlen, "chain %zu has null kmer_count / coverage arrays", c);
-            return PG_ERR_INVALID;
-        }
-    }
-    return PG_OK;
-}
-}  // namespace
 
 // The next batch of samples of a cohort job, uploaded WHILE the current one is being genotyped: a worker thread packs
 // the counts into the pinned staging buffer and copies them into the job's second set of per-sample arrays on a copy
@@ -1710,8 +1686,11 @@ extern "C" int pg_job_upload_begin(pg_job* job, const pg_sample_counts* samples,
     if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
     if (job->upload_pending) { set_err(err, errlen, "an upload is already in flight: call pg_job_upload_end first"); return PG_ERR_INVALID; }
     HIP_TRY(hipSetDevice(job->device));
+    if (!job->cohort) { set_err(err, errlen, "not a cohort job"); return PG_ERR_INVALID; }
+    if (!samples) { set_err(err, errlen, "cohort job: samples must be given"); return PG_ERR_INVALID; }
     auto specs = std::make_shared<std::vector<ChainSpec>>();
-    const int rc = cohort_specs(job, samples, *specs, err, errlen);
+    int rc = cohort_chain_specs(job->n_samples, job->n_contigs, samples, *specs, err, errlen);
+    if (rc == PG_OK) rc = check_chain_arrays(job, *specs, err, errlen);
     if (rc != PG_OK) return rc;
     const size_t n = job->chains.size();
     if (!job->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&job->copy_stream, hipStreamNonBlocking));
@@ -1822,301 +1801,6 @@ extern "C" int pgi_job_fill_end(pg_job* job, uint32_t sample, uint32_t n_contigs
         if (V) job->chains[(size_t)sample * n_contigs + c].coverage.assign(coverage[c], coverage[c] + V);
     }
     job->ran = false;
-    return PG_OK;
-}
-
-namespace {
-// Transition probabilities of the Viterbi, per kept column, formed on the host in long double exactly as the
-// reference forms them (TransitionProbabilityComputer, src/transitionprobabilitycomputer.cpp:8-19, :33-39) and split
-// into exact (hi, lo) double pairs: {t0, t1, t2} = {p^2, pq, q^2}.  The reference's decisions hang on p/q - 1, which
-// drops below fp64's resolution once distance / H > 37 (pg_viterbi.hip).  Column 0 has no predecessor.
-int viterbi_transitions(pg_job* job, hipStream_t s, char* err, size_t errlen) {
-    const uint32_t n = (uint32_t)job->chains.size();
-    std::vector<std::vector<double>> tq_of_index(job->index.size());
-    std::vector<char> done(job->index.size(), 0);
-    std::vector<uint32_t> colv;
-    for (uint32_t c = 0; c < n; ++c) {
-        const ChainHost& ch = job->chains[c];
-        const IndexHost& x = job->index[ch.index];
-        if (x.V == 0) continue;
-        std::vector<double>& tq = tq_of_index[ch.index];
-        if (!done[ch.index]) {  // (the kept columns depend on the index alone: once per index contig)
-            done[ch.index] = 1;
-            uint32_t C = 0;
-            HIP_TRY(hipMemcpy(&C, ch.d.n_cols, sizeof(uint32_t), hipMemcpyDeviceToHost));
-            if (C > x.V) { set_err(err, errlen, "chain %u: bad column count", c); return PG_ERR_DEVICE; }
-            colv.resize(C ? C : 1);
-            if (C) HIP_TRY(hipMemcpy(colv.data(), ch.d.col_variant, (size_t)C * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            tq.assign((size_t)C * 8, 0.0);
-            const long double H = (long double)x.H;
-            for (uint32_t k = 0; k < C; ++k) {
-                long double t[3] = {1.0L, 1.0L, 1.0L};
-                if (k > 0 && !job->params.uniform) {
-                    const long double distance = (x.pos[colv[k]] - x.pos[colv[k - 1]]) * 0.000004L * ((long double)job->params.recombrate) * job->params.effective_N;
-                    const long double recomb_prob = (1.0L - expl(-distance / H)) * (1.0L / H);
-                    const long double no_recomb_prob = expl(-distance / H) + recomb_prob;
-                    t[0] = no_recomb_prob * no_recomb_prob; t[1] = no_recomb_prob * recomb_prob; t[2] = recomb_prob * recomb_prob;
-                }
-                for (int q = 0; q < 3; ++q) {
-                    const double hi = (double)t[q];
-                    tq[(size_t)k * 8 + 2 * q] = hi;
-                    tq[(size_t)k * 8 + 2 * q + 1] = (double)(t[q] - (long double)hi);  // exact: 64 - 53 bits are left
-                }
-            }
-        }
-        if (!tq.empty()) HIP_TRY(hipMemcpyAsync(ch.d.vit_tq, tq.data(), tq.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));  // (tq_of_index goes out of scope)
-    return PG_OK;
-}
-}  // namespace
-
-namespace {
-// The persistent phase 2 needs the kernels of `s` and of the job's second stream to run SIDE BY SIDE (they wait for each other).
-// Streams are mapped onto a few hardware queues, and two streams on one queue run one after the other: ask the device once per
-// stream (k_stream_handshake); a second stream that shares the queue is replaced by a new one, a few times.  False: this run
-// takes a launch per chunk.
-bool streams_concurrent(pg_job* job, hipStream_t s) {
-    if (job->persist_checked_any && job->persist_checked == s) return true;
-    for (int attempt = 0; attempt < 6; ++attempt) {
-        uint32_t w[4] = {0, 0, 0, 0};
-        if (hipMemcpyAsync(job->d_handshake, w, sizeof(w), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) break;
-        pgk_launch_stream_handshake(job->d_handshake, s, job->stream2);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess || hipStreamSynchronize(job->stream2) != hipSuccess) break;
-        if (hipMemcpy(w, job->d_handshake, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess) break;
-        if (w[2] == 1u) { job->persist_checked = s; job->persist_checked_any = true; return true; }
-        hipStream_t fresh = nullptr;   // (created BEFORE the old one is destroyed: the runtime hands a new stream the least used queue)
-        if (hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking) != hipSuccess) break;
-        (void)hipStreamDestroy(job->stream2);
-        job->stream2 = fresh;
-    }
-    (void)hipGetLastError();
-    return false;
-}
-}  // namespace
-
-extern "C" int pg_job_run(pg_job* job, void* stream_, char* err, size_t errlen) {
-    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
-    const double t_run = now_s();
-    HIP_TRY(hipSetDevice(job->device));
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : job->stream;
-    const uint32_t n = (uint32_t)job->chains.size();
-    job->host_s[3] = 0.0;
-    const bool late_own_stream = job->late_pending && s != job->stream;
-    if (late_own_stream) {
-        // (a caller's own stream: no pipelining — group B's inputs are waited for NOW, before streams_concurrent may replace the
-        //  second stream, which their copies are on; `s` waits for the copies, group B's index pass is made up below)
-        join_late_threads(job);
-        for (int rcb : job->late_rc)
-            if (rcb != (int)hipSuccess) { set_err(err, errlen, "input upload: %s", hipGetErrorString((hipError_t)rcb)); return PG_ERR_DEVICE; }
-        HIP_TRY(hipEventRecord(job->ev_late[1], job->stream2));
-        HIP_TRY(hipStreamWaitEvent(s, job->ev_late[1], 0));
-    }
-    const bool persist_now = job->persist && job->max_v > 0 && job->params.run_genotyping && streams_concurrent(job, s);   // (may replace stream2)
-    if (job->persist && job->max_v > 0 && job->params.run_genotyping) { if (persist_now) job->persist_runs += 1; else job->persist_fallbacks += 1; }
-    HIP_TRY(hipMemsetAsync(job->zero_base, 0, job->zero_bytes, s));
-    bool pieces_now = false;   // this run's phase 1 goes in pieces, and the second stream has refilled the partner columns of all chunks but piece 0's
-    if (job->max_v > 0 && job->params.run_genotyping) {
-        HIP_TRY(hipEventRecord(job->ev[0], s));
-        if (job->late_pending) {
-            // The pipelined first run (pg_job::pipeline): group A's preparation and phase 1 start NOW, on `s`; the host then waits for
-            // group B's inputs (they have been crossing PCIe since job_build) and puts B's index pass, preparation and phase 1 on the
-            // second stream, beside A's.  Phase 2 (below) starts when both are done.  (The timing classes: B's preparation counts
-            // into the phase-1 class.)
-            const uint32_t nA = job->nA, nB = n - nA;
-            HIP_TRY(hipEventRecord(job->ev_late[0], s));   // (behind the zeroing of the per-run block)
-            pgk_launch_prep(job->d_contigs_g, nA, job->max_v, job->max_prep_w, job->max_prep_m4, job->tab, s);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(job->ev[1], s));
-            HIP_TRY(hipEventRecord(job->ev[2], s));
-            pgk_launch_records(job->d_contigs_g, nA, job->max_v, s);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(job->ev[3], s));
-            pgk_launch_sweep(job->d_contigs_g, nA, job->hp_mask, 1, s);
-            HIP_TRY(hipGetLastError());
-            join_late_threads(job);   // (their copies are ISSUED — 17 ms on the whole genome —, on stream2)
-            for (int rcb : job->late_rc)
-                if (rcb != (int)hipSuccess) { set_err(err, errlen, "input upload: %s", hipGetErrorString((hipError_t)rcb)); return PG_ERR_DEVICE; }
-            hipStream_t sb = job->stream2;
-            HIP_TRY(hipStreamWaitEvent(sb, job->ev_late[0], 0));
-            uint32_t max_big = 0;
-            for (const IndexHost& x : job->index) max_big = std::max<uint32_t>(max_big, (uint32_t)x.list_big.size());
-            pgk_launch_index(job->d_reps_g + nA, nB, job->max_v, max_big, 0, sb);
-            pgk_launch_prep(job->d_contigs_g + nA, nB, job->max_v, job->max_prep_w, job->max_prep_m4, job->tab, sb);
-            pgk_launch_records(job->d_contigs_g + nA, nB, job->max_v, sb);
-            pgk_launch_sweep(job->d_contigs_g + nA, nB, job->hp_mask, 1, sb);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(job->ev_late[1], sb));
-            HIP_TRY(hipStreamWaitEvent(s, job->ev_late[1], 0));
-            HIP_TRY(hipEventRecord(job->ev[4], s));
-        } else {
-        if (late_own_stream) {   // (group B's index pass, then the run as ever)
-            uint32_t max_big = 0;
-            for (const IndexHost& x : job->index) max_big = std::max<uint32_t>(max_big, (uint32_t)x.list_big.size());
-            pgk_launch_index(job->d_reps_g + job->nA, n - job->nA, job->max_v, max_big, 0, s);
-            HIP_TRY(hipGetLastError());
-        }
-        if (job->any_legacy_prep) pgk_launch_prep(job->d_contigs, n, job->max_v, job->max_prep_w, job->max_prep_m4, job->tab, s);
-        if (job->any_split) pgk_launch_prep_split(job->d_contigs, n, job->max_sb, job->max_sm4, job->max_sw, job->tab, s);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(job->ev[1], s));
-        // (no k_compact: the column list is the index's, made when it was uploaded — the class stays in the timing table, at zero)
-        HIP_TRY(hipEventRecord(job->ev[2], s));
-        if (job->any_legacy_prep) pgk_launch_records(job->d_contigs, n, job->max_v, s);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(job->ev[3], s));
-        // phase 1 in pieces (all chains sparse lean chains; the job's own stream, not the pipelined first run): piece g, then on the
-        // second stream the partner columns of its chunks, the farthest chunk first — a segment resumes from a checkpoint of its own
-        // piece or from the last column of the piece before, both stored by then.  Piece 0's chunks stay with phase 2
-        pieces_now = job->n_pieces > 1u && s == job->stream && !late_own_stream;
-        if (pieces_now) {
-            const uint32_t G = job->piece_chunks;
-            if (job->hp_mask & ~PG_SWEEP_LEAN) pgk_launch_sweep(job->d_contigs, n, job->hp_mask & ~PG_SWEEP_LEAN, 1, s);   // (kernels of chains without columns: the launches they had)
-            for (uint32_t g = job->n_pieces; g-- > 0u;) {
-                pgk_launch_sweep_piece(job->d_contigs, n, G, g, s);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(job->ev_piece[g], s));
-                if (g == 0u) break;
-                HIP_TRY(hipStreamWaitEvent(job->stream2, job->ev_piece[g], 0));
-                for (uint32_t i = std::min((g + 1u) * G, job->n_chunks); i-- > g * G;) pgk_launch_refill(job->d_contigs, n, job->chunk_cols, i, 0, job->piece_refill_blocks, job->stream2);
-                HIP_TRY(hipGetLastError());
-            }
-        } else {
-            pgk_launch_sweep(job->d_contigs, n, job->hp_mask, 1, s);
-        }
-        pgk_launch_sweep_small(job->d_contigs, job->d_small, job->n_small, 1, 0, job->d_dump, s);
-        pgk_launch_sweep_smallx(job->d_contigs, job->d_smallx, job->n_smallx, 1, 0, job->d_dump, s);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(job->ev[4], s));
-        }
-        if (!job->chunked) {
-            pgk_launch_sweep(job->d_contigs, n, job->hp_mask, 2, s);
-            if (job->small_phase2) pgk_launch_sweep_small(job->d_contigs, job->d_small, job->n_small, 2, 0, job->d_dump, s);
-            if (job->smallx_phase2) pgk_launch_sweep_smallx(job->d_contigs, job->d_smallx, job->n_smallx, 2, 0, job->d_dump, s);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(job->ev[5], s));
-            pgk_launch_bins(job->d_contigs, n, job->max_v, job->bins_which, job->max_wide, s);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(job->ev[6], s));
-        } else {
-            // chunk i: store-only sweep on s -> ev_sweep -> k_post on stream2 -> ev_post; the sweep of chunk
-            // i + PG_SCRATCH_BUFS reuses scratch buffer i % PG_SCRATCH_BUFS and therefore waits for the posteriors of chunk i
-            hipStream_t s2 = job->stream2;
-            if (persist_now) {
-                // one launch each: the chunks are handed over on the device (DevContig::sync, zeroed above); k_post_loop must not
-                // start (and wait) before phase 1 has ended
-                HIP_TRY(hipStreamWaitEvent(s2, job->ev[4], 0));
-                pgk_launch_phase2_persistent(job->d_contigs, n, job->post_blocks, s, s2);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(job->ev_post[0], s2));
-                HIP_TRY(hipStreamWaitEvent(s, job->ev_post[0], 0));
-            } else {
-            // sparse phase 1: the refill of chunk i's partner columns (k_refill_lean) goes in front of k_post(i) on the second stream —
-            // beside the sweep of chunk i, behind the posteriors of chunk i - 1; it needs phase 1 ended, nothing else
-            if (job->sparse) HIP_TRY(hipStreamWaitEvent(s2, job->ev[4], 0));
-            // sparse phase 2: the chunk sweeps store their checkpoints into an area of their own and touch no scratch buffer — they
-            // wait for nothing.  The second stream forms chunk i's columns behind sweep i (k_refill_lean from those checkpoints) and
-            // then its posteriors: it writes and reads the scratch buffers alone, in order, so their rotation needs no event
-            if (job->sparse2) for (uint32_t i = 0; i < job->n_chunks; ++i) {
-                pgk_launch_sweep_chunk(job->d_contigs, n, job->hp_mask, i, s);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(job->ev_chunk[i], s));
-                if (!pieces_now || i < job->piece_chunks) pgk_launch_refill(job->d_contigs, n, job->chunk_cols, i, 0, 0u, s2);
-                HIP_TRY(hipStreamWaitEvent(s2, job->ev_chunk[i], 0));
-                pgk_launch_refill(job->d_contigs, n, job->chunk_cols, i, 1, 0u, s2);
-                pgk_launch_post(job->d_contigs, n, job->chunk_cols, i, s2);
-                HIP_TRY(hipGetLastError());
-                if (i + 1u == job->n_chunks) {
-                    HIP_TRY(hipEventRecord(job->ev_post[0], s2));
-                    HIP_TRY(hipStreamWaitEvent(s, job->ev_post[0], 0));
-                }
-            }
-            else for (uint32_t i = 0; i < job->n_chunks; ++i) {
-                const int b = (int)PG_SCR_BUF(i);
-                if (i >= PG_SCRATCH_BUFS) HIP_TRY(hipStreamWaitEvent(s, job->ev_post[b], 0));
-                pgk_launch_sweep_chunk(job->d_contigs, n, job->hp_mask, i, s);
-                pgk_launch_sweep_small(job->d_contigs, job->d_small, job->n_small, 3, i, job->d_dump, s);
-                pgk_launch_sweep_smallx(job->d_contigs, job->d_smallx, job->n_smallx, 3, i, job->d_dump, s);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(job->ev_sweep[b], s));
-                if (job->sparse) pgk_launch_refill(job->d_contigs, n, job->chunk_cols, i, 0, 0u, s2);
-                HIP_TRY(hipStreamWaitEvent(s2, job->ev_sweep[b], 0));
-                pgk_launch_post(job->d_contigs, n, job->chunk_cols, i, s2);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(job->ev_post[b], s2));
-            }
-            }
-            if (!persist_now && !job->sparse2) for (uint32_t q = 0; q < PG_SCRATCH_BUFS && q < job->n_chunks; ++q) HIP_TRY(hipStreamWaitEvent(s, job->ev_post[q], 0));
-            HIP_TRY(hipEventRecord(job->ev[5], s));  // "k_sweep_phase2" = all chunks incl. their posteriors
-            HIP_TRY(hipEventRecord(job->ev[6], s));  // (no k_bins in this mode)
-        }
-    } else if (job->max_v > 0) {
-        // run_genotyping == false: the variant records (what the Viterbi reads; the column list is the index's)
-        pgk_launch_prep(job->d_contigs, n, job->max_v, job->max_prep_w, job->max_prep_m4, job->tab, s);
-        HIP_TRY(hipGetLastError());
-    }
-    if (job->max_v > 0 && job->params.run_phasing) {
-        // Viterbi phasing (reference src/hmm.cpp:47-49): reads k_prep's records, independent of the sweep
-        if (!job->vit_tq_ready) {  // first run with this index: the transition probabilities of the kept columns
-            HIP_TRY(hipStreamSynchronize(s));
-            if (job->stream2) HIP_TRY(hipStreamSynchronize(job->stream2));
-            const int rc = viterbi_transitions(job, s, err, errlen);
-            if (rc != PG_OK) return rc;
-            job->vit_tq_ready = true;
-        }
-        HIP_TRY(hipEventRecord(job->ev_vit[0], s));
-        pgk_launch_viterbi(job->d_contigs, n, job->max_v, job->vit_bits, s);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(job->ev_vit[1], s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    if (job->stream2) HIP_TRY(hipStreamSynchronize(job->stream2));
-    if (job->max_v > 0 && job->params.run_genotyping) {
-        for (int i = 0; i < PG_N_KERNEL_CLASSES; ++i) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, job->ev[i], job->ev[i + 1]));
-            job->ms[i] = ms;
-        }
-    }
-    if (job->max_v > 0 && job->params.run_phasing) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, job->ev_vit[0], job->ev_vit[1]));
-        job->vit_ms = ms;
-    }
-    std::vector<uint32_t> ncols(n), errs(n);
-    {   // (column counts and the index-level kernels' error bits are per index contig)
-        const size_t ni = job->index.size();
-        std::vector<uint32_t> nc_ix(ni), err_ix(ni);
-        HIP_TRY(hipMemcpy(nc_ix.data(), job->d_ncols, sizeof(uint32_t) * ni, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(err_ix.data(), job->d_ixerr, sizeof(uint32_t) * ni, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(errs.data(), job->d_err, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < n; ++i) { ncols[i] = nc_ix[job->chains[i].index]; errs[i] |= err_ix[job->chains[i].index]; }
-    }
-    job->ran = true;
-    job->host_s[2] = now_s() - t_run;
-    for (uint32_t i = 0; i < n; ++i) {
-        job->chains[i].n_cols_host = ncols[i];
-        if (errs[i] & PG_DEVERR_ALLELE_NOT_FOUND) {
-            set_err(err, errlen, "chain %u: a path_allele value is not in the variant's allele list", i);
-            return PG_ERR_INVALID;
-        }
-        if (errs[i] & PG_DEVERR_TOO_MANY_ALLELES) {
-            set_err(err, errlen, "chain %u: a variant has more than %d alleles (device limit)", i, PG_MAX_ALLELES_PER_VARIANT);
-            return PG_ERR_UNSUPPORTED;
-        }
-        if (errs[i] & PG_DEVERR_SYNC_TIMEOUT) {
-            set_err(err, errlen, "chain %u: the persistent phase-2 kernels lost each other (a chunk flag did not arrive within 10 s); without PG_KERNELS=persist phase 2 takes a launch per chunk", i);
-            return PG_ERR_DEVICE;
-        }
-        if (errs[i] & PG_DEVERR_WIDE_FUSED) {
-            set_err(err, errlen, "chain %u: its only column carries more than %d alleles on the selected paths, which a fused job cannot genotype (PG_SWEEP_MODE=chunked)", i, PG_AMAX);
-            return PG_ERR_UNSUPPORTED;
-        }
-        if (errs[i] & PG_DEVERR_TOO_MANY_LOCAL) {
-            set_err(err, errlen, "chain %u: a column has more than %d distinct alleles on the selected paths (device limit)", i, PG_WIDE_MAX);
-            return PG_ERR_UNSUPPORTED;
-        }
-    }
     return PG_OK;
 }
 

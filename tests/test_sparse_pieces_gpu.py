@@ -241,3 +241,37 @@ def test_job_with_a_multiallelic_chain_keeps_the_single_launch(orc, monkeypatch)
     assert n_pieces == 1
     for bb, rr in zip(mixed, got):
         assert_parity(bb, rr, _oracle(orc, bb, args))
+
+
+def test_run_on_a_callers_stream_same_bits(panels, monkeypatch):
+    """Job.run(stream=...): pg_job_run takes phase 1 in pieces only on the job's OWN stream; on a caller's stream phase 1 is the
+    single launch and phase 2 refills every chunk.  One resident job, run on its own stream, on a caller's and on its own again:
+    the same bits each time — chunked (the job is planned in pieces), with PG_SWEEP_MODE unset (two chains: the planner's own
+    choice is the chunked job again) and fused, the one schedule that has no second stream."""
+    import torch
+    all_batches, all_refs = panels
+    pick = [COLUMNS.index(129), COLUMNS.index(254)]
+    batches, refs = [all_batches[i] for i in pick], [all_refs[i] for i in pick]
+    monkeypatch.setenv("PG_CHUNK_COLS", "64")
+    monkeypatch.setenv("PG_PIECE_CHUNKS", "1")
+    monkeypatch.delenv("PG_KERNELS", raising=False)
+    theirs = torch.cuda.Stream()
+    for mode in ("chunked", None, "fused"):
+        if mode:
+            monkeypatch.setenv("PG_SWEEP_MODE", mode)
+        else:
+            monkeypatch.delenv("PG_SWEEP_MODE", raising=False)
+        job = hmm.Job(batches, hmm.ProbabilityTable(*default_table_args()), hmm.make_params(*PARAMS))
+        assert job.plan().startswith("fused job" if mode == "fused" else "chunked job"), job.plan()
+        assert ("in 3 pieces" in job.plan()) == (mode != "fused"), job.plan()
+        job.run()
+        own = job.fetch_all()
+        job.run(stream=theirs.cuda_stream)
+        callers = job.fetch_all()
+        job.run()
+        own_again = job.fetch_all()
+        job.close()
+        for b, r, r2, r3, ref in zip(batches, own, callers, own_again, refs):
+            _same_bits(r, r2)
+            _same_bits(r, r3)
+            assert_parity(b, r, ref)
