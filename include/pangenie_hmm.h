@@ -235,6 +235,18 @@ int pg_sparse_chunk_stored_by_chain(uint32_t n_columns, uint32_t role, uint32_t 
  * beside the pieces behind it (pg_job_plan names the number of pieces; PG_PIECE_CHUNKS sets piece_chunks).  Returns 1 and
  * out = {lowest, highest column of the piece}, 0 when the role has no column that far from the phase boundary, -1 as above. */
 int pg_sparse_piece_range(uint32_t n_columns, uint32_t chunk_cols, uint32_t piece_chunks, uint32_t piece, uint32_t role, uint32_t out[2]);
+/* A job in pieces whose chains are all-biallelic prepares only the ENDS of its chains ahead of phase 1 — what the first `early`
+ * pieces read — and their MIDDLE on the second stream beside those pieces (pg_job_plan says which schedule a job takes;
+ * PG_PREP_EARLY_PIECES sets `early`, PG_KERNELS=prepahead keeps the whole preparation ahead).  The middle of a chain of n_columns
+ * when the job has n_pieces pieces: returns 1 and out_cols = {first column of the middle, first column behind it}; with
+ * col_variant (the n_columns ascending variant ids of the columns) also out_vars = the same for its n_variants variants — a
+ * variant goes with its column, one that is no column with the next column below it.  0: n_pieces < early + 1 (the preparation
+ * stays ahead), -1 as above.  Either output may be NULL. */
+int pg_prep_parts(uint32_t n_columns, uint32_t chunk_cols, uint32_t piece_chunks, uint32_t n_pieces, uint32_t early,
+                  const uint32_t* col_variant, uint32_t n_variants, uint32_t out_cols[2], uint32_t out_vars[2]);
+/* Item `u` of part 1 (the ends: what lies below the middle, then what lies above it) or part 2 (the middle) of n columns or
+ * variants whose middle is [lo, hi) — how the kernels of a part map their threads onto it; n: the part has no item u. */
+uint32_t pg_prep_part_member(uint32_t part, uint32_t lo, uint32_t hi, uint32_t n, uint32_t u);
 /* Elapsed milliseconds of the Viterbi kernels (run_phasing) of the LAST pg_job_run, hipEvents on the launch stream. */
 double pg_job_viterbi_ms(const pg_job* job);
 void pg_job_destroy(pg_job* job);

@@ -361,6 +361,36 @@ PG_HD inline bool pg_sparse_piece(uint32_t C, uint32_t role, uint32_t piece_cols
     else { out[0] = (uint32_t)(mid + d0); out[1] = (uint32_t)(mid + d1 - 1u); }
     return true;
 }
+// The preparation beside phase 1 (pg_job::prep_beside; pg_shim_run.cpp: prepare_in_parts): a job whose phase 1 runs in pieces
+// prepares only what its first E pieces read ahead of them — the ENDS of the chains — and the rest, the MIDDLE, on the second
+// stream beside those pieces.  The middle of a chain of C columns is one band around the phase boundary, W = (n_pieces - E)
+// piece_cols columns (a multiple of S) to either side of it: columns [out[0], out[1]).  Pieces 0 .. n_pieces - E - 1 of either
+// role lie inside it, every column of a later piece outside; W at least a half: the whole chain is middle.
+#define PG_PREP_EARLY_PIECES_DEFAULT 2u   // E (PG_PREP_EARLY_PIECES overrides it)
+PG_HD inline uint32_t pg_prep_band(uint32_t n_pieces, uint32_t E, uint32_t piece_cols) {   // W (n_pieces > E); capped: no half is wider
+    const unsigned long long W = (unsigned long long)(n_pieces - E) * piece_cols;
+    return W > 0xFFFFFFC0ull ? 0xFFFFFFC0u : (uint32_t)W;
+}
+PG_HD inline void pg_prep_middle(uint32_t C, uint32_t W, uint32_t out[2]) {
+    const uint32_t mid = C / 2u;
+    out[0] = mid - (mid < W ? mid : W);
+    out[1] = mid + (C - mid < W ? C - mid : W);
+}
+// ... and of its V variants: a variant goes with its column, a variant that is no column with the next column below it (the
+// variants below the first column: with column 0) — read off col_variant, which ascends, at the band's two edges: variants
+// [out[0], out[1]).  No column: the whole chain is middle.
+PG_HD inline void pg_prep_middle_variants(const uint32_t* col_variant, uint32_t C, uint32_t V, uint32_t W, uint32_t out[2]) {
+    uint32_t cr[2];
+    pg_prep_middle(C, W, cr);
+    out[0] = cr[0] == 0u ? 0u : col_variant[cr[0]];
+    out[1] = cr[1] >= C ? V : col_variant[cr[1]];
+}
+// item `u` of a part of N items (columns or variants) whose middle is [lo, hi): part 2 is the middle in order, part 1 the ends
+// — what lies below the middle, then what lies above it.  N: the part has no item u.
+PG_HD inline uint32_t pg_prep_part_item(uint32_t part, uint32_t lo, uint32_t hi, uint32_t N, uint32_t u) {
+    if (part == 2u) return u < hi - lo ? lo + u : N;
+    return u < lo ? u : (u < N - (hi - lo) ? u + (hi - lo) : N);
+}
 
 // ------------------------------------------------------------------------------------------------------------------
 //  Sparse phase 2 (DevContig::sparse2): the checkpoints go on in phase 1's step from the phase boundary — the forward role walks

@@ -206,6 +206,18 @@ struct pg_job {
     uint32_t piece_chunks = 0, n_pieces = 1;
     uint32_t piece_refill_blocks = 0;   // workgroups of a refill launched beside phase 1: fewer than in phase 2 (job_build)
     std::vector<hipEvent_t> ev_piece;   // one "piece done" event per piece
+    // ... whose chains are all k_prep_bi's (no k_prep, k_prep_m4, no lists, no split chains), n_pieces >= prep_early + 1: a run on
+    // the job's own stream prepares only the ENDS of the chains — what the first prep_early pieces read — ahead of phase 1, and the
+    // MIDDLE (pg_device.h: pg_prep_middle, half-width prep_W columns) on the second stream beside those pieces; `s` waits for
+    // ev_prep2 in front of piece n_pieces - prep_early - 1 (pg_shim_run.cpp: prepare_in_parts, phase1_in_pieces).
+    // (PG_KERNELS=prepahead: the whole preparation ahead; PG_PREP_EARLY_PIECES: prep_early.)
+    bool prep_beside = false;
+    uint32_t prep_early = 0, prep_W = 0;
+    // the grid extents of the two parts: the most variants / columns a chain has in part 1 ([0]) and in part 2 ([1]) — read off the
+    // column lists on the device by the first such run behind an index upload
+    bool prep_parts_ready = false;
+    uint32_t prep_max_v[2] = {0, 0}, prep_max_c[2] = {0, 0};
+    hipEvent_t ev_prep2 = nullptr;
     // The pipelined first run of a one-shot job (job_build with cache_arena: upload and run inside ONE call, the host arrays stay
     // valid): the inputs of the LONG chains (group A: the job's wall time) are uploaded first and their preparation + phase 1
     // start while the other chains' inputs (group B, most of the bytes) are still crossing PCIe; B's index pass, preparation and

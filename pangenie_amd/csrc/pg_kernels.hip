@@ -677,15 +677,18 @@ DEVI double row_last_f64(double v) {  // lane 15 of the row of 16 to all its lan
 }
 DEVI int row_last_i32(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x15F, 0xF, 0xF, true); }
 
-DEVI void prep_bi_unit(const DevContig& dc, const DevTable& tab, uint32_t unit) {
+// PART (k_prep_bi_part: chains that are all this kernel's, no list): the unit's objects are items of one part of the chain's
+// variants (pg_device.h: pg_prep_part_item) — `part`, of `npart` variants, the middle being variants [plo, phi)
+template <bool PART = false>
+DEVI void prep_bi_unit(const DevContig& dc, const DevTable& tab, uint32_t unit, uint32_t part = 0u, uint32_t npart = 0u, uint32_t plo = 0u, uint32_t phi = 0u) {
     const uint32_t lane = threadIdx.x & 63u, grp = lane >> 4, l = lane & 15u;
     // mixed chains (DevContig::prep_fast == 2) hand this kernel the LIST of its objects (prep_b): no rows idling along on
     // the objects of the other kernels
-    const uint32_t nobj = dc.prep_b ? dc.n_prep_b : dc.V;
+    const uint32_t nobj = PART ? npart : (dc.prep_b ? dc.n_prep_b : dc.V);
     const uint32_t pos = unit * 16u + (threadIdx.x >> 6) * 4u + grp;
     if (unit * 16u + (threadIdx.x >> 6) * 4u >= nobj) return;  // the whole wave is beyond the contig
     bool live = pos < nobj;   // (a row beyond the contig idles along: the ballots below are wave-wide)
-    const uint32_t v = dc.prep_b ? dc.prep_b[live ? pos : nobj - 1u] : pos;
+    const uint32_t v = PART ? pg_prep_part_item(part, plo, phi, dc.V, live ? pos : nobj - 1u) : (dc.prep_b ? dc.prep_b[live ? pos : nobj - 1u] : pos);
     const uint32_t vv = live ? v : dc.V - 1u;
     const uint32_t H = dc.H, HP = dc.HP;
     const uint32_t a0 = dc.allele_off[vv];  // two alleles
@@ -1188,12 +1191,15 @@ DEVI bool compact_records_only(const DevContig& dc, uint32_t C) {
     return ((dc.tri == 2u || dc.small == 2u || dc.smallx == 2u) && C >= 2u) || (dc.lean && dc.tri == 0u && dc.chunk_cols > 0u);
 }
 
-DEVI void records_unit(const DevContig& dc, uint32_t unit) {
+// PART (k_records_part: chains with compact records alone): the thread's column is an item of one part of the chain's columns
+// (pg_device.h: pg_prep_part_item) — `part`, the middle being columns [plo, phi)
+template <bool PART = false>
+DEVI void records_unit(const DevContig& dc, uint32_t unit, uint32_t part = 0u, uint32_t plo = 0u, uint32_t phi = 0u) {
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t C = *dc.n_cols;
     if (dc.split) return;   // the split path (pg_split.h): its records are written in column order by the emission kernels
     if (compact_records_only(dc, C) && !dc.smallx) {
-        const uint32_t c = unit * 256u + threadIdx.x;
+        const uint32_t c = PART ? pg_prep_part_item(part, plo, phi, C, unit * 256u + threadIdx.x) : unit * 256u + threadIdx.x;
         if (c >= C) return;
         const uint32_t v = dc.col_variant[c];
         const uint64_t* src = (const uint64_t*)(dc.vrec + (size_t)v * dc.RB);
@@ -1211,6 +1217,7 @@ DEVI void records_unit(const DevContig& dc, uint32_t unit) {
         out[3] = f64x2{__longlong_as_double((long long)E[PG_ESTRIDE + 1]), __longlong_as_double((long long)src[PG_REC_BITS1 / 8])};
         return;
     }
+    if constexpr (PART) return;   // (the job that launches a part has no chain with full records)
     // Full records: a wave takes 64 consecutive columns.  First every LANE forms the transition constants of ONE of them
     // (one wave per column had all 64 lanes evaluate the same exp(): 17.7 ms for 31.5 M columns of 16-path chains), then
     // the wave copies the 64 records into column order, the four constants of a column coming out of its LDS slice.
@@ -7078,6 +7085,29 @@ static void launch_sweep(const DevContig* d_contigs, uint32_t n_contigs, uint32_
                                from64 ? 64u : 256u);
     }
 }
+// ------------------------------------------------------------------------------------------
+//  The preparation in two PARTS (pg_device.h: pg_prep_middle; pg_shim_run.cpp: prepare_in_parts) of a job that runs phase 1 in
+//  pieces and whose chains are all k_prep_bi's, without lists, with compact records alone: part 1 = the ends of every chain, part
+//  2 = its middle, W = the band's half-width in columns.  The bodies are k_prep_bi's and the compact branch of k_records; a unit's
+//  objects / a thread's column are items of the part.  (Behind every other kernel of the unit, so that none of them moves.)
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_prep_bi_part(const DevContig* __restrict__ contigs, DevTable tab, uint32_t part, uint32_t W) {
+    const DevContig& dc = contigs[blockIdx.y];
+    if (dc.prep_fast != 1u || dc.split || dc.prep_b || dc.V == 0u) return;
+    uint32_t vr[2];
+    pg_prep_middle_variants(dc.col_variant, *dc.n_cols, dc.V, W, vr);
+    const uint32_t npart = part == 2u ? vr[1] - vr[0] : dc.V - (vr[1] - vr[0]);
+#pragma unroll 1
+    for (uint32_t r = 0; r < (uint32_t)PG_VREP; ++r) prep_bi_unit<true>(dc, tab, blockIdx.x * (uint32_t)PG_VREP + r, part, npart, vr[0], vr[1]);
+}
+__global__ __launch_bounds__(256) void k_records_part(const DevContig* __restrict__ contigs, uint32_t part, uint32_t W) {
+    const DevContig& dc = contigs[blockIdx.y];
+    if (dc.V == 0u) return;
+    uint32_t cr[2];
+    pg_prep_middle(*dc.n_cols, W, cr);
+    records_unit<true>(dc, blockIdx.x, part, cr[0], cr[1]);
+}
+
 extern "C" {
 
 // max_w = the longest walk of k_prep over the chains (a chain's list of objects, or all its variants), max_m4 = the longest list of k_prep_m4
@@ -7115,6 +7145,14 @@ void pgk_launch_prep_split(const DevContig* d_contigs, uint32_t n_contigs, uint3
 void pgk_launch_records(const DevContig* d_contigs, uint32_t n_contigs, uint32_t max_v, hipStream_t s) {
     dim3 grid((max_v + 255) / 256, n_contigs);   // 256 columns per block either way (a thread or a quarter of a wave's 64 each)
     hipLaunchKernelGGL(k_records, grid, dim3(256), 0, s, d_contigs);
+}
+// prep and records of one part (1: the ends, 2: the middle of half-width W) of every chain: max_pv / max_pc = the most variants /
+// columns a chain has in that part
+void pgk_launch_prep_part(const DevContig* d_contigs, uint32_t n_contigs, uint32_t part, uint32_t W, uint32_t max_pv, DevTable tab, hipStream_t s) {
+    if (max_pv) hipLaunchKernelGGL(k_prep_bi_part, dim3((uint32_t)(((unsigned long long)max_pv + 16 * PG_VREP - 1) / (16 * PG_VREP)), n_contigs), dim3(256), 0, s, d_contigs, tab, part, W);
+}
+void pgk_launch_records_part(const DevContig* d_contigs, uint32_t n_contigs, uint32_t part, uint32_t W, uint32_t max_pc, hipStream_t s) {
+    if (max_pc) hipLaunchKernelGGL(k_records_part, dim3((max_pc + 255u) / 256u, n_contigs), dim3(256), 0, s, d_contigs, part, W);
 }
 // which: the PG_BINS_* bits of pg_launch.h
 void pgk_launch_bins(const DevContig* d_contigs, uint32_t n_contigs, uint32_t max_v, uint32_t which, uint32_t max_wide, hipStream_t s) {

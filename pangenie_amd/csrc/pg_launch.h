@@ -98,6 +98,10 @@ void pgk_launch_compact(const DevContig* d_contigs, uint32_t n_contigs, hipStrea
 void pgk_launch_index(const DevContig* d_reps, uint32_t n_index, uint32_t max_v, uint32_t max_big, int any_split, hipStream_t s);
 void pgk_launch_prep_split(const DevContig* d_contigs, uint32_t n_contigs, uint32_t max_b, uint32_t max_m4, uint32_t max_w, DevTable tab, hipStream_t s);
 void pgk_launch_records(const DevContig* d_contigs, uint32_t n_contigs, uint32_t max_v, hipStream_t s);
+// k_prep_bi_part / k_records_part: one part of every chain (1: the ends, 2: the middle — pg_device.h: pg_prep_middle, W = the
+// band's half-width in columns); max_pv / max_pc = the most variants / columns a chain has in that part (0: no launch)
+void pgk_launch_prep_part(const DevContig* d_contigs, uint32_t n_contigs, uint32_t part, uint32_t W, uint32_t max_pv, DevTable tab, hipStream_t s);
+void pgk_launch_records_part(const DevContig* d_contigs, uint32_t n_contigs, uint32_t part, uint32_t W, uint32_t max_pc, hipStream_t s);
 void pgk_launch_bins(const DevContig* d_contigs, uint32_t n_contigs, uint32_t max_v, uint32_t which, uint32_t max_wide, hipStream_t s);
 void pgk_launch_sweep(const DevContig* d_contigs, uint32_t n_contigs, uint32_t hp_mask, int phase, hipStream_t s);
 void pgk_launch_sweep_piece(const DevContig* d_contigs, uint32_t n_contigs, uint32_t piece_chunks, uint32_t piece, hipStream_t s);

@@ -343,6 +343,7 @@ extern "C" void pg_job_destroy(pg_job* job) {
         for (int q = 0; q < (int)PG_SCRATCH_BUFS; ++q) { hipEventDestroy(job->ev_sweep[q]); hipEventDestroy(job->ev_post[q]); }
     for (hipEvent_t e : job->ev_chunk) hipEventDestroy(e);
     for (hipEvent_t e : job->ev_piece) hipEventDestroy(e);
+    if (job->ev_prep2) hipEventDestroy(job->ev_prep2);
     if (job->arena) {
         if (job->cache_arena) g_pool.put(job->device, job->arena, job->arena_bytes);
         else hipFree(job->arena);
@@ -460,6 +461,7 @@ int upload_inputs(pg_job* job, const pg_contig_batch* batches, const std::vector
     } while (0)
     if (with_index) {
         record_plans_changed(job);   // (new allele ids: the record plans are checked against them again)
+        job->prep_parts_ready = false;   // (a new column list: the extents of a preparation in parts are read again)
         for (size_t i = 0; i < job->index.size(); ++i) {
             const pg_contig_batch& b = batches[i];
             IndexHost& x = job->index[i];
@@ -640,11 +642,13 @@ int upload_inputs(pg_job* job, const pg_contig_batch* batches, const std::vector
 //   nopieces            phase 1 of a job whose chains are all sparse lean chains is one launch, and every chunk's partner columns are
 //                       refilled in phase 2 (instead of a launch per piece with the refills of all pieces but the last beside phase 1)
 //                       — cross-check
-//   nosplit             the 16-path chains of fused jobs prepare every variant per sample (k_prep*, k_records, k_bins_lean2 / _x) instead of
+//   prepahead           a job that runs phase 1 in pieces prepares every variant ahead of phase 1 (instead of the ends of the chains ahead
+//                       and their middle on the second stream beside the first pieces: pg_job::prep_beside) — cross-check
+//   nosplit           the 16-path chains of fused jobs prepare every variant per sample (k_prep*, k_records, k_bins_lean2 / _x) instead of
 //                       taking the split path (pg_split.h)
 struct KernelChoice {
     bool general = false, generic = false, nolean2 = false, notri = false, nocls4 = false, prepwave = false, fullcols = false, nosmall2 = false, nosplit = false;
-    bool persist = false, noleanx2 = false, nowidef = false, nosparse = false, nosparse2 = false, nopieces = false;
+    bool persist = false, noleanx2 = false, nowidef = false, nosparse = false, nosparse2 = false, nopieces = false, prepahead = false;
     int leanx = -1, small = -1;   // -1: by the job, 0 / 1: forced
     std::string unknown;          // a token this list does not know
 };
@@ -666,6 +670,7 @@ KernelChoice kernel_choice() {
         else if (tok == "nosparse") k.nosparse = true;
         else if (tok == "nosparse2") k.nosparse2 = true;
         else if (tok == "nopieces") k.nopieces = true;
+        else if (tok == "prepahead") k.prepahead = true;
         else if (tok == "persist") k.persist = true; else if (tok == "nopersist") k.persist = false;
         else if (!tok.empty()) k.unknown = tok;   // (a typo would quietly test the default path against itself: job creation fails)
         tok.clear();
@@ -1109,6 +1114,20 @@ std::vector<ChainKernels> choose_chain_kernels(pg_job* job, const BuildArgs& a) 
         job->bins_which |= kBins[k.bins].bit | kBins[k.bins_one].bit | kBins[k.bins_wide].bit;
         if (a.params.run_phasing) job->vit_bits |= x.HP == 16 ? 1u : (x.HP == 32 ? 2u : 4u);
     }
+    // the preparation beside phase 1 (pg_job::prep_beside): phase 1 in pieces, k_prep_bi the only emission kernel of the job — every
+    // chain with variants all-biallelic without lists, none split —, and a piece left behind the E prepared ahead
+    job->prep_beside = false; job->prep_early = 0; job->prep_W = 0; job->prep_parts_ready = false;
+    if (job->n_pieces > 1u && !kc.prepahead) {
+        bool only_bi = true;
+        for (size_t c = 0; c < kernels.size(); ++c) if (job->index[a.specs[c].index].V && kernels[c].prep != PREP_BI) only_bi = false;
+        uint32_t E = PG_PREP_EARLY_PIECES_DEFAULT;
+        if (const char* e = getenv("PG_PREP_EARLY_PIECES")) { const long v = strtol(e, nullptr, 0); if (v >= 1 && v <= 0xFFFF) E = (uint32_t)v; }
+        if (only_bi && job->n_pieces >= E + 1u) {
+            job->prep_beside = true;
+            job->prep_early = E;
+            job->prep_W = pg_prep_band(job->n_pieces, E, job->piece_chunks * job->chunk_cols);
+        }
+    }
     return kernels;
 }
 
@@ -1146,7 +1165,11 @@ std::string plan_text(const pg_job* job, const BuildArgs& a, const std::vector<C
         for (auto& g : groups) if (g.text == text) { g.count += 1; found = true; break; }
         if (!found) groups.push_back({text, 1});
     }
-    std::string out = std::string(job->chunked ? "chunked" : "fused") + " job, " + std::to_string(kernels.size()) + " chain(s)" + (a.params.run_phasing ? ", run_phasing (k_viterbi)" : "") + "\n";
+    std::string out = std::string(job->chunked ? "chunked" : "fused") + " job, " + std::to_string(kernels.size()) + " chain(s)" + (a.params.run_phasing ? ", run_phasing (k_viterbi)" : "") +
+                      (job->max_v == 0 || !a.params.run_genotyping ? std::string()
+                       : job->prep_beside ? ", prep in parts: the ends of the chains ahead of the sweeps, their middle beside the first " + std::to_string(job->prep_early) + " of " +
+                                            std::to_string(job->n_pieces) + " pieces (k_prep_bi_part, k_records_part; on the job's own stream)"
+                                          : std::string(", prep ahead of the sweeps")) + "\n";   // (no word of a phase here: callers pick a chain group's line by those)
     for (const auto& g : groups) out += "  " + std::to_string(g.count) + " x " + g.text + "\n";
     return out;
 }
@@ -1338,6 +1361,7 @@ int create_device_objects(pg_job* job, char* err, size_t errlen) {
             if ((he = hipEventCreateWithFlags(&e, hipEventDisableTiming)) != hipSuccess) return hip_fail(err, errlen, "hipEventCreate", he);
             job->ev_piece.push_back(e);
         }
+        if (job->prep_beside && (he = hipEventCreateWithFlags(&job->ev_prep2, hipEventDisableTiming)) != hipSuccess) return hip_fail(err, errlen, "hipEventCreate", he);
     }
     return PG_OK;
 }
@@ -1988,6 +2012,24 @@ extern "C" int pg_sparse_piece_range(uint32_t n_columns, uint32_t chunk_cols, ui
     if (!pg_sparse_piece(n_columns, role, piece_chunks * chunk_cols, piece, r)) return 0;
     if (out) { out[0] = r[0]; out[1] = r[1]; }
     return 1;
+}
+// ... of the preparation in parts (pg_prep_middle, pg_prep_middle_variants): the middle's columns and variants, [lo, hi) each
+extern "C" int pg_prep_parts(uint32_t n_columns, uint32_t chunk_cols, uint32_t piece_chunks, uint32_t n_pieces, uint32_t early,
+                             const uint32_t* col_variant, uint32_t n_variants, uint32_t out_cols[2], uint32_t out_vars[2]) {
+    if (chunk_cols == 0u || chunk_cols % PG_LEAN_SPARSE != 0u || piece_chunks == 0u || (unsigned long long)piece_chunks * chunk_cols > 0xFFFFFFFFull) return -1;
+    if (early == 0u || n_pieces == 0u || n_columns > n_variants) return -1;
+    if (n_pieces < early + 1u) return 0;
+    const uint32_t W = pg_prep_band(n_pieces, early, piece_chunks * chunk_cols);
+    if (out_cols) pg_prep_middle(n_columns, W, out_cols);
+    if (out_vars) {
+        if (!col_variant && n_columns) return -1;
+        pg_prep_middle_variants(col_variant, n_columns, n_variants, W, out_vars);
+    }
+    return 1;
+}
+extern "C" uint32_t pg_prep_part_member(uint32_t part, uint32_t lo, uint32_t hi, uint32_t n, uint32_t u) {
+    if ((part != 1u && part != 2u) || lo > hi || hi > n) return n;
+    return pg_prep_part_item(part, lo, hi, n, u);
 }
 // ... and of the sparse phase 2 (pg_sparse2_*): segment j of chunk `chunk`; out = {checkpoint, lowest column, highest column}
 extern "C" int pg_sparse_chunk_segment(uint32_t n_columns, uint32_t chunk_cols, uint32_t chunk, uint32_t role, uint32_t j, uint32_t out[3]) {

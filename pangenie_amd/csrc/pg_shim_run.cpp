@@ -1,5 +1,6 @@
 // pg_shim_run.cpp — pg_job_run: the run schedule of a job, as a list of named steps (DESIGN.md §4 "The run schedule, step by
-// step" maps each step to the section that explains it).  A run is: settle a pipelined upload, zero the per-run block, prepare,
+// step" maps each step to the section that explains it).  A run is: settle a pipelined upload, zero the per-run block, prepare
+// (whole, or in parts: the ends of the chains ahead, their middle on the second stream beside the first pieces of phase 1),
 // phase 1, ONE of four phase 2s (fused / persistent / sparse / chunks), the Viterbi, one wait, timings and error bits.  Every
 // step says what it reads of the job and which streams it touches; `s` is the run's stream (the caller's, or the job's own),
 // "second" is pg_job::stream2.  Which schedule a job takes was decided when it was built (job_build, pg_shim.cpp); a run adds
@@ -54,6 +55,7 @@ struct RunPlan {
     bool index_b_due = false;   // a pipelined upload was settled for a caller's stream: group B's index pass is made up in `prepare`
     bool persist_now = false;   // this run's phase 2 is the persistent one
     bool pieces_now = false;    // this run's phase 1 went in pieces: the second stream has refilled the partner columns of all chunks but piece 0's
+    bool prep_beside_now = false;   // this run prepares the middle of the chains on the second stream, beside the first pieces of phase 1
 };
 
 // Group B's copy threads are joined and their return codes looked at.  Reads late_threads, late_rc; touches no stream.
@@ -130,14 +132,88 @@ int prepare(pg_job* job, hipStream_t s, bool index_b_due, char* err, size_t errl
     return PG_OK;
 }
 
+// The grid extents of the two parts of a preparation in parts (pg_job::prep_beside): the most variants / columns a chain has in
+// its ends and in its middle, from the column counts and the two column-list entries at the edges of every index contig's middle
+// (pg_device.h: pg_prep_middle, pg_prep_middle_variants).  They hang on the index alone: read once per uploaded index, by the
+// first such run — nothing is in flight on either stream then (an upload and a run both return synchronised).
+// Reads prep_W, d.n_cols, d.col_variant; touches no stream (blocking copies).
+int prep_part_extents(pg_job* job, char* err, size_t errlen) {
+    if (job->prep_parts_ready) return PG_OK;
+    std::vector<char> done(job->index.size(), 0);
+    uint32_t mv[2] = {0, 0}, mc[2] = {0, 0};
+    for (const ChainHost& ch : job->chains) {
+        const IndexHost& x = job->index[ch.index];
+        if (x.V == 0 || done[ch.index]) continue;
+        done[ch.index] = 1;
+        uint32_t C = 0, cr[2], vr[2] = {0u, x.V};
+        HIP_TRY(hipMemcpy(&C, ch.d.n_cols, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (C > x.V) { set_err(err, errlen, "index contig %u: bad column count", ch.index); return PG_ERR_DEVICE; }
+        pg_prep_middle(C, job->prep_W, cr);
+        if (cr[0] > 0u) HIP_TRY(hipMemcpy(&vr[0], ch.d.col_variant + cr[0], sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (cr[1] < C) HIP_TRY(hipMemcpy(&vr[1], ch.d.col_variant + cr[1], sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (vr[0] > vr[1] || vr[1] > x.V) { set_err(err, errlen, "index contig %u: bad column list", ch.index); return PG_ERR_DEVICE; }
+        mc[0] = std::max(mc[0], C - (cr[1] - cr[0])); mc[1] = std::max(mc[1], cr[1] - cr[0]);
+        mv[0] = std::max(mv[0], x.V - (vr[1] - vr[0])); mv[1] = std::max(mv[1], vr[1] - vr[0]);
+    }
+    for (int p = 0; p < 2; ++p) { job->prep_max_v[p] = mv[p]; job->prep_max_c[p] = mc[p]; }
+    job->prep_parts_ready = true;
+    return PG_OK;
+}
+
+// The preparation in parts (pg_job::prep_beside: phase 1 in pieces, k_prep_bi the job's only emission kernel; this run on the
+// job's own stream, no pipelined upload in flight).  Part 1, the ENDS of the chains — every column farther than prep_W from the
+// phase boundary, all that the first prep_early pieces step through — on `s`, in front of phase 1 as ever; part 2, the MIDDLE,
+// on the second stream beside those pieces, behind ev[3] — that is behind the per-run zeroing (ev[0]), which clears the error bits
+// part 2 writes, AND behind part 1: started at ev[0], part 2's forty thousand workgroups took the chip from part 1's thousand, and
+// the first piece waited 0.7 – 2.3 ms for them instead of 0.1 (profiles/r17_prep_beside_phase1.txt).  ev_prep2 says part 2 is done.
+//  * Who reads what part 2 writes (vrec, vpair, kept, allele_present; the compact records, frec): the pieces from
+//    n_pieces - prep_early - 1 down, the chunk sweeps and the Viterbi on `s` — all behind the wait for ev_prep2 in phase1_in_pieces;
+//    every refill, k_post and part 2 itself on the second stream — in stream order behind part 2.
+//  * Read-ahead: a piece fetches compact records up to two 64-column blocks past its last column (LeanRecs::fetch; parked and
+//    expanded in LDS) and reads the record and the emissions of the column behind its last one into registers a step ahead — but a
+//    forward step's column t is formed from the records of columns <= t and a backward step's from those of columns >= t
+//    (lean_forward / lean_backward: `cur`, `ec`; what is read ahead is used by the NEXT step alone, and the zero test that ends a
+//    piece reads its last column's sums).  The last column of the last early piece is an end column, so no record of the middle
+//    is consumed before the wait: the ends need no widening.  The refills behind the early pieces re-run columns of those pieces.
+//  * Two runs of a resident job: part 2 of run n + 1 must not overtake the readers of run n (k_post, the Viterbi).  pg_job_run
+//    returns with both streams synchronised — that orders the runs; a run that failed half way leaves k_post in front of part 2 in
+//    the second stream's own order, and the Viterbi in front of ev[0] on `s`.
+// The k_prep and k_records classes (ev[1 .. 3]) time part 1 alone; part 2 runs inside the span of the phase-1 class.
+// Reads prep_W, prep_max_v / _c, tab, ev_prep2; streams: s (part 1), second (part 2; waits for ev[3]).  Records ev[1 .. 3].
+int prepare_in_parts(pg_job* job, hipStream_t s, char* err, size_t errlen) {
+    const uint32_t n = (uint32_t)job->chains.size(), W = job->prep_W;
+    hipStream_t s2 = job->stream2;
+    pgk_launch_prep_part(job->d_contigs, n, 1u, W, job->prep_max_v[0], job->tab, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(job->ev[1], s));
+    HIP_TRY(hipEventRecord(job->ev[2], s));
+    pgk_launch_records_part(job->d_contigs, n, 1u, W, job->prep_max_c[0], s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(job->ev[3], s));
+    HIP_TRY(hipStreamWaitEvent(s2, job->ev[3], 0));
+    pgk_launch_prep_part(job->d_contigs, n, 2u, W, job->prep_max_v[1], job->tab, s2);
+    pgk_launch_records_part(job->d_contigs, n, 2u, W, job->prep_max_c[1], s2);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(job->ev_prep2, s2));
+    return PG_OK;
+}
+
 // phase 1 in pieces (all chains sparse lean chains; the job's own stream, not the pipelined first run): piece g, then on the
 // second stream the partner columns of its chunks, the farthest chunk first — a segment resumes from a checkpoint of its own
 // piece or from the last column of the piece before, both stored by then.  Piece 0's chunks stay with phase 2
-// Reads n_pieces, piece_chunks, n_chunks, chunk_cols, piece_refill_blocks, hp_mask, ev_piece; streams: s (pieces), second (refills).
-int phase1_in_pieces(pg_job* job, hipStream_t s, char* err, size_t errlen) {
+// `beside` (prepare_in_parts): the middle of the chains is being prepared on the second stream — `s` waits for it (ev_prep2) in front
+// of piece n_pieces - prep_early - 1, the first that can step into the middle and the first in which a chain without ends starts;
+// the refills behind the earlier pieces are behind part 2 in the second stream's order.
+// Reads n_pieces, piece_chunks, n_chunks, chunk_cols, piece_refill_blocks, hp_mask, ev_piece, prep_early, ev_prep2; streams: s (pieces), second (refills).
+int phase1_in_pieces(pg_job* job, hipStream_t s, bool beside, char* err, size_t errlen) {
     const uint32_t n = (uint32_t)job->chains.size(), G = job->piece_chunks;
-    if (job->hp_mask & ~PG_SWEEP_LEAN) pgk_launch_sweep(job->d_contigs, n, job->hp_mask & ~PG_SWEEP_LEAN, 1, s);   // (kernels of chains without columns: the launches they had)
+    const uint32_t others = job->hp_mask & ~PG_SWEEP_LEAN;   // (kernels of chains without columns: the launches they had — behind the wait, like every reader)
+    if (others && !beside) pgk_launch_sweep(job->d_contigs, n, others, 1, s);
     for (uint32_t g = job->n_pieces; g-- > 0u;) {
+        if (beside && g + 1u + job->prep_early == job->n_pieces) {
+            HIP_TRY(hipStreamWaitEvent(s, job->ev_prep2, 0));
+            if (others) pgk_launch_sweep(job->d_contigs, n, others, 1, s);
+        }
         pgk_launch_sweep_piece(job->d_contigs, n, G, g, s);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(job->ev_piece[g], s));
@@ -155,7 +231,7 @@ int phase1_in_pieces(pg_job* job, hipStream_t s, char* err, size_t errlen) {
 int phase1(pg_job* job, hipStream_t s, RunPlan* plan, char* err, size_t errlen) {
     const uint32_t n = (uint32_t)job->chains.size();
     plan->pieces_now = job->n_pieces > 1u && s == job->stream;
-    if (plan->pieces_now) STEP(phase1_in_pieces(job, s, err, errlen));
+    if (plan->pieces_now) STEP(phase1_in_pieces(job, s, plan->prep_beside_now, err, errlen));
     else pgk_launch_sweep(job->d_contigs, n, job->hp_mask, 1, s);
     pgk_launch_sweep_small(job->d_contigs, job->d_small, job->n_small, 1, 0, job->d_dump, s);
     pgk_launch_sweep_smallx(job->d_contigs, job->d_smallx, job->n_smallx, 1, 0, job->d_dump, s);
@@ -386,13 +462,18 @@ extern "C" int pg_job_run(pg_job* job, void* stream_, char* err, size_t errlen) 
     STEP(settle_late_for_callers_stream(job, s, &plan, err, errlen));
     plan.persist_now = job->persist && plan.genotype && streams_concurrent(job, s);   // (may replace stream2)
     if (job->persist && plan.genotype) (plan.persist_now ? job->persist_runs : job->persist_fallbacks) += 1;
+    // (the preparation in parts goes with phase 1 in pieces on the job's own stream; the pipelined first run and a caller's stream
+    //  keep the whole preparation ahead)
+    plan.prep_beside_now = plan.genotype && job->prep_beside && s == job->stream && !job->late_pending;
+    if (plan.prep_beside_now) STEP(prep_part_extents(job, err, errlen));
     HIP_TRY(hipMemsetAsync(job->zero_base, 0, job->zero_bytes, s));
     if (plan.genotype) {
         HIP_TRY(hipEventRecord(job->ev[0], s));
         if (job->late_pending) {
             STEP(first_run_pipelined(job, s, err, errlen));
         } else {
-            STEP(prepare(job, s, plan.index_b_due, err, errlen));
+            if (plan.prep_beside_now) STEP(prepare_in_parts(job, s, err, errlen));
+            else STEP(prepare(job, s, plan.index_b_due, err, errlen));
             STEP(phase1(job, s, &plan, err, errlen));
         }
         if (!job->chunked) STEP(phase2_fused(job, s, err, errlen));
