@@ -235,6 +235,15 @@ int pg_sparse_chunk_stored_by_chain(uint32_t n_columns, uint32_t role, uint32_t 
  * beside the pieces behind it (pg_job_plan names the number of pieces; PG_PIECE_CHUNKS sets piece_chunks).  Returns 1 and
  * out = {lowest, highest column of the piece}, 0 when the role has no column that far from the phase boundary, -1 as above. */
 int pg_sparse_piece_range(uint32_t n_columns, uint32_t chunk_cols, uint32_t piece_chunks, uint32_t piece, uint32_t role, uint32_t out[2]);
+/* The column records of such a launch reach the kernel in blocks of 64, two of them in a ring; the launch numbers its steps so
+ * that its groups of 64 steps (63 store-free, one storing) begin at a multiple of 64, and a group parks and expands the next
+ * block at two fixed steps.  The numbering of a launch, for tests: form 0 = phase 1 in one launch, 1 = piece `arg` of phase 1,
+ * 2 = chunk sweep `arg` of phase 2.  Returns 1 and out = {column of the first step, number of steps, steps in front of the first
+ * group, number of the first step, step of a group that parks a block, step of a group that expands it}; 0: the launch has no
+ * step; -1 as above. */
+int pg_lean_ring_schedule(uint32_t n_columns, uint32_t chunk_cols, uint32_t piece_chunks, uint32_t role, uint32_t form, uint32_t arg, uint32_t out[6]);
+/* Byte offset, inside the ring, of the 256-byte image that holds everything a step reads of record number `record`. */
+uint32_t pg_lean_ring_image_offset(uint32_t record);
 /* A job in pieces whose chains are all-biallelic prepares only the ENDS of its chains ahead of phase 1 — what the first `early`
  * pieces read — and their MIDDLE on the second stream beside those pieces (pg_job_plan says which schedule a job takes;
  * PG_PREP_EARLY_PIECES sets `early`, PG_KERNELS=prepahead keeps the whole preparation ahead).  The middle of a chain of n_columns

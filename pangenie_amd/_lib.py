@@ -159,6 +159,10 @@ def _bind_hip(lib):
     lib.pg_sparse_chunk_stored_by_chain.restype = C.c_int
     lib.pg_sparse_piece_range.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p]
     lib.pg_sparse_piece_range.restype = C.c_int
+    lib.pg_lean_ring_schedule.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p]
+    lib.pg_lean_ring_schedule.restype = C.c_int
+    lib.pg_lean_ring_image_offset.argtypes = [C.c_uint32]
+    lib.pg_lean_ring_image_offset.restype = C.c_uint32
     lib.pg_prep_parts.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint32, u32p, u32p]
     lib.pg_prep_parts.restype = C.c_int
     lib.pg_prep_part_member.argtypes = [C.c_uint32] * 5
@@ -316,7 +320,7 @@ HIP_ABI_SYMBOLS = [
     "pg_job_record_gl_ms", "pg_record_gl_from_bins", "pg_gl_from_values", "pg_gl_text",
     "pg_job_record_plan_strided", "pg_job_record_first", "pg_job_fetch_record_calls_packed", "pg_job_fetch_record_gl_packed",
     "pg_sparse_segment", "pg_sparse_stored_by_chain", "pg_sparse_chunk_segment", "pg_sparse_chunk_stored_by_chain", "pg_sparse_piece_range",
-    "pg_prep_parts", "pg_prep_part_member",
+    "pg_prep_parts", "pg_prep_part_member", "pg_lean_ring_schedule", "pg_lean_ring_image_offset",
 ]
 
 

@@ -361,6 +361,54 @@ PG_HD inline bool pg_sparse_piece(uint32_t C, uint32_t role, uint32_t piece_cols
     else { out[0] = (uint32_t)(mid + d0); out[1] = (uint32_t)(mid + d1 - 1u); }
     return true;
 }
+// The record ring of a sparse lean launch (pg_kernels.hip: LeanRecs, lean_forward / lean_backward in their SPARSE form).  The
+// records of a launch are numbered along the role's direction and live in LDS in two blocks of S; step number n reads records
+// n + 1 and n + 2, parks block (n + 4) / S when n + 4 is a multiple of S and expands block (n + 3) / S when n + 3 is.  A sparse
+// launch runs `lead` storing steps (at most S - 1), then groups of S steps (S - 1 store-free, one storing), then — a chunk sweep
+// of phase 3 — a tail.  Its first step takes the number pg_lean_ring_first(lead) instead of 0, so that the first step of every
+// group has a number that is a multiple of S: inside a group the block is parked at step PG_LEAN_RING_PARK and expanded at step
+// PG_LEAN_RING_EXPAND, the same in every group, and the other steps of a group are compiled without the two tests.  The records
+// in front of the launch's first one that the numbering adds are fetched clamped and never read.  A first number of
+// PG_LEAN_RING_PARK + 1 or more starts behind the step that would park block 1: the launch parks and expands it up front.
+// What a step reads of record `rel` lies in ONE image of PG_LEAN_IMAGE bytes (LeanShared::img: the compact record, its pair table
+// and its pair bytes at fixed offsets), the ring of 2 S images in record order: pg_lean_ring_image is the image's byte offset.
+#define PG_LEAN_IMAGE 256u
+PG_HD inline uint32_t pg_lean_ring_image(uint32_t rel) { return (rel * PG_LEAN_IMAGE) & (2u * PG_LEAN_SPARSE * PG_LEAN_IMAGE - 1u); }
+#define PG_LEAN_RING_PARK (PG_LEAN_SPARSE - 4u)
+#define PG_LEAN_RING_EXPAND (PG_LEAN_SPARSE - 3u)
+PG_HD inline uint32_t pg_lean_ring_first(uint32_t lead) { return (PG_LEAN_SPARSE - lead % PG_LEAN_SPARSE) % PG_LEAN_SPARSE; }
+// steps of a sparse launch in front of its first group: `c0` = column of the launch's first step; `end` = forward, one past the
+// column of its last step (the steps run c0 .. end - 1); backward, the column of its last step (c0 down to end).  Phase 3 starts
+// on a group.
+PG_HD inline uint32_t pg_lean_ring_lead(uint32_t C, uint32_t role, uint32_t phase, uint32_t c0, uint32_t end) {
+    if (phase != 1u) return 0u;
+    if (role == 0u) { const uint32_t ck0 = end ? (end - 1u) % PG_LEAN_SPARSE : 0u; return c0 <= ck0 ? ck0 - c0 + 1u : 0u; }
+    const unsigned long long ckh = (unsigned long long)(C / 2u) + (unsigned long long)pg_sparse_segments(C, 1u) * PG_LEAN_SPARSE;   // the first checkpoint on the way down
+    return c0 >= ckh ? (uint32_t)(c0 - ckh) + 1u : 0u;
+}
+// A sparse launch as the kernels walk it: phase 1 (chunk = 0: the whole half; G << 16 | g: piece g of G chunks) or a chunk sweep
+// of phase 3 (chunk = its number).  false: no step.  out = {column of the first step, number of steps, lead}
+PG_HD inline bool pg_lean_ring_launch(uint32_t C, uint32_t role, uint32_t phase, uint32_t K, uint32_t chunk, uint32_t out[3]) {
+    const unsigned long long mid = C / 2u;
+    if (role == 0u) {
+        unsigned long long lo = phase == 1u ? 0u : mid, hi = phase == 1u ? mid : C;
+        if (phase == 3u) { lo = mid + (unsigned long long)chunk * K; if (lo >= C) return false; hi = C - lo > K ? lo + K : C; }
+        if (phase == 1u && chunk) { uint32_t pc[2]; if (!pg_sparse_piece(C, 0u, (chunk >> 16) * K, chunk & 0xFFFFu, pc)) return false; lo = pc[0]; hi = pc[1] + 1ull; }
+        const unsigned long long first = lo == 0u ? 1u : lo;
+        if (first >= hi) return false;
+        out[0] = (uint32_t)first; out[1] = (uint32_t)(hi - first); out[2] = pg_lean_ring_lead(C, 0u, phase, (uint32_t)first, (uint32_t)hi);
+        return true;
+    }
+    if (C == 0u) return false;
+    long long top = phase == 1u ? (long long)C - 1 : (long long)mid - 1, bot = phase == 1u ? (long long)mid : 0;
+    if (phase == 3u) { top = (long long)mid - 1 - (long long)chunk * K; if (top < 0) return false; bot = top - (long long)K + 1 > 0 ? top - (long long)K + 1 : 0; }
+    bool resumed = phase != 1u;
+    if (phase == 1u && chunk) { uint32_t pc[2]; if (!pg_sparse_piece(C, 1u, (chunk >> 16) * K, chunk & 0xFFFFu, pc)) return false; bot = pc[0]; top = pc[1]; resumed = top != (long long)C - 1; }
+    const long long t0 = resumed ? top : top - 1;
+    if (t0 < bot) return false;
+    out[0] = (uint32_t)t0; out[1] = (uint32_t)(t0 - bot + 1); out[2] = pg_lean_ring_lead(C, 1u, phase, (uint32_t)t0, (uint32_t)bot);
+    return true;
+}
 // The preparation beside phase 1 (pg_job::prep_beside; pg_shim_run.cpp: prepare_in_parts): a job whose phase 1 runs in pieces
 // prepares only what its first E pieces read ahead of them — the ENDS of the chains — and the rest, the MIDDLE, on the second
 // stream beside those pieces.  The middle of a chain of C columns is one band around the phase boundary, W = (n_pieces - E)

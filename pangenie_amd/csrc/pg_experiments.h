@@ -23,6 +23,12 @@ static constexpr bool kChainProf = false;
 #define PG_LEAN_EXP 0
 #endif
 static constexpr unsigned kLeanExp = PG_LEAN_EXP;
+// block upkeep of the lean step (profiles/r18_lean_upkeep.txt): 1 every step of a sparse group tests its number, as the steps
+// outside the groups do; 2 the forward role reads the next record and does the upkeep in front of the column sums
+#ifndef PG_LEAN_UPKEEP_EXP
+#define PG_LEAN_UPKEEP_EXP 0
+#endif
+static constexpr unsigned kLeanUpkeepExp = PG_LEAN_UPKEEP_EXP;
 #ifdef PG_LEAN_DPPSUM   // experiment: the wave total by six DPP steps (wave_sum) instead of the two fp64 MFMAs
 static constexpr bool kLeanDppSum = true;
 #else

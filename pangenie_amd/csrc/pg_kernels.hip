@@ -2911,13 +2911,24 @@ struct LeanShared {
     double psum[2][NW][64];
     double ptot[2][NW] __attribute__((aligned(32)));   // the waves' totals of their partial sums (kLeanPreTotal: lean_put_sums)
     double u[NW][64] __attribute__((aligned(16)));
-    double rec[2][PG_LEAN_BLOCK][8] __attribute__((aligned(16)));  // two blocks of compact records
     double scal[2][64];   // per-column scalars on their way out (ColScalars)
-    // emissions by ROW PAIRS (lean_expand): tab[b][r][c][a] = {e(row 2p, column allele a), e(row 2p+1, a)} for the row
-    // pair's allele combination c = bit(2p) + 2 bit(2p+1); comb[b][r][w][p] = 32 c of pair p of wave w's rows
-    v2f64 tab[2][PG_LEAN_BLOCK][4][2];
-    unsigned char comb[2][PG_LEAN_BLOCK][NW][R / 2] __attribute__((aligned(8)));
+    // The record ring: two blocks of PG_LEAN_BLOCK column records, ONE image of PG_LEAN_IMAGE bytes per record — everything a step
+    // reads of a record at fixed offsets off one address, image(rel) = img + ((rel << 8) & (sizeof img - 1)) (lean_image):
+    //   + 0    the compact record (FRec, 64 bytes)
+    //   + 64   emissions by ROW PAIRS (lean_expand): tab[c][a] = {e(row 2p, column allele a), e(row 2p+1, a)} for the row pair's
+    //          allele combination c = bit(2p) + 2 bit(2p+1) (128 bytes)
+    //   + 192  comb[w][p] = 32 c of pair p of wave w's rows (32 bytes)
+    //   + 224  spare
+    double img[2 * PG_LEAN_BLOCK][PG_LEAN_IMAGE / 8] __attribute__((aligned(PG_LEAN_IMAGE)));
 };
+static_assert(PG_LEAN_IMAGE == 256 && (2 * PG_LEAN_BLOCK * PG_LEAN_IMAGE & (2 * PG_LEAN_BLOCK * PG_LEAN_IMAGE - 1)) == 0, "image(rel): a shift and a mask");
+constexpr uint32_t kLeanImgTab = 64u, kLeanImgComb = 192u;
+// the image of record `rel` (uniform): the one address every read of the record hangs its immediate offset on
+template <class SH>
+DEVI LAS const unsigned char* lean_image(const SH& sh, uint32_t rel /*uniform*/) {
+    static_assert(sizeof(sh.img) == 2u * PG_LEAN_SPARSE * PG_LEAN_IMAGE, "pg_lean_ring_image");
+    return (LAS const unsigned char*)&sh.img[0][0] + pg_lean_ring_image(rel);
+}
 struct FRec {  // compact column record (64 B)
     double c0, c1, c2, kappa, E00, E01, E11;
     unsigned long long bits1;
@@ -2943,12 +2954,12 @@ struct LeanRecs {
     }
     template <class SH>
     DEVI void park(SH& sh, uint32_t block, v2f64 piece) const {
-        if (tid < 256u) ((v2f64*)&sh.rec[block & 1u][0][0])[tid] = piece;
+        if (tid < 256u) *(v2f64*)&sh.img[(block & 1u) * PG_LEAN_BLOCK + (tid >> 2)][(tid & 3u) * 2u] = piece;
     }
 };
 template <class SH>
 DEVI FRec read_frec(const SH& sh, uint32_t rel /*uniform*/) {
-    const double* q = sh.rec[(rel / PG_LEAN_BLOCK) & 1u][rel % PG_LEAN_BLOCK];
+    LAS const double* q = (LAS const double*)lean_image(sh, rel);
     FRec r;
     r.c0 = q[0]; r.c1 = q[1]; r.c2 = q[2]; r.kappa = q[3]; r.E00 = q[4]; r.E01 = q[5]; r.E11 = q[6];
     r.bits1 = (unsigned long long)__double_as_longlong(q[7]);
@@ -3052,23 +3063,23 @@ DEVI uint32_t add_byte(uint32_t bytes, uint32_t base) {
 // where bit test, mask and two selects per row took six instructions per pair.
 template <class SH>
 DEVI void lean_expand(SH& sh, uint32_t block /*uniform*/, uint32_t tid) {
-    static_assert(sizeof(sh.comb[0][0]) == 32, "four waves of eight row pairs");
+    static_assert(sizeof(sh.img[0]) == PG_LEAN_IMAGE && kLeanImgComb + 4u * 8u <= PG_LEAN_IMAGE, "four waves of eight row pairs");
     if (tid >= 256u) return;
-    const uint32_t b = block & 1u;
+    double* im = sh.img[(block & 1u) * PG_LEAN_BLOCK + (tid >> 2)];   // record r = tid >> 2 of the block
     {
-        const uint32_t r = tid >> 2, c = tid & 3u;   // two of the block's 512 table entries per thread: (r, c, column allele 0 / 1)
-        const double* rc = sh.rec[b][r];
-        const double E00 = rc[4], E01 = rc[5], E11 = rc[6];
-        sh.tab[b][r][c][0] = v2f64{(c & 1u) ? E01 : E00, (c & 2u) ? E01 : E00};
-        sh.tab[b][r][c][1] = v2f64{(c & 1u) ? E11 : E01, (c & 2u) ? E11 : E01};
+        const uint32_t c = tid & 3u;   // two of the block's 512 table entries per thread: (r, c, column allele 0 / 1)
+        const double E00 = im[4], E01 = im[5], E11 = im[6];
+        v2f64* tab = (v2f64*)((unsigned char*)im + kLeanImgTab);
+        tab[c * 2u + 0u] = v2f64{(c & 1u) ? E01 : E00, (c & 2u) ? E01 : E00};
+        tab[c * 2u + 1u] = v2f64{(c & 1u) ? E11 : E01, (c & 2u) ? E11 : E01};
     }
     {
-        const uint32_t r = tid >> 2, w = tid & 3u;   // the eight pair bytes of wave w's rows of record r
-        const unsigned long long bits = (unsigned long long)__double_as_longlong(sh.rec[b][r][7]);
+        const uint32_t w = tid & 3u;   // the eight pair bytes of wave w's rows of record r
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(im[7]);
         const uint32_t b16 = (uint32_t)(bits >> (16u * w)) & 0xFFFFu;
         auto spread = [](uint32_t v8) { return ((v8 & 3u) | (((v8 >> 2) & 3u) << 8) | (((v8 >> 4) & 3u) << 16) | (((v8 >> 6) & 3u) << 24)) << 5; };
         typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-        *(u32x2*)&sh.comb[b][r][w][0] = u32x2{spread(b16 & 0xFFu), spread(b16 >> 8)};
+        *(u32x2*)((unsigned char*)im + kLeanImgComb + w * 8u) = u32x2{spread(b16 & 0xFFu), spread(b16 >> 8)};
     }
 }
 // what a step needs to fetch the emissions of column `rel`: the lane's table column and the wave's pair bytes
@@ -3076,11 +3087,11 @@ struct LeanPairs { uint32_t tbase, cd0, cd1; };
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 template <class SH>
 DEVI u32x2 lean_pair_bytes(const SH& sh, uint32_t rel /*uniform*/, uint32_t wave /*uniform*/) {   // (one broadcast LDS read: issue it early)
-    return *(const u32x2*)&sh.comb[(rel / PG_LEAN_BLOCK) & 1u][rel % PG_LEAN_BLOCK][wave][0];
+    return *(LAS const u32x2*)(lean_image(sh, rel) + kLeanImgComb + wave * 8u);
 }
 template <class SH>
 DEVI LeanPairs lean_pairs(const SH& sh, uint32_t rel /*uniform*/, u32x2 cd, uint32_t aj /*0 / 1: the lane's column allele*/) {
-    return LeanPairs{(uint32_t)(uintptr_t)(LAS const unsigned char*)&sh.tab[(rel / PG_LEAN_BLOCK) & 1u][rel % PG_LEAN_BLOCK][0][0] + aj * 16u, cd.x, cd.y};
+    return LeanPairs{(uint32_t)(uintptr_t)lean_image(sh, rel) + kLeanImgTab + aj * 16u, cd.x, cd.y};
 }
 template <class SH>
 DEVI LeanPairs lean_pairs(const SH& sh, uint32_t rel, uint32_t wave, uint32_t aj) { return lean_pairs(sh, rel, lean_pair_bytes(sh, rel, wave), aj); }
@@ -3091,6 +3102,48 @@ DEVI v2f64 lean_pair(const LeanPairs& lp) {
 template <int R>
 DEVI void lean_pairs_all(const LeanPairs& lp, double (&e)[R]) {
     static_for<0, R / 2>([&](auto pc) __attribute__((always_inline)) { constexpr int q = decltype(pc)::value; const v2f64 t = lean_pair<q>(lp); e[2 * q] = t.x; e[2 * q + 1] = t.y; });
+}
+// The record ring of a launch (pg_device.h: pg_lean_ring_*).  Opening it: block 0 parked and expanded, the piece of block 1 in a
+// register — and for a launch whose first step has a number `s0` behind the step that parks block 1 (a sparse launch numbered
+// from its group grid), block 1 parked and expanded as well, the piece of block 2 in the register.
+template <class SH>
+DEVI v2f64 lean_ring_open(SH& sh, const LeanRecs& recs, uint32_t s0 /*uniform*/, uint32_t tid) {
+    const bool two = s0 > PG_LEAN_RING_PARK;
+    recs.park(sh, 0, recs.fetch(0));
+    v2f64 piece = recs.fetch(1);
+    if (two) {
+        lds_barrier();
+        lean_expand(sh, 0, tid);
+        lds_barrier();
+        recs.park(sh, 1, piece);
+        piece = recs.fetch(2);
+    }
+    lds_barrier();
+    lean_expand(sh, two ? 1u : 0u, tid);
+    lds_barrier();
+    return piece;
+}
+// Block upkeep of step number n: the block after next is parked four records before the first read of it and expanded a step later
+// (a barrier lies between).  kUpkeepTested: by the two tests, as every step outside the groups of a sparse launch; inside a group
+// the step's place says which of the three it is (PG_LEAN_RING_PARK, PG_LEAN_RING_EXPAND) and the step is compiled for that alone.
+constexpr int kUpkeepTested = -1, kUpkeepNone = 0, kUpkeepPark = 1, kUpkeepExpand = 2;
+template <int UPKEEP, class SH>
+DEVI void lean_ring_upkeep(SH& sh, const LeanRecs& recs, v2f64& piece, uint32_t n /*uniform*/, uint32_t tid) {
+    if constexpr (UPKEEP == kUpkeepTested || (kLeanUpkeepExp & 1u)) {
+        if (((n + 4u) % PG_LEAN_BLOCK) == 0u) {       // (uniform) a few columns before the next block is needed
+            const uint32_t blk = (n + 4u) / PG_LEAN_BLOCK;
+            recs.park(sh, blk, piece);
+            piece = recs.fetch(blk + 1u);
+        } else if (((n + 3u) % PG_LEAN_BLOCK) == 0u) {
+            lean_expand(sh, (n + 3u) / PG_LEAN_BLOCK, tid);   // the block parked a step ago (a barrier lies between)
+        }
+    } else if constexpr (UPKEEP == kUpkeepPark) {
+        const uint32_t blk = (n + 4u) / PG_LEAN_BLOCK;
+        recs.park(sh, blk, piece);
+        piece = recs.fetch(blk + 1u);
+    } else if constexpr (UPKEEP == kUpkeepExpand) {
+        lean_expand(sh, (n + 3u) / PG_LEAN_BLOCK, tid);
+    }
 }
 template <int R>
 DEVI double lean_colsum(const LeanShared<R>& sh, uint32_t pb, uint32_t lane) {
@@ -3219,12 +3272,10 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
     const uint32_t i0 = wave * R;
     const size_t colsz = TRI ? (size_t)dc.col_stride : (size_t)HP * HP;
     const double unif = 1.0 / 4096.0;
-    LeanRecs recs{(const GAS char*)dc.frec, (int64_t)first - 1, (int64_t)C, +1, tid};
-    recs.park(sh, 0, recs.fetch(0));
-    v2f64 piece = recs.fetch(1);
-    lds_barrier();
-    lean_expand(sh, 0, tid);
-    lds_barrier();
+    // SPARSE: the records are numbered from the group grid (pg_device.h: pg_lean_ring_first) — the first step is number s0, not 0
+    const uint32_t s0 = SPARSE ? pg_lean_ring_first(pg_lean_ring_lead(C, 0u, (uint32_t)PHASE, first, hi)) : 0u;
+    LeanRecs recs{(const GAS char*)dc.frec, (int64_t)first - 1 - (int64_t)s0, (int64_t)C, +1, tid};
+    v2f64 piece = lean_ring_open(sh, recs, s0, tid);
     gdouble* fwd = (gdouble*)dc.fwd;
     gdouble* fscale = (gdouble*)dc.fscale;
     gu8* fallback = (gu8*)dc.fwd_fallback;
@@ -3314,7 +3365,7 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
     ColScalars fsc{&sh.scal[0][0]};
     double x[R];
     {
-        const FRec r0 = read_frec(sh, 0);
+        const FRec r0 = read_frec(sh, s0);
         double eA, eB;
         emis(r0, eA, eB);
         const uint32_t rb = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(r0.bits1 >> i0) & RMASK));
@@ -3356,27 +3407,26 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
     // per column — they sit in front of the total's consumer; product-column multiplies deferred into that shadow: 656.)
     double ec[R];
     {
-        const FRec r1 = read_frec(sh, 1);
-        lean_pairs_all<R>(lean_pairs(sh, 1, wave, (uint32_t)((r1.bits1 >> lane) & 1ull)), ec);   // column `first`
+        const FRec r1 = read_frec(sh, s0 + 1u);
+        lean_pairs_all<R>(lean_pairs(sh, s0 + 1u, wave, (uint32_t)((r1.bits1 >> lane) & 1ull)), ec);   // column `first`
     }
     // One column step.  `cur` = record of this step (constants of the gap t-1 -> t), `nxt` takes the record of the next
     // step (four broadcast LDS reads, a whole step ahead of use); the loop calls the step twice with the two record
     // variables and the two emission arrays in swapped roles, so nothing is ever moved.
     LeanTimeline tl;
     tl.init();
-    auto step = [&](auto store_c, uint32_t t, const FRec& cur, FRec& nxt) __attribute__((always_inline)) {
+    auto step = [&](auto store_c, auto upkeep_c, uint32_t t, const FRec& cur, FRec& nxt) __attribute__((always_inline)) {
         constexpr bool STORE = decltype(store_c)::value;   // (false: a column between two checkpoints of a sparse phase 1)
-        const uint32_t n = t - first;                 // step number: reads the record with rel = n + 2
+        constexpr int UPKEEP = decltype(upkeep_c)::value;  // (kUpkeep*: where the step of a group stands decides it, not a test)
+        const uint32_t n = t - first + s0;            // step number: reads the record with rel = n + 2
         tl.template mark<0>(0.0);                     // (behind the barrier of the step before)
-        nxt = read_frec(sh, n + 2u);
-        const u32x2 cdn = lean_pair_bytes(sh, n + 2u, wave);
-        if (((n + 4u) % PG_LEAN_BLOCK) == 0u) {       // (uniform) a few columns before the next block is needed
-            const uint32_t blk = (n + 4u) / PG_LEAN_BLOCK;
-            recs.park(sh, blk, piece);
-            piece = recs.fetch(blk + 1u);
-        } else if (((n + 3u) % PG_LEAN_BLOCK) == 0u) {
-            lean_expand(sh, (n + 3u) / PG_LEAN_BLOCK, tid);   // the block parked a step ago (a barrier lies between)
-        }
+        u32x2 cdn;
+        auto next_record = [&]() __attribute__((always_inline)) {
+            nxt = read_frec(sh, n + 2u);
+            cdn = lean_pair_bytes(sh, n + 2u, wave);
+            lean_ring_upkeep<UPKEEP>(sh, recs, piece, n, tid);
+        };
+        if constexpr (kLeanUpkeepExp & 2u) next_record();
         const uint32_t pb = (t - 1) & 1u;
         // both column sums' partials are fetched up front (this lane's column; the column of index i0 + (lane & 15):
         // the DPP source of the wave's sixteen u_i); everything that does not need the total S — the second sum, the
@@ -3385,6 +3435,12 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
 #pragma unroll
         for (int q = 0; q < 64 / R; ++q) { pc[q] = sh.psum[pb][q][lane]; pr[q] = sh.psum[pb][q][i0 + (lane & 15u)]; }
         const double Spre = kLeanPreTotal ? lean_total<R>(sh, pb) : 0.0;   // (issued with the other LDS reads)
+        // the column sums head the step's dependent chain: the record of the next step and the block upkeep come behind them
+        if constexpr (!(kLeanUpkeepExp & 2u)) {
+            lean_fence();
+            next_record();
+            lean_fence();
+        }
         const double Cj = (pc[0] + pc[1]) + (pc[2] + pc[3]);
         tl.template mark<1>(Cj);                      // the column sums are back from LDS
         const v4f64 zz = {0.0, 0.0, 0.0, 0.0};
@@ -3451,9 +3507,13 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         tl.template mark<8>(0.0);                     // the barrier
         tl.template fold<8>();
     };
-    FRec ra = read_frec(sh, 1), rb2;
+    FRec ra = read_frec(sh, s0 + 1u), rb2;
     constexpr std::true_type kStore{};
     constexpr std::false_type kNoStore{};
+    constexpr std::integral_constant<int, kUpkeepTested> kTested{};
+    constexpr std::integral_constant<int, kUpkeepNone> kNone{};
+    constexpr std::integral_constant<int, kUpkeepPark> kPark{};
+    constexpr std::integral_constant<int, kUpkeepExpand> kExpand{};
     // every load of the prologue has landed before the loop is entered: a register still "waiting for a load" at the loop
     // head would make the compiler put a vmcnt wait — a cap on the stores in flight — into every step
     __builtin_amdgcn_s_waitcnt(0x0F70);
@@ -3467,10 +3527,10 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         uint32_t q = 0, cend = hi - lo > K ? lo + K : hi;
         for (;;) {
             for (; t + 1 < cend; t += 2) {
-                step(kStore, t, ra, rb2);
-                step(kStore, t + 1, rb2, ra);
+                step(kStore, kTested, t, ra, rb2);
+                step(kStore, kTested, t + 1, rb2, ra);
             }
-            if (t < cend) { step(kStore, t, ra, rb2); ++t; }   // (the last chunk only)
+            if (t < cend) { step(kStore, kTested, t, ra, rb2); ++t; }   // (the last chunk only)
             // what a chunk launch of PHASE 3 does when it ends: the scalars still parked, the zero test of the chunk's last column
             if (wave == 0 && fsc.valid) fsc.flush(fscale, lane, cend - 1);
             {
@@ -3493,33 +3553,38 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         if constexpr (PHASE == 1) {
             const uint32_t ck0 = (hi - 1u) % PG_LEAN_SPARSE;
             for (; t + 1 <= ck0; t += 2) {
-                step(kStore, t, ra, rb2);
-                step(kStore, t + 1, rb2, ra);
+                step(kStore, kTested, t, ra, rb2);
+                step(kStore, kTested, t + 1, rb2, ra);
             }
-            if (t <= ck0) { step(kStore, t, ra, rb2); ra = rb2; ++t; }
+            if (t <= ck0) { step(kStore, kTested, t, ra, rb2); ra = rb2; ++t; }
         }
+        // (a group begins at a step number that is a multiple of the block: its steps PG_LEAN_RING_PARK and PG_LEAN_RING_EXPAND
+        //  do the block upkeep, the others are compiled without it)
+        static_assert(PG_LEAN_SPARSE == PG_LEAN_BLOCK && PG_LEAN_RING_PARK % 2u == 0u && PG_LEAN_RING_EXPAND == PG_LEAN_RING_PARK + 1u && PG_LEAN_RING_PARK + 4u == PG_LEAN_SPARSE, "the group's last four steps: park, expand, plain, store");
         while (hi - t >= PG_LEAN_SPARSE) {   // (phase 1: every column left)
-            for (uint32_t g = 0; g + 1u < PG_LEAN_SPARSE / 2u; ++g, t += 2) {
-                step(kNoStore, t, ra, rb2);
-                step(kNoStore, t + 1, rb2, ra);
+            for (uint32_t g = 0; g < PG_LEAN_RING_PARK / 2u; ++g, t += 2) {
+                step(kNoStore, kNone, t, ra, rb2);
+                step(kNoStore, kNone, t + 1, rb2, ra);
             }
-            step(kNoStore, t, ra, rb2);
-            step(kStore, t + 1, rb2, ra);
-            t += 2;
+            step(kNoStore, kPark, t, ra, rb2);
+            step(kNoStore, kExpand, t + 1, rb2, ra);
+            step(kNoStore, kNone, t + 2, ra, rb2);
+            step(kStore, kNone, t + 3, rb2, ra);
+            t += 4;
         }
         if constexpr (PHASE == 3) {   // the piece behind the half's last checkpoint: a refill segment's, like every other column
             for (; t + 1 < hi; t += 2) {
-                step(kNoStore, t, ra, rb2);
-                step(kNoStore, t + 1, rb2, ra);
+                step(kNoStore, kTested, t, ra, rb2);
+                step(kNoStore, kTested, t + 1, rb2, ra);
             }
-            if (t < hi) step(kNoStore, t, ra, rb2);
+            if (t < hi) step(kNoStore, kTested, t, ra, rb2);
         }
     } else {
         for (; t + 1 < hi; t += 2) {
-            step(kStore, t, ra, rb2);
-            step(kStore, t + 1, rb2, ra);
+            step(kStore, kTested, t, ra, rb2);
+            step(kStore, kTested, t + 1, rb2, ra);
         }
-        if (t < hi) step(kStore, t, ra, rb2);
+        if (t < hi) step(kStore, kTested, t, ra, rb2);
     }
     if constexpr (!SPARSE) if (wave == 0 && fsc.valid) fsc.flush(fscale, lane, hi - 1);   // (a segment is not aligned to the 64-column blocks: what is left of its last one)
     if (kLeanTimeline && tid == 0) tl.write(dc.prof + 32);
@@ -3563,12 +3628,9 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
     const uint32_t i0 = wave * R;
     const size_t colsz = TRI ? (size_t)dc.col_stride : (size_t)HP * HP;
     const double unif = 1.0 / 4096.0;
-    LeanRecs recs{(const GAS char*)dc.frec, t0 + 1, (int64_t)C, -1, tid};
-    recs.park(sh, 0, recs.fetch(0));
-    v2f64 piece = recs.fetch(1);
-    lds_barrier();
-    lean_expand(sh, 0, tid);
-    lds_barrier();
+    const uint32_t s0 = SPARSE && t0 >= bot ? pg_lean_ring_first(pg_lean_ring_lead(C, 1u, (uint32_t)PHASE, (uint32_t)t0, (uint32_t)bot)) : 0u;   // (see lean_forward)
+    LeanRecs recs{(const GAS char*)dc.frec, t0 + 1 + (int64_t)s0, (int64_t)C, -1, tid};
+    v2f64 piece = lean_ring_open(sh, recs, s0, tid);
     gdouble* cols = (gdouble*)dc.fwd;
     gdouble* bscale = (gdouble*)dc.bscale;
     gdouble* bsum = (gdouble*)dc.bsum;
@@ -3640,7 +3702,7 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
     if constexpr (PHASE == 5) if (seg2 && pg_sparse2_stored(C, 1u, (uint32_t)bot)) noscal = bot;
     ColScalars bsc{&sh.scal[0][0]}, bsm{&sh.scal[1][0]};
     double w[R], Sy;
-    FRec cur = read_frec(sh, 0);  // record t0+1: constants of the gap t0 -> t0+1, emission of column t0+1
+    FRec cur = read_frec(sh, s0);  // record t0+1: constants of the gap t0 -> t0+1, emission of column t0+1
     {
         double y[R];
         if (!resumed) {
@@ -3672,8 +3734,8 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
     }
     double ec[R];   // (see lean_forward)
     {
-        const FRec r1 = read_frec(sh, 1);   // column t0: its emission goes into the first step's w
-        lean_pairs_all<R>(lean_pairs(sh, 1, wave, (uint32_t)((r1.bits1 >> lane) & 1ull)), ec);
+        const FRec r1 = read_frec(sh, s0 + 1u);   // column t0: its emission goes into the first step's w
+        lean_pairs_all<R>(lean_pairs(sh, s0 + 1u, wave, (uint32_t)((r1.bits1 >> lane) & 1ull)), ec);
     }
     double one = 1.0;   // (in a register for the whole sweep: the DPP form of v_fmac_f64 takes no constant)
     asm volatile("" : "+v"(one));
@@ -3681,17 +3743,12 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
     // (constants of the next step); `ec` = emissions of column t (this step's w), `en` takes those of column t-1.
     LeanTimeline tl;
     tl.init();
-    auto step = [&](auto store_c, int64_t t, const FRec& cur, FRec& nxt) __attribute__((always_inline)) {
+    auto step = [&](auto store_c, auto upkeep_c, int64_t t, const FRec& cur, FRec& nxt) __attribute__((always_inline)) {
         constexpr bool STORE = decltype(store_c)::value;
-        const uint32_t n = (uint32_t)(t0 - t);        // step number: column t is the record with rel = n + 1
+        constexpr int UPKEEP = decltype(upkeep_c)::value;   // (see lean_forward)
+        const uint32_t n = (uint32_t)(t0 - t) + s0;   // step number: column t is the record with rel = n + 1
         tl.template mark<0>(0.0);
-        if (((n + 4u) % PG_LEAN_BLOCK) == 0u) {
-            const uint32_t blk = (n + 4u) / PG_LEAN_BLOCK;
-            recs.park(sh, blk, piece);
-            piece = recs.fetch(blk + 1u);
-        } else if (((n + 3u) % PG_LEAN_BLOCK) == 0u) {
-            lean_expand(sh, (n + 3u) / PG_LEAN_BLOCK, tid);
-        }
+        lean_ring_upkeep<UPKEEP>(sh, recs, piece, n, tid);
         int es = exponent_of(Sy) - PG_BIAS_B;
         es = es < -900 ? -900 : es;
         const double m = ldexp(Sy, -es - PG_BIAS_B);
@@ -3713,7 +3770,7 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         // the wave would wait out their LDS latency: the barrier's release waits for every outstanding LDS operation)
         lean_fence();
         nxt = read_frec(sh, n + 1u);
-        const unsigned long long bits_n = (unsigned long long)__double_as_longlong(sh.rec[((n + 2u) / PG_LEAN_BLOCK) & 1u][(n + 2u) % PG_LEAN_BLOCK][7]);  // column t-1
+        const unsigned long long bits_n = (unsigned long long)__double_as_longlong(((LAS const double*)lean_image(sh, n + 2u))[7]);  // column t-1
         const u32x2 cdn = lean_pair_bytes(sh, n + 2u, wave);
         lean_fence();
         const double Cj = (pc[0] + pc[1]) + (pc[2] + pc[3]);
@@ -3781,6 +3838,10 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
     FRec rb2;
     constexpr std::true_type kStore{};
     constexpr std::false_type kNoStore{};
+    constexpr std::integral_constant<int, kUpkeepTested> kTested{};
+    constexpr std::integral_constant<int, kUpkeepNone> kNone{};
+    constexpr std::integral_constant<int, kUpkeepPark> kPark{};
+    constexpr std::integral_constant<int, kUpkeepExpand> kExpand{};
     int64_t t = t0;
     __builtin_amdgcn_s_waitcnt(0x0F70);   // (see lean_forward: no load of the prologue is still in flight inside the loop)
     if constexpr (PHASE == 4) {
@@ -3789,10 +3850,10 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         uint32_t q = 0;
         for (;;) {
             for (; t - 1 >= cbot; t -= 2) {
-                step(kStore, t, cur, rb2);
-                step(kStore, t - 1, rb2, cur);
+                step(kStore, kTested, t, cur, rb2);
+                step(kStore, kTested, t - 1, rb2, cur);
             }
-            if (t >= cbot) { step(kStore, t, cur, rb2); --t; }   // (the last chunk only: K is even)
+            if (t >= cbot) { step(kStore, kTested, t, cur, rb2); --t; }   // (the last chunk only: K is even)
             if (wave == 1 && bsc.valid) bsc.flush(bscale, lane, (uint64_t)cbot);
             if (wave == 2 && bsm.valid) bsm.flush(bsum, lane, (uint64_t)cbot);
             chunk_publish(dc.sync + 1, q + 1u);
@@ -3809,33 +3870,35 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         if constexpr (PHASE == 1) {
             const int64_t ckh = mid + (int64_t)pg_sparse_segments(C, 1u) * (int64_t)PG_LEAN_SPARSE;   // the first checkpoint on the way down
             for (; t - 1 >= ckh; t -= 2) {
-                step(kStore, t, cur, rb2);
-                step(kStore, t - 1, rb2, cur);
+                step(kStore, kTested, t, cur, rb2);
+                step(kStore, kTested, t - 1, rb2, cur);
             }
-            if (t >= ckh) { step(kStore, t, cur, rb2); cur = rb2; --t; }
+            if (t >= ckh) { step(kStore, kTested, t, cur, rb2); cur = rb2; --t; }
         }
         while (t - bot >= (int64_t)PG_LEAN_SPARSE - 1) {   // (phase 1: every column left)
-            for (uint32_t g = 0; g + 1u < PG_LEAN_SPARSE / 2u; ++g, t -= 2) {
-                step(kNoStore, t, cur, rb2);
-                step(kNoStore, t - 1, rb2, cur);
+            for (uint32_t g = 0; g < PG_LEAN_RING_PARK / 2u; ++g, t -= 2) {
+                step(kNoStore, kNone, t, cur, rb2);
+                step(kNoStore, kNone, t - 1, rb2, cur);
             }
-            step(kNoStore, t, cur, rb2);
-            step(kStore, t - 1, rb2, cur);
-            t -= 2;
+            step(kNoStore, kPark, t, cur, rb2);
+            step(kNoStore, kExpand, t - 1, rb2, cur);
+            step(kNoStore, kNone, t - 2, cur, rb2);
+            step(kStore, kNone, t - 3, rb2, cur);
+            t -= 4;
         }
         if constexpr (PHASE == 3) {
             for (; t - 1 >= bot; t -= 2) {
-                step(kNoStore, t, cur, rb2);
-                step(kNoStore, t - 1, rb2, cur);
+                step(kNoStore, kTested, t, cur, rb2);
+                step(kNoStore, kTested, t - 1, rb2, cur);
             }
-            if (t >= bot) step(kNoStore, t, cur, rb2);
+            if (t >= bot) step(kNoStore, kTested, t, cur, rb2);
         }
     } else {
         for (; t - 1 >= bot; t -= 2) {
-            step(kStore, t, cur, rb2);
-            step(kStore, t - 1, rb2, cur);
+            step(kStore, kTested, t, cur, rb2);
+            step(kStore, kTested, t - 1, rb2, cur);
         }
-        if (t >= bot) step(kStore, t, cur, rb2);
+        if (t >= bot) step(kStore, kTested, t, cur, rb2);
     }
     if constexpr (!SPARSE) {
         if (wave == 1 && bsc.valid) bsc.flush(bscale, lane, (uint64_t)bot);
@@ -3974,9 +4037,9 @@ DEVI void lean2_forward(const DevContig& dc, LeanShared2<R>& sh2, uint32_t C) {
     // of the sixteen states come pair by pair out of LDS tables (lean_expand), fetched one pair ahead.
     auto step = [&](uint32_t t, const double (&ba)[R], double (&bc)[R]) __attribute__((always_inline)) {
         const uint32_t n = t - first;
-        const double* rq = sh.rec[((n + 1u) / PG_LEAN_BLOCK) & 1u][(n + 1u) % PG_LEAN_BLOCK];   // record t: constants of the gap t-1 -> t
+        LAS const double* rq = (LAS const double*)lean_image(sh, n + 1u);   // record t: constants of the gap t-1 -> t
         const double rc0 = rq[0], rc1 = rq[1], rc2 = rq[2];
-        const unsigned long long nbits = (unsigned long long)__double_as_longlong(sh.rec[((n + 2u) / PG_LEAN_BLOCK) & 1u][(n + 2u) % PG_LEAN_BLOCK][7]);
+        const unsigned long long nbits = (unsigned long long)__double_as_longlong(((LAS const double*)lean_image(sh, n + 2u))[7]);
         const u32x2 ncd = lean_pair_bytes(sh, n + 2u, wave);
         if (((n + 4u) % PG_LEAN_BLOCK) == 0u) {
             const uint32_t blk = (n + 4u) / PG_LEAN_BLOCK;
@@ -4137,9 +4200,9 @@ DEVI void lean2_backward(const DevContig& dc, LeanShared2<R>& sh2, uint32_t C) {
         const double k0 = ldexp(kc0, -es), k1 = ldexp(kc1, -es), k2 = ldexp(kc2, -es), kap = ldexp(kck, -es);
         lds_barrier();
         // the next step's constants (record t: gap t-1 -> t), column alleles and pair bytes (column t-1)
-        const double* rq = sh.rec[((n + 1u) / PG_LEAN_BLOCK) & 1u][(n + 1u) % PG_LEAN_BLOCK];
+        LAS const double* rq = (LAS const double*)lean_image(sh, n + 1u);
         const double nc0 = rq[0], nc1 = rq[1], nc2 = rq[2], nck = rq[3];
-        const unsigned long long nbits = (unsigned long long)__double_as_longlong(sh.rec[((n + 2u) / PG_LEAN_BLOCK) & 1u][(n + 2u) % PG_LEAN_BLOCK][7]);
+        const unsigned long long nbits = (unsigned long long)__double_as_longlong(((LAS const double*)lean_image(sh, n + 2u))[7]);
         const u32x2 ncd = lean_pair_bytes(sh, n + 2u, wave);
         if (t < t0) lean2_flush_partials<R>(sh2, (uint32_t)(t + 1) & 1u, part, (size_t)(t + 1), wave, lane, pbits);
         const double Cj = lean_colsum<R>(sh, (uint32_t)t & 1u, lane);

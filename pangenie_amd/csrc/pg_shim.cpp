@@ -2013,6 +2013,19 @@ extern "C" int pg_sparse_piece_range(uint32_t n_columns, uint32_t chunk_cols, ui
     if (out) { out[0] = r[0]; out[1] = r[1]; }
     return 1;
 }
+// ... of the record ring of a sparse lean launch (pg_lean_ring_*): form 0 = phase 1 in one launch, 1 = piece `arg` of phase 1,
+// 2 = chunk sweep `arg` of phase 3.  out = {column of the first step, steps, steps in front of the first group, number of the first
+// step, step of a group that parks a block, step of a group that expands it}
+extern "C" int pg_lean_ring_schedule(uint32_t n_columns, uint32_t chunk_cols, uint32_t piece_chunks, uint32_t role, uint32_t form, uint32_t arg, uint32_t out[6]) {
+    if (role > 1u || form > 2u || chunk_cols == 0u || chunk_cols % PG_LEAN_SPARSE != 0u) return -1;
+    if (form == 1u && (piece_chunks == 0u || piece_chunks > 0xFFFFu || arg > 0xFFFFu || (unsigned long long)piece_chunks * chunk_cols > 0xFFFFFFFFull)) return -1;
+    uint32_t r[3];
+    const uint32_t chunk = form == 0u ? 0u : (form == 1u ? (piece_chunks << 16 | arg) : arg);
+    if (!pg_lean_ring_launch(n_columns, role, form == 2u ? 3u : 1u, chunk_cols, chunk, r)) return 0;
+    if (out) { out[0] = r[0]; out[1] = r[1]; out[2] = r[2]; out[3] = pg_lean_ring_first(r[2]); out[4] = PG_LEAN_RING_PARK; out[5] = PG_LEAN_RING_EXPAND; }
+    return 1;
+}
+extern "C" uint32_t pg_lean_ring_image_offset(uint32_t record) { return pg_lean_ring_image(record); }
 // ... of the preparation in parts (pg_prep_middle, pg_prep_middle_variants): the middle's columns and variants, [lo, hi) each
 extern "C" int pg_prep_parts(uint32_t n_columns, uint32_t chunk_cols, uint32_t piece_chunks, uint32_t n_pieces, uint32_t early,
                              const uint32_t* col_variant, uint32_t n_variants, uint32_t out_cols[2], uint32_t out_vars[2]) {
