@@ -533,6 +533,65 @@ int  pg_gl_from_values(int device, uint64_t n, const uint64_t* m, const int32_t*
  * length; -1 for PG_GL_DEFERRED, an encoding that is none of the above, or a buffer too small (32 bytes suffice). */
 int  pg_gl_text(pg_gl value, char* buf, size_t len);
 
+/* ------------------------------------------------------------------ *
+ *  Path subsets: the chains of one contig over different path selections combined on the device, and the calls
+ *  from the sums (pangenie_amd/csrc/pg_combine.hip).  The reference's `-a` option genotypes a
+ *  chromosome once per subset of paths, adds the subsets' UNNORMALISED likelihoods per genotype
+ *  (src/commands.cpp:163-177; GenotypingResult::combine, src/genotypingresult.cpp:193-198) and normalises once.
+ *  Chains s = 0 .. S-1 of a GROUP genotype the same index objects; chain s holds key (a <= b) of variant v iff
+ *  kept_s[v] && allele_present_s[a] && allele_present_s[b].  The combined map of a variant has the UNION of the
+ *  chains' keys (a key held with the value 0 is present), each value ((L_s1 + L_s2) + L_s3) ... over the chains
+ *  that hold it IN THE ORDER OF THE GROUP, every addition rounded as the x87 rounds a long double.
+ * ------------------------------------------------------------------ */
+#ifndef PG_COMBINED_DEFINED /* (the same in pangenie_amd/csrc/pg_combine.h) */
+#define PG_COMBINED_DEFINED
+typedef struct pg_combined_bin { uint64_t m; int32_t e; uint32_t flags; } pg_combined_bin;
+/* value = m * 2^e, m in [2^63, 2^64) or 0 (then e == 0): ldexpl((long double)m, e) is exact */
+#define PG_COMBINED_PRESENT  1u   /* the key exists in the combined map                      */
+#define PG_COMBINED_DEFERRED 2u   /* present, not formed on the device: add this key on the  */
+                                  /* host from the chains' bins (m == 0, e == 0)             */
+#endif
+/* A key is PG_COMBINED_DEFERRED iff its largest nonzero summand lies below 2^-16300 (the cut of PG_CALL_DEFERRED).
+ *
+ * The plan: group g = chains[group_off[g] .. group_off[g + 1]), in combine order.  A second plan replaces the first.
+ * PG_ERR_INVALID, and nothing is attached: n_groups == 0, an empty group, a chain >= pg_job_n_chains, a chain listed
+ * twice (in one group or in two), members whose n_variants, alleles per variant or allele ids differ (checked on the
+ * device, against the arrays it holds: sampled panels too), a job without run_genotyping.  The buffers (16 bytes per
+ * bin and 8 per variant of every group) lie outside the arena and are freed by pg_job_destroy; PG_ERR_NOMEM if they
+ * do not fit. */
+int  pg_job_combine_plan(pg_job* job, uint32_t n_groups, const uint32_t* group_off, const uint32_t* chains, char* err, size_t errlen);
+/* Combines every group of the plan from the bins of the last pg_job_run (on the job's stream; blocking).  Refusals as
+ * pg_job_calls, and PG_ERR_INVALID without a plan.  After an index upload the layout is checked again first. */
+int  pg_job_combine(pg_job* job, char* err, size_t errlen);
+/* Group `group`'s combined bins, out[geno_off[V]] in the layout of the members' bins (after pg_job_combine of this run). */
+int  pg_job_fetch_combined(pg_job* job, uint32_t group, pg_combined_bin* out, char* err, size_t errlen);
+/* The same for all groups, outs[n_groups] (NULL allowed for a group without variants): one synchronisation. */
+int  pg_job_fetch_combined_all(pg_job* job, pg_combined_bin* const* outs, char* err, size_t errlen);
+/* Device-resident combined bins of group `group`: pg_combined_bin [n]. */
+int  pg_job_device_combined(pg_job* job, uint32_t group, void** d_bins, uint64_t* n);
+/* One pg_call per variant of every group from its combined bins: normalize, get_likeliest_genotype and
+ * get_genotype_quality on the combined map, as pg_job_calls on one chain's (allele_1 / allele_2 are allele ids).  A
+ * variant with a PG_COMBINED_DEFERRED bin is PG_CALL_DEFERRED.  PG_ERR_INVALID before pg_job_combine of the same run. */
+int  pg_job_combined_calls(pg_job* job, char* err, size_t errlen);
+int  pg_job_fetch_combined_calls(pg_job* job, uint32_t group, pg_call* out, char* err, size_t errlen);
+int  pg_job_fetch_combined_calls_all(pg_job* job, pg_call* const* outs, char* err, size_t errlen);
+int  pg_job_device_combined_calls(pg_job* job, uint32_t group, void** d_calls, uint64_t* n);
+/* Groups of the job's plan (0 without one). */
+uint32_t pg_job_n_groups(const pg_job* job);
+/* Elapsed milliseconds of the kernels of the LAST pg_job_combine / pg_job_combined_calls. */
+double pg_job_combine_ms(const pg_job* job);
+double pg_job_combined_calls_ms(const pg_job* job);
+/* Unit entry points, through the same kernels; PG_ERR_DEVICE without a device, no host fallback.
+ * pg_combine_bins: n_chains >= 1 chains over one layout (allele_off [V+1]); kept[s] [V], allele_present[s] [sumA],
+ * lik[s] / lik_exp[s] [sum A (A + 1) / 2] of chain s, combined in the order given; out[sum A (A + 1) / 2]. */
+int  pg_combine_bins(int device, uint32_t n_variants, const uint32_t* allele_off, uint32_t n_chains,
+                     const uint8_t* const* kept, const uint8_t* const* allele_present,
+                     const double* const* lik, const int32_t* const* lik_exp, pg_combined_bin* out);
+/* pg_calls_from_combined: the calls of n_variants variants from their combined bins; out[V].  PG_ERR_INVALID for a bin
+ * that is no pg_combined_bin: m neither 0 nor normalised, unknown flags, a value without PG_COMBINED_PRESENT. */
+int  pg_calls_from_combined(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id,
+                            const pg_combined_bin* bins, pg_call* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -298,6 +298,31 @@ def _bind_hip(lib):
     lib.pg_gl_from_values.restype = C.c_int
     lib.pg_gl_text.argtypes = [PgGl, C.c_char_p, C.c_size_t]
     lib.pg_gl_text.restype = C.c_int
+    # path subsets combined on the device (pangenie_amd/calls.py); bins are read as numpy arrays of COMBINED_DTYPE
+    lib.pg_job_combine_plan.argtypes = [C.c_void_p, C.c_uint32, u32p, u32p, C.c_char_p, C.c_size_t]
+    lib.pg_job_combine_plan.restype = C.c_int
+    for name in ("pg_job_combine", "pg_job_combined_calls"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+        getattr(lib, name).restype = C.c_int
+    for name in ("pg_job_fetch_combined", "pg_job_fetch_combined_calls"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_size_t]
+        getattr(lib, name).restype = C.c_int
+    for name in ("pg_job_fetch_combined_all", "pg_job_fetch_combined_calls_all"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+        getattr(lib, name).restype = C.c_int
+    for name in ("pg_job_device_combined", "pg_job_device_combined_calls"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), u64p]
+        getattr(lib, name).restype = C.c_int
+    lib.pg_job_n_groups.argtypes = [C.c_void_p]
+    lib.pg_job_n_groups.restype = C.c_uint32
+    for name in ("pg_job_combine_ms", "pg_job_combined_calls_ms"):
+        getattr(lib, name).argtypes = [C.c_void_p]
+        getattr(lib, name).restype = C.c_double
+    lib.pg_combine_bins.argtypes = [C.c_int, C.c_uint32, u32p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                    C.POINTER(C.c_void_p), C.c_void_p]
+    lib.pg_combine_bins.restype = C.c_int
+    lib.pg_calls_from_combined.argtypes = [C.c_int, C.c_uint32, u32p, u16p, C.c_void_p, C.c_void_p]
+    lib.pg_calls_from_combined.restype = C.c_int
     return lib
 
 
@@ -321,6 +346,9 @@ HIP_ABI_SYMBOLS = [
     "pg_job_record_plan_strided", "pg_job_record_first", "pg_job_fetch_record_calls_packed", "pg_job_fetch_record_gl_packed",
     "pg_sparse_segment", "pg_sparse_stored_by_chain", "pg_sparse_chunk_segment", "pg_sparse_chunk_stored_by_chain", "pg_sparse_piece_range",
     "pg_prep_parts", "pg_prep_part_member", "pg_lean_ring_schedule", "pg_lean_ring_image_offset",
+    "pg_job_combine_plan", "pg_job_combine", "pg_job_fetch_combined", "pg_job_fetch_combined_all", "pg_job_device_combined",
+    "pg_job_combined_calls", "pg_job_fetch_combined_calls", "pg_job_fetch_combined_calls_all", "pg_job_device_combined_calls",
+    "pg_job_n_groups", "pg_job_combine_ms", "pg_job_combined_calls_ms", "pg_combine_bins", "pg_calls_from_combined",
 ]
 
 

@@ -381,3 +381,131 @@ def gl_text(value) -> Optional[str]:
     buf = C.create_string_buffer(32)
     n = lib.pg_gl_text(_lib.PgGl(int(value[0]), int(value[1])), buf, 32)
     return buf.value.decode() if n >= 0 else None
+
+
+# ---------------------------------------------------------------------------------------------------------------
+#  Path subsets combined on the device (pg_job_combine_plan, pg_job_combine, pg_job_combined_calls, pg_combine_bins,
+#  pg_calls_from_combined)
+# ---------------------------------------------------------------------------------------------------------------
+COMBINED_DTYPE = np.dtype([("m", "<u8"), ("e", "<i4"), ("flags", "<u4")])
+PG_COMBINED_PRESENT = 1   # the key exists in the combined map
+PG_COMBINED_DEFERRED = 2  # present, not formed on the device: add this key on the host from the chains' bins
+
+
+def combined_to_longdouble(bins) -> np.ndarray:
+    """ldexpl((long double)m, e) of every bin, which is exact (0 for an absent or deferred bin: ask `flags`)."""
+    b = np.asarray(bins)
+    return np.ldexp(b["m"].astype(np.longdouble), b["e"].astype(np.int64))
+
+
+def job_combine_plan(job, groups) -> None:
+    """pg_job_combine_plan: groups = the chains of every group, in combine order."""
+    groups = [[int(c) for c in g] for g in groups]
+    off = np.zeros(len(groups) + 1, np.uint32)
+    if groups:
+        off[1:] = np.cumsum([len(g) for g in groups])
+    flat = np.array([c for g in groups for c in g] or [0], np.uint32)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_combine_plan(job.h, len(groups), off.ctypes.data_as(_lib.u32p), flat.ctypes.data_as(_lib.u32p), err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    job._combine_groups = groups
+
+
+def job_combine(job) -> None:
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_combine(job.h, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+
+
+def _group_batch(job, group: int):
+    groups = getattr(job, "_combine_groups", None)
+    if groups is None or not 0 <= group < len(groups):
+        from .hmm import PanGenieError
+        raise PanGenieError(_lib.PG_ERR_INVALID, f"group {group}: the job has no such group")
+    return job.batches[groups[group][0]]
+
+
+def fetch_combined(job, group: Optional[int] = None):
+    """pg_job_fetch_combined[_all]: the combined bins (COMBINED_DTYPE) of `group`, or of every group."""
+    err = C.create_string_buffer(_ERRLEN)
+    if group is not None:
+        n = int(_group_batch(job, group).geno_off[-1])
+        out = np.zeros(max(n, 1), COMBINED_DTYPE)
+        rc = job._lib.pg_job_fetch_combined(job.h, group, out.ctypes.data, err, _ERRLEN)
+        if rc:
+            raise _error(rc, err)
+        return out[:n]
+    ns = [int(_group_batch(job, g).geno_off[-1]) for g in range(len(getattr(job, "_combine_groups", [])))]
+    outs = [np.zeros(max(n, 1), COMBINED_DTYPE) for n in ns]
+    arr = (C.c_void_p * max(len(outs), 1))(*[o.ctypes.data for o in outs])
+    rc = job._lib.pg_job_fetch_combined_all(job.h, arr, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return [o[:n] for o, n in zip(outs, ns)]
+
+
+def job_combined_calls(job, group: Optional[int] = None):
+    """Job.combined_calls(): forms the calls of every group from its combined bins, fetches all of them (or `group`'s)."""
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_combined_calls(job.h, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    if group is not None:
+        V = _group_batch(job, group).n_variants
+        out = np.zeros(max(V, 1), CALL_DTYPE)
+        rc = job._lib.pg_job_fetch_combined_calls(job.h, group, out.ctypes.data, err, _ERRLEN)
+        if rc:
+            raise _error(rc, err)
+        return out[:V]
+    Vs = [_group_batch(job, g).n_variants for g in range(len(getattr(job, "_combine_groups", [])))]
+    outs = [np.zeros(max(V, 1), CALL_DTYPE) for V in Vs]
+    arr = (C.c_void_p * max(len(outs), 1))(*[o.ctypes.data for o in outs])
+    rc = job._lib.pg_job_fetch_combined_calls_all(job.h, arr, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return [o[:V] for o, V in zip(outs, Vs)]
+
+
+def combine_bins(allele_off, kept, allele_present, lik, lik_exp, device: int = 0) -> np.ndarray:
+    """pg_combine_bins: the combined bins (COMBINED_DTYPE) of S chains over one layout — kept[s] [V], allele_present[s]
+    [sumA], lik[s] / lik_exp[s] [sum A (A + 1) / 2] of chain s — added up in the order given."""
+    lib = _lib.load_hip()
+    aoff = np.ascontiguousarray(allele_off, np.uint32)
+    V, S = len(aoff) - 1, len(kept)
+    A = np.diff(aoff.astype(np.int64))
+    n_lik = int((A * (A + 1) // 2).sum())
+    if S == 0 or not (len(allele_present) == len(lik) == len(lik_exp) == S):
+        raise ValueError("combine_bins: one kept / allele_present / lik / lik_exp per chain, at least one chain")
+    pad = lambda a, dt: np.ascontiguousarray(a, dt) if len(a) else np.zeros(1, dt)
+    cols = []
+    for s in range(S):
+        if len(kept[s]) != V or len(allele_present[s]) != int(aoff[-1]) or len(lik[s]) != n_lik or len(lik_exp[s]) != n_lik:
+            raise ValueError(f"combine_bins: the arrays of chain {s} do not match allele_off")
+        cols.append((pad(kept[s], np.uint8), pad(allele_present[s], np.uint8), pad(lik[s], np.float64), pad(lik_exp[s], np.int32)))
+    ptrs = [(C.c_void_p * S)(*[c[k].ctypes.data for c in cols]) for k in range(4)]
+    out = np.zeros(max(n_lik, 1), COMBINED_DTYPE)
+    rc = lib.pg_combine_bins(device, V, aoff.ctypes.data_as(_lib.u32p), S, ptrs[0], ptrs[1], ptrs[2], ptrs[3], out.ctypes.data)
+    if rc:
+        raise _error(rc, None)
+    return out[:n_lik]
+
+
+def calls_from_combined(allele_off, allele_id, bins, device: int = 0) -> np.ndarray:
+    """pg_calls_from_combined: the calls (CALL_DTYPE) of V variants from their combined bins (COMBINED_DTYPE)."""
+    lib = _lib.load_hip()
+    aoff = np.ascontiguousarray(allele_off, np.uint32)
+    V = len(aoff) - 1
+    A = np.diff(aoff.astype(np.int64))
+    b = np.ascontiguousarray(bins, COMBINED_DTYPE)
+    if len(allele_id) != int(aoff[-1]) or len(b) != int((A * (A + 1) // 2).sum()):
+        raise ValueError("calls_from_combined: array lengths do not match allele_off")
+    aid = np.ascontiguousarray(allele_id, np.uint16) if len(allele_id) else np.zeros(1, np.uint16)
+    if len(b) == 0:
+        b = np.zeros(1, COMBINED_DTYPE)
+    out = np.zeros(max(V, 1), CALL_DTYPE)
+    rc = lib.pg_calls_from_combined(device, V, aoff.ctypes.data_as(_lib.u32p), aid.ctypes.data_as(_lib.u16p), b.ctypes.data, out.ctypes.data)
+    if rc:
+        raise _error(rc, None)
+    return out[:V]

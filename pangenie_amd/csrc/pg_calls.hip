@@ -13,18 +13,13 @@
 #include <stdint.h>
 
 #include "pg_calls.h"
+#include "pg_calls_dev.h"
 #include "pg_launch.h"
 
 #define PC_BLOCK 256
 #define PC_WAVES (PC_BLOCK / 64)
 
 namespace {
-
-__device__ __forceinline__ unsigned long long pack_call(uint32_t a1, uint32_t a2, uint32_t gq, uint32_t flags) {
-    return (unsigned long long)(a1 & 0xFFFFu) | ((unsigned long long)(a2 & 0xFFFFu) << 16) | ((unsigned long long)(gq & 0xFFFFu) << 32) |
-           ((unsigned long long)(flags & 0xFFFFu) << 48);
-}
-__device__ __forceinline__ unsigned long long pack_no_call(uint32_t flags) { return pack_call(0xFFFFu, 0xFFFFu, 0u, flags); }
 
 // the last descriptor whose first block is <= b (descriptors of chains without variants are not in the list)
 __device__ __forceinline__ uint32_t calls_chain_of(const CallsDesc* __restrict__ desc, uint32_t n, uint32_t b) {
@@ -97,12 +92,6 @@ __global__ __launch_bounds__(PC_BLOCK) void k_calls(const DevContig* __restrict_
         rec = pack_call(c->allele_id[a0 + sa], c->allele_id[a0 + sb], r.gq, PGX_CALL_OK);
     }
     out[v] = rec;
-}
-
-// (value, bin) pairs ordered by value, then by bin: the reference's `>=` keeps the LAST of equal maxima
-__device__ __forceinline__ bool wide_better(pgx q, uint32_t bin, pgx best, uint32_t best_bin) {
-    const int c = pgx_cmp(q, best);
-    return c > 0 || (c == 0 && bin > best_bin);
 }
 
 __global__ __launch_bounds__(PC_BLOCK) void k_calls_wide(const DevContig* __restrict__ contigs, const CallsDesc* __restrict__ desc,

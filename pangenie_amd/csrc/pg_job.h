@@ -1,5 +1,5 @@
 // pg_job.h — what the host units of the C-ABI shim share (pg_shim.cpp: jobs, their build and uploads; pg_shim_run.cpp: the
-// run schedule, pg_job_run; pg_shim_calls.cpp: the output columns formed from a job's finished bins): the error helpers, the
+// run schedule, pg_job_run; pg_shim_calls.cpp: the output columns formed from a job's finished bins; pg_shim_combine.cpp: path subsets combined): the error helpers, the
 // host's picture of a job's index contigs, chains and record plans, struct pg_job itself, and the few helpers upload and run
 // both need.  Private: nothing here is exported.
 #pragma once
@@ -118,6 +118,35 @@ struct OutputFamily {
     void release() { if (d) hipFree(d); d = nullptr; }
 };
 
+// What a job keeps of its combine plan (pg_shim_combine.cpp): the groups, and ONE device buffer outside the
+// arena — the combined bins group after group, the calls, then the group descriptors, the member list, the wide kernels' list,
+// the pairs of the layout check and its word.  A second plan makes a new one.
+struct CombineState {
+    bool planned = false;
+    bool layout_ok = false;                    // k_combine_check has passed the members' layouts as the device holds them
+    std::vector<uint32_t> group_off, members;  // [n_groups + 1], [group_off[n_groups]]: chains in combine order
+    std::vector<uint64_t> bin_first, var_first;   // [n_groups + 1] first bin / first variant of every group
+    std::vector<CombineDesc> desc;             // host copy (groups with variants)
+    std::vector<CombinePair> pairs;
+    unsigned char* d = nullptr;
+    size_t o_calls = 0, o_desc = 0, o_members = 0, o_wide = 0, o_pairs = 0, o_hit = 0;
+    uint32_t blocks = 0, wide = 0, check_items = 0;
+    uint64_t combined_run = 0, calls_run = 0;  // pg_job::run_serial of the run they were formed from (0: none)
+    hipEvent_t ev[2];
+    bool events = false;
+    double ms = 0.0, calls_ms = 0.0;
+    void release() {
+        if (d) hipFree(d);
+        d = nullptr;
+        if (events) { hipEventDestroy(ev[0]); hipEventDestroy(ev[1]); events = false; }
+        planned = false;
+    }
+};
+
+// The genotype-quality thresholds on `device` (pg_shim_calls.cpp: built once from log10l, uploaded once per device; the
+// caller has made `device` current).
+int gq_table_on(int device, const uint64_t** d_m, const int32_t** d_e, char* err, size_t errlen);
+
 }  // namespace pgj
 
 struct pg_job {
@@ -179,6 +208,7 @@ struct pg_job {
     uint64_t up_bytes[2] = {0, 0};
     pg_hmm_params params;
     bool ran = false;
+    uint64_t run_serial = 0;   // counts the finished pg_job_run calls: what was formed from a run's bins remembers which
     // Sweep mode.  fused: phase 2 forms the posterior partials inline (k_bins reduces them) — least
     // HBM traffic, the choice when hundreds of chains fill the chip.  chunked: with few chains the
     // chip is idle and a chain's time is its per-column latency, so phase 2 runs as store-only
@@ -272,6 +302,8 @@ struct pg_job {
     // Record GLs (pg_job_record_gl): 4 bytes per genotype of every record's defined alleles, chain after chain, under the same plans.
     pgj::OutputFamily rgl;                    // (first: the first VALUE of every chain)
     std::vector<RGlDesc> rgl_desc;
+    // Path subsets combined on the device (pg_job_combine_plan / pg_job_combine / pg_job_combined_calls).
+    pgj::CombineState combine;
 };
 
 namespace pgj __attribute__((visibility("hidden"))) {
@@ -281,6 +313,7 @@ inline void record_plans_changed(pg_job* job) {
     job->rcalls.dirty = true;
     job->rgl.dirty = true;
     job->rplan_ids_ok = false;
+    job->combine.layout_ok = false;   // (the members' layouts are compared again before the next combine)
 }
 
 // Group B's copies of a pipelined first run (pg_job::late_threads) read the caller's arrays and feed the job's second stream:

@@ -1,4 +1,4 @@
-// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp, pg_shim_run.cpp, pg_shim_calls.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip, pg_calls.hip).
+// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp, pg_shim_run.cpp, pg_shim_calls.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip, pg_calls.hip, pg_combine.hip).
 //
 // The ONE declaration of every host-callable launcher and of the two launch masks a job hands them.  Both sides include
 // it: a launcher whose parameter list changes on one side only no longer compiles (C linkage: the linker would not notice).
@@ -75,6 +75,23 @@ struct RGlDesc {
     RecPlanDev plan;
 };
 
+// Combined groups (pg_combine.hip): one descriptor per group that has variants, in group order.  The chains of a
+// group — members[first .. first + S), indices into the DevContig array in combine order — share one layout (allele_off,
+// allele_id, geno_off: read from the first).  Blocks [blk0, next blk0) of k_combine and of k_ccalls take pgk_combine_block()
+// variants of the group each; `bins` = the group's 16-byte combined bins (pg_combined_bin [geno_off[V]]), `calls` = its
+// 8-byte records (pg_call [V]).
+struct CombineDesc {
+    uint32_t blk0, V;
+    uint32_t first, S;
+    void* bins;
+    void* calls;
+};
+// The layout check (k_combine_check): member `member` against the first chain of its group, `ref`; both hold V + 1 offsets
+// and sumA allele ids.
+struct CombinePair {
+    uint32_t ref, member, V, sumA;
+};
+
 extern "C" {
 // pg_calls.hip: the lists and staging slots of pgk_launch_rcalls, descriptors with the GL buffers
 void pgk_launch_rgl(const DevContig* d_contigs, const RGlDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide, uint32_t n_wide,
@@ -92,6 +109,14 @@ void pgk_launch_rplan_ids(const DevContig* d_contigs, const RCallsDesc* d_desc, 
 void pgk_launch_calls(const DevContig* d_contigs, const CallsDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide, uint32_t n_wide,
                       const uint64_t* d_thr_m, const int32_t* d_thr_e, hipStream_t s);
 uint32_t pgk_calls_block(void);
+// pg_combine.hip: d_wide = uint2 {descriptor, variant} of every variant with more than PG_AMAX alleles (the wave-per-variant kernels' list)
+void pgk_launch_combine(const DevContig* d_contigs, const CombineDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const uint32_t* d_members,
+                        const void* d_wide, uint32_t n_wide, hipStream_t s);
+void pgk_launch_ccalls(const DevContig* d_contigs, const CombineDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const uint32_t* d_members,
+                       const void* d_wide, uint32_t n_wide, const uint64_t* d_thr_m, const int32_t* d_thr_e, hipStream_t s);
+// k_combine_check: *d_hit (4 bytes, 0 going in) = 1 + the number of a pair whose allele_off or allele_id differ
+void pgk_launch_combine_check(const DevContig* d_contigs, const CombinePair* d_pairs, uint32_t n_pairs, uint32_t max_items, uint32_t* d_hit, hipStream_t s);
+uint32_t pgk_combine_block(void);
 // pg_kernels.hip
 void pgk_launch_prep(const DevContig* d_contigs, uint32_t n_contigs, uint32_t max_v, uint32_t max_w, uint32_t max_m4, DevTable tab, hipStream_t s);
 void pgk_launch_compact(const DevContig* d_contigs, uint32_t n_contigs, hipStream_t s);

@@ -57,8 +57,10 @@ struct GqTables {
     unsigned char* dev[PG_MAX_DEVICES_HOST] = {nullptr};
 } g_gq;
 
-// (the caller has made `device` current)
-int gq_table_on(int device, const uint64_t** d_m, const int32_t** d_e, char* err, size_t errlen) {
+}  // namespace
+
+// (the caller has made `device` current; declared in pg_job.h: pg_shim_combine.cpp asks for the table too)
+int pgj::gq_table_on(int device, const uint64_t** d_m, const int32_t** d_e, char* err, size_t errlen) {
     if (device < 0 || device >= PG_MAX_DEVICES_HOST) { set_err(err, errlen, "device %d out of range", device); return PG_ERR_INVALID; }
     std::lock_guard<std::mutex> lock(g_gq.mu);
     if (!g_gq.built) {
@@ -82,6 +84,8 @@ int gq_table_on(int device, const uint64_t** d_m, const int32_t** d_e, char* err
     *d_e = (const int32_t*)(g_gq.dev[device] + off_e);
     return PG_OK;
 }
+
+namespace {
 
 // What every "form this family's output" opens with: the job has run a genotyping (`from_bins`: what the bins would have
 // been for, for the message), its device is current, the GQ thresholds are on it where the family wants them (d_tm non-null)

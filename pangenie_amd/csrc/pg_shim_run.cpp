@@ -440,6 +440,7 @@ int read_errors(pg_job* job, double t_run, char* err, size_t errlen) {
         for (uint32_t i = 0; i < n; ++i) { ncols[i] = nc_ix[job->chains[i].index]; errs[i] |= err_ix[job->chains[i].index]; }
     }
     job->ran = true;
+    ++job->run_serial;
     job->host_s[2] = now_s() - t_run;
     for (uint32_t i = 0; i < n; ++i) {
         job->chains[i].n_cols_host = ncols[i];

@@ -442,6 +442,37 @@ class Job:
         from . import calls as _calls
         return _calls.fetch_record_gl_packed(self)
 
+    def combine_plan(self, groups) -> None:
+        """pg_job_combine_plan: groups = per group the chains (contig x path subset) that genotype the same index objects, in the
+        order they are to be added up; a second plan replaces the first."""
+        from . import calls as _calls
+        _calls.job_combine_plan(self, groups)
+
+    def combine(self) -> None:
+        """pg_job_combine: adds up every group's chains key by key on the device, from the bins of the last run()."""
+        from . import calls as _calls
+        _calls.job_combine(self)
+
+    def combined(self, group: Optional[int] = None):
+        """pg_job_fetch_combined[_all]: the combined bins of `group` (or of every group) as a structured array m, e, flags
+        (calls.COMBINED_DTYPE; calls.combined_to_longdouble gives the values); after combine()."""
+        from . import calls as _calls
+        return _calls.fetch_combined(self, group)
+
+    def combined_calls(self, group: Optional[int] = None):
+        """pg_job_combined_calls + pg_job_fetch_combined_calls[_all]: GT and GQ per variant of every group from its combined
+        bins (calls.CALL_DTYPE per group, or `group`'s alone); after combine()."""
+        from . import calls as _calls
+        return _calls.job_combined_calls(self, group)
+
+    def combine_ms(self) -> float:
+        """elapsed ms of the kernels of the last combine()"""
+        return float(self._lib.pg_job_combine_ms(self.h))
+
+    def combined_calls_ms(self) -> float:
+        """elapsed ms of the kernels of the last combined_calls()"""
+        return float(self._lib.pg_job_combined_calls_ms(self.h))
+
     def viterbi_ms(self) -> float:
         """elapsed ms of the Viterbi kernels (run_phasing) of the last run"""
         return float(self._lib.pg_job_viterbi_ms(self.h))

@@ -831,6 +831,169 @@ std::vector<std::map<std::string, std::vector<GenotypeCall>>> genotype_cohort_ca
     return out;
 }
 
+// ------------------------------------------------------------------ path subsets: one job, combined on the device
+namespace {
+
+// The -a flow as ONE job: chain c * S + s = chromosome c over subsets[s]; group c = its S chains in the order of `subsets`.
+struct SubsetsRun {
+    size_t C = 0, S = 0;
+    std::vector<std::string> names;
+    std::vector<FlatContig> flat;              // [C * S]
+    std::vector<std::vector<uint64_t>> goff;   // [C]
+    pg_job* job = nullptr;
+    char err[512] = {0};
+    ~SubsetsRun() { if (job) pg_job_destroy(job); }
+
+    void run(std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::vector<std::vector<unsigned short>>& subsets,
+             ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device) {
+        C = chromosomes.size(); S = subsets.size();
+        flat.resize(C * S);
+        goff.resize(C);
+        std::vector<pg_contig_batch> batches(C * S);
+        std::vector<uint32_t> group_off(C + 1, 0), chains(C * S);
+        size_t c = 0;
+        for (auto& kv : chromosomes) {
+            names.push_back(kv.first);
+            for (size_t s = 0; s < S; ++s) {
+                std::vector<unsigned short> paths = subsets[s];
+                flatten(&kv.second, &paths, flat[c * S + s]);
+                batches[c * S + s] = flat[c * S + s].batch;
+                chains[c * S + s] = (uint32_t)(c * S + s);
+            }
+            goff[c].assign(flat[c * S].variant_pos.size() + 1, 0);
+            pg_hmm_geno_offsets(&flat[c * S].batch, goff[c].data());
+            group_off[c + 1] = (uint32_t)((c + 1) * S);
+            c += 1;
+        }
+        pg_hmm_params prm{};
+        prm.effective_N = effective_N; prm.recombrate = recombrate; prm.uniform = uniform ? 1 : 0; prm.run_genotyping = 1;
+        int rc = pg_job_new(device, (uint32_t)(C * S), batches.data(), probabilities->handle(), &prm, &job, err, sizeof(err));
+        if (rc == PG_OK) rc = pg_job_run(job, nullptr, err, sizeof(err));
+        if (rc == PG_OK) rc = pg_job_combine_plan(job, (uint32_t)C, group_off.data(), chains.data(), err, sizeof(err));
+        if (rc == PG_OK) rc = pg_job_combine(job, err, sizeof(err));
+        check_rc(rc, err);
+    }
+
+    // chromosome c on the host route: every subset's chain from its fetched bins, combine_likelihoods in the order of the subsets
+    std::vector<GenotypingResult> combined_on_host(size_t c) {
+        std::vector<GenotypingResult> total;
+        const uint64_t n = goff[c].back();
+        std::vector<double> lik(n ? n : 1);
+        std::vector<int32_t> lexp(n ? n : 1);
+        for (size_t s = 0; s < S; ++s) {
+            pg_contig_result res{};
+            res.lik = lik.data(); res.lik_exp = lexp.data();
+            check_rc(pg_job_fetch(job, (uint32_t)(c * S + s), &res, err, sizeof(err)), err);
+            const FlatContig& f = flat[c * S + s];
+            static const uint16_t none = 0;
+            std::vector<GenotypingResult> one = results_of_chain(f, f.coverage.empty() ? &none : f.coverage.data(), goff[c], lik.data(), lexp.data());
+            if (s == 0) total = std::move(one);
+            else for (size_t v = 0; v < total.size(); ++v) total[v].combine(one[v]);
+        }
+        return total;
+    }
+};
+
+}  // namespace
+
+std::map<std::string, std::vector<GenotypingResult>> genotype_subsets(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::vector<std::vector<unsigned short>>& subsets,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device, bool normalize) {
+    std::map<std::string, std::vector<GenotypingResult>> out;
+    if (subsets.empty()) fail("genotype_subsets: no subsets of paths");
+    if (chromosomes.empty()) return out;
+    SubsetsRun R;
+    R.run(chromosomes, subsets, probabilities, recombrate, uniform, effective_N, device);
+    const size_t C = R.C, S = R.S;
+    // all combined bins with one synchronisation
+    std::vector<std::vector<pg_combined_bin>> bins(C);
+    std::vector<pg_combined_bin*> ptrs(C, nullptr);
+    for (size_t c = 0; c < C; ++c) {
+        bins[c].resize(R.goff[c].back());
+        ptrs[c] = bins[c].empty() ? nullptr : bins[c].data();
+    }
+    check_rc(pg_job_fetch_combined_all(R.job, ptrs.data(), R.err, sizeof(R.err)), R.err);
+    for (size_t c = 0; c < C; ++c) {
+        const FlatContig& f = R.flat[c * S];
+        const size_t V = f.variant_pos.size();
+        std::vector<GenotypingResult>& res = out[R.names[c]];
+        res.resize(V);
+        // unique_kmers and coverage are those of the first chain (GenotypingResult::combine leaves them alone)
+        std::vector<uint16_t> n_kmers(V ? V : 1), cov(V ? V : 1);
+        pg_contig_result first{};
+        first.n_kmers = n_kmers.data(); first.coverage = cov.data();
+        check_rc(pg_job_fetch(R.job, (uint32_t)(c * S), &first, R.err, sizeof(R.err)), R.err);
+        std::vector<size_t> deferred;
+        for (size_t v = 0; v < V; ++v) {
+            GenotypingResult& g = res[v];
+            const uint32_t a0 = f.allele_off[v], A = f.allele_off[v + 1] - a0;
+            const pg_combined_bin* b = bins[c].data() + R.goff[c][v];
+            bool any_deferred = false;
+            for (uint32_t x = 0; x < A; ++x)
+                for (uint32_t y = x; y < A; ++y, ++b) {
+                    if (!(b->flags & PG_COMBINED_PRESENT)) continue;
+                    if (b->flags & PG_COMBINED_DEFERRED) { any_deferred = true; continue; }
+                    g.add_to_likelihood(f.allele_id[a0 + x], f.allele_id[a0 + y], ldexpl((long double)b->m, b->e));   // exact
+                }
+            g.set_unique_kmers(n_kmers[v]);
+            g.set_coverage(cov[v]);
+            if (any_deferred) deferred.push_back(v);
+        }
+        if (!deferred.empty()) {   // keys next to long double's subnormals: those variants from the chains' own bins
+            std::vector<GenotypingResult> full = R.combined_on_host(c);
+            for (size_t v : deferred) {
+                full[v].set_unique_kmers(n_kmers[v]);
+                full[v].set_coverage(cov[v]);
+                res[v] = full[v];
+            }
+        }
+        if (normalize) for (GenotypingResult& g : res) g.normalize();
+    }
+    return out;
+}
+
+std::map<std::string, std::vector<GenotypeCall>> genotype_subsets_calls(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::vector<std::vector<unsigned short>>& subsets,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device) {
+    std::map<std::string, std::vector<GenotypeCall>> out;
+    if (subsets.empty()) fail("genotype_subsets_calls: no subsets of paths");
+    if (chromosomes.empty()) return out;
+    SubsetsRun R;
+    R.run(chromosomes, subsets, probabilities, recombrate, uniform, effective_N, device);
+    check_rc(pg_job_combined_calls(R.job, R.err, sizeof(R.err)), R.err);
+    const size_t C = R.C, S = R.S;
+    std::vector<std::vector<pg_call>> recs(C);
+    std::vector<pg_call*> ptrs(C, nullptr);
+    for (size_t c = 0; c < C; ++c) {
+        recs[c].resize(R.flat[c * S].variant_pos.size());
+        ptrs[c] = recs[c].empty() ? nullptr : recs[c].data();
+    }
+    check_rc(pg_job_fetch_combined_calls_all(R.job, ptrs.data(), R.err, sizeof(R.err)), R.err);
+    for (size_t c = 0; c < C; ++c) {
+        const std::vector<pg_call>& r = recs[c];
+        std::vector<GenotypeCall>& calls = out[R.names[c]];
+        calls.resize(r.size());
+        bool any_deferred = false;
+        for (size_t v = 0; v < r.size(); ++v) {
+            if (r[v].flags == PG_CALL_OK) { calls[v].allele_1 = r[v].allele_1; calls[v].allele_2 = r[v].allele_2; calls[v].quality = r[v].gq; }
+            else if (r[v].flags == PG_CALL_DEFERRED) any_deferred = true;
+        }
+        if (!any_deferred) continue;
+        std::vector<GenotypingResult> full = R.combined_on_host(c);
+        for (size_t v = 0; v < r.size(); ++v) {
+            if (r[v].flags != PG_CALL_DEFERRED) continue;
+            full[v].normalize();
+            const std::pair<int, int> g = full[v].get_likeliest_genotype();
+            calls[v].deferred = true;
+            if (g.first >= 0 && g.second >= 0) {
+                calls[v].allele_1 = g.first; calls[v].allele_2 = g.second;
+                calls[v].quality = full[v].get_genotype_quality((unsigned short)g.first, (unsigned short)g.second);
+            }
+        }
+    }
+    return out;
+}
+
 // ------------------------------------------------------------------ cohort job, calls per VCF record
 // GT and GQ of one record as genotype_field prints them (graph.cpp:217-273), without the text
 static GenotypeCall record_call_on_host(const VcfSite& site) {

@@ -351,6 +351,26 @@ std::vector<std::map<std::string, std::vector<GenotypeCall>>> genotype_cohort_ca
     std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::vector<SampleCounts>& samples,
     ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0);
 
+/** The `-a` flow of one sample (reference src/commands.cpp:923-987: every chromosome genotyped once per subset of paths, the
+ *  subsets' unnormalised likelihoods added up by run_genotyping, :163-177, normalised at the end): chromosomes x subsets as ONE
+ *  device job, the chains of a chromosome combined ON THE DEVICE in the order of `subsets` (C ABI pg_job_combine, DESIGN.md
+ *  4e-4).  Per chromosome, what HMM(&objects, probabilities, true, false, recombrate, uniform, effective_N, &subsets[s], false)
+ *  gives per subset s, combine_likelihoods in the order of `subsets` and — `normalize` — normalize(): every long double the
+ *  same, the same keys, unique_kmers / coverage of the first subset's.  16 bytes per combined bin come back instead of 12 per
+ *  bin and subset; a key the device leaves to the host (PG_COMBINED_DEFERRED) is added up here from that variant's chain bins —
+ *  the caller never sees it.  Throws std::runtime_error for no subsets and on the C ABI's errors. */
+std::map<std::string, std::vector<GenotypingResult>> genotype_subsets(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::vector<std::vector<unsigned short>>& subsets,
+    ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
+    bool normalize = true);
+
+/** genotype_subsets for a caller who wants calls: the same job and combine, then one 8-byte record per variant from the
+ *  combined bins (pg_job_combined_calls).  Element v is what normalize() / get_likeliest_genotype() / get_genotype_quality()
+ *  give on element v of genotype_subsets(..., normalize = false); a PG_CALL_DEFERRED variant is formed here (GenotypeCall::deferred). */
+std::map<std::string, std::vector<GenotypeCall>> genotype_subsets_calls(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::vector<std::vector<unsigned short>>& subsets,
+    ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0);
+
 // ------------------------------------------------------------------ haplotype sampling (include/pangenie_sampler.h)
 /** reference src/haplotypesampler.hpp:16-59 */
 struct SampledPaths {
