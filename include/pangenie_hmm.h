@@ -592,6 +592,47 @@ int  pg_combine_bins(int device, uint32_t n_variants, const uint32_t* allele_off
 int  pg_calls_from_combined(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id,
                             const pg_combined_bin* bins, pg_call* out);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ *  Path subsets to VCF lines: GT, GQ and the GL column per VCF RECORD from the combined bins
+ *  (pangenie_amd/csrc/pg_combine_records.hip).  For record r of variant v of group g, under the
+ *  record plan of the index contig of the group's FIRST chain (pg_job_record_plan / pg_job_record_plan_strided), the
+ *  fields are what Graph::write_genotypes prints for GenotypingResult::combine of the members in group order:
+ *  normalize() of the combined map (the bins with PG_COMBINED_PRESENT, value m 2^e), the fold onto the record's alleles,
+ *  an empty result as L(0/0) = 1, get_specific_likelihoods over the defined alleles, then likeliest genotype and quality
+ *  (pg_call: allele_1 <= allele_2 are GT numbers, PG_CALL_EMPTY as in pg_job_record_calls) and setprecision(4) of
+ *  log10 L (pg_gl, laid out by pg_record_gl_offsets).  A variant with a PG_COMBINED_DEFERRED bin makes every one of
+ *  its records PG_CALL_DEFERRED and every one of its values PG_GL_DEFERRED; the other deferral rules are those of
+ *  pg_job_record_calls / pg_job_record_gl.
+ *  A group whose first chain's index contig has no plan is left out (no records); the other members need none.
+ *  Both calls run on the job's stream and block; their buffers lie outside the arena, allocated on first use
+ *  (PG_ERR_NOMEM).  PG_ERR_INVALID without a combine plan, before pg_job_combine of the same run, when no group has
+ *  a plan, and for an allele id of a group's first chain outside a map of its plan (checked on the device before the
+ *  first formation and again after a new record plan, combine plan, index upload or pg_job_combine; the message names
+ *  group and variant).  Each of those four also invalidates what was formed.
+ * --------------------------------------------------------------------------------------------------------------- */
+int  pg_job_combined_record_calls(pg_job* job, char* err, size_t errlen);
+int  pg_job_combined_record_gl(pg_job* job, char* err, size_t errlen);
+/* Group `group`'s records / values (a group without a plan has none: out may be NULL). */
+int  pg_job_fetch_combined_record_calls(pg_job* job, uint32_t group, pg_call* out, char* err, size_t errlen);
+int  pg_job_fetch_combined_record_gl(pg_job* job, uint32_t group, pg_gl* out, char* err, size_t errlen);
+/* Every group's, outs[g] (NULL allowed for a group without records), copies queued on the job's stream, one wait. */
+int  pg_job_fetch_combined_record_calls_all(pg_job* job, pg_call* const* outs, char* err, size_t errlen);
+int  pg_job_fetch_combined_record_gl_all(pg_job* job, pg_gl* const* outs, char* err, size_t errlen);
+/* Device-resident records / values of group `group` and their number. */
+int  pg_job_device_combined_record_calls(pg_job* job, uint32_t group, void** d_calls, uint64_t* n);
+int  pg_job_device_combined_record_gl(pg_job* job, uint32_t group, void** d_gl, uint64_t* n);
+/* Elapsed milliseconds of the kernels of the LAST formation. */
+double pg_job_combined_record_calls_ms(const pg_job* job);
+double pg_job_combined_record_gl_ms(const pg_job* job);
+/* Unit entry points, through the same kernels: one contig's combined bins (as pg_calls_from_combined takes them) and a
+ * plan; out[plan->n_records] records / out[gl_off[n_records]] values.  Checked on the host first: the layout, the plan
+ * (PG_ERR_INVALID; PG_ERR_UNSUPPORTED for a record of more than 256 alleles), every allele id against the plan's maps,
+ * the bins, `out`; then PG_ERR_DEVICE without a device.  No host fallback. */
+int  pg_record_calls_from_combined(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id,
+                                   const pg_combined_bin* bins, const pg_record_plan* plan, pg_call* out);
+int  pg_record_gl_from_combined(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id,
+                                const pg_combined_bin* bins, const pg_record_plan* plan, pg_gl* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -323,6 +323,25 @@ def _bind_hip(lib):
     lib.pg_combine_bins.restype = C.c_int
     lib.pg_calls_from_combined.argtypes = [C.c_int, C.c_uint32, u32p, u16p, C.c_void_p, C.c_void_p]
     lib.pg_calls_from_combined.restype = C.c_int
+    # ... and GT, GQ and GL per VCF record of the combined groups
+    for name in ("pg_job_combined_record_calls", "pg_job_combined_record_gl"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+        getattr(lib, name).restype = C.c_int
+    for name in ("pg_job_fetch_combined_record_calls", "pg_job_fetch_combined_record_gl"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_size_t]
+        getattr(lib, name).restype = C.c_int
+    for name in ("pg_job_fetch_combined_record_calls_all", "pg_job_fetch_combined_record_gl_all"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+        getattr(lib, name).restype = C.c_int
+    for name in ("pg_job_device_combined_record_calls", "pg_job_device_combined_record_gl"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), u64p]
+        getattr(lib, name).restype = C.c_int
+    for name in ("pg_job_combined_record_calls_ms", "pg_job_combined_record_gl_ms"):
+        getattr(lib, name).argtypes = [C.c_void_p]
+        getattr(lib, name).restype = C.c_double
+    for name in ("pg_record_calls_from_combined", "pg_record_gl_from_combined"):
+        getattr(lib, name).argtypes = [C.c_int, C.c_uint32, u32p, u16p, C.c_void_p, C.c_void_p, C.c_void_p]
+        getattr(lib, name).restype = C.c_int
     return lib
 
 
@@ -349,6 +368,10 @@ HIP_ABI_SYMBOLS = [
     "pg_job_combine_plan", "pg_job_combine", "pg_job_fetch_combined", "pg_job_fetch_combined_all", "pg_job_device_combined",
     "pg_job_combined_calls", "pg_job_fetch_combined_calls", "pg_job_fetch_combined_calls_all", "pg_job_device_combined_calls",
     "pg_job_n_groups", "pg_job_combine_ms", "pg_job_combined_calls_ms", "pg_combine_bins", "pg_calls_from_combined",
+    "pg_job_combined_record_calls", "pg_job_combined_record_gl", "pg_job_fetch_combined_record_calls", "pg_job_fetch_combined_record_gl",
+    "pg_job_fetch_combined_record_calls_all", "pg_job_fetch_combined_record_gl_all", "pg_job_device_combined_record_calls",
+    "pg_job_device_combined_record_gl", "pg_job_combined_record_calls_ms", "pg_job_combined_record_gl_ms",
+    "pg_record_calls_from_combined", "pg_record_gl_from_combined",
 ]
 
 

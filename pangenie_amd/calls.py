@@ -509,3 +509,89 @@ def calls_from_combined(allele_off, allele_id, bins, device: int = 0) -> np.ndar
     if rc:
         raise _error(rc, None)
     return out[:V]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+#  GT, GQ and GL per VCF record of the combined groups (pg_job_combined_record_calls, pg_job_combined_record_gl,
+#  pg_record_calls_from_combined, pg_record_gl_from_combined)
+# ---------------------------------------------------------------------------------------------------------------
+def _group_plans(job) -> list:
+    """the record plan of every group: that of its first chain's index contig, or None"""
+    plans, nc = getattr(job, "_record_plans", {}), len(job.index)
+    return [plans.get(g[0] % nc) for g in getattr(job, "_combine_groups", [])]
+
+
+def _combined_records(job, group: Optional[int], gl: bool):
+    lib, err = job._lib, C.create_string_buffer(_ERRLEN)
+    form, fetch, fetch_all = ((lib.pg_job_combined_record_gl, lib.pg_job_fetch_combined_record_gl, lib.pg_job_fetch_combined_record_gl_all) if gl else
+                              (lib.pg_job_combined_record_calls, lib.pg_job_fetch_combined_record_calls, lib.pg_job_fetch_combined_record_calls_all))
+    rc = form(job.h, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    dtype = GL_DTYPE if gl else CALL_DTYPE
+    cache = job.__dict__.setdefault("_group_gl_counts", {})   # (pg_record_gl_offsets checks the whole plan: once per plan, not per fetch)
+
+    def count(p):
+        if p is None:
+            return 0
+        if not gl:
+            return p.n_records
+        if cache.get(id(p), (None, 0))[0] is not p:
+            cache[id(p)] = (p, int(record_gl_offsets(p)[-1]))
+        return cache[id(p)][1]
+    plans = _group_plans(job)
+    if group is not None:
+        _group_batch(job, group)   # (raises for a group the job does not have)
+        n = count(plans[group])
+        out = np.zeros(max(n, 1), dtype)
+        rc = fetch(job.h, group, out.ctypes.data, err, _ERRLEN)
+        if rc:
+            raise _error(rc, err)
+        return out[:n]
+    ns = [count(p) for p in plans]
+    outs = [np.zeros(max(n, 1), dtype) for n in ns]
+    arr = (C.c_void_p * max(len(outs), 1))(*[o.ctypes.data for o in outs])
+    rc = fetch_all(job.h, arr, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return [o[:n] for o, n in zip(outs, ns)]
+
+
+def job_combined_record_calls(job, group: Optional[int] = None):
+    """Job.combined_record_calls(): forms GT and GQ per VCF record of every group that has a plan, fetches all of them (or `group`'s)."""
+    return _combined_records(job, group, False)
+
+
+def job_combined_record_gl(job, group: Optional[int] = None):
+    """Job.combined_record_gl(): forms the GL values per VCF record of every group that has a plan, fetches all of them (or `group`'s)."""
+    return _combined_records(job, group, True)
+
+
+def _records_from_combined(name: str, allele_off, allele_id, bins, plan: RecordPlan, n_out: int, dtype, device: int) -> np.ndarray:
+    lib = _lib.load_hip()
+    aoff = np.ascontiguousarray(allele_off, np.uint32)
+    V = len(aoff) - 1
+    A = np.diff(aoff.astype(np.int64))
+    b = np.ascontiguousarray(bins, COMBINED_DTYPE)
+    if len(allele_id) != int(aoff[-1]) or len(b) != int((A * (A + 1) // 2).sum()):
+        raise ValueError(f"{name}: array lengths do not match allele_off")
+    aid = np.ascontiguousarray(allele_id, np.uint16) if len(allele_id) else np.zeros(1, np.uint16)
+    if len(b) == 0:
+        b = np.zeros(1, COMBINED_DTYPE)
+    out = np.zeros(max(n_out, 1), dtype)
+    c = plan.as_c()
+    rc = getattr(lib, "pg_" + name)(device, V, aoff.ctypes.data_as(_lib.u32p), aid.ctypes.data_as(_lib.u16p), b.ctypes.data, C.addressof(c), out.ctypes.data)
+    if rc:
+        raise _error(rc, None)
+    return out[:n_out]
+
+
+def record_calls_from_combined(allele_off, allele_id, bins, plan: RecordPlan, device: int = 0) -> np.ndarray:
+    """pg_record_calls_from_combined: the calls (CALL_DTYPE) of the plan's records from one contig's combined bins (COMBINED_DTYPE)."""
+    return _records_from_combined("record_calls_from_combined", allele_off, allele_id, bins, plan, plan.n_records, CALL_DTYPE, device)
+
+
+def record_gl_from_combined(allele_off, allele_id, bins, plan: RecordPlan, device: int = 0) -> np.ndarray:
+    """pg_record_gl_from_combined: the GL values (GL_DTYPE) of the plan's records from one contig's combined bins; record r's
+    values at record_gl_offsets(plan)[r] ..."""
+    return _records_from_combined("record_gl_from_combined", allele_off, allele_id, bins, plan, int(record_gl_offsets(plan)[-1]), GL_DTYPE, device)

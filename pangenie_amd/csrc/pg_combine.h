@@ -109,6 +109,50 @@ struct pgc_keys {
     }
 };
 
+// The keys of one variant's combined map for pgx_decide_record and pgx_record_gl: the present bins in bin
+// order as pgc_keys walks them, each with the record alleles its two slots carry — key = (ra << 16) | rb, ra <= rb.
+// Presence is the bin's flag: the union over the chains knows no allele mask (subsets that carry {0,1} and {0,2} leave no
+// key (1,2)).  A PG_COMBINED_DEFERRED bin reads 0; the caller asks any_deferred() first and answers for the whole variant.
+// `Own`: own(s) = the record allele of slot s.  The lane-per-record kernels keep a byte per slot in one 64-bit register
+// (pgc_own_packed: at most 8 slots, PG_AMAX is 5); tests/cpp/test_combined_records_arith.cpp walks wider bubbles over an array.
+struct pgc_own_packed {
+    unsigned long long w;   // byte s: the record allele of slot s
+    PGC_MEMBER uint32_t operator()(uint32_t s) const { return (uint32_t)(w >> (8u * s)) & 0xFFu; }
+};
+struct pgc_own_array {
+    const uint16_t* of_slot;
+    PGC_MEMBER uint32_t operator()(uint32_t s) const { return of_slot[s]; }
+};
+template <class Own>
+struct pgc_record_keys_of {
+    const pg_combined_bin* bins;   // the variant's first bin
+    uint32_t A;
+    Own own;
+    uint32_t a, b, bin;
+    PGC_MEMBER void start() { a = 0; b = 0; bin = 0; }
+    PGC_MEMBER bool next(pgx* v, uint32_t* key) {
+        while (a < A) {
+            const uint32_t ca = a, cb = b;
+            const pg_combined_bin x = bins[bin++];
+            if (++b == A) { ++a; b = a; }
+            if (!(x.flags & PG_COMBINED_PRESENT)) continue;
+            const uint32_t oa = own(ca), ob = own(cb);
+            const bool value = !(x.flags & PG_COMBINED_DEFERRED) && x.m != 0;
+            v->m = value ? x.m : 0;
+            v->e = value ? x.e : 0;
+            *key = oa <= ob ? (oa << 16) | ob : (ob << 16) | oa;
+            return true;
+        }
+        return false;
+    }
+    PGC_MEMBER bool any_deferred() const {
+        bool d = false;
+        for (uint32_t i = 0; i < A * (A + 1u) / 2u; ++i) d = d || (bins[i].flags & PG_COMBINED_DEFERRED) != 0;
+        return d;
+    }
+};
+typedef pgc_record_keys_of<pgc_own_packed> pgc_record_keys;
+
 // allele slots (a <= b) of bin number `bin` of a variant with A alleles
 PGX_FN void pgc_slots_of_bin(uint32_t A, uint32_t bin, uint32_t* sa, uint32_t* sb) {
     uint32_t a = 0, rest = bin;

@@ -9,6 +9,9 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <string.h>
+
+#include <algorithm>
 #include <chrono>
 #include <memory>
 #include <string>
@@ -103,6 +106,63 @@ inline RecordPlanRef record_plan_ref(RecordPlanHost&& h) {
     return RecordPlanRef(new RecordPlanHost(std::move(h)), [](const RecordPlanHost* p) { if (p->d) hipFree(p->d); delete p; });
 }
 
+// The record plans' checks and device copies (pg_shim_calls.cpp), shared by the record families of single chains and of
+// combined groups.  check_record_plan: everything that needs the plan alone, and the host copy; check_record_plan_ids: every
+// allele id of the contig's bubbles has an entry in the map of each of the bubble's records.
+int check_record_plan(const pg_record_plan* p, uint32_t V, RecordPlanHost* h, char* err, size_t errlen);
+int check_record_plan_ids(const RecordPlanHost& h, const uint32_t* allele_off, const uint16_t* allele_id, char* err, size_t errlen);
+size_t record_plan_device_bytes(const RecordPlanHost& h);
+bool record_plan_upload(const RecordPlanHost& h, unsigned char* d, RecPlanDev* dev);   // d: record_plan_device_bytes of room
+std::vector<uint64_t> record_gl_offsets(const RecordPlanHost& h);                        // [R + 1] first GL value of every record
+
+// The wave-per-record kernel stages a bubble's quotients and a record's folded map in device memory: one slot of `stride`
+// 16-byte values per block, at most 1024 blocks and 256 MB (a 256-allele bubble: 32 896 bins and as many keys, 1 MB a slot).
+struct RcallsLaunch {
+    std::vector<uint64_t> first;
+    std::vector<RCallsDesc> desc;
+    std::vector<uint32_t> wide;   // {descriptor, record} pairs
+    uint32_t n_blocks = 0, max_bins = 0, stride = 0, n_slots = 0;
+};
+// planOf(c): the plan of chain c's index contig or nullptr; aoff(c): the chain's allele_off; per: records per block of the
+// lane-per-record kernel.  (pg_shim_combine.cpp plans the records of combined groups with it: a group where this says chain.)
+template <class PlanOf, class AoffOf>
+void plan_rcalls(uint32_t n_chains, PlanOf planOf, AoffOf aoff, uint32_t per, RcallsLaunch* L) {
+    L->first.assign((size_t)n_chains + 1, 0);
+    L->desc.clear();
+    L->wide.clear();
+    uint32_t blk = 0;
+    uint64_t max_bins = 0, max_keys = 0;
+    for (uint32_t c = 0; c < n_chains; ++c) {
+        const RecordPlanHost* h = planOf(c);
+        const uint32_t R = h ? h->R : 0;
+        L->first[c + 1] = L->first[c] + R;
+        if (R == 0) continue;
+        RCallsDesc d;
+        memset(&d, 0, sizeof(d));
+        d.blk0 = blk; d.R = R; d.chain = c;
+        d.plan = h->dev;
+        const uint32_t* off = aoff(c);
+        for (uint32_t v = 0; v < h->V; ++v) {
+            const uint64_t A = off[v + 1] - off[v];
+            if (A <= PG_AMAX) continue;
+            for (uint32_t q = h->rec_off[v]; q < h->rec_off[v + 1]; ++q) {
+                const uint64_t nA = h->vcf_off[q + 1] - h->vcf_off[q];
+                L->wide.push_back((uint32_t)L->desc.size());
+                L->wide.push_back(q);
+                max_bins = std::max(max_bins, A * (A + 1) / 2);
+                max_keys = std::max(max_keys, nA * (nA + 1) / 2);
+            }
+        }
+        L->desc.push_back(d);
+        blk += (R + per - 1) / per;
+    }
+    L->n_blocks = blk;
+    L->max_bins = (uint32_t)max_bins;
+    L->stride = (uint32_t)(max_bins + max_keys);
+    const uint64_t n_wide = L->wide.size() / 2;
+    L->n_slots = n_wide ? (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n_wide, 1024), std::max<uint64_t>(1, ((uint64_t)256 << 20) / ((uint64_t)L->stride * 16))) : 0;
+}
+
 // What a job keeps of ONE output family (the calls, the record calls, the record GLs; pg_shim_calls.cpp): a device buffer of its
 // own outside the arena — the output chain after chain, then (record GLs: the plans' offsets, then) the chain descriptors, the
 // wide kernel's list and its staging slots — and what a launch over it needs.  Made by the family's first forming (a job whose
@@ -141,6 +201,23 @@ struct CombineState {
         if (events) { hipEventDestroy(ev[0]); hipEventDestroy(ev[1]); events = false; }
         planned = false;
     }
+};
+
+// What a job keeps of the records of its combined groups (pg_shim_combine.cpp): ONE device buffer outside the
+// arena — one pg_call per record group after group, the GL values, the plans' GL offsets, the group descriptors, the wide
+// kernels' list, their staging slots (the two formations block, so they share them) and the word of the id check.  Made by the
+// first formation, made anew when `dirty`: a record plan, the combine plan or the index changed.
+struct CombinedRecordsState {
+    unsigned char* d = nullptr;
+    std::vector<uint64_t> rec_first, gl_first;   // [n_groups + 1] first record / first GL value of every group (a group without a plan has none)
+    std::vector<CRecDesc> desc;                  // host copy (groups with records)
+    size_t o_gl = 0, o_desc = 0, o_wide = 0, o_stage = 0, o_hit = 0;
+    uint32_t blocks = 0, wide = 0, max_bins = 0, stride = 0, slots = 0;
+    bool dirty = true;
+    // pg_job::combine_serial of the pg_job_combine whose bins the ids were checked beside / the records / the values were formed from (0: none)
+    uint64_t ids_serial = 0, calls_serial = 0, gl_serial = 0;
+    double calls_ms = 0.0, gl_ms = 0.0;
+    void release() { if (d) hipFree(d); d = nullptr; dirty = true; }
 };
 
 // The genotype-quality thresholds on `device` (pg_shim_calls.cpp: built once from log10l, uploaded once per device; the
@@ -304,6 +381,9 @@ struct pg_job {
     std::vector<RGlDesc> rgl_desc;
     // Path subsets combined on the device (pg_job_combine_plan / pg_job_combine / pg_job_combined_calls).
     pgj::CombineState combine;
+    uint64_t combine_serial = 0;              // counts the finished pg_job_combine calls
+    // ... and GT, GQ and GL per VCF record of the combined groups (pg_job_combined_record_calls / pg_job_combined_record_gl).
+    pgj::CombinedRecordsState crec;
 };
 
 namespace pgj __attribute__((visibility("hidden"))) {
@@ -314,6 +394,7 @@ inline void record_plans_changed(pg_job* job) {
     job->rgl.dirty = true;
     job->rplan_ids_ok = false;
     job->combine.layout_ok = false;   // (the members' layouts are compared again before the next combine)
+    job->crec.dirty = true;           // (the records of the combined groups: rebuilt, the ids checked again)
 }
 
 // Group B's copies of a pipelined first run (pg_job::late_threads) read the caller's arrays and feed the job's second stream:

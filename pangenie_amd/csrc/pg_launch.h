@@ -1,4 +1,4 @@
-// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp, pg_shim_run.cpp, pg_shim_calls.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip, pg_calls.hip, pg_combine.hip).
+// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp, pg_shim_run.cpp, pg_shim_calls.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip, pg_calls.hip, pg_combine.hip, pg_combine_records.hip).
 //
 // The ONE declaration of every host-callable launcher and of the two launch masks a job hands them.  Both sides include
 // it: a launcher whose parameter list changes on one side only no longer compiles (C linkage: the linker would not notice).
@@ -92,7 +92,32 @@ struct CombinePair {
     uint32_t ref, member, V, sumA;
 };
 
+// Records of combined groups (pg_combine_records.hip): one descriptor per group whose first chain's index
+// contig has a record plan with records, in group order.  Blocks [blk0, next blk0) of k_crcalls / k_crgl take
+// pgk_combined_records_block() RECORDS of the group each.  The layout (allele_off, allele_id, geno_off) is read from `chain`,
+// the group's first; `bins` = the group's combined bins, `calls` = one pg_call per record, `gl` = the group's pg_gl values,
+// record r's at gl_off[r] .. gl_off[r + 1].
+struct CRecDesc {
+    uint32_t blk0, R;
+    uint32_t chain, group;
+    const void* bins;
+    void* calls;
+    void* gl;
+    const uint64_t* gl_off;
+    RecPlanDev plan;
+};
+
 extern "C" {
+// pg_combine_records.hip: d_wide = uint2 {descriptor, record} of every record of a bubble with more than PG_AMAX alleles;
+// d_stage = n_slots staging slots of `stride` 16-byte values each (max_bins quotients, then the folded map), one per block
+void pgk_launch_crcalls(const DevContig* d_contigs, const CRecDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide, uint32_t n_wide,
+                        void* d_stage, uint32_t max_bins, uint32_t stride, uint32_t n_slots, const uint64_t* d_thr_m, const int32_t* d_thr_e, hipStream_t s);
+void pgk_launch_crgl(const DevContig* d_contigs, const CRecDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide, uint32_t n_wide,
+                     void* d_stage, uint32_t max_bins, uint32_t stride, uint32_t n_slots, hipStream_t s);
+// k_crplan_ids: *d_hit (8 bytes, all ones going in) = the lowest (group << 32 | variant) with an allele id outside the map of
+// one of the variant's records
+void pgk_launch_crplan_ids(const DevContig* d_contigs, const CRecDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, void* d_hit, hipStream_t s);
+uint32_t pgk_combined_records_block(void);
 // pg_calls.hip: the lists and staging slots of pgk_launch_rcalls, descriptors with the GL buffers
 void pgk_launch_rgl(const DevContig* d_contigs, const RGlDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide, uint32_t n_wide,
                     void* d_stage, uint32_t max_bins, uint32_t stride, uint32_t n_slots, hipStream_t s);

@@ -334,6 +334,7 @@ extern "C" void pg_job_destroy(pg_job* job) {
     job->rcalls.release();
     job->rgl.release();
     job->combine.release();
+    job->crec.release();
     job->rplans.clear();
     if (job->events) {
         for (auto& e : job->ev) hipEventDestroy(e);

@@ -375,6 +375,11 @@ namespace {
 
 static_assert(PG_CALL_EMPTY == PGX_CALL_EMPTY, "the flag of the public header is the kernels' flag");
 
+}  // namespace
+
+// (declared in pg_job.h: pg_shim_combine.cpp forms the records of combined groups under the same plans)
+namespace pgj {
+
 // The checks that need the plan alone (everything but the allele ids), and the host copy the job keeps.
 int check_record_plan(const pg_record_plan* p, uint32_t V, RecordPlanHost* h, char* err, size_t errlen) {
     if (!p) { set_err(err, errlen, "null record plan"); return PG_ERR_INVALID; }
@@ -455,53 +460,20 @@ bool record_plan_upload(const RecordPlanHost& h, unsigned char* d, RecPlanDev* d
     return dev->rec_var && dev->map_off && dev->vcf_off && dev->map && dev->vcf_index;
 }
 
-// The wave-per-record kernel stages a bubble's quotients and a record's folded map in device memory: one slot of `stride`
-// 16-byte values per block, at most 1024 blocks and 256 MB (a 256-allele bubble: 32 896 bins and as many keys, 1 MB a slot).
-struct RcallsLaunch {
-    std::vector<uint64_t> first;
-    std::vector<RCallsDesc> desc;
-    std::vector<uint32_t> wide;   // {descriptor, record} pairs
-    uint32_t n_blocks = 0, max_bins = 0, stride = 0, n_slots = 0;
-};
-// planOf(c): the plan of chain c's index contig or nullptr; aoff(c): the chain's allele_off
-template <class PlanOf, class AoffOf>
-void plan_rcalls(uint32_t n_chains, PlanOf planOf, AoffOf aoff, RcallsLaunch* L) {
-    const uint32_t per = pgk_calls_block();
-    L->first.assign((size_t)n_chains + 1, 0);
-    L->desc.clear();
-    L->wide.clear();
-    uint32_t blk = 0;
-    uint64_t max_bins = 0, max_keys = 0;
-    for (uint32_t c = 0; c < n_chains; ++c) {
-        const RecordPlanHost* h = planOf(c);
-        const uint32_t R = h ? h->R : 0;
-        L->first[c + 1] = L->first[c] + R;
-        if (R == 0) continue;
-        RCallsDesc d;
-        memset(&d, 0, sizeof(d));
-        d.blk0 = blk; d.R = R; d.chain = c;
-        d.plan = h->dev;
-        const uint32_t* off = aoff(c);
-        for (uint32_t v = 0; v < h->V; ++v) {
-            const uint64_t A = off[v + 1] - off[v];
-            if (A <= PG_AMAX) continue;
-            for (uint32_t q = h->rec_off[v]; q < h->rec_off[v + 1]; ++q) {
-                const uint64_t nA = h->vcf_off[q + 1] - h->vcf_off[q];
-                L->wide.push_back((uint32_t)L->desc.size());
-                L->wide.push_back(q);
-                max_bins = std::max(max_bins, A * (A + 1) / 2);
-                max_keys = std::max(max_keys, nA * (nA + 1) / 2);
-            }
-        }
-        L->desc.push_back(d);
-        blk += (R + per - 1) / per;
+// record r owns nd (nd + 1) / 2 values, nd its defined alleles
+std::vector<uint64_t> record_gl_offsets(const RecordPlanHost& h) {
+    std::vector<uint64_t> off((size_t)h.R + 1, 0);
+    for (uint32_t q = 0; q < h.R; ++q) {
+        uint64_t nd = 0;
+        for (uint32_t i = h.vcf_off[q]; i < h.vcf_off[q + 1]; ++i) nd += h.vcf_index[i] != 0xFFFFu;
+        off[q + 1] = off[q] + nd * (nd + 1) / 2;
     }
-    L->n_blocks = blk;
-    L->max_bins = (uint32_t)max_bins;
-    L->stride = (uint32_t)(max_bins + max_keys);
-    const uint64_t n_wide = L->wide.size() / 2;
-    L->n_slots = n_wide ? (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n_wide, 1024), std::max<uint64_t>(1, ((uint64_t)256 << 20) / ((uint64_t)L->stride * 16))) : 0;
+    return off;
 }
+
+}  // namespace pgj
+
+namespace {
 
 // the plan of chain c's index contig, or nullptr
 const RecordPlanHost* plan_of_chain(const pg_job* job, uint32_t c) {
@@ -608,7 +580,7 @@ extern "C" int pg_job_record_calls(pg_job* job, char* err, size_t errlen) {
     const uint32_t n = (uint32_t)job->chains.size();
     if (f.dirty) {   // a plan or the index has changed: the descriptors and lists are made anew, the ids checked on the device
         RcallsLaunch L;
-        plan_rcalls(n, [&](uint32_t c) { return plan_of_chain(job, c); }, [&](uint32_t c) { return job->index[job->chains[c].index].aoff.data(); }, &L);
+        plan_rcalls(n, [&](uint32_t c) { return plan_of_chain(job, c); }, [&](uint32_t c) { return job->index[job->chains[c].index].aoff.data(); }, pgk_calls_block(), &L);
         const size_t o_desc = align_up((size_t)L.first[n] * sizeof(pg_call) + 8);
         const size_t o_wide = o_desc + align_up(L.desc.size() * sizeof(RCallsDesc) + 8);
         const size_t o_stage = o_wide + align_up(L.wide.size() * sizeof(uint32_t) + 8);
@@ -667,7 +639,7 @@ extern "C" int pg_record_calls_from_bins(int device, uint32_t n_variants, const 
     rc = gq_table_on(device, &d_tm, &d_te, nullptr, 0);
     if (rc != PG_OK) return rc;
     RcallsLaunch L;
-    plan_rcalls(1, [&](uint32_t) -> const RecordPlanHost* { return &h; }, [&](uint32_t) { return allele_off; }, &L);
+    plan_rcalls(1, [&](uint32_t) -> const RecordPlanHost* { return &h; }, [&](uint32_t) { return allele_off; }, pgk_calls_block(), &L);
     Region r_desc(sizeof(RCallsDesc), L.desc.data()), r_wide(L.wide.size() * 4, L.wide.data()), r_plan(record_plan_device_bytes(h)),
         r_stage((size_t)L.n_slots * L.stride * 16), r_out((size_t)h.R * sizeof(pg_call));
     rc = bins.upload({&r_desc, &r_wide}, {&r_plan, &r_stage, &r_out}, [&](unsigned char* d) {
@@ -684,17 +656,6 @@ extern "C" int pg_record_calls_from_bins(int device, uint32_t n_variants, const 
 //  The GL column per VCF record (pg_calls.hip: k_rgl / k_rgl_wide / k_gl_values).
 // ---------------------------------------------------------------------------------------
 namespace {
-
-// record r owns nd (nd + 1) / 2 values, nd its defined alleles
-std::vector<uint64_t> record_gl_offsets(const RecordPlanHost& h) {
-    std::vector<uint64_t> off((size_t)h.R + 1, 0);
-    for (uint32_t q = 0; q < h.R; ++q) {
-        uint64_t nd = 0;
-        for (uint32_t i = h.vcf_off[q]; i < h.vcf_off[q + 1]; ++i) nd += h.vcf_index[i] != 0xFFFFu;
-        off[q + 1] = off[q] + nd * (nd + 1) / 2;
-    }
-    return off;
-}
 
 RGlDesc rgl_desc_of(const RCallsDesc& c) {
     RGlDesc d;
@@ -730,7 +691,7 @@ extern "C" int pg_job_record_gl(pg_job* job, char* err, size_t errlen) {
         for (const RecordPlanRef& p : job->rplans)
             if (p && p->R && !offs.count(p.get())) offs[p.get()].gl_off = record_gl_offsets(*p);
         RcallsLaunch L;
-        plan_rcalls(n, [&](uint32_t c) { return plan_of_chain(job, c); }, [&](uint32_t c) { return job->index[job->chains[c].index].aoff.data(); }, &L);
+        plan_rcalls(n, [&](uint32_t c) { return plan_of_chain(job, c); }, [&](uint32_t c) { return job->index[job->chains[c].index].aoff.data(); }, pgk_calls_block(), &L);
         std::vector<uint64_t> first((size_t)n + 1, 0);
         for (uint32_t c = 0; c < n; ++c) {
             const auto o = offs.find(plan_of_chain(job, c));
@@ -804,7 +765,7 @@ extern "C" int pg_record_gl_from_bins(int device, uint32_t n_variants, const uin
     if (rc != PG_OK || n_variants == 0) return rc;
     const std::vector<uint64_t> gl_off = record_gl_offsets(h);
     RcallsLaunch L;
-    plan_rcalls(1, [&](uint32_t) -> const RecordPlanHost* { return &h; }, [&](uint32_t) { return allele_off; }, &L);
+    plan_rcalls(1, [&](uint32_t) -> const RecordPlanHost* { return &h; }, [&](uint32_t) { return allele_off; }, pgk_calls_block(), &L);
     RGlDesc gd;
     Region r_desc(sizeof(RGlDesc), &gd), r_wide(L.wide.size() * 4, L.wide.data()), r_plan(record_plan_device_bytes(h)),
         r_stage((size_t)L.n_slots * L.stride * 16), r_gloff(gl_off.size() * 8, gl_off.data()), r_out((size_t)gl_off.back() * sizeof(pg_gl));

@@ -4,11 +4,16 @@
 // A plan (pg_job_combine_plan) is the groups, the descriptors of the launches and ONE device buffer outside the arena for what
 // they write; pg_job_combine and pg_job_combined_calls are a launch each over it and remember the run whose bins they read.
 // The two unit entry points stage host arrays as DevContigs of their own and go through the same launchers.
+//
+// The records of the groups (pg_combine_records.hip) come last in this file: GT, GQ and the GL column per VCF
+// record from the combined bins, under the record plans of pg_shim_calls.cpp — the plan of a group is that of its first
+// chain's index contig.  Their state is pg_job::crec; their unit entry points stage one contig's combined bins and a plan.
 #include <hip/hip_runtime_api.h>
 
 #include <string.h>
 
 #include <algorithm>
+#include <map>
 #include <vector>
 
 #include "../../include/pangenie_hmm.h"
@@ -250,6 +255,7 @@ extern "C" int pg_job_combine_plan(pg_job* job, uint32_t n_groups, const uint32_
     c.d = d;
     c.planned = true;
     mine = std::move(c);
+    job->crec.dirty = true;   // (the records of the groups: new groups, new bins)
     return PG_OK;
 }
 
@@ -265,7 +271,10 @@ extern "C" int pg_job_combine(pg_job* job, char* err, size_t errlen) {
         pgk_launch_combine(job->d_contigs, (const CombineDesc*)(c.d + c.o_desc), (uint32_t)c.desc.size(), c.blocks, (const uint32_t*)(c.d + c.o_members),
                            c.d + c.o_wide, c.wide, s);
     }, &c.ms, err, errlen);
-    if (rc == PG_OK) c.combined_run = job->run_serial;
+    if (rc == PG_OK) {
+        c.combined_run = job->run_serial;
+        ++job->combine_serial;   // (what was formed from the bins before is no longer this combine's)
+    }
     return rc;
 }
 
@@ -342,6 +351,18 @@ int layout_check(uint32_t V, const uint32_t* allele_off, std::vector<uint64_t>* 
     return PG_OK;
 }
 
+// a bin is a pg_combined_bin: zero, or normalised; deferred and absent bins carry no value
+bool combined_bins_ok(const pg_combined_bin* bins, size_t n) {
+    for (size_t i = 0; i < n; ++i) {
+        const pg_combined_bin& b = bins[i];
+        const bool value_ok = b.m == 0 ? b.e == 0 : ((b.m >> 63) != 0 && b.e > -40000 && b.e < 40000);
+        if (!value_ok || (b.flags & ~(PG_COMBINED_PRESENT | PG_COMBINED_DEFERRED)) || (b.flags != PG_COMBINED_PRESENT && b.m != 0) ||
+            b.flags == PG_COMBINED_DEFERRED)
+            return false;
+    }
+    return true;
+}
+
 int select_device(int device) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); return PG_ERR_DEVICE; }
@@ -411,13 +432,7 @@ extern "C" int pg_calls_from_combined(int device, uint32_t n_variants, const uin
     int rc = layout_check(n_variants, allele_off, &goff);
     if (rc != PG_OK) return rc;
     const size_t V1 = (size_t)n_variants + 1, sumA = allele_off[n_variants], n_lik = goff[n_variants];
-    for (size_t i = 0; i < n_lik; ++i) {   // a bin is a pg_combined_bin: zero, or normalised; deferred and absent bins carry no value
-        const pg_combined_bin& b = bins[i];
-        const bool value_ok = b.m == 0 ? b.e == 0 : ((b.m >> 63) != 0 && b.e > -40000 && b.e < 40000);
-        if (!value_ok || (b.flags & ~(PG_COMBINED_PRESENT | PG_COMBINED_DEFERRED)) || (b.flags != PG_COMBINED_PRESENT && b.m != 0) ||
-            b.flags == PG_COMBINED_DEFERRED)
-            return PG_ERR_INVALID;
-    }
+    if (!combined_bins_ok(bins, n_lik)) return PG_ERR_INVALID;
     rc = select_device(device);
     if (rc != PG_OK) return rc;
     const uint64_t* d_tm = nullptr;
@@ -448,4 +463,295 @@ extern "C" int pg_calls_from_combined(int device, uint32_t n_variants, const uin
     pgk_launch_ccalls((const DevContig*)st.at(p_dc), (const CombineDesc*)st.at(p_desc), 1, n_blocks, (const uint32_t*)st.at(p_mem), st.at(p_wide),
                       (uint32_t)(wide.size() / 2), d_tm, d_te, nullptr);
     return st.read_back(out, p_out);
+}
+
+// ---------------------------------------------------------------------------------------
+//  GT, GQ and GL per VCF record of the combined groups (pg_combine_records.hip).
+// ---------------------------------------------------------------------------------------
+namespace {
+
+static_assert(sizeof(pg_gl) == 4, "a GL value is 4 bytes");
+
+// the plan of group g: that of its first chain's index contig, or nullptr
+const RecordPlanHost* plan_of_group(const pg_job* job, uint32_t g) {
+    const CombineState& c = job->combine;
+    const uint32_t ix = job->chains[c.members[c.group_off[g]]].index;
+    return ix < job->rplans.size() ? job->rplans[ix].get() : nullptr;
+}
+
+// one array of GL offsets per PLAN, whatever the number of groups under it
+struct PlanOffsets { std::vector<uint64_t> gl_off; size_t at = 0; };
+
+// the buffer of pg_job::crec for the plans, the groups and the combined bins as they are
+int crec_rebuild(pg_job* job, char* err, size_t errlen) {
+    const CombineState& c = job->combine;
+    CombinedRecordsState& k = job->crec;
+    const uint32_t n = (uint32_t)(c.group_off.size() - 1);
+    RcallsLaunch L;
+    plan_rcalls(n, [&](uint32_t g) { return plan_of_group(job, g); },
+                [&](uint32_t g) { return job->index[job->chains[c.members[c.group_off[g]]].index].aoff.data(); }, pgk_combined_records_block(), &L);
+    std::map<const RecordPlanHost*, PlanOffsets> offs;
+    std::vector<uint64_t> gl_first((size_t)n + 1, 0);
+    for (uint32_t g = 0; g < n; ++g) {
+        const RecordPlanHost* h = plan_of_group(job, g);
+        if (h && h->R && !offs.count(h)) offs[h].gl_off = record_gl_offsets(*h);
+        gl_first[g + 1] = gl_first[g] + (h && h->R ? offs[h].gl_off.back() : 0);
+    }
+    const size_t o_gl = align_up((size_t)L.first[n] * sizeof(pg_call) + 8);
+    size_t total = o_gl + align_up((size_t)gl_first[n] * sizeof(pg_gl) + 8);
+    for (auto& kv : offs) {
+        kv.second.at = total;
+        total += align_up(kv.second.gl_off.size() * sizeof(uint64_t) + 8);
+    }
+    const size_t o_desc = total;
+    const size_t o_wide = o_desc + align_up(L.desc.size() * sizeof(CRecDesc) + 8);
+    const size_t o_stage = o_wide + align_up(L.wide.size() * sizeof(uint32_t) + 8);
+    const size_t o_hit = o_stage + align_up((size_t)L.n_slots * L.stride * 16 + 8);
+    total = o_hit + align_up(8);
+    unsigned char* d = nullptr;
+    if (hipMalloc((void**)&d, total) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the records of the combined groups failed", total); return PG_ERR_NOMEM; }
+    std::vector<CRecDesc> desc;
+    for (const RCallsDesc& rc : L.desc) {   // (plan_rcalls' "chain" is the group)
+        const uint32_t g = rc.chain;
+        CRecDesc cd;
+        memset(&cd, 0, sizeof(cd));
+        cd.blk0 = rc.blk0; cd.R = rc.R;
+        cd.chain = c.members[c.group_off[g]]; cd.group = g;
+        cd.bins = c.d + c.bin_first[g] * sizeof(pg_combined_bin);
+        cd.calls = d + L.first[g] * sizeof(pg_call);
+        cd.gl = d + o_gl + gl_first[g] * sizeof(pg_gl);
+        cd.gl_off = (const uint64_t*)(d + offs[plan_of_group(job, g)].at);
+        cd.plan = rc.plan;
+        desc.push_back(cd);
+    }
+    hipError_t he = hipSuccess;
+    for (auto& kv : offs)
+        if (he == hipSuccess) he = hipMemcpy(d + kv.second.at, kv.second.gl_off.data(), kv.second.gl_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (he == hipSuccess && !desc.empty()) he = hipMemcpy(d + o_desc, desc.data(), desc.size() * sizeof(CRecDesc), hipMemcpyHostToDevice);
+    if (he == hipSuccess && !L.wide.empty()) he = hipMemcpy(d + o_wide, L.wide.data(), L.wide.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (he != hipSuccess) { hipFree(d); set_err(err, errlen, "upload of the combined groups' record lists failed: %s", hipGetErrorString(he)); return PG_ERR_DEVICE; }
+    if (job->stream) HIP_TRY(hipStreamSynchronize(job->stream));   // (nothing reads the buffer this one replaces any more)
+    k.release();
+    k.d = d;
+    k.rec_first = std::move(L.first);
+    k.gl_first = std::move(gl_first);
+    k.desc = std::move(desc);
+    k.o_gl = o_gl; k.o_desc = o_desc; k.o_wide = o_wide; k.o_stage = o_stage; k.o_hit = o_hit;
+    k.blocks = L.n_blocks; k.wide = (uint32_t)(L.wide.size() / 2);
+    k.max_bins = L.max_bins; k.stride = L.stride; k.slots = L.n_slots;
+    k.dirty = false;
+    k.ids_serial = k.calls_serial = k.gl_serial = 0;
+    return PG_OK;
+}
+
+// k_crplan_ids over the groups' descriptors, on the job's stream; waits for the answer
+int crec_check_ids(pg_job* job, char* err, size_t errlen) {
+    CombinedRecordsState& k = job->crec;
+    if (!k.desc.empty() && k.blocks) {
+        hipStream_t s = job->stream;
+        uint64_t hit = ~(uint64_t)0;
+        HIP_TRY(hipMemcpyAsync(k.d + k.o_hit, &hit, sizeof(hit), hipMemcpyHostToDevice, s));
+        pgk_launch_crplan_ids(job->d_contigs, (const CRecDesc*)(k.d + k.o_desc), (uint32_t)k.desc.size(), k.blocks, k.d + k.o_hit, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&hit, k.d + k.o_hit, sizeof(hit), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (hit != ~(uint64_t)0) {
+            set_err(err, errlen, "group %u, variant %u: an allele id lies outside the map of one of the variant's records (the plan of the group's first chain)",
+                    (uint32_t)(hit >> 32), (uint32_t)hit);
+            return PG_ERR_INVALID;
+        }
+    }
+    k.ids_serial = job->combine_serial;
+    return PG_OK;
+}
+
+// what the two formations open with: the combined bins of this run are there, a group has a plan, the buffer is the plans'
+// and the groups' as they are, and the ids have been checked beside this combine
+int crec_begin(pg_job* job, char* err, size_t errlen) {
+    int rc = combine_begin(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    const CombineState& c = job->combine;
+    if (c.combined_run != job->run_serial) { set_err(err, errlen, "pg_job_combine has not been called for this run"); return PG_ERR_INVALID; }
+    bool any = false;
+    for (uint32_t g = 0; g + 1 < c.group_off.size(); ++g) any = any || plan_of_group(job, g) != nullptr;
+    if (!any) { set_err(err, errlen, "no group's first chain has a record plan on its index contig (pg_job_record_plan)"); return PG_ERR_INVALID; }
+    CombinedRecordsState& k = job->crec;
+    if (k.dirty) {
+        rc = crec_rebuild(job, err, errlen);
+        if (rc != PG_OK) return rc;
+    }
+    if (k.ids_serial != job->combine_serial) rc = crec_check_ids(job, err, errlen);
+    return rc;
+}
+
+// the records (gl == false) or the GL values of this run's combine are there to be fetched
+int crec_ready(pg_job* job, bool gl, char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
+    const CombineState& c = job->combine;
+    const CombinedRecordsState& k = job->crec;
+    if (!c.planned || c.combined_run != job->run_serial || !k.d || k.dirty || (gl ? k.gl_serial : k.calls_serial) != job->combine_serial) {
+        set_err(err, errlen, "%s has not been called for this run's pg_job_combine", gl ? "pg_job_combined_record_gl" : "pg_job_combined_record_calls");
+        return PG_ERR_INVALID;
+    }
+    return PG_OK;
+}
+
+// where group g's elements lie, and how many
+const unsigned char* crec_slice(const CombinedRecordsState& k, bool gl, uint32_t g, uint64_t* n) {
+    const std::vector<uint64_t>& first = gl ? k.gl_first : k.rec_first;
+    *n = first[g + 1] - first[g];
+    return k.d + (gl ? k.o_gl : 0) + first[g] * (gl ? sizeof(pg_gl) : sizeof(pg_call));
+}
+
+int crec_fetch_group(pg_job* job, bool gl, uint32_t g, void* out, char* err, size_t errlen) {
+    int rc = crec_ready(job, gl, err, errlen);
+    if (rc != PG_OK) return rc;
+    const CombinedRecordsState& k = job->crec;
+    if (g + 1 >= k.rec_first.size()) { set_err(err, errlen, "group %u of %zu", g, k.rec_first.size() - 1); return PG_ERR_INVALID; }
+    uint64_t n = 0;
+    const unsigned char* src = crec_slice(k, gl, g, &n);
+    if (n == 0) return PG_OK;
+    if (!out) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(job->device));
+    HIP_TRY(hipMemcpy(out, src, n * (gl ? sizeof(pg_gl) : sizeof(pg_call)), hipMemcpyDeviceToHost));
+    return PG_OK;
+}
+
+int crec_fetch_groups(pg_job* job, bool gl, void* const* outs, char* err, size_t errlen) {
+    int rc = crec_ready(job, gl, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (!outs) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    const CombinedRecordsState& k = job->crec;
+    HIP_TRY(hipSetDevice(job->device));
+    for (uint32_t g = 0; g + 1 < k.rec_first.size(); ++g) {
+        uint64_t n = 0;
+        const unsigned char* src = crec_slice(k, gl, g, &n);
+        if (n == 0) continue;
+        if (!outs[g]) { set_err(err, errlen, "no buffer for group %u", g); return PG_ERR_INVALID; }
+        HIP_TRY(hipMemcpyAsync(outs[g], src, n * (gl ? sizeof(pg_gl) : sizeof(pg_call)), hipMemcpyDeviceToHost, job->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(job->stream));
+    return PG_OK;
+}
+
+int crec_device_group(pg_job* job, bool gl, uint32_t g, void** d_out, uint64_t* n) {
+    if (crec_ready(job, gl, nullptr, 0) != PG_OK || g + 1 >= job->crec.rec_first.size()) return PG_ERR_INVALID;
+    uint64_t count = 0;
+    const unsigned char* src = crec_slice(job->crec, gl, g, &count);
+    if (d_out) *d_out = (void*)src;
+    if (n) *n = count;
+    return PG_OK;
+}
+
+}  // namespace
+
+extern "C" int pg_job_combined_record_calls(pg_job* job, char* err, size_t errlen) {
+    int rc = crec_begin(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    const uint64_t* d_tm = nullptr;
+    const int32_t* d_te = nullptr;
+    rc = gq_table_on(job->device, &d_tm, &d_te, err, errlen);
+    if (rc != PG_OK) return rc;
+    CombinedRecordsState& k = job->crec;
+    rc = timed(job, [&](hipStream_t s) {
+        pgk_launch_crcalls(job->d_contigs, (const CRecDesc*)(k.d + k.o_desc), (uint32_t)k.desc.size(), k.blocks, k.d + k.o_wide, k.wide, k.d + k.o_stage,
+                           k.max_bins, k.stride, k.slots, d_tm, d_te, s);
+    }, &k.calls_ms, err, errlen);
+    if (rc == PG_OK) k.calls_serial = job->combine_serial;
+    return rc;
+}
+
+extern "C" int pg_job_combined_record_gl(pg_job* job, char* err, size_t errlen) {
+    int rc = crec_begin(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    CombinedRecordsState& k = job->crec;
+    rc = timed(job, [&](hipStream_t s) {
+        pgk_launch_crgl(job->d_contigs, (const CRecDesc*)(k.d + k.o_desc), (uint32_t)k.desc.size(), k.blocks, k.d + k.o_wide, k.wide, k.d + k.o_stage,
+                        k.max_bins, k.stride, k.slots, s);
+    }, &k.gl_ms, err, errlen);
+    if (rc == PG_OK) k.gl_serial = job->combine_serial;
+    return rc;
+}
+
+extern "C" int pg_job_fetch_combined_record_calls(pg_job* job, uint32_t group, pg_call* out, char* err, size_t errlen) { return crec_fetch_group(job, false, group, out, err, errlen); }
+extern "C" int pg_job_fetch_combined_record_calls_all(pg_job* job, pg_call* const* outs, char* err, size_t errlen) { return crec_fetch_groups(job, false, (void* const*)outs, err, errlen); }
+extern "C" int pg_job_device_combined_record_calls(pg_job* job, uint32_t group, void** d_calls, uint64_t* n) { return crec_device_group(job, false, group, d_calls, n); }
+extern "C" int pg_job_fetch_combined_record_gl(pg_job* job, uint32_t group, pg_gl* out, char* err, size_t errlen) { return crec_fetch_group(job, true, group, out, err, errlen); }
+extern "C" int pg_job_fetch_combined_record_gl_all(pg_job* job, pg_gl* const* outs, char* err, size_t errlen) { return crec_fetch_groups(job, true, (void* const*)outs, err, errlen); }
+extern "C" int pg_job_device_combined_record_gl(pg_job* job, uint32_t group, void** d_gl, uint64_t* n) { return crec_device_group(job, true, group, d_gl, n); }
+extern "C" double pg_job_combined_record_calls_ms(const pg_job* job) { return job ? job->crec.calls_ms : 0.0; }
+extern "C" double pg_job_combined_record_gl_ms(const pg_job* job) { return job ? job->crec.gl_ms : 0.0; }
+
+// The unit entry points: one contig's combined bins and a plan in, through the same kernels.
+namespace {
+
+int records_from_combined(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id, const pg_combined_bin* bins,
+                          const pg_record_plan* plan, void* out, bool gl) {
+    std::vector<uint64_t> goff(1, 0);
+    if (n_variants) {
+        if (!allele_id || !bins) return PG_ERR_INVALID;
+        const int rc = layout_check(n_variants, allele_off, &goff);
+        if (rc != PG_OK) return rc;
+    }
+    RecordPlanHost h;
+    int rc = check_record_plan(plan, n_variants, &h, nullptr, 0);
+    if (rc == PG_OK && n_variants) rc = check_record_plan_ids(h, allele_off, allele_id, nullptr, 0);
+    if (rc != PG_OK || n_variants == 0) return rc;
+    const size_t V1 = (size_t)n_variants + 1, sumA = allele_off[n_variants], n_lik = goff[n_variants];
+    if (!combined_bins_ok(bins, n_lik) || !out) return PG_ERR_INVALID;
+    rc = select_device(device);
+    if (rc != PG_OK) return rc;
+    const uint64_t* d_tm = nullptr;
+    const int32_t* d_te = nullptr;
+    if (!gl) {
+        rc = gq_table_on(device, &d_tm, &d_te, nullptr, 0);
+        if (rc != PG_OK) return rc;
+    }
+    RcallsLaunch L;
+    plan_rcalls(1, [&](uint32_t) -> const RecordPlanHost* { return &h; }, [&](uint32_t) { return allele_off; }, pgk_combined_records_block(), &L);
+    const std::vector<uint64_t> gl_off = record_gl_offsets(h);
+    DevContig dc;
+    memset(&dc, 0, sizeof(dc));
+    CRecDesc cd;
+    memset(&cd, 0, sizeof(cd));
+    Staged st;
+    const size_t p_dc = st.add(sizeof(dc), &dc), p_desc = st.add(sizeof(cd), &cd), p_wide = st.add(L.wide.size() * 4, L.wide.data()),
+                 p_aoff = st.add(V1 * 4, allele_off), p_aid = st.add(sumA * 2, allele_id), p_goff = st.add(V1 * 8, goff.data()),
+                 p_bins = st.add(n_lik * sizeof(pg_combined_bin), bins), p_plan = st.add(record_plan_device_bytes(h)),
+                 p_stage = st.add((size_t)L.n_slots * L.stride * 16), p_gloff = st.add(gl_off.size() * 8, gl_off.data()),
+                 p_out = st.add(gl ? (size_t)gl_off.back() * sizeof(pg_gl) : (size_t)h.R * sizeof(pg_call));
+    rc = st.alloc();
+    if (rc != PG_OK) return rc;
+    dc.V = n_variants;
+    dc.allele_off = (const uint32_t*)st.at(p_aoff);
+    dc.allele_id = (const uint16_t*)st.at(p_aid);
+    dc.geno_off = (const uint64_t*)st.at(p_goff);
+    cd.blk0 = 0; cd.R = h.R;
+    cd.bins = st.at(p_bins);
+    cd.calls = st.at(p_out);
+    cd.gl = st.at(p_out);
+    cd.gl_off = (const uint64_t*)st.at(p_gloff);
+    if (!record_plan_upload(h, st.at(p_plan), &cd.plan)) return PG_ERR_DEVICE;
+    rc = st.copy_in();
+    if (rc != PG_OK) return rc;
+    if (gl)
+        pgk_launch_crgl((const DevContig*)st.at(p_dc), (const CRecDesc*)st.at(p_desc), 1, L.n_blocks, st.at(p_wide), (uint32_t)(L.wide.size() / 2), st.at(p_stage),
+                        L.max_bins, L.stride, L.n_slots, nullptr);
+    else
+        pgk_launch_crcalls((const DevContig*)st.at(p_dc), (const CRecDesc*)st.at(p_desc), 1, L.n_blocks, st.at(p_wide), (uint32_t)(L.wide.size() / 2), st.at(p_stage),
+                           L.max_bins, L.stride, L.n_slots, d_tm, d_te, nullptr);
+    return st.read_back(out, p_out);
+}
+
+}  // namespace
+
+extern "C" int pg_record_calls_from_combined(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id, const pg_combined_bin* bins,
+                                             const pg_record_plan* plan, pg_call* out) {
+    return records_from_combined(device, n_variants, allele_off, allele_id, bins, plan, out, false);
+}
+
+extern "C" int pg_record_gl_from_combined(int device, uint32_t n_variants, const uint32_t* allele_off, const uint16_t* allele_id, const pg_combined_bin* bins,
+                                          const pg_record_plan* plan, pg_gl* out) {
+    return records_from_combined(device, n_variants, allele_off, allele_id, bins, plan, out, true);
 }

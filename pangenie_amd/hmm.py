@@ -473,6 +473,27 @@ class Job:
         """elapsed ms of the kernels of the last combined_calls()"""
         return float(self._lib.pg_job_combined_calls_ms(self.h))
 
+    def combined_record_calls(self, group: Optional[int] = None):
+        """pg_job_combined_record_calls + pg_job_fetch_combined_record_calls[_all]: GT and GQ per VCF RECORD of every group from
+        its combined bins, under the record plan of the group's first chain's index contig.  One record array
+        (calls.CALL_DTYPE) per group — empty for a group without a plan — or `group`'s alone; after combine()."""
+        from . import calls as _calls
+        return _calls.job_combined_record_calls(self, group)
+
+    def combined_record_gl(self, group: Optional[int] = None):
+        """pg_job_combined_record_gl + pg_job_fetch_combined_record_gl[_all]: the GL column per VCF RECORD of every group from its
+        combined bins (calls.GL_DTYPE per group, laid out by calls.record_gl_offsets(plan), or `group`'s alone); after combine()."""
+        from . import calls as _calls
+        return _calls.job_combined_record_gl(self, group)
+
+    def combined_record_calls_ms(self) -> float:
+        """elapsed ms of the kernels of the last combined_record_calls()"""
+        return float(self._lib.pg_job_combined_record_calls_ms(self.h))
+
+    def combined_record_gl_ms(self) -> float:
+        """elapsed ms of the kernels of the last combined_record_gl()"""
+        return float(self._lib.pg_job_combined_record_gl_ms(self.h))
+
     def viterbi_ms(self) -> float:
         """elapsed ms of the Viterbi kernels (run_phasing) of the last run"""
         return float(self._lib.pg_job_viterbi_ms(self.h))

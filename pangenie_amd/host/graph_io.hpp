@@ -254,4 +254,17 @@ std::vector<std::map<std::string, SampledRecordFields>> genotype_cohort_sampled_
     ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
     bool ignore_imputed = false, std::vector<std::map<std::string, SampledPaths>>* sampled = nullptr);
 
+/** The `-a` flow to VCF lines: genotype_subsets for a caller who wants the sample column.  One job over every
+ *  chromosome and subset, the subsets combined on the device (pg_job_combine), the plan of Graph::record_plan() on the index
+ *  contig of each group's first chain, pg_job_combined_record_calls, pg_job_combined_record_gl and the two _all fetches: no
+ *  genotype bin comes back, except for a chromosome with an entry the device deferred, which is finished from the chains' own
+ *  bins added up on the host, as genotype_cohort_record_fields finishes its entries.  Per chromosome the record fields and the
+ *  first chain's coverage and unique k-mer counts: Graph::genotypes_records(fields, coverage, unique_kmers, ignore_imputed)
+ *  prints the lines of Graph::genotypes_records(genotype_subsets(..., normalize = true), ignore_imputed).  Throws
+ *  std::runtime_error on no subsets, a missing graph, a graph whose bubble count is not the index's, and on the C ABI's errors. */
+std::map<std::string, SampledRecordFields> genotype_subsets_record_fields(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<std::vector<unsigned short>>& subsets, ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false,
+    long double effective_N = 25000.0L, int device = 0, bool ignore_imputed = false);
+
 }  // namespace pangenie

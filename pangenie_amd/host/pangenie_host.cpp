@@ -1225,6 +1225,76 @@ std::vector<std::map<std::string, RecordFields>> genotype_cohort_record_fields(
     return cohort_record_fields(chromosomes, graphs, samples, probabilities, recombrate, uniform, effective_N, device, ignore_imputed, true);
 }
 
+// ------------------------------------------------------------------ path subsets, the sample column per VCF record
+std::map<std::string, SampledRecordFields> genotype_subsets_record_fields(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<std::vector<unsigned short>>& subsets, ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N,
+    int device, bool ignore_imputed) {
+    std::map<std::string, SampledRecordFields> out;
+    if (subsets.empty()) fail("genotype_subsets_record_fields: no subsets of paths");
+    if (chromosomes.empty()) return out;
+    // the graphs first: nothing runs for a chromosome without one
+    std::vector<const Graph*> graph_of;
+    std::vector<RecordPlan> plans;
+    for (auto& kv : chromosomes) {
+        const auto g = graphs.find(kv.first);
+        if (g == graphs.end() || g->second.size() != kv.second.size()) fail("genotype_subsets_record_fields: no graph of " + kv.first + " with the index's bubbles");
+        graph_of.push_back(&g->second);
+        plans.push_back(g->second.record_plan());
+    }
+    SubsetsRun R;
+    R.run(chromosomes, subsets, probabilities, recombrate, uniform, effective_N, device);
+    const size_t C = R.C, S = R.S;
+    int rc = PG_OK;
+    for (size_t c = 0; c < C && rc == PG_OK; ++c) {   // the plan of a group is that of its first chain's index contig
+        const pg_record_plan view = plans[c].view();
+        rc = pg_job_record_plan(R.job, (uint32_t)(c * S), &view, R.err, sizeof(R.err));
+    }
+    if (rc == PG_OK) rc = pg_job_combined_record_calls(R.job, R.err, sizeof(R.err));
+    if (rc == PG_OK) rc = pg_job_combined_record_gl(R.job, R.err, sizeof(R.err));
+    check_rc(rc, R.err);
+    // all records with one synchronisation, all GL values with another
+    std::vector<std::vector<pg_call>> recs(C);
+    std::vector<pg_call*> ptrs(C, nullptr);
+    std::vector<pg_gl*> gl_ptrs(C, nullptr);
+    for (size_t c = 0; c < C; ++c) {
+        RecordFields& fields = out[R.names[c]].fields;
+        recs[c].resize(plans[c].nr_of_records());
+        ptrs[c] = recs[c].empty() ? nullptr : recs[c].data();
+        fields.gl_off.assign(plans[c].nr_of_records() + 1, 0);
+        const pg_record_plan view = plans[c].view();
+        check_rc(pg_record_gl_offsets(&view, fields.gl_off.data()), "pg_record_gl_offsets refused the record plan");
+        fields.gl.resize(fields.gl_off.back());
+        gl_ptrs[c] = fields.gl.empty() ? nullptr : fields.gl.data();
+    }
+    check_rc(pg_job_fetch_combined_record_calls_all(R.job, ptrs.data(), R.err, sizeof(R.err)), R.err);
+    check_rc(pg_job_fetch_combined_record_gl_all(R.job, gl_ptrs.data(), R.err, sizeof(R.err)), R.err);
+    for (size_t c = 0; c < C; ++c) {
+        SampledRecordFields& f = out[R.names[c]];
+        const size_t V = R.flat[c * S].variant_pos.size();
+        // unique_kmers and coverage are those of the first chain (GenotypingResult::combine leaves them alone)
+        std::vector<uint16_t> n_kmers(V ? V : 1), cov(V ? V : 1);
+        pg_contig_result first{};
+        first.n_kmers = n_kmers.data(); first.coverage = cov.data();
+        check_rc(pg_job_fetch(R.job, (uint32_t)(c * S), &first, R.err, sizeof(R.err)), R.err);
+        f.unique_kmers.assign(n_kmers.begin(), n_kmers.begin() + V);
+        f.coverage.assign(cov.begin(), cov.begin() + V);
+        rc = chain_record_fields(
+            *graph_of[c], plans[c], recs[c].data(), ignore_imputed, true, [&](size_t v) { return n_kmers[v] == 0; },
+            [&](std::vector<GenotypingResult>* full) {   // what the device deferred: from the chains' own bins, added up on the host
+                *full = R.combined_on_host(c);
+                for (size_t v = 0; v < full->size(); ++v) {
+                    (*full)[v].set_unique_kmers(n_kmers[v]);
+                    (*full)[v].set_coverage(cov[v]);
+                }
+                return (int)PG_OK;
+            },
+            f.fields);
+        check_rc(rc, R.err);
+    }
+    return out;
+}
+
 // ------------------------------------------------------------------ cohort job fed by the device counter
 std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohort_reads(
     UniqueKmersMap& index, const std::string& prefix, const std::vector<std::string>& readfiles, const std::vector<size_t>& kmer_coverages,
