@@ -29,6 +29,14 @@ static constexpr unsigned kLeanExp = PG_LEAN_EXP;
 #define PG_LEAN_UPKEEP_EXP 0
 #endif
 static constexpr unsigned kLeanUpkeepExp = PG_LEAN_UPKEEP_EXP;
+// state block of the lean step (profiles/r21_lean_pairs.txt; results unchanged, A/B builds): 1 puts part A back — a state's products
+// right behind its DPP asm (one pad each); 2 builds part B, measured and not adopted — the emission addresses of the next column
+// formed ahead of the total, in the second MFMA's shadow; 4 puts part C back — the partial sum starts as fma(e, P', 0) beside the
+// first product.  (5: the step of the commit before; 4: A; 6: A + B; 0: A + C, the product; 2: A + B + C)
+#ifndef PG_LEAN_PAIRS_EXP
+#define PG_LEAN_PAIRS_EXP 0
+#endif
+static constexpr unsigned kLeanPairsExp = PG_LEAN_PAIRS_EXP;
 #ifdef PG_LEAN_DPPSUM   // experiment: the wave total by six DPP steps (wave_sum) instead of the two fp64 MFMAs
 static constexpr bool kLeanDppSum = true;
 #else
@@ -88,7 +96,8 @@ static constexpr unsigned kLeanpExp = PG_LEANP_EXP;
 // -DPG_LEAN_TIMELINE builds only (tools/exp_pipe.py, profiles/r04_lean_chain.txt): s_memtime stamps at the segment
 // boundaries of one column step of wave 0, each issued behind a use of the value that ends the segment; the stamps are
 // only read behind the step's barrier (reading one earlier would drain the LDS queue with it).  Sums per segment over
-// the launch go to DevContig::prof[32 + segment] (forward role) / [48 + segment] (backward role), [.. + 15] = steps.
+// the launches of the sweeps are ADDED to DevContig::prof[32 + segment] (forward role) / [48 + segment] (backward role), [.. + 15] = steps;
+// a refill segment (PHASE 5) runs beside them and writes nothing.
 #ifdef PG_LEAN_TIMELINE
 static constexpr bool kLeanTimeline = true;
 #else
@@ -116,6 +125,9 @@ struct LeanTimeline {
     }
     DEVI void write(unsigned long long* o) const {
         if constexpr (kLeanTimeline) { for (int i = 0; i < 9; ++i) o[i] = acc[i]; o[15] = acc[9]; }
+    }
+    DEVI void add(unsigned long long* o) const {   // (the sweeps of a role are launched one behind the other: their sums add up)
+        if constexpr (kLeanTimeline) { for (int i = 0; i < 9; ++i) o[i] += acc[i]; o[15] += acc[9]; }
     }
 };
 

@@ -3103,6 +3103,62 @@ template <int R>
 DEVI void lean_pairs_all(const LeanPairs& lp, double (&e)[R]) {
     static_for<0, R / 2>([&](auto pc) __attribute__((always_inline)) { constexpr int q = decltype(pc)::value; const v2f64 t = lean_pair<q>(lp); e[2 * q] = t.x; e[2 * q + 1] = t.y; });
 }
+// -DPG_LEAN_PAIRS_EXP=2 (measured and NOT adopted — profiles/r21_lean_pairs.txt: 0.7 ms slower on genome24_h64 in every run): the eight
+// emission addresses of a column formed AHEAD of the state block, in the shadow of the total's second MFMA (nothing in them needs
+// the total).  Plain C++ on pair bytes the compiler may not know to be wave-uniform (it would pull them to the scalar unit:
+// v_readfirstlane and eight s_bfe): it selects v_add_u32_sdwa itself, and an instruction of its own counts towards the wait
+// states of the MFMA it stands behind — what an asm statement holds does not.  Every address is pinned where it is formed.
+// The pad in that shadow shrinks by the eight adds and the state block loses them, but the step is no shorter: the wave waits
+// for the total either way, and eight more registers are live over the states.
+template <int R>
+DEVI void lean_pair_addrs(const LeanPairs& lp, uint32_t (&ea)[R / 2]) {
+    uint32_t cd0 = lp.cd0, cd1 = lp.cd1;
+    asm("" : "+v"(cd0));
+    asm("" : "+v"(cd1));
+    static_for<0, R / 2>([&](auto pc) __attribute__((always_inline)) {
+        constexpr int q = decltype(pc)::value;
+        ea[q] = lp.tbase + (((q < 4 ? cd0 : cd1) >> (8 * (q & 3))) & 0xFFu);
+        asm volatile("" : "+v"(ea[q]));
+    });
+}
+// The sixteen states of a column step, by row pairs.  State k: acc = a x[k] + b, acc += u[row k] s (fmac_row_bcast: an asm statement),
+// part = fma(e[k], acc, part), x[k] = e[k] acc — the same operations on the same operands in either role (forward a = c0, b = u_j,
+// s = 2^-es; backward a = k0, b = u_j, s = 1), `part` added up row after row.  hipcc pads an asm statement whose result the NEXT VALU
+// instruction reads with one wait state (it does not know what the statement wrote): a pair therefore forms BOTH states' sums first
+// and their products behind them, each order held by a fence, so that no product stands right behind the statement it reads from.
+// The partial sum starts as the first product: fma(e, P', 0) has the same bits (both factors are >= 0: no -0 arises).
+// pair_done(q, P'_2q, P'_2q+1): the role's store of the pair and the fetch of the pair's next emissions into e.
+template <int R, class PairDone>
+DEVI double lean_states(double a, double b, double urep, double s, double (&x)[R], double (&e)[R], PairDone&& pair_done) {
+    double part = 0.0;
+    constexpr bool kFirstProduct = !(kLeanPairsExp & 4u);
+    static_for<0, R / 2>([&](auto pc) __attribute__((always_inline)) {
+        constexpr int q = decltype(pc)::value, k = 2 * q;
+        auto product = [&](auto kc, double pk) __attribute__((always_inline)) {
+            constexpr int j = decltype(kc)::value;
+            if constexpr (j == 0 && kFirstProduct) { x[0] = e[0] * pk; part = x[0]; }   // (not pinned: x[0] and the sum are one register until the next state)
+            else { part = fma(e[j], pk, part); x[j] = e[j] * pk; pin_here(x[j]); }
+        };
+        if constexpr (kLeanPairsExp & 1u) {
+            const double pa = fmac_row_bcast<k>(fma(a, x[k], b), urep, s);
+            product(std::integral_constant<int, k>{}, pa);
+            const double pb = fmac_row_bcast<k + 1>(fma(a, x[k + 1], b), urep, s);
+            product(std::integral_constant<int, k + 1>{}, pb);
+            pair_done(pc, pa, pb);
+        } else {
+            const double pa = fmac_row_bcast<k>(fma(a, x[k], b), urep, s);
+            lean_fence();
+            const double pb = fmac_row_bcast<k + 1>(fma(a, x[k + 1], b), urep, s);
+            lean_fence();
+            product(std::integral_constant<int, k>{}, pa);
+            lean_fence();
+            product(std::integral_constant<int, k + 1>{}, pb);
+            pair_done(pc, pa, pb);
+        }
+        lean_fence();
+    });
+    return part;
+}
 // The record ring of a launch (pg_device.h: pg_lean_ring_*).  Opening it: block 0 parked and expanded, the piece of block 1 in a
 // register — and for a launch whose first step has a number `s0` behind the step that parks block 1 (a sparse launch numbered
 // from its group grid), block 1 parked and expanded as well, the piece of block 2 in the register.
@@ -3246,6 +3302,9 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
     static_assert(!SPARSE || ((PHASE == 1 || PHASE == 3) && !TRI), "sparse stores: phases 1 and 3 of full-column lean chains");
     constexpr int HP = 64;
     constexpr uint32_t RMASK = (1u << R) - 1u;
+    // (-DPG_LEAN_PAIRS_EXP=2, measured and not adopted: the pairs' emission addresses formed ahead of the total — lean_pair_addrs.  Not
+    //  for the triangle kernels, which stand at 256 VGPRs: eight addresses held over the state block go to scratch there)
+    constexpr bool kAddrsAhead = !TRI && (kLeanPairsExp & 2u) != 0;
     const uint32_t mid = C / 2, K = dc.chunk_cols;
     uint32_t lo = PHASE == 1 ? 0u : mid, hi = PHASE == 1 ? mid : C;
     if constexpr (PHASE == 3) {
@@ -3381,12 +3440,16 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
             gcdouble2* src = (gcdouble2*)resume + toff;
 #pragma unroll
             for (int k = 0; k < R; k += 2) { const v2f64 t = src[(size_t)(k >> 1) * HP]; x[k] = t.x; x[k + 1] = t.y; }
-            // (the partial sum exactly as the step forms it — part = fma(e, P', part), row after row — so that a column resumed from
-            //  memory and one carried in registers (PHASE 4) hand the same bits to the next step: the result does not depend on
-            //  where the chunk boundaries fall)
+            // (the partial sum exactly as the step forms it — the first product, then part = fma(e, P', part) row after row
+            //  (lean_states) — so that a column resumed from memory and one carried in registers (PHASE 4) hand the same bits to the
+            //  next step: the result does not depend on where the chunk boundaries fall)
             if (!fallback[lo - 1]) {
 #pragma unroll
-                for (int k = 0; k < R; ++k) { const double e = sel_by_bit(rb, k, eA, eB); part = fma(e, x[k], part); x[k] *= e; }
+                for (int k = 0; k < R; ++k) {
+                    const double e = sel_by_bit(rb, k, eA, eB);
+                    if (k == 0 && !(kLeanPairsExp & 4u)) { x[0] *= e; part = x[0]; }
+                    else { part = fma(e, x[k], part); x[k] *= e; }
+                }
             } else if ((PHASE == 5 && !boundary) || (SPARSE && PHASE == 1)) {
                 // (the chain went on from this checkpoint in registers: every state 0, the uniform column entering through the first
                 //  step's zero test — the same instructions here give the same bits; a chunk launch resumes from the STORED uniform
@@ -3453,6 +3516,8 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         tl.template mark<2>(msum);                    // first MFMA + three adds
         lean_fence();
         const v4f64 mb = (kLeanDppSum || kLeanPreTotal) ? zz : __builtin_amdgcn_mfma_f64_16x16x4f64(msum, 1.0, zz, 0, 0, 0);
+        uint32_t ea[R / 2];   // (kAddrsAhead: where the pairs' emissions of column t+1 lie, formed here, in the second MFMA's shadow)
+        if constexpr (kAddrsAhead) lean_pair_addrs<R>(lp, ea);
         if constexpr (!kLeanPreTotal) asm volatile("" :: "v"(mb));   // (the whole result stays allocated: a temporary in one of its registers would wait out the MFMA)
         lean_fence();
         double S = (kLeanExp & 4) ? 64.0 * Cj : (kLeanPreTotal ? Spre : (kLeanDppSum ? wave_sum(Cj) : mb[0]));
@@ -3474,22 +3539,18 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         const double sc = ldexp(1.0, -es), c0s = ldexp(c0, -es), ujs = ldexp(uj, -es);
         tl.template mark<4>(c0s + ujs + sc);          // zero test, exponent, scaled constants
         gdouble2* dst = (gdouble2*)col_at(t) + toff;
-        double part = 0.0, pprev = 0.0;
-        static_for<0, R>([&](auto kc) __attribute__((always_inline)) {
-            constexpr int k = decltype(kc)::value;
-            const double pk = fmac_row_bcast<k>(fma(c0s, x[k], ujs), urep, sc);   // P'_t(i0 + k, lane) 2^-es = c0 x + u_j + u_i
-            part = fma(ec[k], pk, part);
-            x[k] = ec[k] * pk;
-            pin_here(x[k]);
-            if constexpr (k == 1) tl.template mark<5>(x[1]);    // the first row pair's states
-            // (the fence keeps every pair's store where it is: eight 1 KB stores issued back to back stall the wave
+        // P'_t(i0 + k, lane) 2^-es = c0 x + u_j + u_i, x_t = e_t P'_t (lean_states)
+        const double part = lean_states<R>(c0s, ujs, urep, sc, x, ec, [&](auto qc, double pa, double pb2) __attribute__((always_inline)) {
+            constexpr int q = decltype(qc)::value;
+            if constexpr (q == 0) tl.template mark<5>(x[1]);    // the first row pair's states
+            // (lean_states' fence keeps every pair's store where it is: eight 1 KB stores issued back to back stall the wave
             // on the memory pipeline's queue — 787 instead of ~650 ns per column)
-            if constexpr (k & 1) {
-                if constexpr (STORE) { if (!(kLeanExp & 1)) put_pair(dst, k >> 1, pprev, pk); }
-                const v2f64 t2 = (kLeanExp & 2) ? v2f64{0.5, 0.5} : lean_pair<(k >> 1)>(lp);   // e_{t+1} of this row pair
-                ec[k - 1] = t2.x; ec[k] = t2.y;
-                __builtin_amdgcn_sched_barrier(0);
-            } else pprev = pk;
+            if constexpr (STORE) { if (!(kLeanExp & 1)) put_pair(dst, q, pa, pb2); }
+            v2f64 t2;   // e_{t+1} of this row pair
+            if constexpr (kLeanExp & 2) t2 = v2f64{0.5, 0.5};
+            else if constexpr (!kAddrsAhead) t2 = lean_pair<q>(lp);
+            else t2 = *(LAS const v2f64*)(uintptr_t)ea[q];
+            ec[2 * q] = t2.x; ec[2 * q + 1] = t2.y;
         });
         tl.template mark<6>(part);                    // the other seven row pairs: states, stores, next emissions
         lean_put_sums<R>(sh, t & 1u, wave, lane, part);
@@ -3587,7 +3648,8 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         if (t < hi) step(kStore, kTested, t, ra, rb2);
     }
     if constexpr (!SPARSE) if (wave == 0 && fsc.valid) fsc.flush(fscale, lane, hi - 1);   // (a segment is not aligned to the 64-column blocks: what is left of its last one)
-    if (kLeanTimeline && tid == 0) tl.write(dc.prof + 32);
+    // (the launches of a role add up; a refill segment runs beside the sweeps and leaves their slots alone)
+    if constexpr (PHASE != 5) if (kLeanTimeline && tid == 0) tl.add(dc.prof + 32);
     {   // the last column of this phase may itself have summed to zero
         const uint32_t pb = (hi - 1) & 1u;
         const double Cj = lean_colsum<R>(sh, pb, lane);
@@ -3600,6 +3662,7 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
     static_assert(!SPARSE || ((PHASE == 1 || PHASE == 3) && !TRI), "sparse stores: phases 1 and 3 of full-column lean chains");
     constexpr int HP = 64;
     constexpr uint32_t RMASK = (1u << R) - 1u;
+    constexpr bool kAddrsAhead = !TRI && (kLeanPairsExp & 2u) != 0;   // (see lean_forward)
     const int64_t mid = C / 2, K = dc.chunk_cols;
     int64_t top = PHASE == 1 ? (int64_t)C - 1 : mid - 1;
     int64_t bot = PHASE == 1 ? mid : 0;
@@ -3729,7 +3792,11 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         const uint32_t rb = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(cur.bits1 >> i0) & RMASK));
         double part = 0.0;
 #pragma unroll
-        for (int k = 0; k < R; ++k) { const double e = sel_by_bit(rb, k, eA, eB); part = fma(e, y[k], part); w[k] = y[k] * e; }   // (as the step: see lean_forward)
+        for (int k = 0; k < R; ++k) {   // (as the step: see lean_forward)
+            const double e = sel_by_bit(rb, k, eA, eB);
+            if (k == 0 && !(kLeanPairsExp & 4u)) { w[0] = y[0] * e; part = w[0]; }
+            else { part = fma(e, y[k], part); w[k] = y[k] * e; }
+        }
         lean_put_sums<R>(sh, (uint32_t)t0 & 1u, wave, lane, part);
     }
     double ec[R];   // (see lean_forward)
@@ -3785,6 +3852,8 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         tl.template mark<4>(msum);                    // first MFMA + three adds
         lean_fence();
         const v4f64 mb = (kLeanDppSum || kLeanPreTotal) ? zz : __builtin_amdgcn_mfma_f64_16x16x4f64(msum, 1.0, zz, 0, 0, 0);
+        uint32_t ea[R / 2];   // (see lean_forward: the pairs' emissions of column t-1)
+        if constexpr (kAddrsAhead) lean_pair_addrs<R>(lp, ea);
         if constexpr (!kLeanPreTotal) asm volatile("" :: "v"(mb));
         lean_fence();
         const double Sw = (kLeanExp & 4) ? 64.0 * Cj : (kLeanPreTotal ? Spre : (kLeanDppSum ? wave_sum(Cj) : mb[0]));
@@ -3793,21 +3862,17 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         const double Snew = kap * Sw;  // = sum(beta'_t)
         Sy = Snew;                     // (1 behind an all-zero column, below)
         gdouble2* dst = (gdouble2*)col_at(t) + toff;
-        double part = 0.0, yprev = 0.0;
         const bool zero = !(Snew > 0.0);   // beta~_t is all zero (below)
-        static_for<0, R>([&](auto kc) __attribute__((always_inline)) {
-            constexpr int k = decltype(kc)::value;
-            const double yk = fmac_row_bcast<k>(fma(k0, w[k], uj), urep, one);  // beta'_t = k0 w + u_j + u_i
-            part = fma(ec[k], yk, part);
-            w[k] = ec[k] * yk;
-            pin_here(w[k]);
-            if constexpr (k == 1) tl.template mark<6>(w[1]);    // u_j, the first row pair's states
-            if constexpr (k & 1) {
-                if constexpr (STORE) { if (!(kLeanExp & 1)) put_pair(dst, k >> 1, yprev, yk); }
-                const v2f64 t2 = (kLeanExp & 2) ? v2f64{0.5, 0.5} : lean_pair<(k >> 1)>(lp);   // e_{t-1} of this row pair
-                ec[k - 1] = t2.x; ec[k] = t2.y;
-                __builtin_amdgcn_sched_barrier(0);
-            } else yprev = yk;
+        // beta'_t = k0 w + u_j + u_i, w_{t-1} = e_t beta'_t (lean_states)
+        double part = lean_states<R>(k0, uj, urep, one, w, ec, [&](auto qc, double ya, double yb) __attribute__((always_inline)) {
+            constexpr int q = decltype(qc)::value;
+            if constexpr (q == 0) tl.template mark<6>(w[1]);    // u_j, the first row pair's states
+            if constexpr (STORE) { if (!(kLeanExp & 1)) put_pair(dst, q, ya, yb); }
+            v2f64 t2;   // e_{t-1} of this row pair
+            if constexpr (kLeanExp & 2) t2 = v2f64{0.5, 0.5};
+            else if constexpr (!kAddrsAhead) t2 = lean_pair<q>(lp);
+            else t2 = *(LAS const v2f64*)(uintptr_t)ea[q];
+            ec[2 * q] = t2.x; ec[2 * q + 1] = t2.y;
         });
         if (__builtin_expect(zero, 0)) {
             // beta~_t is all zero (a sum of non-negative terms: every y_k above IS 0, and so is what was stored): its own
@@ -3904,7 +3969,7 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         if (wave == 1 && bsc.valid) bsc.flush(bscale, lane, (uint64_t)bot);
         if (PHASE != 5 && wave == 2 && bsm.valid) bsm.flush(bsum, lane, (uint64_t)bot);
     }
-    if (kLeanTimeline && tid == 0) tl.write(dc.prof + 48);
+    if constexpr (PHASE != 5) if (kLeanTimeline && tid == 0) tl.add(dc.prof + 48);   // (see lean_forward)
 }
 
 // ------------------------------------------------------------------------------------------

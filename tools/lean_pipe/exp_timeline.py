@@ -35,7 +35,8 @@ PSEG = ["top of the step: LDS reads issued, descriptor of the column after next"
         "Y partial to LDS, last store, per-column scalars", "barrier"]
 if PIPE:
     FWD = BWD = PSEG
-for name, o, segs in (("forward role (last chunk of phase 2)", 32, FWD), ("backward role", 48, BWD)):
+# (the sweeps of a role add their sums up over both phases and both runs; the refill segments beside them write nothing)
+for name, o, segs in (("forward role (every sweep of the role)", 32, FWD), ("backward role (every sweep of the role)", 48, BWD)):
     n = max(p[o + 15], 1.0)
     print("%s: %d steps" % (name, n))
     tot = 0.0

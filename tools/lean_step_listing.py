@@ -7,8 +7,10 @@
 For every kernel named (default: the sparse phase-1 and phase-3 sweeps, k_sweep_lean<1,16,false> and <3,16,false>) it prints,
 for every s_barrier in text order, the SHORTEST path from it to the next barrier over the kernel's branches — the rare bodies (a
 zero-sum column, the upkeep of a block) only lengthen a path, so the shortest one is the common path of the step: the number of
-instructions on it, and how many of them are fp64 arithmetic / LDS / scalar / branches / s_nop / global stores.  The store-free
-steps of the sparse loops are the paths with 80 or more fp64 operations and no global store."""
+instructions on it, and how many of them are fp64 arithmetic / LDS / scalar / branches / s_nop / global stores, and the wait states
+the path's pads stand for (the sum of N + 1 over its `s_nop N`: work moved into a pad's place shortens the pad and leaves the
+count of instructions as it was).  The store-free steps of the sparse loops are the paths with 80 or more fp64 operations and no
+global store."""
 import re
 import sys
 
@@ -68,7 +70,7 @@ def stretches(body):
                         prev[q] = pc
                         nxt.append(q)
             frontier = nxt
-        cur = dict(n=0, f64=0, lds=0, salu=0, branch=0, nop=0, store=0, end="no barrier" if goal is None else ("barrier" if ins[goal][0] == "s_barrier" else "end"))
+        cur = dict(n=0, f64=0, lds=0, salu=0, branch=0, nop=0, wait=0, store=0, end="no barrier" if goal is None else ("barrier" if ins[goal][0] == "s_barrier" else "end"))
         pc = prev.get(goal) if goal is not None else None
         while pc is not None:
             op = ins[pc][0]
@@ -78,6 +80,8 @@ def stretches(body):
             cur["branch"] += op.startswith("s_cbranch") or op == "s_branch"
             cur["salu"] += op.startswith("s_") and not op.startswith(("s_cbranch", "s_branch", "s_nop", "s_waitcnt"))
             cur["nop"] += op == "s_nop"
+            if op == "s_nop":
+                cur["wait"] += int(ins[pc][1], 0) + 1
             cur["store"] += op.startswith("global_store")
             pc = prev[pc]
         out.append(cur)
@@ -92,7 +96,7 @@ def main():
         print(name)
         for i, s in enumerate(stretches(body)):
             print(f"  stretch {i:3d}: {s['n']:4d} instructions  fp64 {s['f64']:3d}  lds {s['lds']:3d}  scalar {s['salu']:3d}  branches {s['branch']:2d}"
-                  f"  s_nop {s['nop']:2d}  global stores {s['store']:2d}  ends at: {s['end']}")
+                  f"  s_nop {s['nop']:2d}  wait states {s['wait']:3d}  global stores {s['store']:2d}  ends at: {s['end']}")
 
 
 if __name__ == "__main__":
