@@ -386,12 +386,15 @@ int pg_transition_probs(uint64_t from_pos, uint64_t to_pos, double recombrate,
  *  that gives the long double's bits; the records hold the same GT and GQ.  The bins stay where they
  *  are: pg_job_fetch* are not affected.
  * ------------------------------------------------------------------ */
+#ifndef PG_CALL_DEFINED /* (the same in pangenie_amd/csrc/pg_calls.h) */
+#define PG_CALL_DEFINED
 typedef struct pg_call {
     uint16_t allele_1, allele_2; /* allele IDS (not slots) of the likeliest genotype, allele_1 <= allele_2; */
                                  /* 0xFFFF / 0xFFFF unless flags == PG_CALL_OK                              */
     uint16_t gq;                 /* get_genotype_quality: 0 .. 192, or 10000                               */
     uint16_t flags;
 } pg_call;
+#endif
 #define PG_CALL_OK 0         /* a unique likeliest genotype                                                      */
 #define PG_CALL_NONE 1       /* ./. : not a kept column, no key, or every bin zero                               */
 #define PG_CALL_NOT_UNIQUE 2 /* ./. : another genotype within 1e-10 of the best (genotypingresult.cpp:164-172)   */
@@ -532,6 +535,51 @@ int  pg_gl_from_values(int device, uint64_t n, const uint64_t* m, const int32_t*
 /* Host only: the text `ostream << setprecision(4)` gives of the value ("%.4g" of the decimal; "-inf"; "0"), its
  * length; -1 for PG_GL_DEFERRED, an encoding that is none of the above, or a buffer too small (32 bytes suffice). */
 int  pg_gl_text(pg_gl value, char* buf, size_t len);
+
+/* ------------------------------------------------------------------ *
+ *  The sample column as TEXT: the bytes of `GT:GQ:GL:KC` of every VCF record, formed on the device
+ *  from the record calls, the record GLs and the chain's coverage, so that writing a sample's VCF is a splice of these
+ *  bytes behind the fixed columns.  The text of a record has no terminator and no separator:
+ *    `a1/a2:gq:` if (flags & 0xFF) == PG_CALL_OK and the record is not a no-call (PG_CALL_EMPTY prints 0/0:10000:),
+ *    else `.:.:`; the GL values as pg_gl_text prints them, joined by `,`; `:` and KC in decimal.
+ *  A record is left to the HOST — length 0, no bytes — if its call is PG_CALL_DEFERRED, if one of its values is
+ *  PG_GL_DEFERRED (or one pg_gl_text refuses), or if it has fewer than 3 values.  The text of all records is packed:
+ *  chain after chain, record after record, no gaps.  Not covered: the records of combined groups, the phasing column.
+ * ------------------------------------------------------------------ */
+/* 19 n_records + 11 n_gl_total: bytes that always suffice (255/255:10000: is 14, a value at most 10, a comma between
+ * values, :65535 is 6).  Host only. */
+uint64_t pg_record_text_bound(uint64_t n_records, uint64_t n_gl_total);
+/* Forms the text of every chain whose index contig has a plan (a chain without one is left out), on the job's stream;
+ * blocking.  Forms the record calls and the record GLs first where they are not formed for this run.  KC and UK (the
+ * bubble's k-mers) follow pg_job_fetch: both 0 for a chain without a kept column; KC is read from the chain's coverage
+ * on the device.  A record is a no-call if ignore_imputed and UK == 0.  Refusals as pg_job_record_calls.  The buffer
+ * (pg_record_text_bound of all records and values, and 12 bytes per record) lies outside the arena and is freed by
+ * pg_job_destroy.  A later run, a new plan or index make the text stale: the fetches answer PG_ERR_INVALID until it is
+ * formed again; forming it with another ignore_imputed replaces it. */
+int  pg_job_record_text(pg_job* job, int ignore_imputed, char* err, size_t errlen);
+/* text_first[n_chains + 1]: every chain's first byte in the packed text; text_first[n_chains] = its length. */
+int  pg_job_record_text_first(pg_job* job, uint64_t* text_first, char* err, size_t errlen);
+/* Chain `chain`'s bytes, text[n_bytes] with n_bytes = text_first[chain + 1] - text_first[chain] (PG_ERR_INVALID
+ * otherwise), and, unless NULL, off[R + 1]: record r's text is text[off[r] .. off[r + 1]), relative to the chain's
+ * first byte; records in the order of pg_job_fetch_record_calls. */
+int  pg_job_fetch_record_text(pg_job* job, uint32_t chain, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen);
+/* All chains: text[n_bytes], n_bytes = text_first[n_chains], ONE copy; off[R_total + 1] (or NULL) absolute in it,
+ * records in the order of pg_job_record_first's calls_first. */
+int  pg_job_fetch_record_text_packed(pg_job* job, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen);
+/* Device-resident text of chain `chain`: *d_text = its first byte, *d_off = uint64 [n_records + 1] offsets that are
+ * ABSOLUTE in the packed text (d_off[0] is the chain's first byte there). */
+int  pg_job_device_record_text(pg_job* job, uint32_t chain, void** d_off, void** d_text, uint64_t* n_records, uint64_t* n_bytes);
+/* Elapsed milliseconds of the kernels of the LAST pg_job_record_text (lengths, scan, text), and of the kernel that
+ * writes the narrow records' text alone. */
+double pg_job_record_text_ms(const pg_job* job);
+double pg_job_record_text_emit_ms(const pg_job* job);
+/* Unit entry point: the text of n_records records from host arrays, through the same kernels: calls[R], record r's
+ * values gl[gl_off[r] .. gl_off[r + 1]), kc[R], no_call[R] (or NULL: none); off[R + 1] and text[cap] come back.
+ * PG_ERR_INVALID, before any device is asked for: null arrays, gl_off that does not start at 0 or shrinks,
+ * cap < pg_record_text_bound(R, gl_off[R]), a PG_CALL_OK call with a GT number above 255 or a GQ above 10000 (the bound
+ * counts on them).  Then PG_ERR_DEVICE without a device: no host fallback. */
+int  pg_record_text_from_fields(int device, uint64_t n_records, const pg_call* calls, const uint64_t* gl_off, const pg_gl* gl,
+                                const uint16_t* kc, const uint8_t* no_call, uint64_t* off, char* text, uint64_t cap);
 
 /* ------------------------------------------------------------------ *
  *  Path subsets: the chains of one contig over different path selections combined on the device, and the calls

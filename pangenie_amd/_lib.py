@@ -298,6 +298,24 @@ def _bind_hip(lib):
     lib.pg_gl_from_values.restype = C.c_int
     lib.pg_gl_text.argtypes = [PgGl, C.c_char_p, C.c_size_t]
     lib.pg_gl_text.restype = C.c_int
+    # the sample column as text
+    lib.pg_record_text_bound.argtypes = [C.c_uint64, C.c_uint64]
+    lib.pg_record_text_bound.restype = C.c_uint64
+    lib.pg_job_record_text.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]
+    lib.pg_job_record_text.restype = C.c_int
+    lib.pg_job_record_text_first.argtypes = [C.c_void_p, u64p, C.c_char_p, C.c_size_t]
+    lib.pg_job_record_text_first.restype = C.c_int
+    lib.pg_job_fetch_record_text.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+    lib.pg_job_fetch_record_text.restype = C.c_int
+    lib.pg_job_fetch_record_text_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+    lib.pg_job_fetch_record_text_packed.restype = C.c_int
+    lib.pg_job_device_record_text.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), u64p, u64p]
+    lib.pg_job_device_record_text.restype = C.c_int
+    for name in ("pg_job_record_text_ms", "pg_job_record_text_emit_ms"):
+        getattr(lib, name).argtypes = [C.c_void_p]
+        getattr(lib, name).restype = C.c_double
+    lib.pg_record_text_from_fields.argtypes = [C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    lib.pg_record_text_from_fields.restype = C.c_int
     # path subsets combined on the device (pangenie_amd/calls.py); bins are read as numpy arrays of COMBINED_DTYPE
     lib.pg_job_combine_plan.argtypes = [C.c_void_p, C.c_uint32, u32p, u32p, C.c_char_p, C.c_size_t]
     lib.pg_job_combine_plan.restype = C.c_int
@@ -372,6 +390,8 @@ HIP_ABI_SYMBOLS = [
     "pg_job_fetch_combined_record_calls_all", "pg_job_fetch_combined_record_gl_all", "pg_job_device_combined_record_calls",
     "pg_job_device_combined_record_gl", "pg_job_combined_record_calls_ms", "pg_job_combined_record_gl_ms",
     "pg_record_calls_from_combined", "pg_record_gl_from_combined",
+    "pg_record_text_bound", "pg_job_record_text", "pg_job_record_text_first", "pg_job_fetch_record_text", "pg_job_fetch_record_text_packed",
+    "pg_job_device_record_text", "pg_job_record_text_ms", "pg_job_record_text_emit_ms", "pg_record_text_from_fields",
 ]
 
 

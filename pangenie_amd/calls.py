@@ -384,6 +384,85 @@ def gl_text(value) -> Optional[str]:
 
 
 # ---------------------------------------------------------------------------------------------------------------
+#  The sample column as text (pg_job_record_text, pg_record_text_from_fields)
+# ---------------------------------------------------------------------------------------------------------------
+def record_text_bound(n_records: int, n_gl_total: int) -> int:
+    """pg_record_text_bound: bytes that always suffice for the text of n_records records with n_gl_total values."""
+    return int(_lib.load_hip().pg_record_text_bound(int(n_records), int(n_gl_total)))
+
+
+def _record_text_first(job) -> np.ndarray:
+    first = np.zeros(job.n_chains + 1, np.uint64)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_record_text_first(job.h, first.ctypes.data_as(_lib.u64p), err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return first
+
+
+def form_record_text(job, ignore_imputed: bool = False) -> None:
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_record_text(job.h, 1 if ignore_imputed else 0, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+
+
+def fetch_record_text(job, contig: int):
+    """pg_job_fetch_record_text: (off [R + 1], bytes) of chain `contig`; record r's text is bytes[off[r]:off[r + 1]]."""
+    first = _record_text_first(job)
+    n = int(first[contig + 1] - first[contig])
+    off = np.zeros(_n_records(job)[contig] + 1, np.uint64)
+    text = np.zeros(max(n, 1), np.uint8)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_record_text(job.h, contig, off.ctypes.data, text.ctypes.data, n, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return off, text[:n].tobytes()
+
+
+def fetch_record_text_packed(job):
+    """pg_job_fetch_record_text_packed: (off [R_total + 1] absolute in the packed text, bytes, text_first [n_chains + 1])."""
+    first = _record_text_first(job)
+    n = int(first[-1])
+    off = np.zeros(sum(_n_records(job)) + 1, np.uint64)
+    text = np.zeros(max(n, 1), np.uint8)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_record_text_packed(job.h, off.ctypes.data, text.ctypes.data, n, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return off, text[:n].tobytes(), first
+
+
+def job_record_text(job, contig: Optional[int] = None, ignore_imputed: bool = False):
+    """Job.record_text(): forms the text of every chain that has a plan; (off, bytes) of chain `contig`, or of every chain."""
+    form_record_text(job, ignore_imputed)
+    if contig is not None:
+        return fetch_record_text(job, contig)
+    return [fetch_record_text(job, c) for c in range(job.n_chains)]
+
+
+def record_text_from_fields(calls, gl_off, gl, kc, no_call=None, device: int = 0):
+    """pg_record_text_from_fields: (off [R + 1], bytes) — the text of R records from their calls (CALL_DTYPE), their GL values
+    (GL_DTYPE, record r's at gl_off[r] .. gl_off[r + 1]), kc [R] and no_call [R] (or None), through the job's kernels.  A
+    record of length 0 is the host's."""
+    lib = _lib.load_hip()
+    cc, go = np.ascontiguousarray(calls, CALL_DTYPE), np.ascontiguousarray(gl_off, np.uint64)
+    gg, kk = np.ascontiguousarray(gl, GL_DTYPE), np.ascontiguousarray(kc, np.uint16)
+    nc = None if no_call is None else np.ascontiguousarray(no_call, np.uint8)
+    R = len(cc)
+    if len(go) != R + 1 or len(kk) != R or (nc is not None and len(nc) != R) or (R and int(go[-1]) != len(gg)):
+        raise ValueError("record_text_from_fields: array lengths do not match")
+    cap = record_text_bound(R, len(gg))
+    off = np.zeros(R + 1, np.uint64)
+    text = np.zeros(max(cap, 1), np.uint8)
+    rc = lib.pg_record_text_from_fields(device, R, cc.ctypes.data, go.ctypes.data, gg.ctypes.data, kk.ctypes.data,
+                                        None if nc is None else nc.ctypes.data, off.ctypes.data, text.ctypes.data, cap)
+    if rc:
+        raise _error(rc, None)
+    return off, text[:int(off[-1])].tobytes()
+
+
+# ---------------------------------------------------------------------------------------------------------------
 #  Path subsets combined on the device (pg_job_combine_plan, pg_job_combine, pg_job_combined_calls, pg_combine_bins,
 #  pg_calls_from_combined; DESIGN.md 4e-4)
 # ---------------------------------------------------------------------------------------------------------------

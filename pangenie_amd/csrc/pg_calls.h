@@ -491,6 +491,137 @@ PGX_FN void pgx_record_gl(Keys& keys, uint32_t n_alleles, bool has_undefined, Vc
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+//  The text of one VCF record's sample column, `GT:GQ:GL:KC`: what Graph::genotypes_records prints of a
+//  record's call, its GL values and its bubble's coverage.  Pure integer formatting, one rule for the kernels of
+//  pg_record_text.hip and for the host.  The text has no terminator and no separator; it is, in order,
+//    1. `a1/a2:gq:` if (flags & 0xFF) == PGX_CALL_OK and not no_call (PGX_CALL_EMPTY prints like OK: 0/0:10000:), else `.:.:`
+//    2. the n_gl values as pgx_gl_text prints them, joined by `,`
+//    3. `:` and kc in decimal.
+//  A record is THE HOST'S — length 0, nothing written — if its call is PGX_CALL_DEFERRED, if one of its values is
+//  PG_GL_DEFERRED or one pgx_gl_text refuses, or if n_gl < 3 (the host throws "too few likelihoods" for it).
+//  Every character goes through a sink's put(): one that counts gives the length, one that stores gives the text, so the
+//  two cannot differ; no array is indexed at run time (on the device it would be scratch memory).
+// ---------------------------------------------------------------------------------------------------------------
+#ifndef PG_CALL_DEFINED   // (the same in include/pangenie_hmm.h)
+#define PG_CALL_DEFINED
+typedef struct pg_call { uint16_t allele_1, allele_2; uint16_t gq; uint16_t flags; } pg_call;
+#endif
+
+#if defined(__HIP__)
+#define PGX_MEM __host__ __device__
+#else
+#define PGX_MEM
+#endif
+
+struct pgx_count_sink {
+    uint32_t n;
+    PGX_MEM void put(char) { ++n; }
+};
+struct pgx_buf_sink {
+    char* p;
+    uint32_t n;
+    PGX_MEM void put(char c) { p[n++] = c; }
+};
+
+// 255/255:10000: is 14 bytes, a value at most 10 (-1.234e-05, -0.0001234), n_gl - 1 commas, :65535 is 6
+#define PGX_TEXT_PER_RECORD 19u
+#define PGX_TEXT_PER_VALUE 11u
+PGX_FN uint64_t pgx_record_text_bound(uint64_t n_records, uint64_t n_gl_total) { return PGX_TEXT_PER_RECORD * n_records + PGX_TEXT_PER_VALUE * n_gl_total; }
+
+template <class Sink>
+PGX_FN void pgx_put_uint(uint32_t v, Sink& s) {
+    uint32_t div = 1;
+    while (v / div >= 10u) div *= 10u;
+    for (; div; div /= 10u) s.put((char)('0' + (v / div) % 10u));
+}
+
+// a value pgx_gl_text answers -1 for
+PGX_FN bool pgx_gl_refused(pg_gl g) {
+    if (g.mant == 0) return !(g.exp10 == PG_GL_NEG_INF || g.exp10 == 0);
+    const int a = g.mant < 0 ? -(int)g.mant : (int)g.mant;
+    return a < 1000 || a > 9999 || g.exp10 < -99 || g.exp10 > 99;
+}
+
+// the characters of pgx_gl_text, for a value that is not refused
+template <class Sink>
+PGX_FN void pgx_gl_put(pg_gl g, Sink& s) {
+    if (g.mant == 0) {
+        if (g.exp10 == 0) s.put('0');
+        else { s.put('-'); s.put('i'); s.put('n'); s.put('f'); }
+        return;
+    }
+    const int a = g.mant < 0 ? -(int)g.mant : (int)g.mant;
+    const int X = g.exp10;
+    const int d0 = a / 1000, d1 = (a / 100) % 10, d2 = (a / 10) % 10, d3 = a % 10;
+    const int nd = d3 ? 4 : d2 ? 3 : d1 ? 2 : 1;   // trailing zeros stripped
+#define PGX_DIGIT(i) ((char)('0' + ((i) == 0 ? d0 : (i) == 1 ? d1 : (i) == 2 ? d2 : d3)))
+    if (g.mant < 0) s.put('-');
+    if (X < -4 || X >= 4) {
+        s.put(PGX_DIGIT(0));
+        if (nd > 1) { s.put('.'); for (int i = 1; i < nd; ++i) s.put(PGX_DIGIT(i)); }
+        s.put('e');
+        s.put(X < 0 ? '-' : '+');
+        const int ax = X < 0 ? -X : X;
+        s.put((char)('0' + ax / 10));
+        s.put((char)('0' + ax % 10));
+    } else if (X >= 0) {
+        for (int i = 0; i <= X; ++i) s.put(i < nd ? PGX_DIGIT(i) : '0');
+        if (nd > X + 1) { s.put('.'); for (int i = X + 1; i < nd; ++i) s.put(PGX_DIGIT(i)); }
+    } else {
+        s.put('0'); s.put('.');
+        for (int i = 0; i < -X - 1; ++i) s.put('0');
+        for (int i = 0; i < nd; ++i) s.put(PGX_DIGIT(i));
+    }
+#undef PGX_DIGIT
+}
+
+// is the record the host's?  (the values are looked at only if the call and n_gl do not already say so)
+PGX_FN bool pgx_record_is_hosts(pg_call call, const pg_gl* gl, uint32_t n_gl) {
+    if ((call.flags & 0xFFu) == PGX_CALL_DEFERRED || n_gl < 3u) return true;
+    for (uint32_t i = 0; i < n_gl; ++i)
+        if (pgx_gl_refused(gl[i])) return true;
+    return false;
+}
+
+// the three parts of a record that is not the host's
+template <class Sink>
+PGX_FN void pgx_record_head_put(pg_call call, bool no_call, Sink& s) {
+    if ((call.flags & 0xFFu) == PGX_CALL_OK && !no_call) {
+        pgx_put_uint(call.allele_1, s); s.put('/'); pgx_put_uint(call.allele_2, s); s.put(':'); pgx_put_uint(call.gq, s); s.put(':');
+    } else { s.put('.'); s.put(':'); s.put('.'); s.put(':'); }
+}
+template <class Sink>
+PGX_FN void pgx_record_tail_put(uint32_t kc, Sink& s) { s.put(':'); pgx_put_uint(kc, s); }
+template <class Sink>
+PGX_FN void pgx_record_put(pg_call call, const pg_gl* gl, uint32_t n_gl, uint32_t kc, bool no_call, Sink& s) {
+    pgx_record_head_put(call, no_call, s);
+    for (uint32_t i = 0; i < n_gl; ++i) {
+        if (i) s.put(',');
+        pgx_gl_put(gl[i], s);
+    }
+    pgx_record_tail_put(kc, s);
+}
+
+// the length of the record's text; 0: the host's
+PGX_FN uint32_t pgx_record_text_len(pg_call call, const pg_gl* gl, uint32_t n_gl, uint32_t kc, bool no_call) {
+    if (pgx_record_is_hosts(call, gl, n_gl)) return 0;
+    pgx_count_sink s;
+    s.n = 0;
+    pgx_record_put(call, gl, n_gl, kc, no_call, s);
+    return s.n;
+}
+// writes the text to buf (pgx_record_text_bound(1, n_gl) bytes suffice for GT numbers up to 255 and a GQ up to 10000);
+// the length, 0 and nothing written for the host's
+PGX_FN uint32_t pgx_record_text(pg_call call, const pg_gl* gl, uint32_t n_gl, uint32_t kc, bool no_call, char* buf) {
+    if (pgx_record_is_hosts(call, gl, n_gl)) return 0;
+    pgx_buf_sink s;
+    s.p = buf;
+    s.n = 0;
+    pgx_record_put(call, gl, n_gl, kc, no_call, s);
+    return s.n;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 //  Host only: the pair <-> long double, and the threshold table from log10l itself.
 // ---------------------------------------------------------------------------------------------------------------
 #include <math.h>

@@ -174,8 +174,26 @@ struct OutputFamily {
     uint32_t blocks = 0, wide = 0, max_bins = 0, stride = 0, slots = 0;
     bool dirty = true;                        // records: a plan or the index changed: descriptors, lists and the id check are redone
     bool formed = false;                      // a launch over the buffer as it is has finished (NOT reset by a later pg_job_run)
+    uint64_t run = 0;                         // pg_job::run_serial of the run that launch formed it from (0: none)
     double ms = 0.0;
     void release() { if (d) hipFree(d); d = nullptr; }
+};
+
+// The record text (pg_job_record_text) is one more family: `first` = the first RECORD of every chain, and d =
+// the packed text, then every record's first byte in it (64 bits, one more behind the last), the scan's arrays, the
+// descriptors and the wide list.  Unlike its siblings it is stale after a later run: its fetches ask for `run`.
+struct RecordTextFamily : OutputFamily {
+    std::vector<uint64_t> text_first;         // [n_chains + 1] first byte of every chain (after a forming)
+    std::vector<RTextDesc> desc;              // host copy (chains with records)
+    size_t o_off = 0, o_loc = 0, o_wlen = 0, o_bsum = 0, o_bbase = 0;
+    uint64_t n_records = 0, cap = 0;
+    hipEvent_t ev_emit[2];
+    bool events = false;
+    double emit_ms = 0.0;
+    void release() {
+        OutputFamily::release();
+        if (events) { hipEventDestroy(ev_emit[0]); hipEventDestroy(ev_emit[1]); events = false; }
+    }
 };
 
 // What a job keeps of its combine plan (pg_shim_combine.cpp): the groups, and ONE device buffer outside the
@@ -379,6 +397,8 @@ struct pg_job {
     // Record GLs (pg_job_record_gl): 4 bytes per genotype of every record's defined alleles, chain after chain, under the same plans.
     pgj::OutputFamily rgl;                    // (first: the first VALUE of every chain)
     std::vector<RGlDesc> rgl_desc;
+    // Record text (pg_job_record_text): the bytes of the GT:GQ:GL:KC column of every record, packed, from the two families above.
+    pgj::RecordTextFamily rtext;
     // Path subsets combined on the device (pg_job_combine_plan / pg_job_combine / pg_job_combined_calls).
     pgj::CombineState combine;
     uint64_t combine_serial = 0;              // counts the finished pg_job_combine calls
@@ -392,6 +412,7 @@ namespace pgj __attribute__((visibility("hidden"))) {
 inline void record_plans_changed(pg_job* job) {
     job->rcalls.dirty = true;
     job->rgl.dirty = true;
+    job->rtext.dirty = true;          // (its descriptors point into the two buffers above)
     job->rplan_ids_ok = false;
     job->combine.layout_ok = false;   // (the members' layouts are compared again before the next combine)
     job->crec.dirty = true;           // (the records of the combined groups: rebuilt, the ids checked again)

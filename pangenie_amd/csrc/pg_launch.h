@@ -1,4 +1,4 @@
-// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp, pg_shim_run.cpp, pg_shim_calls.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip, pg_calls.hip, pg_combine.hip, pg_combine_records.hip).
+// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp, pg_shim_run.cpp, pg_shim_calls.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip, pg_calls.hip, pg_combine.hip, pg_combine_records.hip, pg_record_text.hip).
 //
 // The ONE declaration of every host-callable launcher and of the two launch masks a job hands them.  Both sides include
 // it: a launcher whose parameter list changes on one side only no longer compiles (C linkage: the linker would not notice).
@@ -107,7 +107,35 @@ struct CRecDesc {
     RecPlanDev plan;
 };
 
+// Record text (pg_record_text.hip): one descriptor per chain (or per call of the unit entry point) that has
+// records, in chain order.  Blocks [blk0, next blk0) take pgk_rtext_block() RECORDS each; rec0 = the chain's first record
+// among all records of the launch (the offsets and the packed text are the launch's, not the chain's).  `calls` = the chain's
+// pg_call records, `gl` its pg_gl values, record r's at gl_off[r] .. gl_off[r + 1].  With rec_var (a job's chain): KC, UK and
+// the column count are read from DevContig `chain`, under pg_job_fetch's rule; without (the unit entry point): kc [R] and
+// no_call [R] (or null) per record.
+struct RTextDesc {
+    uint32_t blk0, R;
+    uint64_t rec0;
+    uint32_t chain, ignore_imputed;
+    const void* calls;
+    const void* gl;
+    const uint64_t* gl_off;
+    const uint32_t* rec_var;
+    const uint16_t* kc;
+    const uint8_t* no_call;
+};
+
 extern "C" {
+// pg_record_text.hip: d_wide = uint2 {descriptor, record} of every record with more than pgk_rtext_wide_values() values;
+// d_loc [n_records], d_wlen [n_wide], d_bsum [n_blocks], d_bbase [n_blocks + 1]: the scan's; d_off [n_records + 1] = every
+// record's first byte in d_text (`cap` bytes of room), the total behind the last.  The two events (or null) go around
+// k_rtext_emit alone.
+void pgk_launch_rtext(const DevContig* d_contigs, const RTextDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide, uint32_t n_wide,
+                      uint32_t* d_loc, uint32_t* d_wlen, uint32_t* d_bsum, uint64_t* d_bbase, uint64_t* d_off, uint64_t n_records, char* d_text,
+                      uint64_t cap, hipEvent_t emit_begin, hipEvent_t emit_end, hipStream_t s);
+uint32_t pgk_rtext_block(void);
+uint32_t pgk_rtext_stage_bytes(void);
+uint32_t pgk_rtext_wide_values(void);
 // pg_combine_records.hip: d_wide = uint2 {descriptor, record} of every record of a bubble with more than PG_AMAX alleles;
 // d_stage = n_slots staging slots of `stride` 16-byte values each (max_bins quotients, then the folded map), one per block
 void pgk_launch_crcalls(const DevContig* d_contigs, const CRecDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, const void* d_wide, uint32_t n_wide,

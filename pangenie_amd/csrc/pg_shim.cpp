@@ -333,6 +333,7 @@ extern "C" void pg_job_destroy(pg_job* job) {
     job->calls.release();
     job->rcalls.release();
     job->rgl.release();
+    job->rtext.release();
     job->combine.release();
     job->crec.release();
     job->rplans.clear();

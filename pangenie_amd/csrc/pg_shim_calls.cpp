@@ -1,5 +1,6 @@
 // pg_shim_calls.cpp — the C-ABI of the output columns formed from a job's finished bins (pg_calls.hip; DESIGN.md 4e .. 4e-3):
-// the calls per variant, the calls per VCF record and the GL column per record.  Host code off the critical path.
+// the calls per variant, the calls per VCF record, the GL column per record and — from the last two — the bytes of the sample
+// column (pg_record_text.hip, 4e-6).  Host code off the critical path.
 //
 // The three families differ in their descriptor type, in whether record plans and staging slots come along, and in what
 // comes back; everything else is ONE path: the state a job keeps of a family (OutputFamily, pg_job.h), the opening checks
@@ -120,6 +121,7 @@ int timed_launch(pg_job* job, OutputFamily& f, Launch launch, char* err, size_t 
     HIP_TRY(hipEventElapsedTime(&ms, job->ev_calls[0], job->ev_calls[1]));
     f.ms = ms;
     f.formed = true;
+    f.run = job->run_serial;
     return PG_OK;
 }
 
@@ -799,6 +801,238 @@ extern "C" int pg_gl_from_values(int device, uint64_t n, const uint64_t* m, cons
         pgk_launch_gl_values((const uint64_t*)d, (const int32_t*)(d + o_e), d + o_out, (uint32_t)n, nullptr);
         ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
              hipMemcpy(out, d + o_out, n * sizeof(pg_gl), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    hipFree(d);
+    return ok ? PG_OK : PG_ERR_DEVICE;
+}
+
+// ---------------------------------------------------------------------------------------
+//  The record text: the bytes of the GT:GQ:GL:KC column (pg_record_text.hip).
+// ---------------------------------------------------------------------------------------
+namespace {
+
+// Where the arrays of one launch lie in ONE buffer: the packed text (`cap` bytes), then the offsets, the scan's arrays, the
+// descriptors and the wide list.
+struct RTextLayout {
+    size_t o_off, o_loc, o_wlen, o_bsum, o_bbase, o_desc, o_wide, total;
+    RTextLayout(uint64_t cap, uint64_t R, uint32_t n_blocks, size_t n_desc, size_t n_wide) {
+        o_off = align_up((size_t)cap + 16);
+        o_loc = o_off + align_up(((size_t)R + 1) * 8 + 8);
+        o_wlen = o_loc + align_up((size_t)R * 4 + 8);
+        o_bsum = o_wlen + align_up(n_wide * 4 + 8);
+        o_bbase = o_bsum + align_up((size_t)n_blocks * 4 + 8);
+        o_desc = o_bbase + align_up(((size_t)n_blocks + 1) * 8 + 8);
+        o_wide = o_desc + align_up(n_desc * sizeof(RTextDesc) + 8);
+        total = o_wide + align_up(n_wide * 8 + 8);
+    }
+};
+
+void rtext_launch(const DevContig* d_contigs, unsigned char* d, const RTextLayout& L, uint32_t n_desc, uint32_t n_blocks, uint32_t n_wide, uint64_t R,
+                  uint64_t cap, hipEvent_t e0, hipEvent_t e1, hipStream_t s) {
+    pgk_launch_rtext(d_contigs, (const RTextDesc*)(d + L.o_desc), n_desc, n_blocks, d + L.o_wide, n_wide, (uint32_t*)(d + L.o_loc), (uint32_t*)(d + L.o_wlen),
+                     (uint32_t*)(d + L.o_bsum), (uint64_t*)(d + L.o_bbase), (uint64_t*)(d + L.o_off), R, (char*)d, cap, e0, e1, s);
+}
+
+int rtext_ready(pg_job* job, char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
+    const RecordTextFamily& f = job->rtext;
+    if (!f.formed || f.dirty || f.run != job->run_serial) { set_err(err, errlen, "pg_job_record_text has not been called for this run and these plans"); return PG_ERR_INVALID; }
+    return PG_OK;
+}
+
+bool family_current(const pg_job* job, const OutputFamily& f) { return f.formed && !f.dirty && f.run == job->run_serial; }
+
+}  // namespace
+
+extern "C" uint64_t pg_record_text_bound(uint64_t n_records, uint64_t n_gl_total) { return pgx_record_text_bound(n_records, n_gl_total); }
+
+extern "C" int pg_job_record_text(pg_job* job, int ignore_imputed, char* err, size_t errlen) {
+    int rc = form_begin(job, "form text from", nullptr, nullptr, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (!family_current(job, job->rcalls) && (rc = pg_job_record_calls(job, err, errlen)) != PG_OK) return rc;
+    if (!family_current(job, job->rgl) && (rc = pg_job_record_gl(job, err, errlen)) != PG_OK) return rc;
+    RecordTextFamily& f = job->rtext;
+    const uint32_t n = (uint32_t)job->chains.size();
+    if (!f.events) {
+        HIP_TRY(hipEventCreate(&f.ev_emit[0]));
+        HIP_TRY(hipEventCreate(&f.ev_emit[1]));
+        f.events = true;
+    }
+    if (f.dirty) {   // a plan or the index has changed: the two families above have been rebuilt, this one follows them
+        if (job->rcalls_desc.size() != job->rgl_desc.size()) { set_err(err, errlen, "the record calls and the record GLs describe different chains"); return PG_ERR_INVALID; }
+        const uint32_t per = pgk_rtext_block(), wide_above = pgk_rtext_wide_values();
+        std::map<const RecordPlanHost*, std::vector<uint64_t>> offs;   // (one array per PLAN)
+        std::vector<RTextDesc> desc;
+        std::vector<uint32_t> wide;
+        uint32_t blk = 0;
+        for (size_t i = 0; i < job->rcalls_desc.size(); ++i) {
+            const RCallsDesc& c = job->rcalls_desc[i];
+            const RGlDesc& g = job->rgl_desc[i];
+            if (c.chain != g.chain || c.R != g.R) { set_err(err, errlen, "the record calls and the record GLs describe different chains"); return PG_ERR_INVALID; }
+            RTextDesc d;
+            memset(&d, 0, sizeof(d));
+            d.blk0 = blk; d.R = c.R; d.rec0 = job->rcalls.first[c.chain]; d.chain = c.chain;
+            d.calls = c.out; d.gl = g.out; d.gl_off = g.gl_off; d.rec_var = c.plan.rec_var;
+            const RecordPlanHost* h = plan_of_chain(job, c.chain);
+            auto it = offs.find(h);
+            if (it == offs.end()) it = offs.emplace(h, record_gl_offsets(*h)).first;
+            const std::vector<uint64_t>& go = it->second;
+            for (uint32_t q = 0; q < c.R; ++q)
+                if (go[q + 1] - go[q] > wide_above) { wide.push_back((uint32_t)desc.size()); wide.push_back(q); }
+            desc.push_back(d);
+            blk += (c.R + per - 1) / per;
+        }
+        const uint64_t R = job->rcalls.first[n], cap = pgx_record_text_bound(R, job->rgl.first[n]);
+        const RTextLayout L(cap, R, blk, desc.size(), wide.size() / 2);
+        unsigned char* d = nullptr;
+        if (hipMalloc((void**)&d, L.total) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the record text failed", L.total); return PG_ERR_NOMEM; }
+        if (!wide.empty() && hipMemcpy(d + L.o_wide, wide.data(), wide.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+            hipFree(d);
+            set_err(err, errlen, "upload of the record text's wide list failed");
+            return PG_ERR_DEVICE;
+        }
+        f.OutputFamily::release();
+        f.d = d;
+        f.first = job->rcalls.first;
+        f.desc = std::move(desc);
+        f.blocks = blk; f.wide = (uint32_t)(wide.size() / 2);
+        f.o_off = L.o_off; f.o_loc = L.o_loc; f.o_wlen = L.o_wlen; f.o_bsum = L.o_bsum; f.o_bbase = L.o_bbase; f.o_desc = L.o_desc; f.o_wide = L.o_wide;
+        f.n_records = R; f.cap = cap;
+        f.dirty = false;
+        f.formed = false;
+    }
+    for (RTextDesc& d : f.desc) d.ignore_imputed = ignore_imputed ? 1u : 0u;
+    const RTextLayout L(f.cap, f.n_records, f.blocks, f.desc.size(), f.wide);
+    if (!f.desc.empty()) HIP_TRY(hipMemcpyAsync(f.d + L.o_desc, f.desc.data(), f.desc.size() * sizeof(RTextDesc), hipMemcpyHostToDevice, job->stream));
+    f.formed = false;
+    rc = timed_launch(job, f, [&](hipStream_t s) {
+        rtext_launch(job->d_contigs, f.d, L, (uint32_t)f.desc.size(), f.blocks, f.wide, f.n_records, f.cap, f.ev_emit[0], f.ev_emit[1], s);
+    }, err, errlen);
+    if (rc != PG_OK) { f.formed = false; return rc; }
+    f.formed = false;   // (until every chain's first byte is known)
+    f.emit_ms = 0.0;
+    f.text_first.assign((size_t)n + 1, 0);
+    if (!f.desc.empty() && f.blocks) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, f.ev_emit[0], f.ev_emit[1]));
+        f.emit_ms = ms;
+        std::vector<uint64_t> bbase((size_t)f.blocks + 1);
+        HIP_TRY(hipMemcpy(bbase.data(), f.d + L.o_bbase, bbase.size() * 8, hipMemcpyDeviceToHost));
+        if (bbase.back() > f.cap) { set_err(err, errlen, "the record text takes %llu bytes, more than its bound %llu", (unsigned long long)bbase.back(), (unsigned long long)f.cap); return PG_ERR_DEVICE; }
+        size_t i = 0;   // a chain begins a block: its first byte is that block's
+        for (uint32_t c = 0; c < n; ++c) {
+            f.text_first[c] = i < f.desc.size() ? bbase[f.desc[i].blk0] : bbase.back();
+            if (i < f.desc.size() && f.desc[i].chain == c) ++i;
+        }
+        f.text_first[n] = bbase.back();
+    }
+    f.formed = true;
+    return PG_OK;
+}
+
+extern "C" double pg_job_record_text_ms(const pg_job* job) { return job ? job->rtext.ms : 0.0; }
+extern "C" double pg_job_record_text_emit_ms(const pg_job* job) { return job ? job->rtext.emit_ms : 0.0; }
+
+extern "C" int pg_job_record_text_first(pg_job* job, uint64_t* text_first, char* err, size_t errlen) {
+    int rc = rtext_ready(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (!text_first) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    memcpy(text_first, job->rtext.text_first.data(), job->rtext.text_first.size() * sizeof(uint64_t));
+    return PG_OK;
+}
+
+namespace {
+
+// records [r0, r1) of a formed job: their offsets less `minus` (or none) and their bytes, n_bytes of them
+int rtext_fetch(pg_job* job, uint64_t r0, uint64_t r1, uint64_t b0, uint64_t b1, uint64_t minus, uint64_t* off, char* text, uint64_t n_bytes, char* err,
+                size_t errlen) {
+    const RecordTextFamily& f = job->rtext;
+    if (n_bytes != b1 - b0) { set_err(err, errlen, "the text holds %llu bytes, not %llu", (unsigned long long)(b1 - b0), (unsigned long long)n_bytes); return PG_ERR_INVALID; }
+    if (n_bytes && !text) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(job->device));
+    if (off) {
+        if (f.n_records == 0) off[0] = 0;
+        else HIP_TRY(hipMemcpyAsync(off, f.d + f.o_off + r0 * 8, (r1 - r0 + 1) * 8, hipMemcpyDeviceToHost, job->stream));
+    }
+    if (n_bytes) HIP_TRY(hipMemcpyAsync(text, f.d + b0, n_bytes, hipMemcpyDeviceToHost, job->stream));
+    HIP_TRY(hipStreamSynchronize(job->stream));
+    if (off && minus && f.n_records)
+        for (uint64_t q = 0; q <= r1 - r0; ++q) off[q] -= minus;
+    return PG_OK;
+}
+
+}  // namespace
+
+extern "C" int pg_job_fetch_record_text(pg_job* job, uint32_t ci, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
+    int rc = rtext_ready(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (ci >= job->chains.size()) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    const RecordTextFamily& f = job->rtext;
+    return rtext_fetch(job, f.first[ci], f.first[ci + 1], f.text_first[ci], f.text_first[ci + 1], f.text_first[ci], off, text, n_bytes, err, errlen);
+}
+
+extern "C" int pg_job_fetch_record_text_packed(pg_job* job, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
+    int rc = rtext_ready(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    const RecordTextFamily& f = job->rtext;
+    return rtext_fetch(job, 0, f.n_records, 0, f.text_first.back(), 0, off, text, n_bytes, err, errlen);
+}
+
+extern "C" int pg_job_device_record_text(pg_job* job, uint32_t ci, void** d_off, void** d_text, uint64_t* n_records, uint64_t* n_bytes) {
+    if (rtext_ready(job, nullptr, 0) != PG_OK || ci >= job->chains.size()) return PG_ERR_INVALID;
+    const RecordTextFamily& f = job->rtext;
+    if (d_off) *d_off = f.d + f.o_off + f.first[ci] * 8;
+    if (d_text) *d_text = f.d + f.text_first[ci];
+    if (n_records) *n_records = f.first[ci + 1] - f.first[ci];
+    if (n_bytes) *n_bytes = f.text_first[ci + 1] - f.text_first[ci];
+    return PG_OK;
+}
+
+// The unit entry point: arbitrary fields in, the packed text and its offsets out, through the same kernels.
+extern "C" int pg_record_text_from_fields(int device, uint64_t n_records, const pg_call* calls, const uint64_t* gl_off, const pg_gl* gl, const uint16_t* kc,
+                                          const uint8_t* no_call, uint64_t* off, char* text, uint64_t cap) {
+    if (!off || !gl_off || n_records >= 0x80000000ull) return PG_ERR_INVALID;
+    if (n_records && (!calls || !kc)) return PG_ERR_INVALID;
+    if (gl_off[0] != 0) return PG_ERR_INVALID;
+    for (uint64_t q = 0; q < n_records; ++q)
+        if (gl_off[q + 1] < gl_off[q]) return PG_ERR_INVALID;
+    const uint64_t n_gl = gl_off[n_records];
+    if ((n_gl && !gl) || cap < pgx_record_text_bound(n_records, n_gl) || (cap && !text)) return PG_ERR_INVALID;
+    for (uint64_t q = 0; q < n_records; ++q)   // what the bound counts on: GT numbers up to 255, a GQ up to 10000
+        if ((calls[q].flags & 0xFFu) == PG_CALL_OK && (calls[q].allele_1 > 255 || calls[q].allele_2 > 255 || calls[q].gq > PG_GQ_CERTAIN)) return PG_ERR_INVALID;
+    if (n_records == 0) { off[0] = 0; return PG_OK; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); return PG_ERR_DEVICE; }
+    if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return PG_ERR_DEVICE;
+    const uint32_t per = pgk_rtext_block(), wide_above = pgk_rtext_wide_values(), R = (uint32_t)n_records, n_blocks = (R + per - 1) / per;
+    std::vector<uint32_t> wide;
+    for (uint32_t q = 0; q < R; ++q)
+        if (gl_off[q + 1] - gl_off[q] > wide_above) { wide.push_back(0); wide.push_back(q); }
+    const uint64_t bound = pgx_record_text_bound(n_records, n_gl);
+    const RTextLayout L(bound, R, n_blocks, 1, wide.size() / 2);
+    // the inputs behind the launch's own arrays
+    const size_t o_calls = L.total, o_gloff = o_calls + align_up((size_t)R * 8 + 8), o_gl = o_gloff + align_up(((size_t)R + 1) * 8 + 8),
+                 o_kc = o_gl + align_up((size_t)n_gl * 4 + 8), o_nc = o_kc + align_up((size_t)R * 2 + 8), total = o_nc + align_up((size_t)R + 8);
+    unsigned char* d = nullptr;
+    if (hipMalloc((void**)&d, total) != hipSuccess) { (void)hipGetLastError(); return PG_ERR_NOMEM; }
+    RTextDesc desc;
+    memset(&desc, 0, sizeof(desc));
+    desc.R = R;
+    desc.calls = d + o_calls; desc.gl = d + o_gl; desc.gl_off = (const uint64_t*)(d + o_gloff); desc.kc = (const uint16_t*)(d + o_kc);
+    desc.no_call = no_call ? d + o_nc : nullptr;
+    bool ok = hipMemcpy(d + L.o_desc, &desc, sizeof(desc), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + o_calls, calls, (size_t)R * 8, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + o_gloff, gl_off, ((size_t)R + 1) * 8, hipMemcpyHostToDevice) == hipSuccess &&
+              (n_gl == 0 || hipMemcpy(d + o_gl, gl, (size_t)n_gl * 4, hipMemcpyHostToDevice) == hipSuccess) &&
+              hipMemcpy(d + o_kc, kc, (size_t)R * 2, hipMemcpyHostToDevice) == hipSuccess &&
+              (!no_call || hipMemcpy(d + o_nc, no_call, R, hipMemcpyHostToDevice) == hipSuccess) &&
+              (wide.empty() || hipMemcpy(d + L.o_wide, wide.data(), wide.size() * 4, hipMemcpyHostToDevice) == hipSuccess);
+    if (ok) {
+        rtext_launch(nullptr, d, L, 1, n_blocks, (uint32_t)(wide.size() / 2), R, bound, nullptr, nullptr, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
+             hipMemcpy(off, d + L.o_off, ((size_t)R + 1) * 8, hipMemcpyDeviceToHost) == hipSuccess && off[R] <= bound &&
+             (off[R] == 0 || hipMemcpy(text, d, off[R], hipMemcpyDeviceToHost) == hipSuccess);
     }
     hipFree(d);
     return ok ? PG_OK : PG_ERR_DEVICE;

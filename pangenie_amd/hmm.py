@@ -442,6 +442,24 @@ class Job:
         from . import calls as _calls
         return _calls.fetch_record_gl_packed(self)
 
+    def record_text(self, contig: Optional[int] = None, ignore_imputed: bool = False):
+        """pg_job_record_text + pg_job_fetch_record_text: the bytes of the GT:GQ:GL:KC column per VCF RECORD formed on the
+        device, under the plans of record_plan().  (off, bytes) of chain `contig` — record r's text is
+        bytes[off[r]:off[r + 1]], empty for a record left to the host — or a list of them, one per chain."""
+        from . import calls as _calls
+        return _calls.job_record_text(self, contig, ignore_imputed)
+
+    def record_text_packed(self, ignore_imputed: bool = False):
+        """pg_job_record_text + pg_job_fetch_record_text_packed: (off [R_total + 1] absolute, all chains' bytes from ONE copy,
+        text_first [n_chains + 1])."""
+        from . import calls as _calls
+        _calls.form_record_text(self, ignore_imputed)
+        return _calls.fetch_record_text_packed(self)
+
+    def record_text_ms(self) -> float:
+        """elapsed ms of the kernels of the last record_text()"""
+        return float(self._lib.pg_job_record_text_ms(self.h))
+
     def combine_plan(self, groups) -> None:
         """pg_job_combine_plan: groups = per group the chains (contig x path subset) that genotype the same index objects, in the
         order they are to be added up; a second plan replaces the first."""

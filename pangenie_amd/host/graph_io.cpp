@@ -461,9 +461,9 @@ static std::string phased_field(const VcfSite& site, const std::vector<unsigned 
     return out.str();
 }
 
-// the sample column `GT:GQ:GL:KC` of record q of bubble i from the device's record fields: genotype_field without a likelihood
-static std::string device_field(const RecordFields& f, size_t q, size_t n_defined, unsigned short coverage, bool no_call) {
-    if (q >= f.calls.size() || q + 1 >= f.gl_off.size() || f.gl_off[q + 1] > f.gl.size() || f.gl_off[q + 1] - f.gl_off[q] != n_defined * (n_defined + 1) / 2)
+// the sample column `GT:GQ:GL:KC` of record q from the device's record fields: genotype_field without a likelihood
+std::string record_field_text(const RecordFields& f, size_t q, unsigned short coverage, bool no_call) {
+    if (q >= f.calls.size() || q + 1 >= f.gl_off.size() || f.gl_off[q + 1] > f.gl.size() || f.gl_off[q + 1] < f.gl_off[q])
         throw std::runtime_error("Graph::write_genotypes_of: the record fields do not fit the graph's records");
     std::ostringstream out;
     const GenotypeCall& c = f.calls[q];
@@ -481,11 +481,30 @@ static std::string device_field(const RecordFields& f, size_t q, size_t n_define
     return out.str();
 }
 
+// ... of record q of a bubble whose records have n_defined defined alleles
+static std::string device_field(const RecordFields& f, size_t q, size_t n_defined, unsigned short coverage, bool no_call) {
+    if (q >= f.calls.size() || q + 1 >= f.gl_off.size() || f.gl_off[q + 1] > f.gl.size() || f.gl_off[q + 1] - f.gl_off[q] != n_defined * (n_defined + 1) / 2)
+        throw std::runtime_error("Graph::write_genotypes_of: the record fields do not fit the graph's records");
+    return record_field_text(f, q, coverage, no_call);
+}
+
+// ... and from the device's bytes
+static std::string text_field(const RecordText& t, size_t q, size_t n_defined) {
+    if (q + 1 >= t.off.size() || t.off[q + 1] < t.off[q] || t.off[q + 1] > t.bytes.size())
+        throw std::runtime_error("Graph::write_genotypes_of: the record text does not fit the graph's records");
+    if (t.off[q + 1] == t.off[q]) {
+        const size_t n = n_defined * (n_defined + 1) / 2;
+        if (n < 3) throw std::runtime_error("Graph::write_genotypes_of: too few likelihoods (" + std::to_string(n) + ") computed");
+        throw std::runtime_error("Graph::write_genotypes_of: a record's text is still left to the host (genotype_cohort_record_text finishes them)");
+    }
+    return t.bytes.substr(t.off[q], t.off[q + 1] - t.off[q]);
+}
+
 std::vector<std::string> Graph::sample_records(const std::vector<GenotypingResult>& genotyping_result, bool ignore_imputed, bool phasing,
                                                const std::vector<SampledPanel>* sampled_paths, const DeviceFields* device) const {
     const char* who = sampled_paths ? "Graph::write_sampled_panel" : phasing ? "Graph::write_phasing_of" : "Graph::write_genotypes_of";
     if (variants_deleted_) throw std::runtime_error(std::string(who) + ": variants have been deleted by delete_variant funtion. Re-build object.");
-    if ((sampled_paths ? sampled_paths->size() : device ? std::min(device->coverage->size(), device->unique_kmers->size()) : genotyping_result.size()) != size())
+    if ((sampled_paths ? sampled_paths->size() : device ? (device->text ? device->unique_kmers->size() : std::min(device->coverage->size(), device->unique_kmers->size())) : genotyping_result.size()) != size())
         throw std::runtime_error(std::string(who) + ": number of variants and number of computed " + (phasing || sampled_paths ? "phasings" : "genotypes") + " differ.");
     std::vector<std::string> lines;
     size_t record_index = 0;   // over single records: the row of variant_ids
@@ -532,6 +551,7 @@ std::vector<std::string> Graph::sample_records(const std::vector<GenotypingResul
                     if (among_defined.at(a) < 0) line << "\t."; else line << '\t' << among_defined[a];
                 }
             }
+            else if (device && device->text) line << "\tGT:GQ:GL:KC\t" << text_field(*device->text, record_index, defined.size());
             else if (device)
                 line << "\tGT:GQ:GL:KC\t"
                      << device_field(*device->fields, record_index, defined.size(), (*device->coverage)[i], ignore_imputed && (*device->unique_kmers)[i] == 0);
@@ -558,6 +578,20 @@ std::vector<std::string> Graph::genotypes_records(const RecordFields& fields, co
                                                   const std::vector<unsigned short>& unique_kmers, bool ignore_imputed) const {
     const DeviceFields device = {&fields, &coverage, &unique_kmers};
     return sample_records({}, ignore_imputed, false, nullptr, &device);
+}
+
+std::vector<std::string> Graph::genotypes_records(const RecordText& text) const {
+    const DeviceFields device = {nullptr, nullptr, &text.unique_kmers, &text};
+    return sample_records({}, false, false, nullptr, &device);
+}
+
+void Graph::write_genotypes(const std::string& filename, const RecordText& text, bool write_header, const std::string& sample) const {
+    const std::vector<std::string> records = genotypes_records(text);   // (throws before the file is touched)
+    std::ofstream out(filename, write_header ? std::ios::out : std::ios::app);
+    if (!out.is_open()) throw std::runtime_error("Graph::write_genotypes_of: genotyping output file cannot be opened. Note that the filename must not contain non-existing directories.");
+    if (write_header)
+        for (const std::string& h : genotypes_header(sample)) out << h << '\n';
+    for (const std::string& l : records) out << l << '\n';
 }
 
 void Graph::write_genotypes(const std::string& filename, const RecordFields& fields, const std::vector<unsigned short>& coverage,

@@ -95,6 +95,20 @@ struct RecordFields {
     std::vector<uint64_t> gl_off;
 };
 
+/** The sample column of a chromosome's VCF lines as BYTES (DESIGN.md 4e-6, C ABI pg_job_record_text): record r's
+ *  `GT:GQ:GL:KC` is bytes[off[r] .. off[r + 1]), records in Graph::genotypes_records order, and `unique_kmers` — one entry per
+ *  bubble — is what the INFO column needs of the sample (UK).  As genotype_cohort_record_text returns it, no record is empty
+ *  except one of fewer than three GL values, which Graph::genotypes_records refuses as it does everywhere. */
+struct RecordText {
+    std::vector<uint64_t> off;
+    std::string bytes;
+    std::vector<unsigned short> unique_kmers;
+};
+
+/** `GT:GQ:GL:KC` of record q from finished record fields: what Graph::genotypes_records(fields, ...) prints of it (the rule
+ *  the device's text follows).  Throws on fewer than three values and on a value that is still deferred. */
+std::string record_field_text(const RecordFields& fields, size_t q, unsigned short coverage, bool no_call);
+
 /** A variant bubble of the graph: one or several VCF records closer than the k-mer size, merged
  *  (reference src/variant.hpp:28-121). */
 class Variant {
@@ -181,6 +195,11 @@ public:
     void write_genotypes(const std::string& filename, const RecordFields& fields, const std::vector<unsigned short>& coverage,
                          const std::vector<unsigned short>& unique_kmers, bool write_header, const std::string& sample, bool ignore_imputed = false) const;
 
+    /** the same lines with the sample column arriving as bytes: the fixed columns as above (UK from text.unique_kmers), the
+     *  column spliced in.  Throws where a record's text is empty: fewer than three likelihoods, or a record nobody finished. */
+    std::vector<std::string> genotypes_records(const RecordText& text) const;
+    void write_genotypes(const std::string& filename, const RecordText& text, bool write_header, const std::string& sample) const;
+
     /** the phasing VCF of a `-p` run (reference Graph::write_phasing, src/graph.cpp:280-412): the same fixed columns, `GT:KC`
      *  with the Viterbi haplotypes `a|b` (HMM with run_phasing; `.` for an allele of undefined sequence) */
     static std::vector<std::string> phasing_header(const std::string& sample, const std::string& date = "");
@@ -199,6 +218,7 @@ private:
         const RecordFields* fields;
         const std::vector<unsigned short>* coverage;
         const std::vector<unsigned short>* unique_kmers;
+        const RecordText* text = nullptr;   // the column as bytes: fields and coverage are not looked at
     };
     std::vector<std::string> sample_records(const std::vector<GenotypingResult>& genotyping_result, bool ignore_imputed, bool phasing,
                                             const std::vector<SampledPanel>* sampled_paths = nullptr, const DeviceFields* device = nullptr) const;
@@ -249,6 +269,23 @@ struct SampledRecordFields {
  *  std::runtime_error on a missing graph, a graph whose bubble count is not the index's, samples that do not fit, and on the C
  *  ABI's errors. */
 std::vector<std::map<std::string, SampledRecordFields>> genotype_cohort_sampled_record_fields(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
+    bool ignore_imputed = false, std::vector<std::map<std::string, SampledPaths>>* sampled = nullptr);
+
+/** genotype_cohort_record_fields with the sample column formed as TEXT on the device: the same job, then
+ *  pg_job_record_text and ONE packed fetch of the bytes and their offsets; neither calls nor GL values come back, except for a
+ *  chain with a record the device left to the host (a deferred call or GL value), whose fields are fetched, finished as
+ *  genotype_cohort_record_fields finishes them and printed by record_field_text.  Graph::genotypes_records(text) gives the
+ *  lines of Graph::genotypes_records(fields, coverage, unique_kmers, ignore_imputed) on the sibling's output. */
+std::vector<std::map<std::string, RecordText>> genotype_cohort_record_text(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false,
+    long double effective_N = 25000.0L, int device = 0, bool ignore_imputed = false);
+
+/** genotype_cohort_sampled_record_fields with the sample column formed as text on the device, as genotype_cohort_record_text. */
+std::vector<std::map<std::string, RecordText>> genotype_cohort_sampled_record_text(
     std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
     const std::vector<SampleCounts>& samples, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
     ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,

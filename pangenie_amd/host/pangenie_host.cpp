@@ -1088,13 +1088,73 @@ static int chain_record_fields(const Graph& graph, const RecordPlan& plan, const
     return PG_OK;
 }
 
-// genotype_cohort_record_calls and, `with_gl`, genotype_cohort_record_fields: one job, the calls and the GL values per record
+// The text of a job's sample columns to the host: pg_job_record_text, then ONE copy of the packed bytes and
+// their offsets.  calls_first[n_chains + 1] = every chain's first record, off = every record's first byte in `packed`.
+static int job_record_text(pg_job* job, size_t n_chains, bool ignore_imputed, std::vector<uint64_t>* calls_first, std::vector<uint64_t>* off,
+                           std::string* packed, char* err, size_t errlen) {
+    int rc = pg_job_record_text(job, ignore_imputed ? 1 : 0, err, errlen);
+    std::vector<uint64_t> text_first(n_chains + 1, 0);
+    calls_first->assign(n_chains + 1, 0);
+    if (rc == PG_OK) rc = pg_job_record_text_first(job, text_first.data(), err, errlen);
+    if (rc == PG_OK) rc = pg_job_record_first(job, calls_first->data(), nullptr, err, errlen);
+    if (rc != PG_OK) return rc;
+    off->assign(calls_first->back() + 1, 0);
+    packed->assign(text_first.back(), '\0');
+    return pg_job_fetch_record_text_packed(job, off->data(), packed->empty() ? nullptr : &(*packed)[0], packed->size(), err, errlen);
+}
+
+// One chain's RecordText from the packed text (`off`: the chain's R + 1 absolute offsets).  A record the device left to the host
+// — empty although it has three values or more: a deferred call or GL value — is finished as chain_record_fields finishes it,
+// from this chain's fetched calls and GL values and, through `results`, its bins, and printed by record_field_text;
+// `coverage(v)`: KC of bubble v.  No other chain's fields leave the device.
+template <class NoKmers, class Coverage, class Results>
+static int chain_record_text(pg_job* job, uint32_t chain, const Graph& graph, const RecordPlan& plan, const std::vector<uint64_t>& gl_off, bool ignore_imputed,
+                             const uint64_t* off, const std::string& packed, NoKmers no_kmers, Coverage coverage, Results results, RecordText& out, char* err,
+                             size_t errlen) {
+    const size_t R = plan.nr_of_records();
+    out.off.assign(R + 1, 0);
+    for (size_t q = 0; q <= R; ++q) out.off[q] = off[q] - off[0];
+    out.bytes.assign(packed, off[0], off[R] - off[0]);
+    std::vector<size_t> pending;
+    for (size_t q = 0; q < R; ++q)
+        if (out.off[q + 1] == out.off[q] && gl_off[q + 1] - gl_off[q] >= 3) pending.push_back(q);
+    if (pending.empty()) return PG_OK;
+    RecordFields fields;
+    fields.gl_off = gl_off;
+    fields.gl.resize(gl_off.back());
+    std::vector<pg_call> r(R);
+    int rc = pg_job_fetch_record_calls(job, chain, r.data(), err, errlen);
+    if (rc == PG_OK) rc = pg_job_fetch_record_gl(job, chain, fields.gl.data(), err, errlen);
+    if (rc == PG_OK) rc = chain_record_fields(graph, plan, r.data(), ignore_imputed, true, no_kmers, results, fields);
+    if (rc != PG_OK) return rc;
+    std::vector<size_t> bubble(R, 0);
+    for (size_t v = 0; v + 1 < plan.rec_off.size(); ++v)
+        for (size_t q = plan.rec_off[v]; q < plan.rec_off[v + 1]; ++q) bubble[q] = v;
+    std::string bytes;
+    std::vector<uint64_t> spliced(R + 1, 0);
+    size_t p = 0;
+    for (size_t q = 0; q < R; ++q) {
+        spliced[q] = bytes.size();
+        if (p < pending.size() && pending[p] == q) {
+            bytes += record_field_text(fields, q, coverage(bubble[q]), ignore_imputed && no_kmers(bubble[q]));
+            ++p;
+        } else bytes.append(out.bytes, out.off[q], out.off[q + 1] - out.off[q]);
+    }
+    spliced[R] = bytes.size();
+    out.off.swap(spliced);
+    out.bytes.swap(bytes);
+    return PG_OK;
+}
+
+// genotype_cohort_record_calls and, `with_gl`, genotype_cohort_record_fields: one job, the calls and the GL values per record;
+// with `text` (genotype_cohort_record_text) the column's bytes instead: neither calls nor values are fetched then
 static std::vector<std::map<std::string, RecordFields>> cohort_record_fields(
     std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
     const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device,
-    bool ignore_imputed, bool with_gl) {
+    bool ignore_imputed, bool with_gl, std::vector<std::map<std::string, RecordText>>* text = nullptr) {
     const size_t C = chromosomes.size(), S = samples.size();
     std::vector<std::map<std::string, RecordFields>> out(S);
+    if (text) text->assign(S, {});
     if (C == 0 || S == 0) return out;
     // (the job is made exactly as genotype_cohort makes it)
     std::vector<std::string> names;
@@ -1150,16 +1210,58 @@ static std::vector<std::map<std::string, RecordFields>> cohort_record_fields(
         rc = pg_job_record_plan(job, (uint32_t)c, &view, err, sizeof(err));
     }
     if (rc == PG_OK) rc = pg_job_run(job, nullptr, err, sizeof(err));
-    if (rc == PG_OK) rc = pg_job_record_calls(job, err, sizeof(err));
-    if (rc == PG_OK && with_gl) rc = pg_job_record_gl(job, err, sizeof(err));
+    if (rc == PG_OK && !text) rc = pg_job_record_calls(job, err, sizeof(err));
+    if (rc == PG_OK && with_gl && !text) rc = pg_job_record_gl(job, err, sizeof(err));
     if (rc != PG_OK) { if (job) pg_job_destroy(job); check_rc(rc, err); }
     // the offsets of the GL values hang on the plan alone
     std::vector<std::vector<uint64_t>> gl_off(C);
-    for (c = 0; c < C && with_gl; ++c) {
+    for (c = 0; c < C && (with_gl || text); ++c) {
         gl_off[c].assign(plans[c].nr_of_records() + 1, 0);
         const pg_record_plan view = plans[c].view();
         rc = pg_record_gl_offsets(&view, gl_off[c].data());
         if (rc != PG_OK) { pg_job_destroy(job); check_rc(rc, "pg_record_gl_offsets refused the record plan"); }
+    }
+    // the fetch of a chain's bins, for what the device deferred
+    const auto results_of = [&](size_t s, size_t cc, std::vector<GenotypingResult>* full) {
+        const uint64_t n = goff[cc].back();
+        std::vector<double> lik(n ? n : 1);
+        std::vector<int32_t> lexp(n ? n : 1);
+        pg_contig_result res{};
+        res.lik = lik.data(); res.lik_exp = lexp.data();
+        const int code = pg_job_fetch(job, (uint32_t)(s * C + cc), &res, err, sizeof(err));
+        if (code == PG_OK) *full = results_of_chain(flat[cc], cov_rows[s][cc], goff[cc], lik.data(), lexp.data());
+        return code;
+    };
+    if (text) {   // the column as bytes: one packed copy, then chain by chain
+        std::vector<uint64_t> calls_first, off;
+        std::string packed;
+        try {
+            rc = job_record_text(job, S * C, ignore_imputed, &calls_first, &off, &packed, err, sizeof(err));
+            for (size_t s = 0; s < S && rc == PG_OK; ++s)
+                for (c = 0; c < C && rc == PG_OK; ++c) {
+                    const FlatContig& f = flat[c];
+                    const size_t chain = s * C + c;
+                    if (calls_first[chain + 1] - calls_first[chain] != plans[c].nr_of_records()) {
+                        std::snprintf(err, sizeof(err), "genotype_cohort_record_text: chain %zu holds other records than its plan's", chain);
+                        rc = PG_ERR_INVALID;
+                        break;
+                    }
+                    RecordText& t = (*text)[s][names[c]];
+                    t.unique_kmers.resize(f.variant_pos.size());
+                    for (size_t v = 0; v < t.unique_kmers.size(); ++v) t.unique_kmers[v] = any_column[c] ? (unsigned short)(f.kmer_off[v + 1] - f.kmer_off[v]) : 0;
+                    rc = chain_record_text(
+                        job, (uint32_t)chain, *graph_of[c], plans[c], gl_off[c], ignore_imputed, off.data() + calls_first[chain], packed,
+                        [&](size_t v) { return !any_column[c] || f.kmer_off[v + 1] == f.kmer_off[v]; },
+                        [&](size_t v) { return any_column[c] ? cov_rows[s][c][v] : (uint16_t)0; },
+                        [&](std::vector<GenotypingResult>* full) { return results_of(s, c, full); }, t, err, sizeof(err));
+                }
+        } catch (...) {
+            pg_job_destroy(job);
+            throw;
+        }
+        pg_job_destroy(job);
+        check_rc(rc, err);
+        return out;
     }
     // all records with one synchronisation
     std::vector<std::vector<pg_call>> recs(S * C);
@@ -1188,17 +1290,7 @@ static std::vector<std::map<std::string, RecordFields>> cohort_record_fields(
             rc = chain_record_fields(
                 *graph_of[c], plan, r.data(), ignore_imputed, with_gl,
                 [&](size_t v) { return !any_column[c] || f.kmer_off[v + 1] == f.kmer_off[v]; },
-                [&](std::vector<GenotypingResult>* full) {
-                    const uint64_t n = goff[c].back();
-                    std::vector<double> lik(n ? n : 1);
-                    std::vector<int32_t> lexp(n ? n : 1);
-                    pg_contig_result res{};
-                    res.lik = lik.data(); res.lik_exp = lexp.data();
-                    const int code = pg_job_fetch(job, (uint32_t)(s * C + c), &res, err, sizeof(err));
-                    if (code == PG_OK) *full = results_of_chain(f, cov_rows[s][c], goff[c], lik.data(), lexp.data());
-                    return code;
-                },
-                fields);
+                [&](std::vector<GenotypingResult>* full) { return results_of(s, c, full); }, fields);
         }
     pg_job_destroy(job);
     check_rc(rc, err);
@@ -1223,6 +1315,15 @@ std::vector<std::map<std::string, RecordFields>> genotype_cohort_record_fields(
     const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device,
     bool ignore_imputed) {
     return cohort_record_fields(chromosomes, graphs, samples, probabilities, recombrate, uniform, effective_N, device, ignore_imputed, true);
+}
+
+std::vector<std::map<std::string, RecordText>> genotype_cohort_record_text(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device,
+    bool ignore_imputed) {
+    std::vector<std::map<std::string, RecordText>> text;
+    cohort_record_fields(chromosomes, graphs, samples, probabilities, recombrate, uniform, effective_N, device, ignore_imputed, true, &text);
+    return text;
 }
 
 // ------------------------------------------------------------------ path subsets, the sample column per VCF record
@@ -1594,7 +1695,7 @@ std::vector<RecordChromosome> record_chromosomes(const std::map<std::string, std
 int sampled_job_record_fields(pg_job* job, size_t n, const std::vector<RecordChromosome>& chroms, const std::vector<FlatContig>& flat,
                               const std::vector<std::vector<const uint16_t*>>* cov_rows, uint32_t size, bool add_reference, bool ignore_imputed,
                               const std::vector<std::vector<uint32_t>>& picks, std::map<std::string, SampledRecordFields>* out,
-                              std::map<std::string, SampledPaths>* sampled, char* err, size_t errlen) {
+                              std::map<std::string, SampledPaths>* sampled, char* err, size_t errlen, std::map<std::string, RecordText>* text = nullptr) {
     const size_t C = chroms.size();
     int rc = PG_OK;
     for (size_t c = 0; c < C && rc == PG_OK; ++c) {   // one plan per chromosome, checked and uploaded once for all samples
@@ -1602,6 +1703,38 @@ int sampled_job_record_fields(pg_job* job, size_t n, const std::vector<RecordChr
         rc = pg_job_record_plan_strided(job, (uint32_t)c, (uint32_t)C, &view, err, errlen);
     }
     if (rc == PG_OK) rc = pg_job_run(job, nullptr, err, errlen);
+    if (rc == PG_OK && text) {   // the column as bytes (genotype_cohort_sampled_record_text): one packed copy, then chain by chain
+        std::vector<uint64_t> first, off;
+        std::string packed;
+        rc = job_record_text(job, n * C, ignore_imputed, &first, &off, &packed, err, errlen);
+        for (size_t s = 0; s < n && rc == PG_OK; ++s)
+            for (size_t c = 0; c < C && rc == PG_OK; ++c) {
+                const uint32_t chain = (uint32_t)(s * C + c);
+                const RecordChromosome& x = chroms[c];
+                const size_t V = flat[c].variant_pos.size();
+                if (first[chain + 1] - first[chain] != x.plan.nr_of_records()) {
+                    std::snprintf(err, errlen, "genotype_cohort_sampled_record_text: chain %u holds other records than its plan's", chain);
+                    return PG_ERR_INVALID;
+                }
+                std::vector<uint16_t> nk(V ? V : 1, 0), cov(V ? V : 1, 0);   // (by pg_job_fetch's rule; host memory of the job)
+                pg_contig_result meta{};
+                meta.n_kmers = nk.data(); meta.coverage = cov.data();
+                rc = pg_job_fetch(job, chain, &meta, err, errlen);
+                if (rc != PG_OK) break;
+                const uint16_t* own = cov_rows ? (*cov_rows)[s][c] : nullptr;
+                RecordText& t = text[s][x.name];
+                t.unique_kmers.assign(nk.begin(), nk.begin() + V);
+                if (sampled) sampled_paths_of(picks[chain].data(), size, V, add_reference, &sampled[s][x.name]);
+                rc = chain_record_text(
+                    job, chain, *x.graph, x.plan, x.gl_off, ignore_imputed, off.data() + first[chain], packed, [&](size_t v) { return t.unique_kmers[v] == 0; },
+                    [&](size_t v) { return (uint16_t)(own && meta.n_columns > 0 ? own[v] : own ? 0 : cov[v]); },
+                    [&](std::vector<GenotypingResult>* full) {
+                        return fetch_sampled_chain(job, chain, flat[c], own, size, add_reference, nullptr, full, nullptr, err, errlen);
+                    },
+                    t, err, errlen);
+            }
+        return rc;
+    }
     if (rc == PG_OK) rc = pg_job_record_calls(job, err, errlen);
     if (rc == PG_OK) rc = pg_job_record_gl(job, err, errlen);
     if (rc != PG_OK) return rc;
@@ -1649,14 +1782,16 @@ int sampled_job_record_fields(pg_job* job, size_t n, const std::vector<RecordChr
 
 }  // namespace
 
-std::vector<std::map<std::string, SampledRecordFields>> genotype_cohort_sampled_record_fields(
+// genotype_cohort_sampled_record_fields and, with `text`, genotype_cohort_sampled_record_text: one sampled cohort job
+static std::vector<std::map<std::string, SampledRecordFields>> sampled_cohort_record_fields(
     std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
     const std::vector<SampleCounts>& samples, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
     ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device, bool ignore_imputed,
-    std::vector<std::map<std::string, SampledPaths>>* sampled) {
+    std::vector<std::map<std::string, SampledPaths>>* sampled, std::vector<std::map<std::string, RecordText>>* text) {
     const size_t C = chromosomes.size(), S = samples.size();
     std::vector<std::map<std::string, SampledRecordFields>> out(S);
     if (sampled) sampled->assign(S, {});
+    if (text) text->assign(S, {});
     if (C == 0 || S == 0) return out;
     const std::vector<RecordChromosome> chroms = record_chromosomes(chromosomes, graphs, "genotype_cohort_sampled_record_fields");
     // (the job is made exactly as genotype_cohort_sampled makes it)
@@ -1700,7 +1835,7 @@ std::vector<std::map<std::string, SampledRecordFields>> genotype_cohort_sampled_
     try {
         if (rc == PG_OK)
             rc = sampled_job_record_fields(job, S, chroms, flat, &cov_rows, size, add_reference, ignore_imputed, picks, out.data(),
-                                           sampled ? sampled->data() : nullptr, err, sizeof(err));
+                                           sampled ? sampled->data() : nullptr, err, sizeof(err), text ? text->data() : nullptr);
     } catch (...) {
         if (job) pg_job_destroy(job);
         throw;
@@ -1710,16 +1845,38 @@ std::vector<std::map<std::string, SampledRecordFields>> genotype_cohort_sampled_
     return out;
 }
 
-std::vector<std::map<std::string, SampledRecordFields>> genotype_cohort_sampled_reads_record_fields(
+std::vector<std::map<std::string, SampledRecordFields>> genotype_cohort_sampled_record_fields(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device, bool ignore_imputed,
+    std::vector<std::map<std::string, SampledPaths>>* sampled) {
+    return sampled_cohort_record_fields(chromosomes, graphs, samples, panel_size, add_reference, allele_penalty, sampling_effective_N, probabilities, recombrate,
+                                        uniform, effective_N, device, ignore_imputed, sampled, nullptr);
+}
+
+std::vector<std::map<std::string, RecordText>> genotype_cohort_sampled_record_text(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device, bool ignore_imputed,
+    std::vector<std::map<std::string, SampledPaths>>* sampled) {
+    std::vector<std::map<std::string, RecordText>> text;
+    sampled_cohort_record_fields(chromosomes, graphs, samples, panel_size, add_reference, allele_penalty, sampling_effective_N, probabilities, recombrate,
+                                 uniform, effective_N, device, ignore_imputed, sampled, &text);
+    return text;
+}
+
+// genotype_cohort_sampled_reads_record_fields and, with `text`, genotype_cohort_sampled_reads_record_text: the same batches
+static std::vector<std::map<std::string, SampledRecordFields>> sampled_reads_record_fields(
     UniqueKmersMap& index, const std::map<std::string, Graph>& graphs, const std::string& prefix, const std::vector<std::string>& readfiles,
     const std::vector<size_t>& kmer_coverages, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
     ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device, size_t batch, bool ignore_imputed,
-    std::vector<std::map<std::string, SampledPaths>>* sampled) {
+    std::vector<std::map<std::string, SampledPaths>>* sampled, std::vector<std::map<std::string, RecordText>>* text) {
     auto& chromosomes = index.unique_kmers;
     const size_t C = chromosomes.size(), S = readfiles.size();
     if (kmer_coverages.size() != S) fail("genotype_cohort_sampled_reads_record_fields: one k-mer coverage per read file");
     std::vector<std::map<std::string, SampledRecordFields>> out(S);
     if (sampled) sampled->assign(S, {});
+    if (text) text->assign(S, {});
     if (C == 0 || S == 0) return out;
     const std::vector<RecordChromosome> chroms = record_chromosomes(chromosomes, graphs, "genotype_cohort_sampled_reads_record_fields");
     // (counter, count plan and batches exactly as genotype_cohort_sampled_reads makes them)
@@ -1777,7 +1934,7 @@ std::vector<std::map<std::string, SampledRecordFields>> genotype_cohort_sampled_
             counts = nullptr;
             if (rc == PG_OK)
                 rc = sampled_job_record_fields(job, n, chroms, flat, nullptr, size, add_reference, ignore_imputed, picks, out.data() + s0,
-                                               sampled ? sampled->data() + s0 : nullptr, err, sizeof(err));
+                                               sampled ? sampled->data() + s0 : nullptr, err, sizeof(err), text ? text->data() + s0 : nullptr);
         } catch (...) {
             if (counts) pg_sampler_counts_destroy(counts);
             if (job) pg_job_destroy(job);
@@ -1787,6 +1944,26 @@ std::vector<std::map<std::string, SampledRecordFields>> genotype_cohort_sampled_
         check_batch(rc);
     }
     return out;
+}
+
+std::vector<std::map<std::string, SampledRecordFields>> genotype_cohort_sampled_reads_record_fields(
+    UniqueKmersMap& index, const std::map<std::string, Graph>& graphs, const std::string& prefix, const std::vector<std::string>& readfiles,
+    const std::vector<size_t>& kmer_coverages, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device, size_t batch, bool ignore_imputed,
+    std::vector<std::map<std::string, SampledPaths>>* sampled) {
+    return sampled_reads_record_fields(index, graphs, prefix, readfiles, kmer_coverages, panel_size, add_reference, allele_penalty, sampling_effective_N,
+                                       probabilities, recombrate, uniform, effective_N, device, batch, ignore_imputed, sampled, nullptr);
+}
+
+std::vector<std::map<std::string, RecordText>> genotype_cohort_sampled_reads_record_text(
+    UniqueKmersMap& index, const std::map<std::string, Graph>& graphs, const std::string& prefix, const std::vector<std::string>& readfiles,
+    const std::vector<size_t>& kmer_coverages, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device, size_t batch, bool ignore_imputed,
+    std::vector<std::map<std::string, SampledPaths>>* sampled) {
+    std::vector<std::map<std::string, RecordText>> text;
+    sampled_reads_record_fields(index, graphs, prefix, readfiles, kmer_coverages, panel_size, add_reference, allele_penalty, sampling_effective_N, probabilities,
+                                recombrate, uniform, effective_N, device, batch, ignore_imputed, sampled, &text);
+    return text;
 }
 
 void HMM::combine_likelihoods(HMM& other) {
