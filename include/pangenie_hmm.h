@@ -545,6 +545,7 @@ int  pg_gl_text(pg_gl value, char* buf, size_t len);
  *  A record is left to the HOST — length 0, no bytes — if its call is PG_CALL_DEFERRED, if one of its values is
  *  PG_GL_DEFERRED (or one pg_gl_text refuses), or if it has fewer than 3 values.  The text of all records is packed:
  *  chain after chain, record after record, no gaps.  Not covered: the records of combined groups, the phasing column.
+ *  The splice itself — whole lines, every sample's column behind the fixed ones — is the next section's (4e-7).
  * ------------------------------------------------------------------ */
 /* 19 n_records + 11 n_gl_total: bytes that always suffice (255/255:10000: is 14, a value at most 10, a comma between
  * values, :65535 is 6).  Host only. */
@@ -580,6 +581,52 @@ double pg_job_record_text_emit_ms(const pg_job* job);
  * counts on them).  Then PG_ERR_DEVICE without a device: no host fallback. */
 int  pg_record_text_from_fields(int device, uint64_t n_records, const pg_call* calls, const uint64_t* gl_off, const pg_gl* gl,
                                 const uint16_t* kc, const uint8_t* no_call, uint64_t* off, char* text, uint64_t cap);
+
+/* ------------------------------------------------------------------ *
+ *  Record LINES: whole VCF lines of a cohort joined on the device.  The MEMBERS of index contig k are
+ *  the chains over k in ascending chain id (pg_cohort_new: samples 0 .. S-1; a job whose chains have index contigs of
+ *  their own: that one chain).  With a record plan of R records and a PREFIX — R byte strings, packed, prefix_off[R + 1],
+ *  the caller's: CHROM .. FORMAT without a trailing tab — the line of record r is
+ *      prefix[r]  ('\t' text_s[r]) for every member s in order  '\n'
+ *  with text_s[r] the bytes pg_job_record_text formed.  A line is the HOST's — length 0, nothing written — if any
+ *  member's text of the record has length 0.  Lines are packed: record after record, index contig after index contig,
+ *  no gaps.  Prefix and texts are opaque bytes of any length, 0 included.  Limits: the lines of 256 consecutive records
+ *  stay below 4 GiB.  Not covered: the combined (-a) record families, the phasing column.
+ * ------------------------------------------------------------------ */
+/* prefix_bytes + text_bytes + n_records (n_members + 1): reached exactly when no line is the host's.  Host only. */
+uint64_t pg_record_lines_bound(uint64_t n_records, uint64_t n_members, uint64_t prefix_bytes, uint64_t text_bytes);
+/* Uploads the prefix of one index contig: off[R + 1] with R the records of its plan, bytes[off[R]]; a second call
+ * replaces it, a new record plan or a new index for that contig drops it.  PG_ERR_INVALID: a null job or null arrays
+ * (bytes may be NULL only if off[R] == 0), index_contig out of range, no record plan on it, off[0] != 0 or off shrinks. */
+int  pg_job_line_prefix(pg_job* job, uint32_t index_contig, const uint64_t* off, const char* bytes, char* err, size_t errlen);
+/* Forms the lines of every index contig that has a plan, a prefix and at least one member (the others are left out: no
+ * error), on the job's stream; blocking.  PG_ERR_INVALID unless pg_job_record_text has been called for this run and
+ * these plans: it does not form the text itself (ignore_imputed is the text's argument).  The buffer — the exact bound,
+ * and 8 bytes a line and the scan's words — lies outside the arena, is made by the first call and freed by
+ * pg_job_destroy; PG_ERR_NOMEM if it does not fit.  The lines are stale exactly when the text they were joined from is
+ * stale or formed again, or a prefix changed: the fetches then answer PG_ERR_INVALID. */
+int  pg_job_record_lines(pg_job* job, char* err, size_t errlen);
+/* *n_index_contigs (or NULL) = the job's index contigs; line_first / byte_first (each [n_index_contigs + 1], or NULL):
+ * every index contig's first line / first byte in the packed lines.  With both arrays NULL only the number is reported
+ * (for any job); otherwise the lines must be formed and current. */
+int  pg_job_record_lines_first(pg_job* job, uint64_t* n_index_contigs, uint64_t* line_first, uint64_t* byte_first, char* err, size_t errlen);
+/* One index contig's bytes, text[n_bytes] with n_bytes = byte_first[k + 1] - byte_first[k] (PG_ERR_INVALID otherwise),
+ * and, unless NULL, off[R + 1] relative to the contig's first byte. */
+int  pg_job_fetch_record_lines(pg_job* job, uint32_t index_contig, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen);
+/* All index contigs: text[n_bytes], n_bytes = byte_first[n_index_contigs], ONE copy; off[n_lines + 1] (or NULL) absolute. */
+int  pg_job_fetch_record_lines_packed(pg_job* job, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen);
+/* Device-resident lines of one index contig: *d_text = its first byte, *d_off = uint64 [n_lines + 1] offsets ABSOLUTE
+ * in the packed lines. */
+int  pg_job_device_record_lines(pg_job* job, uint32_t index_contig, void** d_off, void** d_text, uint64_t* n_lines, uint64_t* n_bytes);
+/* Elapsed milliseconds of the kernels of the LAST pg_job_record_lines (lengths, scan, join). */
+double pg_job_record_lines_ms(const pg_job* job);
+/* Unit entry point: the lines of n_records records of n_members members from host arrays, through the same kernels:
+ * member s's record r = text[s][off[s][r] .. off[s][r + 1]); out_off[R + 1] and out[cap] come back.  PG_ERR_INVALID,
+ * before any device is asked for: null arrays, an offset array that does not start at 0 or shrinks, n_members == 0,
+ * cap below the bound, n_records >= 2^31.  n_records == 0: PG_OK with out_off[0] = 0.  Otherwise PG_ERR_DEVICE without
+ * a device: no host fallback. */
+int  pg_record_lines_from_text(int device, uint64_t n_records, uint64_t n_members, const uint64_t* const* off, const char* const* text,
+                               const uint64_t* prefix_off, const char* prefix, uint64_t* out_off, char* out, uint64_t cap);
 
 /* ------------------------------------------------------------------ *
  *  Path subsets: the chains of one contig over different path selections combined on the device, and the calls

@@ -316,6 +316,25 @@ def _bind_hip(lib):
         getattr(lib, name).restype = C.c_double
     lib.pg_record_text_from_fields.argtypes = [C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     lib.pg_record_text_from_fields.restype = C.c_int
+    # whole VCF lines of a cohort
+    lib.pg_record_lines_bound.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
+    lib.pg_record_lines_bound.restype = C.c_uint64
+    lib.pg_job_line_prefix.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_line_prefix.restype = C.c_int
+    lib.pg_job_record_lines.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_record_lines.restype = C.c_int
+    lib.pg_job_record_lines_first.argtypes = [C.c_void_p, u64p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_record_lines_first.restype = C.c_int
+    lib.pg_job_fetch_record_lines.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+    lib.pg_job_fetch_record_lines.restype = C.c_int
+    lib.pg_job_fetch_record_lines_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+    lib.pg_job_fetch_record_lines_packed.restype = C.c_int
+    lib.pg_job_device_record_lines.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), u64p, u64p]
+    lib.pg_job_device_record_lines.restype = C.c_int
+    lib.pg_job_record_lines_ms.argtypes = [C.c_void_p]
+    lib.pg_job_record_lines_ms.restype = C.c_double
+    lib.pg_record_lines_from_text.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    lib.pg_record_lines_from_text.restype = C.c_int
     # path subsets combined on the device (pangenie_amd/calls.py); bins are read as numpy arrays of COMBINED_DTYPE
     lib.pg_job_combine_plan.argtypes = [C.c_void_p, C.c_uint32, u32p, u32p, C.c_char_p, C.c_size_t]
     lib.pg_job_combine_plan.restype = C.c_int
@@ -392,6 +411,8 @@ HIP_ABI_SYMBOLS = [
     "pg_record_calls_from_combined", "pg_record_gl_from_combined",
     "pg_record_text_bound", "pg_job_record_text", "pg_job_record_text_first", "pg_job_fetch_record_text", "pg_job_fetch_record_text_packed",
     "pg_job_device_record_text", "pg_job_record_text_ms", "pg_job_record_text_emit_ms", "pg_record_text_from_fields",
+    "pg_record_lines_bound", "pg_job_line_prefix", "pg_job_record_lines", "pg_job_record_lines_first", "pg_job_fetch_record_lines",
+    "pg_job_fetch_record_lines_packed", "pg_job_device_record_lines", "pg_job_record_lines_ms", "pg_record_lines_from_text",
 ]
 
 

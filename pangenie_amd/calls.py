@@ -463,6 +463,110 @@ def record_text_from_fields(calls, gl_off, gl, kc, no_call=None, device: int = 0
 
 
 # ---------------------------------------------------------------------------------------------------------------
+#  Whole VCF lines of a cohort (pg_job_line_prefix, pg_job_record_lines, pg_record_lines_from_text)
+# ---------------------------------------------------------------------------------------------------------------
+def record_lines_bound(n_records: int, n_members: int, prefix_bytes: int, text_bytes: int) -> int:
+    """pg_record_lines_bound: prefix_bytes + text_bytes + n_records (n_members + 1), reached when no line is the host's."""
+    return int(_lib.load_hip().pg_record_lines_bound(int(n_records), int(n_members), int(prefix_bytes), int(text_bytes)))
+
+
+def _as_bytes(data) -> np.ndarray:
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        return np.frombuffer(bytes(data), np.uint8)
+    return np.ascontiguousarray(data, np.uint8)
+
+
+def job_line_prefix(job, contig: int, off, data) -> None:
+    """pg_job_line_prefix: the fixed columns of index contig `contig`, record r's = data[off[r]:off[r + 1]]."""
+    oo, bb = np.ascontiguousarray(off, np.uint64), _as_bytes(data)
+    plans = getattr(job, "_record_plans", {})
+    if contig in plans and len(oo) != plans[contig].n_records + 1:   # (the C ABI reads R + 1 offsets: it cannot see a wrong R)
+        raise ValueError("line_prefix: %d offsets for a plan of %d records" % (len(oo), plans[contig].n_records))
+    if len(oo) and int(oo[-1]) > len(bb):
+        raise ValueError("line_prefix: the offsets end behind the bytes")
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_line_prefix(job.h, contig, oo.ctypes.data if len(oo) else None, bb.ctypes.data if len(bb) else None, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+
+
+def form_record_lines(job) -> None:
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_record_lines(job.h, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+
+
+def record_lines_first(job):
+    """pg_job_record_lines_first: (line_first, byte_first), each [n_index_contigs + 1]."""
+    n = C.c_uint64(0)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_record_lines_first(job.h, C.byref(n), None, None, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    lf, bf = np.zeros(n.value + 1, np.uint64), np.zeros(n.value + 1, np.uint64)
+    rc = job._lib.pg_job_record_lines_first(job.h, C.byref(n), lf.ctypes.data, bf.ctypes.data, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return lf, bf
+
+
+def fetch_record_lines(job, contig: int):
+    """pg_job_fetch_record_lines: (off [R + 1], bytes) of index contig `contig`; line r is bytes[off[r]:off[r + 1]]."""
+    lf, bf = record_lines_first(job)
+    n = int(bf[contig + 1] - bf[contig])
+    off = np.zeros(int(lf[contig + 1] - lf[contig]) + 1, np.uint64)
+    text = np.zeros(max(n, 1), np.uint8)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_record_lines(job.h, contig, off.ctypes.data, text.ctypes.data, n, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return off, text[:n].tobytes()
+
+
+def fetch_record_lines_packed(job):
+    """pg_job_fetch_record_lines_packed: (off [n_lines + 1] absolute, bytes, line_first, byte_first) from ONE copy."""
+    lf, bf = record_lines_first(job)
+    n = int(bf[-1])
+    off = np.zeros(int(lf[-1]) + 1, np.uint64)
+    text = np.zeros(max(n, 1), np.uint8)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_record_lines_packed(job.h, off.ctypes.data, text.ctypes.data, n, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return off, text[:n].tobytes(), lf, bf
+
+
+def job_record_lines(job, contig: Optional[int] = None):
+    """Job.record_lines(): forms the lines from the record text as it is; (off, bytes) of index contig `contig`, or of all."""
+    form_record_lines(job)
+    if contig is not None:
+        return fetch_record_lines(job, contig)
+    return [fetch_record_lines(job, k) for k in range(len(record_lines_first(job)[0]) - 1)]
+
+
+def record_lines_from_text(texts, prefix, device: int = 0):
+    """pg_record_lines_from_text: (off [R + 1], bytes) — the lines of R records joined through the job's kernels.  texts = per
+    member (off [R + 1], bytes), prefix = (off [R + 1], bytes): any bytes.  A line of length 0 is the host's."""
+    lib = _lib.load_hip()
+    po, pb = np.ascontiguousarray(prefix[0], np.uint64), _as_bytes(prefix[1])
+    R, S = len(po) - 1, len(texts)
+    offs = [np.ascontiguousarray(t[0], np.uint64) for t in texts]
+    data = [_as_bytes(t[1]) for t in texts]
+    if R < 0 or any(len(o) != R + 1 for o in offs) or any(int(o[-1]) > len(b) for o, b in zip(offs + [po], data + [pb])):
+        raise ValueError("record_lines_from_text: array lengths do not match")
+    cap = record_lines_bound(R, S, int(po[-1]), sum(int(o[-1]) for o in offs))
+    op = (C.c_void_p * max(S, 1))(*[o.ctypes.data for o in offs])
+    tp = (C.c_void_p * max(S, 1))(*[b.ctypes.data if len(b) else None for b in data])
+    off = np.zeros(R + 1, np.uint64)
+    out = np.zeros(max(cap, 1), np.uint8)
+    rc = lib.pg_record_lines_from_text(device, R, S, op, tp, po.ctypes.data, pb.ctypes.data if len(pb) else None, off.ctypes.data, out.ctypes.data, cap)
+    if rc:
+        raise _error(rc, None)
+    return off, out[:int(off[-1])].tobytes()
+
+
+# ---------------------------------------------------------------------------------------------------------------
 #  Path subsets combined on the device (pg_job_combine_plan, pg_job_combine, pg_job_combined_calls, pg_combine_bins,
 #  pg_calls_from_combined; DESIGN.md 4e-4)
 # ---------------------------------------------------------------------------------------------------------------

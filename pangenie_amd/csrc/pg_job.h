@@ -1,5 +1,5 @@
 // pg_job.h — what the host units of the C-ABI shim share (pg_shim.cpp: jobs, their build and uploads; pg_shim_run.cpp: the
-// run schedule, pg_job_run; pg_shim_calls.cpp: the output columns formed from a job's finished bins; pg_shim_combine.cpp: path subsets combined): the error helpers, the
+// run schedule, pg_job_run; pg_shim_calls.cpp: the output columns formed from a job's finished bins; pg_shim_lines.cpp: whole VCF lines joined from the record text; pg_shim_combine.cpp: path subsets combined): the error helpers, the
 // host's picture of a job's index contigs, chains and record plans, struct pg_job itself, and the few helpers upload and run
 // both need.  Private: nothing here is exported.
 #pragma once
@@ -187,12 +187,40 @@ struct RecordTextFamily : OutputFamily {
     std::vector<RTextDesc> desc;              // host copy (chains with records)
     size_t o_off = 0, o_loc = 0, o_wlen = 0, o_bsum = 0, o_bbase = 0;
     uint64_t n_records = 0, cap = 0;
+    uint64_t serial = 0;                      // counts the finished formings: the record lines remember which text they joined
     hipEvent_t ev_emit[2];
     bool events = false;
     double emit_ms = 0.0;
     void release() {
         OutputFamily::release();
         if (events) { hipEventDestroy(ev_emit[0]); hipEventDestroy(ev_emit[1]); events = false; }
+    }
+};
+
+// The record lines (pg_job_record_lines) are the family above the text: per index contig that has a plan, a
+// prefix and members, the line of every record — the caller's prefix, every member's text, a newline — packed.  d = the
+// packed lines (the exact bound), then every line's first byte (64 bits, one more behind the last), the scan's arrays, the
+// descriptors and the members.  A contig's prefix is a device buffer of its own: [R + 1] offsets, then the bytes.
+// Stale when the text it joined is stale or formed anew, and when a prefix changed.
+struct LinePrefix {
+    unsigned char* d = nullptr;
+    uint32_t R = 0;
+    uint64_t bytes = 0;
+};
+struct RecordLinesFamily : OutputFamily {
+    std::vector<LinePrefix> prefix;           // [n_index] (sized by the first pg_job_line_prefix); d null: none
+    std::vector<uint64_t> line_first, byte_first;   // [n_index + 1] first line / first byte of every index contig (after a forming)
+    size_t o_off = 0, alloc = 0;
+    uint64_t n_lines = 0, cap = 0;
+    uint64_t text_serial = 0;                 // RecordTextFamily::serial of the text the lines were joined from
+    void drop_prefix(size_t ix) {
+        if (ix < prefix.size() && prefix[ix].d) { hipFree(prefix[ix].d); prefix[ix] = LinePrefix(); formed = false; }
+    }
+    void release() {
+        OutputFamily::release();
+        for (size_t ix = 0; ix < prefix.size(); ++ix) drop_prefix(ix);
+        alloc = 0;
+        formed = false;
     }
 };
 
@@ -399,6 +427,8 @@ struct pg_job {
     std::vector<RGlDesc> rgl_desc;
     // Record text (pg_job_record_text): the bytes of the GT:GQ:GL:KC column of every record, packed, from the two families above.
     pgj::RecordTextFamily rtext;
+    // Record lines (pg_job_line_prefix / pg_job_record_lines): whole VCF lines per index contig, every member's text joined in.
+    pgj::RecordLinesFamily rlines;
     // Path subsets combined on the device (pg_job_combine_plan / pg_job_combine / pg_job_combined_calls).
     pgj::CombineState combine;
     uint64_t combine_serial = 0;              // counts the finished pg_job_combine calls

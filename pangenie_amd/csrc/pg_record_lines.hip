@@ -1,0 +1,192 @@
+// pg_record_lines.hip — whole VCF lines of a cohort joined on the device (gfx950), DESIGN.md §4e-7.
+//
+// The line of record r of an index contig is  prefix[r] ('\t' text_s[r] for every member s in order) '\n':  the caller's fixed
+// columns, then every member's bytes of that record (pg_record_text.hip's, or any bytes: they are opaque here).  A line is
+// the host's — length 0 — if any member's text of the record is empty.  The lines of a launch are PACKED, so where a byte
+// lies follows from the lengths before it — a scan — and from nothing else: no atomics anywhere.
+//
+//   k_rlines_len   one lane per line walks the members' offsets (adjacent lanes read adjacent offsets of one member); a block
+//                  scans its 256 lengths: every line's offset inside the block, and the block's sum
+//   k_rlines_sums  one workgroup scans the block sums: every block's first byte (64 bits), the total behind the last
+//   k_rlines_emit  one wave takes `lpw` consecutive lines — a power of two, 64 for one member down to 1 for many — as ONE
+//                  stream of pieces: per line the prefix, S times a tab and a text, the newline.  64 pieces a step: a wave
+//                  scan of their lengths gives each its place, the lanes copy their pieces into an LDS stage, and the stage
+//                  goes to its contiguous byte range with 16-byte stores whenever it is full.  The stage is laid out at the
+//                  residue mod 16 of the range's first byte, so LDS and global chunks line up; head and tail go out as
+//                  bytes.  A step longer than the stage's room is taken window by window: a lane copies what of its piece
+//                  falls into the window.  A piece of more than RL_SMALL bytes — an ALT column of a structural variant — is
+//                  copied by the whole wave, 64 bytes abreast, instead of by its lane alone.
+// Since consecutive lines are adjacent in the output, the S = 1 case needs no kernel of its own: 64 lines of about 100
+// bytes are one stream of 192 pieces.  One launch of each kernel covers every index contig: a descriptor per contig, a
+// block finds its own by bisection.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "pg_launch.h"
+#include "pg_text_scan.h"
+
+#define RL_BLOCK PGT_BLOCK            // lines a block of k_rlines_len scans
+#define RL_WAVES PGT_WAVES
+#define RL_EMIT 64                    // threads of k_rlines_emit: one wave
+#define RL_STAGE 8192u                // bytes of its stage: far more than two workgroups share a CU's 160 KB
+#define RL_SMALL 128u                 // a piece of at most this many bytes is copied by its lane
+#define RL_MAX_LPW 64u
+
+namespace {
+
+__device__ __forceinline__ uint32_t rlines_desc_of_len(const RLinesDesc* __restrict__ desc, uint32_t n, uint32_t b) {
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (desc[mid].blk0 <= b) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ uint32_t rlines_desc_of_emit(const RLinesDesc* __restrict__ desc, uint32_t n, uint32_t e) {
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (desc[mid].eblk0 <= e) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// loc[g]: the first byte of line g inside its block.  bsum[b]: the bytes of block b.
+__global__ __launch_bounds__(RL_BLOCK) void k_rlines_len(const RLinesDesc* __restrict__ desc, uint32_t n_desc, const RLinesMember* __restrict__ members,
+                                                         uint32_t* __restrict__ loc, uint32_t* __restrict__ bsum) {
+    __shared__ uint32_t s_wave[RL_WAVES];
+    const uint32_t blk = blockIdx.x, tid = threadIdx.x;
+    const RLinesDesc d = desc[rlines_desc_of_len(desc, n_desc, blk)];
+    const uint32_t r = (blk - d.blk0) * RL_BLOCK + tid;
+    uint32_t len = 0;
+    if (r < d.R) {
+        len = (uint32_t)(d.prefix_off[r + 1] - d.prefix_off[r]) + 1u;   // (the prefix and the newline)
+        bool host = false;
+        for (uint32_t s = 0; s < d.S; ++s) {
+            const uint64_t* __restrict__ o = members[d.mem0 + s].off;
+            const uint32_t l = (uint32_t)(o[r + 1] - o[r]);
+            host |= l == 0;
+            len += l + 1u;                                               // (a tab in front of it)
+        }
+        if (host) len = 0;
+    }
+    uint32_t total;
+    const uint32_t before = block_excl_scan(len, s_wave, &total);
+    if (r < d.R) loc[d.line0 + r] = before;
+    if (tid == 0) bsum[blk] = total;
+}
+
+// bbase[b] = the bytes of the blocks before b, b = 0 .. n
+__global__ __launch_bounds__(RL_BLOCK) void k_rlines_sums(const uint32_t* __restrict__ bsum, uint32_t n, unsigned long long* __restrict__ bbase) {
+    __shared__ unsigned long long s_wave[RL_WAVES];
+    block_sums_scan(bsum, n, bbase, s_wave);
+}
+
+__global__ __launch_bounds__(RL_EMIT) void k_rlines_emit(const RLinesDesc* __restrict__ desc, uint32_t n_desc, const RLinesMember* __restrict__ members,
+                                                         const uint32_t* __restrict__ loc, const unsigned long long* __restrict__ bbase, uint32_t n_blocks,
+                                                         unsigned long long* __restrict__ off, uint64_t n_lines, char* __restrict__ out, uint64_t cap) {
+    __shared__ uint4 s_stage[RL_STAGE / 16];
+    __shared__ uint32_t s_start[RL_MAX_LPW + 1];
+    const uint32_t e = blockIdx.x, lane = threadIdx.x;
+    const RLinesDesc d = desc[rlines_desc_of_emit(desc, n_desc, e)];
+    const uint32_t l0 = (e - d.eblk0) * d.lpw;                       // the wave's first line (lpw divides RL_BLOCK: all in one block of the scan)
+    const uint32_t n = d.R - l0 < d.lpw ? d.R - l0 : d.lpw;
+    const uint32_t blk = d.blk0 + l0 / RL_BLOCK;
+    const uint64_t base = bbase[blk];
+    const uint32_t B = (uint32_t)(bbase[blk + 1] - base);
+    for (uint32_t i = lane; i <= n; i += RL_EMIT) {
+        const uint32_t l = l0 + i;
+        const bool here = i < n || (l < d.R && l % RL_BLOCK != 0u);  // (the line behind the wave's, if the block has one)
+        const uint32_t start = here ? loc[d.line0 + l] : B;
+        s_start[i] = start;
+        if (i < n) off[d.line0 + l] = base + start;
+    }
+    if (e == gridDim.x - 1 && lane == 0) off[n_lines] = bbase[n_blocks];
+    __syncthreads();
+    const uint32_t first = s_start[0];
+    if (s_start[n] == first) return;   // (every line the host's: whole waves leave)
+    unsigned char* stage = (unsigned char*)s_stage;
+    uint64_t gpos = base + first;
+    uint32_t shift = (uint32_t)(gpos & 15u), fill = shift;
+    const uint32_t P = d.S + 2u, Q = n * P;   // pieces of a line: the prefix, the members' texts, the newline
+    for (uint32_t q0 = 0; q0 < Q; q0 += RL_EMIT) {
+        const uint32_t q = q0 + lane;
+        const char* src = nullptr;
+        uint32_t tot = 0, lead = 0;     // lead: the character in front of the piece's bytes, 0 for none
+        if (q < Q) {
+            const uint32_t ll = q / P, p = q - ll * P, r = l0 + ll;
+            if (s_start[ll + 1] != s_start[ll]) {
+                if (p == 0) {
+                    const uint64_t o = d.prefix_off[r];
+                    src = d.prefix + o;
+                    tot = (uint32_t)(d.prefix_off[r + 1] - o);
+                } else if (p <= d.S) {
+                    const RLinesMember m = members[d.mem0 + p - 1u];
+                    const uint64_t o = m.off[r];
+                    src = m.text + o;
+                    lead = '\t';
+                    tot = (uint32_t)(m.off[r + 1] - o) + 1u;
+                } else {
+                    lead = '\n';
+                    tot = 1u;
+                }
+            }
+        }
+        const uint32_t incl = wave_incl_scan(tot, lane), a = incl - tot;
+        const uint32_t T = __shfl(incl, 63, 64);
+        const bool big = tot > RL_SMALL;
+        const unsigned long long bigmask = __ballot(big);
+        const uint32_t nl = lead ? 1u : 0u;
+        uint32_t done = 0;
+        while (done < T) {   // the step's T bytes, window by window
+            const uint32_t room = RL_STAGE - fill, w = T - done < room ? T - done : room, w1 = done + w;
+            if (!big) {
+                const uint32_t x0 = a > done ? a : done, x1 = a + tot < w1 ? a + tot : w1;
+                for (uint32_t x = x0; x < x1; ++x) stage[fill + (x - done)] = nl && x == a ? (unsigned char)lead : (unsigned char)src[x - a - nl];
+            }
+            for (unsigned long long m = bigmask; m; m &= m - 1) {   // (uniform: every lane walks the same mask)
+                const int j = __ffsll((long long)m) - 1;
+                const uint32_t aj = __shfl(a, j, 64), tj = __shfl(tot, j, 64), leadj = __shfl(lead, j, 64), nj = leadj ? 1u : 0u;
+                const uint64_t sj = (uint64_t)__shfl((uint32_t)(uintptr_t)src, j, 64) | ((uint64_t)__shfl((uint32_t)((uintptr_t)src >> 32), j, 64) << 32);
+                const char* srcj = (const char*)(uintptr_t)sj;
+                const uint32_t y0 = aj > done ? aj : done, y1 = aj + tj < w1 ? aj + tj : w1;
+                for (uint32_t x = y0 + lane; x < y1; x += RL_EMIT) stage[fill + (x - done)] = nj && x == aj ? (unsigned char)leadj : (unsigned char)srcj[x - aj - nj];
+            }
+            fill += w;
+            done = w1;
+            if (fill == RL_STAGE) {
+                __syncthreads();
+                rtext_flush<RL_EMIT>(s_stage, out, gpos - shift, shift, fill, cap, lane);
+                __syncthreads();
+                gpos += fill - shift;   // (a multiple of 16 from here on)
+                shift = 0;
+                fill = 0;
+            }
+        }
+    }
+    __syncthreads();
+    if (fill > shift) rtext_flush<RL_EMIT>(s_stage, out, gpos - shift, shift, fill, cap, lane);
+}
+
+}  // namespace
+
+extern "C" uint32_t pgk_rlines_block(void) { return RL_BLOCK; }
+extern "C" uint32_t pgk_rlines_stage_bytes(void) { return RL_STAGE; }
+// lines per wave of k_rlines_emit for S members: the largest power of two with at most 256 pieces, at least 1 and at most 64
+extern "C" uint32_t pgk_rlines_lines_per_wave(uint32_t n_members) {
+    uint32_t lpw = RL_MAX_LPW;
+    while (lpw > 1u && (uint64_t)lpw * ((uint64_t)n_members + 2u) > 256u) lpw >>= 1;
+    return lpw;
+}
+
+extern "C" void pgk_launch_rlines(const RLinesDesc* d_desc, uint32_t n_desc, const RLinesMember* d_members, uint32_t n_blocks, uint32_t n_emit_blocks,
+                                  uint32_t* d_loc, uint32_t* d_bsum, uint64_t* d_bbase, uint64_t* d_off, uint64_t n_lines, char* d_out, uint64_t cap,
+                                  hipStream_t s) {
+    if (!n_desc || !n_blocks || !n_emit_blocks) return;
+    hipLaunchKernelGGL(k_rlines_len, dim3(n_blocks), dim3(RL_BLOCK), 0, s, d_desc, n_desc, d_members, d_loc, d_bsum);
+    hipLaunchKernelGGL(k_rlines_sums, dim3(1), dim3(RL_BLOCK), 0, s, d_bsum, n_blocks, (unsigned long long*)d_bbase);
+    hipLaunchKernelGGL(k_rlines_emit, dim3(n_emit_blocks), dim3(RL_EMIT), 0, s, d_desc, n_desc, d_members, d_loc, (const unsigned long long*)d_bbase, n_blocks,
+                       (unsigned long long*)d_off, n_lines, d_out, cap);
+}

@@ -22,9 +22,10 @@
 
 #include "pg_calls.h"
 #include "pg_launch.h"
+#include "pg_text_scan.h"   // wave_incl_scan, block_excl_scan, block_sums_scan, rtext_flush: shared with pg_record_lines.hip
 
-#define RT_BLOCK 256
-#define RT_WAVES (RT_BLOCK / 64)
+#define RT_BLOCK PGT_BLOCK
+#define RT_WAVES PGT_WAVES
 #define RT_STAGE 32768u               // bytes of k_rtext_emit's stage: four workgroups share a CU's 160 KB
 #define RT_WINDOW (RT_STAGE - 16u)    // bytes of text a window takes at most (the stage begins at the range's residue mod 16)
 #define RT_WIDE_BOUND (RT_STAGE / 4u)
@@ -84,33 +85,6 @@ struct ClipSink {
     }
 };
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane) {
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
-
-// Bytes [lo, hi) of the stage to text[g16 + lo .. g16 + hi), g16 a multiple of 16: chunk c of the stage is chunk c of the
-// range.  Whole chunks as one 16-byte store, the two ends as bytes; nothing at or behind `cap`.
-template <uint32_t NT>
-__device__ __forceinline__ void rtext_flush(const uint4* __restrict__ stage4, char* __restrict__ text, uint64_t g16, uint32_t lo, uint32_t hi, uint64_t cap,
-                                            uint32_t tid) {
-    const unsigned char* stage = (const unsigned char*)stage4;
-    const uint32_t c1 = (hi + 15u) / 16u;
-    for (uint32_t c = lo / 16u + tid; c < c1; c += NT) {
-        const uint32_t b0 = c * 16u;
-        const uint64_t g = g16 + b0;
-        if (b0 >= lo && b0 + 16u <= hi && g + 16u <= cap) *(uint4*)(text + g) = stage4[c];
-        else {
-            const uint32_t x0 = b0 > lo ? b0 : lo, x1 = b0 + 16u < hi ? b0 + 16u : hi;
-            for (uint32_t x = x0; x < x1; ++x)
-                if (g16 + x < cap) text[g16 + x] = (char)stage[x];
-        }
-    }
-}
-
 __global__ __launch_bounds__(RT_BLOCK) void k_rtext_len_wide(const DevContig* __restrict__ contigs, const RTextDesc* __restrict__ desc,
                                                              const uint2* __restrict__ list, uint32_t n_list, uint32_t* __restrict__ wlen,
                                                              uint32_t* __restrict__ loc) {
@@ -147,7 +121,7 @@ __global__ __launch_bounds__(RT_BLOCK) void k_rtext_len_wide(const DevContig* __
 __global__ __launch_bounds__(RT_BLOCK) void k_rtext_len(const DevContig* __restrict__ contigs, const RTextDesc* __restrict__ desc, uint32_t n_desc,
                                                         uint32_t* __restrict__ loc, uint32_t* __restrict__ bsum) {
     __shared__ uint32_t s_wave[RT_WAVES];
-    const uint32_t blk = blockIdx.x, tid = threadIdx.x, lane = tid % 64u, wave = tid / 64u;
+    const uint32_t blk = blockIdx.x, tid = threadIdx.x;
     const RTextDesc d = desc[rtext_chain_of(desc, n_desc, blk)];
     const uint32_t r = (blk - d.blk0) * RT_BLOCK + tid;
     uint32_t len = 0;
@@ -155,45 +129,16 @@ __global__ __launch_bounds__(RT_BLOCK) void k_rtext_len(const DevContig* __restr
         const RecIn in = rtext_record(contigs, d, r);
         len = rtext_is_wide(in.n_gl) ? loc[d.rec0 + r] : pgx_record_text_len(in.call, in.gl, in.n_gl, in.kc, in.no_call);
     }
-    const uint32_t incl = wave_incl_scan(len, lane);
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-    for (uint32_t w = 0; w < RT_WAVES; ++w) {
-        const uint32_t x = s_wave[w];
-        if (w < wave) before += x;
-        total += x;
-    }
-    if (r < d.R) loc[d.rec0 + r] = before + incl - len;
+    uint32_t total;
+    const uint32_t before = block_excl_scan(len, s_wave, &total);
+    if (r < d.R) loc[d.rec0 + r] = before;
     if (tid == 0) bsum[blk] = total;
 }
 
 // bbase[b] = the bytes of the blocks before b, b = 0 .. n (one workgroup: n is a 256th of the records)
 __global__ __launch_bounds__(RT_BLOCK) void k_rtext_sums(const uint32_t* __restrict__ bsum, uint32_t n, unsigned long long* __restrict__ bbase) {
     __shared__ unsigned long long s_wave[RT_WAVES];
-    const uint32_t tid = threadIdx.x, lane = tid % 64u, wave = tid / 64u;
-    unsigned long long carry = 0;
-    for (uint32_t b0 = 0; b0 < n; b0 += RT_BLOCK) {
-        const uint32_t b = b0 + tid;
-        const unsigned long long x = b < n ? bsum[b] : 0ull;
-        unsigned long long incl = x;
-        for (uint32_t dd = 1; dd < 64; dd <<= 1) {
-            const unsigned long long y = __shfl_up(incl, dd, 64);
-            if (lane >= dd) incl += y;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        unsigned long long before = 0, total = 0;
-        for (uint32_t w = 0; w < RT_WAVES; ++w) {
-            const unsigned long long y = s_wave[w];
-            if (w < wave) before += y;
-            total += y;
-        }
-        if (b < n) bbase[b] = carry + before + incl - x;
-        carry += total;
-        __syncthreads();
-    }
-    if (tid == 0) bbase[n] = carry;
+    block_sums_scan(bsum, n, bbase, s_wave);
 }
 
 __global__ __launch_bounds__(RT_BLOCK) void k_rtext_emit(const DevContig* __restrict__ contigs, const RTextDesc* __restrict__ desc, uint32_t n_desc,

@@ -547,6 +547,7 @@ extern "C" int pg_job_record_plan(pg_job* job, uint32_t ix, const pg_record_plan
     rc = record_plan_to_device(job, std::move(h), &ref, err, errlen);
     if (rc != PG_OK) return rc;
     job->rplans[ix] = std::move(ref);   // (this index contig's reference alone: the members of a stride keep theirs)
+    job->rlines.drop_prefix(ix);        // (the prefix of the lines had the old plan's records)
     record_plans_changed(job);
     return PG_OK;
 }
@@ -568,7 +569,7 @@ extern "C" int pg_job_record_plan_strided(pg_job* job, uint32_t contig, uint32_t
     RecordPlanRef ref;
     rc = record_plan_to_device(job, std::move(h), &ref, err, errlen);
     if (rc != PG_OK) return rc;
-    for (size_t ix = contig; ix < job->index.size(); ix += n_contigs) job->rplans[ix] = ref;
+    for (size_t ix = contig; ix < job->index.size(); ix += n_contigs) { job->rplans[ix] = ref; job->rlines.drop_prefix(ix); }
     record_plans_changed(job);
     return PG_OK;
 }
@@ -928,6 +929,7 @@ extern "C" int pg_job_record_text(pg_job* job, int ignore_imputed, char* err, si
         f.text_first[n] = bbase.back();
     }
     f.formed = true;
+    f.serial += 1;
     return PG_OK;
 }
 

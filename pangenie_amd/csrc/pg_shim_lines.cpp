@@ -1,0 +1,302 @@
+// pg_shim_lines.cpp — the C-ABI of the record lines (pg_record_lines.hip): the prefix of an index contig,
+// the forming of whole VCF lines from a job's record text, their fetches, and the unit entry point over host arrays.
+// Host code off the critical path.
+#include <hip/hip_runtime_api.h>
+
+#include <string.h>
+
+#include <vector>
+
+#include "../../include/pangenie_hmm.h"
+#include "pg_device.h"
+#include "pg_job.h"
+#include "pg_launch.h"
+
+using namespace pgj;
+
+namespace {
+
+// Where the arrays of one launch lie in ONE buffer: the packed lines (`cap` bytes), then the offsets, the scan's arrays, the
+// descriptors and the members.
+struct RLinesLayout {
+    size_t o_off, o_loc, o_bsum, o_bbase, o_desc, o_members, total;
+    RLinesLayout(uint64_t cap, uint64_t n_lines, uint32_t n_blocks, size_t n_desc, size_t n_members) {
+        o_off = align_up((size_t)cap + 16);
+        o_loc = o_off + align_up(((size_t)n_lines + 1) * 8 + 8);
+        o_bsum = o_loc + align_up((size_t)n_lines * 4 + 8);
+        o_bbase = o_bsum + align_up((size_t)n_blocks * 4 + 8);
+        o_desc = o_bbase + align_up(((size_t)n_blocks + 1) * 8 + 8);
+        o_members = o_desc + align_up(n_desc * sizeof(RLinesDesc) + 8);
+        total = o_members + align_up(n_members * sizeof(RLinesMember) + 8);
+    }
+};
+
+// one more contig of R records and S members behind those of `desc`: its blocks of both kernels, its first line and member
+void rlines_add(std::vector<RLinesDesc>* desc, uint32_t R, uint32_t S, uint32_t* blk, uint32_t* eblk, uint64_t* line, uint32_t* mem) {
+    RLinesDesc d;
+    memset(&d, 0, sizeof(d));
+    const uint32_t per = pgk_rlines_block();
+    d.blk0 = *blk; d.R = R; d.eblk0 = *eblk; d.lpw = pgk_rlines_lines_per_wave(S); d.line0 = *line; d.mem0 = *mem; d.S = S;
+    *blk += (R + per - 1) / per;
+    *eblk += (R + d.lpw - 1) / d.lpw;
+    *line += R;
+    *mem += S;
+    desc->push_back(d);
+}
+
+void rlines_launch(unsigned char* d, const RLinesLayout& L, uint32_t n_desc, uint32_t n_blocks, uint32_t n_eblocks, uint64_t n_lines, uint64_t cap, hipStream_t s) {
+    pgk_launch_rlines((const RLinesDesc*)(d + L.o_desc), n_desc, (const RLinesMember*)(d + L.o_members), n_blocks, n_eblocks, (uint32_t*)(d + L.o_loc),
+                      (uint32_t*)(d + L.o_bsum), (uint64_t*)(d + L.o_bbase), (uint64_t*)(d + L.o_off), n_lines, (char*)d, cap, s);
+}
+
+bool text_current(const pg_job* job) {
+    const RecordTextFamily& t = job->rtext;
+    return job->ran && t.formed && !t.dirty && t.run == job->run_serial;
+}
+
+int rlines_ready(pg_job* job, char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    const RecordLinesFamily& f = job->rlines;
+    if (!text_current(job) || !f.formed || f.text_serial != job->rtext.serial) {
+        set_err(err, errlen, "pg_job_record_lines has not been called for this text and these prefixes");
+        return PG_ERR_INVALID;
+    }
+    return PG_OK;
+}
+
+// lines [l0, l1) of a formed job: their offsets less `minus` and their bytes [b0, b1), n_bytes of them
+int rlines_fetch(pg_job* job, uint64_t l0, uint64_t l1, uint64_t b0, uint64_t b1, uint64_t minus, uint64_t* off, char* text, uint64_t n_bytes, char* err,
+                 size_t errlen) {
+    const RecordLinesFamily& f = job->rlines;
+    if (n_bytes != b1 - b0) { set_err(err, errlen, "the lines hold %llu bytes, not %llu", (unsigned long long)(b1 - b0), (unsigned long long)n_bytes); return PG_ERR_INVALID; }
+    if (n_bytes && !text) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(job->device));
+    if (off) {
+        if (f.n_lines == 0) off[0] = 0;
+        else HIP_TRY(hipMemcpyAsync(off, f.d + f.o_off + l0 * 8, (l1 - l0 + 1) * 8, hipMemcpyDeviceToHost, job->stream));
+    }
+    if (n_bytes) HIP_TRY(hipMemcpyAsync(text, f.d + b0, n_bytes, hipMemcpyDeviceToHost, job->stream));
+    HIP_TRY(hipStreamSynchronize(job->stream));
+    if (off && minus && f.n_lines)
+        for (uint64_t q = 0; q <= l1 - l0; ++q) off[q] -= minus;
+    return PG_OK;
+}
+
+bool offsets_ok(const uint64_t* off, uint64_t n) {
+    if (!off || off[0] != 0) return false;
+    for (uint64_t q = 0; q < n; ++q)
+        if (off[q + 1] < off[q]) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" uint64_t pg_record_lines_bound(uint64_t n_records, uint64_t n_members, uint64_t prefix_bytes, uint64_t text_bytes) {
+    return prefix_bytes + text_bytes + n_records * (n_members + 1);
+}
+
+extern "C" int pg_job_line_prefix(pg_job* job, uint32_t ix, const uint64_t* off, const char* bytes, char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    if (ix >= job->index.size()) { set_err(err, errlen, "index contig %u of %zu", ix, job->index.size()); return PG_ERR_INVALID; }
+    if (ix >= job->rplans.size() || !job->rplans[ix]) { set_err(err, errlen, "index contig %u has no record plan", ix); return PG_ERR_INVALID; }
+    const uint32_t R = job->rplans[ix]->R;
+    if (!offsets_ok(off, R)) { set_err(err, errlen, "the prefix offsets are null, do not start at 0 or shrink"); return PG_ERR_INVALID; }
+    const uint64_t n = off[R];
+    if (n && !bytes) { set_err(err, errlen, "null prefix bytes"); return PG_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(job->device));
+    const size_t o_bytes = align_up(((size_t)R + 1) * 8);
+    unsigned char* d = nullptr;
+    if (hipMalloc((void**)&d, o_bytes + (size_t)n + 16) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the line prefix failed", o_bytes + (size_t)n + 16); return PG_ERR_NOMEM; }
+    if (hipMemcpy(d, off, ((size_t)R + 1) * 8, hipMemcpyHostToDevice) != hipSuccess || (n && hipMemcpy(d + o_bytes, bytes, n, hipMemcpyHostToDevice) != hipSuccess)) {
+        (void)hipGetLastError();
+        hipFree(d);
+        set_err(err, errlen, "upload of the line prefix failed");
+        return PG_ERR_DEVICE;
+    }
+    RecordLinesFamily& f = job->rlines;
+    if (f.prefix.size() != job->index.size()) f.prefix.resize(job->index.size());
+    if (job->stream) HIP_TRY(hipStreamSynchronize(job->stream));   // (nothing reads the prefix this one replaces any more)
+    f.drop_prefix(ix);
+    f.prefix[ix].d = d; f.prefix[ix].R = R; f.prefix[ix].bytes = n;
+    f.formed = false;
+    return PG_OK;
+}
+
+extern "C" int pg_job_record_lines(pg_job* job, char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    if (!text_current(job)) { set_err(err, errlen, "pg_job_record_text has not been called for this run and these plans"); return PG_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(job->device));
+    RecordLinesFamily& f = job->rlines;
+    const RecordTextFamily& t = job->rtext;
+    const size_t n_index = job->index.size(), n_chains = job->chains.size();
+    f.formed = false;
+    // the members of every index contig: its chains in ascending id
+    std::vector<std::vector<uint32_t>> chains_of(n_index);
+    for (size_t c = 0; c < n_chains; ++c) chains_of[job->chains[c].index].push_back((uint32_t)c);
+    std::vector<RLinesDesc> desc;
+    std::vector<RLinesMember> members;
+    std::vector<size_t> contig_of;   // the index contig of every descriptor
+    uint32_t blk = 0, eblk = 0, mem = 0;
+    uint64_t line = 0, cap = 0;
+    for (size_t ix = 0; ix < n_index; ++ix) {
+        const bool plan = ix < job->rplans.size() && job->rplans[ix], prefix = ix < f.prefix.size() && f.prefix[ix].d;
+        if (!plan || !prefix || chains_of[ix].empty()) continue;
+        const uint32_t R = job->rplans[ix]->R, S = (uint32_t)chains_of[ix].size();
+        if (f.prefix[ix].R != R) { set_err(err, errlen, "the prefix of index contig %zu has %u records, its plan %u", ix, f.prefix[ix].R, R); return PG_ERR_INVALID; }
+        if (R == 0) continue;
+        uint64_t text_bytes = 0;
+        for (uint32_t c : chains_of[ix]) {
+            if (t.first[c + 1] - t.first[c] != R) { set_err(err, errlen, "chain %u holds %llu records of text, its plan %u", c, (unsigned long long)(t.first[c + 1] - t.first[c]), R); return PG_ERR_INVALID; }
+            RLinesMember m;
+            m.off = (const uint64_t*)(t.d + t.o_off) + t.first[c];   // (absolute in the packed text)
+            m.text = (const char*)t.d;
+            members.push_back(m);
+            text_bytes += t.text_first[c + 1] - t.text_first[c];
+        }
+        rlines_add(&desc, R, S, &blk, &eblk, &line, &mem);
+        desc.back().prefix_off = (const uint64_t*)f.prefix[ix].d;
+        desc.back().prefix = (const char*)(f.prefix[ix].d + align_up(((size_t)R + 1) * 8));
+        contig_of.push_back(ix);
+        cap += pg_record_lines_bound(R, S, f.prefix[ix].bytes, text_bytes);
+    }
+    const RLinesLayout L(cap, line, blk, desc.size(), members.size());
+    if (!f.d || f.alloc < L.total) {
+        unsigned char* d = nullptr;
+        if (hipMalloc((void**)&d, L.total) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the record lines failed", L.total); return PG_ERR_NOMEM; }
+        f.OutputFamily::release();
+        f.d = d;
+        f.alloc = L.total;
+    }
+    f.o_off = L.o_off; f.n_lines = line; f.cap = cap; f.blocks = blk;
+    f.line_first.assign(n_index + 1, 0);
+    f.byte_first.assign(n_index + 1, 0);
+    f.ms = 0.0;
+    if (!desc.empty()) {
+        hipStream_t s = job->stream;
+        HIP_TRY(hipMemcpyAsync(f.d + L.o_desc, desc.data(), desc.size() * sizeof(RLinesDesc), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(f.d + L.o_members, members.data(), members.size() * sizeof(RLinesMember), hipMemcpyHostToDevice, s));
+        if (!job->calls_events) {
+            HIP_TRY(hipEventCreate(&job->ev_calls[0]));
+            HIP_TRY(hipEventCreate(&job->ev_calls[1]));
+            job->calls_events = true;
+        }
+        HIP_TRY(hipEventRecord(job->ev_calls[0], s));
+        rlines_launch(f.d, L, (uint32_t)desc.size(), blk, eblk, line, cap, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(job->ev_calls[1], s));
+        HIP_TRY(hipStreamSynchronize(s));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, job->ev_calls[0], job->ev_calls[1]));
+        f.ms = ms;
+        std::vector<uint64_t> bbase((size_t)blk + 1);
+        HIP_TRY(hipMemcpy(bbase.data(), f.d + L.o_bbase, bbase.size() * 8, hipMemcpyDeviceToHost));
+        if (bbase.back() > cap) { set_err(err, errlen, "the record lines take %llu bytes, more than their bound %llu", (unsigned long long)bbase.back(), (unsigned long long)cap); return PG_ERR_DEVICE; }
+        size_t i = 0;   // a contig begins a block: its first byte is that block's
+        for (size_t ix = 0; ix < n_index; ++ix) {
+            f.line_first[ix] = i < desc.size() ? desc[i].line0 : line;
+            f.byte_first[ix] = i < desc.size() ? bbase[desc[i].blk0] : bbase.back();
+            if (i < desc.size() && contig_of[i] == ix) ++i;
+        }
+        f.line_first[n_index] = line;
+        f.byte_first[n_index] = bbase.back();
+    }
+    f.run = job->run_serial;
+    f.text_serial = t.serial;
+    f.dirty = false;
+    f.formed = true;
+    return PG_OK;
+}
+
+extern "C" double pg_job_record_lines_ms(const pg_job* job) { return job ? job->rlines.ms : 0.0; }
+
+extern "C" int pg_job_record_lines_first(pg_job* job, uint64_t* n_index_contigs, uint64_t* line_first, uint64_t* byte_first, char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    if (n_index_contigs) *n_index_contigs = job->index.size();
+    if (!line_first && !byte_first) return PG_OK;
+    const int rc = rlines_ready(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    const RecordLinesFamily& f = job->rlines;
+    if (line_first) memcpy(line_first, f.line_first.data(), f.line_first.size() * sizeof(uint64_t));
+    if (byte_first) memcpy(byte_first, f.byte_first.data(), f.byte_first.size() * sizeof(uint64_t));
+    return PG_OK;
+}
+
+extern "C" int pg_job_fetch_record_lines(pg_job* job, uint32_t ix, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
+    const int rc = rlines_ready(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (ix >= job->index.size()) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    const RecordLinesFamily& f = job->rlines;
+    return rlines_fetch(job, f.line_first[ix], f.line_first[ix + 1], f.byte_first[ix], f.byte_first[ix + 1], f.byte_first[ix], off, text, n_bytes, err, errlen);
+}
+
+extern "C" int pg_job_fetch_record_lines_packed(pg_job* job, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
+    const int rc = rlines_ready(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    const RecordLinesFamily& f = job->rlines;
+    return rlines_fetch(job, 0, f.n_lines, 0, f.byte_first.back(), 0, off, text, n_bytes, err, errlen);
+}
+
+extern "C" int pg_job_device_record_lines(pg_job* job, uint32_t ix, void** d_off, void** d_text, uint64_t* n_lines, uint64_t* n_bytes) {
+    if (rlines_ready(job, nullptr, 0) != PG_OK || ix >= job->index.size()) return PG_ERR_INVALID;
+    const RecordLinesFamily& f = job->rlines;
+    if (d_off) *d_off = f.d + f.o_off + f.line_first[ix] * 8;
+    if (d_text) *d_text = f.d + f.byte_first[ix];
+    if (n_lines) *n_lines = f.line_first[ix + 1] - f.line_first[ix];
+    if (n_bytes) *n_bytes = f.byte_first[ix + 1] - f.byte_first[ix];
+    return PG_OK;
+}
+
+// The unit entry point: arbitrary bytes in, the packed lines and their offsets out, through the same kernels.
+extern "C" int pg_record_lines_from_text(int device, uint64_t n_records, uint64_t n_members, const uint64_t* const* off, const char* const* text,
+                                         const uint64_t* prefix_off, const char* prefix, uint64_t* out_off, char* out, uint64_t cap) {
+    if (!out_off || !off || !text || !prefix_off || n_members == 0 || n_members >= 0x80000000ull - 2 || n_records >= 0x80000000ull) return PG_ERR_INVALID;
+    if (!offsets_ok(prefix_off, n_records) || (prefix_off[n_records] && !prefix)) return PG_ERR_INVALID;
+    uint64_t text_bytes = 0;
+    for (uint64_t s = 0; s < n_members; ++s) {
+        if (!offsets_ok(off[s], n_records) || (off[s][n_records] && !text[s])) return PG_ERR_INVALID;
+        text_bytes += off[s][n_records];
+    }
+    const uint64_t bound = pg_record_lines_bound(n_records, n_members, prefix_off[n_records], text_bytes);
+    if (cap < bound || (cap && !out)) return PG_ERR_INVALID;
+    if (n_records == 0) { out_off[0] = 0; return PG_OK; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); return PG_ERR_DEVICE; }
+    if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return PG_ERR_DEVICE;
+    const uint32_t R = (uint32_t)n_records, S = (uint32_t)n_members;
+    std::vector<RLinesDesc> desc;
+    uint32_t blk = 0, eblk = 0, mem = 0;
+    uint64_t line = 0;
+    rlines_add(&desc, R, S, &blk, &eblk, &line, &mem);
+    const RLinesLayout L(bound, R, blk, 1, S);
+    // the inputs behind the launch's own arrays: the prefix, then member after member (offsets, bytes)
+    const size_t offs_bytes = align_up(((size_t)R + 1) * 8);
+    std::vector<size_t> o_moff(S), o_mtext(S);
+    size_t at = L.total;
+    const size_t o_poff = at; at += offs_bytes;
+    const size_t o_pbytes = at; at += align_up((size_t)prefix_off[R] + 16);
+    for (uint32_t s = 0; s < S; ++s) {
+        o_moff[s] = at; at += offs_bytes;
+        o_mtext[s] = at; at += align_up((size_t)off[s][R] + 16);
+    }
+    unsigned char* d = nullptr;
+    if (hipMalloc((void**)&d, at) != hipSuccess) { (void)hipGetLastError(); return PG_ERR_NOMEM; }
+    std::vector<RLinesMember> members(S);
+    for (uint32_t s = 0; s < S; ++s) { members[s].off = (const uint64_t*)(d + o_moff[s]); members[s].text = (const char*)(d + o_mtext[s]); }
+    desc[0].prefix_off = (const uint64_t*)(d + o_poff);
+    desc[0].prefix = (const char*)(d + o_pbytes);
+    bool ok = hipMemcpy(d + L.o_desc, desc.data(), sizeof(RLinesDesc), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + L.o_members, members.data(), (size_t)S * sizeof(RLinesMember), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + o_poff, prefix_off, ((size_t)R + 1) * 8, hipMemcpyHostToDevice) == hipSuccess &&
+              (prefix_off[R] == 0 || hipMemcpy(d + o_pbytes, prefix, prefix_off[R], hipMemcpyHostToDevice) == hipSuccess);
+    for (uint32_t s = 0; s < S && ok; ++s)
+        ok = hipMemcpy(d + o_moff[s], off[s], ((size_t)R + 1) * 8, hipMemcpyHostToDevice) == hipSuccess &&
+             (off[s][R] == 0 || hipMemcpy(d + o_mtext[s], text[s], off[s][R], hipMemcpyHostToDevice) == hipSuccess);
+    if (ok) {
+        rlines_launch(d, L, 1, blk, eblk, R, bound, nullptr);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
+             hipMemcpy(out_off, d + L.o_off, ((size_t)R + 1) * 8, hipMemcpyDeviceToHost) == hipSuccess && out_off[R] <= bound &&
+             (out_off[R] == 0 || hipMemcpy(out, d, out_off[R], hipMemcpyDeviceToHost) == hipSuccess);
+    }
+    hipFree(d);
+    return ok ? PG_OK : PG_ERR_DEVICE;
+}

@@ -460,6 +460,30 @@ class Job:
         """elapsed ms of the kernels of the last record_text()"""
         return float(self._lib.pg_job_record_text_ms(self.h))
 
+    def line_prefix(self, contig: int, off, data) -> None:
+        """pg_job_line_prefix: the fixed columns (CHROM .. FORMAT, no trailing tab) of the records of INDEX contig `contig`,
+        record r's = data[off[r]:off[r + 1]]; after record_plan().  A second call replaces them."""
+        from . import calls as _calls
+        _calls.job_line_prefix(self, contig, off, data)
+
+    def record_lines(self, contig: Optional[int] = None):
+        """pg_job_record_lines + pg_job_fetch_record_lines: whole VCF lines — the prefix, every member's text behind a tab, a
+        newline — joined on the device from the text of the last record_text().  (off, bytes) of index
+        contig `contig`, or a list of them, one per index contig; a line of length 0 is the host's."""
+        from . import calls as _calls
+        return _calls.job_record_lines(self, contig)
+
+    def record_lines_packed(self):
+        """pg_job_record_lines + pg_job_fetch_record_lines_packed: (off [n_lines + 1] absolute, all bytes from ONE copy,
+        line_first, byte_first [n_index_contigs + 1])."""
+        from . import calls as _calls
+        _calls.form_record_lines(self)
+        return _calls.fetch_record_lines_packed(self)
+
+    def record_lines_ms(self) -> float:
+        """elapsed ms of the kernels of the last record_lines()"""
+        return float(self._lib.pg_job_record_lines_ms(self.h))
+
     def combine_plan(self, groups) -> None:
         """pg_job_combine_plan: groups = per group the chains (contig x path subset) that genotype the same index objects, in the
         order they are to be added up; a second plan replaces the first."""

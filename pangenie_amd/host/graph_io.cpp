@@ -436,6 +436,12 @@ std::vector<std::string> Graph::genotypes_header(const std::string& sample, cons
     };
 }
 
+std::vector<std::string> Graph::genotypes_header(const std::vector<std::string>& samples, const std::string& date) {
+    std::string columns;
+    for (size_t s = 0; s < samples.size(); ++s) columns += (s ? "\t" : "") + samples[s];
+    return genotypes_header(columns, date);
+}
+
 std::vector<std::string> Graph::genotypes_records(const std::vector<GenotypingResult>& genotyping_result, bool ignore_imputed) const {
     return sample_records(genotyping_result, ignore_imputed, false);
 }
@@ -500,6 +506,90 @@ static std::string text_field(const RecordText& t, size_t q, size_t n_defined) {
     return t.bytes.substr(t.off[q], t.off[q + 1] - t.off[q]);
 }
 
+// CHROM .. INFO of one record
+std::string Graph::fixed_columns_of(const VcfSite& site, size_t record_index, size_t unique_kmers, const char* who, std::vector<unsigned short>& defined) const {
+    const size_t n_all = site.alleles.size();
+    if (n_all < 2) throw std::runtime_error(std::string(who) + ": less than 2 alleles given for variant at position " + std::to_string(site.start));
+    // ALT = the defined alternative alleles; genotypes over undefined alleles are dropped by the caller
+    defined = {0};
+    std::vector<std::string> alts;
+    for (size_t a = 1; a < n_all; ++a)
+        if (!site.undefined[a]) { defined.push_back((unsigned short)a); alts.push_back(site.alleles[a]); }
+    // allele frequencies over the panel paths (without the reference path when it was added as one)
+    std::vector<float> freq(n_all, 0.0f);
+    for (unsigned short a : site.paths) freq.at(a) += 1.0f;
+    unsigned int n_paths = (unsigned int)site.paths.size();
+    if (add_reference_) { n_paths -= 1; freq[0] -= 1.0f; }
+    std::ostringstream line;
+    line << site.chromosome << '\t' << (site.start + 1) << "\t.\t" << site.alleles[0] << '\t';
+    for (size_t k = 0; k < alts.size(); ++k) line << (k ? "," : "") << alts[k];
+    line << "\t.\tPASS\tAF=";
+    for (size_t k = 1; k < defined.size(); ++k) line << (k > 1 ? "," : "") << std::setprecision(6) << freq[defined[k]] / n_paths;
+    line << ";UK=" << unique_kmers << ";MA=" << (n_all - defined.size());
+    const std::vector<std::string>& ids = variant_ids_.at(record_index);
+    if (!ids.empty()) {
+        // the ids are kept in the lexicographic order of their ALT alleles: back into ALT order
+        if (ids.size() != alts.size()) throw std::runtime_error(std::string(who) + ": number of variant ids and of ALT alleles differ");
+        std::vector<size_t> by_sequence(alts.size());
+        std::iota(by_sequence.begin(), by_sequence.end(), (size_t)0);
+        std::sort(by_sequence.begin(), by_sequence.end(), [&](size_t x, size_t y) { return alts[x] < alts[y]; });
+        std::vector<const std::string*> in_alt_order(alts.size(), nullptr);
+        for (size_t rank = 0; rank < by_sequence.size(); ++rank) in_alt_order[by_sequence[rank]] = &ids[rank];
+        line << ";ID=";
+        for (size_t k = 0; k < in_alt_order.size(); ++k) line << (k ? "," : "") << *in_alt_order[k];
+    }
+    return line.str();
+}
+
+std::vector<std::string> Graph::genotypes_fixed_columns(const std::vector<unsigned short>& unique_kmers) const {
+    const char* who = "Graph::write_genotypes_of";
+    if (variants_deleted_) throw std::runtime_error(std::string(who) + ": variants have been deleted by delete_variant funtion. Re-build object.");
+    if (unique_kmers.size() != size()) throw std::runtime_error(std::string(who) + ": number of variants and number of computed genotypes differ.");
+    std::vector<std::string> columns;
+    std::vector<unsigned short> defined;
+    for (size_t i = 0; i < size(); ++i)
+        for (const VcfSite& site : get_variant(i).records(nullptr)) {
+            columns.push_back(fixed_columns_of(site, columns.size(), unique_kmers[i], who, defined) + "\tGT:GQ:GL:KC");
+        }
+    return columns;
+}
+
+size_t Graph::nr_of_records() const {
+    size_t n = 0;
+    for (size_t i = 0; i < size(); ++i) n += get_variant(i).nr_of_records();
+    return n;
+}
+
+RecordLines compose_record_lines(const std::vector<std::string>& prefix, const std::vector<const RecordText*>& texts, const RecordLines& device) {
+    const size_t R = prefix.size();
+    if (device.off.size() != R + 1 || device.off[0] != 0 || device.off[R] != device.bytes.size())
+        throw std::runtime_error("compose_record_lines: the lines do not fit the prefixes");
+    for (const RecordText* t : texts)
+        if (!t || t->off.size() != R + 1 || t->off[R] > t->bytes.size()) throw std::runtime_error("compose_record_lines: a sample's text does not fit the prefixes");
+    bool any = false;
+    for (size_t r = 0; r < R; ++r) {
+        if (device.off[r + 1] < device.off[r]) throw std::runtime_error("compose_record_lines: the lines' offsets shrink");
+        if (device.off[r + 1] == device.off[r]) any = true;
+    }
+    if (!any) return device;
+    RecordLines out;
+    out.off.assign(R + 1, 0);
+    out.bytes.reserve(device.bytes.size() + device.bytes.size() / 8);
+    for (size_t r = 0; r < R; ++r) {
+        out.off[r] = out.bytes.size();
+        if (device.off[r + 1] != device.off[r]) { out.bytes.append(device.bytes, device.off[r], device.off[r + 1] - device.off[r]); continue; }
+        out.bytes += prefix[r];
+        for (const RecordText* t : texts) {
+            if (t->off[r + 1] <= t->off[r]) throw std::runtime_error("Graph::write_genotypes_of: too few likelihoods computed");
+            out.bytes += '\t';
+            out.bytes.append(t->bytes, t->off[r], t->off[r + 1] - t->off[r]);
+        }
+        out.bytes += '\n';
+    }
+    out.off[R] = out.bytes.size();
+    return out;
+}
+
 std::vector<std::string> Graph::sample_records(const std::vector<GenotypingResult>& genotyping_result, bool ignore_imputed, bool phasing,
                                                const std::vector<SampledPanel>* sampled_paths, const DeviceFields* device) const {
     const char* who = sampled_paths ? "Graph::write_sampled_panel" : phasing ? "Graph::write_phasing_of" : "Graph::write_genotypes_of";
@@ -512,36 +602,11 @@ std::vector<std::string> Graph::sample_records(const std::vector<GenotypingResul
         for (const VcfSite& site : sampled_paths ? get_variant(i).records(nullptr, &(*sampled_paths)[i])
                                                  : get_variant(i).records(device ? nullptr : &genotyping_result[i])) {
             const size_t n_all = site.alleles.size();
-            if (n_all < 2) throw std::runtime_error(std::string(who) + ": less than 2 alleles given for variant at position " + std::to_string(site.start));
-            // ALT = the defined alternative alleles; genotypes over undefined alleles are dropped below
-            std::vector<unsigned short> defined = {0};
-            std::vector<std::string> alts;
-            for (size_t a = 1; a < n_all; ++a)
-                if (!site.undefined[a]) { defined.push_back((unsigned short)a); alts.push_back(site.alleles[a]); }
-            // allele frequencies over the panel paths (without the reference path when it was added as one)
-            std::vector<float> freq(n_all, 0.0f);
-            for (unsigned short a : site.paths) freq.at(a) += 1.0f;
-            unsigned int n_paths = (unsigned int)site.paths.size();
-            if (add_reference_) { n_paths -= 1; freq[0] -= 1.0f; }
+            std::vector<unsigned short> defined;
             std::ostringstream line;
-            line << site.chromosome << '\t' << (site.start + 1) << "\t.\t" << site.alleles[0] << '\t';
-            for (size_t k = 0; k < alts.size(); ++k) line << (k ? "," : "") << alts[k];
-            line << "\t.\tPASS\tAF=";
-            for (size_t k = 1; k < defined.size(); ++k) line << (k > 1 ? "," : "") << std::setprecision(6) << freq[defined[k]] / n_paths;
-            line << ";UK=" << (sampled_paths ? (*sampled_paths)[i].unique_kmers : device ? (size_t)(*device->unique_kmers)[i] : (size_t)site.likelihoods.nr_unique_kmers())
-                 << ";MA=" << (n_all - defined.size());
-            const std::vector<std::string>& ids = variant_ids_.at(record_index);
-            if (!ids.empty()) {
-                // the ids are kept in the lexicographic order of their ALT alleles: back into ALT order
-                if (ids.size() != alts.size()) throw std::runtime_error(std::string(who) + ": number of variant ids and of ALT alleles differ");
-                std::vector<size_t> by_sequence(alts.size());
-                std::iota(by_sequence.begin(), by_sequence.end(), (size_t)0);
-                std::sort(by_sequence.begin(), by_sequence.end(), [&](size_t x, size_t y) { return alts[x] < alts[y]; });
-                std::vector<const std::string*> in_alt_order(alts.size(), nullptr);
-                for (size_t rank = 0; rank < by_sequence.size(); ++rank) in_alt_order[by_sequence[rank]] = &ids[rank];
-                line << ";ID=";
-                for (size_t k = 0; k < in_alt_order.size(); ++k) line << (k ? "," : "") << *in_alt_order[k];
-            }
+            line << fixed_columns_of(site, record_index,
+                                     sampled_paths ? (*sampled_paths)[i].unique_kmers : device ? (size_t)(*device->unique_kmers)[i] : (size_t)site.likelihoods.nr_unique_kmers(),
+                                     who, defined);
             if (sampled_paths) {
                 // every sampled haplotype's allele as its index among the defined ones
                 std::vector<int> among_defined(n_all, -1);
@@ -592,6 +657,20 @@ void Graph::write_genotypes(const std::string& filename, const RecordText& text,
     if (write_header)
         for (const std::string& h : genotypes_header(sample)) out << h << '\n';
     for (const std::string& l : records) out << l << '\n';
+}
+
+void Graph::write_genotypes(const std::string& filename, const RecordLines& lines, bool write_header, const std::vector<std::string>& samples) const {
+    const size_t R = nr_of_records();   // (throws before the file is touched)
+    if (lines.off.size() != R + 1 || lines.off[0] != 0 || lines.off[R] != lines.bytes.size())
+        throw std::runtime_error("Graph::write_genotypes_of: the record lines do not fit the graph's records");
+    for (size_t r = 0; r < R; ++r)
+        if (lines.off[r + 1] <= lines.off[r] || lines.bytes[lines.off[r + 1] - 1] != '\n')
+            throw std::runtime_error("Graph::write_genotypes_of: a record's line is empty or unfinished (genotype_cohort_record_lines finishes them)");
+    std::ofstream out(filename, write_header ? std::ios::out : std::ios::app);
+    if (!out.is_open()) throw std::runtime_error("Graph::write_genotypes_of: genotyping output file cannot be opened. Note that the filename must not contain non-existing directories.");
+    if (write_header)
+        for (const std::string& h : genotypes_header(samples)) out << h << '\n';
+    out.write(lines.bytes.data(), (std::streamsize)lines.bytes.size());
 }
 
 void Graph::write_genotypes(const std::string& filename, const RecordFields& fields, const std::vector<unsigned short>& coverage,

@@ -105,6 +105,20 @@ struct RecordText {
     std::vector<unsigned short> unique_kmers;
 };
 
+/** Whole VCF lines of a chromosome as BYTES (DESIGN.md 4e-7, C ABI pg_job_record_lines): line r — the fixed columns, one
+ *  `GT:GQ:GL:KC` column per sample behind a tab each, a newline — is bytes[off[r] .. off[r + 1]), records in
+ *  Graph::genotypes_records order.  As genotype_cohort_record_lines returns it no line is empty. */
+struct RecordLines {
+    std::vector<uint64_t> off;
+    std::string bytes;
+};
+
+/** The lines of a chromosome with those the device left to the host (length 0 in `device`) composed here: prefix[r], then
+ *  per sample a tab and its FINISHED text of the record (genotype_cohort_record_text's), a newline.  Every other line is
+ *  copied as it is.  Throws where a sample's text of such a record is empty too (fewer than three likelihoods), and on
+ *  arrays that do not fit each other. */
+RecordLines compose_record_lines(const std::vector<std::string>& prefix, const std::vector<const RecordText*>& texts, const RecordLines& device);
+
 /** `GT:GQ:GL:KC` of record q from finished record fields: what Graph::genotypes_records(fields, ...) prints of it (the rule
  *  the device's text follows).  Throws on fewer than three values and on a value that is still deferred. */
 std::string record_field_text(const RecordFields& fields, size_t q, unsigned short coverage, bool no_call);
@@ -179,6 +193,12 @@ public:
 
     /** the header lines of a genotyped VCF (reference src/graph.cpp:137-149); `date` = yyyymmdd, today when empty */
     static std::vector<std::string> genotypes_header(const std::string& sample, const std::string& date = "");
+    /** ... with one column per sample: the names joined by tabs */
+    static std::vector<std::string> genotypes_header(const std::vector<std::string>& samples, const std::string& date = "");
+    /** per record, in genotypes_records order, what a genotyped line holds in front of the sample columns:
+     *  `CHROM .. INFO\tGT:GQ:GL:KC` without a trailing tab (UK from `unique_kmers`, one entry per bubble).  It depends on the
+     *  index alone: one array per chromosome, whatever the number of samples (the prefix of pg_job_line_prefix). */
+    std::vector<std::string> genotypes_fixed_columns(const std::vector<unsigned short>& unique_kmers) const;
     /** the record lines: one per single variant, in graph order; `genotyping_result` = one (normalised) result per
      *  bubble, as HMM::get_genotyping_result() returns them */
     std::vector<std::string> genotypes_records(const std::vector<GenotypingResult>& genotyping_result, bool ignore_imputed = false) const;
@@ -199,6 +219,9 @@ public:
      *  column spliced in.  Throws where a record's text is empty: fewer than three likelihoods, or a record nobody finished. */
     std::vector<std::string> genotypes_records(const RecordText& text) const;
     void write_genotypes(const std::string& filename, const RecordText& text, bool write_header, const std::string& sample) const;
+    /** a multi-sample VCF: the header (when asked for) with the samples' names, then the lines' bytes in ONE write.  Throws on
+     *  offsets that do not fit the bytes or the graph's records, and on an empty line. */
+    void write_genotypes(const std::string& filename, const RecordLines& lines, bool write_header, const std::vector<std::string>& samples) const;
 
     /** the phasing VCF of a `-p` run (reference Graph::write_phasing, src/graph.cpp:280-412): the same fixed columns, `GT:KC`
      *  with the Viterbi haplotypes `a|b` (HMM with run_phasing; `.` for an allele of undefined sequence) */
@@ -222,6 +245,9 @@ private:
     };
     std::vector<std::string> sample_records(const std::vector<GenotypingResult>& genotyping_result, bool ignore_imputed, bool phasing,
                                             const std::vector<SampledPanel>* sampled_paths = nullptr, const DeviceFields* device = nullptr) const;
+    /** CHROM .. INFO of one record (the ONE place that forms them): `defined` comes back as the record's defined alleles */
+    std::string fixed_columns_of(const VcfSite& site, size_t record_index, size_t unique_kmers, const char* who, std::vector<unsigned short>& defined) const;
+    size_t nr_of_records() const;
     std::vector<std::pair<std::string, std::shared_ptr<DnaSequence>>> fasta_;   // name -> sequence, archive (= sorted) order
     std::string chromosome_;
     size_t kmer_size_ = 0;
@@ -280,6 +306,18 @@ std::vector<std::map<std::string, SampledRecordFields>> genotype_cohort_sampled_
  *  genotype_cohort_record_fields finishes them and printed by record_field_text.  Graph::genotypes_records(text) gives the
  *  lines of Graph::genotypes_records(fields, coverage, unique_kmers, ignore_imputed) on the sibling's output. */
 std::vector<std::map<std::string, RecordText>> genotype_cohort_record_text(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false,
+    long double effective_N = 25000.0L, int device = 0, bool ignore_imputed = false);
+
+/** genotype_cohort_record_text with the LINES joined on the device too: the same job and the record text,
+ *  one pg_job_line_prefix per chromosome (Graph::genotypes_fixed_columns: formed and uploaded once, whatever the number of
+ *  samples), pg_job_record_lines and ONE packed fetch.  Per chromosome the multi-sample lines, sample s in column 9 + s; a
+ *  line the device left to the host is composed here from the prefix and the finished texts (compose_record_lines), so no
+ *  line is empty; a record of fewer than three values throws.  Throws if the samples' unique k-mer counts of a chromosome
+ *  differ: a multi-sample line has one INFO column (over a shared index they cannot).  Not covered: sampled cohorts (UK and
+ *  the reduced panels differ per sample: the C ABI gives them single-member lines), the combined (-a) records, phasing. */
+std::map<std::string, RecordLines> genotype_cohort_record_lines(
     std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
     const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false,
     long double effective_N = 25000.0L, int device = 0, bool ignore_imputed = false);

@@ -1151,7 +1151,7 @@ static int chain_record_text(pg_job* job, uint32_t chain, const Graph& graph, co
 static std::vector<std::map<std::string, RecordFields>> cohort_record_fields(
     std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
     const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device,
-    bool ignore_imputed, bool with_gl, std::vector<std::map<std::string, RecordText>>* text = nullptr) {
+    bool ignore_imputed, bool with_gl, std::vector<std::map<std::string, RecordText>>* text = nullptr, std::map<std::string, RecordLines>* lines = nullptr) {
     const size_t C = chromosomes.size(), S = samples.size();
     std::vector<std::map<std::string, RecordFields>> out(S);
     if (text) text->assign(S, {});
@@ -1255,6 +1255,47 @@ static std::vector<std::map<std::string, RecordFields>> cohort_record_fields(
                         [&](size_t v) { return any_column[c] ? cov_rows[s][c][v] : (uint16_t)0; },
                         [&](std::vector<GenotypingResult>* full) { return results_of(s, c, full); }, t, err, sizeof(err));
                 }
+            if (lines && rc == PG_OK) {   // the lines joined on the device: a prefix per chromosome, one launch, one packed copy
+                std::vector<std::vector<std::string>> fixed(C);
+                for (c = 0; c < C && rc == PG_OK; ++c) {
+                    const std::vector<unsigned short>& uk = (*text)[0][names[c]].unique_kmers;
+                    for (size_t s = 1; s < S; ++s)
+                        if ((*text)[s][names[c]].unique_kmers != uk) fail("genotype_cohort_record_lines: the samples' unique k-mer counts differ on " + names[c]);
+                    fixed[c] = graph_of[c]->genotypes_fixed_columns(uk);
+                    std::vector<uint64_t> poff(fixed[c].size() + 1, 0);
+                    std::string pbytes;
+                    for (size_t r = 0; r < fixed[c].size(); ++r) { pbytes += fixed[c][r]; poff[r + 1] = pbytes.size(); }
+                    rc = pg_job_line_prefix(job, (uint32_t)c, poff.data(), pbytes.empty() ? nullptr : pbytes.data(), err, sizeof(err));
+                }
+                if (rc == PG_OK) rc = pg_job_record_lines(job, err, sizeof(err));
+                std::vector<uint64_t> line_first(C + 1, 0), byte_first(C + 1, 0), loff;
+                std::string lbytes;
+                uint64_t n_index = 0;
+                if (rc == PG_OK) rc = pg_job_record_lines_first(job, &n_index, nullptr, nullptr, err, sizeof(err));
+                if (rc == PG_OK && n_index != C) { std::snprintf(err, sizeof(err), "genotype_cohort_record_lines: the job has %llu index contigs, not %zu", (unsigned long long)n_index, C); rc = PG_ERR_INVALID; }
+                if (rc == PG_OK) rc = pg_job_record_lines_first(job, nullptr, line_first.data(), byte_first.data(), err, sizeof(err));
+                if (rc == PG_OK) {
+                    loff.assign(line_first.back() + 1, 0);
+                    lbytes.assign(byte_first.back(), '\0');
+                    rc = pg_job_fetch_record_lines_packed(job, loff.data(), lbytes.empty() ? nullptr : &lbytes[0], lbytes.size(), err, sizeof(err));
+                }
+                for (c = 0; c < C && rc == PG_OK; ++c) {
+                    const size_t R = fixed[c].size();
+                    RecordLines dev;
+                    dev.off.assign(R + 1, 0);
+                    if (line_first[c + 1] - line_first[c] == R) {   // (a chromosome without records has no lines on the device)
+                        for (size_t r = 0; r <= R; ++r) dev.off[r] = loff[line_first[c] + r] - byte_first[c];
+                        dev.bytes.assign(lbytes, byte_first[c], byte_first[c + 1] - byte_first[c]);
+                    } else if (R != 0 || line_first[c + 1] != line_first[c]) {
+                        std::snprintf(err, sizeof(err), "genotype_cohort_record_lines: chromosome %zu holds other lines than its plan's records", c);
+                        rc = PG_ERR_INVALID;
+                        break;
+                    }
+                    std::vector<const RecordText*> texts(S);
+                    for (size_t s = 0; s < S; ++s) texts[s] = &(*text)[s][names[c]];
+                    (*lines)[names[c]] = compose_record_lines(fixed[c], texts, dev);
+                }
+            }
         } catch (...) {
             pg_job_destroy(job);
             throw;
@@ -1324,6 +1365,16 @@ std::vector<std::map<std::string, RecordText>> genotype_cohort_record_text(
     std::vector<std::map<std::string, RecordText>> text;
     cohort_record_fields(chromosomes, graphs, samples, probabilities, recombrate, uniform, effective_N, device, ignore_imputed, true, &text);
     return text;
+}
+
+std::map<std::string, RecordLines> genotype_cohort_record_lines(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device,
+    bool ignore_imputed) {
+    std::vector<std::map<std::string, RecordText>> text;
+    std::map<std::string, RecordLines> lines;
+    cohort_record_fields(chromosomes, graphs, samples, probabilities, recombrate, uniform, effective_N, device, ignore_imputed, true, &text, &lines);
+    return lines;
 }
 
 // ------------------------------------------------------------------ path subsets, the sample column per VCF record
