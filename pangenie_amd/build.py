@@ -64,6 +64,9 @@ def build_oracle(force: bool = False) -> Path:
 
 
 HOST_DIR = ROOT / "pangenie_amd" / "host"
+# the one list of the host library's units: the library and the sanitizer build of tests/test_host_cpp.py compile these
+HOST_SOURCES = [HOST_DIR / "pangenie_host.cpp", HOST_DIR / "cohort.cpp", HOST_DIR / "cereal_io.cpp", HOST_DIR / "kmer_counts.cpp", HOST_DIR / "graph_io.cpp",
+                HOST_DIR / "index_builder.cpp"]
 HOST_LIB = HOST_DIR / "libpangenie_host.so"
 HOST_TEST = ROOT / "tests" / "cpp" / "test_host.bin"
 HOST_MOCK_TEST = ROOT / "tests" / "cpp" / "test_multi_gpu_mock.bin"
@@ -76,8 +79,8 @@ def build_host(force: bool = False) -> Path:
     cxx = shutil.which("g++") or "g++"
     deps = sorted(HOST_DIR.glob("*.cpp")) + sorted(HOST_DIR.glob("*.hpp")) + sorted((ROOT / "include").glob("*.h"))
     if force or _stale(HOST_LIB, deps):
-        cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", str(HOST_DIR / "pangenie_host.cpp"), str(HOST_DIR / "cereal_io.cpp"),
-               str(HOST_DIR / "kmer_counts.cpp"), str(HOST_DIR / "graph_io.cpp"), str(HOST_DIR / "index_builder.cpp"), "-o", str(HOST_LIB), f"-L{CSRC}", "-lpangenie_hmm", "-lpthread", "-lz", "-Wl,-rpath,$ORIGIN/../csrc"]
+        cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", *map(str, HOST_SOURCES), "-o", str(HOST_LIB), f"-L{CSRC}", "-lpangenie_hmm", "-lpthread", "-lz",
+               "-Wl,-rpath,$ORIGIN/../csrc"]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode:
             raise RuntimeError("g++ (host lib) failed:\n" + r.stderr)

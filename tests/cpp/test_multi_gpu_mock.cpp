@@ -6,6 +6,9 @@
 // reassembly of every task's GenotypingResults.  The mock "posterior" of a genotype bin is a function of (the
 // contig's first position, variant count, bin index) alone, so the expected likelihood of every (task, variant,
 // genotype) is known whatever device the task was planned on.  What stays untested without hardware is RCCL itself.
+// The same seam carries the cohort drivers (pg_cohort_new, pg_job_calls, pg_job_fetch_calls_all): genotype_cohort and
+// genotype_cohort_calls with chosen variants flagged PG_CALL_DEFERRED and with a fetch made to fail, so that the host's
+// deferred path and the ownership of the job (the count of live jobs) run without a GPU.
 // Test infrastructure (tests/ only).  Reference: the job loop of src/commands.cpp:955-978.
 #include <math.h>
 #include <stdint.h>
@@ -16,6 +19,8 @@
 #include <memory>
 #include <mutex>
 #include <set>
+#include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "../../include/pangenie_hmm.h"
@@ -26,9 +31,10 @@ struct pg_job {
     int device = 0;
     std::vector<pg_contig_batch> batches;
     std::vector<std::vector<uint64_t>> goff;
+    std::vector<uint64_t> keys;     // per chain: what its bins are a function of
     std::vector<double> lik;        // packed, chain after chain
     std::vector<int32_t> lexp;
-    bool ran = false;
+    bool ran = false, calls = false;
 };
 struct pg_comm { int rank = 0, device = 0; };
 
@@ -36,6 +42,10 @@ static std::mutex g_mu;
 static std::vector<std::pair<int, uint32_t>> g_jobs_made;   // (device, chains)
 static int g_gathers = 0, g_fetches = 0;
 static std::vector<uint64_t> g_last_plan;
+static int g_live = 0;                                      // jobs made and not yet destroyed
+static std::set<std::pair<uint32_t, uint32_t>> g_deferred;  // (chain, variant): pg_job_fetch_calls_all flags these PG_CALL_DEFERRED
+static int g_fail_fetch = 0;                                // the n-th pg_job_fetch from now (1 = the next) returns PG_ERR_INVALID; 0 = none
+static bool g_fail_calls_fetch = false;                     // pg_job_fetch_calls_all returns PG_ERR_INVALID
 
 static void mock_bin(uint64_t key, uint64_t g, double& m, int32_t& e) {   // deterministic, device independent
     uint64_t x = key * 0x9E3779B97F4A7C15ull + g * 0xD1B54A32D192ED03ull + 12345;
@@ -44,33 +54,77 @@ static void mock_bin(uint64_t key, uint64_t g, double& m, int32_t& e) {   // det
     e = -(int32_t)(x % 37);
 }
 static uint64_t key_of(const pg_contig_batch& b) { return b.n_variants ? (uint64_t)b.variant_pos[0] * 1000003ull + b.n_variants : 7; }
+static uint64_t cohort_key(const pg_contig_batch& b, uint32_t sample) { return key_of(b) + 0x51ED27ull * (sample + 1); }   // (every sample its own bins)
+
+static pg_job* mock_job(int device, const std::vector<pg_contig_batch>& chains, const std::vector<uint64_t>& keys) {
+    pg_job* j = new pg_job;
+    j->device = device;
+    j->batches = chains;
+    j->keys = keys;
+    for (const pg_contig_batch& b : chains) {
+        std::vector<uint64_t> g((size_t)b.n_variants + 1, 0);
+        pg_hmm_geno_offsets(&b, g.data());
+        j->goff.push_back(g);
+    }
+    { std::lock_guard<std::mutex> lk(g_mu); g_jobs_made.push_back({device, (uint32_t)chains.size()}); g_live += 1; }
+    return j;
+}
+
+// variant v of a chain as the host rebuilds it from the job's bins (kept columns and allele presence by the ColumnIndexer rule)
+static pangenie::GenotypingResult mock_result(const pg_job* j, uint32_t chain, uint32_t v) {
+    const pg_contig_batch& b = j->batches[chain];
+    uint64_t base = 0;
+    for (uint32_t c = 0; c < chain; ++c) base += j->goff[c].back();
+    const uint32_t a0 = b.allele_off[v], A = b.allele_off[v + 1] - a0, H = b.n_paths;
+    std::vector<char> present(A, 0);
+    bool kept = false;
+    for (uint32_t p = 0; p < H; ++p)
+        for (uint32_t q = 0; q < A; ++q)
+            if (b.allele_id[a0 + q] == b.path_allele[(size_t)v * H + p]) { present[q] = 1; if (b.allele_id[a0 + q] != 0 && !(b.allele_flags[a0 + q] & 1)) kept = true; }
+    pangenie::GenotypingResult r;
+    for (uint32_t x = 0; x < A && kept; ++x)
+        for (uint32_t y = x; y < A; ++y) {
+            if (!present[x] || !present[y]) continue;
+            const uint64_t idx = base + j->goff[chain][v] + (uint64_t)x * A - (uint64_t)x * (x - 1) / 2 + (y - x);
+            r.add_to_likelihood(b.allele_id[a0 + x], b.allele_id[a0 + y], ldexpl((long double)j->lik[idx], j->lexp[idx]));
+        }
+    return r;
+}
 
 extern "C" {
 int pg_job_new(int device, uint32_t n_contigs, const pg_contig_batch* batches, const pg_table*, const pg_hmm_params* p, pg_job** out, char*, size_t) {
     if (!p || !p->run_genotyping) return PG_ERR_INVALID;
-    pg_job* j = new pg_job;
-    j->device = device;
-    j->batches.assign(batches, batches + n_contigs);
-    for (uint32_t c = 0; c < n_contigs; ++c) {
-        std::vector<uint64_t> g((size_t)batches[c].n_variants + 1, 0);
-        pg_hmm_geno_offsets(&batches[c], g.data());
-        j->goff.push_back(g);
-    }
-    { std::lock_guard<std::mutex> lk(g_mu); g_jobs_made.push_back({device, n_contigs}); }
-    *out = j;
+    std::vector<uint64_t> keys;
+    for (uint32_t c = 0; c < n_contigs; ++c) keys.push_back(key_of(batches[c]));
+    *out = mock_job(device, std::vector<pg_contig_batch>(batches, batches + n_contigs), keys);
+    return PG_OK;
+}
+// chain = sample * n_contigs + contig, over the index contig's batch
+int pg_cohort_new(int device, uint32_t n_contigs, const pg_contig_batch* index, uint32_t n_samples, const pg_sample_counts* samples, const pg_table*,
+                  const pg_hmm_params* p, pg_job** out, char*, size_t) {
+    if (!p || !p->run_genotyping || !samples) return PG_ERR_INVALID;
+    std::vector<pg_contig_batch> chains;
+    std::vector<uint64_t> keys;
+    for (uint32_t s = 0; s < n_samples; ++s)
+        for (uint32_t c = 0; c < n_contigs; ++c) { chains.push_back(index[c]); keys.push_back(cohort_key(index[c], s)); }
+    *out = mock_job(device, chains, keys);
     return PG_OK;
 }
 int pg_job_run(pg_job* j, void*, char*, size_t) {
     j->lik.clear(); j->lexp.clear();
     for (size_t c = 0; c < j->batches.size(); ++c) {
-        const uint64_t n = j->goff[c].back(), key = key_of(j->batches[c]);
+        const uint64_t n = j->goff[c].back(), key = j->keys[c];
         for (uint64_t g = 0; g < n; ++g) { double m; int32_t e; mock_bin(key, g, m, e); j->lik.push_back(m); j->lexp.push_back(e); }
     }
     j->ran = true;
     return PG_OK;
 }
-int pg_job_fetch(pg_job* j, uint32_t ci, pg_contig_result* out, char*, size_t) {
+int pg_job_fetch(pg_job* j, uint32_t ci, pg_contig_result* out, char* err, size_t errlen) {
     if (!j->ran || ci >= j->batches.size()) return PG_ERR_INVALID;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        if (g_fail_fetch > 0 && --g_fail_fetch == 0) { snprintf(err, errlen, "mock: the fetch of chain %u is refused", ci); return PG_ERR_INVALID; }
+    }
     uint64_t off = 0;
     for (uint32_t c = 0; c < ci; ++c) off += j->goff[c].back();
     const uint64_t n = j->goff[ci].back();
@@ -79,7 +133,34 @@ int pg_job_fetch(pg_job* j, uint32_t ci, pg_contig_result* out, char*, size_t) {
     { std::lock_guard<std::mutex> lk(g_mu); g_fetches += 1; }
     return PG_OK;
 }
-void pg_job_destroy(pg_job* j) { delete j; }
+int pg_job_calls(pg_job* j, char*, size_t) {
+    if (!j->ran) return PG_ERR_INVALID;
+    j->calls = true;
+    return PG_OK;
+}
+// every variant's call from the mock's own bins, as GenotypingResult gives it; the variants of g_deferred are left to the host
+int pg_job_fetch_calls_all(pg_job* j, pg_call* const* outs, char* err, size_t errlen) {
+    if (!j->calls) return PG_ERR_INVALID;
+    if (g_fail_calls_fetch) { snprintf(err, errlen, "mock: the fetch of the calls is refused"); return PG_ERR_INVALID; }
+    for (uint32_t chain = 0; chain < j->batches.size(); ++chain)
+        for (uint32_t v = 0; v < j->batches[chain].n_variants; ++v) {
+            pg_call& c = outs[chain][v];
+            c.allele_1 = c.allele_2 = 0xFFFF; c.gq = 0; c.flags = PG_CALL_NONE;
+            if (g_deferred.count({chain, v})) { c.flags = PG_CALL_DEFERRED; continue; }
+            pangenie::GenotypingResult r = mock_result(j, chain, v);
+            r.normalize();
+            const std::pair<int, int> g = r.get_likeliest_genotype();
+            if (g.first < 0 || g.second < 0) continue;
+            c.allele_1 = (uint16_t)g.first; c.allele_2 = (uint16_t)g.second; c.flags = PG_CALL_OK;
+            c.gq = (uint16_t)r.get_genotype_quality((unsigned short)g.first, (unsigned short)g.second);
+        }
+    return PG_OK;
+}
+void pg_job_destroy(pg_job* j) {
+    if (!j) return;
+    { std::lock_guard<std::mutex> lk(g_mu); g_live -= 1; }
+    delete j;
+}
 int pg_comm_init_all(int n, const int* devices, pg_comm** out, char*, size_t) {
     for (int i = 0; i < n; ++i) { out[i] = new pg_comm; out[i]->rank = i; out[i]->device = devices[i]; }
     return PG_OK;
@@ -128,6 +209,108 @@ static std::vector<std::shared_ptr<UniqueKmers>> make_contig(size_t V, unsigned 
     return out;
 }
 
+// ------------------------------------------------------------------ the cohort drivers over the same seam
+// 2 samples x 3 chromosomes of 5, 0 and 17 variants (a short chain, an empty one, one with multi-allelic sites):
+// chain = sample * 3 + chromosome; the chromosomes in the order of their names.
+template <class F>
+static std::string thrown_by(F f) {
+    try { f(); } catch (const std::exception& e) { return e.what(); }
+    return "";
+}
+
+static void test_cohort(ProbabilityTable& table) {
+    const size_t sizes[] = {5, 0, 17};
+    const char* names[] = {"chrA", "chrB", "chrC"};
+    const unsigned H = 6;
+    const size_t C = 3, S = 2;
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>> chromosomes;
+    for (size_t c = 0; c < C; ++c) chromosomes[names[c]] = make_contig(sizes[c], H, 5000 + 1000000 * c, 40 + (unsigned)c);
+    std::vector<SampleCounts> samples(S, SampleCounts::of(chromosomes));
+    for (auto& kv : samples[1].coverage) for (uint16_t& x : kv.second) x += 7;   // (every sample its own rows)
+    auto reset = [&] { std::lock_guard<std::mutex> lk(g_mu); g_jobs_made.clear(); g_fetches = 0; g_live = 0; g_deferred.clear(); g_fail_fetch = 0; g_fail_calls_fetch = false; };
+
+    // (a) genotype_cohort: every chain's bins as the mock made them, the sample's own coverage, no job left
+    reset();
+    const auto results = genotype_cohort(chromosomes, samples, &table, 1.26, false, 25000.0L, 0);
+    printf("genotype_cohort: %zu job(s), %d fetch(es), %d live\n", g_jobs_made.size(), g_fetches, g_live);
+    CHECK(results.size() == S && g_jobs_made.size() == 1 && g_jobs_made[0].second == S * C && g_fetches == (int)(S * C) && g_live == 0);
+    for (size_t s = 0; s < S && results.size() == S; ++s)
+        for (size_t c = 0; c < C; ++c) {
+            const std::vector<GenotypingResult>& got = results[s].at(names[c]);
+            CHECK(got.size() == sizes[c]);
+            FlatContig f;
+            flatten(&chromosomes[names[c]], nullptr, f);
+            std::vector<uint64_t> goff(sizes[c] + 1, 0);
+            pg_hmm_geno_offsets(&f.batch, goff.data());
+            for (size_t v = 0; v < got.size(); ++v) {
+                const uint32_t a0 = f.allele_off[v], A = f.allele_off[v + 1] - a0;
+                CHECK(got[v].coverage() == samples[s].coverage.at(names[c])[v] && got[v].nr_unique_kmers() == 6);
+                for (uint32_t ia = 0; ia < A; ++ia)
+                    for (uint32_t ib = ia; ib < A; ++ib) {
+                        const unsigned short a = f.allele_id[a0 + ia], b = f.allele_id[a0 + ib];
+                        double m; int32_t e;
+                        mock_bin(cohort_key(f.batch, (uint32_t)s), goff[v] + (uint64_t)ia * A - (uint64_t)ia * (ia - 1) / 2 + (ib - ia), m, e);
+                        bool pa = false, pb = false;   // (alleles no path carries have no bin: 0)
+                        for (unsigned p = 0; p < H; ++p) { pa = pa || f.path_allele[v * H + p] == a; pb = pb || f.path_allele[v * H + p] == b; }
+                        CHECK(got[v].get_genotype_likelihood(a, b) == (pa && pb ? ldexpl((long double)m, e) : 0.0L));
+                    }
+            }
+        }
+
+    // (b) genotype_cohort_calls with variant 2 of chain 0 and the first and last variant of chain 5 left to the host: every call
+    // is what normalize / get_likeliest_genotype / get_genotype_quality give on (a)'s element; only those two chains' bins are fetched
+    const std::set<std::pair<uint32_t, uint32_t>> flagged = {{0, 2}, {5, 0}, {5, 16}};
+    reset();
+    g_deferred = flagged;
+    const auto calls = genotype_cohort_calls(chromosomes, samples, &table, 1.26, false, 25000.0L, 0);
+    printf("genotype_cohort_calls: %zu job(s), %d fetch(es), %d live\n", g_jobs_made.size(), g_fetches, g_live);
+    CHECK(calls.size() == S && g_jobs_made.size() == 1 && g_fetches == 2 && g_live == 0);
+    size_t n_deferred = 0;
+    for (size_t s = 0; s < S && calls.size() == S && results.size() == S; ++s)
+        for (size_t c = 0; c < C; ++c) {
+            const std::vector<GenotypeCall>& got = calls[s].at(names[c]);
+            CHECK(got.size() == sizes[c]);
+            for (size_t v = 0; v < got.size(); ++v) {
+                GenotypingResult r = results[s].at(names[c])[v];
+                r.normalize();
+                const std::pair<int, int> g = r.get_likeliest_genotype();
+                GenotypeCall want;
+                if (g.first >= 0 && g.second >= 0) { want.allele_1 = g.first; want.allele_2 = g.second; want.quality = r.get_genotype_quality((unsigned short)g.first, (unsigned short)g.second); }
+                CHECK(got[v].allele_1 == want.allele_1 && got[v].allele_2 == want.allele_2 && got[v].quality == want.quality);
+                CHECK(got[v].deferred == (flagged.count({(uint32_t)(s * C + c), (uint32_t)v}) > 0));
+                n_deferred += got[v].deferred;
+            }
+        }
+    CHECK(n_deferred == flagged.size());
+
+    // (c) a refused fetch — of the first chain's bins, of the last chain's, of the calls — is thrown with its text, and no job is left
+    for (int nth : {1, (int)(S * C)}) {
+        reset();
+        g_fail_fetch = nth;
+        const std::string what = thrown_by([&] { genotype_cohort(chromosomes, samples, &table, 1.26, false, 25000.0L, 0); });
+        CHECK(what == "mock: the fetch of chain " + std::to_string(nth - 1) + " is refused" && g_jobs_made.size() == 1 && g_live == 0);
+    }
+    for (int nth : {1, 2}) {   // (the two chains with a deferred variant are the first and the last)
+        reset();
+        g_deferred = flagged;
+        g_fail_fetch = nth;
+        const std::string what = thrown_by([&] { genotype_cohort_calls(chromosomes, samples, &table, 1.26, false, 25000.0L, 0); });
+        CHECK(what == std::string("mock: the fetch of chain ") + (nth == 1 ? "0" : "5") + " is refused" && g_jobs_made.size() == 1 && g_live == 0);
+    }
+    reset();
+    g_fail_calls_fetch = true;
+    CHECK(thrown_by([&] { genotype_cohort_calls(chromosomes, samples, &table, 1.26, false, 25000.0L, 0); }) == "mock: the fetch of the calls is refused");
+    CHECK(g_jobs_made.size() == 1 && g_live == 0 && g_fetches == 0);
+
+    // (d) a sample whose counts do not fit the index is refused before any job is made
+    reset();
+    std::vector<SampleCounts> unfit = samples;
+    unfit[1].kmer_count["chrC"].pop_back();
+    CHECK(thrown_by([&] { genotype_cohort(chromosomes, unfit, &table, 1.26, false, 25000.0L, 0); }) == "genotype_cohort: sample 1 does not fit the index on chrC");
+    CHECK(g_jobs_made.empty() && g_live == 0);
+    reset();
+}
+
 int main() {
     const size_t sizes[] = {40, 5, 23, 0, 17, 31, 9, 12, 28};
     const unsigned paths[] = {6, 4, 8, 4, 6, 5, 4, 7, 6};
@@ -154,7 +337,7 @@ int main() {
         const std::vector<std::vector<GenotypingResult>> out = run(devices);
         const size_t D = devices.size();
         printf("%zu device(s): %zu job(s), %d gather(s), %d fetch(es)\n", D, g_jobs_made.size(), g_gathers, g_fetches);
-        CHECK(out.size() == T);
+        CHECK(out.size() == T && g_live == 0);   // (every device's job is destroyed)
         // one job per device that got tasks, every task in exactly one job, ONE exchange (none on a single device)
         uint32_t chains = 0;
         std::set<int> used;
@@ -191,6 +374,7 @@ int main() {
             }
         }
     }
+    test_cohort(table);
     printf("%d checks, %d failed\n", g_checks, g_failed);
     return g_failed ? 1 : 0;
 }

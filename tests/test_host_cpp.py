@@ -22,7 +22,10 @@ def test_multi_gpu_job_loop_with_the_device_mocked_at_the_c_abi(binary):
     """pangenie::run_contigs_multi_gpu on 1 / 2 / 3 / 8 / 12 'devices' without a GPU: pg_job_* / pg_comm_* /
     pg_hmm_gather_to_host are replaced at the C-ABI seam (tests/cpp/test_multi_gpu_mock.cpp), so the plan (longest
     processing time first), one job per device, the ONE exchange with its block sizes, and the reassembly of every
-    task's GenotypingResults run for real; what is left untested without hardware is RCCL itself."""
+    task's GenotypingResults run for real; what is left untested without hardware is RCCL itself.  Over the same seam
+    genotype_cohort and genotype_cohort_calls on 2 samples x 3 chromosomes: the mock's bins per chain, calls with chosen
+    variants left to the host (PG_CALL_DEFERRED), a refused fetch thrown with its text, a sample that does not fit, and
+    after each of them no job left alive."""
     r = subprocess.run([str(build.HOST_MOCK_TEST)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and " 0 failed" in r.stdout, r.stdout + r.stderr
 
@@ -35,11 +38,9 @@ def test_host_classes_cpu_under_sanitizers(binary, tmp_path):
     cxx = shutil.which("g++")
     if cxx is None:
         pytest.skip("no g++")
-    host = build.ROOT / "pangenie_amd" / "host"
     exe = tmp_path / "test_host_san"
     cmd = [cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined",
-           str(build.ROOT / "tests" / "cpp" / "test_host.cpp"), str(host / "pangenie_host.cpp"), str(host / "cereal_io.cpp"),
-           str(host / "kmer_counts.cpp"), str(host / "graph_io.cpp"), str(host / "index_builder.cpp"), "-o", str(exe),
+           str(build.ROOT / "tests" / "cpp" / "test_host.cpp"), *map(str, build.HOST_SOURCES), "-o", str(exe),
            f"-L{build.ROOT / 'pangenie_amd' / 'csrc'}", "-lpangenie_hmm", "-lz", "-lpthread", f"-Wl,-rpath,{build.ROOT / 'pangenie_amd' / 'csrc'}"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     if r.returncode != 0 and "sanitize" in r.stderr:
