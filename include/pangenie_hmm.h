@@ -629,6 +629,43 @@ int  pg_record_lines_from_text(int device, uint64_t n_records, uint64_t n_member
                                const uint64_t* prefix_off, const char* prefix, uint64_t* out_off, char* out, uint64_t cap);
 
 /* ------------------------------------------------------------------ *
+ *  SLOTTED prefixes: the lines of sampled cohorts.  There every chain is an index contig of its own,
+ *  and the fixed columns of the chains of one chromosome differ in one number only: UK, the k-mer count of the record's
+ *  bubble in the chain's reduced panel.  A slotted prefix is a prefix and slot[R] with 0 <= slot[r] <= len(prefix[r]);
+ *  the line of record r is
+ *      prefix[r][0 : slot[r]]  dec(UK)  prefix[r][slot[r] :]  ('\t' text_s[r]) for every member s in order  '\n'
+ *  with UK the value pg_job_fetch reports in n_kmers[v] for the bubble v of record r (the plan's rec_var) of the index
+ *  contig's FIRST member chain — 0 for a chain without a kept column, 16 bits — and dec its decimal digits without
+ *  leading zeros, "0" for 0.  Everything else is the rule above.  slot == NULL: a plain prefix.  A job with at least
+ *  one slotted prefix among the index contigs that take part forms all its lines through pg_record_lines_slot.hip's
+ *  kernels (a plain prefix gives the same bytes there); a job without one through pg_record_lines.hip's, as before.
+ *  Not covered: the combined (-a) record families, the phasing column.
+ * ------------------------------------------------------------------ */
+/* pg_record_lines_bound(...) + 5 n_records: an upper bound (UK has at most 5 digits).  Host only. */
+uint64_t pg_record_lines_bound_slotted(uint64_t n_records, uint64_t n_members, uint64_t prefix_bytes, uint64_t text_bytes);
+/* pg_job_line_prefix with slot[R] (or NULL: pg_job_line_prefix itself).  Also PG_ERR_INVALID: slot[r] > off[r + 1] -
+ * off[r]. */
+int  pg_job_line_prefix_slotted(pg_job* job, uint32_t index_contig, const uint64_t* off, const char* bytes, const uint32_t* slot, char* err,
+                                size_t errlen);
+/* ONE prefix, checked once, uploaded once and reference-counted, for every index contig ix with ix % n_contigs ==
+ * contig, as pg_job_record_plan_strided shares the record plan; slot may be NULL.  PG_ERR_INVALID: the refusals of
+ * pg_job_record_plan_strided (n_contigs == 0, contig >= n_contigs, index contigs that are no multiple of n_contigs),
+ * those of pg_job_line_prefix for any member (no record plan; plans of the members that differ in their number of
+ * records), and slot[r] > off[r + 1] - off[r].  Nothing is attached on a refusal.  A later pg_job_line_prefix on one
+ * member replaces that member's reference alone; a new record plan or index for a member drops its reference.  The
+ * lines are stale after it. */
+int  pg_job_line_prefix_strided(pg_job* job, uint32_t contig, uint32_t n_contigs, const uint64_t* off, const char* bytes, const uint32_t* slot, char* err,
+                                size_t errlen);
+/* Unit entry point: pg_record_lines_from_text over a slotted prefix with UK of record r = uk[r], always through
+ * pg_record_lines_slot.hip's kernels.  slot == NULL (uk is then not read): a plain prefix, the bytes and offsets of
+ * pg_record_lines_from_text.  PG_ERR_INVALID, before any device is asked for: the refusals of pg_record_lines_from_text
+ * (cap: below pg_record_lines_bound_slotted with slots, below pg_record_lines_bound without), slot without uk,
+ * slot[r] > prefix_off[r + 1] - prefix_off[r]. */
+int  pg_record_lines_from_text_slotted(int device, uint64_t n_records, uint64_t n_members, const uint64_t* const* off, const char* const* text,
+                                       const uint64_t* prefix_off, const char* prefix, const uint32_t* slot, const uint16_t* uk, uint64_t* out_off,
+                                       char* out, uint64_t cap);
+
+/* ------------------------------------------------------------------ *
  *  Path subsets: the chains of one contig over different path selections combined on the device, and the calls
  *  from the sums (pangenie_amd/csrc/pg_combine.hip).  The reference's `-a` option genotypes a
  *  chromosome once per subset of paths, adds the subsets' UNNORMALISED likelihoods per genotype

@@ -335,6 +335,15 @@ def _bind_hip(lib):
     lib.pg_job_record_lines_ms.restype = C.c_double
     lib.pg_record_lines_from_text.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     lib.pg_record_lines_from_text.restype = C.c_int
+    lib.pg_record_lines_bound_slotted.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
+    lib.pg_record_lines_bound_slotted.restype = C.c_uint64
+    lib.pg_job_line_prefix_slotted.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_line_prefix_slotted.restype = C.c_int
+    lib.pg_job_line_prefix_strided.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_line_prefix_strided.restype = C.c_int
+    lib.pg_record_lines_from_text_slotted.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_uint64]
+    lib.pg_record_lines_from_text_slotted.restype = C.c_int
     # path subsets combined on the device (pangenie_amd/calls.py); bins are read as numpy arrays of COMBINED_DTYPE
     lib.pg_job_combine_plan.argtypes = [C.c_void_p, C.c_uint32, u32p, u32p, C.c_char_p, C.c_size_t]
     lib.pg_job_combine_plan.restype = C.c_int
@@ -413,6 +422,7 @@ HIP_ABI_SYMBOLS = [
     "pg_job_device_record_text", "pg_job_record_text_ms", "pg_job_record_text_emit_ms", "pg_record_text_from_fields",
     "pg_record_lines_bound", "pg_job_line_prefix", "pg_job_record_lines", "pg_job_record_lines_first", "pg_job_fetch_record_lines",
     "pg_job_fetch_record_lines_packed", "pg_job_device_record_lines", "pg_job_record_lines_ms", "pg_record_lines_from_text",
+    "pg_record_lines_bound_slotted", "pg_job_line_prefix_slotted", "pg_job_line_prefix_strided", "pg_record_lines_from_text_slotted",
 ]
 
 

@@ -476,16 +476,49 @@ def _as_bytes(data) -> np.ndarray:
     return np.ascontiguousarray(data, np.uint8)
 
 
-def job_line_prefix(job, contig: int, off, data) -> None:
-    """pg_job_line_prefix: the fixed columns of index contig `contig`, record r's = data[off[r]:off[r + 1]]."""
+def record_lines_bound_slotted(n_records: int, n_members: int, prefix_bytes: int, text_bytes: int) -> int:
+    """pg_record_lines_bound_slotted: record_lines_bound + 5 n_records, an upper bound (UK has at most 5 digits)."""
+    return int(_lib.load_hip().pg_record_lines_bound_slotted(int(n_records), int(n_members), int(prefix_bytes), int(text_bytes)))
+
+
+def _prefix_arrays(job, what: str, contig: int, off, data, slot):
+    """the arrays of a prefix as the C ABI reads them (it reads R + 1 offsets and R slots: it cannot see a wrong R)"""
     oo, bb = np.ascontiguousarray(off, np.uint64), _as_bytes(data)
     plans = getattr(job, "_record_plans", {})
-    if contig in plans and len(oo) != plans[contig].n_records + 1:   # (the C ABI reads R + 1 offsets: it cannot see a wrong R)
-        raise ValueError("line_prefix: %d offsets for a plan of %d records" % (len(oo), plans[contig].n_records))
+    if contig in plans and len(oo) != plans[contig].n_records + 1:
+        raise ValueError("%s: %d offsets for a plan of %d records" % (what, len(oo), plans[contig].n_records))
     if len(oo) and int(oo[-1]) > len(bb):
-        raise ValueError("line_prefix: the offsets end behind the bytes")
+        raise ValueError("%s: the offsets end behind the bytes" % what)
+    ss = None
+    if slot is not None:
+        ss = np.ascontiguousarray(slot, np.uint32)
+        if len(ss) + 1 != len(oo):
+            raise ValueError("%s: %d slots for %d offsets" % (what, len(ss), len(oo)))
+        ss = np.concatenate([ss, np.zeros(1, np.uint32)])   # (never empty: a null pointer means a plain prefix)
+    return oo, bb, ss
+
+
+def job_line_prefix(job, contig: int, off, data, slot=None) -> None:
+    """pg_job_line_prefix[_slotted]: the fixed columns of index contig `contig`, record r's = data[off[r]:off[r + 1]]; with
+    slot [R], the digits of the chain's UK go in front of byte slot[r] of it."""
+    oo, bb, ss = _prefix_arrays(job, "line_prefix", contig, off, data, slot)
     err = C.create_string_buffer(_ERRLEN)
-    rc = job._lib.pg_job_line_prefix(job.h, contig, oo.ctypes.data if len(oo) else None, bb.ctypes.data if len(bb) else None, err, _ERRLEN)
+    po, pb = oo.ctypes.data if len(oo) else None, bb.ctypes.data if len(bb) else None
+    if ss is None:
+        rc = job._lib.pg_job_line_prefix(job.h, contig, po, pb, err, _ERRLEN)
+    else:
+        rc = job._lib.pg_job_line_prefix_slotted(job.h, contig, po, pb, ss.ctypes.data, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+
+
+def job_line_prefix_strided(job, contig: int, n_contigs: int, off, data, slot=None) -> None:
+    """pg_job_line_prefix_strided: ONE prefix, checked and uploaded once, for every index contig ix with ix % n_contigs ==
+    contig; slot as for job_line_prefix."""
+    oo, bb, ss = _prefix_arrays(job, "line_prefix_strided", contig, off, data, slot)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_line_prefix_strided(job.h, contig, n_contigs, oo.ctypes.data if len(oo) else None, bb.ctypes.data if len(bb) else None,
+                                             None if ss is None else ss.ctypes.data, err, _ERRLEN)
     if rc:
         raise _error(rc, err)
 
@@ -561,6 +594,39 @@ def record_lines_from_text(texts, prefix, device: int = 0):
     off = np.zeros(R + 1, np.uint64)
     out = np.zeros(max(cap, 1), np.uint8)
     rc = lib.pg_record_lines_from_text(device, R, S, op, tp, po.ctypes.data, pb.ctypes.data if len(pb) else None, off.ctypes.data, out.ctypes.data, cap)
+    if rc:
+        raise _error(rc, None)
+    return off, out[:int(off[-1])].tobytes()
+
+
+def record_lines_from_text_slotted(texts, prefix, slot=None, uk=None, device: int = 0):
+    """pg_record_lines_from_text_slotted: record_lines_from_text over a slotted prefix — the digits of uk[r] in front of byte
+    slot[r] of record r's prefix — through the kernels of pg_record_lines_slot.hip.  slot=None: a plain prefix, the bytes of
+    record_lines_from_text through those kernels."""
+    lib = _lib.load_hip()
+    po, pb = np.ascontiguousarray(prefix[0], np.uint64), _as_bytes(prefix[1])
+    R, S = len(po) - 1, len(texts)
+    offs = [np.ascontiguousarray(t[0], np.uint64) for t in texts]
+    data = [_as_bytes(t[1]) for t in texts]
+    if R < 0 or any(len(o) != R + 1 for o in offs) or any(int(o[-1]) > len(b) for o, b in zip(offs + [po], data + [pb])):
+        raise ValueError("record_lines_from_text_slotted: array lengths do not match")
+    ss = uu = None
+    if slot is not None:
+        if uk is None:
+            raise ValueError("record_lines_from_text_slotted: slots without UK values")
+        ss, uu = np.ascontiguousarray(slot, np.uint32), np.ascontiguousarray(uk, np.uint16)
+        if len(ss) != R or len(uu) != R:
+            raise ValueError("record_lines_from_text_slotted: array lengths do not match")
+        ss, uu = np.concatenate([ss, np.zeros(1, np.uint32)]), np.concatenate([uu, np.zeros(1, np.uint16)])   # (never empty)
+    bound = record_lines_bound if ss is None else record_lines_bound_slotted
+    cap = bound(R, S, int(po[-1]), sum(int(o[-1]) for o in offs))
+    op = (C.c_void_p * max(S, 1))(*[o.ctypes.data for o in offs])
+    tp = (C.c_void_p * max(S, 1))(*[b.ctypes.data if len(b) else None for b in data])
+    off = np.zeros(R + 1, np.uint64)
+    out = np.zeros(max(cap, 1), np.uint8)
+    rc = lib.pg_record_lines_from_text_slotted(device, R, S, op, tp, po.ctypes.data, pb.ctypes.data if len(pb) else None,
+                                               None if ss is None else ss.ctypes.data, None if uu is None else uu.ctypes.data, off.ctypes.data,
+                                               out.ctypes.data, cap)
     if rc:
         raise _error(rc, None)
     return off, out[:int(off[-1])].tobytes()

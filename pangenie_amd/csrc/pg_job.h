@@ -200,21 +200,28 @@ struct RecordTextFamily : OutputFamily {
 // The record lines (pg_job_record_lines) are the family above the text: per index contig that has a plan, a
 // prefix and members, the line of every record — the caller's prefix, every member's text, a newline — packed.  d = the
 // packed lines (the exact bound), then every line's first byte (64 bits, one more behind the last), the scan's arrays, the
-// descriptors and the members.  A contig's prefix is a device buffer of its own: [R + 1] offsets, then the bytes.
+// descriptors and the members.  A prefix is a device buffer of its own: [R + 1] offsets, then (a slotted one, DESIGN.md
+// 4e-8) [R] slots, then the bytes.  Index contigs refer to it, one alone (pg_job_line_prefix[_slotted]) or every member of a
+// stride (pg_job_line_prefix_strided); the buffer goes with the last reference, as a record plan's does.
 // Stale when the text it joined is stale or formed anew, and when a prefix changed.
 struct LinePrefix {
     unsigned char* d = nullptr;
     uint32_t R = 0;
     uint64_t bytes = 0;
+    size_t o_slot = 0, o_bytes = 0;           // bytes into d: the slots (0: a plain prefix), the prefix bytes
 };
+using LinePrefixRef = std::shared_ptr<const LinePrefix>;
+inline LinePrefixRef line_prefix_ref(const LinePrefix& p) {
+    return LinePrefixRef(new LinePrefix(p), [](const LinePrefix* q) { if (q->d) hipFree(q->d); delete q; });
+}
 struct RecordLinesFamily : OutputFamily {
-    std::vector<LinePrefix> prefix;           // [n_index] (sized by the first pg_job_line_prefix); d null: none
+    std::vector<LinePrefixRef> prefix;        // [n_index] (sized by the first pg_job_line_prefix*); null: none
     std::vector<uint64_t> line_first, byte_first;   // [n_index + 1] first line / first byte of every index contig (after a forming)
     size_t o_off = 0, alloc = 0;
     uint64_t n_lines = 0, cap = 0;
     uint64_t text_serial = 0;                 // RecordTextFamily::serial of the text the lines were joined from
     void drop_prefix(size_t ix) {
-        if (ix < prefix.size() && prefix[ix].d) { hipFree(prefix[ix].d); prefix[ix] = LinePrefix(); formed = false; }
+        if (ix < prefix.size() && prefix[ix]) { prefix[ix].reset(); formed = false; }
     }
     void release() {
         OutputFamily::release();

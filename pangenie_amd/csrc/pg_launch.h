@@ -1,4 +1,4 @@
-// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp, pg_shim_run.cpp, pg_shim_calls.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip, pg_calls.hip, pg_combine.hip, pg_combine_records.hip, pg_record_text.hip, pg_record_lines.hip).
+// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp, pg_shim_run.cpp, pg_shim_calls.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip, pg_calls.hip, pg_combine.hip, pg_combine_records.hip, pg_record_text.hip, pg_record_lines.hip, pg_record_lines_slot.hip).
 //
 // The ONE declaration of every host-callable launcher and of the two launch masks a job hands them.  Both sides include
 // it: a launcher whose parameter list changes on one side only no longer compiles (C linkage: the linker would not notice).
@@ -142,8 +142,25 @@ struct RLinesDesc {
     const uint64_t* prefix_off;
     const char* prefix;
 };
+// Record lines over a slotted prefix (pg_record_lines_slot.hip): RLinesDesc with lpw =
+// pgk_rlines_slot_lines_per_wave(S), and where the UK of every record goes and comes from.  slot null: a plain prefix, the
+// line of pg_record_lines.hip.  Otherwise record r's digits stand in front of byte slot[r] of its prefix; UK = uk[r] (the
+// unit entry point), or without `uk` the k-mer count of bubble rec_var[r] of DevContig `chain`, the contig's first member,
+// under pg_job_fetch's rule.
+struct RLinesSlotDesc {
+    RLinesDesc l;
+    const uint32_t* slot;
+    const uint16_t* uk;
+    const uint32_t* rec_var;
+    uint32_t chain, pad;
+};
 
 extern "C" {
+// pg_record_lines_slot.hip: the arrays of pgk_launch_rlines; d_contigs may be null if no descriptor reads a chain
+void pgk_launch_rlines_slot(const DevContig* d_contigs, const RLinesSlotDesc* d_desc, uint32_t n_desc, const RLinesMember* d_members, uint32_t n_blocks,
+                            uint32_t n_emit_blocks, uint32_t* d_loc, uint32_t* d_bsum, uint64_t* d_bbase, uint64_t* d_off, uint64_t n_lines, char* d_out,
+                            uint64_t cap, hipStream_t s);
+uint32_t pgk_rlines_slot_lines_per_wave(uint32_t n_members);
 // pg_record_lines.hip: d_loc [n_lines], d_bsum [n_blocks], d_bbase [n_blocks + 1]: the scan's; d_off [n_lines + 1] = every
 // line's first byte in d_out (`cap` bytes of room), the total behind the last
 void pgk_launch_rlines(const RLinesDesc* d_desc, uint32_t n_desc, const RLinesMember* d_members, uint32_t n_blocks, uint32_t n_emit_blocks, uint32_t* d_loc,

@@ -1,6 +1,6 @@
-// pg_shim_lines.cpp — the C-ABI of the record lines (pg_record_lines.hip): the prefix of an index contig,
-// the forming of whole VCF lines from a job's record text, their fetches, and the unit entry point over host arrays.
-// Host code off the critical path.
+// pg_shim_lines.cpp — the C-ABI of the record lines (pg_record_lines.hip; pg_record_lines_slot.hip, 4e-8):
+// the prefix of an index contig or of a stride of them, plain or slotted, the forming of whole VCF lines from a job's record
+// text, their fetches, and the unit entry points over host arrays.  Host code off the critical path.
 #include <hip/hip_runtime_api.h>
 
 #include <string.h>
@@ -20,33 +20,49 @@ namespace {
 // descriptors and the members.
 struct RLinesLayout {
     size_t o_off, o_loc, o_bsum, o_bbase, o_desc, o_members, total;
-    RLinesLayout(uint64_t cap, uint64_t n_lines, uint32_t n_blocks, size_t n_desc, size_t n_members) {
+    RLinesLayout(uint64_t cap, uint64_t n_lines, uint32_t n_blocks, size_t desc_bytes, size_t n_members) {
         o_off = align_up((size_t)cap + 16);
         o_loc = o_off + align_up(((size_t)n_lines + 1) * 8 + 8);
         o_bsum = o_loc + align_up((size_t)n_lines * 4 + 8);
         o_bbase = o_bsum + align_up((size_t)n_blocks * 4 + 8);
         o_desc = o_bbase + align_up(((size_t)n_blocks + 1) * 8 + 8);
-        o_members = o_desc + align_up(n_desc * sizeof(RLinesDesc) + 8);
+        o_members = o_desc + align_up(desc_bytes + 8);
         total = o_members + align_up(n_members * sizeof(RLinesMember) + 8);
     }
 };
 
-// one more contig of R records and S members behind those of `desc`: its blocks of both kernels, its first line and member
-void rlines_add(std::vector<RLinesDesc>* desc, uint32_t R, uint32_t S, uint32_t* blk, uint32_t* eblk, uint64_t* line, uint32_t* mem) {
-    RLinesDesc d;
-    memset(&d, 0, sizeof(d));
+// one more contig of R records and S members behind those of `desc`: its blocks of both kernels, its first line and member.
+// slot_kernels: the launch goes through pg_record_lines_slot.hip, whose waves take other runs of lines.
+void rlines_add(std::vector<RLinesSlotDesc>* desc, bool slot_kernels, uint32_t R, uint32_t S, uint32_t* blk, uint32_t* eblk, uint64_t* line, uint32_t* mem) {
+    RLinesSlotDesc sd;
+    memset(&sd, 0, sizeof(sd));
+    RLinesDesc& d = sd.l;
     const uint32_t per = pgk_rlines_block();
-    d.blk0 = *blk; d.R = R; d.eblk0 = *eblk; d.lpw = pgk_rlines_lines_per_wave(S); d.line0 = *line; d.mem0 = *mem; d.S = S;
+    d.blk0 = *blk; d.R = R; d.eblk0 = *eblk; d.lpw = slot_kernels ? pgk_rlines_slot_lines_per_wave(S) : pgk_rlines_lines_per_wave(S);
+    d.line0 = *line; d.mem0 = *mem; d.S = S;
     *blk += (R + per - 1) / per;
     *eblk += (R + d.lpw - 1) / d.lpw;
     *line += R;
     *mem += S;
-    desc->push_back(d);
+    desc->push_back(sd);
 }
 
-void rlines_launch(unsigned char* d, const RLinesLayout& L, uint32_t n_desc, uint32_t n_blocks, uint32_t n_eblocks, uint64_t n_lines, uint64_t cap, hipStream_t s) {
-    pgk_launch_rlines((const RLinesDesc*)(d + L.o_desc), n_desc, (const RLinesMember*)(d + L.o_members), n_blocks, n_eblocks, (uint32_t*)(d + L.o_loc),
-                      (uint32_t*)(d + L.o_bsum), (uint64_t*)(d + L.o_bbase), (uint64_t*)(d + L.o_off), n_lines, (char*)d, cap, s);
+// the descriptors as the kernels of the launch read them: whole (slot kernels) or their RLinesDesc alone
+std::vector<unsigned char> rlines_desc_bytes(const std::vector<RLinesSlotDesc>& desc, bool slot_kernels) {
+    const size_t each = slot_kernels ? sizeof(RLinesSlotDesc) : sizeof(RLinesDesc);
+    std::vector<unsigned char> b(desc.size() * each);
+    for (size_t i = 0; i < desc.size(); ++i) memcpy(b.data() + i * each, slot_kernels ? (const void*)&desc[i] : (const void*)&desc[i].l, each);
+    return b;
+}
+
+void rlines_launch(unsigned char* d, const RLinesLayout& L, bool slot_kernels, const DevContig* d_contigs, uint32_t n_desc, uint32_t n_blocks,
+                   uint32_t n_eblocks, uint64_t n_lines, uint64_t cap, hipStream_t s) {
+    if (slot_kernels)
+        pgk_launch_rlines_slot(d_contigs, (const RLinesSlotDesc*)(d + L.o_desc), n_desc, (const RLinesMember*)(d + L.o_members), n_blocks, n_eblocks,
+                               (uint32_t*)(d + L.o_loc), (uint32_t*)(d + L.o_bsum), (uint64_t*)(d + L.o_bbase), (uint64_t*)(d + L.o_off), n_lines, (char*)d, cap, s);
+    else
+        pgk_launch_rlines((const RLinesDesc*)(d + L.o_desc), n_desc, (const RLinesMember*)(d + L.o_members), n_blocks, n_eblocks, (uint32_t*)(d + L.o_loc),
+                          (uint32_t*)(d + L.o_bsum), (uint64_t*)(d + L.o_bbase), (uint64_t*)(d + L.o_off), n_lines, (char*)d, cap, s);
 }
 
 bool text_current(const pg_job* job) {
@@ -94,31 +110,91 @@ bool offsets_ok(const uint64_t* off, uint64_t n) {
 extern "C" uint64_t pg_record_lines_bound(uint64_t n_records, uint64_t n_members, uint64_t prefix_bytes, uint64_t text_bytes) {
     return prefix_bytes + text_bytes + n_records * (n_members + 1);
 }
+extern "C" uint64_t pg_record_lines_bound_slotted(uint64_t n_records, uint64_t n_members, uint64_t prefix_bytes, uint64_t text_bytes) {
+    return pg_record_lines_bound(n_records, n_members, prefix_bytes, text_bytes) + 5 * n_records;   // (UK has 16 bits: at most 5 digits a line)
+}
 
-extern "C" int pg_job_line_prefix(pg_job* job, uint32_t ix, const uint64_t* off, const char* bytes, char* err, size_t errlen) {
+namespace {
+
+// a prefix of R records as the caller handed it in: everything that needs the arrays alone
+int check_prefix(uint32_t R, const uint64_t* off, const char* bytes, const uint32_t* slot, char* err, size_t errlen) {
+    if (!offsets_ok(off, R)) { set_err(err, errlen, "the prefix offsets are null, do not start at 0 or shrink"); return PG_ERR_INVALID; }
+    if (off[R] && !bytes) { set_err(err, errlen, "null prefix bytes"); return PG_ERR_INVALID; }
+    if (slot)
+        for (uint32_t r = 0; r < R; ++r)
+            if (slot[r] > off[r + 1] - off[r]) {
+                set_err(err, errlen, "the slot of record %u lies at byte %u of a prefix of %llu bytes", r, slot[r], (unsigned long long)(off[r + 1] - off[r]));
+                return PG_ERR_INVALID;
+            }
+    return PG_OK;
+}
+
+// the checked prefix on the job's device, ready to be referred to by index contigs
+int prefix_to_device(pg_job* job, uint32_t R, const uint64_t* off, const char* bytes, const uint32_t* slot, LinePrefixRef* ref, char* err, size_t errlen) {
+    HIP_TRY(hipSetDevice(job->device));
+    LinePrefix p;
+    p.R = R; p.bytes = off[R];
+    p.o_slot = slot ? align_up(((size_t)R + 1) * 8) : 0;
+    p.o_bytes = align_up(((size_t)R + 1) * 8) + (slot ? align_up((size_t)R * 4 + 4) : 0);
+    const size_t total = p.o_bytes + (size_t)p.bytes + 16;
+    if (hipMalloc((void**)&p.d, total) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the line prefix failed", total); return PG_ERR_NOMEM; }
+    if (hipMemcpy(p.d, off, ((size_t)R + 1) * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        (slot && R && hipMemcpy(p.d + p.o_slot, slot, (size_t)R * 4, hipMemcpyHostToDevice) != hipSuccess) ||
+        (p.bytes && hipMemcpy(p.d + p.o_bytes, bytes, p.bytes, hipMemcpyHostToDevice) != hipSuccess)) {
+        (void)hipGetLastError();
+        hipFree(p.d);
+        set_err(err, errlen, "upload of the line prefix failed");
+        return PG_ERR_DEVICE;
+    }
+    *ref = line_prefix_ref(p);
+    RecordLinesFamily& f = job->rlines;
+    if (f.prefix.size() != job->index.size()) f.prefix.resize(job->index.size());
+    if (job->stream) HIP_TRY(hipStreamSynchronize(job->stream));   // (nothing reads the prefixes this one replaces any more)
+    return PG_OK;
+}
+
+}  // namespace
+
+extern "C" int pg_job_line_prefix_slotted(pg_job* job, uint32_t ix, const uint64_t* off, const char* bytes, const uint32_t* slot, char* err, size_t errlen) {
     if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
     if (ix >= job->index.size()) { set_err(err, errlen, "index contig %u of %zu", ix, job->index.size()); return PG_ERR_INVALID; }
     if (ix >= job->rplans.size() || !job->rplans[ix]) { set_err(err, errlen, "index contig %u has no record plan", ix); return PG_ERR_INVALID; }
     const uint32_t R = job->rplans[ix]->R;
-    if (!offsets_ok(off, R)) { set_err(err, errlen, "the prefix offsets are null, do not start at 0 or shrink"); return PG_ERR_INVALID; }
-    const uint64_t n = off[R];
-    if (n && !bytes) { set_err(err, errlen, "null prefix bytes"); return PG_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(job->device));
-    const size_t o_bytes = align_up(((size_t)R + 1) * 8);
-    unsigned char* d = nullptr;
-    if (hipMalloc((void**)&d, o_bytes + (size_t)n + 16) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the line prefix failed", o_bytes + (size_t)n + 16); return PG_ERR_NOMEM; }
-    if (hipMemcpy(d, off, ((size_t)R + 1) * 8, hipMemcpyHostToDevice) != hipSuccess || (n && hipMemcpy(d + o_bytes, bytes, n, hipMemcpyHostToDevice) != hipSuccess)) {
-        (void)hipGetLastError();
-        hipFree(d);
-        set_err(err, errlen, "upload of the line prefix failed");
-        return PG_ERR_DEVICE;
+    int rc = check_prefix(R, off, bytes, slot, err, errlen);
+    if (rc != PG_OK) return rc;
+    LinePrefixRef ref;
+    rc = prefix_to_device(job, R, off, bytes, slot, &ref, err, errlen);
+    if (rc != PG_OK) return rc;
+    job->rlines.prefix[ix] = std::move(ref);   // (this index contig's reference alone: the members of a stride keep theirs)
+    job->rlines.formed = false;
+    return PG_OK;
+}
+
+extern "C" int pg_job_line_prefix(pg_job* job, uint32_t ix, const uint64_t* off, const char* bytes, char* err, size_t errlen) {
+    return pg_job_line_prefix_slotted(job, ix, off, bytes, nullptr, err, errlen);
+}
+
+extern "C" int pg_job_line_prefix_strided(pg_job* job, uint32_t contig, uint32_t n_contigs, const uint64_t* off, const char* bytes, const uint32_t* slot,
+                                          char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    if (n_contigs == 0 || contig >= n_contigs) { set_err(err, errlen, "contig %u of %u", contig, n_contigs); return PG_ERR_INVALID; }
+    if (job->index.size() % n_contigs != 0) { set_err(err, errlen, "the job's %zu index contigs are no multiple of %u contigs", job->index.size(), n_contigs); return PG_ERR_INVALID; }
+    if (contig >= job->index.size()) return PG_OK;   // (a job without index contigs: no member)
+    for (size_t ix = contig; ix < job->index.size(); ix += n_contigs) {
+        if (ix >= job->rplans.size() || !job->rplans[ix]) { set_err(err, errlen, "index contig %zu (member %zu of the stride) has no record plan", ix, ix / n_contigs); return PG_ERR_INVALID; }
+        if (job->rplans[ix]->R != job->rplans[contig]->R) {
+            set_err(err, errlen, "the plan of index contig %zu (member %zu of the stride) has %u records, that of the first member %u", ix, ix / n_contigs, job->rplans[ix]->R, job->rplans[contig]->R);
+            return PG_ERR_INVALID;
+        }
     }
-    RecordLinesFamily& f = job->rlines;
-    if (f.prefix.size() != job->index.size()) f.prefix.resize(job->index.size());
-    if (job->stream) HIP_TRY(hipStreamSynchronize(job->stream));   // (nothing reads the prefix this one replaces any more)
-    f.drop_prefix(ix);
-    f.prefix[ix].d = d; f.prefix[ix].R = R; f.prefix[ix].bytes = n;
-    f.formed = false;
+    const uint32_t R = job->rplans[contig]->R;
+    int rc = check_prefix(R, off, bytes, slot, err, errlen);
+    if (rc != PG_OK) return rc;
+    LinePrefixRef ref;
+    rc = prefix_to_device(job, R, off, bytes, slot, &ref, err, errlen);
+    if (rc != PG_OK) return rc;
+    for (size_t ix = contig; ix < job->index.size(); ix += n_contigs) job->rlines.prefix[ix] = ref;
+    job->rlines.formed = false;
     return PG_OK;
 }
 
@@ -133,16 +209,22 @@ extern "C" int pg_job_record_lines(pg_job* job, char* err, size_t errlen) {
     // the members of every index contig: its chains in ascending id
     std::vector<std::vector<uint32_t>> chains_of(n_index);
     for (size_t c = 0; c < n_chains; ++c) chains_of[job->chains[c].index].push_back((uint32_t)c);
-    std::vector<RLinesDesc> desc;
+    auto takes_part = [&](size_t ix) {
+        return ix < job->rplans.size() && job->rplans[ix] && ix < f.prefix.size() && f.prefix[ix] && !chains_of[ix].empty() && job->rplans[ix]->R != 0;
+    };
+    bool slot_kernels = false;   // one slotted prefix among the contigs that take part: the launch is pg_record_lines_slot.hip's
+    for (size_t ix = 0; ix < n_index; ++ix) slot_kernels |= takes_part(ix) && f.prefix[ix]->o_slot != 0;
+    std::vector<RLinesSlotDesc> desc;
     std::vector<RLinesMember> members;
     std::vector<size_t> contig_of;   // the index contig of every descriptor
     uint32_t blk = 0, eblk = 0, mem = 0;
     uint64_t line = 0, cap = 0;
     for (size_t ix = 0; ix < n_index; ++ix) {
-        const bool plan = ix < job->rplans.size() && job->rplans[ix], prefix = ix < f.prefix.size() && f.prefix[ix].d;
+        const bool plan = ix < job->rplans.size() && job->rplans[ix], prefix = ix < f.prefix.size() && f.prefix[ix];
         if (!plan || !prefix || chains_of[ix].empty()) continue;
         const uint32_t R = job->rplans[ix]->R, S = (uint32_t)chains_of[ix].size();
-        if (f.prefix[ix].R != R) { set_err(err, errlen, "the prefix of index contig %zu has %u records, its plan %u", ix, f.prefix[ix].R, R); return PG_ERR_INVALID; }
+        const LinePrefix& px = *f.prefix[ix];
+        if (px.R != R) { set_err(err, errlen, "the prefix of index contig %zu has %u records, its plan %u", ix, px.R, R); return PG_ERR_INVALID; }
         if (R == 0) continue;
         uint64_t text_bytes = 0;
         for (uint32_t c : chains_of[ix]) {
@@ -153,13 +235,20 @@ extern "C" int pg_job_record_lines(pg_job* job, char* err, size_t errlen) {
             members.push_back(m);
             text_bytes += t.text_first[c + 1] - t.text_first[c];
         }
-        rlines_add(&desc, R, S, &blk, &eblk, &line, &mem);
-        desc.back().prefix_off = (const uint64_t*)f.prefix[ix].d;
-        desc.back().prefix = (const char*)(f.prefix[ix].d + align_up(((size_t)R + 1) * 8));
+        rlines_add(&desc, slot_kernels, R, S, &blk, &eblk, &line, &mem);
+        RLinesSlotDesc& sd = desc.back();
+        sd.l.prefix_off = (const uint64_t*)px.d;
+        sd.l.prefix = (const char*)(px.d + px.o_bytes);
+        if (px.o_slot) {   // UK: the first member's count of the record's bubble
+            sd.slot = (const uint32_t*)(px.d + px.o_slot);
+            sd.rec_var = job->rplans[ix]->dev.rec_var;
+            sd.chain = chains_of[ix][0];
+        }
         contig_of.push_back(ix);
-        cap += pg_record_lines_bound(R, S, f.prefix[ix].bytes, text_bytes);
+        cap += px.o_slot ? pg_record_lines_bound_slotted(R, S, px.bytes, text_bytes) : pg_record_lines_bound(R, S, px.bytes, text_bytes);
     }
-    const RLinesLayout L(cap, line, blk, desc.size(), members.size());
+    const std::vector<unsigned char> desc_bytes = rlines_desc_bytes(desc, slot_kernels);
+    const RLinesLayout L(cap, line, blk, desc_bytes.size(), members.size());
     if (!f.d || f.alloc < L.total) {
         unsigned char* d = nullptr;
         if (hipMalloc((void**)&d, L.total) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the record lines failed", L.total); return PG_ERR_NOMEM; }
@@ -173,7 +262,7 @@ extern "C" int pg_job_record_lines(pg_job* job, char* err, size_t errlen) {
     f.ms = 0.0;
     if (!desc.empty()) {
         hipStream_t s = job->stream;
-        HIP_TRY(hipMemcpyAsync(f.d + L.o_desc, desc.data(), desc.size() * sizeof(RLinesDesc), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(f.d + L.o_desc, desc_bytes.data(), desc_bytes.size(), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(f.d + L.o_members, members.data(), members.size() * sizeof(RLinesMember), hipMemcpyHostToDevice, s));
         if (!job->calls_events) {
             HIP_TRY(hipEventCreate(&job->ev_calls[0]));
@@ -181,7 +270,7 @@ extern "C" int pg_job_record_lines(pg_job* job, char* err, size_t errlen) {
             job->calls_events = true;
         }
         HIP_TRY(hipEventRecord(job->ev_calls[0], s));
-        rlines_launch(f.d, L, (uint32_t)desc.size(), blk, eblk, line, cap, s);
+        rlines_launch(f.d, L, slot_kernels, job->d_contigs, (uint32_t)desc.size(), blk, eblk, line, cap, s);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(job->ev_calls[1], s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -193,8 +282,8 @@ extern "C" int pg_job_record_lines(pg_job* job, char* err, size_t errlen) {
         if (bbase.back() > cap) { set_err(err, errlen, "the record lines take %llu bytes, more than their bound %llu", (unsigned long long)bbase.back(), (unsigned long long)cap); return PG_ERR_DEVICE; }
         size_t i = 0;   // a contig begins a block: its first byte is that block's
         for (size_t ix = 0; ix < n_index; ++ix) {
-            f.line_first[ix] = i < desc.size() ? desc[i].line0 : line;
-            f.byte_first[ix] = i < desc.size() ? bbase[desc[i].blk0] : bbase.back();
+            f.line_first[ix] = i < desc.size() ? desc[i].l.line0 : line;
+            f.byte_first[ix] = i < desc.size() ? bbase[desc[i].l.blk0] : bbase.back();
             if (i < desc.size() && contig_of[i] == ix) ++i;
         }
         f.line_first[n_index] = line;
@@ -246,34 +335,44 @@ extern "C" int pg_job_device_record_lines(pg_job* job, uint32_t ix, void** d_off
     return PG_OK;
 }
 
-// The unit entry point: arbitrary bytes in, the packed lines and their offsets out, through the same kernels.
-extern "C" int pg_record_lines_from_text(int device, uint64_t n_records, uint64_t n_members, const uint64_t* const* off, const char* const* text,
-                                         const uint64_t* prefix_off, const char* prefix, uint64_t* out_off, char* out, uint64_t cap) {
-    if (!out_off || !off || !text || !prefix_off || n_members == 0 || n_members >= 0x80000000ull - 2 || n_records >= 0x80000000ull) return PG_ERR_INVALID;
+namespace {
+
+// The unit entry points: arbitrary bytes in, the packed lines and their offsets out, through the kernels of a job — those of
+// pg_record_lines_slot.hip with slot_kernels (slot and uk may then be null: a descriptor without slots), else the plain ones.
+int rlines_from_text(int device, uint64_t n_records, uint64_t n_members, const uint64_t* const* off, const char* const* text, const uint64_t* prefix_off,
+                     const char* prefix, const uint32_t* slot, const uint16_t* uk, bool slot_kernels, uint64_t* out_off, char* out, uint64_t cap) {
+    if (!out_off || !off || !text || !prefix_off || n_members == 0 || n_members >= 0x80000000ull - (slot_kernels ? 4 : 2) || n_records >= 0x80000000ull) return PG_ERR_INVALID;
     if (!offsets_ok(prefix_off, n_records) || (prefix_off[n_records] && !prefix)) return PG_ERR_INVALID;
+    if (slot && !uk) return PG_ERR_INVALID;
+    if (slot)
+        for (uint64_t r = 0; r < n_records; ++r)
+            if (slot[r] > prefix_off[r + 1] - prefix_off[r]) return PG_ERR_INVALID;
     uint64_t text_bytes = 0;
     for (uint64_t s = 0; s < n_members; ++s) {
         if (!offsets_ok(off[s], n_records) || (off[s][n_records] && !text[s])) return PG_ERR_INVALID;
         text_bytes += off[s][n_records];
     }
-    const uint64_t bound = pg_record_lines_bound(n_records, n_members, prefix_off[n_records], text_bytes);
+    const uint64_t bound = slot ? pg_record_lines_bound_slotted(n_records, n_members, prefix_off[n_records], text_bytes)
+                                : pg_record_lines_bound(n_records, n_members, prefix_off[n_records], text_bytes);
     if (cap < bound || (cap && !out)) return PG_ERR_INVALID;
     if (n_records == 0) { out_off[0] = 0; return PG_OK; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); return PG_ERR_DEVICE; }
     if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return PG_ERR_DEVICE;
     const uint32_t R = (uint32_t)n_records, S = (uint32_t)n_members;
-    std::vector<RLinesDesc> desc;
+    std::vector<RLinesSlotDesc> desc;
     uint32_t blk = 0, eblk = 0, mem = 0;
     uint64_t line = 0;
-    rlines_add(&desc, R, S, &blk, &eblk, &line, &mem);
-    const RLinesLayout L(bound, R, blk, 1, S);
-    // the inputs behind the launch's own arrays: the prefix, then member after member (offsets, bytes)
+    rlines_add(&desc, slot_kernels, R, S, &blk, &eblk, &line, &mem);
+    const RLinesLayout L(bound, R, blk, sizeof(RLinesSlotDesc), S);
+    // the inputs behind the launch's own arrays: the prefix (offsets, bytes, slots, UK), then member after member (offsets, bytes)
     const size_t offs_bytes = align_up(((size_t)R + 1) * 8);
     std::vector<size_t> o_moff(S), o_mtext(S);
     size_t at = L.total;
     const size_t o_poff = at; at += offs_bytes;
     const size_t o_pbytes = at; at += align_up((size_t)prefix_off[R] + 16);
+    const size_t o_slot = at; at += slot ? align_up((size_t)R * 4 + 4) : 0;
+    const size_t o_uk = at; at += slot ? align_up((size_t)R * 2 + 4) : 0;
     for (uint32_t s = 0; s < S; ++s) {
         o_moff[s] = at; at += offs_bytes;
         o_mtext[s] = at; at += align_up((size_t)off[s][R] + 16);
@@ -282,21 +381,38 @@ extern "C" int pg_record_lines_from_text(int device, uint64_t n_records, uint64_
     if (hipMalloc((void**)&d, at) != hipSuccess) { (void)hipGetLastError(); return PG_ERR_NOMEM; }
     std::vector<RLinesMember> members(S);
     for (uint32_t s = 0; s < S; ++s) { members[s].off = (const uint64_t*)(d + o_moff[s]); members[s].text = (const char*)(d + o_mtext[s]); }
-    desc[0].prefix_off = (const uint64_t*)(d + o_poff);
-    desc[0].prefix = (const char*)(d + o_pbytes);
-    bool ok = hipMemcpy(d + L.o_desc, desc.data(), sizeof(RLinesDesc), hipMemcpyHostToDevice) == hipSuccess &&
+    desc[0].l.prefix_off = (const uint64_t*)(d + o_poff);
+    desc[0].l.prefix = (const char*)(d + o_pbytes);
+    if (slot) { desc[0].slot = (const uint32_t*)(d + o_slot); desc[0].uk = (const uint16_t*)(d + o_uk); }
+    const std::vector<unsigned char> desc_bytes = rlines_desc_bytes(desc, slot_kernels);
+    bool ok = hipMemcpy(d + L.o_desc, desc_bytes.data(), desc_bytes.size(), hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(d + L.o_members, members.data(), (size_t)S * sizeof(RLinesMember), hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(d + o_poff, prefix_off, ((size_t)R + 1) * 8, hipMemcpyHostToDevice) == hipSuccess &&
-              (prefix_off[R] == 0 || hipMemcpy(d + o_pbytes, prefix, prefix_off[R], hipMemcpyHostToDevice) == hipSuccess);
+              (prefix_off[R] == 0 || hipMemcpy(d + o_pbytes, prefix, prefix_off[R], hipMemcpyHostToDevice) == hipSuccess) &&
+              (!slot || (hipMemcpy(d + o_slot, slot, (size_t)R * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                         hipMemcpy(d + o_uk, uk, (size_t)R * 2, hipMemcpyHostToDevice) == hipSuccess));
     for (uint32_t s = 0; s < S && ok; ++s)
         ok = hipMemcpy(d + o_moff[s], off[s], ((size_t)R + 1) * 8, hipMemcpyHostToDevice) == hipSuccess &&
              (off[s][R] == 0 || hipMemcpy(d + o_mtext[s], text[s], off[s][R], hipMemcpyHostToDevice) == hipSuccess);
     if (ok) {
-        rlines_launch(d, L, 1, blk, eblk, R, bound, nullptr);
+        rlines_launch(d, L, slot_kernels, nullptr, 1, blk, eblk, R, bound, nullptr);
         ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
              hipMemcpy(out_off, d + L.o_off, ((size_t)R + 1) * 8, hipMemcpyDeviceToHost) == hipSuccess && out_off[R] <= bound &&
              (out_off[R] == 0 || hipMemcpy(out, d, out_off[R], hipMemcpyDeviceToHost) == hipSuccess);
     }
     hipFree(d);
     return ok ? PG_OK : PG_ERR_DEVICE;
+}
+
+}  // namespace
+
+extern "C" int pg_record_lines_from_text(int device, uint64_t n_records, uint64_t n_members, const uint64_t* const* off, const char* const* text,
+                                         const uint64_t* prefix_off, const char* prefix, uint64_t* out_off, char* out, uint64_t cap) {
+    return rlines_from_text(device, n_records, n_members, off, text, prefix_off, prefix, nullptr, nullptr, false, out_off, out, cap);
+}
+
+extern "C" int pg_record_lines_from_text_slotted(int device, uint64_t n_records, uint64_t n_members, const uint64_t* const* off, const char* const* text,
+                                                 const uint64_t* prefix_off, const char* prefix, const uint32_t* slot, const uint16_t* uk, uint64_t* out_off,
+                                                 char* out, uint64_t cap) {
+    return rlines_from_text(device, n_records, n_members, off, text, prefix_off, prefix, slot, uk, true, out_off, out, cap);
 }

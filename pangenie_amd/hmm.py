@@ -460,11 +460,20 @@ class Job:
         """elapsed ms of the kernels of the last record_text()"""
         return float(self._lib.pg_job_record_text_ms(self.h))
 
-    def line_prefix(self, contig: int, off, data) -> None:
+    def line_prefix(self, contig: int, off, data, slot=None) -> None:
         """pg_job_line_prefix: the fixed columns (CHROM .. FORMAT, no trailing tab) of the records of INDEX contig `contig`,
-        record r's = data[off[r]:off[r + 1]]; after record_plan().  A second call replaces them."""
+        record r's = data[off[r]:off[r + 1]]; after record_plan().  A second call replaces them.  With
+        slot [R] (pg_job_line_prefix_slotted) the decimal UK of the record's bubble in the contig's first
+        member chain is printed on the device in front of byte slot[r] of record r's columns."""
         from . import calls as _calls
-        _calls.job_line_prefix(self, contig, off, data)
+        _calls.job_line_prefix(self, contig, off, data, slot)
+
+    def line_prefix_strided(self, contig: int, n_contigs: int, off, data, slot=None) -> None:
+        """pg_job_line_prefix_strided: ONE prefix, checked and uploaded once, for every index contig ix with ix % n_contigs ==
+        contig — the chains of one chromosome in a sampled cohort; after record_plan_strided().  A later
+        line_prefix() on one member replaces that member's alone."""
+        from . import calls as _calls
+        _calls.job_line_prefix_strided(self, contig, n_contigs, off, data, slot)
 
     def record_lines(self, contig: Optional[int] = None):
         """pg_job_record_lines + pg_job_fetch_record_lines: whole VCF lines — the prefix, every member's text behind a tab, a

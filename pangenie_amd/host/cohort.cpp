@@ -1175,6 +1175,83 @@ int sampled_job_record_text(pg_job* job, size_t n, const std::vector<Chromosome>
     return rc;
 }
 
+// whole lines: the text stays on the device, ONE slotted prefix per chromosome is shared by its chains, one
+// launch joins every chain's lines with its own UK, one packed copy brings them.  Only a chain with a line the device left to
+// the host has its counts and its text fetched: the text is finished as sampled_job_record_text finishes it, the lines are
+// composed over a prefix formed with that chain's UK.
+int sampled_job_record_lines(pg_job* job, size_t n, const std::vector<Chromosome>& chroms, const CoverageRows* cov_rows, uint32_t size, bool add_reference,
+                             bool ignore_imputed, const Picks& picks, std::map<std::string, RecordLines>* lines, std::map<std::string, SampledPaths>* sampled,
+                             char* err, size_t errlen) {
+    const size_t C = chroms.size();
+    int rc = sampled_job_run_records(job, chroms, err, errlen);
+    if (rc == PG_OK) rc = pg_job_record_text(job, ignore_imputed ? 1 : 0, err, errlen);
+    for (size_t c = 0; c < C && rc == PG_OK; ++c) {
+        std::vector<uint32_t> slot;
+        const std::vector<std::string> fixed = chroms[c].graph->genotypes_fixed_columns_slotted(&slot);
+        std::vector<uint64_t> poff(fixed.size() + 1, 0);
+        std::string pbytes;
+        for (size_t r = 0; r < fixed.size(); ++r) { pbytes += fixed[r]; poff[r + 1] = pbytes.size(); }
+        slot.push_back(0);   // (never empty: a null pointer means a plain prefix)
+        rc = pg_job_line_prefix_strided(job, (uint32_t)c, (uint32_t)C, poff.data(), pbytes.empty() ? nullptr : pbytes.data(), slot.data(), err, errlen);
+    }
+    if (rc == PG_OK) rc = pg_job_record_lines(job, err, errlen);
+    if (rc != PG_OK) return rc;
+    std::vector<uint64_t> line_first(n * C + 1, 0), byte_first(n * C + 1, 0), text_first(n * C + 1, 0);
+    uint64_t n_index = 0;
+    rc = pg_job_record_lines_first(job, &n_index, nullptr, nullptr, err, errlen);
+    if (rc == PG_OK && n_index != n * C) {
+        std::snprintf(err, errlen, "genotype_cohort_sampled_record_lines: the job has %llu index contigs, not %zu", (unsigned long long)n_index, n * C);
+        return PG_ERR_INVALID;
+    }
+    if (rc == PG_OK) rc = pg_job_record_lines_first(job, nullptr, line_first.data(), byte_first.data(), err, errlen);
+    if (rc == PG_OK) rc = pg_job_record_text_first(job, text_first.data(), err, errlen);
+    if (rc != PG_OK) return rc;
+    std::vector<uint64_t> loff(line_first.back() + 1, 0);
+    std::string lbytes(byte_first.back(), '\0');
+    rc = pg_job_fetch_record_lines_packed(job, loff.data(), lbytes.empty() ? nullptr : &lbytes[0], lbytes.size(), err, errlen);
+    for (size_t s = 0; s < n && rc == PG_OK; ++s)
+        for (size_t c = 0; c < C && rc == PG_OK; ++c) {
+            const uint32_t chain = (uint32_t)(s * C + c);   // chain id = sample * n_contigs + contig: an index contig of its own
+            const Chromosome& x = chroms[c];
+            const size_t V = x.flat.variant_pos.size(), R = x.plan.nr_of_records();
+            RecordLines dev;
+            dev.off.assign(R + 1, 0);
+            if (line_first[chain + 1] - line_first[chain] == R) {   // (a chromosome without records has no lines on the device)
+                for (size_t r = 0; r <= R; ++r) dev.off[r] = loff[line_first[chain] + r] - byte_first[chain];
+                dev.bytes.assign(lbytes, byte_first[chain], byte_first[chain + 1] - byte_first[chain]);
+            } else if (R != 0 || line_first[chain + 1] != line_first[chain]) {
+                std::snprintf(err, errlen, "genotype_cohort_sampled_record_lines: chain %u holds other lines than its plan's records", chain);
+                return PG_ERR_INVALID;
+            }
+            if (sampled) sampled_paths_of(picks[chain].data(), size, V, add_reference, &sampled[s][x.name]);
+            bool whole = true;
+            for (size_t r = 0; r < R; ++r) whole = whole && dev.off[r + 1] != dev.off[r];
+            if (whole) { lines[s][x.name] = std::move(dev); continue; }
+            // a line is left to the host: this chain's counts and text, finished, and the prefix with its UK
+            std::vector<uint16_t> nk, cov;
+            uint32_t n_columns = 0;
+            rc = fetch_chain_meta(job, chain, V, &nk, &cov, &n_columns, err, errlen);
+            if (rc != PG_OK) break;
+            std::vector<uint64_t> toff(R + 1, 0);
+            std::string tbytes(text_first[chain + 1] - text_first[chain], '\0');
+            rc = pg_job_fetch_record_text(job, chain, toff.data(), tbytes.empty() ? nullptr : &tbytes[0], tbytes.size(), err, errlen);
+            if (rc != PG_OK) break;
+            const uint16_t* own = cov_rows ? (*cov_rows)[s][c] : nullptr;
+            RecordText t;
+            t.unique_kmers.assign(nk.begin(), nk.end());
+            rc = chain_record_text(
+                job, chain, x, ignore_imputed, toff.data(), tbytes, [&](size_t v) { return t.unique_kmers[v] == 0; },
+                [&](size_t v) { return sampled_coverage(own, n_columns, cov, v); },
+                [&](std::vector<GenotypingResult>* full) {
+                    return fetch_sampled_chain(job, chain, x.flat, own, size, add_reference, nullptr, full, nullptr, err, errlen);
+                },
+                t, err, errlen);
+            if (rc != PG_OK) break;
+            lines[s][x.name] = compose_record_lines(x.graph->genotypes_fixed_columns(t.unique_kmers), {&t}, dev);
+        }
+    return rc;
+}
+
 // One sampled cohort job from the samples' counts on the host (`who`: the caller's name in a refusal), then
 // `tail(job, cov_rows, picks, err, errlen)` on the made job: one of the three tails above; it returns the C ABI's code.
 template <class Tail>
@@ -1331,6 +1408,15 @@ std::vector<std::map<std::string, RecordText>> genotype_cohort_sampled_record_te
                                               recombrate, uniform, effective_N, device, ignore_imputed, sampled, sampled_job_record_text);
 }
 
+std::vector<std::map<std::string, RecordLines>> genotype_cohort_sampled_record_lines(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device, bool ignore_imputed,
+    std::vector<std::map<std::string, SampledPaths>>* sampled) {
+    return sampled_cohort_records<RecordLines>(chromosomes, graphs, samples, panel_size, add_reference, allele_penalty, sampling_effective_N, probabilities,
+                                               recombrate, uniform, effective_N, device, ignore_imputed, sampled, sampled_job_record_lines);
+}
+
 // ------------------------------------------------------------------ sampled cohort job fed by the device counter
 std::vector<std::map<std::string, std::vector<GenotypingResult>>> genotype_cohort_sampled_reads(
     UniqueKmersMap& index, const std::string& prefix, const std::vector<std::string>& readfiles, const std::vector<size_t>& kmer_coverages,
@@ -1371,6 +1457,15 @@ std::vector<std::map<std::string, RecordText>> genotype_cohort_sampled_reads_rec
     std::vector<std::map<std::string, SampledPaths>>* sampled) {
     return sampled_reads_records<RecordText>(index, graphs, prefix, readfiles, kmer_coverages, panel_size, add_reference, allele_penalty, sampling_effective_N,
                                              probabilities, recombrate, uniform, effective_N, device, batch, ignore_imputed, sampled, sampled_job_record_text);
+}
+
+std::vector<std::map<std::string, RecordLines>> genotype_cohort_sampled_reads_record_lines(
+    UniqueKmersMap& index, const std::map<std::string, Graph>& graphs, const std::string& prefix, const std::vector<std::string>& readfiles,
+    const std::vector<size_t>& kmer_coverages, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device, size_t batch, bool ignore_imputed,
+    std::vector<std::map<std::string, SampledPaths>>* sampled) {
+    return sampled_reads_records<RecordLines>(index, graphs, prefix, readfiles, kmer_coverages, panel_size, add_reference, allele_penalty, sampling_effective_N,
+                                              probabilities, recombrate, uniform, effective_N, device, batch, ignore_imputed, sampled, sampled_job_record_lines);
 }
 
 }  // namespace pangenie

@@ -507,7 +507,8 @@ static std::string text_field(const RecordText& t, size_t q, size_t n_defined) {
 }
 
 // CHROM .. INFO of one record
-std::string Graph::fixed_columns_of(const VcfSite& site, size_t record_index, size_t unique_kmers, const char* who, std::vector<unsigned short>& defined) const {
+std::string Graph::fixed_columns_of(const VcfSite& site, size_t record_index, size_t unique_kmers, const char* who, std::vector<unsigned short>& defined,
+                                    size_t* uk_slot) const {
     const size_t n_all = site.alleles.size();
     if (n_all < 2) throw std::runtime_error(std::string(who) + ": less than 2 alleles given for variant at position " + std::to_string(site.start));
     // ALT = the defined alternative alleles; genotypes over undefined alleles are dropped by the caller
@@ -525,7 +526,10 @@ std::string Graph::fixed_columns_of(const VcfSite& site, size_t record_index, si
     for (size_t k = 0; k < alts.size(); ++k) line << (k ? "," : "") << alts[k];
     line << "\t.\tPASS\tAF=";
     for (size_t k = 1; k < defined.size(); ++k) line << (k > 1 ? "," : "") << std::setprecision(6) << freq[defined[k]] / n_paths;
-    line << ";UK=" << unique_kmers << ";MA=" << (n_all - defined.size());
+    line << ";UK=";
+    if (uk_slot) *uk_slot = (size_t)line.tellp();   // (the digits are left out: whoever holds the count puts them in here)
+    else line << unique_kmers;
+    line << ";MA=" << (n_all - defined.size());
     const std::vector<std::string>& ids = variant_ids_.at(record_index);
     if (!ids.empty()) {
         // the ids are kept in the lexicographic order of their ALT alleles: back into ALT order
@@ -550,6 +554,22 @@ std::vector<std::string> Graph::genotypes_fixed_columns(const std::vector<unsign
     for (size_t i = 0; i < size(); ++i)
         for (const VcfSite& site : get_variant(i).records(nullptr)) {
             columns.push_back(fixed_columns_of(site, columns.size(), unique_kmers[i], who, defined) + "\tGT:GQ:GL:KC");
+        }
+    return columns;
+}
+
+std::vector<std::string> Graph::genotypes_fixed_columns_slotted(std::vector<uint32_t>* slot) const {
+    const char* who = "Graph::write_genotypes_of";
+    if (variants_deleted_) throw std::runtime_error(std::string(who) + ": variants have been deleted by delete_variant funtion. Re-build object.");
+    if (!slot) throw std::runtime_error("Graph::genotypes_fixed_columns_slotted: nowhere to report the slots");
+    std::vector<std::string> columns;
+    std::vector<unsigned short> defined;
+    slot->clear();
+    for (size_t i = 0; i < size(); ++i)
+        for (const VcfSite& site : get_variant(i).records(nullptr)) {
+            size_t at = 0;
+            columns.push_back(fixed_columns_of(site, columns.size(), 0, who, defined, &at) + "\tGT:GQ:GL:KC");
+            slot->push_back((uint32_t)at);
         }
     return columns;
 }

@@ -199,6 +199,11 @@ public:
      *  `CHROM .. INFO\tGT:GQ:GL:KC` without a trailing tab (UK from `unique_kmers`, one entry per bubble).  It depends on the
      *  index alone: one array per chromosome, whatever the number of samples (the prefix of pg_job_line_prefix). */
     std::vector<std::string> genotypes_fixed_columns(const std::vector<unsigned short>& unique_kmers) const;
+    /** the same columns with the digits of UK left out, and per record where they belong: slot[r] = the position behind
+     *  `;UK=`.  genotypes_fixed_columns(uk)[r] is this record's string with the decimal uk of its bubble put in at slot[r].
+     *  It depends on the graph alone: one array per chromosome of a SAMPLED cohort, whose chains differ in UK only (the
+     *  slotted prefix of pg_job_line_prefix_strided). */
+    std::vector<std::string> genotypes_fixed_columns_slotted(std::vector<uint32_t>* slot) const;
     /** the record lines: one per single variant, in graph order; `genotyping_result` = one (normalised) result per
      *  bubble, as HMM::get_genotyping_result() returns them */
     std::vector<std::string> genotypes_records(const std::vector<GenotypingResult>& genotyping_result, bool ignore_imputed = false) const;
@@ -245,8 +250,10 @@ private:
     };
     std::vector<std::string> sample_records(const std::vector<GenotypingResult>& genotyping_result, bool ignore_imputed, bool phasing,
                                             const std::vector<SampledPanel>* sampled_paths = nullptr, const DeviceFields* device = nullptr) const;
-    /** CHROM .. INFO of one record (the ONE place that forms them): `defined` comes back as the record's defined alleles */
-    std::string fixed_columns_of(const VcfSite& site, size_t record_index, size_t unique_kmers, const char* who, std::vector<unsigned short>& defined) const;
+    /** CHROM .. INFO of one record (the ONE place that forms them): `defined` comes back as the record's defined alleles.
+     *  With `uk_slot` the digits of `unique_kmers` are left out and *uk_slot = where they belong. */
+    std::string fixed_columns_of(const VcfSite& site, size_t record_index, size_t unique_kmers, const char* who, std::vector<unsigned short>& defined,
+                                 size_t* uk_slot = nullptr) const;
     size_t nr_of_records() const;
     std::vector<std::pair<std::string, std::shared_ptr<DnaSequence>>> fasta_;   // name -> sequence, archive (= sorted) order
     std::string chromosome_;
@@ -315,8 +322,8 @@ std::vector<std::map<std::string, RecordText>> genotype_cohort_record_text(
  *  samples), pg_job_record_lines and ONE packed fetch.  Per chromosome the multi-sample lines, sample s in column 9 + s; a
  *  line the device left to the host is composed here from the prefix and the finished texts (compose_record_lines), so no
  *  line is empty; a record of fewer than three values throws.  Throws if the samples' unique k-mer counts of a chromosome
- *  differ: a multi-sample line has one INFO column (over a shared index they cannot).  Not covered: sampled cohorts (UK and
- *  the reduced panels differ per sample: the C ABI gives them single-member lines), the combined (-a) records, phasing. */
+ *  differ: a multi-sample line has one INFO column (over a shared index they cannot).  Sampled cohorts, whose UK and reduced
+ *  panels differ per sample, have genotype_cohort_sampled_record_lines.  Not covered: the combined (-a) records, phasing. */
 std::map<std::string, RecordLines> genotype_cohort_record_lines(
     std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
     const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false,
@@ -324,6 +331,20 @@ std::map<std::string, RecordLines> genotype_cohort_record_lines(
 
 /** genotype_cohort_sampled_record_fields with the sample column formed as text on the device, as genotype_cohort_record_text. */
 std::vector<std::map<std::string, RecordText>> genotype_cohort_sampled_record_text(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
+    bool ignore_imputed = false, std::vector<std::map<std::string, SampledPaths>>* sampled = nullptr);
+
+/** genotype_cohort_sampled_record_text with the LINES joined on the device too: the same job, the strided plans,
+ *  the run and pg_job_record_text, then ONE slotted prefix per chromosome (Graph::genotypes_fixed_columns_slotted through
+ *  pg_job_line_prefix_strided: the device prints every chain's own UK at the slot), pg_job_record_lines and ONE packed fetch.
+ *  Per sample and chromosome the single-sample lines — the '\n'-joined Graph::genotypes_records of the sibling's text —, which
+ *  Graph::write_genotypes(filename, lines, ...) writes.  Neither text nor k-mer counts come back, except for a chain with a line
+ *  the device left to the host: that chain's counts and text are fetched, the text finished as the sibling finishes it, and the
+ *  lines composed over a prefix formed with that chain's UK (compose_record_lines).  A record of fewer than three values
+ *  throws.  Not covered: the combined (-a) records, phasing. */
+std::vector<std::map<std::string, RecordLines>> genotype_cohort_sampled_record_lines(
     std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
     const std::vector<SampleCounts>& samples, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
     ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
