@@ -9,6 +9,7 @@
 #include "pg_oracle.h"
 
 #include <math.h>
+#include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -43,10 +44,22 @@ static double get_error_param(double kmer_coverage) {
 
 /* reference src/probabilitytable.cpp:75-81.  `log(i)` there is the double
  * overload (integer argument), `log(mean)`/`exp` the long double ones. */
+/* (the sum of the logs up to `value`: the reference's loop, i ascending, run once for all 16-bit counts and kept — a count of
+ *  60000 outside the table's box cost 120000 log() calls per k-mer and allele pair, whole seconds per chain of the tests without
+ *  regularisation; the partial sums are the loop's own, bit for bit) */
+static long double g_log_sum[65536];
+static pthread_once_t g_log_sum_once = PTHREAD_ONCE_INIT;
+static void fill_log_sums(void) {
+    long double sum = 0.0L;
+    g_log_sum[0] = 0.0L;
+    for (size_t i = 1; i < 65536; ++i) { sum += log((double)i); g_log_sum[i] = sum; }
+}
+
 static long double poisson(long double mean, unsigned int value) {
     long double sum = 0.0L;
     int v = (int)value;
-    for (size_t i = 1; i <= value; ++i) sum += log((double)i);
+    if (value < 65536u) { pthread_once(&g_log_sum_once, fill_log_sums); sum = g_log_sum[value]; }
+    else for (size_t i = 1; i <= value; ++i) sum += log((double)i);
     long double log_val = -mean + v * logl(mean) - sum;
     return expl(log_val);
 }

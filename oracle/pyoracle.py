@@ -256,9 +256,7 @@ def sampler_run(batch, size, recombrate=1.26, effective_N=25000.0, allele_penalt
 _ref_transitions = None
 
 
-def ref_transition_cost(from_pos, to_pos, recombrate, nr_paths, effective_N=25000.0):
-    """The reference's OWN SamplingTransitions translation unit (oracle/_ref/libref_transitions.so, built by
-    `make ref` where /root/reference exists).  Returns None when the library is not there."""
+def _ref_transitions_lib():
     global _ref_transitions
     path = HERE / "_ref" / "libref_transitions.so"
     if _ref_transitions is None:
@@ -267,8 +265,32 @@ def ref_transition_cost(from_pos, to_pos, recombrate, nr_paths, effective_N=2500
         lib = C.CDLL(str(path))
         lib.ref_sampling_transition_cost.argtypes = [C.c_ulonglong, C.c_ulonglong, C.c_double, C.c_ushort, C.c_longdouble]
         lib.ref_sampling_transition_cost.restype = C.c_uint
+        if hasattr(lib, "ref_transition_probs"):   # (a library left by an earlier build of the tree has the sampler's entry point alone)
+            lib.ref_transition_probs.argtypes = [C.c_ulonglong, C.c_ulonglong, C.c_double, C.c_ushort, C.c_int, C.c_longdouble, ldp]
+            lib.ref_transition_probs.restype = None
         _ref_transitions = lib
-    return int(_ref_transitions.ref_sampling_transition_cost(int(from_pos), int(to_pos), float(recombrate), int(nr_paths), _ld(effective_N)))
+    return _ref_transitions
+
+
+def ref_transition_cost(from_pos, to_pos, recombrate, nr_paths, effective_N=25000.0):
+    """The reference's OWN SamplingTransitions translation unit (oracle/_ref/libref_transitions.so, built by
+    `make ref` where /root/reference exists).  Returns None when the library is not there."""
+    lib = _ref_transitions_lib()
+    if lib is None:
+        return None
+    return int(lib.ref_sampling_transition_cost(int(from_pos), int(to_pos), float(recombrate), int(nr_paths), _ld(effective_N)))
+
+
+def ref_transition_probs(from_pos, to_pos, recombrate, nr_paths, uniform, effective_N):
+    """The reference's OWN TransitionProbabilityComputer from the same library: {no switch, one switch, two switches} as three
+    long doubles (compute_transition_prob(0..2)).  Returns None when the library is not there, or was built before it had this entry
+    point and not since (`make -C oracle ref` builds it anew)."""
+    lib = _ref_transitions_lib()
+    if lib is None or not hasattr(lib, "ref_transition_probs"):
+        return None
+    out, ptr = _ld3()
+    lib.ref_transition_probs(int(from_pos), int(to_pos), float(recombrate), int(nr_paths), int(uniform), _ld(effective_N), ptr)
+    return out
 
 
 # --------------------------------------------------------------------------- #

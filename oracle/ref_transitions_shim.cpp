@@ -11,3 +11,14 @@ extern "C" unsigned int ref_sampling_transition_cost(unsigned long long from_pos
     SamplingTransitions t((size_t)from_pos, (size_t)to_pos, recombrate, nr_paths, effective_N);
     return t.compute_transition_cost(true);
 }
+
+// The same around the reference's OWN TransitionProbabilityComputer (src/transitionprobabilitycomputer.cpp); pins
+// pgo_transition_probs bit for bit (tests/test_transition_regimes_cpu.py).  Its header includes uniquekmers.hpp, of which it
+// uses nothing and which wants <cereal/...>: the Makefile rule defines that header's include guard, so it is skipped.
+#include "transitionprobabilitycomputer.hpp"
+
+extern "C" void ref_transition_probs(unsigned long long from_pos, unsigned long long to_pos, double recombrate, unsigned short nr_paths,
+                                     int uniform, long double effective_N, long double out3[3]) {
+    TransitionProbabilityComputer t((size_t)from_pos, (size_t)to_pos, recombrate, nr_paths, uniform != 0, effective_N);
+    for (unsigned short s = 0; s < 3; ++s) out3[s] = t.compute_transition_prob(s);
+}

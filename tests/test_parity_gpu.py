@@ -152,6 +152,9 @@ def test_panels_vs_oracle(V, H, K, multi, kw, orc):
 @pytest.mark.parametrize("recomb,uniform,N", [(1.26, True, 1e-5), (0.001, False, 1e-5), (1e-9, False, 1e-5),
                                               (446.287102628, False, 0.25), (1.26, False, 25000.0)])
 def test_transition_regimes_vs_oracle(recomb, uniform, N, orc):
+    """One 24-path panel through the one-shot call: a chunked job on k_sweep<32,8> (phase 1, the chunk sweeps, k_post), whose
+    constants come from the full-record branch of k_records alone.  The compact-record branch, k_index_cols / k_index_cols_t and
+    every other step formulation under such parameters: tests/test_transition_regimes_gpu.py."""
     b = synthetic_panel(400, 24, 16, seed=77, multiallelic_frac=0.2)
     args = default_table_args()
     res = hmm.genotype_contig(b, hmm.ProbabilityTable(*args), hmm.make_params(recomb, uniform, N))
@@ -164,7 +167,8 @@ def test_zero_recombination_documented_range(orc):
     never produces: recombrate is fixed at 1.26, src/pangenie-genotype.cpp:33-45).  The stored fp64
     columns then keep 2^-1400 of a column's sum where the reference's long double keeps 2^-16445
     (include/pangenie_hmm.h, numeric contract): bins within 350 decades of their variant's largest bin
-    are held to the usual 1e-6 relative, calls are identical; deeper bins may flush to 0."""
+    are held to the usual 1e-6 relative, calls are identical; deeper bins may flush to 0.
+    (The same 24-path one-shot panel as above: a chunked job on k_sweep<32,8>, constants from the full-record branch of k_records.)"""
     b = synthetic_panel(400, 24, 16, seed=77, multiallelic_frac=0.2)
     args = default_table_args()
     res = hmm.genotype_contig(b, hmm.ProbabilityTable(*args), hmm.make_params(0.0, False, 1e-5))
