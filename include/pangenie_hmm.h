@@ -637,8 +637,8 @@ int  pg_record_lines_from_text(int device, uint64_t n_records, uint64_t n_member
  *  with UK the value pg_job_fetch reports in n_kmers[v] for the bubble v of record r (the plan's rec_var) of the index
  *  contig's FIRST member chain — 0 for a chain without a kept column, 16 bits — and dec its decimal digits without
  *  leading zeros, "0" for 0.  Everything else is the rule above.  slot == NULL: a plain prefix.  A job with at least
- *  one slotted prefix among the index contigs that take part forms all its lines through pg_record_lines_slot.hip's
- *  kernels (a plain prefix gives the same bytes there); a job without one through pg_record_lines.hip's, as before.
+ *  one slotted prefix among the index contigs that take part forms all its lines through the slotted instantiation of
+ *  pg_record_lines.hip's kernels (a plain prefix gives the same bytes there); a job without one through the plain one.
  *  Not covered: the combined (-a) record families, the phasing column.
  * ------------------------------------------------------------------ */
 /* pg_record_lines_bound(...) + 5 n_records: an upper bound (UK has at most 5 digits).  Host only. */
@@ -657,7 +657,7 @@ int  pg_job_line_prefix_slotted(pg_job* job, uint32_t index_contig, const uint64
 int  pg_job_line_prefix_strided(pg_job* job, uint32_t contig, uint32_t n_contigs, const uint64_t* off, const char* bytes, const uint32_t* slot, char* err,
                                 size_t errlen);
 /* Unit entry point: pg_record_lines_from_text over a slotted prefix with UK of record r = uk[r], always through
- * pg_record_lines_slot.hip's kernels.  slot == NULL (uk is then not read): a plain prefix, the bytes and offsets of
+ * the slotted instantiation of pg_record_lines.hip's kernels.  slot == NULL (uk is then not read): a plain prefix, the bytes and offsets of
  * pg_record_lines_from_text.  PG_ERR_INVALID, before any device is asked for: the refusals of pg_record_lines_from_text
  * (cap: below pg_record_lines_bound_slotted with slots, below pg_record_lines_bound without), slot without uk,
  * slot[r] > prefix_off[r + 1] - prefix_off[r]. */

@@ -601,7 +601,7 @@ def record_lines_from_text(texts, prefix, device: int = 0):
 
 def record_lines_from_text_slotted(texts, prefix, slot=None, uk=None, device: int = 0):
     """pg_record_lines_from_text_slotted: record_lines_from_text over a slotted prefix — the digits of uk[r] in front of byte
-    slot[r] of record r's prefix — through the kernels of pg_record_lines_slot.hip.  slot=None: a plain prefix, the bytes of
+    slot[r] of record r's prefix — through the slotted kernels of pg_record_lines.hip.  slot=None: a plain prefix, the bytes of
     record_lines_from_text through those kernels."""
     lib = _lib.load_hip()
     po, pb = np.ascontiguousarray(prefix[0], np.uint64), _as_bytes(prefix[1])

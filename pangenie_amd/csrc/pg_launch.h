@@ -1,4 +1,4 @@
-// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp, pg_shim_run.cpp, pg_shim_calls.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip, pg_calls.hip, pg_combine.hip, pg_combine_records.hip, pg_record_text.hip, pg_record_lines.hip, pg_record_lines_slot.hip).
+// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp, pg_shim_run.cpp, pg_shim_calls.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip, pg_calls.hip, pg_combine.hip, pg_combine_records.hip, pg_record_text.hip, pg_record_lines.hip).
 //
 // The ONE declaration of every host-callable launcher and of the two launch masks a job hands them.  Both sides include
 // it: a launcher whose parameter list changes on one side only no longer compiles (C linkage: the linker would not notice).
@@ -125,11 +125,15 @@ struct RTextDesc {
     const uint8_t* no_call;
 };
 
-// Record lines (pg_record_lines.hip): one descriptor per index contig that takes part, in contig order, and one
-// RLinesMember per member of each, members[mem0 .. mem0 + S) in member order: record r's text = text[off[r] .. off[r + 1]).
+// Record lines (pg_record_lines.hip): one descriptor per index contig that takes part, in contig order,
+// and one RLinesMember per member of each, members[mem0 .. mem0 + S) in member order: record r's text = text[off[r] .. off[r + 1]).
 // Blocks [blk0, next blk0) of k_rlines_len take pgk_rlines_block() LINES of the contig each; workgroups [eblk0, next eblk0)
-// of k_rlines_emit take lpw = pgk_rlines_lines_per_wave(S) lines each.  line0 = the contig's first line among all lines of
-// the launch (the offsets and the packed bytes are the launch's).  prefix r = prefix[prefix_off[r] .. prefix_off[r + 1]).
+// of k_rlines_emit take lpw = pgk_rlines_lines_per_wave(S, slotted) lines each, `slotted` the launch's.  line0 = the contig's
+// first line among all lines of the launch (the offsets and the packed bytes are the launch's).  prefix r =
+// prefix[prefix_off[r] .. prefix_off[r + 1]).  The fields from `slot` on are read by a slotted launch alone: where the UK of
+// every record goes and comes from.  slot null: a plain prefix.  Otherwise record r's digits stand in front of byte slot[r]
+// of its prefix; UK = uk[r] (the unit entry point), or without `uk` the k-mer count of bubble rec_var[r] of DevContig `chain`,
+// the contig's first member, under pg_job_fetch's rule.
 struct RLinesMember {
     const uint64_t* off;
     const char* text;
@@ -141,14 +145,6 @@ struct RLinesDesc {
     uint32_t mem0, S;
     const uint64_t* prefix_off;
     const char* prefix;
-};
-// Record lines over a slotted prefix (pg_record_lines_slot.hip): RLinesDesc with lpw =
-// pgk_rlines_slot_lines_per_wave(S), and where the UK of every record goes and comes from.  slot null: a plain prefix, the
-// line of pg_record_lines.hip.  Otherwise record r's digits stand in front of byte slot[r] of its prefix; UK = uk[r] (the
-// unit entry point), or without `uk` the k-mer count of bubble rec_var[r] of DevContig `chain`, the contig's first member,
-// under pg_job_fetch's rule.
-struct RLinesSlotDesc {
-    RLinesDesc l;
     const uint32_t* slot;
     const uint16_t* uk;
     const uint32_t* rec_var;
@@ -156,18 +152,15 @@ struct RLinesSlotDesc {
 };
 
 extern "C" {
-// pg_record_lines_slot.hip: the arrays of pgk_launch_rlines; d_contigs may be null if no descriptor reads a chain
-void pgk_launch_rlines_slot(const DevContig* d_contigs, const RLinesSlotDesc* d_desc, uint32_t n_desc, const RLinesMember* d_members, uint32_t n_blocks,
-                            uint32_t n_emit_blocks, uint32_t* d_loc, uint32_t* d_bsum, uint64_t* d_bbase, uint64_t* d_off, uint64_t n_lines, char* d_out,
-                            uint64_t cap, hipStream_t s);
-uint32_t pgk_rlines_slot_lines_per_wave(uint32_t n_members);
 // pg_record_lines.hip: d_loc [n_lines], d_bsum [n_blocks], d_bbase [n_blocks + 1]: the scan's; d_off [n_lines + 1] = every
-// line's first byte in d_out (`cap` bytes of room), the total behind the last
-void pgk_launch_rlines(const RLinesDesc* d_desc, uint32_t n_desc, const RLinesMember* d_members, uint32_t n_blocks, uint32_t n_emit_blocks, uint32_t* d_loc,
-                       uint32_t* d_bsum, uint64_t* d_bbase, uint64_t* d_off, uint64_t n_lines, char* d_out, uint64_t cap, hipStream_t s);
+// line's first byte in d_out (`cap` bytes of room), the total behind the last.  slotted: the kernels that read the
+// descriptors' slot fields; d_contigs may be null if no descriptor reads a chain
+void pgk_launch_rlines(const DevContig* d_contigs, const RLinesDesc* d_desc, uint32_t n_desc, const RLinesMember* d_members, bool slotted, uint32_t n_blocks,
+                       uint32_t n_emit_blocks, uint32_t* d_loc, uint32_t* d_bsum, uint64_t* d_bbase, uint64_t* d_off, uint64_t n_lines, char* d_out,
+                       uint64_t cap, hipStream_t s);
 uint32_t pgk_rlines_block(void);
 uint32_t pgk_rlines_stage_bytes(void);
-uint32_t pgk_rlines_lines_per_wave(uint32_t n_members);
+uint32_t pgk_rlines_lines_per_wave(uint32_t n_members, bool slotted);
 // pg_record_text.hip: d_wide = uint2 {descriptor, record} of every record with more than pgk_rtext_wide_values() values;
 // d_loc [n_records], d_wlen [n_wide], d_bsum [n_blocks], d_bbase [n_blocks + 1]: the scan's; d_off [n_records + 1] = every
 // record's first byte in d_text (`cap` bytes of room), the total behind the last.  The two events (or null) go around

@@ -1,4 +1,4 @@
-// pg_shim_lines.cpp — the C-ABI of the record lines (pg_record_lines.hip; pg_record_lines_slot.hip, 4e-8):
+// pg_shim_lines.cpp — the C-ABI of the record lines (pg_record_lines.hip):
 // the prefix of an index contig or of a stride of them, plain or slotted, the forming of whole VCF lines from a job's record
 // text, their fetches, and the unit entry points over host arrays.  Host code off the critical path.
 #include <hip/hip_runtime_api.h>
@@ -32,37 +32,25 @@ struct RLinesLayout {
 };
 
 // one more contig of R records and S members behind those of `desc`: its blocks of both kernels, its first line and member.
-// slot_kernels: the launch goes through pg_record_lines_slot.hip, whose waves take other runs of lines.
-void rlines_add(std::vector<RLinesSlotDesc>* desc, bool slot_kernels, uint32_t R, uint32_t S, uint32_t* blk, uint32_t* eblk, uint64_t* line, uint32_t* mem) {
-    RLinesSlotDesc sd;
-    memset(&sd, 0, sizeof(sd));
-    RLinesDesc& d = sd.l;
+// slotted: the launch's kernels are the slotted ones, whose waves take other runs of lines.
+RLinesDesc& rlines_add(std::vector<RLinesDesc>* desc, bool slotted, uint32_t R, uint32_t S, uint32_t* blk, uint32_t* eblk, uint64_t* line, uint32_t* mem) {
+    RLinesDesc d;
+    memset(&d, 0, sizeof(d));
     const uint32_t per = pgk_rlines_block();
-    d.blk0 = *blk; d.R = R; d.eblk0 = *eblk; d.lpw = slot_kernels ? pgk_rlines_slot_lines_per_wave(S) : pgk_rlines_lines_per_wave(S);
+    d.blk0 = *blk; d.R = R; d.eblk0 = *eblk; d.lpw = pgk_rlines_lines_per_wave(S, slotted);
     d.line0 = *line; d.mem0 = *mem; d.S = S;
     *blk += (R + per - 1) / per;
     *eblk += (R + d.lpw - 1) / d.lpw;
     *line += R;
     *mem += S;
-    desc->push_back(sd);
+    desc->push_back(d);
+    return desc->back();
 }
 
-// the descriptors as the kernels of the launch read them: whole (slot kernels) or their RLinesDesc alone
-std::vector<unsigned char> rlines_desc_bytes(const std::vector<RLinesSlotDesc>& desc, bool slot_kernels) {
-    const size_t each = slot_kernels ? sizeof(RLinesSlotDesc) : sizeof(RLinesDesc);
-    std::vector<unsigned char> b(desc.size() * each);
-    for (size_t i = 0; i < desc.size(); ++i) memcpy(b.data() + i * each, slot_kernels ? (const void*)&desc[i] : (const void*)&desc[i].l, each);
-    return b;
-}
-
-void rlines_launch(unsigned char* d, const RLinesLayout& L, bool slot_kernels, const DevContig* d_contigs, uint32_t n_desc, uint32_t n_blocks,
-                   uint32_t n_eblocks, uint64_t n_lines, uint64_t cap, hipStream_t s) {
-    if (slot_kernels)
-        pgk_launch_rlines_slot(d_contigs, (const RLinesSlotDesc*)(d + L.o_desc), n_desc, (const RLinesMember*)(d + L.o_members), n_blocks, n_eblocks,
-                               (uint32_t*)(d + L.o_loc), (uint32_t*)(d + L.o_bsum), (uint64_t*)(d + L.o_bbase), (uint64_t*)(d + L.o_off), n_lines, (char*)d, cap, s);
-    else
-        pgk_launch_rlines((const RLinesDesc*)(d + L.o_desc), n_desc, (const RLinesMember*)(d + L.o_members), n_blocks, n_eblocks, (uint32_t*)(d + L.o_loc),
-                          (uint32_t*)(d + L.o_bsum), (uint64_t*)(d + L.o_bbase), (uint64_t*)(d + L.o_off), n_lines, (char*)d, cap, s);
+void rlines_launch(unsigned char* d, const RLinesLayout& L, bool slotted, const DevContig* d_contigs, uint32_t n_desc, uint32_t n_blocks, uint32_t n_eblocks,
+                   uint64_t n_lines, uint64_t cap, hipStream_t s) {
+    pgk_launch_rlines(d_contigs, (const RLinesDesc*)(d + L.o_desc), n_desc, (const RLinesMember*)(d + L.o_members), slotted, n_blocks, n_eblocks,
+                      (uint32_t*)(d + L.o_loc), (uint32_t*)(d + L.o_bsum), (uint64_t*)(d + L.o_bbase), (uint64_t*)(d + L.o_off), n_lines, (char*)d, cap, s);
 }
 
 bool text_current(const pg_job* job) {
@@ -212,9 +200,9 @@ extern "C" int pg_job_record_lines(pg_job* job, char* err, size_t errlen) {
     auto takes_part = [&](size_t ix) {
         return ix < job->rplans.size() && job->rplans[ix] && ix < f.prefix.size() && f.prefix[ix] && !chains_of[ix].empty() && job->rplans[ix]->R != 0;
     };
-    bool slot_kernels = false;   // one slotted prefix among the contigs that take part: the launch is pg_record_lines_slot.hip's
-    for (size_t ix = 0; ix < n_index; ++ix) slot_kernels |= takes_part(ix) && f.prefix[ix]->o_slot != 0;
-    std::vector<RLinesSlotDesc> desc;
+    bool slotted = false;   // one slotted prefix among the contigs that take part: the launch is the slotted kernels'
+    for (size_t ix = 0; ix < n_index; ++ix) slotted |= takes_part(ix) && f.prefix[ix]->o_slot != 0;
+    std::vector<RLinesDesc> desc;
     std::vector<RLinesMember> members;
     std::vector<size_t> contig_of;   // the index contig of every descriptor
     uint32_t blk = 0, eblk = 0, mem = 0;
@@ -235,20 +223,18 @@ extern "C" int pg_job_record_lines(pg_job* job, char* err, size_t errlen) {
             members.push_back(m);
             text_bytes += t.text_first[c + 1] - t.text_first[c];
         }
-        rlines_add(&desc, slot_kernels, R, S, &blk, &eblk, &line, &mem);
-        RLinesSlotDesc& sd = desc.back();
-        sd.l.prefix_off = (const uint64_t*)px.d;
-        sd.l.prefix = (const char*)(px.d + px.o_bytes);
+        RLinesDesc& d = rlines_add(&desc, slotted, R, S, &blk, &eblk, &line, &mem);
+        d.prefix_off = (const uint64_t*)px.d;
+        d.prefix = (const char*)(px.d + px.o_bytes);
         if (px.o_slot) {   // UK: the first member's count of the record's bubble
-            sd.slot = (const uint32_t*)(px.d + px.o_slot);
-            sd.rec_var = job->rplans[ix]->dev.rec_var;
-            sd.chain = chains_of[ix][0];
+            d.slot = (const uint32_t*)(px.d + px.o_slot);
+            d.rec_var = job->rplans[ix]->dev.rec_var;
+            d.chain = chains_of[ix][0];
         }
         contig_of.push_back(ix);
         cap += px.o_slot ? pg_record_lines_bound_slotted(R, S, px.bytes, text_bytes) : pg_record_lines_bound(R, S, px.bytes, text_bytes);
     }
-    const std::vector<unsigned char> desc_bytes = rlines_desc_bytes(desc, slot_kernels);
-    const RLinesLayout L(cap, line, blk, desc_bytes.size(), members.size());
+    const RLinesLayout L(cap, line, blk, desc.size() * sizeof(RLinesDesc), members.size());
     if (!f.d || f.alloc < L.total) {
         unsigned char* d = nullptr;
         if (hipMalloc((void**)&d, L.total) != hipSuccess) { (void)hipGetLastError(); set_err(err, errlen, "hipMalloc of %zu bytes for the record lines failed", L.total); return PG_ERR_NOMEM; }
@@ -262,7 +248,7 @@ extern "C" int pg_job_record_lines(pg_job* job, char* err, size_t errlen) {
     f.ms = 0.0;
     if (!desc.empty()) {
         hipStream_t s = job->stream;
-        HIP_TRY(hipMemcpyAsync(f.d + L.o_desc, desc_bytes.data(), desc_bytes.size(), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(f.d + L.o_desc, desc.data(), desc.size() * sizeof(RLinesDesc), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(f.d + L.o_members, members.data(), members.size() * sizeof(RLinesMember), hipMemcpyHostToDevice, s));
         if (!job->calls_events) {
             HIP_TRY(hipEventCreate(&job->ev_calls[0]));
@@ -270,7 +256,7 @@ extern "C" int pg_job_record_lines(pg_job* job, char* err, size_t errlen) {
             job->calls_events = true;
         }
         HIP_TRY(hipEventRecord(job->ev_calls[0], s));
-        rlines_launch(f.d, L, slot_kernels, job->d_contigs, (uint32_t)desc.size(), blk, eblk, line, cap, s);
+        rlines_launch(f.d, L, slotted, job->d_contigs, (uint32_t)desc.size(), blk, eblk, line, cap, s);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(job->ev_calls[1], s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -282,8 +268,8 @@ extern "C" int pg_job_record_lines(pg_job* job, char* err, size_t errlen) {
         if (bbase.back() > cap) { set_err(err, errlen, "the record lines take %llu bytes, more than their bound %llu", (unsigned long long)bbase.back(), (unsigned long long)cap); return PG_ERR_DEVICE; }
         size_t i = 0;   // a contig begins a block: its first byte is that block's
         for (size_t ix = 0; ix < n_index; ++ix) {
-            f.line_first[ix] = i < desc.size() ? desc[i].l.line0 : line;
-            f.byte_first[ix] = i < desc.size() ? bbase[desc[i].l.blk0] : bbase.back();
+            f.line_first[ix] = i < desc.size() ? desc[i].line0 : line;
+            f.byte_first[ix] = i < desc.size() ? bbase[desc[i].blk0] : bbase.back();
             if (i < desc.size() && contig_of[i] == ix) ++i;
         }
         f.line_first[n_index] = line;
@@ -337,16 +323,12 @@ extern "C" int pg_job_device_record_lines(pg_job* job, uint32_t ix, void** d_off
 
 namespace {
 
-// The unit entry points: arbitrary bytes in, the packed lines and their offsets out, through the kernels of a job — those of
-// pg_record_lines_slot.hip with slot_kernels (slot and uk may then be null: a descriptor without slots), else the plain ones.
+// The unit entry points: arbitrary bytes in, the packed lines and their offsets out, through the kernels of a job — the
+// slotted ones with `slotted` (slot and uk may then be null: a descriptor without slots), else the plain ones.
 int rlines_from_text(int device, uint64_t n_records, uint64_t n_members, const uint64_t* const* off, const char* const* text, const uint64_t* prefix_off,
-                     const char* prefix, const uint32_t* slot, const uint16_t* uk, bool slot_kernels, uint64_t* out_off, char* out, uint64_t cap) {
-    if (!out_off || !off || !text || !prefix_off || n_members == 0 || n_members >= 0x80000000ull - (slot_kernels ? 4 : 2) || n_records >= 0x80000000ull) return PG_ERR_INVALID;
-    if (!offsets_ok(prefix_off, n_records) || (prefix_off[n_records] && !prefix)) return PG_ERR_INVALID;
-    if (slot && !uk) return PG_ERR_INVALID;
-    if (slot)
-        for (uint64_t r = 0; r < n_records; ++r)
-            if (slot[r] > prefix_off[r + 1] - prefix_off[r]) return PG_ERR_INVALID;
+                     const char* prefix, const uint32_t* slot, const uint16_t* uk, bool slotted, uint64_t* out_off, char* out, uint64_t cap) {
+    if (!out_off || !off || !text || !prefix_off || n_members == 0 || n_members >= 0x80000000ull - (slotted ? 4 : 2) || n_records >= 0x80000000ull) return PG_ERR_INVALID;
+    if (check_prefix((uint32_t)n_records, prefix_off, prefix, slot, nullptr, 0) != PG_OK || (slot && !uk)) return PG_ERR_INVALID;
     uint64_t text_bytes = 0;
     for (uint64_t s = 0; s < n_members; ++s) {
         if (!offsets_ok(off[s], n_records) || (off[s][n_records] && !text[s])) return PG_ERR_INVALID;
@@ -360,11 +342,11 @@ int rlines_from_text(int device, uint64_t n_records, uint64_t n_members, const u
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); return PG_ERR_DEVICE; }
     if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return PG_ERR_DEVICE;
     const uint32_t R = (uint32_t)n_records, S = (uint32_t)n_members;
-    std::vector<RLinesSlotDesc> desc;
+    std::vector<RLinesDesc> desc;
     uint32_t blk = 0, eblk = 0, mem = 0;
     uint64_t line = 0;
-    rlines_add(&desc, slot_kernels, R, S, &blk, &eblk, &line, &mem);
-    const RLinesLayout L(bound, R, blk, sizeof(RLinesSlotDesc), S);
+    rlines_add(&desc, slotted, R, S, &blk, &eblk, &line, &mem);
+    const RLinesLayout L(bound, R, blk, sizeof(RLinesDesc), S);
     // the inputs behind the launch's own arrays: the prefix (offsets, bytes, slots, UK), then member after member (offsets, bytes)
     const size_t offs_bytes = align_up(((size_t)R + 1) * 8);
     std::vector<size_t> o_moff(S), o_mtext(S);
@@ -381,11 +363,10 @@ int rlines_from_text(int device, uint64_t n_records, uint64_t n_members, const u
     if (hipMalloc((void**)&d, at) != hipSuccess) { (void)hipGetLastError(); return PG_ERR_NOMEM; }
     std::vector<RLinesMember> members(S);
     for (uint32_t s = 0; s < S; ++s) { members[s].off = (const uint64_t*)(d + o_moff[s]); members[s].text = (const char*)(d + o_mtext[s]); }
-    desc[0].l.prefix_off = (const uint64_t*)(d + o_poff);
-    desc[0].l.prefix = (const char*)(d + o_pbytes);
+    desc[0].prefix_off = (const uint64_t*)(d + o_poff);
+    desc[0].prefix = (const char*)(d + o_pbytes);
     if (slot) { desc[0].slot = (const uint32_t*)(d + o_slot); desc[0].uk = (const uint16_t*)(d + o_uk); }
-    const std::vector<unsigned char> desc_bytes = rlines_desc_bytes(desc, slot_kernels);
-    bool ok = hipMemcpy(d + L.o_desc, desc_bytes.data(), desc_bytes.size(), hipMemcpyHostToDevice) == hipSuccess &&
+    bool ok = hipMemcpy(d + L.o_desc, desc.data(), sizeof(RLinesDesc), hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(d + L.o_members, members.data(), (size_t)S * sizeof(RLinesMember), hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(d + o_poff, prefix_off, ((size_t)R + 1) * 8, hipMemcpyHostToDevice) == hipSuccess &&
               (prefix_off[R] == 0 || hipMemcpy(d + o_pbytes, prefix, prefix_off[R], hipMemcpyHostToDevice) == hipSuccess) &&
@@ -395,7 +376,7 @@ int rlines_from_text(int device, uint64_t n_records, uint64_t n_members, const u
         ok = hipMemcpy(d + o_moff[s], off[s], ((size_t)R + 1) * 8, hipMemcpyHostToDevice) == hipSuccess &&
              (off[s][R] == 0 || hipMemcpy(d + o_mtext[s], text[s], off[s][R], hipMemcpyHostToDevice) == hipSuccess);
     if (ok) {
-        rlines_launch(d, L, slot_kernels, nullptr, 1, blk, eblk, R, bound, nullptr);
+        rlines_launch(d, L, slotted, nullptr, 1, blk, eblk, R, bound, nullptr);
         ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess &&
              hipMemcpy(out_off, d + L.o_off, ((size_t)R + 1) * 8, hipMemcpyDeviceToHost) == hipSuccess && out_off[R] <= bound &&
              (out_off[R] == 0 || hipMemcpy(out, d, out_off[R], hipMemcpyDeviceToHost) == hipSuccess);

@@ -1,6 +1,6 @@
 // pg_text_scan.h — the device helpers the units of packed text share (pg_record_text.hip: the bytes of a sample column;
-// pg_record_lines.hip: whole VCF lines; pg_record_lines_slot.hip: those over a slotted prefix): the wave scan, the block scan,
-// the scan of the block sums and the flush of an LDS stage to its contiguous byte range.  Device code only; each unit keeps
+// pg_record_lines.hip: whole VCF lines, over plain and slotted prefixes): the wave scan, the block scan, the scan of the
+// block sums and the flush of an LDS stage to its contiguous byte range.  Device code only; each unit keeps
 // its own kernels.
 #pragma once
 #include <hip/hip_runtime.h>

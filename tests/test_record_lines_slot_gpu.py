@@ -1,6 +1,6 @@
 """The record lines of jobs whose chains are index contigs of their own, over ONE slotted prefix per stride of chains
-(pg_job_line_prefix_strided, pg_job_line_prefix_slotted, pg_job_record_lines; k_rlslot_* of
-pangenie_amd/csrc/pg_record_lines_slot.hip).  (a) 3 x 2 chains over 2 panels, the three members of a stride
+(pg_job_line_prefix_strided, pg_job_line_prefix_slotted, pg_job_record_lines; the SLOT instantiation of k_rlines_* of
+pangenie_amd/csrc/pg_record_lines.hip).  (a) 3 x 2 chains over 2 panels, the three members of a stride
 reduced to different paths: the same bubbles, allele ids of one id space, other k-mer counts per bubble.  (b) the same through
 sampler.sample_cohort, 24 paths sampled to 5 and the reference path.  In both the test asserts that some record's UK differs
 between two members of a stride, and every chain's lines are compared byte for byte with the join, in Python, of the chain's

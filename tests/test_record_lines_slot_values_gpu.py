@@ -1,5 +1,5 @@
-"""The record lines over a slotted prefix through the unit entry point (pg_record_lines_from_text_slotted; k_rlslot_* of
-pangenie_amd/csrc/pg_record_lines_slot.hip): arbitrary bytes in, the packed lines out, compared byte for byte with the plain
+"""The record lines over a slotted prefix through the unit entry point (pg_record_lines_from_text_slotted; the SLOT instantiation
+of k_rlines_* of pangenie_amd/csrc/pg_record_lines.hip): arbitrary bytes in, the packed lines out, compared byte for byte with the plain
 Python join
     prefix[r][:slot[r]] + str(uk[r]) + prefix[r][slot[r]:] + b"".join(b"\\t" + text_s[r] for s) + b"\\n"
 (nothing, if a text_s[r] is empty).  The shapes are the kernels' seams: 1, 255, 256, 257 and 1025 records (a block of the scan

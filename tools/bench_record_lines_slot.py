@@ -7,8 +7,8 @@ differ in UK only.
   (a)  what the C ABI offered before: one pg_job_line_prefix per CHAIN with that chain's UK already in the bytes (the bytes are
        put together before the clock starts: the fetch of every chain's k-mer counts and the formatting are NOT in (a)'s time),
        pg_job_record_lines — the plain kernels of pg_record_lines.hip —, the packed fetch;
-  (b)  one pg_job_line_prefix_strided per CONTIG with a slot per record, pg_job_record_lines — the kernels of
-       pg_record_lines_slot.hip, which print every chain's UK at the slot —, the packed fetch.
+  (b)  one pg_job_line_prefix_strided per CONTIG with a slot per record, pg_job_record_lines — the slotted kernels of
+       pg_record_lines.hip, which print every chain's UK at the slot —, the packed fetch.
 
 One process, one warm-up, several repeats with their spread, the two routes alternating inside every repeat; each route starts
 from a job without prefixes (the other route's are dropped off the clock, by attaching the plans anew).  Asserts that both
