@@ -2909,7 +2909,6 @@ template <int R>
 struct LeanShared {
     static constexpr int NW = 64 / R;  // waves = row groups
     double psum[2][NW][64];
-    double ptot[2][NW] __attribute__((aligned(32)));   // the waves' totals of their partial sums (kLeanPreTotal: lean_put_sums)
     double u[NW][64] __attribute__((aligned(16)));
     double scal[2][64];   // per-column scalars on their way out (ColScalars)
     // The record ring: two blocks of PG_LEAN_BLOCK column records, ONE image of PG_LEAN_IMAGE bytes per record — everything a step
@@ -3103,24 +3102,7 @@ template <int R>
 DEVI void lean_pairs_all(const LeanPairs& lp, double (&e)[R]) {
     static_for<0, R / 2>([&](auto pc) __attribute__((always_inline)) { constexpr int q = decltype(pc)::value; const v2f64 t = lean_pair<q>(lp); e[2 * q] = t.x; e[2 * q + 1] = t.y; });
 }
-// -DPG_LEAN_PAIRS_EXP=2 (measured and NOT adopted — profiles/r21_lean_pairs.txt: 0.7 ms slower on genome24_h64 in every run): the eight
-// emission addresses of a column formed AHEAD of the state block, in the shadow of the total's second MFMA (nothing in them needs
-// the total).  Plain C++ on pair bytes the compiler may not know to be wave-uniform (it would pull them to the scalar unit:
-// v_readfirstlane and eight s_bfe): it selects v_add_u32_sdwa itself, and an instruction of its own counts towards the wait
-// states of the MFMA it stands behind — what an asm statement holds does not.  Every address is pinned where it is formed.
-// The pad in that shadow shrinks by the eight adds and the state block loses them, but the step is no shorter: the wave waits
-// for the total either way, and eight more registers are live over the states.
-template <int R>
-DEVI void lean_pair_addrs(const LeanPairs& lp, uint32_t (&ea)[R / 2]) {
-    uint32_t cd0 = lp.cd0, cd1 = lp.cd1;
-    asm("" : "+v"(cd0));
-    asm("" : "+v"(cd1));
-    static_for<0, R / 2>([&](auto pc) __attribute__((always_inline)) {
-        constexpr int q = decltype(pc)::value;
-        ea[q] = lp.tbase + (((q < 4 ? cd0 : cd1) >> (8 * (q & 3))) & 0xFFu);
-        asm volatile("" : "+v"(ea[q]));
-    });
-}
+// (The eight emission addresses formed ahead of the state block, in the second MFMA's shadow: measured slower — profiles/r21_lean_pairs.txt.)
 // The sixteen states of a column step, by row pairs.  State k: acc = a x[k] + b, acc += u[row k] s (fmac_row_bcast: an asm statement),
 // part = fma(e[k], acc, part), x[k] = e[k] acc — the same operations on the same operands in either role (forward a = c0, b = u_j,
 // s = 2^-es; backward a = k0, b = u_j, s = 1), `part` added up row after row.  hipcc pads an asm statement whose result the NEXT VALU
@@ -3131,30 +3113,21 @@ DEVI void lean_pair_addrs(const LeanPairs& lp, uint32_t (&ea)[R / 2]) {
 template <int R, class PairDone>
 DEVI double lean_states(double a, double b, double urep, double s, double (&x)[R], double (&e)[R], PairDone&& pair_done) {
     double part = 0.0;
-    constexpr bool kFirstProduct = !(kLeanPairsExp & 4u);
     static_for<0, R / 2>([&](auto pc) __attribute__((always_inline)) {
         constexpr int q = decltype(pc)::value, k = 2 * q;
         auto product = [&](auto kc, double pk) __attribute__((always_inline)) {
             constexpr int j = decltype(kc)::value;
-            if constexpr (j == 0 && kFirstProduct) { x[0] = e[0] * pk; part = x[0]; }   // (not pinned: x[0] and the sum are one register until the next state)
+            if constexpr (j == 0) { x[0] = e[0] * pk; part = x[0]; }   // (not pinned: x[0] and the sum are one register until the next state)
             else { part = fma(e[j], pk, part); x[j] = e[j] * pk; pin_here(x[j]); }
         };
-        if constexpr (kLeanPairsExp & 1u) {
-            const double pa = fmac_row_bcast<k>(fma(a, x[k], b), urep, s);
-            product(std::integral_constant<int, k>{}, pa);
-            const double pb = fmac_row_bcast<k + 1>(fma(a, x[k + 1], b), urep, s);
-            product(std::integral_constant<int, k + 1>{}, pb);
-            pair_done(pc, pa, pb);
-        } else {
-            const double pa = fmac_row_bcast<k>(fma(a, x[k], b), urep, s);
-            lean_fence();
-            const double pb = fmac_row_bcast<k + 1>(fma(a, x[k + 1], b), urep, s);
-            lean_fence();
-            product(std::integral_constant<int, k>{}, pa);
-            lean_fence();
-            product(std::integral_constant<int, k + 1>{}, pb);
-            pair_done(pc, pa, pb);
-        }
+        const double pa = fmac_row_bcast<k>(fma(a, x[k], b), urep, s);
+        lean_fence();
+        const double pb = fmac_row_bcast<k + 1>(fma(a, x[k + 1], b), urep, s);
+        lean_fence();
+        product(std::integral_constant<int, k>{}, pa);
+        lean_fence();
+        product(std::integral_constant<int, k + 1>{}, pb);
+        pair_done(pc, pa, pb);
         lean_fence();
     });
     return part;
@@ -3185,7 +3158,7 @@ DEVI v2f64 lean_ring_open(SH& sh, const LeanRecs& recs, uint32_t s0 /*uniform*/,
 constexpr int kUpkeepTested = -1, kUpkeepNone = 0, kUpkeepPark = 1, kUpkeepExpand = 2;
 template <int UPKEEP, class SH>
 DEVI void lean_ring_upkeep(SH& sh, const LeanRecs& recs, v2f64& piece, uint32_t n /*uniform*/, uint32_t tid) {
-    if constexpr (UPKEEP == kUpkeepTested || (kLeanUpkeepExp & 1u)) {
+    if constexpr (UPKEEP == kUpkeepTested) {
         if (((n + 4u) % PG_LEAN_BLOCK) == 0u) {       // (uniform) a few columns before the next block is needed
             const uint32_t blk = (n + 4u) / PG_LEAN_BLOCK;
             recs.park(sh, blk, piece);
@@ -3253,34 +3226,14 @@ DEVI void chunk_wait_buffer(uint32_t* flag, uint32_t want, uint32_t* err) {   //
     __syncthreads();
 }
 
-// A wave parks its 64 partial column sums — and (kLeanPreTotal, round 6) their TOTAL over the wave, formed in front of the step's
-// barrier by six DPP levels (the sum ends in lane 63, which stores it): behind the barrier the column's total S is then three
-// additions of four broadcast LDS reads, next to the column sums — instead of two dependent fp64 MFMAs behind them
-// (profiles/r06_lean_chain.txt: the exchange -> column sums -> MFMA -> MFMA -> exponent chain was 756 of a column's 1384 cycles).
-// a column store of the lean sweeps (-DPG_NT_STORES: as a non-temporal store — the columns are streamed out and never read by this kernel)
-DEVI void lean_store(gdouble2* p, v2f64 v) {
-    if constexpr (kNtStores) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
+// a column store of the lean sweeps (as a non-temporal store: no gain — profiles/r06_persist.txt §5); a function, so that the address is formed
+// in front of the value: the triangle kernels' schedule hangs on it (profiles/r29_dead_variants.txt)
+DEVI void lean_store(gdouble2* p, v2f64 v) { *p = v; }
+// A wave parks its 64 partial column sums.
+// (Their total over the wave formed here as well, in front of the barrier: + 3.6 % per column — profiles/r06_lean_chain.txt.)
 template <int R>
 DEVI void lean_put_sums(LeanShared<R>& sh, uint32_t pb, uint32_t wave, uint32_t lane, double part) {
     sh.psum[pb][wave][lane] = part;
-    if constexpr (kLeanPreTotal) {
-        double v = part;
-        v += dpp_f64<0x111, 0xF, true>(v);   // row_shr:1
-        v += dpp_f64<0x112, 0xF, true>(v);   // row_shr:2
-        v += dpp_f64<0x114, 0xF, true>(v);   // row_shr:4
-        v += dpp_f64<0x118, 0xF, true>(v);   // row_shr:8
-        v += dpp_f64<0x142, 0xA, false>(v);  // row_bcast:15 -> rows 1,3
-        v += dpp_f64<0x143, 0xC, false>(v);  // row_bcast:31 -> rows 2,3
-        if (lane == 63u) sh.ptot[pb][wave] = v;
-    }
-}
-template <int R>
-DEVI double lean_total(const LeanShared<R>& sh, uint32_t pb) {   // (kLeanPreTotal) the column's total: every lane reads the waves' totals
-    static_assert(R == 16, "four waves");
-    const v2f64 a = *(const v2f64*)&sh.ptot[pb][0], b = *(const v2f64*)&sh.ptot[pb][2];
-    return (a.x + a.y) + (b.x + b.y);
 }
 
 // SPARSE (PHASE 1 of DevContig::sparse chains): only the checkpoints of pg_device.h's pg_sparse_* are stored — the step is compiled
@@ -3302,9 +3255,6 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
     static_assert(!SPARSE || ((PHASE == 1 || PHASE == 3) && !TRI), "sparse stores: phases 1 and 3 of full-column lean chains");
     constexpr int HP = 64;
     constexpr uint32_t RMASK = (1u << R) - 1u;
-    // (-DPG_LEAN_PAIRS_EXP=2, measured and not adopted: the pairs' emission addresses formed ahead of the total — lean_pair_addrs.  Not
-    //  for the triangle kernels, which stand at 256 VGPRs: eight addresses held over the state block go to scratch there)
-    constexpr bool kAddrsAhead = !TRI && (kLeanPairsExp & 2u) != 0;
     const uint32_t mid = C / 2, K = dc.chunk_cols;
     uint32_t lo = PHASE == 1 ? 0u : mid, hi = PHASE == 1 ? mid : C;
     if constexpr (PHASE == 3) {
@@ -3447,7 +3397,7 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
 #pragma unroll
                 for (int k = 0; k < R; ++k) {
                     const double e = sel_by_bit(rb, k, eA, eB);
-                    if (k == 0 && !(kLeanPairsExp & 4u)) { x[0] *= e; part = x[0]; }
+                    if (k == 0) { x[0] *= e; part = x[0]; }
                     else { part = fma(e, x[k], part); x[k] *= e; }
                 }
             } else if ((PHASE == 5 && !boundary) || (SPARSE && PHASE == 1)) {
@@ -3489,7 +3439,6 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
             cdn = lean_pair_bytes(sh, n + 2u, wave);
             lean_ring_upkeep<UPKEEP>(sh, recs, piece, n, tid);
         };
-        if constexpr (kLeanUpkeepExp & 2u) next_record();
         const uint32_t pb = (t - 1) & 1u;
         // both column sums' partials are fetched up front (this lane's column; the column of index i0 + (lane & 15):
         // the DPP source of the wave's sixteen u_i); everything that does not need the total S — the second sum, the
@@ -3497,17 +3446,15 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         double pc[64 / R], pr[64 / R];
 #pragma unroll
         for (int q = 0; q < 64 / R; ++q) { pc[q] = sh.psum[pb][q][lane]; pr[q] = sh.psum[pb][q][i0 + (lane & 15u)]; }
-        const double Spre = kLeanPreTotal ? lean_total<R>(sh, pb) : 0.0;   // (issued with the other LDS reads)
         // the column sums head the step's dependent chain: the record of the next step and the block upkeep come behind them
-        if constexpr (!(kLeanUpkeepExp & 2u)) {
-            lean_fence();
-            next_record();
-            lean_fence();
-        }
+        // (the record read ahead of the sums: measured, not adopted — profiles/r18_lean_upkeep.txt)
+        lean_fence();
+        next_record();
+        lean_fence();
         const double Cj = (pc[0] + pc[1]) + (pc[2] + pc[3]);
         tl.template mark<1>(Cj);                      // the column sums are back from LDS
         const v4f64 zz = {0.0, 0.0, 0.0, 0.0};
-        const v4f64 ma = (kLeanDppSum || kLeanPreTotal) ? zz : __builtin_amdgcn_mfma_f64_16x16x4f64(Cj, 1.0, zz, 0, 0, 0);
+        const v4f64 ma = __builtin_amdgcn_mfma_f64_16x16x4f64(Cj, 1.0, zz, 0, 0, 0);
         lean_fence();
         const double ucol = cur.c1 * Cj;
         const double urep = dpp_source(cur.c1 * ((pr[0] + pr[1]) + (pr[2] + pr[3])));
@@ -3515,12 +3462,10 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
         const double msum = (ma[0] + ma[1]) + (ma[2] + ma[3]);
         tl.template mark<2>(msum);                    // first MFMA + three adds
         lean_fence();
-        const v4f64 mb = (kLeanDppSum || kLeanPreTotal) ? zz : __builtin_amdgcn_mfma_f64_16x16x4f64(msum, 1.0, zz, 0, 0, 0);
-        uint32_t ea[R / 2];   // (kAddrsAhead: where the pairs' emissions of column t+1 lie, formed here, in the second MFMA's shadow)
-        if constexpr (kAddrsAhead) lean_pair_addrs<R>(lp, ea);
-        if constexpr (!kLeanPreTotal) asm volatile("" :: "v"(mb));   // (the whole result stays allocated: a temporary in one of its registers would wait out the MFMA)
+        const v4f64 mb = __builtin_amdgcn_mfma_f64_16x16x4f64(msum, 1.0, zz, 0, 0, 0);
+        asm volatile("" :: "v"(mb));   // (the whole result stays allocated: a temporary in one of its registers would wait out the MFMA)
         lean_fence();
-        double S = (kLeanExp & 4) ? 64.0 * Cj : (kLeanPreTotal ? Spre : (kLeanDppSum ? wave_sum(Cj) : mb[0]));
+        double S = (kLeanExp & 4) ? 64.0 * Cj : mb[0];
         tl.template mark<3>(S);                       // second MFMA: the total
         double uj = fma(cur.c2, S, ucol);
         double c0 = cur.c0;
@@ -3548,8 +3493,7 @@ DEVI void lean_forward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint3
             if constexpr (STORE) { if (!(kLeanExp & 1)) put_pair(dst, q, pa, pb2); }
             v2f64 t2;   // e_{t+1} of this row pair
             if constexpr (kLeanExp & 2) t2 = v2f64{0.5, 0.5};
-            else if constexpr (!kAddrsAhead) t2 = lean_pair<q>(lp);
-            else t2 = *(LAS const v2f64*)(uintptr_t)ea[q];
+            else t2 = lean_pair<q>(lp);
             ec[2 * q] = t2.x; ec[2 * q + 1] = t2.y;
         });
         tl.template mark<6>(part);                    // the other seven row pairs: states, stores, next emissions
@@ -3662,7 +3606,6 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
     static_assert(!SPARSE || ((PHASE == 1 || PHASE == 3) && !TRI), "sparse stores: phases 1 and 3 of full-column lean chains");
     constexpr int HP = 64;
     constexpr uint32_t RMASK = (1u << R) - 1u;
-    constexpr bool kAddrsAhead = !TRI && (kLeanPairsExp & 2u) != 0;   // (see lean_forward)
     const int64_t mid = C / 2, K = dc.chunk_cols;
     int64_t top = PHASE == 1 ? (int64_t)C - 1 : mid - 1;
     int64_t bot = PHASE == 1 ? mid : 0;
@@ -3794,7 +3737,7 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
 #pragma unroll
         for (int k = 0; k < R; ++k) {   // (as the step: see lean_forward)
             const double e = sel_by_bit(rb, k, eA, eB);
-            if (k == 0 && !(kLeanPairsExp & 4u)) { w[0] = y[0] * e; part = w[0]; }
+            if (k == 0) { w[0] = y[0] * e; part = w[0]; }
             else { part = fma(e, y[k], part); w[k] = y[k] * e; }
         }
         lean_put_sums<R>(sh, (uint32_t)t0 & 1u, wave, lane, part);
@@ -3832,7 +3775,6 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         double pc[64 / R], pr[64 / R];  // (see lean_forward)
 #pragma unroll
         for (int q = 0; q < 64 / R; ++q) { pc[q] = sh.psum[pb][q][lane]; pr[q] = sh.psum[pb][q][i0 + (lane & 15u)]; }
-        const double Spre = kLeanPreTotal ? lean_total<R>(sh, pb) : 0.0;
         // the records of the next step are read HERE, behind the barrier and behind the column sums (in front of the barrier
         // the wave would wait out their LDS latency: the barrier's release waits for every outstanding LDS operation)
         lean_fence();
@@ -3843,7 +3785,7 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         const double Cj = (pc[0] + pc[1]) + (pc[2] + pc[3]);
         tl.template mark<3>(Cj);                      // the column sums are back from LDS (the next records read behind them)
         const v4f64 zz = {0.0, 0.0, 0.0, 0.0};
-        const v4f64 ma = (kLeanDppSum || kLeanPreTotal) ? zz : __builtin_amdgcn_mfma_f64_16x16x4f64(Cj, 1.0, zz, 0, 0, 0);
+        const v4f64 ma = __builtin_amdgcn_mfma_f64_16x16x4f64(Cj, 1.0, zz, 0, 0, 0);
         lean_fence();
         const double ucol = k1 * Cj;
         const double urep = dpp_source(k1 * ((pr[0] + pr[1]) + (pr[2] + pr[3])));  // u_i of row i0 + (lane & 15)
@@ -3851,12 +3793,10 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
         const double msum = (ma[0] + ma[1]) + (ma[2] + ma[3]);
         tl.template mark<4>(msum);                    // first MFMA + three adds
         lean_fence();
-        const v4f64 mb = (kLeanDppSum || kLeanPreTotal) ? zz : __builtin_amdgcn_mfma_f64_16x16x4f64(msum, 1.0, zz, 0, 0, 0);
-        uint32_t ea[R / 2];   // (see lean_forward: the pairs' emissions of column t-1)
-        if constexpr (kAddrsAhead) lean_pair_addrs<R>(lp, ea);
-        if constexpr (!kLeanPreTotal) asm volatile("" :: "v"(mb));
+        const v4f64 mb = __builtin_amdgcn_mfma_f64_16x16x4f64(msum, 1.0, zz, 0, 0, 0);
+        asm volatile("" :: "v"(mb));
         lean_fence();
-        const double Sw = (kLeanExp & 4) ? 64.0 * Cj : (kLeanPreTotal ? Spre : (kLeanDppSum ? wave_sum(Cj) : mb[0]));
+        const double Sw = (kLeanExp & 4) ? 64.0 * Cj : mb[0];
         tl.template mark<5>(Sw);                      // second MFMA: the total
         const double uj = fma(k2, Sw, ucol);
         const double Snew = kap * Sw;  // = sum(beta'_t)
@@ -3870,8 +3810,7 @@ DEVI void lean_backward(const DevContig& dc, LeanShared<R>& sh, uint32_t C, uint
             if constexpr (STORE) { if (!(kLeanExp & 1)) put_pair(dst, q, ya, yb); }
             v2f64 t2;   // e_{t-1} of this row pair
             if constexpr (kLeanExp & 2) t2 = v2f64{0.5, 0.5};
-            else if constexpr (!kAddrsAhead) t2 = lean_pair<q>(lp);
-            else t2 = *(LAS const v2f64*)(uintptr_t)ea[q];
+            else t2 = lean_pair<q>(lp);
             ec[2 * q] = t2.x; ec[2 * q + 1] = t2.y;
         });
         if (__builtin_expect(zero, 0)) {
@@ -5013,40 +4952,11 @@ DEVI void leanx_backward(const DevContig& dc, LxShared<HP>& sh, uint32_t C, uint
 //  Until round 6 these chains ran phase 2 on the general kernel: one workgroup per CU (the ring takes the LDS), 0.45 of the HBM peak.
 // ------------------------------------------------------------------------------------------
 #define PG_LX2_PAIRS ((PG_AMAX + 1) / 2)
-#ifndef PG_LX2_TWO
-#define PG_LX2_TWO 1   // columns with at most two local alleles add into two accumulators (0: five for every column)
-#endif
-#ifndef PG_LX2_EW
-#define PG_LX2_EW 4   // emissions of a column in flight (LDS reads issued this many states ahead of their use)
-#endif
+constexpr int kLx2Ew = 4;   // emissions of a column in flight (LDS reads issued this many states ahead of their use; 2 and 8: no difference — profiles/r06_leanx2.txt)
 struct LxShared2 {
     LxShared<64> a;
     v2f64 pp[2][4][PG_LX2_PAIRS][64];   // posterior partials {row allele 2q, 2q + 1} per wave and lane, by column parity
-    // the row-allele weights: row a (at the byte offset a * 48 — a row's table-row offset IS its address here) has 1.0 at a; row
-    // PG_AMAX (a phantom path) is zeros.  A state's weights are one SDWA add + one to three broadcast LDS reads (k_sweep_small16x's
-    // scheme) instead of a compare and a select per allele on the scalar unit — the A/B build -DPG_LX2_ONEHOT=1; the product takes the
-    // scalar selects
-    double onehot[PG_ESTRIDE][PG_ESTRIDE] __attribute__((aligned(16)));
 };
-#ifndef PG_LX2_ONEHOT
-#define PG_LX2_ONEHOT 0   // (measured on cohort_h64m, tools/r06_runs/gpu44.sh: phase 2 17.0 ms with the scalar selects, 17.7 with the one-hot reads)
-#endif
-DEVI void lx2_init_onehot(LxShared2& sh, uint32_t tid) {
-    if (tid < (uint32_t)(PG_ESTRIDE * PG_ESTRIDE)) sh.onehot[tid / (uint32_t)PG_ESTRIDE][tid % (uint32_t)PG_ESTRIDE] = (tid / (uint32_t)PG_ESTRIDE == tid % (uint32_t)PG_ESTRIDE && tid / (uint32_t)PG_ESTRIDE < (uint32_t)PG_AMAX) ? 1.0 : 0.0;
-}
-// the same through the one-hot rows: K = the state's row inside the wave, rows = the wave's sixteen row offsets, oh = LDS address of the table
-template <int NA, int K>
-DEVI void lx2_add_oh(double (&acc)[2 * PG_LX2_PAIRS], double pr, const uint32_t (&rows)[4], uint32_t oh) {
-    const uint32_t wa = add_byte<(K & 3)>(rows[K >> 2], oh);
-    const v2f64 w01 = *(LAS const v2f64*)(uintptr_t)wa;
-    acc[0] = fma(pr, w01.x, acc[0]); acc[1] = fma(pr, w01.y, acc[1]);
-    if constexpr (NA > 2) {
-        const v2f64 w23 = *(LAS const v2f64*)(uintptr_t)(wa + 16u);
-        const double w4 = *(LAS const double*)(uintptr_t)(wa + 32u);
-        acc[2] = fma(pr, w23.x, acc[2]); acc[3] = fma(pr, w23.y, acc[3]);
-        acc[4] = fma(pr, w4, acc[4]);
-    }
-}
 // (behind the barrier that follows the step of column c) wave q: slot pair q of column c, the four waves' partials added, 64 entries out
 DEVI void lx2_flush(const LxShared2& sh, uint32_t pb, gdouble* part, uint32_t part_slots, size_t c, uint32_t nl, uint32_t wave, uint32_t lane) {
     if (wave >= (uint32_t)PG_LX2_PAIRS || 2u * wave >= nl) return;
@@ -5070,13 +4980,14 @@ DEVI Lx2Col lx2_col(const LxShared<64>& sh, uint32_t rel, uint32_t lane, uint32_
 template <int K>
 DEVI double lx2_emission(const Lx2Col& c) { return *(LAS const double*)(uintptr_t)add_byte<(K & 3)>(c.rows[K >> 2], c.ecol); }
 // one state's product into the accumulators of its row's allele (ro = the row's table-row offset a * 48; 5 * 48 = a phantom path: none)
+// (the multipliers read from a one-of-six table in LDS instead of these scalar selects: 17.7 against 17.0 ms — profiles/r06_leanx2.txt)
 template <int NA>
 DEVI void lx2_add(double (&acc)[2 * PG_LX2_PAIRS], double pr, uint32_t ro /*uniform*/) {
 #pragma unroll
     for (int a = 0; a < NA; ++a) acc[a] = fma(pr, ro == (uint32_t)(a * PG_ESTRIDE * 8) ? 1.0 : 0.0, acc[a]);
 }
 
-DEVI void leanx2_forward(const DevContig& dc, LxShared2& sh2, uint32_t C, uint32_t oh /* LDS address of sh2.onehot */) {
+DEVI void leanx2_forward(const DevContig& dc, LxShared2& sh2, uint32_t C) {
     constexpr int R = 16, BLK = LxCfg<64>::BLK, PPT = LxCfg<64>::PPT;
     LxShared<64>& sh = sh2.a;
     const uint32_t mid = C / 2, lo = mid, hi = C, first = lo == 0 ? 1u : lo;   // (C == 1: lo = 0, the one column is the prologue's)
@@ -5091,7 +5002,6 @@ DEVI void leanx2_forward(const DevContig& dc, LxShared2& sh2, uint32_t C, uint32
     for (int p = 0; p < PPT; ++p) recs.park(sh, 0, p, recs.fetch(0, p));
 #pragma unroll
     for (int p = 0; p < PPT; ++p) piece[p] = recs.fetch(1, p);
-    lx2_init_onehot(sh2, tid);
     lds_barrier();
     lx_transform<64>(sh, 0, tid);
     lds_barrier();
@@ -5196,21 +5106,20 @@ DEVI void leanx2_forward(const DevContig& dc, LxShared2& sh2, uint32_t C, uint32
         for (int a = 0; a < 2 * PG_LX2_PAIRS; ++a) acc[a] = 0.0;
         auto states = [&](auto na_c) __attribute__((always_inline)) {
             constexpr int NA = decltype(na_c)::value;
-            double ew[PG_LX2_EW];   // emissions of the column, a few states ahead of their use
-            static_for<0, PG_LX2_EW>([&](auto kc) __attribute__((always_inline)) { constexpr int k = decltype(kc)::value; ew[k] = lx2_emission<k>(col); });
+            double ew[kLx2Ew];   // emissions of the column, a few states ahead of their use
+            static_for<0, kLx2Ew>([&](auto kc) __attribute__((always_inline)) { constexpr int k = decltype(kc)::value; ew[k] = lx2_emission<k>(col); });
             static_for<0, R>([&](auto kc) __attribute__((always_inline)) {
                 constexpr int k = decltype(kc)::value;
-                const double e = ew[k % PG_LX2_EW];
-                if constexpr (k + PG_LX2_EW < R) ew[k % PG_LX2_EW] = lx2_emission<k + PG_LX2_EW>(col);
+                const double e = ew[k % kLx2Ew];
+                if constexpr (k + kLx2Ew < R) ew[k % kLx2Ew] = lx2_emission<k + kLx2Ew>(col);
                 const double pk = fmac_row_bcast<k>(fma(c0s, x[k], ujs), urep, sc);   // P'_t = c0 x + u_j + u_i
                 x[k] = pk * e;
                 part0 += x[k];
-                if constexpr (PG_LX2_ONEHOT) lx2_add_oh<NA, k>(acc, pk * ba[k], col.rows, oh);   // P'_t beta'_t (0 below the stored half)
-                else lx2_add<NA>(acc, pk * ba[k], (rw[k >> 2] >> (8 * (k & 3))) & 0xFFu);
+                lx2_add<NA>(acc, pk * ba[k], (rw[k >> 2] >> (8 * (k & 3))) & 0xFFu);   // P'_t beta'_t (0 below the stored half)
                 if constexpr ((k & 3) == 3) __builtin_amdgcn_sched_barrier(0);
             });
         };
-        if (PG_LX2_TWO && nl <= 2u) states(std::integral_constant<int, 2>{});
+        if (nl <= 2u) states(std::integral_constant<int, 2>{});
         else states(std::integral_constant<int, PG_AMAX>{});
         sh.psum[t & 1u][wave][lane] = part0;
 #pragma unroll
@@ -5246,7 +5155,7 @@ DEVI void leanx2_forward(const DevContig& dc, LxShared2& sh2, uint32_t C, uint32
     }
 }
 
-DEVI void leanx2_backward(const DevContig& dc, LxShared2& sh2, uint32_t C, uint32_t oh) {
+DEVI void leanx2_backward(const DevContig& dc, LxShared2& sh2, uint32_t C) {
     constexpr int R = 16, BLK = LxCfg<64>::BLK, PPT = LxCfg<64>::PPT;
     LxShared<64>& sh = sh2.a;
     const int64_t mid = C / 2, top = mid - 1, bot = 0, t0 = top;
@@ -5262,7 +5171,6 @@ DEVI void leanx2_backward(const DevContig& dc, LxShared2& sh2, uint32_t C, uint3
     for (int p = 0; p < PPT; ++p) recs.park(sh, 0, p, recs.fetch(0, p));
 #pragma unroll
     for (int p = 0; p < PPT; ++p) piece[p] = recs.fetch(1, p);
-    lx2_init_onehot(sh2, tid);
     lds_barrier();
     lx_transform<64>(sh, 0, tid);
     lds_barrier();
@@ -5349,21 +5257,20 @@ DEVI void leanx2_backward(const DevContig& dc, LxShared2& sh2, uint32_t C, uint3
         } else {
             auto states = [&](auto na_c) __attribute__((always_inline)) {
                 constexpr int NA = decltype(na_c)::value;
-                double ew[PG_LX2_EW];
-                static_for<0, PG_LX2_EW>([&](auto kc) __attribute__((always_inline)) { constexpr int k = decltype(kc)::value; ew[k] = lx2_emission<k>(col); });
+                double ew[kLx2Ew];
+                static_for<0, kLx2Ew>([&](auto kc) __attribute__((always_inline)) { constexpr int k = decltype(kc)::value; ew[k] = lx2_emission<k>(col); });
                 static_for<0, R>([&](auto kc) __attribute__((always_inline)) {
                     constexpr int k = decltype(kc)::value;
-                    const double e = ew[k % PG_LX2_EW];
-                    if constexpr (k + PG_LX2_EW < R) ew[k % PG_LX2_EW] = lx2_emission<k + PG_LX2_EW>(col);
+                    const double e = ew[k % kLx2Ew];
+                    if constexpr (k + kLx2Ew < R) ew[k % kLx2Ew] = lx2_emission<k + kLx2Ew>(col);
                     const double yk = fmac_row_bcast<k>(fma(k0, w[k], uj), urep, one);   // beta'_t = k0 w + u_j + u_i
                     w[k] = yk * e;
                     part0 += w[k];
-                    if constexpr (PG_LX2_ONEHOT) lx2_add_oh<NA, k>(acc, ba[k] * yk, col.rows, oh);   // P'_t beta'_t
-                    else lx2_add<NA>(acc, ba[k] * yk, (rw[k >> 2] >> (8 * (k & 3))) & 0xFFu);
+                    lx2_add<NA>(acc, ba[k] * yk, (rw[k >> 2] >> (8 * (k & 3))) & 0xFFu);   // P'_t beta'_t
                     if constexpr ((k & 3) == 3) __builtin_amdgcn_sched_barrier(0);
                 });
             };
-            if (PG_LX2_TWO && nl <= 2u) states(std::integral_constant<int, 2>{});
+            if (nl <= 2u) states(std::integral_constant<int, 2>{});
             else states(std::integral_constant<int, PG_AMAX>{});
         }
         sh.psum[(uint32_t)(t - 1) & 1u][wave][lane] = part0;
@@ -5399,11 +5306,8 @@ void k_sweep_leanx2(const DevContig* __restrict__ contigs) {
     if (!dc.leanx2 || dc.HP != 64u || dc.tri != 1u) return;
     const uint32_t C = (uint32_t)__builtin_amdgcn_readfirstlane((int)*dc.n_cols);
     if (C == 0) return;
-    // (LDS address of the one-hot table, taken relative to the record blocks': the direct cast of &sh.onehot trips this compiler's
-    //  machine verifier — "V_CMP_NE_U32 0, $src_shared_base: operand has incorrect register class")
-    const uint32_t oh = (uint32_t)(uintptr_t)(LAS const unsigned char*)((const unsigned char*)&sh.a.rec[0][0][0]) + (uint32_t)(offsetof(LxShared2, onehot) - offsetof(LxShared2, a) - offsetof(LxShared<64>, rec));
-    if (blockIdx.y == 0) leanx2_forward(dc, sh, C, oh);
-    else leanx2_backward(dc, sh, C, oh);
+    if (blockIdx.y == 0) leanx2_forward(dc, sh, C);
+    else leanx2_backward(dc, sh, C);
 }
 
 // phase 1 of the 64-path chains of fused jobs with multiallelic objects (DevContig::tri == 1, leanx == 2): the lean-x step with
@@ -6610,8 +6514,7 @@ DEVI void post_lean64(const DevContig& dc, uint32_t C, uint32_t c, const double*
         for (int u = 0; u < 4; ++u) {
             const uint32_t ip = (uint32_t)(4 * bt + u), ipc = ip < ipmax ? ip : ipmax;
             const uint32_t off = (ipc * HP + ln) * 16u;
-            if constexpr (kNtPost) { av[buf][u] = __builtin_nontemporal_load((gcdouble2*)(A2 + off)); bv[buf][u] = __builtin_nontemporal_load((gcdouble2*)(B2 + off)); }
-            else { av[buf][u] = *(gcdouble2*)(A2 + off); bv[buf][u] = *(gcdouble2*)(B2 + off); }
+            av[buf][u] = *(gcdouble2*)(A2 + off); bv[buf][u] = *(gcdouble2*)(B2 + off);
         }
     };
     fetch(std::integral_constant<int, 0>{});
@@ -6707,7 +6610,7 @@ DEVI void post_column(const DevContig& dc, uint32_t chunk, uint32_t idx, uint32_
         B = scr + (size_t)K * colsz + (size_t)(idx - K) * colsz;
         A = dc.fwd + (size_t)c * colsz;
     }
-    if (dc.lean == 1u && dc.tri == 0u && !kPostGeneric) post_lean64(dc, C, c, A, B, lane, s_bins[wave]);
+    if (dc.lean == 1u && dc.tri == 0u) post_lean64(dc, C, c, A, B, lane, s_bins[wave]);
     else post_ab(dc, C, c, A, B, lane, s_bins[wave]);
 }
 // s_wide (optional): PG_WIDE_LDS_BINS doubles of LDS of this wave's own — the raw bins of a wide column with at most

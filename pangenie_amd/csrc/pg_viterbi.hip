@@ -144,19 +144,15 @@ DEVI Cand better(Cand a, Cand b) {
 //  A row of the state matrix (first path fixed) lies in one DPP row of 16 lanes, K neighbouring second paths per lane;
 //  a wave holds 4 rows, the workgroup 16 (K = 1) or 32 rows per pass, R passes cover the matrix.
 // ------------------------------------------------------------------------------------------
-#ifndef PG_VIT_NW
-#define PG_VIT_NW 8
-#endif
-#ifndef PG_VIT_FASTG
-#define PG_VIT_FASTG 1
-#endif
+// PG_VIT_FASTR 1: row maxima by ballots, measured slower (profiles/r06_viterbi.txt).  The one rejected variant still in the text: without
+// its constant-false rowfast[] and the dead reads behind the barrier this compiler allocates k_viterbi<4> differently (profiles/r29_dead_variants.txt).
 #ifndef PG_VIT_FASTR
 #define PG_VIT_FASTR 0
 #endif
 template <int K>
 struct VitCfg {
     static constexpr int HP = 16 * K;
-    static constexpr int NW = K == 1 ? 4 : PG_VIT_NW;   // waves
+    static constexpr int NW = K == 1 ? 4 : 8;            // waves (four for K > 1: slower — profiles/r06_viterbi.txt)
     static constexpr int T = 64 * NW;
     static constexpr int RPP = NW * 4;                  // rows per pass of the workgroup
     static constexpr int R = HP / RPP;                  // passes: 1 / 1 / 2
@@ -414,8 +410,8 @@ __global__ __launch_bounds__((VitCfg<K>::T)) void k_viterbi(const DevContig* __r
         const uint32_t glast = (uint32_t)__builtin_amdgcn_readfirstlane((int)last_bit64(gh));
         gmax.lo = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x.lo), (int)glast), __builtin_amdgcn_readlane(__double2loint(x.lo), (int)glast));
         uint32_t ga = glast;
-        if (!PG_VIT_FASTG || (kVitExp & 4u) == 0u) {
-            if (!PG_VIT_FASTG || (__ballot((x.hi == gmax.hi) & (x.lo != gmax.lo)) != 0ull)) {
+        if ((kVitExp & 4u) == 0u) {
+            if (__ballot((x.hi == gmax.hi) & (x.lo != gmax.lo)) != 0ull) {
                 gmax.lo = wave_max<false>(x.hi == gmax.hi ? x.lo : kNone);
                 ga = last_bit64(__ballot((x.hi == gmax.hi) & (x.lo == gmax.lo)));  // last row that holds the column's maximum
             }

@@ -1,7 +1,7 @@
 """The state block of the lean column step (pg_kernels.hip: lean_states; lean_forward / lean_backward).  A row pair forms both
-states' sums in front of their products, and the partial sum starts as the first product (the resume prologues mirror it); a build
-with -DPG_LEAN_PAIRS_EXP=2 also forms the eight emission addresses of the next column ahead of the column's total
-(lean_pair_addrs).  No floating-point operation changes its operands or its order:
+states' sums in front of their products, and the partial sum starts as the first product (the resume prologues mirror it); the A/B
+build that also formed the eight emission addresses of the next column ahead of the column's total was measured slower and is in
+history (profiles/r21_lean_pairs.txt).  No floating-point operation changes its operands or its order:
 the results carry the bits of the commit before (tests/golden/lean_pairs_parent.npz, written by tools/lean_pairs_golden.py at that
 commit), of PG_KERNELS=nosparse and nopieces, twice in a row, and match the oracle at the bar of every parity test.
 

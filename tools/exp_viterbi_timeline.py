@@ -41,9 +41,7 @@ def main():
     lib = R / "pangenie_amd/csrc/libpangenie_hmm.so"
     keep = Path("/tmp/lib_keep.so")
     shutil.copy(lib, keep)
-    variants = [("product", None), ("no fast paths", ["PG_VIT_FASTG=0", "PG_VIT_FASTR=0"]), ("rows fast only", ["PG_VIT_FASTG=0"]),
-                ("column fast only", ["PG_VIT_FASTR=0"]), ("4 waves", ["PG_VIT_NW=4"]), ("timeline", ["PG_VIT_TIMELINE"]),
-                ("timeline, 4 waves", ["PG_VIT_TIMELINE", "PG_VIT_NW=4"])] + [("exp %d" % m, ["PG_VIT_EXP=%d" % m]) for m in (8, 16)]
+    variants = [("product", None), ("timeline", ["PG_VIT_TIMELINE"])] + [("exp %d" % m, ["PG_VIT_EXP=%d" % m]) for m in (8, 16)]
     if len(sys.argv) > 1:
         variants = [v for v in variants if v[0] in sys.argv[1:]]
     try:

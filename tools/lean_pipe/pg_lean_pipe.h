@@ -19,6 +19,12 @@
 // Reference: src/hmm.cpp:175-273 (forward column), :275-405 (backward column).
 #pragma once
 
+// timing experiments (results WRONG): 1 no column stores, 2 no class totals
+#ifndef PG_LEANP_EXP
+#define PG_LEANP_EXP 0
+#endif
+static constexpr unsigned kLeanpExp = PG_LEANP_EXP;
+
 struct LeanSharedP {
     double psum[2][4][64];   // per wave and lane: the Y partials of a step (by step parity); plain partials when priming
     double u[4][64] __attribute__((aligned(16)));      // wave-private: the new column sums, read back by row index
