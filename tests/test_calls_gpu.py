@@ -3,7 +3,8 @@
 get_likeliest_genotype -> get_genotype_quality in np.longdouble, the reference's src/genotypingresult.cpp:118-210 — on the
 job's OWN fetched bins.  No variant is left out of the comparison and none may be deferred: the panels' likelihoods are
 nowhere near 2^-16300 (smallest bin exponent of these panels: -247; the test prints it per chain).  The refusals, a second
-pg_job_calls, and the bins before and after it."""
+pg_job_calls, and the bins before and after it.  (All-zero, tied and deferred variants through a job:
+tests/test_regime_consumers_gpu.py.)"""
 import numpy as np
 import pytest
 

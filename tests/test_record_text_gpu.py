@@ -5,7 +5,8 @@ with ignore_imputed off and on.  A cohort of 2 samples x 2 contigs x 300 bubbles
 without k-mers (so `.:.:` occurs under ignore_imputed), random plans of 1-3 records a bubble with a tenth of the record alleles
 undefined.  The only records left out are those of fewer than three values — predicted from the plan — since the seeds give no
 deferred call and no deferred value, which is asserted.  Then: a chain without a kept column (KC 0, UK 0), a contig without a
-plan, the packed fetch, the device pointers, what makes the text stale, and the refusals."""
+plan, the packed fetch, the device pointers, what makes the text stale, and the refusals.  (Deferred calls and values inside a
+job's packed text: tests/test_regime_consumers_gpu.py.)"""
 import ctypes as C
 
 import numpy as np
