@@ -544,7 +544,8 @@ int  pg_gl_text(pg_gl value, char* buf, size_t len);
  *    else `.:.:`; the GL values as pg_gl_text prints them, joined by `,`; `:` and KC in decimal.
  *  A record is left to the HOST — length 0, no bytes — if its call is PG_CALL_DEFERRED, if one of its values is
  *  PG_GL_DEFERRED (or one pg_gl_text refuses), or if it has fewer than 3 values.  The text of all records is packed:
- *  chain after chain, record after record, no gaps.  Not covered: the records of combined groups, the phasing column.
+ *  chain after chain, record after record, no gaps.  Not covered: the records of combined groups.  (The phasing column
+ *  GT:KC is a text family of its own: 4e-9, below.)
  *  The splice itself — whole lines, every sample's column behind the fixed ones — is the next section's (4e-7).
  * ------------------------------------------------------------------ */
 /* 19 n_records + 11 n_gl_total: bytes that always suffice (255/255:10000: is 14, a value at most 10, a comma between
@@ -591,7 +592,7 @@ int  pg_record_text_from_fields(int device, uint64_t n_records, const pg_call* c
  *  with text_s[r] the bytes pg_job_record_text formed.  A line is the HOST's — length 0, nothing written — if any
  *  member's text of the record has length 0.  Lines are packed: record after record, index contig after index contig,
  *  no gaps.  Prefix and texts are opaque bytes of any length, 0 included.  Limits: the lines of 256 consecutive records
- *  stay below 4 GiB.  Not covered: the combined (-a) record families, the phasing column.
+ *  stay below 4 GiB.  Not covered: the combined (-a) record families.  (The lines of the phasing column: 4e-9, below.)
  * ------------------------------------------------------------------ */
 /* prefix_bytes + text_bytes + n_records (n_members + 1): reached exactly when no line is the host's.  Host only. */
 uint64_t pg_record_lines_bound(uint64_t n_records, uint64_t n_members, uint64_t prefix_bytes, uint64_t text_bytes);
@@ -639,7 +640,7 @@ int  pg_record_lines_from_text(int device, uint64_t n_records, uint64_t n_member
  *  leading zeros, "0" for 0.  Everything else is the rule above.  slot == NULL: a plain prefix.  A job with at least
  *  one slotted prefix among the index contigs that take part forms all its lines through the slotted instantiation of
  *  pg_record_lines.hip's kernels (a plain prefix gives the same bytes there); a job without one through the plain one.
- *  Not covered: the combined (-a) record families, the phasing column.
+ *  Not covered: the combined (-a) record families; the phasing column over slotted prefixes (its UK follows another rule).
  * ------------------------------------------------------------------ */
 /* pg_record_lines_bound(...) + 5 n_records: an upper bound (UK has at most 5 digits).  Host only. */
 uint64_t pg_record_lines_bound_slotted(uint64_t n_records, uint64_t n_members, uint64_t prefix_bytes, uint64_t text_bytes);
@@ -664,6 +665,77 @@ int  pg_job_line_prefix_strided(pg_job* job, uint32_t contig, uint32_t n_contigs
 int  pg_record_lines_from_text_slotted(int device, uint64_t n_records, uint64_t n_members, const uint64_t* const* off, const char* const* text,
                                        const uint64_t* prefix_off, const char* prefix, const uint32_t* slot, const uint16_t* uk, uint64_t* out_off,
                                        char* out, uint64_t cap);
+
+/* ------------------------------------------------------------------ *
+ *  The PHASING column: `GT:KC` of a run_phasing job per VCF record, formed on the device from the
+ *  Viterbi haplotypes the run left there (pangenie_amd/csrc/pg_phase_text.hip; the rule: pg_phase.h), under the record
+ *  plans of pg_job_record_plan.  What Graph::write_phasing (reference src/graph.cpp:388-411) prints: for record r of
+ *  bubble v with haplotypes H1, H2 (allele ids; 0 at a variant without a column), a_i = map[map_off[r] + H_i]:
+ *    allele_i = PG_PHASE_UNDEFINED (printed `.`) if vcf_index[vcf_off[r] + a_i] == 0xFFFF;
+ *               else 0 if the record has alleles of undefined sequence and the bubble's result holds no likelihoods (not
+ *               run_genotyping, or not a kept column): get_specific_likelihoods maps a haplotype only while it walks
+ *               stored genotypes;
+ *               else vcf_index[vcf_off[r] + a_i].
+ *  The text of a record, no separator, no terminator: `./.` if ignore_imputed and UK == 0, else `allele_1|allele_2`;
+ *  then `:` and KC in decimal.  UK and KC follow pg_job_fetch: with run_genotyping and at least one column the bubble's
+ *  k-mer count and coverage; otherwise those of the bubbles v < n_columns and 0 beyond (the Viterbi backtrace sets both
+ *  at the COLUMN index).  Every record has a text: none is the host's.  The plan calls REF defined whatever it holds.
+ *  Everything here is PG_ERR_INVALID for a job without run_phasing, before pg_job_run and after an upload that
+ *  invalidated the run; formations run on the job's stream and block; their buffers lie outside the arena, are made by
+ *  the first forming and freed by pg_job_destroy (PG_ERR_NOMEM if they do not fit).  A chain whose index contig has no
+ *  plan is left out.  Phase, text and lines are stale after a later run, a new plan or a new index, the lines also after
+ *  a new prefix: the fetches then answer PG_ERR_INVALID.  Not covered: the combined (-a) record families; slotted and
+ *  strided prefixes (the slotted kernel prints UK by the genotyping rule).
+ * ------------------------------------------------------------------ */
+#ifndef PG_PHASE_DEFINED /* (the same in pangenie_amd/csrc/pg_phase.h) */
+#define PG_PHASE_DEFINED
+typedef struct pg_phase { uint16_t allele_1, allele_2; } pg_phase;
+#define PG_PHASE_UNDEFINED 0xFFFFu   /* the haplotype carries an allele of undefined sequence: printed `.` */
+#endif
+/* One pg_phase per record of every chain with a plan.  Before the first formation (and after a new plan or index) every
+ * allele id is checked on the device against the plans' maps, as pg_job_record_calls checks them: PG_ERR_INVALID. */
+int  pg_job_record_phase(pg_job* job, char* err, size_t errlen);
+/* Chain `chain`'s records (a chain without a plan has none: out may be NULL) / every chain's, one synchronisation. */
+int  pg_job_fetch_record_phase(pg_job* job, uint32_t chain, pg_phase* out, char* err, size_t errlen);
+int  pg_job_fetch_record_phase_all(pg_job* job, pg_phase* const* outs, char* err, size_t errlen);
+/* Device-resident records of chain `chain` and their number. */
+int  pg_job_device_record_phase(pg_job* job, uint32_t chain, void** d_phase, uint64_t* n);
+double pg_job_record_phase_ms(const pg_job* job);
+/* 13 n_records (255|255:65535): reached exactly when every record is that one.  Host only. */
+uint64_t pg_phase_text_bound(uint64_t n_records);
+/* Forms the text of every chain with a plan, packed chain after chain; forms the record phase first where it is not
+ * formed for this run.  Forming it with another ignore_imputed replaces it. */
+int  pg_job_phased_text(pg_job* job, int ignore_imputed, char* err, size_t errlen);
+/* record_first / text_first (each [n_chains + 1], either may be NULL): every chain's first record / first byte. */
+int  pg_job_phased_text_first(pg_job* job, uint64_t* record_first, uint64_t* text_first, char* err, size_t errlen);
+/* As pg_job_fetch_record_text, pg_job_fetch_record_text_packed and pg_job_device_record_text. */
+int  pg_job_fetch_phased_text(pg_job* job, uint32_t chain, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen);
+int  pg_job_fetch_phased_text_packed(pg_job* job, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen);
+int  pg_job_device_phased_text(pg_job* job, uint32_t chain, void** d_off, void** d_text, uint64_t* n_records, uint64_t* n_bytes);
+double pg_job_phased_text_ms(const pg_job* job);
+/* Whole lines of the phasing VCF: the second lines family of a job, with prefixes of its own (FORMAT is GT:KC), joined
+ * from the phased text by the kernels of pg_job_record_lines (plain prefixes).  Each call is its record-lines sibling
+ * over this family: pg_job_line_prefix, pg_job_record_lines (PG_ERR_INVALID unless pg_job_phased_text has been called
+ * for this run and these plans), pg_job_record_lines_first, the fetches, the device pointers, the time. */
+int  pg_job_phased_line_prefix(pg_job* job, uint32_t index_contig, const uint64_t* off, const char* bytes, char* err, size_t errlen);
+int  pg_job_phased_lines(pg_job* job, char* err, size_t errlen);
+int  pg_job_phased_lines_first(pg_job* job, uint64_t* n_index_contigs, uint64_t* line_first, uint64_t* byte_first, char* err, size_t errlen);
+int  pg_job_fetch_phased_lines(pg_job* job, uint32_t index_contig, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen);
+int  pg_job_fetch_phased_lines_packed(pg_job* job, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen);
+int  pg_job_device_phased_lines(pg_job* job, uint32_t index_contig, void** d_off, void** d_text, uint64_t* n_lines, uint64_t* n_bytes);
+double pg_job_phased_lines_ms(const pg_job* job);
+/* Unit entry points, through the same kernels; everything is checked on the host first (PG_ERR_INVALID), then
+ * PG_ERR_DEVICE without a device: no host fallback.
+ * pg_record_phase_from_haplotypes: a plan, hap1 / hap2 [n_variants] allele ids and keyed [n_variants] (the bubble's
+ * result holds likelihoods); out[n_records].  Refused: a malformed plan (pg_record_calls_from_bins' checks), null
+ * arrays, a haplotype id outside the map of one of its bubble's records.  A plan without variants: PG_OK.
+ * pg_phase_text_from_fields: phase[R], kc[R], no_call[R] (or NULL: none); off[R + 1] and text[cap] come back.  Refused:
+ * null arrays, n_records >= 2^31, cap < pg_phase_text_bound(R), an allele above 255 that is not PG_PHASE_UNDEFINED (the
+ * bound counts on it).  n_records == 0: PG_OK with off[0] = 0. */
+int  pg_record_phase_from_haplotypes(int device, const pg_record_plan* plan, const uint16_t* hap1, const uint16_t* hap2, const uint8_t* keyed,
+                                     pg_phase* out);
+int  pg_phase_text_from_fields(int device, uint64_t n_records, const pg_phase* phase, const uint16_t* kc, const uint8_t* no_call, uint64_t* off,
+                               char* text, uint64_t cap);
 
 /* ------------------------------------------------------------------ *
  *  Path subsets: the chains of one contig over different path selections combined on the device, and the calls

@@ -344,6 +344,42 @@ def _bind_hip(lib):
     lib.pg_record_lines_from_text_slotted.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                       C.c_void_p, C.c_void_p, C.c_uint64]
     lib.pg_record_lines_from_text_slotted.restype = C.c_int
+    # the phasing column of a run_phasing job (pangenie_amd/calls.py); records are read as numpy arrays of PHASE_DTYPE
+    for name in ("pg_job_record_phase", "pg_job_phased_lines"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+        getattr(lib, name).restype = C.c_int
+    lib.pg_job_fetch_record_phase.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_fetch_record_phase.restype = C.c_int
+    lib.pg_job_fetch_record_phase_all.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+    lib.pg_job_fetch_record_phase_all.restype = C.c_int
+    lib.pg_job_device_record_phase.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), u64p]
+    lib.pg_job_device_record_phase.restype = C.c_int
+    lib.pg_phase_text_bound.argtypes = [C.c_uint64]
+    lib.pg_phase_text_bound.restype = C.c_uint64
+    lib.pg_job_phased_text.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]
+    lib.pg_job_phased_text.restype = C.c_int
+    lib.pg_job_phased_text_first.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_phased_text_first.restype = C.c_int
+    for name in ("pg_job_fetch_phased_text", "pg_job_fetch_phased_lines"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+        getattr(lib, name).restype = C.c_int
+    for name in ("pg_job_fetch_phased_text_packed", "pg_job_fetch_phased_lines_packed"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+        getattr(lib, name).restype = C.c_int
+    for name in ("pg_job_device_phased_text", "pg_job_device_phased_lines"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), u64p, u64p]
+        getattr(lib, name).restype = C.c_int
+    lib.pg_job_phased_line_prefix.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_phased_line_prefix.restype = C.c_int
+    lib.pg_job_phased_lines_first.argtypes = [C.c_void_p, u64p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_phased_lines_first.restype = C.c_int
+    for name in ("pg_job_record_phase_ms", "pg_job_phased_text_ms", "pg_job_phased_lines_ms"):
+        getattr(lib, name).argtypes = [C.c_void_p]
+        getattr(lib, name).restype = C.c_double
+    lib.pg_record_phase_from_haplotypes.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pg_record_phase_from_haplotypes.restype = C.c_int
+    lib.pg_phase_text_from_fields.argtypes = [C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    lib.pg_phase_text_from_fields.restype = C.c_int
     # path subsets combined on the device (pangenie_amd/calls.py); bins are read as numpy arrays of COMBINED_DTYPE
     lib.pg_job_combine_plan.argtypes = [C.c_void_p, C.c_uint32, u32p, u32p, C.c_char_p, C.c_size_t]
     lib.pg_job_combine_plan.restype = C.c_int
@@ -423,6 +459,11 @@ HIP_ABI_SYMBOLS = [
     "pg_record_lines_bound", "pg_job_line_prefix", "pg_job_record_lines", "pg_job_record_lines_first", "pg_job_fetch_record_lines",
     "pg_job_fetch_record_lines_packed", "pg_job_device_record_lines", "pg_job_record_lines_ms", "pg_record_lines_from_text",
     "pg_record_lines_bound_slotted", "pg_job_line_prefix_slotted", "pg_job_line_prefix_strided", "pg_record_lines_from_text_slotted",
+    "pg_job_record_phase", "pg_job_fetch_record_phase", "pg_job_fetch_record_phase_all", "pg_job_device_record_phase", "pg_job_record_phase_ms",
+    "pg_phase_text_bound", "pg_job_phased_text", "pg_job_phased_text_first", "pg_job_fetch_phased_text", "pg_job_fetch_phased_text_packed",
+    "pg_job_device_phased_text", "pg_job_phased_text_ms",
+    "pg_job_phased_line_prefix", "pg_job_phased_lines", "pg_job_phased_lines_first", "pg_job_fetch_phased_lines", "pg_job_fetch_phased_lines_packed",
+    "pg_job_device_phased_lines", "pg_job_phased_lines_ms", "pg_record_phase_from_haplotypes", "pg_phase_text_from_fields",
 ]
 
 

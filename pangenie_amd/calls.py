@@ -633,6 +633,206 @@ def record_lines_from_text_slotted(texts, prefix, slot=None, uk=None, device: in
 
 
 # ---------------------------------------------------------------------------------------------------------------
+#  The phasing column of a run_phasing job (pg_job_record_phase, pg_job_phased_text, pg_job_phased_lines and the unit entry
+#  points)
+# ---------------------------------------------------------------------------------------------------------------
+PHASE_DTYPE = np.dtype([("allele_1", "<u2"), ("allele_2", "<u2")])
+PG_PHASE_UNDEFINED = 0xFFFF   # the haplotype carries an allele of undefined sequence: printed `.`
+
+
+def phase_text_bound(n_records: int) -> int:
+    """pg_phase_text_bound: 13 bytes a record (255|255:65535)."""
+    return int(_lib.load_hip().pg_phase_text_bound(int(n_records)))
+
+
+def form_record_phase(job) -> None:
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_record_phase(job.h, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+
+
+def fetch_record_phase(job, contig: int) -> np.ndarray:
+    R = _n_records(job)[contig]
+    out = np.zeros(max(R, 1), PHASE_DTYPE)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_record_phase(job.h, contig, out.ctypes.data, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return out[:R]
+
+
+def fetch_record_phase_all(job) -> List[np.ndarray]:
+    Rs = _n_records(job)
+    outs = [np.zeros(max(R, 1), PHASE_DTYPE) for R in Rs]
+    arr = (C.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_record_phase_all(job.h, arr, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return [o[:R] for o, R in zip(outs, Rs)]
+
+
+def job_record_phase(job, contig: Optional[int] = None):
+    """Job.record_phase(): forms the record phase of every chain that has a plan, fetches all of them (or chain `contig`'s)."""
+    form_record_phase(job)
+    if contig is not None:
+        return fetch_record_phase(job, contig)
+    return fetch_record_phase_all(job)
+
+
+def form_phased_text(job, ignore_imputed: bool = False) -> None:
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_phased_text(job.h, 1 if ignore_imputed else 0, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+
+
+def phased_text_first(job):
+    """pg_job_phased_text_first: (record_first, text_first), each [n_chains + 1]."""
+    rf, tf = np.zeros(job.n_chains + 1, np.uint64), np.zeros(job.n_chains + 1, np.uint64)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_phased_text_first(job.h, rf.ctypes.data, tf.ctypes.data, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return rf, tf
+
+
+def fetch_phased_text(job, contig: int):
+    """pg_job_fetch_phased_text: (off [R + 1], bytes) of chain `contig`; record r's text is bytes[off[r]:off[r + 1]]."""
+    rf, tf = phased_text_first(job)
+    n = int(tf[contig + 1] - tf[contig])
+    off = np.zeros(int(rf[contig + 1] - rf[contig]) + 1, np.uint64)
+    text = np.zeros(max(n, 1), np.uint8)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_phased_text(job.h, contig, off.ctypes.data, text.ctypes.data, n, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return off, text[:n].tobytes()
+
+
+def fetch_phased_text_packed(job):
+    """pg_job_fetch_phased_text_packed: (off [R_total + 1] absolute in the packed text, bytes, record_first, text_first)."""
+    rf, tf = phased_text_first(job)
+    n = int(tf[-1])
+    off = np.zeros(int(rf[-1]) + 1, np.uint64)
+    text = np.zeros(max(n, 1), np.uint8)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_phased_text_packed(job.h, off.ctypes.data, text.ctypes.data, n, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return off, text[:n].tobytes(), rf, tf
+
+
+def job_phased_text(job, contig: Optional[int] = None, ignore_imputed: bool = False):
+    """Job.phased_text(): forms the text of every chain that has a plan; (off, bytes) of chain `contig`, or of every chain."""
+    form_phased_text(job, ignore_imputed)
+    if contig is not None:
+        return fetch_phased_text(job, contig)
+    return [fetch_phased_text(job, c) for c in range(job.n_chains)]
+
+
+def job_phased_line_prefix(job, contig: int, off, data) -> None:
+    """pg_job_phased_line_prefix: the fixed columns (CHROM .. INFO, GT:KC) of index contig `contig` for the phased lines."""
+    oo, bb, _ = _prefix_arrays(job, "phased_line_prefix", contig, off, data, None)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_phased_line_prefix(job.h, contig, oo.ctypes.data if len(oo) else None, bb.ctypes.data if len(bb) else None, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+
+
+def form_phased_lines(job) -> None:
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_phased_lines(job.h, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+
+
+def phased_lines_first(job):
+    """pg_job_phased_lines_first: (line_first, byte_first), each [n_index_contigs + 1]."""
+    n = C.c_uint64(0)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_phased_lines_first(job.h, C.byref(n), None, None, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    lf, bf = np.zeros(n.value + 1, np.uint64), np.zeros(n.value + 1, np.uint64)
+    rc = job._lib.pg_job_phased_lines_first(job.h, C.byref(n), lf.ctypes.data, bf.ctypes.data, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return lf, bf
+
+
+def fetch_phased_lines(job, contig: int):
+    """pg_job_fetch_phased_lines: (off [R + 1], bytes) of index contig `contig`; line r is bytes[off[r]:off[r + 1]]."""
+    lf, bf = phased_lines_first(job)
+    n = int(bf[contig + 1] - bf[contig])
+    off = np.zeros(int(lf[contig + 1] - lf[contig]) + 1, np.uint64)
+    text = np.zeros(max(n, 1), np.uint8)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_phased_lines(job.h, contig, off.ctypes.data, text.ctypes.data, n, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return off, text[:n].tobytes()
+
+
+def fetch_phased_lines_packed(job):
+    """pg_job_fetch_phased_lines_packed: (off [n_lines + 1] absolute, bytes, line_first, byte_first) from ONE copy."""
+    lf, bf = phased_lines_first(job)
+    n = int(bf[-1])
+    off = np.zeros(int(lf[-1]) + 1, np.uint64)
+    text = np.zeros(max(n, 1), np.uint8)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_phased_lines_packed(job.h, off.ctypes.data, text.ctypes.data, n, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return off, text[:n].tobytes(), lf, bf
+
+
+def job_phased_lines(job, contig: Optional[int] = None):
+    """Job.phased_lines(): forms the lines from the phased text as it is; (off, bytes) of index contig `contig`, or of all."""
+    form_phased_lines(job)
+    if contig is not None:
+        return fetch_phased_lines(job, contig)
+    return [fetch_phased_lines(job, k) for k in range(len(phased_lines_first(job)[0]) - 1)]
+
+
+def record_phase_from_haplotypes(plan: RecordPlan, hap1, hap2, keyed, device: int = 0) -> np.ndarray:
+    """pg_record_phase_from_haplotypes: one PHASE_DTYPE record per record of the plan from the haplotypes' allele ids
+    (hap1, hap2 [V]) and keyed [V] — whether the bubble's result holds likelihoods — through the job's kernel."""
+    lib = _lib.load_hip()
+    pad = lambda a, dt: np.ascontiguousarray(a, dt) if len(a) else np.zeros(1, dt)
+    V = plan.n_variants
+    if len(hap1) != V or len(hap2) != V or len(keyed) != V:
+        raise ValueError("record_phase_from_haplotypes: array lengths do not match the plan")
+    h1, h2, kd = pad(hap1, np.uint16), pad(hap2, np.uint16), pad(keyed, np.uint8)
+    out = np.zeros(max(plan.n_records, 1), PHASE_DTYPE)
+    c = plan.as_c()
+    rc = lib.pg_record_phase_from_haplotypes(device, C.addressof(c), h1.ctypes.data, h2.ctypes.data, kd.ctypes.data, out.ctypes.data)
+    if rc:
+        raise _error(rc, None)
+    return out[:plan.n_records]
+
+
+def phase_text_from_fields(phase, kc, no_call=None, device: int = 0):
+    """pg_phase_text_from_fields: (off [R + 1], bytes) — the text of R records from their phase (PHASE_DTYPE), kc [R] and
+    no_call [R] (or None), through the job's kernels."""
+    lib = _lib.load_hip()
+    pp, kk = np.ascontiguousarray(phase, PHASE_DTYPE), np.ascontiguousarray(kc, np.uint16)
+    nc = None if no_call is None else np.ascontiguousarray(no_call, np.uint8)
+    R = len(pp)
+    if len(kk) != R or (nc is not None and len(nc) != R):
+        raise ValueError("phase_text_from_fields: array lengths do not match")
+    cap = phase_text_bound(R)
+    off = np.zeros(R + 1, np.uint64)
+    text = np.zeros(max(cap, 1), np.uint8)
+    rc = lib.pg_phase_text_from_fields(device, R, pp.ctypes.data if R else None, kk.ctypes.data if R else None, None if nc is None or not R else nc.ctypes.data,
+                                       off.ctypes.data, text.ctypes.data, cap)
+    if rc:
+        raise _error(rc, None)
+    return off, text[:int(off[-1])].tobytes()
+
+
+# ---------------------------------------------------------------------------------------------------------------
 #  Path subsets combined on the device (pg_job_combine_plan, pg_job_combine, pg_job_combined_calls, pg_combine_bins,
 #  pg_calls_from_combined; DESIGN.md 4e-4)
 # ---------------------------------------------------------------------------------------------------------------

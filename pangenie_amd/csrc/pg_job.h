@@ -1,5 +1,5 @@
 // pg_job.h — what the host units of the C-ABI shim share (pg_shim.cpp: jobs, their build and uploads; pg_shim_run.cpp: the
-// run schedule, pg_job_run; pg_shim_calls.cpp: the output columns formed from a job's finished bins; pg_shim_lines.cpp: whole VCF lines joined from the record text; pg_shim_combine.cpp: path subsets combined): the error helpers, the
+// run schedule, pg_job_run; pg_shim_calls.cpp: the output columns formed from a job's finished bins; pg_shim_lines.cpp: whole VCF lines joined from the record text or the phased text; pg_shim_phase.cpp: the phasing column; pg_shim_combine.cpp: path subsets combined): the error helpers, the
 // host's picture of a job's index contigs, chains and record plans, struct pg_job itself, and the few helpers upload and run
 // both need.  Private: nothing here is exported.
 #pragma once
@@ -114,6 +114,10 @@ int check_record_plan_ids(const RecordPlanHost& h, const uint32_t* allele_off, c
 size_t record_plan_device_bytes(const RecordPlanHost& h);
 bool record_plan_upload(const RecordPlanHost& h, unsigned char* d, RecPlanDev* dev);   // d: record_plan_device_bytes of room
 std::vector<uint64_t> record_gl_offsets(const RecordPlanHost& h);                        // [R + 1] first GL value of every record
+const RecordPlanHost* plan_of_chain(const pg_job* job, uint32_t c);                      // the plan of chain c's index contig, or nullptr
+// k_rplan_ids over the RCallsDesc list of plan_rcalls on the device (d_hit: 8 bytes next to it); passes at once while
+// pg_job::rplan_ids_ok
+int check_record_plan_ids_on_device(pg_job* job, const RCallsDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, unsigned char* d_hit, char* err, size_t errlen);
 
 // The wave-per-record kernel stages a bubble's quotients and a record's folded map in device memory: one slot of `stride`
 // 16-byte values per block, at most 1024 blocks and 256 MB (a 256-allele bubble: 32 896 bins and as many keys, 1 MB a slot).
@@ -436,6 +440,15 @@ struct pg_job {
     pgj::RecordTextFamily rtext;
     // Record lines (pg_job_line_prefix / pg_job_record_lines): whole VCF lines per index contig, every member's text joined in.
     pgj::RecordLinesFamily rlines;
+    // The phasing column of a run_phasing job (pg_shim_phase.cpp), under the same plans: two numbers per VCF
+    // record from the Viterbi haplotypes (pg_job_record_phase), the bytes of `GT:KC` from them (pg_job_phased_text: a
+    // RecordTextFamily without wide records) and whole lines over prefixes of their own (pg_job_phased_lines).  All three are
+    // stale after a later run.
+    pgj::OutputFamily rphase;
+    std::vector<RPhaseDesc> rphase_desc;
+    pgj::RecordTextFamily ptext;
+    std::vector<PTextDesc> ptext_desc;
+    pgj::RecordLinesFamily plines;
     // Path subsets combined on the device (pg_job_combine_plan / pg_job_combine / pg_job_combined_calls).
     pgj::CombineState combine;
     uint64_t combine_serial = 0;              // counts the finished pg_job_combine calls
@@ -450,10 +463,35 @@ inline void record_plans_changed(pg_job* job) {
     job->rcalls.dirty = true;
     job->rgl.dirty = true;
     job->rtext.dirty = true;          // (its descriptors point into the two buffers above)
+    job->rphase.dirty = true;         // (the phasing column: its descriptors hold the plans' device arrays)
+    job->ptext.dirty = true;
     job->rplan_ids_ok = false;
     job->combine.layout_ok = false;   // (the members' layouts are compared again before the next combine)
     job->crec.dirty = true;           // (the records of the combined groups: rebuilt, the ids checked again)
 }
+
+// The two text families of a job and the lines joined from each.  What the fetches of a text (pg_shim_calls.cpp) and the
+// whole of the lines (pg_shim_lines.cpp) do is written once and told the family by one of these rows; the formers differ.
+struct TextKind {
+    RecordTextFamily pg_job::*text;
+    const char* former;   // the entry point that forms it, as the messages name it
+};
+struct LinesKind {
+    TextKind text;
+    RecordLinesFamily pg_job::*lines;
+    const char* former;
+};
+inline const TextKind kRecordText = {&pg_job::rtext, "pg_job_record_text"};
+inline const TextKind kPhasedText = {&pg_job::ptext, "pg_job_phased_text"};
+inline const LinesKind kRecordLines = {kRecordText, &pg_job::rlines, "pg_job_record_lines"};
+inline const LinesKind kPhasedLines = {kPhasedText, &pg_job::plines, "pg_job_phased_lines"};
+// formed for the last run and the plans as they are?  then: every chain's first byte; one chain's bytes and offsets; all
+// chains' from one copy; one chain's device pointers
+int text_family_ready(pg_job* job, const TextKind& k, char* err, size_t errlen);
+int text_family_first(pg_job* job, const TextKind& k, uint64_t* text_first, char* err, size_t errlen);
+int text_family_fetch_chain(pg_job* job, const TextKind& k, uint32_t ci, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen);
+int text_family_fetch_packed(pg_job* job, const TextKind& k, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen);
+int text_family_device(pg_job* job, const TextKind& k, uint32_t ci, void** d_off, void** d_text, uint64_t* n_records, uint64_t* n_bytes);
 
 // Group B's copies of a pipelined first run (pg_job::late_threads) read the caller's arrays and feed the job's second stream:
 // whoever needs either to be left alone waits for the threads first.

@@ -1,4 +1,4 @@
-// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp, pg_shim_run.cpp, pg_shim_calls.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip, pg_calls.hip, pg_combine.hip, pg_combine_records.hip, pg_record_text.hip, pg_record_lines.hip).
+// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp, pg_shim_run.cpp, pg_shim_calls.cpp, pg_shim_phase.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip, pg_calls.hip, pg_combine.hip, pg_combine_records.hip, pg_record_text.hip, pg_record_lines.hip, pg_phase_text.hip).
 //
 // The ONE declaration of every host-callable launcher and of the two launch masks a job hands them.  Both sides include
 // it: a launcher whose parameter list changes on one side only no longer compiles (C linkage: the linker would not notice).
@@ -151,7 +151,44 @@ struct RLinesDesc {
     uint32_t chain, pad;
 };
 
+// Record phase and phased text (pg_phase_text.hip): one descriptor per chain (or per call of a unit entry
+// point) that has records, in chain order.  Blocks [blk0, next blk0) take pgk_ptext_block() RECORDS each.
+// RPhaseDesc: `out` = the chain's 4-byte records (pg_phase, pg_phase.h), one per VCF record.  With hap1 (the unit entry
+// point): hap1 / hap2 [V] the haplotypes' allele ids and keyed [V] per variant; without (a job's chain): hap1, hap2 and kept
+// of DevContig `chain`, keyed = run_genotyping && kept.
+struct RPhaseDesc {
+    uint32_t blk0, R;
+    uint32_t chain, run_genotyping;
+    void* out;
+    RecPlanDev plan;
+    const uint16_t* hap1;
+    const uint16_t* hap2;
+    const uint8_t* keyed;
+};
+// PTextDesc: rec0 = the chain's first record among all records of the launch (the offsets and the packed text are the
+// launch's); `phase` = the chain's pg_phase records.  With rec_var (a job's chain): KC and UK are read from DevContig `chain`
+// under pg_job_fetch's rule — every bubble's with run_genotyping and a column, else those of the bubbles below the column
+// count and 0 beyond; without (the unit entry point): kc [R] and no_call [R] (or null) per record.
+struct PTextDesc {
+    uint32_t blk0, R;
+    uint64_t rec0;
+    uint32_t chain, ignore_imputed;
+    uint32_t run_genotyping, pad;
+    const void* phase;
+    const uint32_t* rec_var;
+    const uint16_t* kc;
+    const uint8_t* no_call;
+};
+
 extern "C" {
+// pg_phase_text.hip: k_rphase over the descriptors' records
+void pgk_launch_rphase(const DevContig* d_contigs, const RPhaseDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, hipStream_t s);
+// ... and the packed text: d_loc [n_records], d_bsum [n_blocks], d_bbase [n_blocks + 1]: the scan's; d_off [n_records + 1] =
+// every record's first byte in d_text (`cap` bytes of room), the total behind the last
+void pgk_launch_ptext(const DevContig* d_contigs, const PTextDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, uint32_t* d_loc, uint32_t* d_bsum,
+                      uint64_t* d_bbase, uint64_t* d_off, uint64_t n_records, char* d_text, uint64_t cap, hipStream_t s);
+uint32_t pgk_ptext_block(void);
+uint32_t pgk_ptext_stage_bytes(void);
 // pg_record_lines.hip: d_loc [n_lines], d_bsum [n_blocks], d_bbase [n_blocks + 1]: the scan's; d_off [n_lines + 1] = every
 // line's first byte in d_out (`cap` bytes of room), the total behind the last.  slotted: the kernels that read the
 // descriptors' slot fields; d_contigs may be null if no descriptor reads a chain

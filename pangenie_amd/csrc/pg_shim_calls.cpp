@@ -473,15 +473,15 @@ std::vector<uint64_t> record_gl_offsets(const RecordPlanHost& h) {
     return off;
 }
 
-}  // namespace pgj
-
-namespace {
-
 // the plan of chain c's index contig, or nullptr
 const RecordPlanHost* plan_of_chain(const pg_job* job, uint32_t c) {
     const uint32_t ix = job->chains[c].index;
     return ix < job->rplans.size() ? job->rplans[ix].get() : nullptr;
 }
+
+}  // namespace pgj
+
+namespace {
 
 // the checked plan on the job's device, ready to be referred to by index contigs
 int record_plan_to_device(pg_job* job, RecordPlanHost&& h, RecordPlanRef* ref, char* err, size_t errlen) {
@@ -509,11 +509,14 @@ void adopt(OutputFamily& f, unsigned char* d, std::vector<uint64_t>&& first, con
     f.formed = false;
 }
 
+}  // namespace
+
 // The id check on the device (k_rplan_ids): every allele id of every chain that has a plan, against the maps of its bubble's
 // records.  `d_desc` = the RCallsDesc list of plan_rcalls on the device, `d_hit` = 8 bytes next to it.  On a hit the ids of
-// that one chain come to the host and check_record_plan_ids forms the message.
-int check_record_plan_ids_on_device(pg_job* job, const RCallsDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, unsigned char* d_hit, char* err,
-                                    size_t errlen) {
+// that one chain come to the host and check_record_plan_ids forms the message.  (Declared in pg_job.h: pg_shim_phase.cpp
+// asks for the same check in front of its first formation.)
+int pgj::check_record_plan_ids_on_device(pg_job* job, const RCallsDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, unsigned char* d_hit, char* err,
+                                         size_t errlen) {
     if (job->rplan_ids_ok || n_desc == 0 || n_blocks == 0) { job->rplan_ids_ok = true; return PG_OK; }
     hipStream_t s = job->stream;
     uint64_t hit = ~(uint64_t)0;
@@ -535,8 +538,6 @@ int check_record_plan_ids_on_device(pg_job* job, const RCallsDesc* d_desc, uint3
     return rc;
 }
 
-}  // namespace
-
 extern "C" int pg_job_record_plan(pg_job* job, uint32_t ix, const pg_record_plan* plan, char* err, size_t errlen) {
     if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
     if (ix >= job->index.size()) { set_err(err, errlen, "index contig %u of %zu", ix, job->index.size()); return PG_ERR_INVALID; }
@@ -548,6 +549,7 @@ extern "C" int pg_job_record_plan(pg_job* job, uint32_t ix, const pg_record_plan
     if (rc != PG_OK) return rc;
     job->rplans[ix] = std::move(ref);   // (this index contig's reference alone: the members of a stride keep theirs)
     job->rlines.drop_prefix(ix);        // (the prefix of the lines had the old plan's records)
+    job->plines.drop_prefix(ix);
     record_plans_changed(job);
     return PG_OK;
 }
@@ -569,7 +571,7 @@ extern "C" int pg_job_record_plan_strided(pg_job* job, uint32_t contig, uint32_t
     RecordPlanRef ref;
     rc = record_plan_to_device(job, std::move(h), &ref, err, errlen);
     if (rc != PG_OK) return rc;
-    for (size_t ix = contig; ix < job->index.size(); ix += n_contigs) { job->rplans[ix] = ref; job->rlines.drop_prefix(ix); }
+    for (size_t ix = contig; ix < job->index.size(); ix += n_contigs) { job->rplans[ix] = ref; job->rlines.drop_prefix(ix); job->plines.drop_prefix(ix); }
     record_plans_changed(job);
     return PG_OK;
 }
@@ -834,14 +836,6 @@ void rtext_launch(const DevContig* d_contigs, unsigned char* d, const RTextLayou
                      (uint32_t*)(d + L.o_bsum), (uint64_t*)(d + L.o_bbase), (uint64_t*)(d + L.o_off), R, (char*)d, cap, e0, e1, s);
 }
 
-int rtext_ready(pg_job* job, char* err, size_t errlen) {
-    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
-    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
-    const RecordTextFamily& f = job->rtext;
-    if (!f.formed || f.dirty || f.run != job->run_serial) { set_err(err, errlen, "pg_job_record_text has not been called for this run and these plans"); return PG_ERR_INVALID; }
-    return PG_OK;
-}
-
 bool family_current(const pg_job* job, const OutputFamily& f) { return f.formed && !f.dirty && f.run == job->run_serial; }
 
 }  // namespace
@@ -936,20 +930,21 @@ extern "C" int pg_job_record_text(pg_job* job, int ignore_imputed, char* err, si
 extern "C" double pg_job_record_text_ms(const pg_job* job) { return job ? job->rtext.ms : 0.0; }
 extern "C" double pg_job_record_text_emit_ms(const pg_job* job) { return job ? job->rtext.emit_ms : 0.0; }
 
-extern "C" int pg_job_record_text_first(pg_job* job, uint64_t* text_first, char* err, size_t errlen) {
-    int rc = rtext_ready(job, err, errlen);
-    if (rc != PG_OK) return rc;
-    if (!text_first) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
-    memcpy(text_first, job->rtext.text_first.data(), job->rtext.text_first.size() * sizeof(uint64_t));
+// ---- what the two text families (the record text; the phased text of pg_shim_phase.cpp) share: declared in pg_job.h -------
+
+int pgj::text_family_ready(pg_job* job, const TextKind& k, char* err, size_t errlen) {
+    if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
+    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
+    const RecordTextFamily& f = job->*k.text;
+    if (!f.formed || f.dirty || f.run != job->run_serial) { set_err(err, errlen, "%s has not been called for this run and these plans", k.former); return PG_ERR_INVALID; }
     return PG_OK;
 }
 
 namespace {
 
-// records [r0, r1) of a formed job: their offsets less `minus` (or none) and their bytes, n_bytes of them
-int rtext_fetch(pg_job* job, uint64_t r0, uint64_t r1, uint64_t b0, uint64_t b1, uint64_t minus, uint64_t* off, char* text, uint64_t n_bytes, char* err,
-                size_t errlen) {
-    const RecordTextFamily& f = job->rtext;
+// records [r0, r1) of a formed text family: their offsets less `minus` (or none) and their bytes, n_bytes of them
+int text_family_fetch(pg_job* job, const RecordTextFamily& f, uint64_t r0, uint64_t r1, uint64_t b0, uint64_t b1, uint64_t minus, uint64_t* off, char* text,
+                      uint64_t n_bytes, char* err, size_t errlen) {
     if (n_bytes != b1 - b0) { set_err(err, errlen, "the text holds %llu bytes, not %llu", (unsigned long long)(b1 - b0), (unsigned long long)n_bytes); return PG_ERR_INVALID; }
     if (n_bytes && !text) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
     HIP_TRY(hipSetDevice(job->device));
@@ -966,29 +961,49 @@ int rtext_fetch(pg_job* job, uint64_t r0, uint64_t r1, uint64_t b0, uint64_t b1,
 
 }  // namespace
 
-extern "C" int pg_job_fetch_record_text(pg_job* job, uint32_t ci, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
-    int rc = rtext_ready(job, err, errlen);
+int pgj::text_family_first(pg_job* job, const TextKind& k, uint64_t* text_first, char* err, size_t errlen) {
+    int rc = text_family_ready(job, k, err, errlen);
+    if (rc != PG_OK) return rc;
+    if (!text_first) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
+    const RecordTextFamily& f = job->*k.text;
+    memcpy(text_first, f.text_first.data(), f.text_first.size() * sizeof(uint64_t));
+    return PG_OK;
+}
+
+int pgj::text_family_fetch_chain(pg_job* job, const TextKind& k, uint32_t ci, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
+    int rc = text_family_ready(job, k, err, errlen);
     if (rc != PG_OK) return rc;
     if (ci >= job->chains.size()) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
-    const RecordTextFamily& f = job->rtext;
-    return rtext_fetch(job, f.first[ci], f.first[ci + 1], f.text_first[ci], f.text_first[ci + 1], f.text_first[ci], off, text, n_bytes, err, errlen);
+    const RecordTextFamily& f = job->*k.text;
+    return text_family_fetch(job, f, f.first[ci], f.first[ci + 1], f.text_first[ci], f.text_first[ci + 1], f.text_first[ci], off, text, n_bytes, err, errlen);
 }
 
-extern "C" int pg_job_fetch_record_text_packed(pg_job* job, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
-    int rc = rtext_ready(job, err, errlen);
+int pgj::text_family_fetch_packed(pg_job* job, const TextKind& k, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
+    int rc = text_family_ready(job, k, err, errlen);
     if (rc != PG_OK) return rc;
-    const RecordTextFamily& f = job->rtext;
-    return rtext_fetch(job, 0, f.n_records, 0, f.text_first.back(), 0, off, text, n_bytes, err, errlen);
+    const RecordTextFamily& f = job->*k.text;
+    return text_family_fetch(job, f, 0, f.n_records, 0, f.text_first.back(), 0, off, text, n_bytes, err, errlen);
 }
 
-extern "C" int pg_job_device_record_text(pg_job* job, uint32_t ci, void** d_off, void** d_text, uint64_t* n_records, uint64_t* n_bytes) {
-    if (rtext_ready(job, nullptr, 0) != PG_OK || ci >= job->chains.size()) return PG_ERR_INVALID;
-    const RecordTextFamily& f = job->rtext;
+int pgj::text_family_device(pg_job* job, const TextKind& k, uint32_t ci, void** d_off, void** d_text, uint64_t* n_records, uint64_t* n_bytes) {
+    if (text_family_ready(job, k, nullptr, 0) != PG_OK || ci >= job->chains.size()) return PG_ERR_INVALID;
+    const RecordTextFamily& f = job->*k.text;
     if (d_off) *d_off = f.d + f.o_off + f.first[ci] * 8;
     if (d_text) *d_text = f.d + f.text_first[ci];
     if (n_records) *n_records = f.first[ci + 1] - f.first[ci];
     if (n_bytes) *n_bytes = f.text_first[ci + 1] - f.text_first[ci];
     return PG_OK;
+}
+
+extern "C" int pg_job_record_text_first(pg_job* job, uint64_t* text_first, char* err, size_t errlen) { return text_family_first(job, kRecordText, text_first, err, errlen); }
+extern "C" int pg_job_fetch_record_text(pg_job* job, uint32_t ci, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
+    return text_family_fetch_chain(job, kRecordText, ci, off, text, n_bytes, err, errlen);
+}
+extern "C" int pg_job_fetch_record_text_packed(pg_job* job, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
+    return text_family_fetch_packed(job, kRecordText, off, text, n_bytes, err, errlen);
+}
+extern "C" int pg_job_device_record_text(pg_job* job, uint32_t ci, void** d_off, void** d_text, uint64_t* n_records, uint64_t* n_bytes) {
+    return text_family_device(job, kRecordText, ci, d_off, d_text, n_records, n_bytes);
 }
 
 // The unit entry point: arbitrary fields in, the packed text and its offsets out, through the same kernels.

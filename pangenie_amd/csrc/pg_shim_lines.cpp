@@ -1,6 +1,9 @@
 // pg_shim_lines.cpp — the C-ABI of the record lines (pg_record_lines.hip):
 // the prefix of an index contig or of a stride of them, plain or slotted, the forming of whole VCF lines from a job's record
-// text, their fetches, and the unit entry points over host arrays.  Host code off the critical path.
+// text, their fetches, and the unit entry points over host arrays.  A job has two such families — the lines of the record
+// text (GT:GQ:GL:KC) and those of the phased text (GT:KC), each with prefixes of its own — and ONE
+// implementation: every function below the unit entry points' takes the family as a LinesKind row (pg_job.h).  Host code
+// off the critical path.
 #include <hip/hip_runtime_api.h>
 
 #include <string.h>
@@ -53,25 +56,24 @@ void rlines_launch(unsigned char* d, const RLinesLayout& L, bool slotted, const 
                       (uint32_t*)(d + L.o_loc), (uint32_t*)(d + L.o_bsum), (uint64_t*)(d + L.o_bbase), (uint64_t*)(d + L.o_off), n_lines, (char*)d, cap, s);
 }
 
-bool text_current(const pg_job* job) {
-    const RecordTextFamily& t = job->rtext;
+bool text_current(const pg_job* job, const LinesKind& k) {
+    const RecordTextFamily& t = job->*k.text.text;
     return job->ran && t.formed && !t.dirty && t.run == job->run_serial;
 }
 
-int rlines_ready(pg_job* job, char* err, size_t errlen) {
+int rlines_ready(pg_job* job, const LinesKind& k, char* err, size_t errlen) {
     if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
-    const RecordLinesFamily& f = job->rlines;
-    if (!text_current(job) || !f.formed || f.text_serial != job->rtext.serial) {
-        set_err(err, errlen, "pg_job_record_lines has not been called for this text and these prefixes");
+    const RecordLinesFamily& f = job->*k.lines;
+    if (!text_current(job, k) || !f.formed || f.text_serial != (job->*k.text.text).serial) {
+        set_err(err, errlen, "%s has not been called for this text and these prefixes", k.former);
         return PG_ERR_INVALID;
     }
     return PG_OK;
 }
 
 // lines [l0, l1) of a formed job: their offsets less `minus` and their bytes [b0, b1), n_bytes of them
-int rlines_fetch(pg_job* job, uint64_t l0, uint64_t l1, uint64_t b0, uint64_t b1, uint64_t minus, uint64_t* off, char* text, uint64_t n_bytes, char* err,
-                 size_t errlen) {
-    const RecordLinesFamily& f = job->rlines;
+int rlines_fetch(pg_job* job, const RecordLinesFamily& f, uint64_t l0, uint64_t l1, uint64_t b0, uint64_t b1, uint64_t minus, uint64_t* off, char* text,
+                 uint64_t n_bytes, char* err, size_t errlen) {
     if (n_bytes != b1 - b0) { set_err(err, errlen, "the lines hold %llu bytes, not %llu", (unsigned long long)(b1 - b0), (unsigned long long)n_bytes); return PG_ERR_INVALID; }
     if (n_bytes && !text) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
     HIP_TRY(hipSetDevice(job->device));
@@ -118,7 +120,8 @@ int check_prefix(uint32_t R, const uint64_t* off, const char* bytes, const uint3
 }
 
 // the checked prefix on the job's device, ready to be referred to by index contigs
-int prefix_to_device(pg_job* job, uint32_t R, const uint64_t* off, const char* bytes, const uint32_t* slot, LinePrefixRef* ref, char* err, size_t errlen) {
+int prefix_to_device(pg_job* job, const LinesKind& k, uint32_t R, const uint64_t* off, const char* bytes, const uint32_t* slot, LinePrefixRef* ref, char* err,
+                     size_t errlen) {
     HIP_TRY(hipSetDevice(job->device));
     LinePrefix p;
     p.R = R; p.bytes = off[R];
@@ -135,15 +138,14 @@ int prefix_to_device(pg_job* job, uint32_t R, const uint64_t* off, const char* b
         return PG_ERR_DEVICE;
     }
     *ref = line_prefix_ref(p);
-    RecordLinesFamily& f = job->rlines;
+    RecordLinesFamily& f = job->*k.lines;
     if (f.prefix.size() != job->index.size()) f.prefix.resize(job->index.size());
     if (job->stream) HIP_TRY(hipStreamSynchronize(job->stream));   // (nothing reads the prefixes this one replaces any more)
     return PG_OK;
 }
 
-}  // namespace
-
-extern "C" int pg_job_line_prefix_slotted(pg_job* job, uint32_t ix, const uint64_t* off, const char* bytes, const uint32_t* slot, char* err, size_t errlen) {
+// the prefix of one index contig, plain (slot null) or slotted
+int line_prefix(pg_job* job, const LinesKind& k, uint32_t ix, const uint64_t* off, const char* bytes, const uint32_t* slot, char* err, size_t errlen) {
     if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
     if (ix >= job->index.size()) { set_err(err, errlen, "index contig %u of %zu", ix, job->index.size()); return PG_ERR_INVALID; }
     if (ix >= job->rplans.size() || !job->rplans[ix]) { set_err(err, errlen, "index contig %u has no record plan", ix); return PG_ERR_INVALID; }
@@ -151,15 +153,26 @@ extern "C" int pg_job_line_prefix_slotted(pg_job* job, uint32_t ix, const uint64
     int rc = check_prefix(R, off, bytes, slot, err, errlen);
     if (rc != PG_OK) return rc;
     LinePrefixRef ref;
-    rc = prefix_to_device(job, R, off, bytes, slot, &ref, err, errlen);
+    rc = prefix_to_device(job, k, R, off, bytes, slot, &ref, err, errlen);
     if (rc != PG_OK) return rc;
-    job->rlines.prefix[ix] = std::move(ref);   // (this index contig's reference alone: the members of a stride keep theirs)
-    job->rlines.formed = false;
+    (job->*k.lines).prefix[ix] = std::move(ref);   // (this index contig's reference alone: the members of a stride keep theirs)
+    (job->*k.lines).formed = false;
     return PG_OK;
 }
 
+}  // namespace
+
+extern "C" int pg_job_line_prefix_slotted(pg_job* job, uint32_t ix, const uint64_t* off, const char* bytes, const uint32_t* slot, char* err, size_t errlen) {
+    return line_prefix(job, kRecordLines, ix, off, bytes, slot, err, errlen);
+}
+
 extern "C" int pg_job_line_prefix(pg_job* job, uint32_t ix, const uint64_t* off, const char* bytes, char* err, size_t errlen) {
-    return pg_job_line_prefix_slotted(job, ix, off, bytes, nullptr, err, errlen);
+    return line_prefix(job, kRecordLines, ix, off, bytes, nullptr, err, errlen);
+}
+
+// (a plain prefix: the slotted kernel prints UK by the genotyping rule, which is not the phasing column's)
+extern "C" int pg_job_phased_line_prefix(pg_job* job, uint32_t ix, const uint64_t* off, const char* bytes, char* err, size_t errlen) {
+    return line_prefix(job, kPhasedLines, ix, off, bytes, nullptr, err, errlen);
 }
 
 extern "C" int pg_job_line_prefix_strided(pg_job* job, uint32_t contig, uint32_t n_contigs, const uint64_t* off, const char* bytes, const uint32_t* slot,
@@ -179,19 +192,22 @@ extern "C" int pg_job_line_prefix_strided(pg_job* job, uint32_t contig, uint32_t
     int rc = check_prefix(R, off, bytes, slot, err, errlen);
     if (rc != PG_OK) return rc;
     LinePrefixRef ref;
-    rc = prefix_to_device(job, R, off, bytes, slot, &ref, err, errlen);
+    rc = prefix_to_device(job, kRecordLines, R, off, bytes, slot, &ref, err, errlen);
     if (rc != PG_OK) return rc;
     for (size_t ix = contig; ix < job->index.size(); ix += n_contigs) job->rlines.prefix[ix] = ref;
     job->rlines.formed = false;
     return PG_OK;
 }
 
-extern "C" int pg_job_record_lines(pg_job* job, char* err, size_t errlen) {
+namespace {
+
+// the lines of every index contig that takes part, joined from the family's text as it is
+int form_lines(pg_job* job, const LinesKind& k, char* err, size_t errlen) {
     if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
-    if (!text_current(job)) { set_err(err, errlen, "pg_job_record_text has not been called for this run and these plans"); return PG_ERR_INVALID; }
+    if (!text_current(job, k)) { set_err(err, errlen, "%s has not been called for this run and these plans", k.text.former); return PG_ERR_INVALID; }
     HIP_TRY(hipSetDevice(job->device));
-    RecordLinesFamily& f = job->rlines;
-    const RecordTextFamily& t = job->rtext;
+    RecordLinesFamily& f = job->*k.lines;
+    const RecordTextFamily& t = job->*k.text.text;
     const size_t n_index = job->index.size(), n_chains = job->chains.size();
     f.formed = false;
     // the members of every index contig: its chains in ascending id
@@ -282,43 +298,74 @@ extern "C" int pg_job_record_lines(pg_job* job, char* err, size_t errlen) {
     return PG_OK;
 }
 
-extern "C" double pg_job_record_lines_ms(const pg_job* job) { return job ? job->rlines.ms : 0.0; }
-
-extern "C" int pg_job_record_lines_first(pg_job* job, uint64_t* n_index_contigs, uint64_t* line_first, uint64_t* byte_first, char* err, size_t errlen) {
+int lines_first(pg_job* job, const LinesKind& k, uint64_t* n_index_contigs, uint64_t* line_first, uint64_t* byte_first, char* err, size_t errlen) {
     if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
     if (n_index_contigs) *n_index_contigs = job->index.size();
     if (!line_first && !byte_first) return PG_OK;
-    const int rc = rlines_ready(job, err, errlen);
+    const int rc = rlines_ready(job, k, err, errlen);
     if (rc != PG_OK) return rc;
-    const RecordLinesFamily& f = job->rlines;
+    const RecordLinesFamily& f = job->*k.lines;
     if (line_first) memcpy(line_first, f.line_first.data(), f.line_first.size() * sizeof(uint64_t));
     if (byte_first) memcpy(byte_first, f.byte_first.data(), f.byte_first.size() * sizeof(uint64_t));
     return PG_OK;
 }
 
-extern "C" int pg_job_fetch_record_lines(pg_job* job, uint32_t ix, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
-    const int rc = rlines_ready(job, err, errlen);
+int fetch_lines(pg_job* job, const LinesKind& k, uint32_t ix, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
+    const int rc = rlines_ready(job, k, err, errlen);
     if (rc != PG_OK) return rc;
     if (ix >= job->index.size()) { set_err(err, errlen, "bad argument"); return PG_ERR_INVALID; }
-    const RecordLinesFamily& f = job->rlines;
-    return rlines_fetch(job, f.line_first[ix], f.line_first[ix + 1], f.byte_first[ix], f.byte_first[ix + 1], f.byte_first[ix], off, text, n_bytes, err, errlen);
+    const RecordLinesFamily& f = job->*k.lines;
+    return rlines_fetch(job, f, f.line_first[ix], f.line_first[ix + 1], f.byte_first[ix], f.byte_first[ix + 1], f.byte_first[ix], off, text, n_bytes, err, errlen);
 }
 
-extern "C" int pg_job_fetch_record_lines_packed(pg_job* job, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
-    const int rc = rlines_ready(job, err, errlen);
+int fetch_lines_packed(pg_job* job, const LinesKind& k, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
+    const int rc = rlines_ready(job, k, err, errlen);
     if (rc != PG_OK) return rc;
-    const RecordLinesFamily& f = job->rlines;
-    return rlines_fetch(job, 0, f.n_lines, 0, f.byte_first.back(), 0, off, text, n_bytes, err, errlen);
+    const RecordLinesFamily& f = job->*k.lines;
+    return rlines_fetch(job, f, 0, f.n_lines, 0, f.byte_first.back(), 0, off, text, n_bytes, err, errlen);
 }
 
-extern "C" int pg_job_device_record_lines(pg_job* job, uint32_t ix, void** d_off, void** d_text, uint64_t* n_lines, uint64_t* n_bytes) {
-    if (rlines_ready(job, nullptr, 0) != PG_OK || ix >= job->index.size()) return PG_ERR_INVALID;
-    const RecordLinesFamily& f = job->rlines;
+int device_lines(pg_job* job, const LinesKind& k, uint32_t ix, void** d_off, void** d_text, uint64_t* n_lines, uint64_t* n_bytes) {
+    if (rlines_ready(job, k, nullptr, 0) != PG_OK || ix >= job->index.size()) return PG_ERR_INVALID;
+    const RecordLinesFamily& f = job->*k.lines;
     if (d_off) *d_off = f.d + f.o_off + f.line_first[ix] * 8;
     if (d_text) *d_text = f.d + f.byte_first[ix];
     if (n_lines) *n_lines = f.line_first[ix + 1] - f.line_first[ix];
     if (n_bytes) *n_bytes = f.byte_first[ix + 1] - f.byte_first[ix];
     return PG_OK;
+}
+
+}  // namespace
+
+extern "C" int pg_job_record_lines(pg_job* job, char* err, size_t errlen) { return form_lines(job, kRecordLines, err, errlen); }
+extern "C" double pg_job_record_lines_ms(const pg_job* job) { return job ? job->rlines.ms : 0.0; }
+extern "C" int pg_job_record_lines_first(pg_job* job, uint64_t* n_index_contigs, uint64_t* line_first, uint64_t* byte_first, char* err, size_t errlen) {
+    return lines_first(job, kRecordLines, n_index_contigs, line_first, byte_first, err, errlen);
+}
+extern "C" int pg_job_fetch_record_lines(pg_job* job, uint32_t ix, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
+    return fetch_lines(job, kRecordLines, ix, off, text, n_bytes, err, errlen);
+}
+extern "C" int pg_job_fetch_record_lines_packed(pg_job* job, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
+    return fetch_lines_packed(job, kRecordLines, off, text, n_bytes, err, errlen);
+}
+extern "C" int pg_job_device_record_lines(pg_job* job, uint32_t ix, void** d_off, void** d_text, uint64_t* n_lines, uint64_t* n_bytes) {
+    return device_lines(job, kRecordLines, ix, d_off, d_text, n_lines, n_bytes);
+}
+
+// the lines of the phased text: the same joiner over the family's own prefixes
+extern "C" int pg_job_phased_lines(pg_job* job, char* err, size_t errlen) { return form_lines(job, kPhasedLines, err, errlen); }
+extern "C" double pg_job_phased_lines_ms(const pg_job* job) { return job ? job->plines.ms : 0.0; }
+extern "C" int pg_job_phased_lines_first(pg_job* job, uint64_t* n_index_contigs, uint64_t* line_first, uint64_t* byte_first, char* err, size_t errlen) {
+    return lines_first(job, kPhasedLines, n_index_contigs, line_first, byte_first, err, errlen);
+}
+extern "C" int pg_job_fetch_phased_lines(pg_job* job, uint32_t ix, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
+    return fetch_lines(job, kPhasedLines, ix, off, text, n_bytes, err, errlen);
+}
+extern "C" int pg_job_fetch_phased_lines_packed(pg_job* job, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
+    return fetch_lines_packed(job, kPhasedLines, off, text, n_bytes, err, errlen);
+}
+extern "C" int pg_job_device_phased_lines(pg_job* job, uint32_t ix, void** d_off, void** d_text, uint64_t* n_lines, uint64_t* n_bytes) {
+    return device_lines(job, kPhasedLines, ix, d_off, d_text, n_lines, n_bytes);
 }
 
 namespace {

@@ -493,6 +493,57 @@ class Job:
         """elapsed ms of the kernels of the last record_lines()"""
         return float(self._lib.pg_job_record_lines_ms(self.h))
 
+    def record_phase(self, contig: Optional[int] = None):
+        """pg_job_record_phase + the fetches: of a run_phasing job, per VCF RECORD the two GT numbers of the phasing column
+        (calls.PHASE_DTYPE; PG_PHASE_UNDEFINED prints `.`) from the Viterbi haplotypes on the device.  One
+        array per chain (empty for a chain whose index contig has no plan), or chain `contig`'s."""
+        from . import calls as _calls
+        return _calls.job_record_phase(self, contig)
+
+    def record_phase_ms(self) -> float:
+        """elapsed ms of the kernel of the last record_phase()"""
+        return float(self._lib.pg_job_record_phase_ms(self.h))
+
+    def phased_text(self, contig: Optional[int] = None, ignore_imputed: bool = False):
+        """pg_job_phased_text + pg_job_fetch_phased_text: the bytes of the GT:KC column per VCF RECORD (`a|b:KC`, `./.:KC` for a
+        bubble without unique k-mers under ignore_imputed).  (off [R + 1], bytes) per chain, or chain `contig`'s."""
+        from . import calls as _calls
+        return _calls.job_phased_text(self, contig, ignore_imputed)
+
+    def phased_text_packed(self, ignore_imputed: bool = False):
+        """pg_job_phased_text + pg_job_fetch_phased_text_packed: (off [R_total + 1] absolute, all chains' bytes from ONE copy,
+        record_first, text_first [n_chains + 1])."""
+        from . import calls as _calls
+        _calls.form_phased_text(self, ignore_imputed)
+        return _calls.fetch_phased_text_packed(self)
+
+    def phased_text_ms(self) -> float:
+        """elapsed ms of the kernels of the last phased_text()"""
+        return float(self._lib.pg_job_phased_text_ms(self.h))
+
+    def phased_line_prefix(self, contig: int, off, data) -> None:
+        """pg_job_phased_line_prefix: the fixed columns (CHROM .. INFO, GT:KC, no trailing tab) of the records of INDEX contig
+        `contig` for the phased lines: a family of prefixes of its own beside line_prefix()'s."""
+        from . import calls as _calls
+        _calls.job_phased_line_prefix(self, contig, off, data)
+
+    def phased_lines(self, contig: Optional[int] = None):
+        """pg_job_phased_lines + pg_job_fetch_phased_lines: whole lines of the phasing VCF joined on the device from the text
+        of the last phased_text().  (off, bytes) of index contig `contig`, or of all."""
+        from . import calls as _calls
+        return _calls.job_phased_lines(self, contig)
+
+    def phased_lines_packed(self):
+        """pg_job_phased_lines + pg_job_fetch_phased_lines_packed: (off [n_lines + 1] absolute, all bytes from ONE copy,
+        line_first, byte_first [n_index_contigs + 1])."""
+        from . import calls as _calls
+        _calls.form_phased_lines(self)
+        return _calls.fetch_phased_lines_packed(self)
+
+    def phased_lines_ms(self) -> float:
+        """elapsed ms of the kernels of the last phased_lines()"""
+        return float(self._lib.pg_job_phased_lines_ms(self.h))
+
     def combine_plan(self, groups) -> None:
         """pg_job_combine_plan: groups = per group the chains (contig x path subset) that genotype the same index objects, in the
         order they are to be added up; a second plan replaces the first."""

@@ -106,22 +106,24 @@ int fetch_chain_meta(pg_job* job, uint32_t chain, size_t V, std::vector<uint16_t
 // What the drivers need of one chromosome: depends on the index alone, made once whatever the samples and batches.
 struct Chromosome {
     std::string name;
-    FlatContig flat;              // ALL paths of the panel
+    FlatContig flat;              // ALL paths of the panel (the phasing drivers: the selected ones)
     std::vector<uint64_t> goff;   // pg_hmm_geno_offsets of `flat`
     // what the functions that return VCF records add (add_record_plans, record_chromosomes)
     const Graph* graph = nullptr;
     RecordPlan plan;
     std::vector<uint64_t> gl_off;
+    bool host_route = false;      // the phasing drivers: no plan on the device, the column is formed here (phase_cohort_record_text)
 };
 
-// the index view of `chromosomes` over all paths, in the order of the map (a DeviceCountPlan's too)
-std::vector<Chromosome> index_chromosomes(std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes) {
+// the index view of `chromosomes` over all paths (or `only_paths`), in the order of the map (a DeviceCountPlan's too)
+std::vector<Chromosome> index_chromosomes(std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes,
+                                          std::vector<unsigned short>* only_paths = nullptr) {
     std::vector<Chromosome> chroms(chromosomes.size());
     size_t c = 0;
     for (auto& kv : chromosomes) {
         Chromosome& x = chroms[c++];
         x.name = kv.first;
-        flatten(&kv.second, nullptr, x.flat);
+        flatten(&kv.second, only_paths, x.flat);
         x.goff.assign(x.flat.variant_pos.size() + 1, 0);
         pg_hmm_geno_offsets(&x.flat.batch, x.goff.data());
     }
@@ -691,27 +693,40 @@ int chain_record_text(pg_job* job, uint32_t chain, const Chromosome& x, bool ign
 // ------------------------------------------------------------------ cohort job, the sample column per VCF record
 using CoverageRows = std::vector<std::vector<const uint16_t*>>;   // [sample][chromosome], SampleRows::cov_rows
 
-// The job of the four genotype_cohort_record_* functions: a cohort job with one record plan per chromosome, whatever the number
-// of samples, made and run; then `tail(job, chroms, cov_rows)`: exactly one of the three tails below.  (All four name
-// genotype_cohort_record_calls in a refusal: callers match on these texts.)
-template <class Tail>
+// The job of the genotype_cohort_record_* and phase_cohort_record_* functions: a cohort job over all paths or `only_paths`
+// under `prm`, with one record plan per chromosome, whatever the number of samples — none for a chromosome `on_host(graph)`
+// keeps for the host route —, made and run; then `tail(job, chroms, cov_rows)`: exactly one of the tails below.  `who`: the
+// name in a refusal.
+template <class OnHost, class Tail>
 void run_record_cohort(std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
-                       const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N,
-                       int device, Tail tail) {
+                       const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, std::vector<unsigned short>* only_paths, const pg_hmm_params& prm,
+                       int device, const char* who, OnHost on_host, Tail tail) {
     if (chromosomes.empty() || samples.empty()) return;
-    std::vector<Chromosome> chroms = index_chromosomes(chromosomes);
-    add_record_plans(chroms, graphs, "genotype_cohort_record_calls");
-    const SampleRows rows = sample_rows(samples, chroms, "genotype_cohort_record_calls");
-    const Job job = cohort_job(device, chroms, rows.rows, probabilities, genotyping_params(recombrate, uniform, effective_N));
+    std::vector<Chromosome> chroms = index_chromosomes(chromosomes, only_paths);
+    add_record_plans(chroms, graphs, who);
+    for (Chromosome& x : chroms) x.host_route = on_host(*x.graph);   // (every graph is looked at once)
+    const SampleRows rows = sample_rows(samples, chroms, who);
+    const Job job = cohort_job(device, chroms, rows.rows, probabilities, prm);
     char err[512] = {0};
     int rc = PG_OK;
     for (size_t c = 0; c < chroms.size() && rc == PG_OK; ++c) {
+        if (chroms[c].host_route) continue;
         const pg_record_plan view = chroms[c].plan.view();
         rc = pg_job_record_plan(job.get(), (uint32_t)c, &view, err, sizeof(err));
     }
     if (rc == PG_OK) rc = pg_job_run(job.get(), nullptr, err, sizeof(err));
     check_rc(rc, err);
     tail(job.get(), chroms, rows.cov_rows);
+}
+
+// ... of the four genotype_cohort_record_* functions: all paths, the genotyping.  (All four name genotype_cohort_record_calls in
+// a refusal: callers match on these texts.)
+template <class Tail>
+void run_record_cohort(std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+                       const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N,
+                       int device, Tail tail) {
+    run_record_cohort(chromosomes, graphs, samples, probabilities, nullptr, genotyping_params(recombrate, uniform, effective_N), device,
+                      "genotype_cohort_record_calls", [](const Graph&) { return false; }, tail);
 }
 
 void add_gl_offsets(std::vector<Chromosome>& chroms) {
@@ -897,6 +912,150 @@ std::map<std::string, RecordLines> genotype_cohort_record_lines(
                       [&](pg_job* job, std::vector<Chromosome>& chroms, const CoverageRows& cov_rows) {
                           cohort_record_lines(job, chroms, cov_rows, ignore_imputed, &lines);
                       });
+    return lines;
+}
+
+// ------------------------------------------------------------------ cohort job, the phasing column per VCF record
+namespace {
+
+pg_hmm_params phasing_params(double recombrate, bool uniform, long double effective_N) {
+    pg_hmm_params prm = genotyping_params(recombrate, uniform, effective_N);
+    prm.run_genotyping = 0; prm.run_phasing = 1;
+    return prm;
+}
+
+// The host route of one chain: pg_job_fetch's haplotypes, kept flags, k-mer counts and coverage as one GenotypingResult per
+// bubble — what HMM(..., false, true, ...) hands out —, printed by Graph::phasing_records; the last column of every line.
+int chain_phasing_on_host(pg_job* job, uint32_t chain, const Chromosome& x, bool ignore_imputed, RecordText& out, char* err, size_t errlen) {
+    const size_t V = x.flat.variant_pos.size();
+    std::vector<uint16_t> hap1(V ? V : 1), hap2(V ? V : 1), n_kmers(V ? V : 1), cov(V ? V : 1);
+    std::vector<uint8_t> kept(V ? V : 1);
+    pg_contig_result r{};
+    r.haplotype_1 = hap1.data(); r.haplotype_2 = hap2.data(); r.kept = kept.data(); r.n_kmers = n_kmers.data(); r.coverage = cov.data();
+    const int rc = pg_job_fetch(job, chain, &r, err, errlen);
+    if (rc != PG_OK) return rc;
+    std::vector<GenotypingResult> results(V);
+    for (size_t v = 0; v < V; ++v) {
+        if (kept[v]) { results[v].add_first_haplotype_allele(hap1[v]); results[v].add_second_haplotype_allele(hap2[v]); }
+        results[v].set_unique_kmers(n_kmers[v]);
+        results[v].set_coverage(cov[v]);
+    }
+    out.off.assign(1, 0);
+    out.bytes.clear();
+    for (const std::string& line : x.graph->phasing_records(results, ignore_imputed)) {
+        out.bytes.append(line, line.rfind('\t') + 1, std::string::npos);
+        out.off.push_back(out.bytes.size());
+    }
+    return PG_OK;
+}
+
+// the column as bytes: one packed copy, then chain by chain; no haplotype is fetched except on the host route.  text[s] = sample s
+void cohort_phased_text(pg_job* job, std::vector<Chromosome>& chroms, const CoverageRows& cov_rows, bool ignore_imputed,
+                        std::vector<std::map<std::string, RecordText>>* text) {
+    const size_t C = chroms.size(), S = cov_rows.size();
+    char err[512] = {0};
+    check_rc(pg_job_phased_text(job, ignore_imputed ? 1 : 0, err, sizeof(err)), err);
+    std::vector<uint64_t> rec_first(S * C + 1, 0), text_first(S * C + 1, 0);
+    check_rc(pg_job_phased_text_first(job, rec_first.data(), text_first.data(), err, sizeof(err)), err);
+    std::vector<uint64_t> off(rec_first.back() + 1, 0);
+    std::string packed(text_first.back(), '\0');
+    check_rc(pg_job_fetch_phased_text_packed(job, off.data(), packed.empty() ? nullptr : &packed[0], packed.size(), err, sizeof(err)), err);
+    for (size_t s = 0; s < S; ++s)
+        for (size_t c = 0; c < C; ++c) {
+            const Chromosome& x = chroms[c];
+            const size_t chain = s * C + c, R = x.plan.nr_of_records();
+            RecordText& t = (*text)[s][x.name];
+            std::vector<uint16_t> n_kmers, coverage;   // (host memory of the job: no device copy)
+            check_rc(fetch_chain_meta(job, (uint32_t)chain, x.flat.variant_pos.size(), &n_kmers, &coverage, nullptr, err, sizeof(err)), err);
+            t.unique_kmers.assign(n_kmers.begin(), n_kmers.end());
+            if (x.host_route) {
+                check_rc(chain_phasing_on_host(job, (uint32_t)chain, x, ignore_imputed, t, err, sizeof(err)), err);
+                continue;
+            }
+            if (rec_first[chain + 1] - rec_first[chain] != R) fail("phase_cohort_record_text: chain " + std::to_string(chain) + " holds other records than its plan's");
+            const uint64_t* o = off.data() + rec_first[chain];
+            t.off.assign(R + 1, 0);
+            for (size_t q = 0; q <= R; ++q) t.off[q] = o[q] - o[0];
+            t.bytes.assign(packed, o[0], o[R] - o[0]);
+        }
+}
+
+// The phased text formed and left on the device, then the lines joined there: a prefix per chromosome, one launch, ONE packed
+// copy — of the lines.  No text comes to the host: every record has one, so no line is the host's to compose.  UK is what
+// pg_job_fetch reports (host memory of the job).  Only the chains of a chromosome on the host route are fetched and printed here.
+void cohort_phased_lines(pg_job* job, std::vector<Chromosome>& chroms, const CoverageRows& cov_rows, bool ignore_imputed,
+                         std::map<std::string, RecordLines>* lines) {
+    const size_t C = chroms.size(), S = cov_rows.size();
+    char err[512] = {0};
+    check_rc(pg_job_phased_text(job, ignore_imputed ? 1 : 0, err, sizeof(err)), err);
+    std::vector<std::vector<std::string>> fixed(C);
+    for (size_t c = 0; c < C; ++c) {
+        const std::string& name = chroms[c].name;
+        const size_t V = chroms[c].flat.variant_pos.size();
+        std::vector<uint16_t> first, n_kmers, coverage;
+        for (size_t s = 0; s < S; ++s) {
+            check_rc(fetch_chain_meta(job, (uint32_t)(s * C + c), V, s ? &n_kmers : &first, &coverage, nullptr, err, sizeof(err)), err);
+            if (s && n_kmers != first) fail("phase_cohort_record_lines: the samples' unique k-mer counts differ on " + name);
+        }
+        fixed[c] = chroms[c].graph->phasing_fixed_columns(std::vector<unsigned short>(first.begin(), first.end()));
+        if (chroms[c].host_route) continue;
+        std::vector<uint64_t> poff(fixed[c].size() + 1, 0);
+        std::string pbytes;
+        for (size_t r = 0; r < fixed[c].size(); ++r) { pbytes += fixed[c][r]; poff[r + 1] = pbytes.size(); }
+        check_rc(pg_job_phased_line_prefix(job, (uint32_t)c, poff.data(), pbytes.empty() ? nullptr : pbytes.data(), err, sizeof(err)), err);
+    }
+    check_rc(pg_job_phased_lines(job, err, sizeof(err)), err);
+    std::vector<uint64_t> line_first(C + 1, 0), byte_first(C + 1, 0);
+    uint64_t n_index = 0;
+    check_rc(pg_job_phased_lines_first(job, &n_index, nullptr, nullptr, err, sizeof(err)), err);
+    if (n_index != C) fail("phase_cohort_record_lines: the job has " + std::to_string(n_index) + " index contigs, not " + std::to_string(C));
+    check_rc(pg_job_phased_lines_first(job, nullptr, line_first.data(), byte_first.data(), err, sizeof(err)), err);
+    std::vector<uint64_t> loff(line_first.back() + 1, 0);
+    std::string lbytes(byte_first.back(), '\0');
+    check_rc(pg_job_fetch_phased_lines_packed(job, loff.data(), lbytes.empty() ? nullptr : &lbytes[0], lbytes.size(), err, sizeof(err)), err);
+    for (size_t c = 0; c < C; ++c) {
+        const size_t R = fixed[c].size();
+        RecordLines& out = (*lines)[chroms[c].name];
+        if (chroms[c].host_route) {   // no line on the device: every one is composed from the samples' columns formed here
+            std::vector<RecordText> text(S);
+            std::vector<const RecordText*> texts(S);
+            for (size_t s = 0; s < S; ++s) {
+                check_rc(chain_phasing_on_host(job, (uint32_t)(s * C + c), chroms[c], ignore_imputed, text[s], err, sizeof(err)), err);
+                texts[s] = &text[s];
+            }
+            RecordLines none;
+            none.off.assign(R + 1, 0);
+            out = compose_record_lines(fixed[c], texts, none);
+            continue;
+        }
+        if (line_first[c + 1] - line_first[c] != R) fail("phase_cohort_record_lines: chromosome " + std::to_string(c) + " holds other lines than its plan's records");
+        out.off.assign(R + 1, 0);
+        for (size_t r = 0; r <= R; ++r) out.off[r] = loff[line_first[c] + r] - byte_first[c];
+        out.bytes.assign(lbytes, byte_first[c], byte_first[c + 1] - byte_first[c]);
+    }
+}
+
+}  // namespace
+
+std::vector<std::map<std::string, RecordText>> phase_cohort_record_text(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, std::vector<unsigned short>* only_paths, double recombrate, bool uniform,
+    long double effective_N, int device, bool ignore_imputed) {
+    std::vector<std::map<std::string, RecordText>> text(samples.size());
+    run_record_cohort(chromosomes, graphs, samples, probabilities, only_paths, phasing_params(recombrate, uniform, effective_N), device, "phase_cohort_record_text",
+                      [](const Graph& g) { return g.has_undefined_reference_allele(); },
+                      [&](pg_job* job, std::vector<Chromosome>& chroms, const CoverageRows& cov_rows) { cohort_phased_text(job, chroms, cov_rows, ignore_imputed, &text); });
+    return text;
+}
+
+std::map<std::string, RecordLines> phase_cohort_record_lines(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, std::vector<unsigned short>* only_paths, double recombrate, bool uniform,
+    long double effective_N, int device, bool ignore_imputed) {
+    std::map<std::string, RecordLines> lines;
+    run_record_cohort(chromosomes, graphs, samples, probabilities, only_paths, phasing_params(recombrate, uniform, effective_N), device, "phase_cohort_record_lines",
+                      [](const Graph& g) { return g.has_undefined_reference_allele(); },
+                      [&](pg_job* job, std::vector<Chromosome>& chroms, const CoverageRows& cov_rows) { cohort_phased_lines(job, chroms, cov_rows, ignore_imputed, &lines); });
     return lines;
 }
 

@@ -495,10 +495,11 @@ static std::string device_field(const RecordFields& f, size_t q, size_t n_define
 }
 
 // ... and from the device's bytes
-static std::string text_field(const RecordText& t, size_t q, size_t n_defined) {
+static std::string text_field(const RecordText& t, size_t q, size_t n_defined, bool phasing) {
     if (q + 1 >= t.off.size() || t.off[q + 1] < t.off[q] || t.off[q + 1] > t.bytes.size())
-        throw std::runtime_error("Graph::write_genotypes_of: the record text does not fit the graph's records");
+        throw std::runtime_error(std::string(phasing ? "Graph::write_phasing_of" : "Graph::write_genotypes_of") + ": the record text does not fit the graph's records");
     if (t.off[q + 1] == t.off[q]) {
+        if (phasing) throw std::runtime_error("Graph::write_phasing_of: a record's text is empty (every record has a phasing column)");
         const size_t n = n_defined * (n_defined + 1) / 2;
         if (n < 3) throw std::runtime_error("Graph::write_genotypes_of: too few likelihoods (" + std::to_string(n) + ") computed");
         throw std::runtime_error("Graph::write_genotypes_of: a record's text is still left to the host (genotype_cohort_record_text finishes them)");
@@ -545,17 +546,31 @@ std::string Graph::fixed_columns_of(const VcfSite& site, size_t record_index, si
     return line.str();
 }
 
-std::vector<std::string> Graph::genotypes_fixed_columns(const std::vector<unsigned short>& unique_kmers) const {
-    const char* who = "Graph::write_genotypes_of";
+std::vector<std::string> Graph::fixed_columns(const std::vector<unsigned short>& unique_kmers, const char* who, const char* format) const {
     if (variants_deleted_) throw std::runtime_error(std::string(who) + ": variants have been deleted by delete_variant funtion. Re-build object.");
     if (unique_kmers.size() != size()) throw std::runtime_error(std::string(who) + ": number of variants and number of computed genotypes differ.");
     std::vector<std::string> columns;
     std::vector<unsigned short> defined;
     for (size_t i = 0; i < size(); ++i)
         for (const VcfSite& site : get_variant(i).records(nullptr)) {
-            columns.push_back(fixed_columns_of(site, columns.size(), unique_kmers[i], who, defined) + "\tGT:GQ:GL:KC");
+            columns.push_back(fixed_columns_of(site, columns.size(), unique_kmers[i], who, defined) + '\t' + format);
         }
     return columns;
+}
+
+std::vector<std::string> Graph::genotypes_fixed_columns(const std::vector<unsigned short>& unique_kmers) const {
+    return fixed_columns(unique_kmers, "Graph::write_genotypes_of", "GT:GQ:GL:KC");
+}
+
+std::vector<std::string> Graph::phasing_fixed_columns(const std::vector<unsigned short>& unique_kmers) const {
+    return fixed_columns(unique_kmers, "Graph::write_phasing_of", "GT:KC");
+}
+
+bool Graph::has_undefined_reference_allele() const {
+    for (size_t i = 0; i < size(); ++i)
+        for (const VcfSite& site : get_variant(i).records(nullptr))
+            if (!site.undefined.empty() && site.undefined[0]) return true;
+    return false;
 }
 
 std::vector<std::string> Graph::genotypes_fixed_columns_slotted(std::vector<uint32_t>* slot) const {
@@ -636,7 +651,7 @@ std::vector<std::string> Graph::sample_records(const std::vector<GenotypingResul
                     if (among_defined.at(a) < 0) line << "\t."; else line << '\t' << among_defined[a];
                 }
             }
-            else if (device && device->text) line << "\tGT:GQ:GL:KC\t" << text_field(*device->text, record_index, defined.size());
+            else if (device && device->text) line << (phasing ? "\tGT:KC\t" : "\tGT:GQ:GL:KC\t") << text_field(*device->text, record_index, defined.size(), phasing);
             else if (device)
                 line << "\tGT:GQ:GL:KC\t"
                      << device_field(*device->fields, record_index, defined.size(), (*device->coverage)[i], ignore_imputed && (*device->unique_kmers)[i] == 0);
@@ -679,18 +694,29 @@ void Graph::write_genotypes(const std::string& filename, const RecordText& text,
     for (const std::string& l : records) out << l << '\n';
 }
 
-void Graph::write_genotypes(const std::string& filename, const RecordLines& lines, bool write_header, const std::vector<std::string>& samples) const {
+void Graph::write_lines(const std::string& filename, const RecordLines& lines, const std::vector<std::string>* header, bool phasing) const {
+    const char* who = phasing ? "Graph::write_phasing_of" : "Graph::write_genotypes_of";
     const size_t R = nr_of_records();   // (throws before the file is touched)
     if (lines.off.size() != R + 1 || lines.off[0] != 0 || lines.off[R] != lines.bytes.size())
-        throw std::runtime_error("Graph::write_genotypes_of: the record lines do not fit the graph's records");
+        throw std::runtime_error(std::string(who) + ": the record lines do not fit the graph's records");
     for (size_t r = 0; r < R; ++r)
         if (lines.off[r + 1] <= lines.off[r] || lines.bytes[lines.off[r + 1] - 1] != '\n')
-            throw std::runtime_error("Graph::write_genotypes_of: a record's line is empty or unfinished (genotype_cohort_record_lines finishes them)");
-    std::ofstream out(filename, write_header ? std::ios::out : std::ios::app);
-    if (!out.is_open()) throw std::runtime_error("Graph::write_genotypes_of: genotyping output file cannot be opened. Note that the filename must not contain non-existing directories.");
-    if (write_header)
-        for (const std::string& h : genotypes_header(samples)) out << h << '\n';
+            throw std::runtime_error(std::string(who) + ": a record's line is empty or unfinished (" + (phasing ? "phase_cohort_record_lines" : "genotype_cohort_record_lines") + " finishes them)");
+    std::ofstream out(filename, header ? std::ios::out : std::ios::app);
+    if (!out.is_open()) throw std::runtime_error(std::string(who) + ": " + (phasing ? "phasing" : "genotyping") + " output file cannot be opened. Note that the filename must not contain non-existing directories.");
+    if (header)
+        for (const std::string& h : *header) out << h << '\n';
     out.write(lines.bytes.data(), (std::streamsize)lines.bytes.size());
+}
+
+void Graph::write_genotypes(const std::string& filename, const RecordLines& lines, bool write_header, const std::vector<std::string>& samples) const {
+    const std::vector<std::string> header = genotypes_header(samples);
+    write_lines(filename, lines, write_header ? &header : nullptr, false);
+}
+
+void Graph::write_phasing(const std::string& filename, const RecordLines& lines, bool write_header, const std::vector<std::string>& samples) const {
+    const std::vector<std::string> header = phasing_header(samples);
+    write_lines(filename, lines, write_header ? &header : nullptr, true);
 }
 
 void Graph::write_genotypes(const std::string& filename, const RecordFields& fields, const std::vector<unsigned short>& coverage,
@@ -738,6 +764,17 @@ std::vector<std::string> Graph::phasing_header(const std::string& sample, const 
         lines.push_back(l);
     }
     return lines;
+}
+
+std::vector<std::string> Graph::phasing_header(const std::vector<std::string>& samples, const std::string& date) {
+    std::string columns;
+    for (size_t s = 0; s < samples.size(); ++s) columns += (s ? "\t" : "") + samples[s];
+    return phasing_header(columns, date);
+}
+
+std::vector<std::string> Graph::phasing_records(const RecordText& text) const {
+    const DeviceFields device = {nullptr, nullptr, &text.unique_kmers, &text};
+    return sample_records({}, false, true, nullptr, &device);
 }
 
 void Graph::write_phasing(const std::string& filename, const std::vector<GenotypingResult>& genotyping_result, bool write_header,

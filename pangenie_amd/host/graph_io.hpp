@@ -231,9 +231,23 @@ public:
     /** the phasing VCF of a `-p` run (reference Graph::write_phasing, src/graph.cpp:280-412): the same fixed columns, `GT:KC`
      *  with the Viterbi haplotypes `a|b` (HMM with run_phasing; `.` for an allele of undefined sequence) */
     static std::vector<std::string> phasing_header(const std::string& sample, const std::string& date = "");
+    /** ... with one column per sample: the names joined by tabs */
+    static std::vector<std::string> phasing_header(const std::vector<std::string>& samples, const std::string& date = "");
     std::vector<std::string> phasing_records(const std::vector<GenotypingResult>& genotyping_result, bool ignore_imputed = false) const;
     void write_phasing(const std::string& filename, const std::vector<GenotypingResult>& genotyping_result, bool write_header,
                        const std::string& sample, bool ignore_imputed = false) const;
+    /** per record, in phasing_records order, what a phased line holds in front of the sample columns: `CHROM .. INFO\tGT:KC`
+     *  without a trailing tab (UK from `unique_kmers`, one entry per bubble): the prefix of pg_job_phased_line_prefix */
+    std::vector<std::string> phasing_fixed_columns(const std::vector<unsigned short>& unique_kmers) const;
+    /** the phased lines with the `GT:KC` column arriving as bytes (DESIGN.md 4e-9, C ABI pg_job_phased_text): the fixed
+     *  columns as above (UK from text.unique_kmers), the column spliced in.  Throws where a record's text is empty. */
+    std::vector<std::string> phasing_records(const RecordText& text) const;
+    /** a multi-sample phasing VCF: the header (when asked for) with the samples' names, then the lines' bytes in ONE write.
+     *  Throws on offsets that do not fit the bytes or the graph's records, and on an empty line. */
+    void write_phasing(const std::string& filename, const RecordLines& lines, bool write_header, const std::vector<std::string>& samples) const;
+    /** a record whose REF holds a base outside ACGT: the record plan calls REF defined whatever it holds, the host prints `.`
+     *  for a haplotype on it — the device's phasing column is not the host's for such a graph (phase_cohort_record_text) */
+    bool has_undefined_reference_allele() const;
 
     /** the sampled panel as a VCF (`-d`; reference Graph::write_sampled_panel, src/graph.cpp:414-547): one column per sampled
      *  haplotype (`sampledHT<i>`), its allele among the record's defined ones, `.` where it carries undefined sequence */
@@ -250,6 +264,10 @@ private:
     };
     std::vector<std::string> sample_records(const std::vector<GenotypingResult>& genotyping_result, bool ignore_imputed, bool phasing,
                                             const std::vector<SampledPanel>* sampled_paths = nullptr, const DeviceFields* device = nullptr) const;
+    /** CHROM .. INFO and `format` of every record: genotypes_fixed_columns and phasing_fixed_columns */
+    std::vector<std::string> fixed_columns(const std::vector<unsigned short>& unique_kmers, const char* who, const char* format) const;
+    /** header lines (when asked for), then the lines' bytes in one write: the two multi-sample writers */
+    void write_lines(const std::string& filename, const RecordLines& lines, const std::vector<std::string>* header, bool phasing) const;
     /** CHROM .. INFO of one record (the ONE place that forms them): `defined` comes back as the record's defined alleles.
      *  With `uk_slot` the digits of `unique_kmers` are left out and *uk_slot = where they belong. */
     std::string fixed_columns_of(const VcfSite& site, size_t record_index, size_t unique_kmers, const char* who, std::vector<unsigned short>& defined,
@@ -323,7 +341,8 @@ std::vector<std::map<std::string, RecordText>> genotype_cohort_record_text(
  *  line the device left to the host is composed here from the prefix and the finished texts (compose_record_lines), so no
  *  line is empty; a record of fewer than three values throws.  Throws if the samples' unique k-mer counts of a chromosome
  *  differ: a multi-sample line has one INFO column (over a shared index they cannot).  Sampled cohorts, whose UK and reduced
- *  panels differ per sample, have genotype_cohort_sampled_record_lines.  Not covered: the combined (-a) records, phasing. */
+ *  panels differ per sample, have genotype_cohort_sampled_record_lines.  Not covered: the combined (-a) records (the phasing
+ *  column has phase_cohort_record_lines). */
 std::map<std::string, RecordLines> genotype_cohort_record_lines(
     std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
     const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false,
@@ -343,12 +362,39 @@ std::vector<std::map<std::string, RecordText>> genotype_cohort_sampled_record_te
  *  Graph::write_genotypes(filename, lines, ...) writes.  Neither text nor k-mer counts come back, except for a chain with a line
  *  the device left to the host: that chain's counts and text are fetched, the text finished as the sibling finishes it, and the
  *  lines composed over a prefix formed with that chain's UK (compose_record_lines).  A record of fewer than three values
- *  throws.  Not covered: the combined (-a) records, phasing. */
+ *  throws.  Not covered: the combined (-a) records; the phasing column over slotted prefixes. */
 std::vector<std::map<std::string, RecordLines>> genotype_cohort_sampled_record_lines(
     std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
     const std::vector<SampleCounts>& samples, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
     ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
     bool ignore_imputed = false, std::vector<std::map<std::string, SampledPaths>>* sampled = nullptr);
+
+/** The phasing job of a `-p` run to VCF text (reference src/commands.cpp:936-966, Graph::write_phasing): a
+ *  phasing-only cohort job over `only_paths` (null: all paths; the Viterbi kernels take at most 64, the reference passes at
+ *  most 30) with the setup of the genotype_cohort_record_* drivers — one plan per chromosome, whatever the number of samples —,
+ *  the run, pg_job_phased_text and ONE packed fetch of the bytes and their offsets: no haplotype comes back.  Per sample and
+ *  chromosome the `GT:KC` column of every record and, per bubble, UK as pg_job_fetch reports it (set at the COLUMN index);
+ *  Graph::phasing_records(text) gives the lines of Graph::phasing_records(results, ignore_imputed) on an HMM(..., false, true,
+ *  ...)'s results.  Every graph is checked once: a chromosome with a record whose REF is of undefined sequence
+ *  (Graph::has_undefined_reference_allele) gets no plan and goes down the host route — pg_job_fetch's haplotypes, one
+ *  GenotypingResult per bubble, Graph::phasing_records — inside the same job.  Throws std::runtime_error on a missing graph, a
+ *  graph whose bubble count is not the index's, samples that do not fit, and on the C ABI's errors. */
+std::vector<std::map<std::string, RecordText>> phase_cohort_record_text(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, std::vector<unsigned short>* only_paths = nullptr, double recombrate = 1.26,
+    bool uniform = false, long double effective_N = 25000.0L, int device = 0, bool ignore_imputed = false);
+
+/** The multi-sample phasing VCF with the LINES joined on the device: the job of phase_cohort_record_text, pg_job_phased_text —
+ *  whose bytes stay on the device —, one pg_job_phased_line_prefix per chromosome (Graph::phasing_fixed_columns; UK from
+ *  pg_job_fetch's host-side counts), pg_job_phased_lines and ONE packed fetch, of the lines: neither text nor haplotypes come to
+ *  the host.  Per chromosome the lines, sample s in column 9 + s, which Graph::write_phasing(filename, lines, ...) writes.  Only a
+ *  chromosome on the host route has its chains fetched, and its lines composed here from the fixed columns and the samples'
+ *  columns.  Throws if the samples' unique k-mer counts of a chromosome differ: a multi-sample line has one INFO column (over a
+ *  shared index and one path selection they cannot). */
+std::map<std::string, RecordLines> phase_cohort_record_lines(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, ProbabilityTable* probabilities, std::vector<unsigned short>* only_paths = nullptr, double recombrate = 1.26,
+    bool uniform = false, long double effective_N = 25000.0L, int device = 0, bool ignore_imputed = false);
 
 /** The `-a` flow to VCF lines: genotype_subsets for a caller who wants the sample column.  One job over every
  *  chromosome and subset, the subsets combined on the device (pg_job_combine), the plan of Graph::record_plan() on the index
