@@ -738,6 +738,57 @@ int  pg_phase_text_from_fields(int device, uint64_t n_records, const pg_phase* p
                                char* text, uint64_t cap);
 
 /* ------------------------------------------------------------------ *
+ *  The SAMPLED-PANEL VCF (PanGenie's `-d` output, all that PanGenie-sampling writes) from the device: per VCF
+ *  record one `GT` column per selected path of the chain's reduced panel (pangenie_amd/csrc/pg_panel_text.hip; the
+ *  rule: pg_panel.h), under the record plan of the chain's index contig.  Cell p of record r:
+ *  H = path_allele[v P + p], v the record's bubble and P the chain's paths; a = map[map_off[r] + H];
+ *  x = vcf_index[vcf_off[r] + a]; `.` if x == 0xFFFF, else x in decimal.  A record's text = its cells joined by
+ *  tabs, no leading tab, no terminator (what Graph::sample_records prints behind `\tGT\t`); every record has one.
+ *  pg_panel_text_bound(R, P) = R (4 P - 1) for P >= 1.
+ *  pg_job_panel_text needs a record plan on the chain's index contig and NO pg_job_run: it reads the panel, not the
+ *  bins, and a later run does not make it stale.  A chain whose index contig has no plan is left out.  The ids are
+ *  checked on the device first as pg_job_record_calls does (PG_ERR_INVALID), a path allele outside a record's map is
+ *  PG_ERR_INVALID, a chain of more than 64 paths PG_ERR_UNSUPPORTED (the host route is the caller's then), the
+ *  buffer outside the arena PG_ERR_NOMEM.  The text is stale after a new plan and after pg_job_upload of a new index
+ *  (a new panel): the fetches and device pointers then answer PG_ERR_INVALID, as for an n_bytes that is not the
+ *  buffer's.  The fetches are those of pg_job_record_text: per chain (offsets from 0), packed (absolute offsets, all
+ *  chains from one copy), device pointers; pg_job_panel_text_first: record_first and / or text_first [n_chains + 1].
+ * ------------------------------------------------------------------ */
+uint64_t pg_panel_text_bound(uint64_t n_records, uint64_t n_paths);
+int  pg_job_panel_text(pg_job* job, char* err, size_t errlen);
+int  pg_job_panel_text_first(pg_job* job, uint64_t* record_first, uint64_t* text_first, char* err, size_t errlen);
+int  pg_job_fetch_panel_text(pg_job* job, uint32_t chain, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen);
+int  pg_job_fetch_panel_text_packed(pg_job* job, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen);
+int  pg_job_device_panel_text(pg_job* job, uint32_t chain, void** d_off, void** d_text, uint64_t* n_records, uint64_t* n_bytes);
+double pg_job_panel_text_ms(const pg_job* job);
+/* uk[n_records], n_records = record_first[n_chains]: the UK of every record's line (below), all chains from one copy */
+int  pg_job_fetch_panel_uk_packed(pg_job* job, uint16_t* uk, uint64_t n_records, char* err, size_t errlen);
+/* Whole lines of the sampled-panel VCF: a third family of prefixes (CHROM .. INFO, `GT`, no trailing tab), joined
+ * from the panel text by the kernels of pg_job_record_lines.  Each call is its record-lines sibling over this family.
+ * The UK a SLOTTED prefix prints is the panel's own count of the record's bubble, kmer_off[v + 1] - kmer_off[v]
+ * (UniqueKmers::size(), what SampledPanel::unique_kmers holds, in 16 bits), which pg_job_panel_text keeps per record
+ * — not pg_job_fetch's rule, which answers 0 for a chain without a kept column.  The lines are stale when the text
+ * is, after a text formed again and after a new prefix. */
+int  pg_job_panel_line_prefix(pg_job* job, uint32_t index_contig, const uint64_t* off, const char* bytes, char* err, size_t errlen);
+int  pg_job_panel_line_prefix_slotted(pg_job* job, uint32_t index_contig, const uint64_t* off, const char* bytes, const uint32_t* slot, char* err,
+                                      size_t errlen);
+int  pg_job_panel_line_prefix_strided(pg_job* job, uint32_t contig, uint32_t n_contigs, const uint64_t* off, const char* bytes, const uint32_t* slot,
+                                      char* err, size_t errlen);
+int  pg_job_panel_lines(pg_job* job, char* err, size_t errlen);
+int  pg_job_panel_lines_first(pg_job* job, uint64_t* n_index_contigs, uint64_t* line_first, uint64_t* byte_first, char* err, size_t errlen);
+int  pg_job_fetch_panel_lines(pg_job* job, uint32_t index_contig, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen);
+int  pg_job_fetch_panel_lines_packed(pg_job* job, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen);
+int  pg_job_device_panel_lines(pg_job* job, uint32_t index_contig, void** d_off, void** d_text, uint64_t* n_lines, uint64_t* n_bytes);
+double pg_job_panel_lines_ms(const pg_job* job);
+/* Unit entry point, through the same kernels: a plan and path_allele [n_variants x n_paths] in; off[R + 1] and text[cap]
+ * come back.  Everything is checked on the host first — a malformed plan (pg_record_calls_from_bins' checks, 2^31 records
+ * or more), null arrays, n_paths == 0, an allele id outside the map of one of its bubble's records, cap below
+ * pg_panel_text_bound(R, n_paths): PG_ERR_INVALID; n_paths > 64: PG_ERR_UNSUPPORTED — then PG_ERR_DEVICE without a device:
+ * no host fallback.  A plan without variants: PG_OK with off[0] = 0. */
+int  pg_panel_text_from_paths(int device, const pg_record_plan* plan, uint32_t n_paths, const uint16_t* path_allele, uint64_t* off, char* text,
+                              uint64_t cap);
+
+/* ------------------------------------------------------------------ *
  *  Path subsets: the chains of one contig over different path selections combined on the device, and the calls
  *  from the sums (pangenie_amd/csrc/pg_combine.hip).  The reference's `-a` option genotypes a
  *  chromosome once per subset of paths, adds the subsets' UNNORMALISED likelihoods per genotype

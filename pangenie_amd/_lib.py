@@ -380,6 +380,38 @@ def _bind_hip(lib):
     lib.pg_record_phase_from_haplotypes.restype = C.c_int
     lib.pg_phase_text_from_fields.argtypes = [C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     lib.pg_phase_text_from_fields.restype = C.c_int
+    # the sample columns of the sampled-panel VCF (pangenie_amd/calls.py)
+    lib.pg_panel_text_bound.argtypes = [C.c_uint64, C.c_uint64]
+    lib.pg_panel_text_bound.restype = C.c_uint64
+    for name in ("pg_job_panel_text", "pg_job_panel_lines"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+        getattr(lib, name).restype = C.c_int
+    lib.pg_job_panel_text_first.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_panel_text_first.restype = C.c_int
+    for name in ("pg_job_fetch_panel_text", "pg_job_fetch_panel_lines"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+        getattr(lib, name).restype = C.c_int
+    for name in ("pg_job_fetch_panel_text_packed", "pg_job_fetch_panel_lines_packed"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+        getattr(lib, name).restype = C.c_int
+    for name in ("pg_job_device_panel_text", "pg_job_device_panel_lines"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), u64p, u64p]
+        getattr(lib, name).restype = C.c_int
+    lib.pg_job_panel_line_prefix.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_panel_line_prefix.restype = C.c_int
+    lib.pg_job_panel_line_prefix_slotted.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_panel_line_prefix_slotted.restype = C.c_int
+    lib.pg_job_panel_line_prefix_strided.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_panel_line_prefix_strided.restype = C.c_int
+    lib.pg_job_panel_lines_first.argtypes = [C.c_void_p, u64p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.pg_job_panel_lines_first.restype = C.c_int
+    lib.pg_job_fetch_panel_uk_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+    lib.pg_job_fetch_panel_uk_packed.restype = C.c_int
+    for name in ("pg_job_panel_text_ms", "pg_job_panel_lines_ms"):
+        getattr(lib, name).argtypes = [C.c_void_p]
+        getattr(lib, name).restype = C.c_double
+    lib.pg_panel_text_from_paths.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    lib.pg_panel_text_from_paths.restype = C.c_int
     # path subsets combined on the device (pangenie_amd/calls.py); bins are read as numpy arrays of COMBINED_DTYPE
     lib.pg_job_combine_plan.argtypes = [C.c_void_p, C.c_uint32, u32p, u32p, C.c_char_p, C.c_size_t]
     lib.pg_job_combine_plan.restype = C.c_int
@@ -464,6 +496,10 @@ HIP_ABI_SYMBOLS = [
     "pg_job_device_phased_text", "pg_job_phased_text_ms",
     "pg_job_phased_line_prefix", "pg_job_phased_lines", "pg_job_phased_lines_first", "pg_job_fetch_phased_lines", "pg_job_fetch_phased_lines_packed",
     "pg_job_device_phased_lines", "pg_job_phased_lines_ms", "pg_record_phase_from_haplotypes", "pg_phase_text_from_fields",
+    "pg_panel_text_bound", "pg_job_panel_text", "pg_job_panel_text_first", "pg_job_fetch_panel_text", "pg_job_fetch_panel_text_packed",
+    "pg_job_device_panel_text", "pg_job_panel_text_ms", "pg_job_fetch_panel_uk_packed", "pg_job_panel_line_prefix", "pg_job_panel_line_prefix_slotted",
+    "pg_job_panel_line_prefix_strided", "pg_job_panel_lines", "pg_job_panel_lines_first", "pg_job_fetch_panel_lines",
+    "pg_job_fetch_panel_lines_packed", "pg_job_device_panel_lines", "pg_job_panel_lines_ms", "pg_panel_text_from_paths",
 ]
 
 

@@ -13,7 +13,8 @@ HIP_LIB = CSRC / "libpangenie_hmm.so"
 HIP_SOURCES = [CSRC / "pg_kernels.hip", CSRC / "pg_shim.cpp", CSRC / "pg_shim_run.cpp", CSRC / "pg_shim_calls.cpp", CSRC / "pg_gather.cpp",
                CSRC / "pg_sampler.hip", CSRC / "pg_viterbi.hip", CSRC / "pg_kmers.hip", CSRC / "pg_calls.hip", CSRC / "pg_combine.hip", CSRC / "pg_shim_combine.cpp",
                CSRC / "pg_combine_records.hip", CSRC / "pg_record_text.hip", CSRC / "pg_record_lines.hip",
-               CSRC / "pg_shim_lines.cpp", CSRC / "pg_phase_text.hip", CSRC / "pg_shim_phase.cpp"]
+               CSRC / "pg_shim_lines.cpp", CSRC / "pg_phase_text.hip", CSRC / "pg_shim_phase.cpp",
+               CSRC / "pg_panel_text.hip", CSRC / "pg_shim_panel.cpp"]
 # every header is a dependency of the library: a new one is picked up without anyone listing it
 HIP_DEPS = HIP_SOURCES + sorted(CSRC.glob("*.h")) + sorted((ROOT / "include").glob("*.h"))
 

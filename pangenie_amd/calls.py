@@ -833,6 +833,179 @@ def phase_text_from_fields(phase, kc, no_call=None, device: int = 0):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+#  The sample columns of the sampled-panel VCF (pg_job_panel_text, pg_job_panel_lines and the unit entry point;
+#  DESIGN.md 4e-10).  No run is needed: the text is formed from the panel the job holds.
+# ---------------------------------------------------------------------------------------------------------------
+PG_PANEL_MAX_PATHS = 64   # the device's limit: above it PG_ERR_UNSUPPORTED and the host route
+
+
+def panel_text_bound(n_records: int, n_paths: int) -> int:
+    """pg_panel_text_bound: R (4 P - 1) for P >= 1 (a cell is at most `255`, a tab in front of every cell but the first)."""
+    return int(_lib.load_hip().pg_panel_text_bound(int(n_records), int(n_paths)))
+
+
+def form_panel_text(job) -> None:
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_panel_text(job.h, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+
+
+def panel_text_first(job):
+    """pg_job_panel_text_first: (record_first, text_first), each [n_chains + 1]."""
+    rf, tf = np.zeros(job.n_chains + 1, np.uint64), np.zeros(job.n_chains + 1, np.uint64)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_panel_text_first(job.h, rf.ctypes.data, tf.ctypes.data, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return rf, tf
+
+
+def fetch_panel_text(job, contig: int):
+    """pg_job_fetch_panel_text: (off [R + 1], bytes) of chain `contig`; record r's text is bytes[off[r]:off[r + 1]]."""
+    rf, tf = panel_text_first(job)
+    n = int(tf[contig + 1] - tf[contig])
+    off = np.zeros(int(rf[contig + 1] - rf[contig]) + 1, np.uint64)
+    text = np.zeros(max(n, 1), np.uint8)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_panel_text(job.h, contig, off.ctypes.data, text.ctypes.data, n, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return off, text[:n].tobytes()
+
+
+def fetch_panel_text_packed(job):
+    """pg_job_fetch_panel_text_packed: (off [R_total + 1] absolute in the packed text, bytes, record_first, text_first)."""
+    rf, tf = panel_text_first(job)
+    n = int(tf[-1])
+    off = np.zeros(int(rf[-1]) + 1, np.uint64)
+    text = np.zeros(max(n, 1), np.uint8)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_panel_text_packed(job.h, off.ctypes.data, text.ctypes.data, n, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return off, text[:n].tobytes(), rf, tf
+
+
+def fetch_panel_uk_packed(job) -> np.ndarray:
+    """pg_job_fetch_panel_uk_packed: the UK of every record's line — the panel's own count of its bubble — all chains' from ONE copy."""
+    rf, _ = panel_text_first(job)
+    uk = np.zeros(max(int(rf[-1]), 1), np.uint16)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_panel_uk_packed(job.h, uk.ctypes.data, int(rf[-1]), err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return uk[:int(rf[-1])]
+
+
+def job_panel_text(job, contig: Optional[int] = None):
+    """Job.panel_text(): forms the text of every chain that has a plan; (off, bytes) of chain `contig`, or of every chain."""
+    form_panel_text(job)
+    if contig is not None:
+        return fetch_panel_text(job, contig)
+    return [fetch_panel_text(job, c) for c in range(job.n_chains)]
+
+
+def job_panel_line_prefix(job, contig: int, off, data, slot=None) -> None:
+    """pg_job_panel_line_prefix[_slotted]: the fixed columns (CHROM .. INFO, GT) of index contig `contig` for the panel lines;
+    with slot [R], the digits of the panel's own UK go in front of byte slot[r] of record r's."""
+    oo, bb, ss = _prefix_arrays(job, "panel_line_prefix", contig, off, data, slot)
+    err = C.create_string_buffer(_ERRLEN)
+    po, pb = oo.ctypes.data if len(oo) else None, bb.ctypes.data if len(bb) else None
+    if ss is None:
+        rc = job._lib.pg_job_panel_line_prefix(job.h, contig, po, pb, err, _ERRLEN)
+    else:
+        rc = job._lib.pg_job_panel_line_prefix_slotted(job.h, contig, po, pb, ss.ctypes.data, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+
+
+def job_panel_line_prefix_strided(job, contig: int, n_contigs: int, off, data, slot=None) -> None:
+    """pg_job_panel_line_prefix_strided: ONE prefix for every index contig ix with ix % n_contigs == contig."""
+    oo, bb, ss = _prefix_arrays(job, "panel_line_prefix_strided", contig, off, data, slot)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_panel_line_prefix_strided(job.h, contig, n_contigs, oo.ctypes.data if len(oo) else None, bb.ctypes.data if len(bb) else None,
+                                                   None if ss is None else ss.ctypes.data, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+
+
+def form_panel_lines(job) -> None:
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_panel_lines(job.h, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+
+
+def panel_lines_first(job):
+    """pg_job_panel_lines_first: (line_first, byte_first), each [n_index_contigs + 1]."""
+    n = C.c_uint64(0)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_panel_lines_first(job.h, C.byref(n), None, None, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    lf, bf = np.zeros(n.value + 1, np.uint64), np.zeros(n.value + 1, np.uint64)
+    rc = job._lib.pg_job_panel_lines_first(job.h, C.byref(n), lf.ctypes.data, bf.ctypes.data, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return lf, bf
+
+
+def fetch_panel_lines(job, contig: int):
+    """pg_job_fetch_panel_lines: (off [R + 1], bytes) of index contig `contig`; line r is bytes[off[r]:off[r + 1]]."""
+    lf, bf = panel_lines_first(job)
+    n = int(bf[contig + 1] - bf[contig])
+    off = np.zeros(int(lf[contig + 1] - lf[contig]) + 1, np.uint64)
+    text = np.zeros(max(n, 1), np.uint8)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_panel_lines(job.h, contig, off.ctypes.data, text.ctypes.data, n, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return off, text[:n].tobytes()
+
+
+def fetch_panel_lines_packed(job):
+    """pg_job_fetch_panel_lines_packed: (off [n_lines + 1] absolute, bytes, line_first, byte_first) from ONE copy."""
+    lf, bf = panel_lines_first(job)
+    n = int(bf[-1])
+    off = np.zeros(int(lf[-1]) + 1, np.uint64)
+    text = np.zeros(max(n, 1), np.uint8)
+    err = C.create_string_buffer(_ERRLEN)
+    rc = job._lib.pg_job_fetch_panel_lines_packed(job.h, off.ctypes.data, text.ctypes.data, n, err, _ERRLEN)
+    if rc:
+        raise _error(rc, err)
+    return off, text[:n].tobytes(), lf, bf
+
+
+def job_panel_lines(job, contig: Optional[int] = None):
+    """Job.panel_lines(): forms the lines from the panel text as it is; (off, bytes) of index contig `contig`, or of all."""
+    form_panel_lines(job)
+    if contig is not None:
+        return fetch_panel_lines(job, contig)
+    return [fetch_panel_lines(job, k) for k in range(len(panel_lines_first(job)[0]) - 1)]
+
+
+def panel_text_from_paths(plan: RecordPlan, n_paths: int, path_allele, device: int = 0):
+    """pg_panel_text_from_paths: (off [R + 1], bytes) — the text of the plan's records from path_allele [V x n_paths] (the
+    allele id of every path at every bubble), through the job's kernels."""
+    lib = _lib.load_hip()
+    pa = np.ascontiguousarray(path_allele, np.uint16).reshape(-1)
+    if len(pa) != plan.n_variants * int(n_paths):
+        raise ValueError("panel_text_from_paths: path_allele does not hold n_variants x n_paths ids")
+    if len(pa) == 0:
+        pa = np.zeros(1, np.uint16)
+    R = plan.n_records
+    cap = panel_text_bound(R, n_paths)
+    off = np.zeros(R + 1, np.uint64)
+    text = np.zeros(max(cap, 1), np.uint8)
+    c = plan.as_c()
+    rc = lib.pg_panel_text_from_paths(device, C.addressof(c), int(n_paths), pa.ctypes.data, off.ctypes.data, text.ctypes.data, cap)
+    if rc:
+        raise _error(rc, None)
+    return off, text[:int(off[-1])].tobytes()
+
+
+# ---------------------------------------------------------------------------------------------------------------
 #  Path subsets combined on the device (pg_job_combine_plan, pg_job_combine, pg_job_combined_calls, pg_combine_bins,
 #  pg_calls_from_combined; DESIGN.md 4e-4)
 # ---------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // pg_job.h — what the host units of the C-ABI shim share (pg_shim.cpp: jobs, their build and uploads; pg_shim_run.cpp: the
-// run schedule, pg_job_run; pg_shim_calls.cpp: the output columns formed from a job's finished bins; pg_shim_lines.cpp: whole VCF lines joined from the record text or the phased text; pg_shim_phase.cpp: the phasing column; pg_shim_combine.cpp: path subsets combined): the error helpers, the
+// run schedule, pg_job_run; pg_shim_calls.cpp: the output columns formed from a job's finished bins; pg_shim_lines.cpp: whole VCF lines joined from the record text or the phased text; pg_shim_phase.cpp: the phasing column; pg_shim_panel.cpp: the sampled panel's columns; pg_shim_combine.cpp: path subsets combined): the error helpers, the
 // host's picture of a job's index contigs, chains and record plans, struct pg_job itself, and the few helpers upload and run
 // both need.  Private: nothing here is exported.
 #pragma once
@@ -190,6 +190,7 @@ struct RecordTextFamily : OutputFamily {
     std::vector<uint64_t> text_first;         // [n_chains + 1] first byte of every chain (after a forming)
     std::vector<RTextDesc> desc;              // host copy (chains with records)
     size_t o_off = 0, o_loc = 0, o_wlen = 0, o_bsum = 0, o_bbase = 0;
+    size_t o_uk = 0;                          // the panel text alone: [n_records] 16-bit UK of every record, for slotted lines over it (0: none)
     uint64_t n_records = 0, cap = 0;
     uint64_t serial = 0;                      // counts the finished formings: the record lines remember which text they joined
     hipEvent_t ev_emit[2];
@@ -449,6 +450,13 @@ struct pg_job {
     pgj::RecordTextFamily ptext;
     std::vector<PTextDesc> ptext_desc;
     pgj::RecordLinesFamily plines;
+    // The sample columns of the sampled-panel VCF (pg_shim_panel.cpp), under the same plans: the bytes of
+    // every record's P cells from the chain's reduced panel (pg_job_panel_text: a RecordTextFamily that no run makes stale —
+    // it reads the panel, not the bins) and whole lines over `GT` prefixes of their own (pg_job_panel_lines), whose UK is
+    // the panel's own count, kept per record next to the text.
+    pgj::RecordTextFamily paneltext;
+    std::vector<PanelDesc> panel_desc;
+    pgj::RecordLinesFamily panellines;
     // Path subsets combined on the device (pg_job_combine_plan / pg_job_combine / pg_job_combined_calls).
     pgj::CombineState combine;
     uint64_t combine_serial = 0;              // counts the finished pg_job_combine calls
@@ -465,26 +473,30 @@ inline void record_plans_changed(pg_job* job) {
     job->rtext.dirty = true;          // (its descriptors point into the two buffers above)
     job->rphase.dirty = true;         // (the phasing column: its descriptors hold the plans' device arrays)
     job->ptext.dirty = true;
+    job->paneltext.dirty = true;      // (the panel text: the plans' arrays, and with a new index a new panel)
     job->rplan_ids_ok = false;
     job->combine.layout_ok = false;   // (the members' layouts are compared again before the next combine)
     job->crec.dirty = true;           // (the records of the combined groups: rebuilt, the ids checked again)
 }
 
-// The two text families of a job and the lines joined from each.  What the fetches of a text (pg_shim_calls.cpp) and the
+// The three text families of a job and the lines joined from each.  What the fetches of a text (pg_shim_calls.cpp) and the
 // whole of the lines (pg_shim_lines.cpp) do is written once and told the family by one of these rows; the formers differ.
 struct TextKind {
     RecordTextFamily pg_job::*text;
     const char* former;   // the entry point that forms it, as the messages name it
+    bool per_run;         // formed from a run's results: stale after the next run, nothing without one (the panel text is neither)
 };
 struct LinesKind {
     TextKind text;
     RecordLinesFamily pg_job::*lines;
     const char* former;
 };
-inline const TextKind kRecordText = {&pg_job::rtext, "pg_job_record_text"};
-inline const TextKind kPhasedText = {&pg_job::ptext, "pg_job_phased_text"};
+inline const TextKind kRecordText = {&pg_job::rtext, "pg_job_record_text", true};
+inline const TextKind kPhasedText = {&pg_job::ptext, "pg_job_phased_text", true};
+inline const TextKind kPanelText = {&pg_job::paneltext, "pg_job_panel_text", false};
 inline const LinesKind kRecordLines = {kRecordText, &pg_job::rlines, "pg_job_record_lines"};
 inline const LinesKind kPhasedLines = {kPhasedText, &pg_job::plines, "pg_job_phased_lines"};
+inline const LinesKind kPanelLines = {kPanelText, &pg_job::panellines, "pg_job_panel_lines"};
 // formed for the last run and the plans as they are?  then: every chain's first byte; one chain's bytes and offsets; all
 // chains' from one copy; one chain's device pointers
 int text_family_ready(pg_job* job, const TextKind& k, char* err, size_t errlen);

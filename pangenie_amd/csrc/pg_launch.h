@@ -1,4 +1,4 @@
-// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp, pg_shim_run.cpp, pg_shim_calls.cpp, pg_shim_phase.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip, pg_calls.hip, pg_combine.hip, pg_combine_records.hip, pg_record_text.hip, pg_record_lines.hip, pg_phase_text.hip).
+// pg_launch.h — the launch seam between the C-ABI shim (pg_shim.cpp, pg_shim_run.cpp, pg_shim_calls.cpp, pg_shim_phase.cpp, pg_shim_panel.cpp) and the kernels (pg_kernels.hip, pg_viterbi.hip, pg_calls.hip, pg_combine.hip, pg_combine_records.hip, pg_record_text.hip, pg_record_lines.hip, pg_phase_text.hip, pg_panel_text.hip).
 //
 // The ONE declaration of every host-callable launcher and of the two launch masks a job hands them.  Both sides include
 // it: a launcher whose parameter list changes on one side only no longer compiles (C linkage: the linker would not notice).
@@ -180,7 +180,29 @@ struct PTextDesc {
     const uint8_t* no_call;
 };
 
+// Panel text (pg_panel_text.hip): one descriptor per chain (or per call of the unit entry point) that has
+// records, in chain order.  Blocks [blk0, next blk0) take pgk_ptpanel_block() CELLS of the chain each, cell r P + p = path p
+// of record r; rec0 = the chain's first record among all records of the launch (the offsets and the packed text are the
+// launch's).  path_allele [V x P] = the chain's reduced panel.  With kmer_off (a job's chain): uk [R] takes the panel's own
+// count of every record's bubble (RLinesDesc::uk of the lines over this text); without (the unit entry point): no UK.
+struct PanelDesc {
+    uint32_t blk0, R;
+    uint64_t rec0;
+    uint32_t chain, P;
+    const uint16_t* path_allele;
+    const uint32_t* kmer_off;
+    uint16_t* uk;
+    RecPlanDev plan;
+};
+
 extern "C" {
+// pg_panel_text.hip: d_bsum [n_blocks], d_bbase [n_blocks + 1]: the scan's; d_off [n_records + 1] = every record's first byte
+// in d_text (`cap` bytes of room), the total behind the last; *d_bad (4 bytes, 0 going in) = 1 if a path's allele id lies
+// outside a record's map (the cell is then printed `.`)
+void pgk_launch_ptpanel(const PanelDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, uint32_t* d_bsum, uint64_t* d_bbase, uint64_t* d_off, uint64_t n_records,
+                        char* d_text, uint64_t cap, uint32_t* d_bad, hipStream_t s);
+uint32_t pgk_ptpanel_block(void);
+uint32_t pgk_ptpanel_stage_bytes(void);
 // pg_phase_text.hip: k_rphase over the descriptors' records
 void pgk_launch_rphase(const DevContig* d_contigs, const RPhaseDesc* d_desc, uint32_t n_desc, uint32_t n_blocks, hipStream_t s);
 // ... and the packed text: d_loc [n_records], d_bsum [n_blocks], d_bbase [n_blocks + 1]: the scan's; d_off [n_records + 1] =

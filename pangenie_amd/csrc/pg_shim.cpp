@@ -338,6 +338,8 @@ extern "C" void pg_job_destroy(pg_job* job) {
     job->rphase.release();
     job->ptext.release();
     job->plines.release();
+    job->paneltext.release();
+    job->panellines.release();
     job->combine.release();
     job->crec.release();
     job->rplans.clear();
@@ -468,7 +470,7 @@ int upload_inputs(pg_job* job, const pg_contig_batch* batches, const std::vector
     } while (0)
     if (with_index) {
         record_plans_changed(job);   // (new allele ids: the record plans are checked against them again)
-        for (size_t i = 0; i < job->index.size(); ++i) { job->rlines.drop_prefix(i); job->plines.drop_prefix(i); }   // (a new index: its lines' fixed columns are the caller's to send again)
+        for (size_t i = 0; i < job->index.size(); ++i) { job->rlines.drop_prefix(i); job->plines.drop_prefix(i); job->panellines.drop_prefix(i); }   // (a new index: its lines' fixed columns are the caller's to send again)
         job->prep_parts_ready = false;   // (a new column list: the extents of a preparation in parts are read again)
         for (size_t i = 0; i < job->index.size(); ++i) {
             const pg_contig_batch& b = batches[i];

@@ -550,6 +550,7 @@ extern "C" int pg_job_record_plan(pg_job* job, uint32_t ix, const pg_record_plan
     job->rplans[ix] = std::move(ref);   // (this index contig's reference alone: the members of a stride keep theirs)
     job->rlines.drop_prefix(ix);        // (the prefix of the lines had the old plan's records)
     job->plines.drop_prefix(ix);
+    job->panellines.drop_prefix(ix);
     record_plans_changed(job);
     return PG_OK;
 }
@@ -571,7 +572,7 @@ extern "C" int pg_job_record_plan_strided(pg_job* job, uint32_t contig, uint32_t
     RecordPlanRef ref;
     rc = record_plan_to_device(job, std::move(h), &ref, err, errlen);
     if (rc != PG_OK) return rc;
-    for (size_t ix = contig; ix < job->index.size(); ix += n_contigs) { job->rplans[ix] = ref; job->rlines.drop_prefix(ix); job->plines.drop_prefix(ix); }
+    for (size_t ix = contig; ix < job->index.size(); ix += n_contigs) { job->rplans[ix] = ref; job->rlines.drop_prefix(ix); job->plines.drop_prefix(ix); job->panellines.drop_prefix(ix); }
     record_plans_changed(job);
     return PG_OK;
 }
@@ -934,9 +935,9 @@ extern "C" double pg_job_record_text_emit_ms(const pg_job* job) { return job ? j
 
 int pgj::text_family_ready(pg_job* job, const TextKind& k, char* err, size_t errlen) {
     if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
-    if (!job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
+    if (k.per_run && !job->ran) { set_err(err, errlen, "pg_job_run has not been called"); return PG_ERR_INVALID; }
     const RecordTextFamily& f = job->*k.text;
-    if (!f.formed || f.dirty || f.run != job->run_serial) { set_err(err, errlen, "%s has not been called for this run and these plans", k.former); return PG_ERR_INVALID; }
+    if (!f.formed || f.dirty || (k.per_run && f.run != job->run_serial)) { set_err(err, errlen, "%s has not been called for this run and these plans", k.former); return PG_ERR_INVALID; }
     return PG_OK;
 }
 

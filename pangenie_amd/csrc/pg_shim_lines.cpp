@@ -1,7 +1,8 @@
 // pg_shim_lines.cpp — the C-ABI of the record lines (pg_record_lines.hip):
 // the prefix of an index contig or of a stride of them, plain or slotted, the forming of whole VCF lines from a job's record
-// text, their fetches, and the unit entry points over host arrays.  A job has two such families — the lines of the record
-// text (GT:GQ:GL:KC) and those of the phased text (GT:KC), each with prefixes of its own — and ONE
+// text, their fetches, and the unit entry points over host arrays.  A job has three such families — the lines of the record
+// text (GT:GQ:GL:KC), those of the phased text (GT:KC) and those of the panel text (GT, one column per
+// selected path), each with prefixes of its own — and ONE
 // implementation: every function below the unit entry points' takes the family as a LinesKind row (pg_job.h).  Host code
 // off the critical path.
 #include <hip/hip_runtime_api.h>
@@ -58,7 +59,7 @@ void rlines_launch(unsigned char* d, const RLinesLayout& L, bool slotted, const 
 
 bool text_current(const pg_job* job, const LinesKind& k) {
     const RecordTextFamily& t = job->*k.text.text;
-    return job->ran && t.formed && !t.dirty && t.run == job->run_serial;
+    return t.formed && !t.dirty && (!k.text.per_run || (job->ran && t.run == job->run_serial));
 }
 
 int rlines_ready(pg_job* job, const LinesKind& k, char* err, size_t errlen) {
@@ -175,8 +176,11 @@ extern "C" int pg_job_phased_line_prefix(pg_job* job, uint32_t ix, const uint64_
     return line_prefix(job, kPhasedLines, ix, off, bytes, nullptr, err, errlen);
 }
 
-extern "C" int pg_job_line_prefix_strided(pg_job* job, uint32_t contig, uint32_t n_contigs, const uint64_t* off, const char* bytes, const uint32_t* slot,
-                                          char* err, size_t errlen) {
+namespace {
+
+// one prefix for every member of a stride of index contigs
+int line_prefix_strided(pg_job* job, const LinesKind& k, uint32_t contig, uint32_t n_contigs, const uint64_t* off, const char* bytes, const uint32_t* slot,
+                        char* err, size_t errlen) {
     if (!job) { set_err(err, errlen, "null job"); return PG_ERR_INVALID; }
     if (n_contigs == 0 || contig >= n_contigs) { set_err(err, errlen, "contig %u of %u", contig, n_contigs); return PG_ERR_INVALID; }
     if (job->index.size() % n_contigs != 0) { set_err(err, errlen, "the job's %zu index contigs are no multiple of %u contigs", job->index.size(), n_contigs); return PG_ERR_INVALID; }
@@ -192,11 +196,30 @@ extern "C" int pg_job_line_prefix_strided(pg_job* job, uint32_t contig, uint32_t
     int rc = check_prefix(R, off, bytes, slot, err, errlen);
     if (rc != PG_OK) return rc;
     LinePrefixRef ref;
-    rc = prefix_to_device(job, kRecordLines, R, off, bytes, slot, &ref, err, errlen);
+    rc = prefix_to_device(job, k, R, off, bytes, slot, &ref, err, errlen);
     if (rc != PG_OK) return rc;
-    for (size_t ix = contig; ix < job->index.size(); ix += n_contigs) job->rlines.prefix[ix] = ref;
-    job->rlines.formed = false;
+    for (size_t ix = contig; ix < job->index.size(); ix += n_contigs) (job->*k.lines).prefix[ix] = ref;
+    (job->*k.lines).formed = false;
     return PG_OK;
+}
+
+}  // namespace
+
+extern "C" int pg_job_line_prefix_strided(pg_job* job, uint32_t contig, uint32_t n_contigs, const uint64_t* off, const char* bytes, const uint32_t* slot,
+                                          char* err, size_t errlen) {
+    return line_prefix_strided(job, kRecordLines, contig, n_contigs, off, bytes, slot, err, errlen);
+}
+
+// the prefixes of the panel lines (CHROM .. INFO, GT): a slotted one takes its UK from the panel text's per-record array
+extern "C" int pg_job_panel_line_prefix(pg_job* job, uint32_t ix, const uint64_t* off, const char* bytes, char* err, size_t errlen) {
+    return line_prefix(job, kPanelLines, ix, off, bytes, nullptr, err, errlen);
+}
+extern "C" int pg_job_panel_line_prefix_slotted(pg_job* job, uint32_t ix, const uint64_t* off, const char* bytes, const uint32_t* slot, char* err, size_t errlen) {
+    return line_prefix(job, kPanelLines, ix, off, bytes, slot, err, errlen);
+}
+extern "C" int pg_job_panel_line_prefix_strided(pg_job* job, uint32_t contig, uint32_t n_contigs, const uint64_t* off, const char* bytes, const uint32_t* slot,
+                                                char* err, size_t errlen) {
+    return line_prefix_strided(job, kPanelLines, contig, n_contigs, off, bytes, slot, err, errlen);
 }
 
 namespace {
@@ -244,8 +267,11 @@ int form_lines(pg_job* job, const LinesKind& k, char* err, size_t errlen) {
         d.prefix = (const char*)(px.d + px.o_bytes);
         if (px.o_slot) {   // UK: the first member's count of the record's bubble
             d.slot = (const uint32_t*)(px.d + px.o_slot);
-            d.rec_var = job->rplans[ix]->dev.rec_var;
-            d.chain = chains_of[ix][0];
+            if (t.o_uk) d.uk = (const uint16_t*)(t.d + t.o_uk) + t.first[chains_of[ix][0]];   // (the panel text keeps it per record)
+            else {
+                d.rec_var = job->rplans[ix]->dev.rec_var;
+                d.chain = chains_of[ix][0];
+            }
         }
         contig_of.push_back(ix);
         cap += px.o_slot ? pg_record_lines_bound_slotted(R, S, px.bytes, text_bytes) : pg_record_lines_bound(R, S, px.bytes, text_bytes);
@@ -366,6 +392,22 @@ extern "C" int pg_job_fetch_phased_lines_packed(pg_job* job, uint64_t* off, char
 }
 extern "C" int pg_job_device_phased_lines(pg_job* job, uint32_t ix, void** d_off, void** d_text, uint64_t* n_lines, uint64_t* n_bytes) {
     return device_lines(job, kPhasedLines, ix, d_off, d_text, n_lines, n_bytes);
+}
+
+// the lines of the panel text: the same joiner over the family's own prefixes
+extern "C" int pg_job_panel_lines(pg_job* job, char* err, size_t errlen) { return form_lines(job, kPanelLines, err, errlen); }
+extern "C" double pg_job_panel_lines_ms(const pg_job* job) { return job ? job->panellines.ms : 0.0; }
+extern "C" int pg_job_panel_lines_first(pg_job* job, uint64_t* n_index_contigs, uint64_t* line_first, uint64_t* byte_first, char* err, size_t errlen) {
+    return lines_first(job, kPanelLines, n_index_contigs, line_first, byte_first, err, errlen);
+}
+extern "C" int pg_job_fetch_panel_lines(pg_job* job, uint32_t ix, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
+    return fetch_lines(job, kPanelLines, ix, off, text, n_bytes, err, errlen);
+}
+extern "C" int pg_job_fetch_panel_lines_packed(pg_job* job, uint64_t* off, char* text, uint64_t n_bytes, char* err, size_t errlen) {
+    return fetch_lines_packed(job, kPanelLines, off, text, n_bytes, err, errlen);
+}
+extern "C" int pg_job_device_panel_lines(pg_job* job, uint32_t ix, void** d_off, void** d_text, uint64_t* n_lines, uint64_t* n_bytes) {
+    return device_lines(job, kPanelLines, ix, d_off, d_text, n_lines, n_bytes);
 }
 
 namespace {

@@ -544,6 +544,52 @@ class Job:
         """elapsed ms of the kernels of the last phased_lines()"""
         return float(self._lib.pg_job_phased_lines_ms(self.h))
 
+    def panel_text(self, contig: Optional[int] = None):
+        """pg_job_panel_text + pg_job_fetch_panel_text: the sample columns of the sampled-panel VCF per VCF RECORD — one cell
+        per path of the chain's panel, joined by tabs — formed on the device from the panel the job holds (DESIGN.md 4e-10);
+        needs a record plan, no run().  (off [R + 1], bytes) per chain, or chain `contig`'s."""
+        from . import calls as _calls
+        return _calls.job_panel_text(self, contig)
+
+    def panel_text_packed(self):
+        """pg_job_panel_text + pg_job_fetch_panel_text_packed: (off [R_total + 1] absolute, all chains' bytes from ONE copy,
+        record_first, text_first [n_chains + 1])."""
+        from . import calls as _calls
+        _calls.form_panel_text(self)
+        return _calls.fetch_panel_text_packed(self)
+
+    def panel_text_ms(self) -> float:
+        """elapsed ms of the kernels of the last panel_text()"""
+        return float(self._lib.pg_job_panel_text_ms(self.h))
+
+    def panel_line_prefix(self, contig: int, off, data, slot=None) -> None:
+        """pg_job_panel_line_prefix[_slotted]: the fixed columns (CHROM .. INFO, GT, no trailing tab) of the records of INDEX
+        contig `contig` for the panel lines; with slot [R] the panel's own UK is printed in front of byte slot[r]."""
+        from . import calls as _calls
+        _calls.job_panel_line_prefix(self, contig, off, data, slot)
+
+    def panel_line_prefix_strided(self, contig: int, n_contigs: int, off, data, slot=None) -> None:
+        """pg_job_panel_line_prefix_strided: ONE prefix for every index contig ix with ix % n_contigs == contig."""
+        from . import calls as _calls
+        _calls.job_panel_line_prefix_strided(self, contig, n_contigs, off, data, slot)
+
+    def panel_lines(self, contig: Optional[int] = None):
+        """pg_job_panel_lines + pg_job_fetch_panel_lines: whole lines of the sampled-panel VCF joined on the device from the
+        text of the last panel_text().  (off, bytes) of index contig `contig`, or of all."""
+        from . import calls as _calls
+        return _calls.job_panel_lines(self, contig)
+
+    def panel_lines_packed(self):
+        """pg_job_panel_lines + pg_job_fetch_panel_lines_packed: (off [n_lines + 1] absolute, all bytes from ONE copy,
+        line_first, byte_first [n_index_contigs + 1])."""
+        from . import calls as _calls
+        _calls.form_panel_lines(self)
+        return _calls.fetch_panel_lines_packed(self)
+
+    def panel_lines_ms(self) -> float:
+        """elapsed ms of the kernels of the last panel_lines()"""
+        return float(self._lib.pg_job_panel_lines_ms(self.h))
+
     def combine_plan(self, groups) -> None:
         """pg_job_combine_plan: groups = per group the chains (contig x path subset) that genotype the same index objects, in the
         order they are to be added up; a second plan replaces the first."""

@@ -1411,6 +1411,160 @@ int sampled_job_record_lines(pg_job* job, size_t n, const std::vector<Chromosome
     return rc;
 }
 
+// ---- the sampled-panel VCF: tails of the same shape; they need no run and no picks
+
+// The host route of one chain: its reduced panel's kmer_off and path_allele back from the device, SampledPanels from them,
+// Graph::sampled_panel_records.  Per record the whole line; uk (may be null) = the panel's count per bubble.
+int panel_chain_on_host(pg_job* job, uint32_t chain, const Chromosome& x, std::vector<std::string>* lines, std::vector<unsigned short>* uk, char* err,
+                        size_t errlen) {
+    const size_t V = x.flat.variant_pos.size();
+    uint32_t nv = 0, np = 0;
+    int rc = pg_job_panel_sizes(job, chain, &nv, &np, nullptr, nullptr);
+    if (rc != PG_OK || nv != V) { std::snprintf(err, errlen, "sample_cohort_panel_text: pg_job_panel_sizes failed for chain %u", chain); return rc != PG_OK ? rc : PG_ERR_INVALID; }
+    std::vector<uint32_t> koff(V + 1, 0);
+    std::vector<uint16_t> pa(V * np, 0);
+    if (V) rc = pg_job_fetch_panel(job, chain, koff.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pa.data(), err, errlen);
+    if (rc != PG_OK) return rc;
+    std::vector<SampledPanel> panels(V);
+    for (size_t v = 0; v < V; ++v) {
+        panels[v].path_to_allele.assign(pa.begin() + v * np, pa.begin() + (v + 1) * np);
+        panels[v].unique_kmers = (unsigned short)(koff[v + 1] - koff[v]);
+    }
+    *lines = x.graph->sampled_panel_records(panels);
+    if (uk) {
+        uk->resize(V);
+        for (size_t v = 0; v < V; ++v) (*uk)[v] = (unsigned short)panels[v].unique_kmers;
+    }
+    return PG_OK;
+}
+
+// One strided plan per chromosome that takes the device route, and the text formed.  A chromosome whose graph has a REF of
+// undefined sequence gets no plan (the plan calls REF defined, the host prints `.` for a haplotype on it); a panel of more
+// paths than the device forms sends every chromosome down the host route.  host[c]: chromosome c is the host's.
+int sampled_job_panel_begin(pg_job* job, const std::vector<Chromosome>& chroms, std::vector<char>* host, char* err, size_t errlen) {
+    const size_t C = chroms.size();
+    host->assign(C, 0);
+    int rc = PG_OK;
+    for (size_t c = 0; c < C && rc == PG_OK; ++c) {
+        if (chroms[c].graph->has_undefined_reference_allele()) { (*host)[c] = 1; continue; }
+        const pg_record_plan view = chroms[c].plan.view();
+        rc = pg_job_record_plan_strided(job, (uint32_t)c, (uint32_t)C, &view, err, errlen);
+    }
+    if (rc == PG_OK) rc = pg_job_panel_text(job, err, errlen);
+    if (rc == PG_ERR_UNSUPPORTED) {   // (more than 64 paths: nothing was formed)
+        host->assign(C, 1);
+        rc = PG_OK;
+    }
+    return rc;
+}
+
+// the haplotype columns as bytes: one packed copy of the text, one of the records' UK, then chain by chain
+int sampled_job_panel_text(pg_job* job, size_t n, const std::vector<Chromosome>& chroms, const CoverageRows*, uint32_t, bool, bool, const Picks&,
+                           std::map<std::string, RecordText>* text, std::map<std::string, SampledPaths>*, char* err, size_t errlen) {
+    const size_t C = chroms.size();
+    std::vector<char> host;
+    int rc = sampled_job_panel_begin(job, chroms, &host, err, errlen);
+    if (rc != PG_OK) return rc;
+    const bool any_device = std::find(host.begin(), host.end(), 0) != host.end();
+    std::vector<uint64_t> rfirst(n * C + 1, 0), tfirst(n * C + 1, 0), off(1, 0);
+    std::vector<uint16_t> uk;
+    std::string packed;
+    if (any_device) {
+        rc = pg_job_panel_text_first(job, rfirst.data(), tfirst.data(), err, errlen);
+        if (rc != PG_OK) return rc;
+        off.assign(rfirst.back() + 1, 0);
+        packed.assign(tfirst.back(), '\0');
+        uk.assign(rfirst.back(), 0);
+        rc = pg_job_fetch_panel_text_packed(job, off.data(), packed.empty() ? nullptr : &packed[0], packed.size(), err, errlen);
+        if (rc == PG_OK) rc = pg_job_fetch_panel_uk_packed(job, uk.empty() ? nullptr : uk.data(), uk.size(), err, errlen);
+    }
+    for (size_t s = 0; s < n && rc == PG_OK; ++s)
+        for (size_t c = 0; c < C && rc == PG_OK; ++c) {
+            const uint32_t chain = (uint32_t)(s * C + c);
+            const Chromosome& x = chroms[c];
+            const size_t V = x.flat.variant_pos.size(), R = x.plan.nr_of_records();
+            RecordText& t = text[s][x.name];
+            t.off.assign(R + 1, 0);
+            if (host[c]) {   // the lines less their fixed columns and the tab behind them
+                std::vector<std::string> lines;
+                rc = panel_chain_on_host(job, chain, x, &lines, &t.unique_kmers, err, errlen);
+                if (rc != PG_OK) break;
+                const std::vector<std::string> fixed = x.graph->sampled_panel_fixed_columns(t.unique_kmers);
+                for (size_t r = 0; r < R; ++r) { t.bytes.append(lines[r], fixed[r].size() + 1, std::string::npos); t.off[r + 1] = t.bytes.size(); }
+                continue;
+            }
+            if (rfirst[chain + 1] - rfirst[chain] != R) {
+                std::snprintf(err, errlen, "sample_cohort_panel_text: chain %u holds other records than its plan's", chain);
+                return PG_ERR_INVALID;
+            }
+            for (size_t r = 0; r <= R; ++r) t.off[r] = off[rfirst[chain] + r] - tfirst[chain];
+            t.bytes.assign(packed, tfirst[chain], tfirst[chain + 1] - tfirst[chain]);
+            t.unique_kmers.resize(V);
+            for (size_t v = 0; v < V; ++v) t.unique_kmers[v] = uk[rfirst[chain] + x.plan.rec_off[v]];   // (every bubble has a record)
+        }
+    return rc;
+}
+
+// whole lines: the text stays on the device, ONE slotted prefix per chromosome is shared by its chains, one launch joins every
+// chain's lines with its panel's own UK, one packed copy brings them
+int sampled_job_panel_lines(pg_job* job, size_t n, const std::vector<Chromosome>& chroms, const CoverageRows*, uint32_t, bool, bool, const Picks&,
+                            std::map<std::string, RecordLines>* lines, std::map<std::string, SampledPaths>*, char* err, size_t errlen) {
+    const size_t C = chroms.size();
+    std::vector<char> host;
+    int rc = sampled_job_panel_begin(job, chroms, &host, err, errlen);
+    if (rc != PG_OK) return rc;
+    const bool any_device = std::find(host.begin(), host.end(), 0) != host.end();
+    for (size_t c = 0; c < C && rc == PG_OK; ++c) {
+        if (host[c]) continue;
+        std::vector<uint32_t> slot;
+        const std::vector<std::string> fixed = chroms[c].graph->sampled_panel_fixed_columns_slotted(&slot);
+        std::vector<uint64_t> poff(fixed.size() + 1, 0);
+        std::string pbytes;
+        for (size_t r = 0; r < fixed.size(); ++r) { pbytes += fixed[r]; poff[r + 1] = pbytes.size(); }
+        slot.push_back(0);   // (never empty: a null pointer means a plain prefix)
+        rc = pg_job_panel_line_prefix_strided(job, (uint32_t)c, (uint32_t)C, poff.data(), pbytes.empty() ? nullptr : pbytes.data(), slot.data(), err, errlen);
+    }
+    std::vector<uint64_t> line_first(n * C + 1, 0), byte_first(n * C + 1, 0), loff(1, 0);
+    std::string lbytes;
+    if (rc == PG_OK && any_device) {
+        rc = pg_job_panel_lines(job, err, errlen);
+        uint64_t n_index = 0;
+        if (rc == PG_OK) rc = pg_job_panel_lines_first(job, &n_index, nullptr, nullptr, err, errlen);
+        if (rc == PG_OK && n_index != n * C) {
+            std::snprintf(err, errlen, "sample_cohort_panel_lines: the job has %llu index contigs, not %zu", (unsigned long long)n_index, n * C);
+            return PG_ERR_INVALID;
+        }
+        if (rc == PG_OK) rc = pg_job_panel_lines_first(job, nullptr, line_first.data(), byte_first.data(), err, errlen);
+        if (rc != PG_OK) return rc;
+        loff.assign(line_first.back() + 1, 0);
+        lbytes.assign(byte_first.back(), '\0');
+        rc = pg_job_fetch_panel_lines_packed(job, loff.data(), lbytes.empty() ? nullptr : &lbytes[0], lbytes.size(), err, errlen);
+    }
+    for (size_t s = 0; s < n && rc == PG_OK; ++s)
+        for (size_t c = 0; c < C && rc == PG_OK; ++c) {
+            const uint32_t chain = (uint32_t)(s * C + c);   // chain id = sample * n_contigs + contig: an index contig of its own
+            const Chromosome& x = chroms[c];
+            const size_t R = x.plan.nr_of_records();
+            RecordLines& out = lines[s][x.name];
+            out.off.assign(R + 1, 0);
+            if (host[c]) {
+                std::vector<std::string> host_lines;
+                rc = panel_chain_on_host(job, chain, x, &host_lines, nullptr, err, errlen);
+                if (rc != PG_OK) break;
+                for (size_t r = 0; r < R; ++r) { out.bytes += host_lines[r]; out.bytes += '\n'; out.off[r + 1] = out.bytes.size(); }
+                continue;
+            }
+            if (line_first[chain + 1] - line_first[chain] == R) {   // (a chromosome without records has no lines on the device)
+                for (size_t r = 0; r <= R; ++r) out.off[r] = loff[line_first[chain] + r] - byte_first[chain];
+                out.bytes.assign(lbytes, byte_first[chain], byte_first[chain + 1] - byte_first[chain]);
+            } else if (R != 0 || line_first[chain + 1] != line_first[chain]) {
+                std::snprintf(err, errlen, "sample_cohort_panel_lines: chain %u holds other lines than its plan's records", chain);
+                return PG_ERR_INVALID;
+            }
+        }
+    return rc;
+}
+
 // One sampled cohort job from the samples' counts on the host (`who`: the caller's name in a refusal), then
 // `tail(job, cov_rows, picks, err, errlen)` on the made job: one of the three tails above; it returns the C ABI's code.
 template <class Tail>
@@ -1574,6 +1728,38 @@ std::vector<std::map<std::string, RecordLines>> genotype_cohort_sampled_record_l
     std::vector<std::map<std::string, SampledPaths>>* sampled) {
     return sampled_cohort_records<RecordLines>(chromosomes, graphs, samples, panel_size, add_reference, allele_penalty, sampling_effective_N, probabilities,
                                                recombrate, uniform, effective_N, device, ignore_imputed, sampled, sampled_job_record_lines);
+}
+
+std::vector<std::map<std::string, RecordText>> sample_cohort_panel_text(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device) {
+    return sampled_cohort_records<RecordText>(chromosomes, graphs, samples, panel_size, add_reference, allele_penalty, sampling_effective_N, probabilities,
+                                              recombrate, uniform, effective_N, device, false, nullptr, sampled_job_panel_text);
+}
+
+std::vector<std::map<std::string, RecordLines>> sample_cohort_panel_lines(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device) {
+    return sampled_cohort_records<RecordLines>(chromosomes, graphs, samples, panel_size, add_reference, allele_penalty, sampling_effective_N, probabilities,
+                                               recombrate, uniform, effective_N, device, false, nullptr, sampled_job_panel_lines);
+}
+
+std::vector<std::map<std::string, RecordText>> sample_cohort_reads_panel_text(
+    UniqueKmersMap& index, const std::map<std::string, Graph>& graphs, const std::string& prefix, const std::vector<std::string>& readfiles,
+    const std::vector<size_t>& kmer_coverages, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device, size_t batch) {
+    return sampled_reads_records<RecordText>(index, graphs, prefix, readfiles, kmer_coverages, panel_size, add_reference, allele_penalty, sampling_effective_N,
+                                             probabilities, recombrate, uniform, effective_N, device, batch, false, nullptr, sampled_job_panel_text);
+}
+
+std::vector<std::map<std::string, RecordLines>> sample_cohort_reads_panel_lines(
+    UniqueKmersMap& index, const std::map<std::string, Graph>& graphs, const std::string& prefix, const std::vector<std::string>& readfiles,
+    const std::vector<size_t>& kmer_coverages, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate, bool uniform, long double effective_N, int device, size_t batch) {
+    return sampled_reads_records<RecordLines>(index, graphs, prefix, readfiles, kmer_coverages, panel_size, add_reference, allele_penalty, sampling_effective_N,
+                                              probabilities, recombrate, uniform, effective_N, device, batch, false, nullptr, sampled_job_panel_lines);
 }
 
 // ------------------------------------------------------------------ sampled cohort job fed by the device counter

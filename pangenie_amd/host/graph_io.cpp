@@ -573,17 +573,28 @@ bool Graph::has_undefined_reference_allele() const {
     return false;
 }
 
+std::vector<std::string> Graph::sampled_panel_fixed_columns(const std::vector<unsigned short>& unique_kmers) const {
+    return fixed_columns(unique_kmers, "Graph::write_sampled_panel", "GT");
+}
+
 std::vector<std::string> Graph::genotypes_fixed_columns_slotted(std::vector<uint32_t>* slot) const {
-    const char* who = "Graph::write_genotypes_of";
+    return fixed_columns_slotted(slot, "Graph::write_genotypes_of", "Graph::genotypes_fixed_columns_slotted", "GT:GQ:GL:KC");
+}
+
+std::vector<std::string> Graph::sampled_panel_fixed_columns_slotted(std::vector<uint32_t>* slot) const {
+    return fixed_columns_slotted(slot, "Graph::write_sampled_panel", "Graph::sampled_panel_fixed_columns_slotted", "GT");
+}
+
+std::vector<std::string> Graph::fixed_columns_slotted(std::vector<uint32_t>* slot, const char* who, const char* method, const char* format) const {
     if (variants_deleted_) throw std::runtime_error(std::string(who) + ": variants have been deleted by delete_variant funtion. Re-build object.");
-    if (!slot) throw std::runtime_error("Graph::genotypes_fixed_columns_slotted: nowhere to report the slots");
+    if (!slot) throw std::runtime_error(std::string(method) + ": nowhere to report the slots");
     std::vector<std::string> columns;
     std::vector<unsigned short> defined;
     slot->clear();
     for (size_t i = 0; i < size(); ++i)
         for (const VcfSite& site : get_variant(i).records(nullptr)) {
             size_t at = 0;
-            columns.push_back(fixed_columns_of(site, columns.size(), 0, who, defined, &at) + "\tGT:GQ:GL:KC");
+            columns.push_back(fixed_columns_of(site, columns.size(), 0, who, defined, &at) + '\t' + format);
             slot->push_back((uint32_t)at);
         }
     return columns;
@@ -627,7 +638,7 @@ RecordLines compose_record_lines(const std::vector<std::string>& prefix, const s
 
 std::vector<std::string> Graph::sample_records(const std::vector<GenotypingResult>& genotyping_result, bool ignore_imputed, bool phasing,
                                                const std::vector<SampledPanel>* sampled_paths, const DeviceFields* device) const {
-    const char* who = sampled_paths ? "Graph::write_sampled_panel" : phasing ? "Graph::write_phasing_of" : "Graph::write_genotypes_of";
+    const char* who = sampled_paths || (device && device->panel) ? "Graph::write_sampled_panel" : phasing ? "Graph::write_phasing_of" : "Graph::write_genotypes_of";
     if (variants_deleted_) throw std::runtime_error(std::string(who) + ": variants have been deleted by delete_variant funtion. Re-build object.");
     if ((sampled_paths ? sampled_paths->size() : device ? (device->text ? device->unique_kmers->size() : std::min(device->coverage->size(), device->unique_kmers->size())) : genotyping_result.size()) != size())
         throw std::runtime_error(std::string(who) + ": number of variants and number of computed " + (phasing || sampled_paths ? "phasings" : "genotypes") + " differ.");
@@ -651,7 +662,7 @@ std::vector<std::string> Graph::sample_records(const std::vector<GenotypingResul
                     if (among_defined.at(a) < 0) line << "\t."; else line << '\t' << among_defined[a];
                 }
             }
-            else if (device && device->text) line << (phasing ? "\tGT:KC\t" : "\tGT:GQ:GL:KC\t") << text_field(*device->text, record_index, defined.size(), phasing);
+            else if (device && device->text) line << (device->panel ? "\tGT\t" : phasing ? "\tGT:KC\t" : "\tGT:GQ:GL:KC\t") << text_field(*device->text, record_index, defined.size(), phasing);
             else if (device)
                 line << "\tGT:GQ:GL:KC\t"
                      << device_field(*device->fields, record_index, defined.size(), (*device->coverage)[i], ignore_imputed && (*device->unique_kmers)[i] == 0);
@@ -694,16 +705,17 @@ void Graph::write_genotypes(const std::string& filename, const RecordText& text,
     for (const std::string& l : records) out << l << '\n';
 }
 
-void Graph::write_lines(const std::string& filename, const RecordLines& lines, const std::vector<std::string>* header, bool phasing) const {
-    const char* who = phasing ? "Graph::write_phasing_of" : "Graph::write_genotypes_of";
+void Graph::write_lines(const std::string& filename, const RecordLines& lines, const std::vector<std::string>* header, LinesOf of) const {
+    const bool phasing = of == LinesOf::Phasing, panel = of == LinesOf::SampledPanel;
+    const char* who = panel ? "Graph::write_sampled_panel" : phasing ? "Graph::write_phasing_of" : "Graph::write_genotypes_of";
     const size_t R = nr_of_records();   // (throws before the file is touched)
     if (lines.off.size() != R + 1 || lines.off[0] != 0 || lines.off[R] != lines.bytes.size())
         throw std::runtime_error(std::string(who) + ": the record lines do not fit the graph's records");
     for (size_t r = 0; r < R; ++r)
         if (lines.off[r + 1] <= lines.off[r] || lines.bytes[lines.off[r + 1] - 1] != '\n')
-            throw std::runtime_error(std::string(who) + ": a record's line is empty or unfinished (" + (phasing ? "phase_cohort_record_lines" : "genotype_cohort_record_lines") + " finishes them)");
+            throw std::runtime_error(std::string(who) + ": a record's line is empty or unfinished (" + (panel ? "sample_cohort_panel_lines" : phasing ? "phase_cohort_record_lines" : "genotype_cohort_record_lines") + " finishes them)");
     std::ofstream out(filename, header ? std::ios::out : std::ios::app);
-    if (!out.is_open()) throw std::runtime_error(std::string(who) + ": " + (phasing ? "phasing" : "genotyping") + " output file cannot be opened. Note that the filename must not contain non-existing directories.");
+    if (!out.is_open()) throw std::runtime_error(std::string(who) + ": " + (panel ? "panel" : phasing ? "phasing" : "genotyping") + " output file cannot be opened. Note that the filename must not contain non-existing directories.");
     if (header)
         for (const std::string& h : *header) out << h << '\n';
     out.write(lines.bytes.data(), (std::streamsize)lines.bytes.size());
@@ -711,12 +723,12 @@ void Graph::write_lines(const std::string& filename, const RecordLines& lines, c
 
 void Graph::write_genotypes(const std::string& filename, const RecordLines& lines, bool write_header, const std::vector<std::string>& samples) const {
     const std::vector<std::string> header = genotypes_header(samples);
-    write_lines(filename, lines, write_header ? &header : nullptr, false);
+    write_lines(filename, lines, write_header ? &header : nullptr, LinesOf::Genotypes);
 }
 
 void Graph::write_phasing(const std::string& filename, const RecordLines& lines, bool write_header, const std::vector<std::string>& samples) const {
     const std::vector<std::string> header = phasing_header(samples);
-    write_lines(filename, lines, write_header ? &header : nullptr, true);
+    write_lines(filename, lines, write_header ? &header : nullptr, LinesOf::Phasing);
 }
 
 void Graph::write_genotypes(const std::string& filename, const RecordFields& fields, const std::vector<unsigned short>& coverage,
@@ -753,6 +765,17 @@ void Graph::write_sampled_panel(const std::string& filename, const std::vector<S
     if (write_header)
         for (const std::string& h : sampled_panel_header(sampled_paths.empty() ? 0 : sampled_paths[0].path_to_allele.size())) out << h << '\n';
     for (const std::string& l : records) out << l << '\n';
+}
+
+std::vector<std::string> Graph::sampled_panel_records_of_text(const RecordText& text) const {
+    DeviceFields device = {nullptr, nullptr, &text.unique_kmers, &text};
+    device.panel = true;
+    return sample_records({}, false, true, nullptr, &device);   // (every record has a text, as the phasing column's)
+}
+
+void Graph::write_sampled_panel(const std::string& filename, const RecordLines& lines, bool write_header, size_t nr_paths) const {
+    const std::vector<std::string> header = sampled_panel_header(nr_paths);
+    write_lines(filename, lines, write_header ? &header : nullptr, LinesOf::SampledPanel);
 }
 
 std::vector<std::string> Graph::phasing_header(const std::string& sample, const std::string& date) {

@@ -24,6 +24,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -254,6 +255,21 @@ public:
     static std::vector<std::string> sampled_panel_header(size_t nr_paths, const std::string& date = "");
     std::vector<std::string> sampled_panel_records(const std::vector<SampledPanel>& sampled_paths) const;
     void write_sampled_panel(const std::string& filename, const std::vector<SampledPanel>& sampled_paths, bool write_header) const;
+    /** per record, in sampled_panel_records order, what a panel line holds in front of the haplotype columns:
+     *  `CHROM .. INFO\tGT` without a trailing tab (UK from `unique_kmers`, one entry per bubble: SampledPanel::unique_kmers) */
+    std::vector<std::string> sampled_panel_fixed_columns(const std::vector<unsigned short>& unique_kmers) const;
+    /** the same columns with the digits of UK left out and slot[r] = where they belong, as genotypes_fixed_columns_slotted:
+     *  the slotted prefix of pg_job_panel_line_prefix_strided */
+    std::vector<std::string> sampled_panel_fixed_columns_slotted(std::vector<uint32_t>* slot) const;
+    /** the panel lines with the haplotype columns arriving as bytes (C ABI pg_job_panel_text): the fixed columns as above
+     *  (UK from text.unique_kmers), the columns spliced in.  Throws where a record's text is empty. */
+    std::vector<std::string> sampled_panel_records_of_text(const RecordText& text) const;
+    /** (the same under the siblings' name; a template, so that a braced list still means the SampledPanels) */
+    template <class Text, class = typename std::enable_if<std::is_same<Text, RecordText>::value>::type>
+    std::vector<std::string> sampled_panel_records(const Text& text) const { return sampled_panel_records_of_text(text); }
+    /** header (when asked for) for `nr_paths` haplotype columns, then the lines' bytes in ONE write.  Throws on offsets that
+     *  do not fit the bytes or the graph's records, and on an empty line. */
+    void write_sampled_panel(const std::string& filename, const RecordLines& lines, bool write_header, size_t nr_paths) const;
 
 private:
     struct DeviceFields {   // the sample column from the device's record fields instead of a GenotypingResult per bubble
@@ -261,13 +277,17 @@ private:
         const std::vector<unsigned short>* coverage;
         const std::vector<unsigned short>* unique_kmers;
         const RecordText* text = nullptr;   // the column as bytes: fields and coverage are not looked at
+        bool panel = false;                 // ... the haplotype columns of the sampled panel (FORMAT `GT`)
     };
     std::vector<std::string> sample_records(const std::vector<GenotypingResult>& genotyping_result, bool ignore_imputed, bool phasing,
                                             const std::vector<SampledPanel>* sampled_paths = nullptr, const DeviceFields* device = nullptr) const;
     /** CHROM .. INFO and `format` of every record: genotypes_fixed_columns and phasing_fixed_columns */
     std::vector<std::string> fixed_columns(const std::vector<unsigned short>& unique_kmers, const char* who, const char* format) const;
-    /** header lines (when asked for), then the lines' bytes in one write: the two multi-sample writers */
-    void write_lines(const std::string& filename, const RecordLines& lines, const std::vector<std::string>* header, bool phasing) const;
+    /** the slotted columns of genotypes_fixed_columns_slotted and sampled_panel_fixed_columns_slotted (`method`: the caller, as a refusal names it) */
+    std::vector<std::string> fixed_columns_slotted(std::vector<uint32_t>* slot, const char* who, const char* method, const char* format) const;
+    /** header lines (when asked for), then the lines' bytes in one write: the writers of whole lines */
+    enum class LinesOf { Genotypes, Phasing, SampledPanel };
+    void write_lines(const std::string& filename, const RecordLines& lines, const std::vector<std::string>* header, LinesOf of) const;
     /** CHROM .. INFO of one record (the ONE place that forms them): `defined` comes back as the record's defined alleles.
      *  With `uk_slot` the digits of `unique_kmers` are left out and *uk_slot = where they belong. */
     std::string fixed_columns_of(const VcfSite& site, size_t record_index, size_t unique_kmers, const char* who, std::vector<unsigned short>& defined,
@@ -368,6 +388,29 @@ std::vector<std::map<std::string, RecordLines>> genotype_cohort_sampled_record_l
     const std::vector<SampleCounts>& samples, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
     ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
     bool ignore_imputed = false, std::vector<std::map<std::string, SampledPaths>>* sampled = nullptr);
+
+/** The SAMPLED-PANEL VCF of a sampled cohort from the device (the `-d` output, all that PanGenie-sampling
+ *  writes): pg_sampler_cohort_new with sampled_paths = NULL, one strided plan per chromosome, pg_job_panel_text — no run —,
+ *  and ONE packed fetch of the bytes and their offsets (one more of the records' UK): no reduced panel and no pick comes
+ *  back.  Per sample and chromosome the haplotype columns of every record and, per bubble, the panel's own unique k-mer
+ *  count; Graph::sampled_panel_records(text) gives the lines of Graph::sampled_panel_records over the SampledPanels of
+ *  genotype_cohort_sampled(..., &sampled).  A chromosome with a record whose REF is of undefined sequence
+ *  (Graph::has_undefined_reference_allele: the plan calls REF defined, the host prints `.` for a haplotype on it) and a
+ *  panel of more than 64 paths go down the host route — pg_job_fetch_panel per chain, SampledPanels,
+ *  Graph::sampled_panel_records.  Throws as genotype_cohort_sampled_record_text does. */
+std::vector<std::map<std::string, RecordText>> sample_cohort_panel_text(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0);
+
+/** ... with the LINES joined on the device too: ONE slotted prefix per chromosome (Graph::sampled_panel_fixed_columns_slotted
+ *  through pg_job_panel_line_prefix_strided: the device prints every chain's own UK at the slot), pg_job_panel_lines and ONE
+ *  packed fetch, of the lines alone.  Per sample and chromosome the lines — the '\n'-joined Graph::sampled_panel_records —,
+ *  which Graph::write_sampled_panel(filename, lines, ...) writes. */
+std::vector<std::map<std::string, RecordLines>> sample_cohort_panel_lines(
+    std::map<std::string, std::vector<std::shared_ptr<UniqueKmers>>>& chromosomes, const std::map<std::string, Graph>& graphs,
+    const std::vector<SampleCounts>& samples, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0);
 
 /** The phasing job of a `-p` run to VCF text (reference src/commands.cpp:936-966, Graph::write_phasing): a
  *  phasing-only cohort job over `only_paths` (null: all paths; the Viterbi kernels take at most 64, the reference passes at

@@ -249,6 +249,19 @@ std::vector<std::map<std::string, RecordLines>> genotype_cohort_sampled_reads_re
     ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
     size_t batch = 64, bool ignore_imputed = false, std::vector<std::map<std::string, SampledPaths>>* sampled = nullptr);
 
+/** sample_cohort_panel_text / _lines (graph_io.hpp) from reads: the batches of genotype_cohort_sampled_reads,
+ *  per job the sampled-panel VCF's haplotype columns or whole lines from the device; no job is run. */
+std::vector<std::map<std::string, RecordText>> sample_cohort_reads_panel_text(
+    UniqueKmersMap& index, const std::map<std::string, Graph>& graphs, const std::string& prefix, const std::vector<std::string>& readfiles,
+    const std::vector<size_t>& kmer_coverages, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
+    size_t batch = 64);
+std::vector<std::map<std::string, RecordLines>> sample_cohort_reads_panel_lines(
+    UniqueKmersMap& index, const std::map<std::string, Graph>& graphs, const std::string& prefix, const std::vector<std::string>& readfiles,
+    const std::vector<size_t>& kmer_coverages, size_t panel_size, bool add_reference, unsigned short allele_penalty, long double sampling_effective_N,
+    ProbabilityTable* probabilities, double recombrate = 1.26, bool uniform = false, long double effective_N = 25000.0L, int device = 0,
+    size_t batch = 64);
+
 /** The reader of the counters' count() on its own: the sequences of a FASTA / FASTQ file (plain or gzipped) in batches of
  *  about `batch_bytes`, back to back with a newline after each, handed to `sink`; returns the bytes of all batches.  With a sink
  *  that drops its batch this is the ceiling of any design with one host reader (tools/bench_kmer_counter.py). */
